@@ -8,6 +8,7 @@ hyperpose_amd/ does.
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import os
 import subprocess
 
@@ -175,16 +176,19 @@ def nhwc_u8_to_nchw_f32(images: np.ndarray, factor: float = 1.0 / 255, flip_rb: 
 def ref_ppn_process(tensors, net_w=384, net_h=384, point_thresh=0.10, limb_thresh=0.05, nms_thresh=0.3,
                     cap=256, fast=False):
     L = ref_lib(fast)
-    if L is None:
-        raise RuntimeError("oracle/_ref not built")
     t = [np.ascontiguousarray(a, np.float32) for a in tensors]
+    key = _call_key("ppn", t, (net_w, net_h, point_thresh, limb_thresh, nms_thresh, cap, fast))
+    if L is None:
+        return _replay(key, 1)[0]
     k, gh, gw = t[0].shape
     e, nh, nw = t[6].shape[:3]
     out = (OHuman * cap)()
     n = L.ref_ppn_process(net_w, net_h, C.c_float(point_thresh), C.c_float(limb_thresh), C.c_float(nms_thresh),
                           *[_fp(a) for a in t], k, gh, gw, e, nh, nw, out, cap)
     assert 0 <= n <= cap
-    return np.frombuffer(out, dtype=HUMAN_DTYPE, count=n).copy()
+    h = np.frombuffer(out, dtype=HUMAN_DTYPE, count=n).copy()
+    _record(key, [h])
+    return h
 
 
 _PEAK_DTYPE = np.dtype([("part_id", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4"), ("id", "<i4")])
@@ -197,10 +201,13 @@ def ref_paf_process(conf, paf, conf_thresh=0.05, paf_thresh=0.05, res_w=-1, res_
     two OpenCV calls are restated).  Returns (humans, peaks, conns) like paf_process(); peaks / conns come from
     the reference's own functions called stage by stage (ref_paf_debug) and are None with debug=False."""
     L = ref_lib(fast)
-    if L is None or not hasattr(L, "ref_paf_process"):
-        raise RuntimeError("oracle/_ref not built (or older than the PAF entry points)")
     conf = np.ascontiguousarray(conf, np.float32)
     paf = np.ascontiguousarray(paf, np.float32)
+    key = _call_key("paf", (conf, paf), (conf_thresh, paf_thresh, res_w, res_h, cap_humans, cap_peaks, cap_conns, fast, debug))
+    if L is None:
+        return tuple(_replay(key, 3))
+    if not hasattr(L, "ref_paf_process"):
+        raise RuntimeError("oracle/_ref is older than the PAF entry points")
     j, rows, cols = conf.shape
     humans = (OHuman * cap_humans)()
     n = L.ref_paf_process(_fp(conf), j, rows, cols, _fp(paf), paf.shape[0], C.c_float(conf_thresh),
@@ -209,6 +216,7 @@ def ref_paf_process(conf, paf, conf_thresh=0.05, paf_thresh=0.05, res_w=-1, res_
         raise RuntimeError(f"ref_paf_process overflow/err: humans={n}")
     h = np.frombuffer(humans, dtype=HUMAN_DTYPE, count=n).copy()
     if not debug:
+        _record(key, [h])
         return h, None, None
     peaks = (OPeak * cap_peaks)()
     conns = (OConn * cap_conns)()
@@ -220,6 +228,7 @@ def ref_paf_process(conf, paf, conf_thresh=0.05, paf_thresh=0.05, res_w=-1, res_
         raise RuntimeError(f"ref_paf_debug: humans={n2} vs {n}, peaks={n_peaks.value} conns={n_conns.value}")
     p = np.frombuffer(peaks, dtype=_PEAK_DTYPE, count=n_peaks.value).copy()
     c = np.frombuffer(conns, dtype=_CONN_DTYPE, count=n_conns.value).copy()
+    _record(key, [h, p, c])
     return h, p, c
 
 
@@ -228,17 +237,66 @@ def have_ref_paf(fast: bool = False) -> bool:
     return L is not None and hasattr(L, "ref_paf_process")
 
 
+# ---------------------------------------------------------------- recorded reference results (tests/golden/ref_calls)
+# The reference's sources are not part of this repository, so oracle/_ref only exists where they are mounted.  There, every call of
+# ref_paf_process / ref_ppn_process / ref_pifpaf_process made with HP_REF_RECORD=<dir> also writes its result to
+# <dir>/<function>_<key>.npz, the key a hash of the call's input arrays and settings; the files are committed under
+# tests/golden/ref_calls.  Everywhere else these functions return the recorded result of the same call, and a call that was never
+# recorded raises: the tests compare against what the reference computed, never against nothing.
+RECORDED = os.path.join(os.path.dirname(HERE), "tests", "golden", "ref_calls")
+
+
+def _call_key(fn: str, arrays, params) -> str:
+    h = hashlib.sha256(fn.encode())
+    for a in arrays:
+        a = np.ascontiguousarray(a, np.float32)
+        h.update(f"{a.shape}".encode())
+        h.update(a.tobytes())
+    h.update(repr(tuple(params)).encode())
+    return f"{fn}_{h.hexdigest()[:24]}"
+
+
+def _record(key: str, outs) -> None:
+    d = os.environ.get("HP_REF_RECORD")
+    if d:
+        os.makedirs(d, exist_ok=True)
+        np.savez_compressed(os.path.join(d, key + ".npz"), **{f"out{i}": o for i, o in enumerate(outs) if o is not None})
+
+
+def _replay(key: str, n_out: int):
+    path = os.path.join(RECORDED, key + ".npz")
+    if not os.path.exists(path):
+        raise RuntimeError(f"oracle/_ref not built and no recorded result {os.path.relpath(path, os.path.dirname(HERE))} for this call "
+                           "(record it where the reference is mounted: HP_REF_RECORD=tests/golden/ref_calls)")
+    g = np.load(path)
+    outs = [g[f"out{i}"] if f"out{i}" in g else None for i in range(n_out)]
+    return outs
+
+
+def have_recorded_ref() -> bool:
+    """Recorded reference results are committed (tests/golden/ref_calls): the ref_* functions answer without oracle/_ref."""
+    return os.path.isdir(RECORDED) and any(f.endswith(".npz") for f in os.listdir(RECORDED))
+
+
+def have_ref() -> bool:
+    """The ref_* functions can answer here: oracle/_ref is built, or its recorded results are committed."""
+    return ref_lib() is not None or have_recorded_ref()
+
+
 def ref_pifpaf_process(paf, pif, net_h=385, net_w=385, thresh=0.1, cap=256, fast=False):
     L = ref_lib(fast)
-    if L is None:
-        raise RuntimeError("oracle/_ref not built")
     paf = np.ascontiguousarray(paf, np.float32)
     pif = np.ascontiguousarray(pif, np.float32)
+    key = _call_key("pifpaf", (paf, pif), (net_h, net_w, thresh, cap, fast))
+    if L is None:
+        return _replay(key, 1)[0]
     fh, fw = pif.shape[-2:]
     out = (OHuman * cap)()
     n = L.ref_pifpaf_process(net_h, net_w, C.c_float(thresh), _fp(paf), _fp(pif), fh, fw, out, cap)
     assert 0 <= n <= cap
-    return np.frombuffer(out, dtype=HUMAN_DTYPE, count=n).copy()
+    h = np.frombuffer(out, dtype=HUMAN_DTYPE, count=n).copy()
+    _record(key, [h])
+    return h
 
 
 # ---------------------------------------------------------------- stream front-end (cv::resize / non_scaling_resize)

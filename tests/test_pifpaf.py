@@ -25,7 +25,7 @@ def _cases():
 
 
 def test_golden_matches_reference_build_when_present():
-    if loader.ref_lib() is None:
+    if not loader.have_ref():
         pytest.skip("oracle/_ref not built here (no /root/reference)")
     n = 0
     for m, paf, pif, humans in _cases():
@@ -47,7 +47,7 @@ def test_gpu_matches_golden(hp):
 def test_gpu_batch_matches_reference_live(hp):
     """Batch of 16 at BASELINE config 4 geometry (385x385 -> 49x49 fields), host and device-resident inputs."""
     from hyperpose_amd.parser import PifPaf
-    if loader.ref_lib() is None:
+    if not loader.have_ref():
         pytest.skip("oracle/_ref not built")
     B = 16
     paf, pif = synth.pifpaf_maps(synth.rng_for(4, salt=9), B, people=(1, 2, 3, 4, 6, 8, 0, 5))
@@ -67,7 +67,7 @@ def test_gpu_batch_matches_reference_live(hp):
 @pytest.mark.gpu
 def test_gpu_threshold_variants(hp):
     from hyperpose_amd.parser import PifPaf
-    if loader.ref_lib() is None:
+    if not loader.have_ref():
         pytest.skip("oracle/_ref not built")
     paf, pif = synth.pifpaf_maps(synth.rng_for(4, salt=3), 2, people=(4, 7), noise=0.15)
     for thr in (0.05, 0.3, 0.6):
@@ -82,7 +82,7 @@ def test_gpu_async_enqueue_collect(hp):
     """hp_pifpaf_enqueue / hp_pifpaf_collect == the blocking call == the reference's own decoder, batch of 24 decoded on the host
     worker pool (frames in any order across the threads, results in frame order)."""
     from hyperpose_amd.parser import PifPaf
-    if loader.ref_lib() is None:
+    if not loader.have_ref():
         pytest.skip("oracle/_ref not built")
     B = 24
     p = PifPaf(385, 385, max_batch=B)

@@ -27,7 +27,7 @@ def _parser(host_tail, *a, **k):
 
 
 def test_device_decoder_matches_reference_and_host_tail(hp):
-    if loader.ref_lib() is None:
+    if not loader.have_ref():
         pytest.skip("oracle/_ref not built")
     B = 24
     dev, host = _parser(False, 385, 385, max_batch=B), _parser(True, 385, 385, max_batch=B)

@@ -27,7 +27,7 @@ def _cases():
 
 def test_golden_matches_reference_build_when_present():
     """CPU: in a container that mounts /root/reference, the committed fixtures are what the reference computes."""
-    if loader.ref_lib() is None:
+    if not loader.have_ref():
         pytest.skip("oracle/_ref not built here (no /root/reference)")
     n = 0
     for m, t, humans in _cases():
@@ -50,7 +50,7 @@ def test_gpu_matches_golden(hp):
 def test_gpu_batch_matches_reference_live(hp):
     """Batch of 32 (BASELINE config 3 geometry: 384x384, 12x12 grid), clutter included, device-resident inputs."""
     from hyperpose_amd.parser import PoseProposal
-    if loader.ref_lib() is None:
+    if not loader.have_ref():
         pytest.skip("oracle/_ref not built")
     B = 32
     t = synth.ppn_maps(synth.rng_for(3, salt=77), B, people=(1, 2, 3, 4, 6, 8, 0, 5), spurious=0.03)
@@ -76,7 +76,7 @@ def test_gpu_device_tail_crowds_ties_and_host_tail(hp, monkeypatch, seed):
     edge confidences quantised to a few values (mass ties: the order of equal candidates is libstdc++'s).  Against the reference's
     own code, frame by frame, with the decode flags asserted; and the host statements (HP_PPN_HOST_TAIL=1) give the same bytes."""
     from hyperpose_amd.parser import PoseProposal
-    if loader.ref_lib() is None:
+    if not loader.have_ref():
         pytest.skip("oracle/_ref not built")
     rng = np.random.default_rng(100 + seed)
     B = 16
@@ -110,7 +110,7 @@ def test_gpu_device_tail_crowds_ties_and_host_tail(hp, monkeypatch, seed):
 @pytest.mark.gpu
 def test_gpu_thresholds_and_other_resolution(hp):
     from hyperpose_amd.parser import PoseProposal
-    if loader.ref_lib() is None:
+    if not loader.have_ref():
         pytest.skip("oracle/_ref not built")
     t = synth.ppn_maps(synth.rng_for(3, salt=5), 4, people=(2, 4, 6, 3), spurious=0.05)
     p = PoseProposal((384, 384), 0.3, 0.1, 0.5, max_batch=4)
@@ -128,7 +128,7 @@ def test_gpu_async_enqueue_collect(hp):
     """hp_ppn_enqueue / hp_ppn_collect (lists written straight to pinned memory, tails on the worker pool) == the blocking call ==
     the reference; a second enqueue before collect is refused; repeated batches do not leak state between frames."""
     from hyperpose_amd.parser import PoseProposal
-    if loader.ref_lib() is None:
+    if not loader.have_ref():
         pytest.skip("oracle/_ref not built")
     B = 16
     p = PoseProposal((384, 384), max_batch=B)

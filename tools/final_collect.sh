@@ -14,7 +14,7 @@ echo "pytest: $(( $(date +%s) - t0 )) s" > $o/${tag}_times.txt
 bash tools/collect_all.sh $tag all > $o/collect_all.log 2>&1
 echo "profiles: $(( $(date +%s) - t0 )) s" >> $o/${tag}_times.txt
 cp $o/${tag}_kernel_stats*.csv $o/${tag}_pmc_*.json $o/noarena_${tag}_*.json $o/noarena_${tag}_*.csv profiles/ 2>/dev/null
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $o/${tag}_bench_final.json 2> $o/${tag}_bench_final.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $o/${tag}_bench_final.json 2> $o/${tag}_bench_final.err
 cp bench_detail.json $o/${tag}_bench_detail.json
 echo "bench: $(( $(date +%s) - t0 )) s" >> $o/${tag}_times.txt
 PYTHONPATH=. timeout 300 python tools/pifpaf_stress.py 4 64 > $o/${tag}_pifpaf_stress.txt 2>&1

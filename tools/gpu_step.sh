@@ -11,7 +11,7 @@ for v in base "nofuse HP_NO_FUSE32=1" "mw4 HP_DIRECT_MW_MAX=4"; do
   env $2 timeout 300 python tools/profile_layers.py lw_openpose_mobilenet 432 368 8 f32 > $out/${name}_layers_f32_$1.txt 2>&1
 done
 timeout 200 python tools/direct_timeline.py f32s 2> $out/${name}_timeline_f32s.txt >/dev/null
-timeout 600 python bench.py --steps 20 --warmup 5 --extra 1/f16,1/f32s > $out/${name}_bench.json 2> $out/${name}_bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --extra 1/f16,1/f32s > $out/${name}_bench.json 2> $out/${name}_bench.err
 cp bench_detail.json $out/${name}_bench_detail.json 2>/dev/null
 tail -n 8 $out/${name}_pytest_fp32.txt | cut -c1-300
 for f in $out/${name}_layers_*.txt; do echo $f; tail -n 3 $f; done

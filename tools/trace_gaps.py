@@ -15,7 +15,7 @@ pipes = sys.argv[1] if len(sys.argv) > 1 else "4"
 repo = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 out = "/tmp/prof_gap_" + pipes
 subprocess.run(f"rm -rf {out}; cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --output-format csv -d {out} -- python {repo}/bench.py "
-               f"--steps 40 --warmup 10 --pipes {pipes} --no-cpu-baseline --no-roofline --no-from-host > /dev/null 2>&1", shell=True)
+               f"--full --steps 40 --warmup 10 --pipes {pipes} --no-cpu-baseline --no-roofline --no-from-host > /dev/null 2>&1", shell=True)
 path = glob.glob(out + "/**/*kernel_trace.csv", recursive=True)[0]
 rows = list(csv.DictReader(open(path)))
 ev = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Queue_Id"], r["Kernel_Name"]) for r in rows]

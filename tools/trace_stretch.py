@@ -2,7 +2,7 @@ import csv, glob, os, subprocess, sys, collections
 repo = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
 def run(pipes):
     out = f"/tmp/prof_st_{pipes}"
-    subprocess.run(f"rm -rf {out}; cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --output-format csv -d {out} -- python {repo}/bench.py --steps 60 --warmup 10 --pipes {pipes} --no-cpu-baseline --no-roofline --no-from-host --no-dnn-output > /dev/null 2>&1", shell=True)
+    subprocess.run(f"rm -rf {out}; cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --output-format csv -d {out} -- python {repo}/bench.py --full --steps 60 --warmup 10 --pipes {pipes} --no-cpu-baseline --no-roofline --no-from-host --no-dnn-output > /dev/null 2>&1", shell=True)
     rows = list(csv.DictReader(open(glob.glob(out + "/**/*kernel_trace.csv", recursive=True)[0])))
     rows = rows[len(rows) // 3:]
     d = collections.defaultdict(list)
