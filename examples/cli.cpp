@@ -41,6 +41,7 @@ static double FLAGS_alpha = 0.5;
 static std::string FLAGS_saving_prefix = "output";
 static bool FLAGS_logging = false;
 static bool FLAGS_half = false; // addition: data_type::kHALF engines (the reference CLI always builds data_type::kFLOAT ones)
+static bool FLAGS_int8 = false; // addition: data_type::kINT8 engines, calibrated on the first batch of the source
 
 static std::ostream& cli_log() { return std::cout << "[HyperPose::CLI] "; }
 
@@ -49,7 +50,7 @@ static bool parse_flags(int argc, char** argv)
     std::map<std::string, std::string*> sflags = { { "model", &FLAGS_model }, { "post", &FLAGS_post }, { "source", &FLAGS_source },
         { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix } };
     std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size } };
-    std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half } };
+    std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 } };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a.rfind("--", 0) != 0 && a.rfind("-", 0) == 0)
@@ -216,7 +217,7 @@ static hp::dnn::tensorrt build_engine()
     const cv::Size net_size(FLAGS_w, FLAGS_h);
     cli_log() << "engine: model '" << FLAGS_model << "', network input " << FLAGS_w << " x " << FLAGS_h << " (w x h), batches of up to "
               << FLAGS_max_batch_size << (FLAGS_keep_ratio ? ", aspect ratio kept (letter-box)\n" : ", frames stretched to the network size\n");
-    const hp::data_type dtype = FLAGS_half ? hp::data_type::kHALF : hp::data_type::kFLOAT;
+    const hp::data_type dtype = FLAGS_int8 ? hp::data_type::kINT8 : FLAGS_half ? hp::data_type::kHALF : hp::data_type::kFLOAT;
     if (FLAGS_model.rfind("builtin:", 0) == 0)
         return hp::dnn::tensorrt(hp::dnn::builtin_model{ FLAGS_model.substr(8), {}, 20241 }, net_size, FLAGS_max_batch_size, FLAGS_keep_ratio, dtype);
     if (has_suffix(FLAGS_model, ".onnx"))
@@ -271,6 +272,11 @@ int main(int argc, char** argv)
     }
 
     auto engine = build_engine();
+    if (FLAGS_int8 && !engine.calibrated()) { // calibration is never implicit in the engine: the CLI asks for it and says so
+        const size_t n = std::min(images.size(), (size_t)FLAGS_max_batch_size);
+        engine.calibrate(std::vector<cv::Mat>(images.begin(), images.begin() + n));
+        std::cerr << "--int8: calibrated the kINT8 engine on the first " << n << " frame(s) of the source (MinMax)" << std::endl;
+    }
     any_parser parser = build_parser(engine);
     if (FLAGS_runtime != kOPERATOR && FLAGS_runtime != kSTREAM) {
         cli_log() << "WARNING: --runtime=" << FLAGS_runtime << " is neither " kOPERATOR " nor " kSTREAM "; using " kOPERATOR "\n";

@@ -11,6 +11,7 @@
 //   * heads write fp32 NCHW straight from the conv epilogue into the buffers the parser kernels read —
 //     feature maps never cross PCIe.
 #include "conv_fp32.hpp"
+#include "conv_i8.hpp"
 #include "conv_kernels.hpp"
 #include "hp_common.hpp"
 
@@ -98,6 +99,11 @@ struct step {
     hp::head32_hidden hh{};
     int cin_split = 0;     // fp32 engines: input channels as conv32_direct_kernel reads them (whole chunks), 0 = the layer stays on conv32_kernel
     int n_layers = 1;      // consecutive layers this step covers
+    // HP_DTYPE_I8 engines: a layer conv_i8_kernel covers keeps its fp16 launch (cp) and gets the int8 one beside it; which of the two runs
+    // is the layer's entry of hp_engine::i8_scale (> 0: int8 with that activation scale, 0: fp16)
+    bool i8 = false;
+    hp::conv_i8_params q8{}; // q8.c is refreshed from cp at every launch; q8.dq points at i8_dq
+    float* i8_dq = nullptr;  // device [cp.Cout_pad]: s_a * s_w[c], rewritten by hp_engine::apply_int8_scales
     double flops = 0, bytes = 0; // per frame
 };
 constexpr int OP_SEPCONV = 100; // schedule-only op codes (not part of the hp_layer ABI)
@@ -120,6 +126,16 @@ struct hp_engine {
     int dtype = HP_DTYPE_F16; // HP_DTYPE_F32: fp32 storage and arithmetic (the reference's data_type::kFLOAT), conv_fp32.hip;
                               // HP_DTYPE_F32S: the same engine with the dense layers' products on the fp16 pipe (conv32_direct.hip)
     bool is_f32() const { return dtype == HP_DTYPE_F32 || dtype == HP_DTYPE_F32S; }
+    // HP_DTYPE_I8 (post-training quantization, TensorRT's kINT8): the fp16 engine's per-layer schedule (no fusions) with the layers conv_i8_kernel
+    // covers on the int8 matrix pipe.  One float per layer: > 0 the layer runs int8 with this activation scale s_a, 0 it runs its fp16 kernel
+    // (ineligible, or kept in fp16 by the caller), -1 eligible but not calibrated yet (such an engine does not infer).
+    std::vector<float> i8_scale;
+    std::vector<std::vector<float>> i8_sw; // per layer: the per-output-channel weight scales s_w[c] (empty for ineligible layers)
+    bool i8_on(const step& st) const { return st.i8 && i8_scale[st.layer] > 0.f; }
+    bool i8_eligible(int layer) const { return !i8_sw[layer].empty(); }
+    int check_int8_scales(const float* s, int n, bool allow_uncalibrated) const;
+    int apply_int8_scales(); // dq / inv_a of every int8 step from i8_scale; the caller has synchronised and dropped the graphs
+    int drop_graphs();       // synchronise, then forget every captured graph (they hold the launches and arguments of the old schedule)
     // which engines may run a batch as two half-batches (hp_engine_set_concurrency): the fp32 engines (their steps take a frame offset)
     bool halves_ok() const { return is_f32(); }
     // HP_DTYPE_F32S: a pinned host word the split kernels OR into when an activation exceeds fp16's range (|x| > 65504); once seen
@@ -201,10 +217,13 @@ int hp_engine::build(const hp_engine_desc* d)
     HP_REQUIRE(d->in_w > 0 && d->in_h > 0 && d->max_batch >= 1, HP_ERR_INVALID, "engine: bad input size / batch");
     HP_REQUIRE(d->layers && d->n_layers > 0 && d->weights, HP_ERR_INVALID, "engine: no layers / weights");
     in_w = d->in_w, in_h = d->in_h, max_batch = d->max_batch, factor = d->factor, flip_rb = d->flip_rb;
-    HP_REQUIRE(d->dtype == HP_DTYPE_F16 || d->dtype == HP_DTYPE_F32 || d->dtype == HP_DTYPE_F32S, HP_ERR_INVALID,
-        "engine: dtype %d is none of HP_DTYPE_F16 / HP_DTYPE_F32 / HP_DTYPE_F32S", d->dtype);
+    HP_REQUIRE(d->dtype == HP_DTYPE_F16 || d->dtype == HP_DTYPE_F32 || d->dtype == HP_DTYPE_F32S || d->dtype == HP_DTYPE_I8, HP_ERR_INVALID,
+        "engine: dtype %d is none of HP_DTYPE_F16 / HP_DTYPE_F32 / HP_DTYPE_F32S / HP_DTYPE_I8", d->dtype);
     dtype = d->dtype;
     const bool f32 = is_f32();
+    // HP_NO_FUSE=1: one launch per layer.  An HP_DTYPE_I8 engine always runs that schedule: its fp16 layers are the kernels of the fp16 engine's
+    // per-layer plan, its int8 layers replace single launches of it
+    const bool no_fuse = dtype == HP_DTYPE_I8 || getenv("HP_NO_FUSE") != nullptr;
     unsigned* ovf_dev = nullptr;
     if (dtype == HP_DTYPE_F32S) {
         HP_TRY(ovf_flag.alloc(64));
@@ -301,7 +320,7 @@ int hp_engine::build(const hp_engine_desc* d)
     // ---- separable blocks: a depthwise layer whose only consumer is the next layer, a plain 1x1 convolution, runs
     // as ONE launch (sepconv_kernel) and its output tensor is never materialised.  HP_NO_FUSE=1 keeps the two launches.
     std::vector<char> fuse_with_next(layers.size(), 0);
-    if (!getenv("HP_NO_FUSE") && !f32) {
+    if (!no_fuse && !f32) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
             if (A.op != HP_OP_DWCONV || A.kh != 3 || A.kw != 3 || A.in == 0 || A.out_coff != 0 || A.in_coff % 8)
@@ -350,7 +369,7 @@ int hp_engine::build(const hp_engine_desc* d)
     // a second stream against 125 / 107 for the two launches (profiles/r05_ab_layers_f32_sep_kernel.txt): one block of eight wavefronts per CU
     // moves in step with its own barrier, where conv32_kernel's four independent blocks per CU fill each other's gaps.  Not adopted, removed.
     std::vector<char> fuse32_with_next(layers.size(), 0);
-    if (f32 && !getenv("HP_NO_FUSE") && !getenv("HP_NO_FUSE32") && (dtype == HP_DTYPE_F32S || getenv("HP_FUSE32"))) {
+    if (f32 && !no_fuse && !getenv("HP_NO_FUSE32") && (dtype == HP_DTYPE_F32S || getenv("HP_FUSE32"))) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
             if (A.op != HP_OP_DWCONV || A.kh != 3 || A.kw != 3 || A.in == 0 || A.out_coff != 0 || A.in_coff % 4 || A.stride != 1 || (A.dil != 1 && A.dil != 2)
@@ -386,7 +405,7 @@ int hp_engine::build(const hp_engine_desc* d)
     }
     // ---- two-layer heads: 1x1 K1 -> 512 (relu) whose only consumer is the next layer, a 1x1 512 -> <= 64 channels
     std::vector<char> head_with_next(layers.size(), 0);
-    if (!getenv("HP_NO_FUSE") && !f32) {
+    if (!no_fuse && !f32) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
             if (A.op != HP_OP_CONV || A.kh != 1 || A.kw != 1 || A.stride != 1 || A.in == 0 || A.res >= 0 || A.out_coff != 0 || A.in_coff % 8
@@ -418,7 +437,7 @@ int hp_engine::build(const hp_engine_desc* d)
     // ---- HP_DTYPE_F32: the same two-layer heads for conv32_head_kernel (1 x 1 128 -> HID, ReLU family, sole consumer a 1 x 1 HID -> <= 64
     // channels; the hidden tensor stays in registers).  HP_NO_FUSE=1 / HP_NO_HEAD32=1 keep two launches.
     std::vector<char> head32_with_next(layers.size(), 0);
-    if (dtype == HP_DTYPE_F32 && !getenv("HP_NO_FUSE") && !getenv("HP_NO_HEAD32")) {
+    if (dtype == HP_DTYPE_F32 && !no_fuse && !getenv("HP_NO_HEAD32")) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
             if (A.op != HP_OP_CONV || A.kh != 1 || A.kw != 1 || A.stride != 1 || A.in == 0 || A.res >= 0 || A.out_coff != 0 || A.in_coff % 4
@@ -586,6 +605,7 @@ int hp_engine::build(const hp_engine_desc* d)
         return HP_OK;
     };
 
+    i8_sw.assign(layers.size(), {});
     for (size_t i = 0; i < layers.size(); ++i) {
         const hp_layer& L = layers[i];
         const tensor_info& ti = *tensors[L.in];
@@ -1029,6 +1049,40 @@ int hp_engine::build(const hp_engine_desc* d)
             p.w = (const __half*)dw;
             st.flops = 2.0 * opix * L.cout * taps * L.cin;
             st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cout * 2 + (double)nw * 2;
+            if (dtype == HP_DTYPE_I8 && hp::conv_i8_ok(L.kh, L.kw, L.stride, L.dil)) {
+                // int8 weights, symmetric per output channel: s_w[c] = max |w| / 127 (1 for an all-zero channel), q_w = clamp(rint(w / s_w[c]), -127, 127)
+                // in fp32, round-half-even; rows [tap][Cout_pad][Cin_pad] as conv_i8_kernel reads them
+                std::vector<float> sw(L.cout);
+                std::vector<int8_t> wq((size_t)taps * cout_pad * cin_pad, 0);
+                for (int co = 0; co < L.cout; ++co) {
+                    const float* wc = w + (size_t)co * taps * L.cin;
+                    float m = 0.f;
+                    for (size_t k = 0; k < (size_t)taps * L.cin; ++k)
+                        m = std::max(m, std::fabs(wc[k]));
+                    const float sc = m > 0.f ? m / 127.f : 1.f;
+                    sw[co] = sc;
+                    for (int t = 0; t < taps; ++t)
+                        for (int ci = 0; ci < L.cin; ++ci)
+                            wq[((size_t)t * cout_pad + co) * cin_pad + ci] = (int8_t)std::min(std::max(std::rint(wc[(size_t)t * L.cin + ci] / sc), -127.f), 127.f);
+                }
+                void *dq = nullptr, *dd = nullptr;
+                HP_TRY(upload(wq.data(), wq.size(), &dq));
+                const std::vector<float> zeros(cout_pad, 0.f);
+                HP_TRY(upload(zeros.data(), zeros.size() * sizeof(float), &dd));
+                st.i8 = true, st.q8.w = (const int8_t*)dq, st.q8.dq = (const float*)dd, st.i8_dq = (float*)dd, st.q8.inv_a = 0.f;
+                st.q8.w_direct = nullptr;
+                if (hp::conv_i8_direct_ok(p)) { // the same q_w in conv_i8_direct_kernel's fragment order
+                    std::vector<int8_t> wd(wq.size(), 0);
+                    for (int t = 0; t < taps; ++t)
+                        for (int co = 0; co < cout_pad; ++co)
+                            for (int ci = 0; ci < cin_pad; ++ci)
+                                wd[hp::conv_i8_direct_index(t, co, ci, cin_pad, cout_pad)] = wq[((size_t)t * cout_pad + co) * cin_pad + ci];
+                    void* dd2 = nullptr;
+                    HP_TRY(upload(wd.data(), wd.size(), &dd2));
+                    st.q8.w_direct = (const int8_t*)dd2;
+                }
+                i8_sw[i] = std::move(sw);
+            }
         } else if (L.op == HP_OP_DWCONV && fuse_with_next[i]) {
             const hp_layer& Pn = layers[i + 1];
             tensor_info& tp = *tensors[Pn.out];
@@ -1177,7 +1231,7 @@ int hp_engine::build(const hp_engine_desc* d)
     // ---- chains of 128-channel convolutions (LW-OpenPose's CPM / initial / refinement stages, lw_openpose.py:106-191): consecutive
     // steps [1x1 ->] 3x3 -> 3x3 whose intermediates nobody else reads run as ONE launch with the intermediates in LDS
     // (conv_chain.hip).  HP_NO_CHAIN=1 keeps one launch per layer (A/B measurements, and hp_engine_debug_tensor on an intermediate).
-    if (!getenv("HP_NO_CHAIN") && !getenv("HP_NO_FUSE") && !f32) {
+    if (!getenv("HP_NO_CHAIN") && !no_fuse && !f32) {
         auto plain_conv = [&](const step& st) { return st.op == HP_OP_CONV && !st.first && st.n_layers == 1; };
         // the tensor a step writes is read only by the given layers (as input or residual) and is no network output
         auto only_read_by = [&](int tensor, int la, int lb) {
@@ -1233,7 +1287,7 @@ int hp_engine::build(const hp_engine_desc* d)
     // ---- ResNet bottlenecks (configs[3] / [4]): [3x3 ->] expansion 1x1 (+ shortcut) [-> the NEXT block's reduction 1x1] as one launch
     // (conv_bottleneck.hip).  The reduction may sit one or two steps further down the schedule (behind the next stage's projection
     // shortcut, which reads the same tensor): it has no other input, so it can run here.  HP_NO_BNECK=1 keeps one launch per layer.
-    if (!getenv("HP_NO_BNECK") && !getenv("HP_NO_FUSE") && !f32) {
+    if (!getenv("HP_NO_BNECK") && !no_fuse && !f32) {
         auto plain_conv = [&](const step& st) { return st.op == HP_OP_CONV && !st.first && st.n_layers == 1; };
         auto readers_other_than = [&](int tensor, int la) { // some layer other than la reads the tensor, or it is a network output
             for (size_t j = 0; j < layers.size(); ++j)
@@ -1408,7 +1462,7 @@ int hp_engine::build(const hp_engine_desc* d)
     }
     // ---- the MobileNet stem's separable blocks 32 -> 64 and 64 -> 128 (stride 2) as ONE launch, the 64-channel tensor between them (the
     // largest of the network) in LDS only (sepconv_pair_kernel).  HP_NO_SEPPAIR=1 keeps one launch per block.
-    if (!getenv("HP_NO_SEPPAIR") && !getenv("HP_NO_FUSE") && !f32) {
+    if (!getenv("HP_NO_SEPPAIR") && !no_fuse && !f32) {
         for (size_t k = 0; k + 1 < steps.size(); ++k) {
             step &a = steps[k], &b = steps[k + 1];
             if (a.op != OP_SEPCONV || b.op != OP_SEPCONV || a.sep_pair || b.sep_pair)
@@ -1456,6 +1510,63 @@ int hp_engine::build(const hp_engine_desc* d)
     HP_HIP_TRY(hipEventCreate(&ev1));
     HP_HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
     HP_HIP_TRY(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
+    if (dtype == HP_DTYPE_I8) {
+        i8_scale.assign(layers.size(), 0.f);
+        for (size_t i = 0; i < layers.size(); ++i)
+            if (i8_eligible((int)i))
+                i8_scale[i] = -1.f;
+        if (d->int8_scales) { // a calibration cache (hp_engine_describe of another engine, hp_engine_load)
+            HP_TRY(check_int8_scales(d->int8_scales, d->n_layers, true));
+            i8_scale.assign(d->int8_scales, d->int8_scales + d->n_layers);
+            for (auto& v : i8_scale)
+                v = v < 0.f ? -1.f : v;
+        }
+        HP_TRY(apply_int8_scales());
+    }
+    return HP_OK;
+}
+
+int hp_engine::check_int8_scales(const float* s, int n, bool allow_uncalibrated) const
+{
+    HP_REQUIRE(s, HP_ERR_INVALID, "int8 scales: null vector");
+    HP_REQUIRE(n == (int)layers.size(), HP_ERR_INVALID, "int8 scales: %d values for %zu layers", n, layers.size());
+    for (int i = 0; i < n; ++i) {
+        HP_REQUIRE(std::isfinite(s[i]), HP_ERR_INVALID, "int8 scales: layer %d: %g is not finite", i, (double)s[i]);
+        const bool uncal = allow_uncalibrated && s[i] == -1.f && i8_eligible(i);
+        HP_REQUIRE(s[i] >= 0.f || uncal, HP_ERR_INVALID, "int8 scales: layer %d: negative scale %g", i, (double)s[i]);
+        HP_REQUIRE(s[i] <= 0.f || i8_eligible(i), HP_ERR_INVALID,
+            "int8 scales: layer %d has no int8 kernel (first layer, depthwise, pooling or an uncovered geometry): its scale must be 0", i);
+    }
+    return HP_OK;
+}
+
+int hp_engine::apply_int8_scales()
+{
+    for (auto& st : steps) {
+        if (!st.i8)
+            continue;
+        const float sa = i8_scale[st.layer];
+        const std::vector<float>& sw = i8_sw[st.layer];
+        std::vector<float> dq(st.cp.Cout_pad, 0.f);
+        if (sa > 0.f)
+            for (size_t c = 0; c < sw.size(); ++c)
+                dq[c] = sa * sw[c]; // dq[c] = s_a * s_w[c], one fp32 product
+        st.q8.inv_a = sa > 0.f ? 1.0f / sa : 0.f;
+        HP_HIP_TRY(hipMemcpy(st.i8_dq, dq.data(), dq.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return HP_OK;
+}
+
+int hp_engine::drop_graphs()
+{
+    HP_HIP_TRY(hipStreamSynchronize(stream));
+    if (last.stream)
+        HP_HIP_TRY(hipStreamSynchronize((hipStream_t)last.stream));
+    if (stream2)
+        HP_HIP_TRY(hipStreamSynchronize(stream2));
+    for (auto& g : graphs)
+        (void)hipGraphExecDestroy(g.second);
+    graphs.clear();
     return HP_OK;
 }
 
@@ -1666,6 +1777,10 @@ int hp_engine::run_step(step& st, const uint8_t* u8, const float* f32, int n, hi
     if (st.first) {
         st.fp.in_u8 = u8, st.fp.in_f32 = f32, st.fp.B = n;
         HP_HIP_TRY(hp::launch_first_conv(st.fp, s));
+    } else if (st.op == HP_OP_CONV && i8_on(st)) {
+        st.cp.B = n, st.cp.npix = n * st.cp.OH * st.cp.OW;
+        st.q8.c = st.cp;
+        HP_HIP_TRY(hp::launch_conv_i8(st.q8, s));
     } else if (st.op == HP_OP_CONV) {
         st.cp.B = n, st.cp.npix = n * st.cp.OH * st.cp.OW;
         HP_HIP_TRY(hp::launch_conv_mfma(st.cp, s));
@@ -1886,7 +2001,7 @@ int hp_engine_create(hp_engine** out, const hp_engine_desc* desc)
 // was given - topology, outputs, pre-processing, fp32 weights - so loading rebuilds the identical engine without the model
 // source; the packing into kernel layouts happens at load (tens of ms), there is no per-device tuning cache to carry.
 namespace {
-constexpr char ENGINE_MAGIC[8] = { 'H', 'P', 'E', 'N', 'G', '0', '0', '2' }; // 002: + dtype
+constexpr char ENGINE_MAGIC[8] = { 'H', 'P', 'E', 'N', 'G', '0', '0', '3' }; // 002: + dtype; 003: + the int8 scale vector
 struct engine_file_header {
     char magic[8];
     int32_t layer_size, output_size; // sizeof(hp_layer) / sizeof(hp_output_desc): ABI guard
@@ -1895,7 +2010,8 @@ struct engine_file_header {
     float mean[3], inv_std[3];
     int32_t n_layers, n_outputs;
     uint64_t n_weights;
-    int32_t dtype, reserved; // HP_DTYPE_*: TensorRT bakes the builder's precision into the plan it serializes, so does this file
+    int32_t dtype;    // HP_DTYPE_*: TensorRT bakes the builder's precision into the plan it serializes, so does this file
+    int32_t n_scales; // 003: n_layers (HP_DTYPE_I8: the per-layer int8 scales follow the weights, -1 = not calibrated) or 0 (002: reserved, 0)
 };
 } // namespace
 
@@ -1912,10 +2028,12 @@ int hp_engine_save(const hp_engine* e, const char* path)
         h.mean[c] = e->mean[c], h.inv_std[c] = e->inv_std[c];
     h.n_layers = (int32_t)e->layers.size(), h.n_outputs = (int32_t)e->out_descs.size(), h.n_weights = e->weights_blob.size();
     h.dtype = e->dtype;
+    h.n_scales = (int32_t)e->i8_scale.size();
     bool ok = fwrite(&h, sizeof(h), 1, f) == 1;
     ok = ok && fwrite(e->layers.data(), sizeof(hp_layer), e->layers.size(), f) == e->layers.size();
     ok = ok && fwrite(e->out_descs.data(), sizeof(hp_output_desc), e->out_descs.size(), f) == e->out_descs.size();
     ok = ok && fwrite(e->weights_blob.data(), sizeof(float), e->weights_blob.size(), f) == e->weights_blob.size();
+    ok = ok && fwrite(e->i8_scale.data(), sizeof(float), e->i8_scale.size(), f) == e->i8_scale.size();
     ok = (fclose(f) == 0) && ok;
     HP_REQUIRE(ok, HP_ERR_INVALID, "hp_engine_save: short write to %s", path);
     return HP_OK;
@@ -1929,28 +2047,36 @@ int hp_engine_load(hp_engine** out, const char* path, int max_batch)
     engine_file_header h{};
     std::vector<hp_layer> layers;
     std::vector<hp_output_desc> outs;
-    std::vector<float> w;
-    // an HPENG001 file (before data_type was honoured) is an 002 file without the trailing (dtype, reserved) pair, and its engine was fp16
+    std::vector<float> w, scales;
+    // an HPENG001 file (before data_type was honoured) is an 002 file without the trailing (dtype, reserved) pair, and its engine was fp16;
+    // an 002 file is an 003 file without scales (its `reserved` word was written as 0)
     constexpr size_t HDR_001 = offsetof(engine_file_header, dtype);
     bool ok = fread(&h, HDR_001, 1, f) == 1;
     if (ok && memcmp(h.magic, "HPENG001", 8) == 0)
-        memcpy(h.magic, ENGINE_MAGIC, 8), h.dtype = HP_DTYPE_F16, h.reserved = 0;
-    else
+        memcpy(h.magic, ENGINE_MAGIC, 8), h.dtype = HP_DTYPE_F16, h.n_scales = 0;
+    else {
         ok = ok && fread(reinterpret_cast<char*>(&h) + HDR_001, sizeof(h) - HDR_001, 1, f) == 1;
+        if (ok && memcmp(h.magic, "HPENG002", 8) == 0)
+            memcpy(h.magic, ENGINE_MAGIC, 8), ok = h.n_scales == 0 && h.dtype != HP_DTYPE_I8;
+    }
     ok = ok && memcmp(h.magic, ENGINE_MAGIC, 8) == 0 && h.layer_size == (int32_t)sizeof(hp_layer)
         && h.output_size == (int32_t)sizeof(hp_output_desc) && h.n_layers > 0 && h.n_layers < (1 << 20) && h.n_outputs > 0
-        && h.n_outputs < 4096 && h.n_weights < ((uint64_t)1 << 34) && (h.dtype == HP_DTYPE_F16 || h.dtype == HP_DTYPE_F32 || h.dtype == HP_DTYPE_F32S);
+        && h.n_outputs < 4096 && h.n_weights < ((uint64_t)1 << 34)
+        && (h.dtype == HP_DTYPE_F16 || h.dtype == HP_DTYPE_F32 || h.dtype == HP_DTYPE_F32S || h.dtype == HP_DTYPE_I8)
+        && h.n_scales == (h.dtype == HP_DTYPE_I8 ? h.n_layers : 0);
     if (ok) { // the counts must account for the file exactly before anything is allocated from them
         const long at = ftell(f);
         ok = fseek(f, 0, SEEK_END) == 0;
         const long size = ftell(f);
         ok = ok && fseek(f, at, SEEK_SET) == 0
-            && (uint64_t)size == (uint64_t)at + (uint64_t)h.n_layers * sizeof(hp_layer) + (uint64_t)h.n_outputs * sizeof(hp_output_desc) + h.n_weights * sizeof(float);
+            && (uint64_t)size == (uint64_t)at + (uint64_t)h.n_layers * sizeof(hp_layer) + (uint64_t)h.n_outputs * sizeof(hp_output_desc) + h.n_weights * sizeof(float)
+                    + (uint64_t)h.n_scales * sizeof(float);
     }
     if (ok) {
-        layers.resize(h.n_layers), outs.resize(h.n_outputs), w.resize(h.n_weights);
+        layers.resize(h.n_layers), outs.resize(h.n_outputs), w.resize(h.n_weights), scales.resize(h.n_scales);
         ok = fread(layers.data(), sizeof(hp_layer), layers.size(), f) == layers.size()
-            && fread(outs.data(), sizeof(hp_output_desc), outs.size(), f) == outs.size() && fread(w.data(), sizeof(float), w.size(), f) == w.size();
+            && fread(outs.data(), sizeof(hp_output_desc), outs.size(), f) == outs.size() && fread(w.data(), sizeof(float), w.size(), f) == w.size()
+            && fread(scales.data(), sizeof(float), scales.size(), f) == scales.size();
     }
     fclose(f);
     HP_REQUIRE(ok, HP_ERR_INVALID, "hp_engine_load: %s is not an engine file written by this library version", path);
@@ -1960,6 +2086,7 @@ int hp_engine_load(hp_engine** out, const char* path, int max_batch)
         d.mean[c] = h.mean[c], d.inv_std[c] = h.inv_std[c];
     d.layers = layers.data(), d.n_layers = h.n_layers, d.outputs = outs.data(), d.n_outputs = h.n_outputs, d.weights = w.data(), d.n_weights = w.size();
     d.dtype = h.dtype;
+    d.int8_scales = scales.empty() ? nullptr : scales.data();
     return hp_engine_create(out, &d);
 }
 
@@ -1984,6 +2111,7 @@ int hp_engine_describe(const hp_engine* e, hp_engine_desc* d)
     d->outputs = e->out_descs.data(), d->n_outputs = (int32_t)e->out_descs.size();
     d->weights = e->weights_blob.data(), d->n_weights = e->weights_blob.size();
     d->dtype = e->dtype;
+    d->int8_scales = e->dtype == HP_DTYPE_I8 ? e->i8_scale.data() : nullptr;
     return HP_OK;
 }
 
@@ -1998,12 +2126,7 @@ int hp_engine_input_size(const hp_engine* e, int* w, int* h)
 
 int hp_engine::leave_split()
 {
-    HP_HIP_TRY(hipStreamSynchronize(stream));
-    if (last.stream)
-        HP_HIP_TRY(hipStreamSynchronize((hipStream_t)last.stream));
-    for (auto& g : graphs)
-        (void)hipGraphExecDestroy(g.second);
-    graphs.clear();
+    HP_TRY(drop_graphs());
     split_off = true, ++split_fallbacks;
     *static_cast<volatile unsigned*>(ovf_flag.p) = 0;
     return HP_OK;
@@ -2016,6 +2139,10 @@ static int infer_common(hp_engine* e, const void* input, size_t frame_bytes, int
         HP_TRY(e->leave_split());
     e->last.input = input, e->last.frame_bytes = frame_bytes, e->last.n = n, e->last.on_device = on_device, e->last.kind = kind, e->last.stream = stream;
     HP_REQUIRE(n >= 1, HP_ERR_INVALID, "hp_engine_infer: empty batch");
+    // TensorRT builds no kINT8 engine without a calibrator or per-tensor dynamic ranges; here the engine exists and refuses to run
+    for (float v : e->i8_scale)
+        HP_REQUIRE(v >= 0.f, HP_ERR_STATE,
+            "hp_engine_infer: the HP_DTYPE_I8 engine is not calibrated: call hp_engine_calibrate_u8 (calibrate()) or hp_engine_set_int8_scales first");
     // src/tensorrt.cpp:439-443 throws std::logic_error here
     HP_REQUIRE(n <= e->max_batch, HP_ERR_CAPACITY, "Input batch size overflow: Yours@%d Max@%d", n, e->max_batch);
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
@@ -2124,6 +2251,86 @@ int hp_engine_synchronize(hp_engine* e)
 
 int hp_engine_split_fallbacks(const hp_engine* e) { return e ? e->split_fallbacks : HP_ERR_INVALID; }
 
+int hp_engine_int8_scales(const hp_engine* e, float* scales, int n)
+{
+    HP_REQUIRE(e && scales, HP_ERR_INVALID, "hp_engine_int8_scales: null argument");
+    HP_REQUIRE(e->dtype == HP_DTYPE_I8, HP_ERR_STATE, "hp_engine_int8_scales: not an HP_DTYPE_I8 engine");
+    HP_REQUIRE(n == (int)e->i8_scale.size(), HP_ERR_INVALID, "hp_engine_int8_scales: room for %d values, the engine has %zu layers", n, e->i8_scale.size());
+    std::copy(e->i8_scale.begin(), e->i8_scale.end(), scales);
+    return HP_OK;
+}
+
+int hp_engine_set_int8_scales(hp_engine* e, const float* scales, int n)
+{
+    HP_REQUIRE(e && scales, HP_ERR_INVALID, "hp_engine_set_int8_scales: null argument");
+    HP_REQUIRE(e->dtype == HP_DTYPE_I8, HP_ERR_STATE, "hp_engine_set_int8_scales: not an HP_DTYPE_I8 engine");
+    HP_TRY(e->check_int8_scales(scales, n, false));
+    HP_TRY(e->drop_graphs()); // a captured graph holds the old kernels and arguments
+    e->i8_scale.assign(scales, scales + n);
+    return e->apply_int8_scales();
+}
+
+int hp_engine_calibrate_u8(hp_engine* e, const uint8_t* hwc_bgr, int n, int on_device)
+{
+    HP_REQUIRE(e && hwc_bgr, HP_ERR_INVALID, "hp_engine_calibrate_u8: null argument");
+    HP_REQUIRE(e->dtype == HP_DTYPE_I8, HP_ERR_STATE, "hp_engine_calibrate_u8: not an HP_DTYPE_I8 engine");
+    HP_REQUIRE(n >= 1, HP_ERR_INVALID, "hp_engine_calibrate_u8: no frames");
+    HP_TRY(e->drop_graphs());
+    const int NL = (int)e->layers.size();
+    // every layer in fp16 (scale 0) while the frames run: x is what the fp16 per-layer schedule computes.  A failure leaves the old scales.
+    std::vector<float> scales(NL, 0.f);
+    struct restore {
+        hp_engine* e;
+        std::vector<float> old;
+        ~restore()
+        {
+            if (e)
+                e->i8_scale = old;
+        }
+    } guard{ e, e->i8_scale };
+    e->i8_scale.assign(NL, 0.f);
+    hp::dev_buf amax;
+    HP_TRY(amax.alloc((size_t)NL * sizeof(unsigned)));
+    HP_HIP_TRY(hipMemsetAsync(amax.p, 0, (size_t)NL * sizeof(unsigned), e->stream));
+    const size_t frame_bytes = (size_t)e->in_h * e->in_w * 3;
+    if (!on_device) {
+        const size_t need = (size_t)e->max_batch * frame_bytes * sizeof(float); // (the size infer_common keeps)
+        if (e->in_stage.bytes < need)
+            HP_TRY(e->in_stage.alloc(need));
+    }
+    for (int b0 = 0; b0 < n; b0 += e->max_batch) {
+        const int cnt = std::min(e->max_batch, n - b0);
+        const uint8_t* src = hwc_bgr + (size_t)b0 * frame_bytes;
+        if (!on_device) {
+            HP_HIP_TRY(hipMemcpyAsync(e->in_stage.p, src, (size_t)cnt * frame_bytes, hipMemcpyHostToDevice, e->stream));
+            src = e->in_stage.as<uint8_t>();
+        }
+        HP_TRY(e->enqueue(src, nullptr, cnt, e->stream));
+        for (const auto& st : e->steps) {
+            if (!st.i8)
+                continue;
+            const hp_layer& L = e->layers[st.layer];
+            const auto& ti = *e->tensors[L.in];
+            HP_HIP_TRY(hp::launch_absmax(ti.view(L.in_coff), cnt, ti.H, ti.W, L.cin, amax.as<unsigned>() + st.layer, e->stream));
+        }
+        // the next chunk's copy overwrites the staged frames only after this chunk's kernels read them (same stream)
+    }
+    std::vector<unsigned> bits(NL);
+    HP_HIP_TRY(hipStreamSynchronize(e->stream));
+    HP_HIP_TRY(hipMemcpy(bits.data(), amax.p, (size_t)NL * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (int i = 0; i < NL; ++i)
+        if (e->i8_eligible(i)) {
+            float a;
+            memcpy(&a, &bits[i], sizeof(float));
+            // (an fp16 activation that overflowed would give s_a = inf: inv_a = 0, dq = inf, NaN outputs)
+            HP_REQUIRE(std::isfinite(a), HP_ERR_INVALID, "hp_engine_calibrate_u8: layer %d: the input of this layer is not finite on the calibration frames (max |x| = %g)", i, (double)a);
+            scales[i] = a > 0.f ? a / 127.f : 1.f; // TensorRT's MinMax calibrator: s_a = A / 127
+        }
+    guard.e = nullptr;
+    e->i8_scale = scales;
+    return e->apply_int8_scales();
+}
+
 int hp_engine_device_bytes(const hp_engine* e, uint64_t bytes[3])
 {
     HP_REQUIRE(e && bytes, HP_ERR_INVALID, "hp_engine_device_bytes: null argument");
@@ -2168,14 +2375,9 @@ int hp_engine_set_concurrency(hp_engine* e, int parts)
         parts = 1;
     if (parts == e->parts)
         return HP_OK;
-    HP_HIP_TRY(hipStreamSynchronize(e->stream));
-    if (e->last.stream)
-        HP_HIP_TRY(hipStreamSynchronize((hipStream_t)e->last.stream));
+    HP_TRY(e->drop_graphs()); // (the captured schedules are of the other form)
     if (parts == 2 && !e->stream2)
         HP_HIP_TRY(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
-    for (auto& g : e->graphs) // (the captured schedules are of the other form)
-        (void)hipGraphExecDestroy(g.second);
-    e->graphs.clear();
     e->parts = parts;
     return HP_OK;
 }
@@ -2263,7 +2465,7 @@ int hp_engine_profile(hp_engine* e, int n, int iters, hp_layer_time* out, int ca
                 : st.op == OP_MLPHEAD        ? 6000000 + st.hp_.K1
                 : st.op == OP_CHAIN          ? 7000000 + hp::conv_chain_variant(st.ch)
                 : st.op == OP_BNECK          ? 9000000 + hp::bottleneck_variant(st.bn)
-                : (st.op == HP_OP_CONV && !st.first) ? (st.f32 ? (st.head32 ? hp::conv32_head_tile(st.hh.HID, st.cp32.Cout) : st.wino ? hp::conv32_winograd_tile(st.cp32) : st.cin_split ? hp::conv32_direct_tile(st.cp32, e->dtype == HP_DTYPE_F32S && !e->split_off) : hp::conv32_tile(st.cp32)) : hp::conv_mfma_tile(st.cp))
+                : (st.op == HP_OP_CONV && !st.first) ? (st.f32 ? (st.head32 ? hp::conv32_head_tile(st.hh.HID, st.cp32.Cout) : st.wino ? hp::conv32_winograd_tile(st.cp32) : st.cin_split ? hp::conv32_direct_tile(st.cp32, e->dtype == HP_DTYPE_F32S && !e->split_off) : hp::conv32_tile(st.cp32)) : e->i8_on(st) ? hp::conv_i8_tile(st.cp) : hp::conv_mfma_tile(st.cp))
                                                     : 0;
             out[k].ms = ms / iters;
             out[k].flops = st.flops * n, out[k].bytes = st.bytes * n;
@@ -2316,7 +2518,7 @@ int hp_engine_profile_pair(hp_engine* e, hp_engine* f, int n, int iters, hp_laye
                 : st.op == OP_MLPHEAD        ? 6000000 + st.hp_.K1
                 : st.op == OP_CHAIN          ? 7000000 + hp::conv_chain_variant(st.ch)
                 : st.op == OP_BNECK          ? 9000000 + hp::bottleneck_variant(st.bn)
-                : (st.op == HP_OP_CONV && !st.first) ? (st.f32 ? (st.head32 ? hp::conv32_head_tile(st.hh.HID, st.cp32.Cout) : st.wino ? hp::conv32_winograd_tile(st.cp32) : st.cin_split ? hp::conv32_direct_tile(st.cp32, e->dtype == HP_DTYPE_F32S && !e->split_off) : hp::conv32_tile(st.cp32)) : hp::conv_mfma_tile(st.cp))
+                : (st.op == HP_OP_CONV && !st.first) ? (st.f32 ? (st.head32 ? hp::conv32_head_tile(st.hh.HID, st.cp32.Cout) : st.wino ? hp::conv32_winograd_tile(st.cp32) : st.cin_split ? hp::conv32_direct_tile(st.cp32, e->dtype == HP_DTYPE_F32S && !e->split_off) : hp::conv32_tile(st.cp32)) : e->i8_on(st) ? hp::conv_i8_tile(st.cp) : hp::conv_mfma_tile(st.cp))
                                                     : 0;
             out[k].ms = std::max(m0, m1) / (2 * iters);
             out[k].flops = st.flops * n, out[k].bytes = st.bytes * n;
@@ -2374,7 +2576,7 @@ int hp_engine_profile_sequence(hp_engine* e, int n, int iters, hp_layer_time* ou
                 : st.op == OP_MLPHEAD        ? 6000000 + st.hp_.K1
                 : st.op == OP_CHAIN          ? 7000000 + hp::conv_chain_variant(st.ch)
                 : st.op == OP_BNECK          ? 9000000 + hp::bottleneck_variant(st.bn)
-                : (st.op == HP_OP_CONV && !st.first) ? (st.f32 ? (st.head32 ? hp::conv32_head_tile(st.hh.HID, st.cp32.Cout) : st.wino ? hp::conv32_winograd_tile(st.cp32) : st.cin_split ? hp::conv32_direct_tile(st.cp32, e->dtype == HP_DTYPE_F32S && !e->split_off) : hp::conv32_tile(st.cp32)) : hp::conv_mfma_tile(st.cp))
+                : (st.op == HP_OP_CONV && !st.first) ? (st.f32 ? (st.head32 ? hp::conv32_head_tile(st.hh.HID, st.cp32.Cout) : st.wino ? hp::conv32_winograd_tile(st.cp32) : st.cin_split ? hp::conv32_direct_tile(st.cp32, e->dtype == HP_DTYPE_F32S && !e->split_off) : hp::conv32_tile(st.cp32)) : e->i8_on(st) ? hp::conv_i8_tile(st.cp) : hp::conv_mfma_tile(st.cp))
                                                     : 0;
             out[k].ms = (float)(acc[k] / iters);
             out[k].flops = st.flops * n, out[k].bytes = st.bytes * n;

@@ -74,6 +74,11 @@ int hp_pipeline_create_ex(hp_pipeline** out, const hp_engine_desc* desc, const h
     // hp_engine_output_to_host, which a pipeline never calls - a batch that overflowed would be parsed and returned as humans with no error
     HP_REQUIRE(desc->dtype != HP_DTYPE_F32S, HP_ERR_INVALID,
         "hp_pipeline_create: HP_DTYPE_F32S engines are for single-stream use (hp_engine_infer_* + hp_engine_synchronize); use HP_DTYPE_F32 or HP_DTYPE_F16 in a pipeline");
+    if (desc->dtype == HP_DTYPE_I8) { // every pipe's engine is created calibrated from the same scales: a stream never calibrates by itself
+        HP_REQUIRE(desc->int8_scales, HP_ERR_STATE, "hp_pipeline_create: HP_DTYPE_I8 engine without int8 scales: calibrate an engine first (hp_engine_calibrate_u8) and pass its hp_engine_describe");
+        for (int i = 0; i < desc->n_layers; ++i)
+            HP_REQUIRE(desc->int8_scales[i] >= 0.f, HP_ERR_STATE, "hp_pipeline_create: HP_DTYPE_I8 engine not calibrated (layer %d has scale %g)", i, (double)desc->int8_scales[i]);
+    }
     std::unique_ptr<hp_pipeline> pl(new hp_pipeline());
     pl->kind = parser->kind;
     pl->n_pipes = n_pipes, pl->max_batch = desc->max_batch, pl->in_w = desc->in_w, pl->in_h = desc->in_h, pl->keep_ratio = keep_ratio;

@@ -36,15 +36,17 @@ class EngineDesc(C.Structure):
                 ("flip_rb", C.c_int32), ("mean", C.c_float * 3), ("inv_std", C.c_float * 3),
                 ("layers", C.POINTER(Layer)), ("n_layers", C.c_int32), ("outputs", C.POINTER(OutputDesc)),
                 ("n_outputs", C.c_int32), ("weights", C.POINTER(C.c_float)), ("n_weights", C.c_size_t),
-                ("dtype", C.c_int32)]
+                ("dtype", C.c_int32), ("int8_scales", C.POINTER(C.c_float))]
 
 
 # HP_DTYPE_*: data_type::kHALF / data_type::kFLOAT of the reference's engine; F32S = the kFLOAT engine with the dense layers' products
-# formed as three exact fp16 x fp16 products on the fp16 matrix pipe (csrc/conv32_direct.hip), opt-in
-DTYPE_F16, DTYPE_F32, DTYPE_F32S = 0, 1, 2
+# formed as three exact fp16 x fp16 products on the fp16 matrix pipe (csrc/conv32_direct.hip), opt-in; I8 = data_type::kINT8: post-training
+# quantization on the int8 matrix pipe (csrc/conv_i8.hip), calibrated before it infers (Engine.calibrate / Engine.int8_scales)
+DTYPE_F16, DTYPE_F32, DTYPE_F32S, DTYPE_I8 = 0, 1, 2, 3
 _DTYPES = {"f16": DTYPE_F16, "fp16": DTYPE_F16, "half": DTYPE_F16, DTYPE_F16: DTYPE_F16,
            "f32": DTYPE_F32, "fp32": DTYPE_F32, "float": DTYPE_F32, DTYPE_F32: DTYPE_F32,
-           "f32s": DTYPE_F32S, "f32_split": DTYPE_F32S, DTYPE_F32S: DTYPE_F32S}
+           "f32s": DTYPE_F32S, "f32_split": DTYPE_F32S, DTYPE_F32S: DTYPE_F32S,
+           "i8": DTYPE_I8, DTYPE_I8: DTYPE_I8}
 
 
 class LayerTime(C.Structure):
@@ -190,6 +192,32 @@ class Engine:
         check(lib().hp_engine_load(C.byref(handle), path.encode(), int(max_batch)))
         self._adopt(handle, max_batch)
         return self
+
+    # ---- HP_DTYPE_I8 engines
+    def calibrate(self, frames_u8: np.ndarray) -> None:
+        """TensorRT's MinMax calibration on network-sized u8 HWC BGR frames [n,h,w,3] (any n: run in max_batch chunks): every eligible
+        layer's activation scale becomes max |x| / 127 of its input over all frames, x from this engine with every layer in fp16."""
+        frames = np.ascontiguousarray(frames_u8, np.uint8)
+        assert frames.ndim == 4 and frames.shape[1:] == (self.in_h, self.in_w, 3)
+        check(lib().hp_engine_calibrate_u8(self._h, frames.ctypes.data_as(C.POINTER(C.c_uint8)), frames.shape[0], 0))
+
+    @property
+    def int8_scales(self) -> np.ndarray:
+        """One float per layer: > 0 the layer runs int8 with this activation scale, 0 it runs in fp16, -1 eligible but not calibrated."""
+        n = self._n_layers()
+        out = np.zeros(n, np.float32)
+        check(lib().hp_engine_int8_scales(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return out
+
+    @int8_scales.setter
+    def int8_scales(self, scales) -> None:
+        s = np.ascontiguousarray(scales, np.float32).ravel()
+        check(lib().hp_engine_set_int8_scales(self._h, s.ctypes.data_as(C.POINTER(C.c_float)), s.size))
+
+    def _n_layers(self) -> int:
+        d = EngineDesc()
+        check(lib().hp_engine_describe(self._h, C.byref(d)))
+        return int(d.n_layers)
 
     @property
     def split_fallbacks(self) -> int:

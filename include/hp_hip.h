@@ -248,8 +248,18 @@ typedef struct hp_output_desc {
  * HP_DTYPE_F32S ("split"): the HP_DTYPE_F32 engine - fp32 storage, fp32 accumulation, same launches - with the products of its dense
  * 1 x 1 / 3 x 3 stride-1 layers formed on the fp16 matrix pipe: x = hi + 2^-11 lo with hi, lo fp16, a b = hi hi + 2^-11 (hi lo + lo hi),
  * every partial product exact in the fp32 accumulator, ~2^-22 relative per product (csrc/conv32_direct.hip).  Opt-in; an activation beyond
- * fp16's range (|x| > 65504) makes the engine re-run the batch on the fp32 pipe and stay there (hp_engine_split_fallbacks counts). */
-enum { HP_DTYPE_F16 = 0, HP_DTYPE_F32 = 1, HP_DTYPE_F32S = 2 };
+ * fp16's range (|x| > 65504) makes the engine re-run the batch on the fp32 pipe and stay there (hp_engine_split_fallbacks counts).
+ * HP_DTYPE_I8 (data_type::kINT8): post-training quantization in TensorRT's form on the HP_DTYPE_F16 engine's per-layer schedule (no fusions).
+ * Every dense convolution that does not read the network input and whose geometry the int8 kernel covers (1 x 1 stride 1 | 2, 3 x 3 stride
+ * 1 | 2 dilation 1 | 2, 7 x 7 stride 1) may run on the int8 matrix pipe: weights symmetric per output channel (s_w[c] = max |w| / 127,
+ * q_w = clamp(rint(w / s_w[c]), -127, 127)), activations with one scale per layer input (q_x = clamp(rint(x * (1 / s_a)), -127, 127), computed
+ * while the kernel stages its fp16 input), exact int32 sums, v = (float)acc * (s_a * s_w[c]) + bias[c], then the fp16 engine's epilogue.
+ * Activations between layers stay fp16 NHWC.  The per-layer scale vector (hp_engine_int8_scales) says what runs where: > 0 int8 with that
+ * s_a, 0 the layer's fp16 kernel, -1 eligible but not calibrated - an engine with a -1 entry does not infer (HP_ERR_STATE) until
+ * hp_engine_calibrate_u8 (TensorRT's MinMax rule: s_a = max |x| / 127 over the calibration frames, x from the same engine in fp16) or
+ * hp_engine_set_int8_scales (a calibration cache) fills it.  An engine with every scale 0 is bit-identical to the HP_DTYPE_F16 engine built
+ * with HP_NO_FUSE=1. */
+enum { HP_DTYPE_F16 = 0, HP_DTYPE_F32 = 1, HP_DTYPE_F32S = 2, HP_DTYPE_I8 = 3 };
 
 typedef struct hp_engine_desc {
     int32_t in_w, in_h, max_batch;   /* tensorrt(..., cv::Size input_size, int max_batch_size = 8, ...) */
@@ -262,8 +272,10 @@ typedef struct hp_engine_desc {
     int32_t n_outputs;
     const float* weights;            /* host fp32 blob */
     size_t n_weights;
-    int32_t dtype;                   /* HP_DTYPE_F16 (0, the zero-initialised default), HP_DTYPE_F32 or HP_DTYPE_F32S: the reference's data_type argument
-                                      * (include/hyperpose/operator/dnn/tensorrt.hpp:14-21,48; src/tensorrt.cpp:327,353) */
+    int32_t dtype;                   /* HP_DTYPE_F16 (0, the zero-initialised default), HP_DTYPE_F32, HP_DTYPE_F32S or HP_DTYPE_I8: the reference's data_type
+                                      * argument (include/hyperpose/operator/dnn/tensorrt.hpp:14-21,48; src/tensorrt.cpp:327,353) */
+    const float* int8_scales;        /* HP_DTYPE_I8: n_layers per-layer activation scales (see HP_DTYPE_I8; -1 = not calibrated), or NULL for an
+                                      * uncalibrated engine; ignored by the other dtypes.  hp_engine_describe fills it (NULL for the other dtypes). */
 } hp_engine_desc;
 
 typedef struct hp_engine hp_engine;
@@ -357,6 +369,13 @@ int hp_engine_create_from_model(hp_engine** out, const hp_model* m, int max_batc
 int hp_engine_create_from_model_dtype(hp_engine** out, const hp_model* m, int max_batch, double factor, int flip_rb,
                                       const float* weights, size_t n_weights, int dtype);
 int hp_engine_dtype(const hp_engine* e); /* HP_DTYPE_* of an engine (serialized engines carry theirs) */
+/* HP_DTYPE_I8 engines (HP_ERR_STATE for the other dtypes).  Calibration: n network-sized u8 HWC BGR frames (any n: the engine runs them in
+ * max_batch chunks, synchronously, every layer in fp16); every eligible layer's scale becomes max |x| / 127 of its input channels over the valid
+ * pixels of all frames (1 where that maximum is 0) - independent of frame order and chunking.  Setting scales imports a calibration cache:
+ * n == the layer count, every value finite and >= 0, > 0 only on eligible layers (HP_ERR_INVALID otherwise).  Both drop the captured graphs. */
+int hp_engine_calibrate_u8(hp_engine* e, const uint8_t* hwc_bgr, int n, int on_device);
+int hp_engine_int8_scales(const hp_engine* e, float* scales, int n);
+int hp_engine_set_int8_scales(hp_engine* e, const float* scales, int n);
 /* HP_DTYPE_F32S engines: how many times the engine left the split kernels for the fp32 pipe because an activation did not fit fp16's
  * range (0 or 1: it does not go back); 0 for the other types */
 int hp_engine_split_fallbacks(const hp_engine* e);

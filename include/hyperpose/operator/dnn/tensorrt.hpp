@@ -5,8 +5,10 @@
 //     engine.inference(std::vector<cv::Mat>)       engine.inference(std::vector<float> nchw, n)       engine.save(path)
 // Header-only on top of the C ABI (include/hp_hip.h); the network runs as hand-written gfx950 kernels.  `data_type` selects the
 // arithmetic as it does in the reference (src/tensorrt.cpp:327,353): kFLOAT - the default, as there - is fp32 storage and fp32
-// matrix-pipe arithmetic (HP_DTYPE_F32), kHALF the fused fp16 kernels with fp32 accumulation (HP_DTYPE_F16, the fast path); the integer
-// types have no meaning for these networks and are refused like an engine-build failure.  Frames of any size are resized on
+// matrix-pipe arithmetic (HP_DTYPE_F32), kHALF the fused fp16 kernels with fp32 accumulation (HP_DTYPE_F16, the fast path), kINT8
+// post-training quantization on the int8 matrix pipe (HP_DTYPE_I8): such an engine infers only after calibrate() (TensorRT's MinMax
+// calibrator over the given frames) or after loading a serialized engine that was calibrated; kINT32 / kBOOL have no meaning for these
+// networks and are refused like an engine-build failure.  Frames of any size are resized on
 // the DEVICE exactly as the reference does on the host: cv::resize (INTER_LINEAR) or, with keep_ratio, non_scaling_resize
 // (src/tensorrt.cpp:446-451, src/data.cpp:53-69) through hp_resize_u8c3 / hp_letterbox_u8c3.
 #pragma once
@@ -40,7 +42,7 @@ struct data_type {
     {
     }
     /// HP_DTYPE_* of the C ABI, or -1 for the types no engine is built in
-    inline int hp_dtype() const { return val == kFLOAT ? HP_DTYPE_F32 : val == kHALF ? HP_DTYPE_F16 : -1; }
+    inline int hp_dtype() const { return val == kFLOAT ? HP_DTYPE_F32 : val == kHALF ? HP_DTYPE_F16 : val == kINT8 ? HP_DTYPE_I8 : -1; }
 };
 
 namespace detail {
@@ -83,7 +85,7 @@ namespace dnn {
             : m_inp_size(input_size), m_max_batch_size(max_batch_size), m_keep_ratio(keep_ratio), m_factor(factor), m_flip_rgb(flip_rgb)
         {
             if (dtype.hp_dtype() < 0)
-                fatal("hyperpose::dnn::tensorrt: only data_type::kFLOAT and data_type::kHALF engines can be built");
+                fatal("hyperpose::dnn::tensorrt: only data_type::kFLOAT, data_type::kHALF and data_type::kINT8 engines can be built");
             if (hp_model_from_onnx_file(&m_model, onnx_model.model_path.c_str(), input_size.width, input_size.height) != HP_OK)
                 fatal(hp_last_error());
             if (hp_engine_create_from_model_dtype(&m_engine, m_model, max_batch_size, factor, flip_rgb ? 1 : 0, nullptr, 0, dtype.hp_dtype()) != HP_OK)
@@ -111,7 +113,7 @@ namespace dnn {
             : m_inp_size(input_size), m_max_batch_size(max_batch_size), m_keep_ratio(keep_ratio), m_factor(factor), m_flip_rgb(flip_rgb)
         {
             if (dtype.hp_dtype() < 0)
-                fatal("hyperpose::dnn::tensorrt: only data_type::kFLOAT and data_type::kHALF engines can be built");
+                fatal("hyperpose::dnn::tensorrt: only data_type::kFLOAT, data_type::kHALF and data_type::kINT8 engines can be built");
             if (hp_model_build(&m_model, model.arch.c_str(), input_size.width, input_size.height) != HP_OK)
                 fatal(hp_last_error());
             std::vector<float> w = model.weights;
@@ -152,6 +154,7 @@ namespace dnn {
         /// and the batch is inferred; throws std::logic_error on an over-size batch (:439-443).
         std::vector<internal_t> inference(std::vector<cv::Mat> inputs)
         {
+            require_calibrated();
             if (inputs.size() > (size_t)m_max_batch_size)
                 throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(inputs.size()) + " Max@" + std::to_string(m_max_batch_size));
             if (inputs.empty())
@@ -179,37 +182,50 @@ namespace dnn {
                     fatal(hp_last_error());
                 return collect(inputs.size());
             }
-            for (size_t i = 0; i < inputs.size(); ++i) {
-                const cv::Mat& f = inputs[i];
-                const uint8_t* src = detail::mat_bytes(f, scratch);
-                const size_t bytes = (size_t)f.cols * f.rows * 3;
-                uint8_t* dst = m_dev_net + i * net_frame;
-                if (f.cols == m_inp_size.width && f.rows == m_inp_size.height) { // resize to the same size is a copy
-                    if (hp_memcpy_h2d(dst, src, bytes) != HP_OK)
-                        fatal(hp_last_error());
-                    continue;
-                }
-                if (bytes > m_raw_bytes) {
-                    if (m_dev_raw)
-                        hp_free(m_dev_raw);
-                    m_dev_raw = nullptr, m_raw_bytes = 0;
-                    if (hp_malloc((void**)&m_dev_raw, bytes) != HP_OK)
-                        fatal(hp_last_error());
-                    m_raw_bytes = bytes;
-                }
-                if (hp_memcpy_h2d(m_dev_raw, src, bytes) != HP_OK)
-                    fatal(hp_last_error());
-                const int rc = m_keep_ratio
-                    ? hp_letterbox_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, 0, 0, 0,
-                          hp_engine_stream(m_engine))
-                    : hp_resize_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3,
-                          hp_engine_stream(m_engine));
-                if (rc != HP_OK || hp_engine_synchronize(m_engine) != HP_OK) // m_dev_raw is re-used by the next frame
-                    fatal(hp_last_error());
-            }
+            for (size_t i = 0; i < inputs.size(); ++i)
+                frame_to_device(inputs[i], m_dev_net + i * net_frame, scratch);
             if (hp_engine_infer_u8(m_engine, m_dev_net, (int)inputs.size(), 1, nullptr) != HP_OK)
                 fatal(hp_last_error());
             return collect(inputs.size());
+        }
+
+        /// data_type::kINT8: TensorRT's MinMax calibration (an IInt8MinMaxCalibrator fed with these frames).  Frames of any size are brought to
+        /// the network's size exactly as inference() does; any number of frames (the engine runs them in max_batch_size chunks).  Replaces
+        /// every per-layer activation scale; calibration is never implicit.
+        void calibrate(const std::vector<cv::Mat>& frames)
+        {
+            if (hp_engine_dtype(m_engine) != HP_DTYPE_I8)
+                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: only data_type::kINT8 engines are calibrated");
+            if (frames.empty())
+                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: no frames");
+            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
+            retire_last_batch();
+            uint8_t* all = nullptr; // every frame at the network's size, on the device: the calibration is one call over all of them
+            if (hp_malloc((void**)&all, net_frame * frames.size()) != HP_OK)
+                fatal(hp_last_error());
+            std::vector<uint8_t> scratch;
+            for (size_t i = 0; i < frames.size(); ++i) {
+                if (frames[i].empty())
+                    fatal("hyperpose::dnn::tensorrt::calibrate: empty image");
+                frame_to_device(frames[i], all + i * net_frame, scratch);
+            }
+            const int rc = hp_device_synchronize() == HP_OK ? hp_engine_calibrate_u8(m_engine, all, (int)frames.size(), 1) : HP_ERR_HIP;
+            hp_free(all);
+            if (rc != HP_OK)
+                fatal(hp_last_error());
+        }
+        /// false for a data_type::kINT8 engine that was neither calibrated nor loaded calibrated
+        bool calibrated() const
+        {
+            if (hp_engine_dtype(m_engine) != HP_DTYPE_I8)
+                return true;
+            hp_engine_desc d{};
+            if (hp_engine_describe(m_engine, &d) != HP_OK || !d.int8_scales)
+                return false;
+            for (int i = 0; i < d.n_layers; ++i)
+                if (d.int8_scales[i] < 0.f)
+                    return false;
+            return true;
         }
 
         /// src/tensorrt.cpp:364-434: plain NCHW float buffers, no scaling / channel swap.
@@ -219,6 +235,7 @@ namespace dnn {
                 throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(batch_size) + " Max@" + std::to_string(m_max_batch_size));
             if (float_buffer.size() < batch_size * 3 * (size_t)m_inp_size.area())
                 throw std::logic_error("Input float buffer is smaller than batch_size x 3 x H x W");
+            require_calibrated();
             retire_last_batch();
             if (hp_engine_infer_f32(m_engine, float_buffer.data(), (int)batch_size, 0, nullptr) != HP_OK)
                 fatal(hp_last_error());
@@ -235,6 +252,7 @@ namespace dnn {
         // ---- additions for device-resident use (the stream operator and the parsers' process_device forms)
         void inference_device(const uint8_t* dev_hwc_bgr, int n, void* stream = nullptr)
         {
+            require_calibrated();
             retire_last_batch();
             if (hp_engine_infer_u8(m_engine, dev_hwc_bgr, n, 1, stream) != HP_OK)
                 fatal(hp_last_error());
@@ -242,7 +260,43 @@ namespace dnn {
         hp_engine* handle() { return m_engine; }
         bool keep_ratio() const { return m_keep_ratio; }
 
+        void require_calibrated() const
+        {
+            if (!calibrated())
+                throw std::logic_error("hyperpose::dnn::tensorrt: a data_type::kINT8 engine must be calibrated first: call calibrate() with "
+                                       "representative frames (or load a serialized engine that was calibrated)");
+        }
+
     private:
+        // one frame brought to the network's size at device address dst (src/tensorrt.cpp:446-451): cv::resize (INTER_LINEAR) or, with
+        // keep_ratio, non_scaling_resize on the device; a network-sized frame is a copy
+        void frame_to_device(const cv::Mat& f, uint8_t* dst, std::vector<uint8_t>& scratch)
+        {
+            const uint8_t* src = detail::mat_bytes(f, scratch);
+            const size_t bytes = (size_t)f.cols * f.rows * 3;
+            if (f.cols == m_inp_size.width && f.rows == m_inp_size.height) { // resize to the same size is a copy
+                if (hp_memcpy_h2d(dst, src, bytes) != HP_OK)
+                    fatal(hp_last_error());
+                return;
+            }
+            if (bytes > m_raw_bytes) {
+                if (m_dev_raw)
+                    hp_free(m_dev_raw);
+                m_dev_raw = nullptr, m_raw_bytes = 0;
+                if (hp_malloc((void**)&m_dev_raw, bytes) != HP_OK)
+                    fatal(hp_last_error());
+                m_raw_bytes = bytes;
+            }
+            if (hp_memcpy_h2d(m_dev_raw, src, bytes) != HP_OK)
+                fatal(hp_last_error());
+            const int rc = m_keep_ratio
+                ? hp_letterbox_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, 0, 0, 0,
+                      hp_engine_stream(m_engine))
+                : hp_resize_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3,
+                      hp_engine_stream(m_engine));
+            if (rc != HP_OK || hp_engine_synchronize(m_engine) != HP_OK) // m_dev_raw is re-used by the next frame
+                fatal(hp_last_error());
+        }
         [[noreturn]] static void fatal(const char* msg)
         {
             std::cerr << "[HyperPose::ERROR  ] " << msg << "\n";

@@ -119,6 +119,11 @@ private:
         hp_engine_desc d{};
         detail::hp_check(hp_engine_describe(engine, &d));
         d.max_batch = max_batch_size;
+        if (d.dtype == HP_DTYPE_I8) // every pipe's engine is created from the calibrated scales of this one
+            for (int i = 0; i < d.n_layers; ++i)
+                if (!d.int8_scales || d.int8_scales[i] < 0.f)
+                    throw std::logic_error("hyperpose::dnn::tensorrt: a data_type::kINT8 engine must be calibrated first: call calibrate() with "
+                                           "representative frames (or load a serialized engine that was calibrated)");
         detail::hp_check(hp_pipeline_create_ex(&m_pl, &d, &parser, n_pipes, keep_ratio ? 1 : 0, (size_t)max_frame.area() * 3));
         m_pipes = n_pipes;
         m_out.resize((size_t)max_batch_size * CAP);
