@@ -450,16 +450,12 @@ static int direct_mw(const conv32_params& p, bool split, int dwd)
 {
     const int groups = p.Cout_pad / (split ? 64 : 32);
     const long tiles = (long)p.B * ((p.OH + 7) / 8) * ((p.OW + 7) / 8);
-    static const int force = getenv("HP_DIRECT_MW") ? atoi(getenv("HP_DIRECT_MW")) : 0;
-    static const int mw_max = getenv("HP_DIRECT_MW_MAX") ? atoi(getenv("HP_DIRECT_MW_MAX")) : 8;
     for (int mw : { 8, 4, 2, 1 }) {
         if (mw == 8 && (!split || p.KH != 1 || dwd == 2))
             continue; // (8 wavefronts of 64 channels: the split 1 x 1 layers with 512 outputs read their input tile once; behind a depthwise layer of dilation 2: 68 spilled registers - not compiled)
         if (dwd && mw == 1)
             break;
-        if ((force && mw != force) || mw > mw_max)
-            continue;
-        if (groups % mw == 0 && (force || mw == 1 || (dwd && mw == 2) || tiles * (groups / mw) >= (split ? 256 : 640)))
+        if (groups % mw == 0 && (mw == 1 || (dwd && mw == 2) || tiles * (groups / mw) >= (split ? 256 : 640)))
             return mw;
     }
     return dwd ? 0 : 1;

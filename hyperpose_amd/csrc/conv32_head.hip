@@ -235,16 +235,17 @@ static bool head_args_ok(const conv32_params& q, const head32_hidden& h)
 }
 
 // whether two head launches may share one grid: the same input view and map
-bool conv32_head_pair_ok(const conv32_params& a, const conv32_params& b)
+static bool same_input(const conv32_params& a, const conv32_params& b)
 {
-    const bool off = getenv("HP_HEAD_PAIR") && atoi(getenv("HP_HEAD_PAIR")) == 0; // A/B switch (read per launch / capture: the tests compare both in one process)
-    return !off && a.in.p == b.in.p && a.in.cs == b.in.cs && a.in.coff == b.in.coff && a.in.wp == b.in.wp && a.in.img == b.in.img && a.OH == b.OH && a.OW == b.OW
+    return a.in.p == b.in.p && a.in.cs == b.in.cs && a.in.coff == b.in.coff && a.in.wp == b.in.wp && a.in.img == b.in.img && a.OH == b.OH && a.OW == b.OW
         && a.npix == b.npix;
 }
 
+bool conv32_head_pair_ok(const conv32_params& a, const conv32_params& b, const engine_switches& sw) { return sw.head_pair32 && same_input(a, b); }
+
 hipError_t launch_conv32_head_pair(const conv32_params& qa, const head32_hidden& ha, const conv32_params& qb, const head32_hidden& hb, hipStream_t s)
 {
-    if (!head_args_ok(qa, ha) || !head_args_ok(qb, hb) || !conv32_head_pair_ok(qa, qb))
+    if (!head_args_ok(qa, ha) || !head_args_ok(qb, hb) || !same_input(qa, qb))
         return hipErrorInvalidValue;
     const dim3 grid(((qa.npix + 31) / 32 + 7) / 8 * 8 * 2);
     const bool a1 = qa.Cout <= 32, b1 = qb.Cout <= 32;

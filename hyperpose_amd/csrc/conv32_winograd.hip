@@ -17,7 +17,7 @@
 // Kernel shape (MW = wavefronts per block, 4 by default):
 //   block   = 16 x 8 output pixels = 8 x 4 Winograd tiles (two N = 16 column tiles of the MFMA) x 16 MW output channels; a wavefront = ONE
 //             16-row MFMA tile of channels x 32 tiles x 16 positions = 128 accumulator registers.  MW = 4: two blocks per CU - one block's
-//             transform phases and epilogue run under the other's MFMAs; MW = 8 (HP_WINO_MW=8): one block of two wavefronts per SIMD per
+//             transform phases and epilogue run under the other's MFMAs; MW = 8 (measured, no longer launched): one block of two wavefronts per SIMD per
 //             CU, the staging / transform of a pixel tile shared by 128 channels - 44.6 us alone against 46.3 for a 128 -> 128 layer at
 //             8 x 46 x 54, but 31.5 against 28.8 with a second stream (its phases are in step inside the one block).
 //             (The first form - 32 channels x 16 tiles per wavefront - read 2 KB of A per eight MFMAs: 68 us alone.)
@@ -25,7 +25,7 @@
 //             registers), goes to LDS, is transformed cooperatively (a wavefront = ONE row of Bt d B for 16 tiles, lane = (tile, 4-channel
 //             quad): 8 LDS reads, 8 vector additions, 4 LDS writes) into V[pos][tile][16 channels].  MW = 4 (PIPE): two V buffers, the
 //             transform of chunk c + 1 cut into 16 pieces that sit inside the 16 MFMA steps of chunk c (46.6 -> 44.3 us alone, 28.9 -> 27.0
-//             with a second stream; HP_WINO_PIPE=0 is the A/B switch back); MW = 8: one buffer, the transform between two barriers;
+//             with a second stream; the unpipelined form is no longer launched); MW = 8: one buffer, the transform between two barriers;
 //   MFMA    = per position one step of 16 channels: lane (row / tile, kq) holds channels 4 kq .. 4 kq + 3 of its row (A, 1 KB from L2 in
 //             fragment order, six steps ahead) / tile (B, two ds_read_b128 from V) and feeds element e to MFMA e - 8 MFMAs of 32 cycles per step;
 //   output  = At M A per lane from its own registers (lane (tile, kq) holds channels 4 kq + r at all 16 positions), written into a slab the
@@ -324,14 +324,8 @@ bool conv32_winograd_ok(const conv32_params& p)
         && p.pad_l == 1 && !p.out_f32 && p.out.p;
 }
 
-// Wavefronts (16-channel MFMA tiles) per block: 4 (two blocks per CU); HP_WINO_MW=8 where the channel count allows: see "Kernel shape"
-static int winograd_mw(const conv32_params& p)
-{
-    static const int force = getenv("HP_WINO_MW") ? atoi(getenv("HP_WINO_MW")) : 0;
-    return (force == 8 && p.Cout_pad % 128 == 0) ? 8 : 4;
-}
-
-int conv32_winograd_tile(const conv32_params& p) { return p.w_wino3 ? conv32_winograd3_tile(p) : 35000000 + 3000 + winograd_mw(p); }
+// four wavefronts (16-channel MFMA tiles) per block, the pipelined form: see "Kernel shape"
+int conv32_winograd_tile(const conv32_params& p) { return p.w_wino3 ? conv32_winograd3_tile(p) : 35000000 + 3000 + 4; }
 
 // MFMA work of one launch (what the roofline fraction of this kernel is computed from): 16 products per tile and channel pair
 double conv32_winograd_flops(const conv32_params& p)
@@ -390,20 +384,20 @@ static hipError_t launch_wino_case(const conv32_params& q, dim3 grid, int tiles_
 // set the launch's time (45.0 us); as 672 blocks of the second it takes 35.9 us alone and the same 27 us next to a second stream's launch -
 // but four pipes lose 1.4 % (5 113 -> 5 042 frames/s, three runs each: the U stream).  So: the small form for a caller with ONE batch in flight
 // (conv32_params::latency, i.e. hp_engine_set_concurrency(e, 2)) when the large form would not fill the chip's 512 slots twice; the same
-// tiles, the same arithmetic: the same bits (tests/test_engine_fp32_gpu.py).  HP_WINO_NC=1 | 2 forces one (read per launch).
-static int winograd_nc(const conv32_params& p, int blocks_nc2)
+// tiles, the same arithmetic: the same bits (tests/test_engine_fp32_gpu.py).  HP_WINO_NC=1 | 2 forces one.
+static int winograd_nc(const conv32_params& p, const engine_switches& sw, int blocks_nc2)
 {
-    const int force = getenv("HP_WINO_NC") ? atoi(getenv("HP_WINO_NC")) : 0;
+    const int force = sw.wino_nc;
     if (force == 1 || force == 2)
         return force;
     return p.latency && blocks_nc2 <= 512 ? 1 : 2;
 }
 
 // Rows per image of the tall form, or 0 where it does not apply: the input's images must lie vh = even rows apart with at least one (zero) halo
-// row above and below each.  HP_WINO_TALL=0: the A/B switch (read per launch).
-static int winograd_tall(const conv32_params& p)
+// row above and below each.  HP_WINO_TALL=0: the A/B switch.
+static int winograd_tall(const conv32_params& p, const engine_switches& sw)
 {
-    if (getenv("HP_WINO_TALL") && atoi(getenv("HP_WINO_TALL")) == 0)
+    if (!sw.wino_tall)
         return 0;
     if (p.B < 2 || p.in.wp <= 0 || p.in.img % p.in.wp)
         return 0;
@@ -411,19 +405,14 @@ static int winograd_tall(const conv32_params& p)
     return (vh & 1) == 0 && vh >= p.H + 2 ? vh : 0;
 }
 
-static bool winograd_pipe() // HP_WINO_PIPE=0: the A/B switch back to the form with the transform between two barriers
-{
-    static const bool off = getenv("HP_WINO_PIPE") && atoi(getenv("HP_WINO_PIPE")) == 0;
-    return !off;
-}
-
-hipError_t launch_conv32_winograd(const conv32_params& p, hipStream_t s)
+hipError_t launch_conv32_winograd(const conv32_params& p, const engine_switches& sw, hipStream_t s)
 {
     if (!conv32_winograd_ok(p) || !p.w_wino || p.npix <= 0)
         return hipErrorInvalidValue;
-    const int tiles_x = (p.OW + 7) / 8, mw = winograd_mw(p);
-    const int nc = mw == 4 && winograd_pipe() ? winograd_nc(p, tiles_x * ((p.OH + 15) / 16) * p.B * (p.Cout_pad / 64)) : 2, bh = 8 * nc;
-    int tiles_y = (p.OH + bh - 1) / bh, vh = winograd_tall(p), images = p.B;
+    constexpr int mw = 4;
+    const int tiles_x = (p.OW + 7) / 8;
+    const int nc = winograd_nc(p, sw, tiles_x * ((p.OH + 15) / 16) * p.B * (p.Cout_pad / 64)), bh = 8 * nc;
+    int tiles_y = (p.OH + bh - 1) / bh, vh = winograd_tall(p, sw), images = p.B;
     if (vh) {
         const int tall_y = ((p.B - 1) * vh + p.H + bh - 1) / bh;
         if (tall_y < tiles_y * p.B)
@@ -432,20 +421,14 @@ hipError_t launch_conv32_winograd(const conv32_params& p, hipStream_t s)
             vh = 0; // (a map that is whole 16-row blocks already: 48 rows + 2 halo rows would only add separator rows)
     }
     const dim3 grid((tiles_x * tiles_y * images + 7) / 8 * 8 * (p.Cout_pad / (16 * mw))); // XCD-aware 1-D order: see the kernel
-    if (mw == 8)
-        return launch_wino_case<8, false>(p, grid, tiles_x, tiles_y, vh, s);
     if (nc == 1)
         return launch_wino_case<4, true, 1>(p, grid, tiles_x, tiles_y, vh, s);
-    return winograd_pipe() ? launch_wino_case<4, true>(p, grid, tiles_x, tiles_y, vh, s) : launch_wino_case<4, false>(p, grid, tiles_x, tiles_y, vh, s);
+    return launch_wino_case<4, true>(p, grid, tiles_x, tiles_y, vh, s);
 }
 
-hipError_t conv32_winograd_occupancy(const conv32_params& p, int* blocks_per_cu)
+hipError_t conv32_winograd_occupancy(const conv32_params&, int* blocks_per_cu)
 {
-    if (winograd_mw(p) == 8)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, conv32_winograd_kernel<8, false>, 512, wino_geom<8>::LDS_BYTES);
-    if (winograd_pipe())
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, conv32_winograd_kernel<4, true>, 256, wino_geom<4>::PLDS_BYTES);
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, conv32_winograd_kernel<4, false>, 256, wino_geom<4>::LDS_BYTES);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, conv32_winograd_kernel<4, true>, 256, wino_geom<4>::PLDS_BYTES);
 }
 
 } // namespace hp

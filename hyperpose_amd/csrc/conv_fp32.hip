@@ -654,9 +654,9 @@ static hipError_t launch_wk(const conv32_params& p, dim3 grid, hipStream_t s)
 
 // Which layers take conv32_wk_kernel: 1 x 1 (any stride), exactly 32 / 64 / 128 input channels, an NHWC output only, and enough pixel tiles that
 // two blocks per CU stay busy (HP_C32_WK=0: none, the A/B switch; =1: every layer of that shape).  Looks at pick_npix like conv32_pick.
-static int conv32_wk_bn(const conv32_params& p)
+static int conv32_wk_bn(const conv32_params& p, const engine_switches& sw)
 {
-    const int wk = getenv("HP_C32_WK") ? atoi(getenv("HP_C32_WK")) : -1;
+    const int wk = sw.c32_wk;
     if (wk == 0 || p.KH != 1 || p.KW != 1 || p.dil != 1 || p.out_f32 || !p.out.p || (p.Cin != 32 && p.Cin != 64 && p.Cin != 128))
         return 0;
     // K = 128 (two blocks per CU) wins nothing: ResNet's 128 -> 512 at 32 x 48 x 48 140 -> 135 us, MobileNet's 128 -> 128 at 8 x 92 x 108 38.6 -> 41.6
@@ -671,24 +671,17 @@ static int conv32_wk_bn(const conv32_params& p)
 // Block tile (BM output channels x BN pixels) of a layer.  The fp32 matrix pipe is slow enough (64 cycles per MFMA) that small tiles cost
 // little per MFMA, and a layer that is one wave of 128 x 128 tiles leaves CUs idle: LW-OpenPose's 3 x 3 128 -> 128 layers at 8 x 46 x 54 pixels
 // are 156 such tiles on 256 CUs (0.38 of the fp32 MFMA peak) - as 64 x 64 tiles they are 622 blocks, several per CU.
-static void conv32_pick(const conv32_params& p, int& BM, int& BN)
+static void conv32_pick(const conv32_params& p, const engine_switches& sw, int& BM, int& BN)
 {
     BM = p.Cout_pad % 128 == 0 ? 128 : 64, BN = 128;
-    static const int force = getenv("HP_C32_TILE") ? atoi(getenv("HP_C32_TILE")) : 0; // A/B switch: 1 = the largest tile, 2 = 64 x 128 at most
-    if (force == 1)
-        return;
-    if (force == 2) {
-        BM = 64;
-        return;
-    }
     const long blocks = (long)(((p.pick_npix > 0 ? p.pick_npix : p.npix) + 127) / 128) * (p.Cout_pad / BM);
     if (blocks < 448) // fewer than ~1.75 blocks per CU: quarter the tile
         BM = 64, BN = 64;
     else if (blocks < 1024 && BM == 128) // up to four blocks per CU: halve the tile (512 -> 512 at 8 x 46 x 54: 115 -> 100 us alone, same machine time)
         BM = 64;
     // Round quantisation: 64 x 128 tiles have 1024 slots (four blocks per CU); a layer that is "one round and a bit" of them but ONE round of
-    // 64 x 160 tiles takes conv32_t16_kernel<160> (see there).  HP_C32_BN160=0: the A/B switch back; =1: every layer (tests).  Read per launch.
-    const int bn160 = getenv("HP_C32_BN160") ? atoi(getenv("HP_C32_BN160")) : -1;
+    // 64 x 160 tiles takes conv32_t16_kernel<160> (see there).  HP_C32_BN160=0: the A/B switch back; =1: every layer (tests).
+    const int bn160 = sw.c32_bn160;
     if (bn160 == 1 || bn160 == 176) { // (tests: every layer on the 64 x 160 | 64 x 176 tile)
         BM = 64, BN = bn160 == 1 ? 160 : 176;
         return;
@@ -722,12 +715,12 @@ static bool conv32_rows(const conv32_params& p, int BN)
     return !p.out_f32 && (p.lane_epilogue < 0 || (p.lane_epilogue == 0 && BN == 64));
 }
 
-int conv32_tile(const conv32_params& p)
+int conv32_tile(const conv32_params& p, const engine_switches& sw)
 {
-    if (const int bn = conv32_wk_bn(p))
+    if (const int bn = conv32_wk_bn(p, sw))
         return 39000000 + p.Cin * 1000 + bn;
     int BM, BN;
-    conv32_pick(p, BM, BN);
+    conv32_pick(p, sw, BM, BN);
     return 32000000 + (conv32_rows(p, BN) ? 400000 : 0) + BM * 1000 + BN;
 }
 
@@ -755,16 +748,16 @@ bool set_act32(conv32_params& p)
     }
 }
 
-hipError_t launch_conv32(const conv32_params& p, hipStream_t s)
+hipError_t launch_conv32(const conv32_params& p, const engine_switches& sw, hipStream_t s)
 {
     if (p.Cin % 16 || p.Cout_pad % 64 || p.npix <= 0)
         return hipErrorInvalidValue;
-    if (const int bn = conv32_wk_bn(p)) {
+    if (const int bn = conv32_wk_bn(p, sw)) {
         const dim3 g(((p.npix + bn - 1) / bn + 7) / 8 * 8 * (p.Cout_pad / 64));
         return p.Cin == 32 ? launch_wk<32, 64>(p, g, s) : p.Cin == 64 ? launch_wk<64, 64>(p, g, s) : launch_wk<128, 64>(p, g, s);
     }
     int BM, BN;
-    conv32_pick(p, BM, BN);
+    conv32_pick(p, sw, BM, BN);
     const dim3 grid(((p.npix + BN - 1) / BN + 7) / 8 * 8 * (p.Cout_pad / BM)); // XCD-aware 1-D order: see conv32_kernel
     const bool rows = conv32_rows(p, BN);
 #define HP_C32_CASE(BM_, BN_, WM_, WN_)                                                    \
@@ -968,7 +961,7 @@ void first_conv32_verify_counts(unsigned out[4], bool reset)
     }
 }
 
-hipError_t launch_first_conv32(const first_conv32_params& p, hipStream_t s)
+hipError_t launch_first_conv32(const first_conv32_params& p, const engine_switches& sw, hipStream_t s)
 {
     const int G = (p.Cout + 7) / 8, GP = std::min(G, 32);
     const int TH = 256 / GP / 2; // two threads (of four pixels) per row of eight
@@ -977,7 +970,7 @@ hipError_t launch_first_conv32(const first_conv32_params& p, hipStream_t s)
     if (lds > 64 * 1024)
         return hipErrorInvalidValue;
     const int tiles_x = (p.OW + 7) / 8, tiles_y = (p.OH + TH - 1) / TH;
-    HP_LAUNCH(first_conv32_kernel, dim3(tiles_x * tiles_y * p.B), dim3(256), lds, s, p, tiles_x, tiles_y, TH, GP, getenv("HP_FIRST_CONV_VERIFY") ? 1 : 0);
+    HP_LAUNCH(first_conv32_kernel, dim3(tiles_x * tiles_y * p.B), dim3(256), lds, s, p, tiles_x, tiles_y, TH, GP, sw.first_conv_verify ? 1 : 0);
     return hipGetLastError();
 }
 
@@ -1100,13 +1093,13 @@ __global__ __launch_bounds__(256) void dwconv32_any_kernel(const dw32_params p)
     }
 }
 
-hipError_t launch_dwconv32(const dw32_params& p, hipStream_t s)
+hipError_t launch_dwconv32(const dw32_params& p, const engine_switches& sw, hipStream_t s)
 {
     if (p.C % 4)
         return hipErrorInvalidValue;
     // rows per thread: long runs re-use more, short runs give more threads; 8 keeps > 100 k threads on the 46 x 54 maps of LW-OpenPose
     const int run = p.OH >= 32 ? 8 : 4;
-    const int px_env = getenv("HP_DW32_PX") ? atoi(getenv("HP_DW32_PX")) : 0; // A/B switch and test hook: 1 = one column per thread always, 2 = pairs always (read per launch: tests toggle it)
+    const int px_env = sw.dw32_px; // A/B switch and test hook: 1 = one column per thread always, 2 = pairs always
     const bool pairs = px_env != 1;
     // column pairs where they still leave > 120 k threads.  LW-OpenPose @ 8 x 46 x 54, us alone | with a second stream, one column -> pairs: 512 channels
     // 24.4 | 19.5 -> 20.0 | 16.6, dilation 2 34.0 | 29.4 -> 27.1 | 22.3, 128 channels at 92 x 108 20.5 | 15.4 -> 17.6 | 14.8; 256 channels (83 k pair

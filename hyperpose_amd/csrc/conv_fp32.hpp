@@ -8,6 +8,7 @@
 // products; HP_DTYPE_F32S is the same engine with the dense products formed on the fp16 pipe (conv32_direct.hip, SPLIT).
 #pragma once
 #include "conv_kernels.hpp"
+#include "hp_common.hpp"
 
 namespace hp {
 
@@ -61,8 +62,8 @@ struct conv32_params {
 // fills act_slope / act_hi from act / act_param; false for activations the epilogue does not evaluate (sigmoid / softplus are output post-ops)
 bool set_act32(conv32_params& p);
 // Dense KH x KW convolution (any stride / dilation) as an implicit GEMM on v_mfma_f32_32x32x2_f32.
-hipError_t launch_conv32(const conv32_params& p, hipStream_t s);
-int conv32_tile(const conv32_params& p); // profile rows: 32000000 + 400000 (row-major epilogue) + BM * 1000 + BN; conv32_wk_kernel (1 x 1, 32 / 64 input channels, large maps): 39000000 + Cin * 1000 + pixels per block
+hipError_t launch_conv32(const conv32_params& p, const engine_switches& sw, hipStream_t s);
+int conv32_tile(const conv32_params& p, const engine_switches& sw); // profile rows: 32000000 + 400000 (row-major epilogue) + BM * 1000 + BN; conv32_wk_kernel (1 x 1, 32 / 64 input channels, large maps): 39000000 + Cin * 1000 + pixels per block
 // The barrier-free direct form for square 1 x 1 / 3 x 3, stride 1, dilation 1, SAME padding (conv32_direct.hip): a chunk's halo tile staged in LDS once
 // for all taps, weights in fragment order straight from L2.  split = false: exact fp32 products on v_mfma_f32_32x32x2_f32 (needs w_frag);
 // split = true: every fp32 product formed as three exact fp16 x fp16 products on the fp16 matrix pipe, x = hi + 2^-11 lo,
@@ -79,7 +80,7 @@ void conv32_frag_pack(const float* packed, int taps, int cout_pad, int cin, floa
 // Winograd F(2 x 2, 3 x 3) on the fp32 matrix pipe for 3 x 3, stride 1, dilation 1, SAME-padded layers with an NHWC output (conv32_winograd.hip):
 // 16 instead of 36 MFMA products per output tile and channel pair.  Needs w_wino (conv32_winograd_pack of the packed matrix).
 bool conv32_winograd_ok(const conv32_params& p);
-hipError_t launch_conv32_winograd(const conv32_params& p, hipStream_t s);
+hipError_t launch_conv32_winograd(const conv32_params& p, const engine_switches& sw, hipStream_t s);
 hipError_t conv32_winograd_occupancy(const conv32_params& p, int* blocks_per_cu);
 // Winograd F(3 x 3, 3 x 3) for the same layers (conv32_winograd3.hip): 25 products per 3 x 3 output tile and channel pair - 2.78 per pixel against 4.
 // Needs w_wino3 (conv32_winograd3_pack of the packed matrix: 25 * cout_pad * cin floats).
@@ -87,7 +88,7 @@ bool conv32_winograd3_ok(const conv32_params& p);
 hipError_t launch_conv32_winograd3(const conv32_params& p, hipStream_t s);
 int conv32_winograd3_tile(const conv32_params& p);
 void conv32_winograd3_pack(const float* packed, int cout_pad, int cin, float* out); // what the runtime grants this launch's kernel
-int conv32_winograd_tile(const conv32_params& p);     // profile rows: 35000000 + 3000 + wavefronts per block
+int conv32_winograd_tile(const conv32_params& p);     // profile rows: 35003004 (F(3 x 3, 3 x 3): conv32_winograd3_tile)
 double conv32_winograd_flops(const conv32_params& p); // the MFMA work of one launch: 2 * 16 * tiles * Cout * Cin
 void conv32_winograd_pack(const float* packed, int cout_pad, int cin, float* out); // [9][cout_pad][cin] -> 16 * cout_pad * cin floats
 
@@ -104,7 +105,7 @@ struct head32_hidden {
 bool conv32_head_ok(int k1, int hid, int c2);
 hipError_t launch_conv32_head(const conv32_params& q, const head32_hidden& h, hipStream_t s);
 // two heads that read the same tensor in one grid (LW-OpenPose's heat-map and PAF heads of a stage): same results, the blocks of both side by side
-bool conv32_head_pair_ok(const conv32_params& a, const conv32_params& b);
+bool conv32_head_pair_ok(const conv32_params& a, const conv32_params& b, const engine_switches& sw);
 hipError_t launch_conv32_head_pair(const conv32_params& qa, const head32_hidden& ha, const conv32_params& qb, const head32_hidden& hb, hipStream_t s);
 int conv32_head_tile(int hid, int c2); // profile rows: 37000000 + 100 * HID + C2
 void conv32_head_pack(const float* w2, int tm2, int hid, float* out);
@@ -124,7 +125,7 @@ struct first_conv32_params {
     tview32 out;
 };
 // The 3-channel network input (u8 HWC or f32 NCHW), pre-processing of src/data.cpp:21-51 folded into the load; all-fp32.
-hipError_t launch_first_conv32(const first_conv32_params& p, hipStream_t s);
+hipError_t launch_first_conv32(const first_conv32_params& p, const engine_switches& sw, hipStream_t s);
 void first_conv32_verify_counts(unsigned out[4], bool reset); // HP_FIRST_CONV_VERIFY=1: LDS words that differed from global memory (patch, weights), blocks checked
 
 struct dw32_params {
@@ -137,7 +138,7 @@ struct dw32_params {
     float act_param;
     tview32 out;
 };
-hipError_t launch_dwconv32(const dw32_params& p, hipStream_t s);
+hipError_t launch_dwconv32(const dw32_params& p, const engine_switches& sw, hipStream_t s);
 
 struct pool32_params {
     tview32 in;

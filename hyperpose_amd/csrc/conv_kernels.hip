@@ -3264,9 +3264,8 @@ template <int D, int CMAX>
 static hipError_t launch_sep_pipe(const sep_params& p, hipStream_t s)
 {
     const int tiles_x = (p.OW + 7) / 8, tiles_y = (p.OH + 11) / 12;
-    // the round-3 anti-phase form: A/B switch (HP_SEP_PIPE1=1) and the blocks with an odd number of 64-channel chunks
-    static const bool anti_phase = getenv("HP_SEP_PIPE1") != nullptr;
-    if (anti_phase || p.C % 128)
+    // the round-3 anti-phase form: the blocks with an odd number of 64-channel chunks
+    if (p.C % 128)
         HP_LAUNCH((sepconv_pipe_kernel<D, CMAX>), dim3(tiles_x * tiles_y * p.B), dim3(512), 0, s, p, tiles_x, tiles_y);
     else if (p.pw.res.p || p.pw.alpha || p.pw.act_slope != 0.f) // (no block of the built-in networks: the general epilogue after the last interval)
         HP_LAUNCH((sepconv_pipe3_kernel<D, false, false>), dim3(tiles_x * tiles_y * p.B), dim3(512), 0, s, p, tiles_x, tiles_y);
@@ -3687,10 +3686,7 @@ int sepconv_variant(const sep_params& p)
 
 hipError_t launch_sepconv(const sep_params& p, hipStream_t s)
 {
-    int v = sepconv_variant(p);
-    static const bool half_cu = getenv("HP_SEP_SLOT") != nullptr; // A/B switch: the half-CU forms of the 512-channel blocks
-    if (half_cu && (v == 5 || v == 6))
-        v += 10;
+    const int v = sepconv_variant(p);
     // <= 128 output channels at 64 / 128 input channels: ONE block of all channels (sepconv_small_kernel)
     if (p.pw.Cout <= 128) {
         if (v == 1 && p.C == 128)
@@ -3715,10 +3711,6 @@ hipError_t launch_sepconv(const sep_params& p, hipStream_t s)
         return launch_sep_pipe<1, 512>(p, s);
     case 6:
         return launch_sep_pipe<2, 512>(p, s);
-    case 15: // (the half-CU forms of 5 / 6: HP_SEP_SLOT=1, kept for the A/B in DESIGN.md section 7)
-        return launch_sep_slot<2, 2, 1, 1, 512>(p, s);
-    case 16:
-        return launch_sep_slot<2, 2, 1, 2, 512, 32>(p, s);
     default:
         return hipErrorInvalidValue;
     }
@@ -3956,10 +3948,9 @@ __device__ __forceinline__ void mlp_head_body(const head_params& p, int tiles_x,
 }
 
 // 0: no fused head kernel for this pair
-int mlp_head_variant(int k1, int hidden, int cout2)
+int mlp_head_variant(int k1, int hidden, int cout2, bool no_fuse_head)
 {
-    const int off = getenv("HP_NO_FUSE_HEAD") ? atoi(getenv("HP_NO_FUSE_HEAD")) : 0; // read per engine build (tests toggle it)
-    if (off || hidden != 512 || cout2 > 64 || cout2 < 1)
+    if (no_fuse_head || hidden != 512 || cout2 > 64 || cout2 < 1)
         return 0;
     return k1 == 64 ? 1 : k1 == 128 ? 2 : k1 == 256 ? 4 : 0;
 }
@@ -3981,8 +3972,8 @@ hipError_t launch_mlp_head_pair(const head_params& p0, const head_params& p1, hi
 {
     const int tiles_x = (p0.W + 7) / 8, tiles_y = (p0.H + 7) / 8;
     const dim3 grid(tiles_x * tiles_y * p0.B, 2);
-    const int v = mlp_head_variant(p0.K1, 512, p0.pw.Cout);
-    if (v == 0 || v != mlp_head_variant(p1.K1, 512, p1.pw.Cout) || p0.H != p1.H || p0.W != p1.W || p0.B != p1.B)
+    const int v = mlp_head_variant(p0.K1, 512, p0.pw.Cout, false);
+    if (v == 0 || v != mlp_head_variant(p1.K1, 512, p1.pw.Cout, false) || p0.H != p1.H || p0.W != p1.W || p0.B != p1.B)
         return hipErrorInvalidValue;
     switch (v) {
     case 1:
@@ -4002,7 +3993,7 @@ hipError_t launch_mlp_head(const head_params& p, hipStream_t s)
 {
     const int tiles_x = (p.W + 7) / 8, tiles_y = (p.H + 7) / 8;
     const dim3 grid(tiles_x * tiles_y * p.B);
-    switch (mlp_head_variant(p.K1, 512, p.pw.Cout)) {
+    switch (mlp_head_variant(p.K1, 512, p.pw.Cout, false)) {
     case 1:
         HP_LAUNCH((mlp_head_kernel<1>), grid, dim3(256), 0, s, p, tiles_x, tiles_y);
         break;

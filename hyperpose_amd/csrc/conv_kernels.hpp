@@ -154,7 +154,7 @@ struct head_params {
     const __half* w2;
     conv_params pw;
 };
-int mlp_head_variant(int k1, int hidden, int cout2);
+int mlp_head_variant(int k1, int hidden, int cout2, bool no_fuse_head); // no_fuse_head: HP_NO_FUSE_HEAD (the launchers pass false)
 hipError_t launch_mlp_head(const head_params& p, hipStream_t s);
 // two heads on the same input, same K1 / geometry, in one launch (blockIdx.y = head)
 hipError_t launch_mlp_head_pair(const head_params& p0, const head_params& p1, hipStream_t s);

@@ -106,10 +106,25 @@ struct step {
     float* i8_dq = nullptr;  // device [cp.Cout_pad]: s_a * s_w[c], rewritten by hp_engine::apply_int8_scales
     double flops = 0, bytes = 0; // per frame
 };
+struct geo { // a layer's output size and the padding in front of its first row / column
+    int OH, OW, pt, pl;
+};
+// what a layer's launch shares with the next layer's (hp_engine::fuse_next)
+enum class fuse_kind : char {
+    none,
+    sep,    // fp16: depthwise 3x3 + the 1x1 behind it in one sepconv launch
+    sep32,  // fp32: depthwise 3x3 fused into conv32_direct_kernel's load of the 1x1 behind it
+    head,   // fp16: 1x1 K1 -> 512 + 1x1 512 -> <= 64 in one mlp_head launch
+    head32, // fp32: 1x1 128 -> HID + 1x1 HID -> <= 64 in one conv32_head launch
+};
 constexpr int OP_SEPCONV = 100; // schedule-only op codes (not part of the hp_layer ABI)
 constexpr int OP_MLPHEAD = 101;
 constexpr int OP_CHAIN = 102;
 constexpr int OP_BNECK = 103;
+
+// element (m, k) of a K-wide fp16 matrix in MFMA fragment order: [32-row tile][16-wide k step][lane = (k % 16 / 8) * 32 + m % 32][k % 8],
+// KQ = K / 16 steps; tile0 = 32-row tiles in front of the matrix (a convolution's earlier taps)
+inline size_t frag16(size_t m, size_t k, size_t KQ, size_t tile0 = 0) { return (((tile0 + m / 32) * KQ + k / 16) * 64 + (k % 16 / 8) * 32 + m % 32) * 8 + k % 8; }
 
 void same_pad(int in, int k, int stride, int dil, int& out, int& pad_before)
 {
@@ -146,7 +161,7 @@ struct hp_engine {
     struct { const void* input = nullptr; size_t frame_bytes = 0; int n = 0, on_device = 0, kind = 0; void* stream = nullptr; } last; // the newest hp_engine_infer_* call
     bool split_overflowed() const { return dtype == HP_DTYPE_F32S && !split_off && ovf_flag.p && *static_cast<volatile unsigned*>(ovf_flag.p) != 0; }
     int leave_split(); // stop using conv32_direct_kernel: drop the captured graphs (they hold its launches), count the event
-    bool dbg_conv = false, dbg_bn = false, dbg_chain = false, dbg_sep = false; // HP_*_DBG block timelines, read once at creation
+    hp::engine_switches switches; // read_engine_switches() at hp_engine_create / hp_engine_load
     double factor = 1.0 / 255;
     int flip_rb = 1;
     float mean[3] = { 0, 0, 0 }, inv_std[3] = { 1, 1, 1 };
@@ -206,13 +221,87 @@ struct hp_engine {
     }
 
     int build(const hp_engine_desc* d);
+    // build's passes, in order (engine.cpp)
+    int validate_and_infer(const hp_engine_desc* d);
+    int mark_pair_fusions(const hp_engine_desc* d);
+    int bind_outputs(const hp_engine_desc* d);
+    int plan_activations();
+    int lower_layers();
+    int lower32(size_t i);
+    int lower16(size_t i);
+    int lower16_head_pair(size_t i);
+    int lower16_sep_pair(size_t i);
+    int plan_splitk();
+    int fuse_chains();
+    int fuse_bottlenecks();
+    int fuse_sep_pairs();
+    int pair_heads();
+    int finish(const hp_engine_desc* d);
+    // what the passes share
+    std::vector<geo> geos;           // per layer
+    std::vector<fuse_kind> fuse_next; // per layer: fused with the next layer (mark_pair_fusions)
+    unsigned* ovf_dev = nullptr;     // HP_DTYPE_F32S: device view of ovf_flag
+    // HP_NO_FUSE=1: one launch per layer.  An HP_DTYPE_I8 engine always runs that schedule: its fp16 layers are the kernels of the fp16 engine's
+    // per-layer plan, its int8 layers replace single launches of it
+    bool fuse_off() const { return dtype == HP_DTYPE_I8 || switches.no_fuse; }
+    bool tensor_is_read(int t) const; // some layer reads it (input or residual), or an un-fused output conversion will
+    const float* blob(int64_t off, size_t n, const char* what, size_t layer) const; // weights_blob[off, off + n), or nullptr + error
+    int upload(const void* src, size_t bytes, void** dst); // a new weight buffer holding src
     // host_src != nullptr (eager launches of a host batch): every range copies ITS frames to the device on ITS stream first (frame_bytes each)
     int enqueue(const uint8_t* u8, const float* f32, int n, hipStream_t s, const void* host_src = nullptr, size_t frame_bytes = 0);
     int run_step(step& st, const uint8_t* u8, const float* f32, int n, hipStream_t s, int b0 = 0);
+    int print_timeline(const step& st, const hp::conv32_params* q32, hipStream_t s); // HP_*_DBG block timelines of the step just launched (q32: an fp32 layer's launch)
+    int step_tile(const step& st) const; // hp_layer_time::tile: which kernel form the step launches (0: ops with one form)
+    int stage_profile_input();           // in_stage as the hp_engine_profile* calls' synthetic max_batch input
     int enqueue_range(const uint8_t* u8, const float* f32, int b0, int n, hipStream_t s);
 };
 
+bool hp_engine::tensor_is_read(int t) const
+{
+    for (const auto& L2 : layers)
+        if (L2.in == t || L2.res == t)
+            return true;
+    for (const auto& o : outputs)
+        if (o.tensor == t && o.fused_layer < 0)
+            return true;
+    return false;
+}
+
+const float* hp_engine::blob(int64_t off, size_t n, const char* what, size_t layer) const
+{
+    if (off < 0 || (size_t)off + n > weights_blob.size()) {
+        hp::set_error("layer %zu: %s range [%lld,+%zu) outside the %zu-float weight blob", layer, what, (long long)off, n, weights_blob.size());
+        return nullptr;
+    }
+    return weights_blob.data() + off;
+}
+
+int hp_engine::upload(const void* src, size_t bytes, void** dst)
+{
+    weight_bufs.push_back(std::make_unique<hp::dev_buf>());
+    HP_TRY(weight_bufs.back()->alloc(bytes));
+    HP_HIP_TRY(hipMemcpy(weight_bufs.back()->p, src, bytes, hipMemcpyHostToDevice));
+    *dst = weight_bufs.back()->p;
+    return HP_OK;
+}
+
 int hp_engine::build(const hp_engine_desc* d)
+{
+    HP_TRY(validate_and_infer(d)); // 1. the description, tensor shapes and halos
+    HP_TRY(mark_pair_fusions(d));  // 2. which consecutive layers run as one launch
+    HP_TRY(bind_outputs(d));       // 3. network outputs
+    HP_TRY(plan_activations());    // 4. activation memory
+    HP_TRY(lower_layers());        // 5. weights packed and uploaded, one step per layer or fused pair
+    // 6. the fp16 schedule rewrites (each a no-op on fp32 engines and under HP_NO_FUSE)
+    HP_TRY(plan_splitk());
+    HP_TRY(fuse_chains());
+    HP_TRY(fuse_bottlenecks());
+    HP_TRY(fuse_sep_pairs());
+    HP_TRY(pair_heads());
+    return finish(d);              // 7. streams, events, int8 scales
+}
+
+int hp_engine::validate_and_infer(const hp_engine_desc* d)
 {
     HP_REQUIRE(d->in_w > 0 && d->in_h > 0 && d->max_batch >= 1, HP_ERR_INVALID, "engine: bad input size / batch");
     HP_REQUIRE(d->layers && d->n_layers > 0 && d->weights, HP_ERR_INVALID, "engine: no layers / weights");
@@ -220,18 +309,11 @@ int hp_engine::build(const hp_engine_desc* d)
     HP_REQUIRE(d->dtype == HP_DTYPE_F16 || d->dtype == HP_DTYPE_F32 || d->dtype == HP_DTYPE_F32S || d->dtype == HP_DTYPE_I8, HP_ERR_INVALID,
         "engine: dtype %d is none of HP_DTYPE_F16 / HP_DTYPE_F32 / HP_DTYPE_F32S / HP_DTYPE_I8", d->dtype);
     dtype = d->dtype;
-    const bool f32 = is_f32();
-    // HP_NO_FUSE=1: one launch per layer.  An HP_DTYPE_I8 engine always runs that schedule: its fp16 layers are the kernels of the fp16 engine's
-    // per-layer plan, its int8 layers replace single launches of it
-    const bool no_fuse = dtype == HP_DTYPE_I8 || getenv("HP_NO_FUSE") != nullptr;
-    unsigned* ovf_dev = nullptr;
     if (dtype == HP_DTYPE_F32S) {
         HP_TRY(ovf_flag.alloc(64));
         memset(ovf_flag.p, 0, 64);
         HP_HIP_TRY(hipHostGetDevicePointer((void**)&ovf_dev, ovf_flag.p, 0));
     }
-    dbg_conv = getenv("HP_CONV_DBG") != nullptr, dbg_bn = getenv("HP_BN_DBG") != nullptr;
-    dbg_chain = getenv("HP_CHAIN_DBG") != nullptr, dbg_sep = getenv("HP_SEP_DBG") != nullptr;
     for (int c = 0; c < 3; ++c)
         mean[c] = d->mean[c], inv_std[c] = d->inv_std[c];
     layers.assign(d->layers, d->layers + d->n_layers);
@@ -269,10 +351,7 @@ int hp_engine::build(const hp_engine_desc* d)
     for (auto& t : tensors)
         t = std::make_unique<tensor_info>();
     tensors[0]->defined = true, tensors[0]->H = in_h, tensors[0]->W = in_w, tensors[0]->C = 3;
-    struct geo {
-        int OH, OW, pt, pl;
-    };
-    std::vector<geo> geos(layers.size());
+    geos.assign(layers.size(), geo{});
     for (size_t i = 0; i < layers.size(); ++i) {
         const hp_layer& L = layers[i];
         HP_REQUIRE(L.in >= 0 && L.in <= max_id && tensors[L.in]->defined, HP_ERR_INVALID, "layer %zu reads undefined tensor %d", i, L.in);
@@ -317,9 +396,16 @@ int hp_engine::build(const hp_engine_desc* d)
             tensors[L.in]->P = std::max({ tensors[L.in]->P, g.pt, g.pl, pb_y, pb_x });
         }
     }
+    return HP_OK;
+}
+
+int hp_engine::mark_pair_fusions(const hp_engine_desc* d)
+{
+    const bool f32 = is_f32();
+    const bool no_fuse = fuse_off();
+    fuse_next.assign(layers.size(), fuse_kind::none);
     // ---- separable blocks: a depthwise layer whose only consumer is the next layer, a plain 1x1 convolution, runs
     // as ONE launch (sepconv_kernel) and its output tensor is never materialised.  HP_NO_FUSE=1 keeps the two launches.
-    std::vector<char> fuse_with_next(layers.size(), 0);
     if (!no_fuse && !f32) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
@@ -354,7 +440,7 @@ int hp_engine::build(const hp_engine_desc* d)
             const int variant = hp::sepconv_variant_for(A.cin, cout_pad, A.stride, A.dil, Bn.cout);
             if (!variant || (Bn.cout <= 64 && variant != 7))
                 continue; // (<= 64 output channels idle half of the general fused kernels' wavefronts - slower than two launches - except in the dedicated 32-channel form)
-            fuse_with_next[i] = 1;
+            fuse_next[i] = fuse_kind::sep;
             tensors[A.out]->elided = true;
         }
     }
@@ -368,8 +454,7 @@ int hp_engine::build(const hp_engine_desc* d)
     // reads hidden under the chunk's 32 MFMAs, one barrier per chunk) - computed the depthwise tile once and still ran 161 us alone / 108 with
     // a second stream against 125 / 107 for the two launches (profiles/r05_ab_layers_f32_sep_kernel.txt): one block of eight wavefronts per CU
     // moves in step with its own barrier, where conv32_kernel's four independent blocks per CU fill each other's gaps.  Not adopted, removed.
-    std::vector<char> fuse32_with_next(layers.size(), 0);
-    if (f32 && !no_fuse && !getenv("HP_NO_FUSE32") && (dtype == HP_DTYPE_F32S || getenv("HP_FUSE32"))) {
+    if (f32 && !no_fuse && !switches.no_fuse32 && (dtype == HP_DTYPE_F32S || switches.fuse32)) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
             if (A.op != HP_OP_DWCONV || A.kh != 3 || A.kw != 3 || A.in == 0 || A.out_coff != 0 || A.in_coff % 4 || A.stride != 1 || (A.dil != 1 && A.dil != 2)
@@ -399,12 +484,11 @@ int hp_engine::build(const hp_engine_desc* d)
             // (an HP_DTYPE_F32S engine must also be able to run the block on the fp32 pipe: where it goes when a value leaves fp16's range)
             if (!hp::conv32_dw_fusable(q, false, A.dil) || (dtype == HP_DTYPE_F32S && !hp::conv32_dw_fusable(q, true, A.dil)))
                 continue;
-            fuse32_with_next[i] = 1;
+            fuse_next[i] = fuse_kind::sep32;
             tensors[A.out]->elided = true;
         }
     }
     // ---- two-layer heads: 1x1 K1 -> 512 (relu) whose only consumer is the next layer, a 1x1 512 -> <= 64 channels
-    std::vector<char> head_with_next(layers.size(), 0);
     if (!no_fuse && !f32) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
@@ -414,12 +498,12 @@ int hp_engine::build(const hp_engine_desc* d)
             if (Bn.op != HP_OP_CONV || Bn.kh != 1 || Bn.kw != 1 || Bn.stride != 1 || Bn.in != A.out || Bn.in_coff != 0 || Bn.cin != A.cout
                 || Bn.res >= 0 || Bn.out == A.out || Bn.act == HP_ACT_SIGMOID || Bn.act == HP_ACT_SOFTPLUS)
                 continue;
-            if (tensors[A.out]->C != A.cout || !hp::mlp_head_variant(A.cin, A.cout, Bn.cout))
+            if (tensors[A.out]->C != A.cout || !hp::mlp_head_variant(A.cin, A.cout, Bn.cout, switches.no_fuse_head))
                 continue;
             if (geos[i].OH != tensors[A.in]->H || geos[i].OW != tensors[A.in]->W || geos[i].pt || geos[i].pl || geos[i + 1].OH != geos[i].OH
                 || geos[i + 1].OW != geos[i].OW || geos[i + 1].pt || geos[i + 1].pl)
                 continue; // a padded 1x1 (ONNX pads) changes the map size: the fused head assumes it does not
-            if (i > 0 && fuse_with_next[i - 1])
+            if (i > 0 && (fuse_next[i - 1] == fuse_kind::sep))
                 continue; // already the pointwise half of a separable block
             bool sole = true;
             for (size_t j = 0; j < layers.size(); ++j)
@@ -430,14 +514,13 @@ int hp_engine::build(const hp_engine_desc* d)
                     sole = false;
             if (!sole)
                 continue;
-            head_with_next[i] = 1;
+            fuse_next[i] = fuse_kind::head;
             tensors[A.out]->elided = true;
         }
     }
     // ---- HP_DTYPE_F32: the same two-layer heads for conv32_head_kernel (1 x 1 128 -> HID, ReLU family, sole consumer a 1 x 1 HID -> <= 64
     // channels; the hidden tensor stays in registers).  HP_NO_FUSE=1 / HP_NO_HEAD32=1 keep two launches.
-    std::vector<char> head32_with_next(layers.size(), 0);
-    if (dtype == HP_DTYPE_F32 && !no_fuse && !getenv("HP_NO_HEAD32")) {
+    if (dtype == HP_DTYPE_F32 && !no_fuse && !switches.no_head32) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
             if (A.op != HP_OP_CONV || A.kh != 1 || A.kw != 1 || A.stride != 1 || A.in == 0 || A.res >= 0 || A.out_coff != 0 || A.in_coff % 4
@@ -451,7 +534,7 @@ int hp_engine::build(const hp_engine_desc* d)
             if (geos[i].OH != tensors[A.in]->H || geos[i].OW != tensors[A.in]->W || geos[i].pt || geos[i].pl || geos[i + 1].OH != geos[i].OH
                 || geos[i + 1].OW != geos[i].OW || geos[i + 1].pt || geos[i + 1].pl)
                 continue; // a padded 1x1 (ONNX pads) changes the map size: the fused head assumes it does not
-            if ((i > 0 && fuse32_with_next[i - 1]) || fuse32_with_next[i])
+            if ((i > 0 && (fuse_next[i - 1] == fuse_kind::sep32)) || (fuse_next[i] == fuse_kind::sep32))
                 continue;
             bool sole = true;
             for (size_t j = 0; j < layers.size(); ++j)
@@ -462,15 +545,20 @@ int hp_engine::build(const hp_engine_desc* d)
                     sole = false;
             if (!sole)
                 continue;
-            head32_with_next[i] = 1;
+            fuse_next[i] = fuse_kind::head32;
             tensors[A.out]->elided = true;
         }
     }
+    return HP_OK;
+}
+
+int hp_engine::bind_outputs(const hp_engine_desc* d)
+{
     // ---- outputs
     HP_REQUIRE(d->n_outputs >= 1 && d->outputs, HP_ERR_INVALID, "engine: no outputs");
     for (int i = 0; i < d->n_outputs; ++i) {
         const hp_output_desc& o = d->outputs[i];
-        HP_REQUIRE(o.tensor > 0 && o.tensor <= max_id && tensors[o.tensor]->defined, HP_ERR_INVALID, "output %d: bad tensor", i);
+        HP_REQUIRE(o.tensor > 0 && o.tensor < (int)tensors.size() && tensors[o.tensor]->defined, HP_ERR_INVALID, "output %d: bad tensor", i);
         const tensor_info& ti = *tensors[o.tensor];
         HP_REQUIRE(o.coff >= 0 && o.channels > 0 && o.coff + o.channels <= ti.C, HP_ERR_INVALID, "output %d: bad channel range", i);
         out_info oi;
@@ -507,15 +595,21 @@ int hp_engine::build(const hp_engine_desc* d)
             o.fused_layer = last;
     }
 
+    return HP_OK;
+}
+
+int hp_engine::plan_activations()
+{
+    const bool f32 = is_f32();
     // ---- activation memory.  fp16 engines: one zero-filled allocation per tensor.  fp32 engines: the arena (see hp_engine::arena).
     {
-        const bool use_arena = f32 && !getenv("HP_NO_ARENA");
+        const bool use_arena = f32 && !switches.no_arena;
         const int NL = (int)layers.size(), INF = NL + 1;
         std::vector<int> first(tensors.size(), INF), last(tensors.size(), -1);
         for (int i = 0; i < NL; ++i) {
             const hp_layer& L = layers[i];
             // the step a layer's reads happen in: the first half of a fused pair (depthwise / hidden head layer) runs inside the NEXT layer's launch
-            const int at = (fuse32_with_next[i] || head32_with_next[i]) ? i + 1 : i;
+            const int at = ((fuse_next[i] == fuse_kind::sep32) || (fuse_next[i] == fuse_kind::head32)) ? i + 1 : i;
             first[L.out] = std::min(first[L.out], i);
             last[L.out] = std::max(last[L.out], i);
             if (L.in > 0)
@@ -577,643 +671,658 @@ int hp_engine::build(const hp_engine_desc* d)
             }
         }
     }
+    return HP_OK;
+}
 
-    // a tensor some layer reads (input or residual), or that an un-fused output conversion will read
-    auto tensor_is_read = [&](int t) {
-        for (const auto& L2 : layers)
-            if (L2.in == t || L2.res == t)
-                return true;
-        for (const auto& o : outputs)
-            if (o.tensor == t && o.fused_layer < 0)
-                return true;
-        return false;
-    };
-
-    // ---- pass 2: pack weights, build the schedule
-    auto blob = [&](int64_t off, size_t n, const char* what, size_t layer) -> const float* {
-        if (off < 0 || (size_t)off + n > d->n_weights) {
-            hp::set_error("layer %zu: %s range [%lld,+%zu) outside the %zu-float weight blob", layer, what, (long long)off, n, d->n_weights);
-            return nullptr;
-        }
-        return d->weights + off;
-    };
-    auto upload = [&](const void* src, size_t bytes, void** dst) -> int {
-        weight_bufs.push_back(std::make_unique<hp::dev_buf>());
-        HP_TRY(weight_bufs.back()->alloc(bytes));
-        HP_HIP_TRY(hipMemcpy(weight_bufs.back()->p, src, bytes, hipMemcpyHostToDevice));
-        *dst = weight_bufs.back()->p;
-        return HP_OK;
-    };
-
+int hp_engine::lower_layers()
+{
     i8_sw.assign(layers.size(), {});
     for (size_t i = 0; i < layers.size(); ++i) {
         const hp_layer& L = layers[i];
-        const tensor_info& ti = *tensors[L.in];
-        tensor_info& to = *tensors[L.out];
-        const geo& g = geos[i];
-        step st;
-        st.layer = (int)i, st.op = L.op;
-        const double opix = (double)g.OH * g.OW;
-        if (f32) {
-            // ---- HP_DTYPE_F32: one fp32 launch per layer (conv_fp32.hip), weights uploaded as they are
-            st.f32 = true;
-            if (fuse32_with_next[i] || head32_with_next[i]) // the first half of a fused pair: described at the 1 x 1 layer that follows
-                continue;
-            const bool dw_in_front = i > 0 && fuse32_with_next[i - 1];
-            const bool head_in_front = i > 0 && head32_with_next[i - 1];
-            auto padded = [&](int64_t off, int n, int n_pad, const char* what, std::vector<float>& v) -> bool {
-                v.assign(n_pad, 0.f);
-                if (off < 0)
-                    return true;
-                const float* src = blob(off, n, what, i);
-                if (!src)
-                    return false;
-                std::copy(src, src + n, v.begin());
-                return true;
-            };
-            if (L.op == HP_OP_CONV && L.in == 0) {
-                HP_REQUIRE(L.cin == 3 && L.in_coff == 0, HP_ERR_INVALID, "layer %zu: the network input has 3 channels", i);
-                HP_REQUIRE(L.dil == 1 && L.res < 0 && L.act != HP_ACT_PRELU, HP_ERR_INVALID, "layer %zu: unsupported first-layer options", i);
-                const size_t nw = (size_t)L.cout * L.kh * L.kw * 3;
-                const float* w = blob(L.w_off, nw, "weights", i);
-                std::vector<float> bias;
-                if (!w || !padded(L.b_off, L.cout, round_up(L.cout, 8), "bias", bias))
-                    return HP_ERR_INVALID;
-                st.first = true;
-                auto& p = st.fp32;
-                p.factor = factor, p.flip_rb = flip_rb;
-                for (int c = 0; c < 3; ++c)
-                    p.mean[c] = mean[c], p.inv_std[c] = inv_std[c];
-                p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cout = L.cout, p.KH = L.kh, p.KW = L.kw, p.stride = L.stride;
-                p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
-                void *dw = nullptr, *db = nullptr;
-                HP_TRY(upload(w, nw * sizeof(float), &dw));
-                HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-                p.w = (const float*)dw, p.bias = (const float*)db;
-                p.out = to.view32(L.out_coff);
-                st.flops = 2.0 * opix * L.cout * L.kh * L.kw * 3;
-                st.bytes = (double)ti.H * ti.W * 3 + opix * L.cout * 4 + nw * 4;
-            } else if (L.op == HP_OP_CONV) {
-                const int cin_pad = round_up(L.cin, 16), cout_pad = round_up(L.cout, 64), taps = L.kh * L.kw;
-                // (behind a fused depthwise layer the tensor this layer "reads" is never materialised: what the kernel reads is the depthwise input)
-                const tensor_info& tsrc = (dw_in_front || head_in_front) ? *tensors[layers[i - 1].in] : ti;
-                const int src_coff = (dw_in_front || head_in_front) ? layers[i - 1].in_coff : L.in_coff;
-                HP_REQUIRE(src_coff % 4 == 0 && src_coff + (head_in_front ? layers[i - 1].cin : cin_pad) <= tsrc.cs, HP_ERR_INVALID,
-                    "layer %zu: channel slice [%d,+%d) not 4-aligned / exceeds the padded stride %d", i, src_coff, cin_pad, tsrc.cs);
-                const size_t nw = (size_t)L.cout * taps * L.cin;
-                const float* w = blob(L.w_off, nw, "weights", i);
-                std::vector<float> bias, alpha;
-                if (!w || !padded(L.b_off, L.cout, cout_pad, "bias", bias))
-                    return HP_ERR_INVALID;
-                auto& p = st.cp32;
-                p.alpha = nullptr;
-                if (L.act == HP_ACT_PRELU) {
-                    HP_REQUIRE(L.alpha_off >= 0, HP_ERR_INVALID, "layer %zu: PReLU without slopes", i);
-                    if (!padded(L.alpha_off, L.cout, cout_pad, "prelu slopes", alpha))
-                        return HP_ERR_INVALID;
-                    void* da = nullptr;
-                    HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
-                    p.alpha = (const float*)da;
-                }
-                std::vector<float> packed((size_t)taps * cout_pad * cin_pad, 0.f);
-                for (int co = 0; co < L.cout; ++co)
-                    for (int t = 0; t < taps; ++t)
-                        std::copy(w + ((size_t)co * taps + t) * L.cin, w + ((size_t)co * taps + t + 1) * L.cin, packed.begin() + ((size_t)t * cout_pad + co) * cin_pad);
-                void *dw = nullptr, *db = nullptr;
-                HP_TRY(upload(packed.data(), packed.size() * sizeof(float), &dw));
-                HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-                p.w = (const float*)dw, p.bias = (const float*)db;
-                p.in = ti.view32(L.in_coff);
-                p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cin = cin_pad, p.Cout = L.cout, p.Cout_pad = cout_pad;
-                p.KH = L.kh, p.KW = L.kw, p.stride = L.stride, p.dil = L.dil, p.pad_t = g.pt, p.pad_l = g.pl;
-                p.dw_w = nullptr, p.dw_dil = 0, p.dw_slope = 1.f, p.dw_hi = __builtin_huge_valf();
-                if (dw_in_front) { // conv32_direct_kernel's fused form: `in` is the depthwise layer's input, its weights ride along as [9][C] + [C]
-                    const hp_layer& D = layers[i - 1];
-                    const float* dwf = blob(D.w_off, (size_t)D.cin * 9, "weights", i - 1);
-                    std::vector<float> dbias;
-                    if (!dwf || !padded(D.b_off, D.cin, D.cin, "bias", dbias))
-                        return HP_ERR_INVALID;
-                    std::vector<float> dpack((size_t)10 * D.cin);
-                    for (int c = 0; c < D.cin; ++c) {
-                        for (int t = 0; t < 9; ++t)
-                            dpack[(size_t)t * D.cin + c] = dwf[(size_t)c * 9 + t];
-                        dpack[(size_t)9 * D.cin + c] = dbias[c];
-                    }
-                    void* ddw = nullptr;
-                    HP_TRY(upload(dpack.data(), dpack.size() * sizeof(float), &ddw));
-                    p.dw_w = (const float*)ddw, p.dw_dil = D.dil;
-                    p.dw_slope = D.act == HP_ACT_NONE ? 1.f : D.act == HP_ACT_LEAKY ? D.act_param : 0.f;
-                    p.dw_hi = D.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
-                    p.in = tensors[D.in]->view32(D.in_coff);
-                    st.layer = (int)i - 1, st.n_layers = 2;
-                }
-                p.act = L.act, p.act_param = L.act_param;
-                p.res = hp::tview32{ nullptr, 0, 0, 0, 0 }, p.res_before_act = L.res_before_act;
-                if (L.res >= 0)
-                    p.res = tensors[L.res]->view32(0);
-                p.out = to.view32(L.out_coff);
-                p.out_f32 = nullptr;
-                for (auto& o : outputs)
-                    if (o.fused_layer == (int)i)
-                        p.out_f32 = o.buf->as<float>();
-                if (p.out_f32 && !tensor_is_read(L.out) && tensors[L.out]->C == L.cout)
-                    p.out.p = nullptr, to.unwritten = true; // only the fp32 network output is wanted
-                HP_REQUIRE(hp::set_act32(p), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv (use an output post-op)", i, L.act);
-                p.B = max_batch, p.npix = p.pick_npix = max_batch * g.OH * g.OW;
-                p.w_split = nullptr, p.w_frag = nullptr, p.w_wino = nullptr, p.w_wino3 = nullptr, p.ovf = ovf_dev, p.dbg = nullptr;
-                p.lane_epilogue = getenv("HP_LANE_EPILOGUE") ? atoi(getenv("HP_LANE_EPILOGUE")) : 0; // (A/B switches are read per build: an in-process A/B compares two engines)
-                // The layers conv32_direct_kernel covers (square 1 x 1 / 3 x 3, stride 1, whole 32- / 64-channel chunks inside the buffer's
-                // channel stride) get their weights in fragment order as well: fp32 for HP_DTYPE_F32 (HP_NO_DIRECT32=1: the A/B switch back
-                // to conv32_kernel), fp16 (hi, lo) pairs for HP_DTYPE_F32S; the others stay on conv32_kernel
-                // fp32 pipe, measured per layer of LW-OpenPose @ 8 x 46 x 54 (conv32_kernel -> direct, us alone | with a second stream): 3 x 3 128 -> 128
-                // 72.2 -> 58.7 | 52.6 -> 48.9; the 1 x 1 heads 512 -> 19 / 38 27.9 / 29.3 -> 26.1 / 27.4 | 18.8 / 19.6 -> 17.9 / 18.2; every wider 1 x 1
-                // layer within +-3 % or worse (64 -> 128 22.9 -> 29.0 paired, 512 -> 512 100 -> 100 alone): 1 x 1 layers wider than 64 padded outputs
-                // stay on conv32_kernel (HP_DIRECT32_MAX_1X1 moves the limit, HP_NO_DIRECT32=1 is the A/B switch)
-                const bool no_direct = getenv("HP_NO_DIRECT32") != nullptr;
-                const int direct_max_1x1 = getenv("HP_DIRECT32_MAX_1X1") ? atoi(getenv("HP_DIRECT32_MAX_1X1")) : 64;
-                // (a 3 x 3 layer the Winograd kernel will take needs no direct-form fragments: they doubled its weight bytes in HBM)
-                const bool wino_takes_it = dtype == HP_DTYPE_F32 && !dw_in_front && !getenv("HP_NO_WINOGRAD32") && hp::conv32_winograd_ok(p) && !head_in_front;
-                // HP_SPLIT_LAYERS="lo hi" (diagnostic, section 7B.8): an HP_DTYPE_F32S engine forms split products in layers lo .. hi only, every other
-                // dense layer runs conv32_kernel
-                bool split_here = dtype == HP_DTYPE_F32S;
-                if (const char* sl = getenv("HP_SPLIT_LAYERS")) {
-                    int lo = 0, hi = 1 << 30;
-                    sscanf(sl, "%d %d", &lo, &hi);
-                    split_here = split_here && ((int)i >= lo && (int)i <= hi);
-                }
-                if (split_here || dw_in_front || (dtype != HP_DTYPE_F32S && !no_direct && !wino_takes_it && (taps > 1 || cout_pad <= direct_max_1x1))) {
-                    const int ck = taps == 1 ? 64 : 32, cin_s = round_up(L.cin, ck);
-                    hp::conv32_params q = p;
-                    q.Cin = cin_s;
-                    HP_REQUIRE(!dw_in_front || (src_coff + cin_s <= tsrc.cs && hp::conv32_direct_ok(q)), HP_ERR_STATE,
-                        "layer %zu: fused behind a depthwise layer but not a direct-kernel layer (engine bug)", i);
-                    if (src_coff + cin_s <= tsrc.cs && hp::conv32_direct_ok(q)) {
-                        std::vector<float> wide((size_t)taps * cout_pad * cin_s, 0.f);
-                        for (int t = 0; t < taps; ++t)
-                            for (int co = 0; co < cout_pad; ++co)
-                                std::copy(packed.begin() + ((size_t)t * cout_pad + co) * cin_pad, packed.begin() + ((size_t)t * cout_pad + co) * cin_pad + cin_pad,
-                                    wide.begin() + ((size_t)t * cout_pad + co) * cin_s);
-                        void* dws = nullptr;
-                        if (dtype == HP_DTYPE_F32S) {
-                            // (a BN-folded weight beyond fp16's range has no (hi, lo) split - hi would be inf - and the run-time flag only watches
-                            // activations: such an engine starts on the fp32 pipe.  ADVICE r5)
-                            for (float v : wide)
-                                if (!(std::fabs(v) <= 65504.f) && !split_off)
-                                    split_off = true, ++split_fallbacks;
-                            std::vector<_Float16> ws(wide.size() * 2);
-                            hp::conv32_split_pack(wide.data(), taps, cout_pad, cin_s, ws.data());
-                            HP_TRY(upload(ws.data(), ws.size() * sizeof(_Float16), &dws));
-                            p.w_split = (const _Float16*)dws;
-                        }
-                        // (an HP_DTYPE_F32S engine keeps the fp32 fragments too: what it runs after a value left fp16's range)
-                        std::vector<float> wf(wide.size());
-                        hp::conv32_frag_pack(wide.data(), taps, cout_pad, cin_s, wf.data());
-                        HP_TRY(upload(wf.data(), wf.size() * sizeof(float), &dws));
-                        p.w_frag = (const float*)dws;
-                        st.cin_split = cin_s;
-                    }
-                }
-                st.flops = 2.0 * opix * L.cout * taps * L.cin;
-                st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cout * 4 + (double)nw * 4;
-                // HP_DTYPE_F32: 3 x 3 stride-1 layers in Winograd's F(2 x 2, 3 x 3) form - 16 MFMA products per 2 x 2 output tile and channel pair
-                // instead of 36 (conv32_winograd.hip; HP_NO_WINOGRAD32=1 is the A/B switch back to the direct kernel).  The step's `flops` stay the
-                // layer's ALGORITHMIC count (the direct form's 2 * 9 * Cin * Cout per pixel); the MFMA work issued is 16 / 36 of it (bench.py reports both).
-                if (dtype == HP_DTYPE_F32 && !dw_in_front && !getenv("HP_NO_WINOGRAD32") && hp::conv32_winograd_ok(p)) {
-                    std::vector<float> wu((size_t)16 * cout_pad * cin_pad);
-                    hp::conv32_winograd_pack(packed.data(), cout_pad, cin_pad, wu.data());
-                    void* dwu = nullptr;
-                    HP_TRY(upload(wu.data(), wu.size() * sizeof(float), &dwu));
-                    p.w_wino = (const float*)dwu;
-                    st.wino = true;
-                    st.bytes += (double)nw * 4 * (16.0 / 9 - 1);
-                    // ... or, opt-in (HP_WINO_F33=1, read per engine), F(3 x 3, 3 x 3): 25 products per 3 x 3 tile - 1.44 x fewer MFMA cycles, same accuracy
-                    // (conv32_winograd3.hip).  Measured: it wins where its 24 x 6-pixel blocks tile the map exactly and the layer is mid-sized (256 -> 256
-                    // at 32 x 24 x 24: 121 -> 87 us) and loses everywhere else - LW-OpenPose's 128 -> 128 at 8 x 46 x 54 48.6 | 28.6 us alone | paired against
-                    // 45.0 (35.9 in 8 x 8 blocks) | 27.0, every layer of PifPaf's 97 / 49 / 25-row maps - because one 16-tile column per wavefront streams
-                    // 3.1 x the U bytes per output pixel.  Not the default: taken by itself only on PoseProposal's exactly tiled 48 x 48 / 24 x 24
-                    // stages it made configs[3] 0.6 % faster (4 353 -> 4 380 frames/s resident, two runs each) - not worth a second numeric path.
-                    const bool f33 = getenv("HP_WINO_F33") && atoi(getenv("HP_WINO_F33")) == 1;
-                    if (f33 && hp::conv32_winograd3_ok(p)) {
-                        std::vector<float> wu3((size_t)25 * cout_pad * cin_pad);
-                        hp::conv32_winograd3_pack(packed.data(), cout_pad, cin_pad, wu3.data());
-                        void* dwu3 = nullptr;
-                        HP_TRY(upload(wu3.data(), wu3.size() * sizeof(float), &dwu3));
-                        p.w_wino3 = (const float*)dwu3;
-                        st.bytes += (double)nw * 4 * (25.0 / 9 - 16.0 / 9);
-                    }
-                }
-                if (dw_in_front) // + the depthwise taps; the tensor between the two layers costs no bytes any more
-                    st.flops += 2.0 * opix * L.cin * 9, st.bytes += (double)L.cin * 10 * 4;
-                if (head_in_front) { // conv32_head_kernel: this layer's epilogue + the hidden layer in front of it
-                    const hp_layer& A = layers[i - 1];
-                    const size_t nwa = (size_t)A.cout * A.cin;
-                    const float* wa = blob(A.w_off, nwa, "weights", i - 1);
-                    std::vector<float> biasa;
-                    if (!wa || !padded(A.b_off, A.cout, A.cout, "bias", biasa))
-                        return HP_ERR_INVALID;
-                    std::vector<float> w1f(nwa), w2p((size_t)cout_pad * L.cin, 0.f), w2f;
-                    hp::conv32_frag_pack(wa, 1, A.cout, A.cin, w1f.data()); // ([1][HID][128] is the blob's own layout: HID rows of 128)
-                    const int tm2 = L.cout <= 32 ? 1 : 2;
-                    std::copy(w, w + nw, w2p.begin()); // [cout][HID] rows, zero rows up to 32 tm2
-                    w2f.resize((size_t)32 * tm2 * L.cin);
-                    hp::conv32_head_pack(w2p.data(), tm2, L.cin, w2f.data());
-                    void *d1 = nullptr, *db1 = nullptr, *d2 = nullptr;
-                    HP_TRY(upload(w1f.data(), w1f.size() * sizeof(float), &d1));
-                    HP_TRY(upload(biasa.data(), biasa.size() * sizeof(float), &db1));
-                    HP_TRY(upload(w2f.data(), w2f.size() * sizeof(float), &d2));
-                    st.hh.w1_frag = (const float*)d1, st.hh.bias1 = (const float*)db1, st.hh.w2_frag = (const float*)d2, st.hh.HID = A.cout;
-                    st.hh.slope1 = A.act == HP_ACT_NONE ? 1.f : A.act == HP_ACT_LEAKY ? A.act_param : 0.f;
-                    st.hh.hi1 = A.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
-                    p.in = tsrc.view32(src_coff);
-                    st.head32 = true, st.wino = false, st.cin_split = 0;
-                    st.layer = (int)i - 1, st.n_layers = 2;
-                    st.flops = 2.0 * opix * ((double)A.cout * A.cin + (double)L.cout * L.cin);
-                    st.bytes = (double)tsrc.H * tsrc.W * A.cin * 4 + opix * L.cout * 4 + (double)(nwa + nw) * 4;
-                }
-            } else if (L.op == HP_OP_DWCONV) {
-                HP_REQUIRE(L.kh == 3 && L.kw == 3, HP_ERR_INVALID, "layer %zu: depthwise kernels are 3x3", i);
-                HP_REQUIRE(L.cin % 4 == 0 && L.in_coff % 4 == 0 && L.out_coff % 4 == 0, HP_ERR_INVALID, "layer %zu: depthwise needs 4-aligned channels", i);
-                // (the fp16 path refuses the same set, set_act: a PReLU here would silently run as ReLU - there are no slopes in dw32_params)
-                HP_REQUIRE(L.act != HP_ACT_PRELU && L.act != HP_ACT_SIGMOID && L.act != HP_ACT_SOFTPLUS && L.res < 0, HP_ERR_INVALID,
-                    "layer %zu: activation %d / a residual on a depthwise layer is not supported", i, L.act);
-                const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
-                std::vector<float> bias;
-                if (!w || !padded(L.b_off, L.cin, L.cin, "bias", bias))
-                    return HP_ERR_INVALID;
-                std::vector<float> packed((size_t)9 * L.cin);
-                for (int c = 0; c < L.cin; ++c)
-                    for (int t = 0; t < 9; ++t)
-                        packed[(size_t)t * L.cin + c] = w[(size_t)c * 9 + t];
-                auto& p = st.dp32;
-                void *dw = nullptr, *db = nullptr;
-                HP_TRY(upload(packed.data(), packed.size() * sizeof(float), &dw));
-                HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-                p.w = (const float*)dw, p.bias = (const float*)db;
-                p.in = ti.view32(L.in_coff);
-                p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.stride = L.stride, p.dil = L.dil;
-                p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
-                p.out = to.view32(L.out_coff);
-                st.flops = 2.0 * opix * L.cin * 9;
-                st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cin * 4;
-            } else { // max-pool / up-sampling
-                HP_REQUIRE(L.cin % 4 == 0 && L.in_coff % 4 == 0 && L.out_coff % 4 == 0 && (L.op == HP_OP_UPSAMPLE || L.kh == L.kw), HP_ERR_INVALID,
-                    "layer %zu: pooling / up-sampling needs 4-aligned channels and a square window", i);
-                auto& p = st.pp32;
-                p.in = ti.view32(L.in_coff);
-                p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.k = L.kh, p.stride = L.stride;
-                p.pad_t = L.op == HP_OP_UPSAMPLE ? 0 : g.pt, p.pad_l = L.op == HP_OP_UPSAMPLE ? 0 : g.pl;
-                p.out = to.view32(L.out_coff);
-                st.flops = 0;
-                st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cin * 4;
-            }
-            steps.push_back(st);
-            continue;
-        }
-        if (L.op == HP_OP_CONV && L.in == 0) {
-            HP_REQUIRE(L.cin == 3 && L.in_coff == 0, HP_ERR_INVALID, "layer %zu: the network input has 3 channels", i);
-            HP_REQUIRE(L.dil == 1 && L.res < 0 && L.act != HP_ACT_PRELU, HP_ERR_INVALID, "layer %zu: unsupported first-layer options", i);
-            const size_t nw = (size_t)L.cout * L.kh * L.kw * 3;
-            const float* w = blob(L.w_off, nw, "weights", i);
-            if (!w)
-                return HP_ERR_INVALID;
-            std::vector<float> bias(round_up(L.cout, 8), 0.f);
-            if (L.b_off >= 0) {
-                const float* b = blob(L.b_off, L.cout, "bias", i);
-                if (!b)
-                    return HP_ERR_INVALID;
-                std::copy(b, b + L.cout, bias.begin());
-            }
-            st.first = true;
-            auto& p = st.fp;
-            p.factor = factor, p.flip_rb = flip_rb;
-            for (int c = 0; c < 3; ++c)
-                p.mean[c] = mean[c], p.inv_std[c] = inv_std[c];
-            p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cout = L.cout, p.KH = L.kh, p.KW = L.kw, p.stride = L.stride;
-            p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
-            void* dw = nullptr;
-            void* db = nullptr;
-            HP_TRY(upload(w, nw * sizeof(float), &dw));
-            HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-            p.w = (const float*)dw, p.bias = (const float*)db;
-            p.w16 = nullptr;
-            if (L.kh == L.kw && (L.kh == 3 || L.kh == 7) && L.cout % 8 == 0 && L.cout <= 64) {
-                // fragment order of first_conv_f16_kernel: kernel rows padded to ROWP (a multiple of 8), K' = KS * ROWP in steps of 16
-                const int KS = L.kh, ROWP = (KS * 3 + 7) / 8 * 8, KP = KS * ROWP, STEPS = (KP + 15) / 16, MT = L.cout <= 32 ? 1 : 2;
-                std::vector<__half> w16((size_t)MT * STEPS * 64 * 8, __float2half(0.f));
-                for (int co = 0; co < L.cout; ++co)
-                    for (int ky = 0; ky < KS; ++ky)
-                        for (int r = 0; r < KS * 3; ++r) {
-                            const int k = ky * ROWP + r, st = k / 16, hh = (k % 16) / 8, e = k % 8;
-                            w16[((((size_t)(co / 32) * STEPS + st) * 64) + hh * 32 + co % 32) * 8 + e] = __float2half(w[((size_t)co * KS + ky) * KS * 3 + r]);
-                        }
-                void* d16 = nullptr;
-                HP_TRY(upload(w16.data(), w16.size() * sizeof(__half), &d16));
-                p.w16 = (const __half*)d16;
-            }
-            p.out = to.view(L.out_coff);
-            st.flops = 2.0 * opix * L.cout * L.kh * L.kw * 3;
-            st.bytes = (double)ti.H * ti.W * 3 + opix * L.cout * 2 + nw * 4;
-        } else if (L.op == HP_OP_CONV && head_with_next[i]) {
-            const hp_layer& Pn = layers[i + 1];
-            tensor_info& tp = *tensors[Pn.out];
-            const int K1 = L.cin, KQ1 = K1 / 16, HID = L.cout;
-            const float* w1f = blob(L.w_off, (size_t)HID * K1, "weights", i);
-            const float* w2f = blob(Pn.w_off, (size_t)Pn.cout * HID, "weights", i + 1);
-            if (!w1f || !w2f)
-                return HP_ERR_INVALID;
-            std::vector<__half> w1p((size_t)HID * K1), w2p((size_t)64 * HID, __float2half(0.f));
-            for (int m = 0; m < HID; ++m)
-                for (int k = 0; k < K1; ++k)
-                    w1p[((((size_t)(m / 32) * KQ1 + k / 16) * 64) + (k % 16 / 8) * 32 + m % 32) * 8 + k % 8] = __float2half(w1f[(size_t)m * K1 + k]);
-            for (int m = 0; m < Pn.cout; ++m)
-                for (int c = 0; c < HID; ++c) {
-                    const int wv = c / 128, ii = (c % 128) / 32, r32 = c % 32;
-                    const int hh = (r32 >> 2) & 1, r = (r32 & 3) + 4 * (r32 >> 3), ss = r >> 3, ee = r & 7;
-                    w2p[((((size_t)(m / 32) * 32 + 8 * wv + 2 * ii + ss) * 64) + hh * 32 + m % 32) * 8 + ee] = __float2half(w2f[(size_t)m * HID + c]);
-                }
-            std::vector<float> b1(HID, 0.f), b2(64, 0.f), alpha;
-            if (L.b_off >= 0) {
-                const float* bb = blob(L.b_off, HID, "bias", i);
-                if (!bb)
-                    return HP_ERR_INVALID;
-                std::copy(bb, bb + HID, b1.begin());
-            }
-            if (Pn.b_off >= 0) {
-                const float* bb = blob(Pn.b_off, Pn.cout, "bias", i + 1);
-                if (!bb)
-                    return HP_ERR_INVALID;
-                std::copy(bb, bb + Pn.cout, b2.begin());
-            }
-            st.op = OP_MLPHEAD, st.n_layers = 2; // (covers layers i and i + 1: the passes below must see every layer a step touches)
-            auto& p = st.hp_;
-            void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-            HP_TRY(upload(w1p.data(), w1p.size() * sizeof(__half), &d0));
-            HP_TRY(upload(b1.data(), b1.size() * sizeof(float), &d1));
-            HP_TRY(upload(w2p.data(), w2p.size() * sizeof(__half), &d2));
-            HP_TRY(upload(b2.data(), b2.size() * sizeof(float), &d3));
-            p.in = ti.view(L.in_coff);
-            p.H = ti.H, p.W = ti.W, p.K1 = K1;
-            p.w1 = (const __half*)d0, p.b1 = (const float*)d1, p.w2 = (const __half*)d2;
-            p.hi1 = L.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
-            auto& q = p.pw;
-            q.w = nullptr, q.w_layout = 0, q.bias = (const float*)d3, q.alpha = nullptr;
-            if (Pn.act == HP_ACT_PRELU) {
-                alpha.assign(64, 0.f);
-                const float* a = blob(Pn.alpha_off, Pn.cout, "prelu slopes", i + 1);
-                if (!a)
-                    return HP_ERR_INVALID;
-                std::copy(a, a + Pn.cout, alpha.begin());
-                void* da = nullptr;
-                HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
-                q.alpha = (const float*)da;
-            }
-            q.H = ti.H, q.W = ti.W, q.OH = ti.H, q.OW = ti.W, q.Cin = HID, q.Cout = Pn.cout, q.Cout_pad = 64;
-            q.KH = q.KW = 1, q.stride = 1, q.dil = 1, q.pad_t = q.pad_l = 0;
-            q.act = Pn.act, q.act_param = Pn.act_param;
-            q.res = hp::tview{ nullptr, 0, 0, 0, 0 }, q.res_before_act = 0;
-            q.out = tp.view(Pn.out_coff);
-            q.out_f32 = nullptr, q.dbg = nullptr;
-            for (auto& o : outputs)
-                if (o.fused_layer == (int)i + 1)
-                    q.out_f32 = o.buf->as<float>();
-            if (q.out_f32 && !tensor_is_read(Pn.out))
-                q.out.p = nullptr, tp.unwritten = true; // only the fp32 network output is wanted
-            HP_REQUIRE(hp::set_act(q), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv", i + 1, Pn.act);
-            st.flops = 2.0 * opix * HID * K1 + 2.0 * opix * Pn.cout * HID;
-            st.bytes = (double)ti.H * ti.W * K1 * 2 + opix * Pn.cout * 2 + ((double)HID * K1 + (double)Pn.cout * HID) * 2;
-            steps.push_back(st);
+        if (is_f32()) {
+            HP_TRY(lower32(i));
+        } else if (L.op == HP_OP_CONV && L.in != 0 && fuse_next[i] == fuse_kind::head) {
+            HP_TRY(lower16_head_pair(i));
             ++i; // the second convolution is part of this step
-            continue;
-        } else if (L.op == HP_OP_CONV) {
-            const int cin_pad = round_up(L.cin, 32);
-            HP_REQUIRE(L.in_coff % 8 == 0 && L.in_coff + cin_pad <= ti.cs, HP_ERR_INVALID,
-                "layer %zu: channel slice [%d,+%d) not 8-aligned / exceeds the padded stride %d", i, L.in_coff, cin_pad, ti.cs);
-            const int cout_pad = L.cout > 64 ? round_up(L.cout, 128) : 64;
-            const int taps = L.kh * L.kw;
-            const size_t nw = (size_t)L.cout * taps * L.cin;
-            const float* w = blob(L.w_off, nw, "weights", i);
-            if (!w)
-                return HP_ERR_INVALID;
-            std::vector<float> bias(cout_pad, 0.f), alpha;
-            if (L.b_off >= 0) {
-                const float* b = blob(L.b_off, L.cout, "bias", i);
-                if (!b)
-                    return HP_ERR_INVALID;
-                std::copy(b, b + L.cout, bias.begin());
-            }
-            auto& p = st.cp;
-            void* dw = nullptr;
-            void* db = nullptr;
-            HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-            p.w = nullptr, p.w_layout = 0, p.bias = (const float*)db, p.alpha = nullptr;
-            if (L.act == HP_ACT_PRELU) {
-                alpha.assign(cout_pad, 0.f);
-                const float* a = blob(L.alpha_off, L.cout, "prelu slopes", i);
-                if (!a)
-                    return HP_ERR_INVALID;
-                std::copy(a, a + L.cout, alpha.begin());
-                void* da = nullptr;
-                HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
-                p.alpha = (const float*)da;
-            }
-            p.in = ti.view(L.in_coff);
-            p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cin = cin_pad, p.Cout = L.cout, p.Cout_pad = cout_pad;
-            p.KH = L.kh, p.KW = L.kw, p.stride = L.stride, p.dil = L.dil, p.pad_t = g.pt, p.pad_l = g.pl;
-            p.act = L.act, p.act_param = L.act_param;
-            p.res = hp::tview{ nullptr, 0, 0, 0, 0 }, p.res_before_act = L.res_before_act;
-            if (L.res >= 0)
-                p.res = tensors[L.res]->view(0);
-            p.out = to.view(L.out_coff);
-            p.out_f32 = nullptr;
-            p.dbg = nullptr;
-            for (auto& o : outputs)
-                if (o.fused_layer == (int)i)
-                    p.out_f32 = o.buf->as<float>();
-            if (p.out_f32 && !tensor_is_read(L.out) && tensors[L.out]->C == L.cout)
-                p.out.p = nullptr, to.unwritten = true; // only the fp32 network output is wanted
-            HP_REQUIRE(hp::set_act(p), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv (use an output post-op)", i, L.act);
-            // weights: the launcher says which packing its kernel for this shape reads
-            p.B = max_batch, p.npix = max_batch * g.OH * g.OW;
-            p.w_layout = hp::conv_weight_layout(p);
-            std::vector<__half> packed((size_t)taps * cout_pad * cin_pad, __float2half(0.f));
-            const int KQ = cin_pad / 16;
-            for (int co = 0; co < L.cout; ++co)
-                for (int t = 0; t < taps; ++t)
-                    for (int ci = 0; ci < L.cin; ++ci) {
-                        const size_t at = p.w_layout == 1
-                            ? ((((size_t)t * (cout_pad / 32) + co / 32) * KQ + ci / 16) * 64 + (ci % 16 / 8) * 32 + co % 32) * 8 + ci % 8
-                            : ((size_t)t * cout_pad + co) * cin_pad + ci;
-                        packed[at] = __float2half(w[((size_t)co * taps + t) * L.cin + ci]);
-                    }
-            HP_TRY(upload(packed.data(), packed.size() * sizeof(__half), &dw));
-            p.w = (const __half*)dw;
-            st.flops = 2.0 * opix * L.cout * taps * L.cin;
-            st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cout * 2 + (double)nw * 2;
-            if (dtype == HP_DTYPE_I8 && hp::conv_i8_ok(L.kh, L.kw, L.stride, L.dil)) {
-                // int8 weights, symmetric per output channel: s_w[c] = max |w| / 127 (1 for an all-zero channel), q_w = clamp(rint(w / s_w[c]), -127, 127)
-                // in fp32, round-half-even; rows [tap][Cout_pad][Cin_pad] as conv_i8_kernel reads them
-                std::vector<float> sw(L.cout);
-                std::vector<int8_t> wq((size_t)taps * cout_pad * cin_pad, 0);
-                for (int co = 0; co < L.cout; ++co) {
-                    const float* wc = w + (size_t)co * taps * L.cin;
-                    float m = 0.f;
-                    for (size_t k = 0; k < (size_t)taps * L.cin; ++k)
-                        m = std::max(m, std::fabs(wc[k]));
-                    const float sc = m > 0.f ? m / 127.f : 1.f;
-                    sw[co] = sc;
-                    for (int t = 0; t < taps; ++t)
-                        for (int ci = 0; ci < L.cin; ++ci)
-                            wq[((size_t)t * cout_pad + co) * cin_pad + ci] = (int8_t)std::min(std::max(std::rint(wc[(size_t)t * L.cin + ci] / sc), -127.f), 127.f);
-                }
-                void *dq = nullptr, *dd = nullptr;
-                HP_TRY(upload(wq.data(), wq.size(), &dq));
-                const std::vector<float> zeros(cout_pad, 0.f);
-                HP_TRY(upload(zeros.data(), zeros.size() * sizeof(float), &dd));
-                st.i8 = true, st.q8.w = (const int8_t*)dq, st.q8.dq = (const float*)dd, st.i8_dq = (float*)dd, st.q8.inv_a = 0.f;
-                st.q8.w_direct = nullptr;
-                if (hp::conv_i8_direct_ok(p)) { // the same q_w in conv_i8_direct_kernel's fragment order
-                    std::vector<int8_t> wd(wq.size(), 0);
-                    for (int t = 0; t < taps; ++t)
-                        for (int co = 0; co < cout_pad; ++co)
-                            for (int ci = 0; ci < cin_pad; ++ci)
-                                wd[hp::conv_i8_direct_index(t, co, ci, cin_pad, cout_pad)] = wq[((size_t)t * cout_pad + co) * cin_pad + ci];
-                    void* dd2 = nullptr;
-                    HP_TRY(upload(wd.data(), wd.size(), &dd2));
-                    st.q8.w_direct = (const int8_t*)dd2;
-                }
-                i8_sw[i] = std::move(sw);
-            }
-        } else if (L.op == HP_OP_DWCONV && fuse_with_next[i]) {
-            const hp_layer& Pn = layers[i + 1];
-            tensor_info& tp = *tensors[Pn.out];
-            const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
-            if (!w)
-                return HP_ERR_INVALID;
-            std::vector<__half> dpacked((size_t)9 * L.cin);
-            for (int c = 0; c < L.cin; ++c)
-                for (int t = 0; t < 9; ++t)
-                    dpacked[(size_t)t * L.cin + c] = __float2half(w[(size_t)c * 9 + t]);
-            std::vector<float> dbias(L.cin, 0.f);
-            if (L.b_off >= 0) {
-                const float* b = blob(L.b_off, L.cin, "bias", i);
-                if (!b)
-                    return HP_ERR_INVALID;
-                std::copy(b, b + L.cin, dbias.begin());
-            }
-            const int C = L.cin, KQ = C / 16, cout_pad = round_up(Pn.cout, 128);
-            const float* pwf = blob(Pn.w_off, (size_t)Pn.cout * C, "weights", i + 1);
-            if (!pwf)
-                return HP_ERR_INVALID;
-            // MFMA-fragment order: [32-row tile][k16 step][lane = (k % 16 / 8) * 32 + m % 32][k % 8]
-            std::vector<__half> ppacked((size_t)cout_pad * C, __float2half(0.f));
-            for (int m = 0; m < Pn.cout; ++m)
-                for (int k = 0; k < C; ++k)
-                    ppacked[((((size_t)(m / 32) * KQ + k / 16) * 64) + (k % 16 / 8) * 32 + m % 32) * 8 + k % 8] = __float2half(pwf[(size_t)m * C + k]);
-            std::vector<float> pbias(cout_pad, 0.f), alpha;
-            if (Pn.b_off >= 0) {
-                const float* b = blob(Pn.b_off, Pn.cout, "bias", i + 1);
-                if (!b)
-                    return HP_ERR_INVALID;
-                std::copy(b, b + Pn.cout, pbias.begin());
-            }
-            st.op = OP_SEPCONV, st.n_layers = 2;
-            auto& p = st.sp;
-            void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-            HP_TRY(upload(dpacked.data(), dpacked.size() * sizeof(__half), &d0));
-            HP_TRY(upload(dbias.data(), dbias.size() * sizeof(float), &d1));
-            HP_TRY(upload(ppacked.data(), ppacked.size() * sizeof(__half), &d2));
-            HP_TRY(upload(pbias.data(), pbias.size() * sizeof(float), &d3));
-            p.in = ti.view(L.in_coff);
-            p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = C, p.stride = L.stride, p.dil = L.dil;
-            p.pad_t = g.pt, p.pad_l = g.pl, p.halo = ti.P;
-            p.dw_w = (const __half*)d0, p.dw_bias = (const float*)d1;
-            {
-                hp::conv_params tmp{};
-                tmp.act = L.act, tmp.act_param = L.act_param, tmp.alpha = nullptr;
-                HP_REQUIRE(hp::set_act(tmp), HP_ERR_INVALID, "layer %zu: unsupported depthwise activation %d", i, L.act);
-                p.dw_slope = tmp.act_slope, p.dw_hi = tmp.act_hi;
-            }
-            auto& q = p.pw;
-            q.w = (const __half*)d2, q.bias = (const float*)d3, q.alpha = nullptr;
-            if (Pn.act == HP_ACT_PRELU) {
-                alpha.assign(cout_pad, 0.f);
-                const float* a = blob(Pn.alpha_off, Pn.cout, "prelu slopes", i + 1);
-                if (!a)
-                    return HP_ERR_INVALID;
-                std::copy(a, a + Pn.cout, alpha.begin());
-                void* da = nullptr;
-                HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
-                q.alpha = (const float*)da;
-            }
-            q.H = g.OH, q.W = g.OW, q.OH = g.OH, q.OW = g.OW, q.Cin = C, q.Cout = Pn.cout, q.Cout_pad = cout_pad;
-            q.KH = q.KW = 1, q.stride = 1, q.dil = 1, q.pad_t = q.pad_l = 0;
-            q.act = Pn.act, q.act_param = Pn.act_param;
-            q.res = hp::tview{ nullptr, 0, 0, 0, 0 }, q.res_before_act = 0;
-            q.out = tp.view(Pn.out_coff);
-            q.out_f32 = nullptr, q.dbg = nullptr;
-            HP_REQUIRE(hp::set_act(q), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv", i + 1, Pn.act);
-            HP_REQUIRE(hp::sepconv_variant(p) != 0, HP_ERR_INVALID, "layer %zu: no fused separable kernel for this block (set HP_NO_FUSE=1)", i);
-            st.flops = 2.0 * opix * L.cin * 9 + 2.0 * opix * Pn.cout * C;
-            st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * Pn.cout * 2 + (double)Pn.cout * C * 2;
-            steps.push_back(st);
+        } else if (!(L.op == HP_OP_CONV && L.in == 0) && L.op == HP_OP_DWCONV && fuse_next[i] == fuse_kind::sep) {
+            HP_TRY(lower16_sep_pair(i));
             ++i; // the pointwise layer is part of this step
-            continue;
-        } else if (L.op == HP_OP_DWCONV) {
-            HP_REQUIRE(L.kh == 3 && L.kw == 3, HP_ERR_INVALID, "layer %zu: depthwise kernels are 3x3", i);
-            HP_REQUIRE(L.cin % 8 == 0 && L.in_coff % 8 == 0 && L.out_coff % 8 == 0, HP_ERR_INVALID, "layer %zu: depthwise needs 8-aligned channels", i);
-            const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
-            if (!w)
-                return HP_ERR_INVALID;
-            std::vector<__half> packed((size_t)9 * L.cin);
-            for (int c = 0; c < L.cin; ++c)
-                for (int t = 0; t < 9; ++t)
-                    packed[(size_t)t * L.cin + c] = __float2half(w[(size_t)c * 9 + t]);
-            std::vector<float> bias(L.cin, 0.f);
-            if (L.b_off >= 0) {
-                const float* b = blob(L.b_off, L.cin, "bias", i);
-                if (!b)
-                    return HP_ERR_INVALID;
-                std::copy(b, b + L.cin, bias.begin());
-            }
-            auto& p = st.dp;
-            void* dw = nullptr;
-            void* db = nullptr;
-            HP_TRY(upload(packed.data(), packed.size() * sizeof(__half), &dw));
-            HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-            p.w = (const __half*)dw, p.bias = (const float*)db;
-            p.in = ti.view(L.in_coff);
-            p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.stride = L.stride, p.dil = L.dil;
-            p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param, p.halo = ti.P;
-            p.out = to.view(L.out_coff);
-            st.flops = 2.0 * opix * L.cin * 9;
-            st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cin * 2;
-        } else if (L.op == HP_OP_UPSAMPLE) {
-            HP_REQUIRE(L.cin % 8 == 0 && L.in_coff % 8 == 0 && L.out_coff % 8 == 0, HP_ERR_INVALID, "layer %zu: up-sampling needs 8-aligned channels", i);
-            auto& p = st.pp;
-            p.in = ti.view(L.in_coff);
-            p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.k = L.kh, p.stride = L.stride, p.pad_t = p.pad_l = 0;
-            p.out = to.view(L.out_coff);
-            st.flops = 0;
-            st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cin * 2;
-        } else { // max-pool
-            HP_REQUIRE(L.cin % 8 == 0 && L.in_coff % 8 == 0 && L.out_coff % 8 == 0 && L.kh == L.kw, HP_ERR_INVALID, "layer %zu: bad pool", i);
-            auto& p = st.pp;
-            p.in = ti.view(L.in_coff);
-            p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.k = L.kh, p.stride = L.stride;
-            p.pad_t = g.pt, p.pad_l = g.pl;
-            p.out = to.view(L.out_coff);
-            st.flops = 0;
-            st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cin * 2;
-        }
-        steps.push_back(st);
+        } else
+            HP_TRY(lower16(i));
     }
+    return HP_OK;
+}
+
+// HP_DTYPE_F32 / F32S: one fp32 launch per layer (conv_fp32.hip), or per fused pair (described at its second layer)
+int hp_engine::lower32(size_t i)
+{
+    const hp_layer& L = layers[i];
+    const tensor_info& ti = *tensors[L.in];
+    tensor_info& to = *tensors[L.out];
+    const geo& g = geos[i];
+    step st;
+    st.layer = (int)i, st.op = L.op;
+    const double opix = (double)g.OH * g.OW;
+    // ---- HP_DTYPE_F32: one fp32 launch per layer (conv_fp32.hip), weights uploaded as they are
+    st.f32 = true;
+    if ((fuse_next[i] == fuse_kind::sep32) || (fuse_next[i] == fuse_kind::head32)) // the first half of a fused pair: described at the 1 x 1 layer that follows
+        return HP_OK;
+    const bool dw_in_front = i > 0 && (fuse_next[i - 1] == fuse_kind::sep32);
+    const bool head_in_front = i > 0 && (fuse_next[i - 1] == fuse_kind::head32);
+    auto padded = [&](int64_t off, int n, int n_pad, const char* what, std::vector<float>& v) -> bool {
+        v.assign(n_pad, 0.f);
+        if (off < 0)
+            return true;
+        const float* src = blob(off, n, what, i);
+        if (!src)
+            return false;
+        std::copy(src, src + n, v.begin());
+        return true;
+    };
+    if (L.op == HP_OP_CONV && L.in == 0) {
+        HP_REQUIRE(L.cin == 3 && L.in_coff == 0, HP_ERR_INVALID, "layer %zu: the network input has 3 channels", i);
+        HP_REQUIRE(L.dil == 1 && L.res < 0 && L.act != HP_ACT_PRELU, HP_ERR_INVALID, "layer %zu: unsupported first-layer options", i);
+        const size_t nw = (size_t)L.cout * L.kh * L.kw * 3;
+        const float* w = blob(L.w_off, nw, "weights", i);
+        std::vector<float> bias;
+        if (!w || !padded(L.b_off, L.cout, round_up(L.cout, 8), "bias", bias))
+            return HP_ERR_INVALID;
+        st.first = true;
+        auto& p = st.fp32;
+        p.factor = factor, p.flip_rb = flip_rb;
+        for (int c = 0; c < 3; ++c)
+            p.mean[c] = mean[c], p.inv_std[c] = inv_std[c];
+        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cout = L.cout, p.KH = L.kh, p.KW = L.kw, p.stride = L.stride;
+        p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
+        void *dw = nullptr, *db = nullptr;
+        HP_TRY(upload(w, nw * sizeof(float), &dw));
+        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
+        p.w = (const float*)dw, p.bias = (const float*)db;
+        p.out = to.view32(L.out_coff);
+        st.flops = 2.0 * opix * L.cout * L.kh * L.kw * 3;
+        st.bytes = (double)ti.H * ti.W * 3 + opix * L.cout * 4 + nw * 4;
+    } else if (L.op == HP_OP_CONV) {
+        const int cin_pad = round_up(L.cin, 16), cout_pad = round_up(L.cout, 64), taps = L.kh * L.kw;
+        // (behind a fused depthwise layer the tensor this layer "reads" is never materialised: what the kernel reads is the depthwise input)
+        const tensor_info& tsrc = (dw_in_front || head_in_front) ? *tensors[layers[i - 1].in] : ti;
+        const int src_coff = (dw_in_front || head_in_front) ? layers[i - 1].in_coff : L.in_coff;
+        HP_REQUIRE(src_coff % 4 == 0 && src_coff + (head_in_front ? layers[i - 1].cin : cin_pad) <= tsrc.cs, HP_ERR_INVALID,
+            "layer %zu: channel slice [%d,+%d) not 4-aligned / exceeds the padded stride %d", i, src_coff, cin_pad, tsrc.cs);
+        const size_t nw = (size_t)L.cout * taps * L.cin;
+        const float* w = blob(L.w_off, nw, "weights", i);
+        std::vector<float> bias, alpha;
+        if (!w || !padded(L.b_off, L.cout, cout_pad, "bias", bias))
+            return HP_ERR_INVALID;
+        auto& p = st.cp32;
+        p.alpha = nullptr;
+        if (L.act == HP_ACT_PRELU) {
+            HP_REQUIRE(L.alpha_off >= 0, HP_ERR_INVALID, "layer %zu: PReLU without slopes", i);
+            if (!padded(L.alpha_off, L.cout, cout_pad, "prelu slopes", alpha))
+                return HP_ERR_INVALID;
+            void* da = nullptr;
+            HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
+            p.alpha = (const float*)da;
+        }
+        std::vector<float> packed((size_t)taps * cout_pad * cin_pad, 0.f);
+        for (int co = 0; co < L.cout; ++co)
+            for (int t = 0; t < taps; ++t)
+                std::copy(w + ((size_t)co * taps + t) * L.cin, w + ((size_t)co * taps + t + 1) * L.cin, packed.begin() + ((size_t)t * cout_pad + co) * cin_pad);
+        void *dw = nullptr, *db = nullptr;
+        HP_TRY(upload(packed.data(), packed.size() * sizeof(float), &dw));
+        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
+        p.w = (const float*)dw, p.bias = (const float*)db;
+        p.in = ti.view32(L.in_coff);
+        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cin = cin_pad, p.Cout = L.cout, p.Cout_pad = cout_pad;
+        p.KH = L.kh, p.KW = L.kw, p.stride = L.stride, p.dil = L.dil, p.pad_t = g.pt, p.pad_l = g.pl;
+        p.dw_w = nullptr, p.dw_dil = 0, p.dw_slope = 1.f, p.dw_hi = __builtin_huge_valf();
+        if (dw_in_front) { // conv32_direct_kernel's fused form: `in` is the depthwise layer's input, its weights ride along as [9][C] + [C]
+            const hp_layer& D = layers[i - 1];
+            const float* dwf = blob(D.w_off, (size_t)D.cin * 9, "weights", i - 1);
+            std::vector<float> dbias;
+            if (!dwf || !padded(D.b_off, D.cin, D.cin, "bias", dbias))
+                return HP_ERR_INVALID;
+            std::vector<float> dpack((size_t)10 * D.cin);
+            for (int c = 0; c < D.cin; ++c) {
+                for (int t = 0; t < 9; ++t)
+                    dpack[(size_t)t * D.cin + c] = dwf[(size_t)c * 9 + t];
+                dpack[(size_t)9 * D.cin + c] = dbias[c];
+            }
+            void* ddw = nullptr;
+            HP_TRY(upload(dpack.data(), dpack.size() * sizeof(float), &ddw));
+            p.dw_w = (const float*)ddw, p.dw_dil = D.dil;
+            p.dw_slope = D.act == HP_ACT_NONE ? 1.f : D.act == HP_ACT_LEAKY ? D.act_param : 0.f;
+            p.dw_hi = D.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
+            p.in = tensors[D.in]->view32(D.in_coff);
+            st.layer = (int)i - 1, st.n_layers = 2;
+        }
+        p.act = L.act, p.act_param = L.act_param;
+        p.res = hp::tview32{ nullptr, 0, 0, 0, 0 }, p.res_before_act = L.res_before_act;
+        if (L.res >= 0)
+            p.res = tensors[L.res]->view32(0);
+        p.out = to.view32(L.out_coff);
+        p.out_f32 = nullptr;
+        for (auto& o : outputs)
+            if (o.fused_layer == (int)i)
+                p.out_f32 = o.buf->as<float>();
+        if (p.out_f32 && !tensor_is_read(L.out) && tensors[L.out]->C == L.cout)
+            p.out.p = nullptr, to.unwritten = true; // only the fp32 network output is wanted
+        HP_REQUIRE(hp::set_act32(p), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv (use an output post-op)", i, L.act);
+        p.B = max_batch, p.npix = p.pick_npix = max_batch * g.OH * g.OW;
+        p.w_split = nullptr, p.w_frag = nullptr, p.w_wino = nullptr, p.w_wino3 = nullptr, p.ovf = ovf_dev, p.dbg = nullptr;
+        p.lane_epilogue = switches.lane_epilogue;
+        // The layers conv32_direct_kernel covers (square 1 x 1 / 3 x 3, stride 1, whole 32- / 64-channel chunks inside the buffer's
+        // channel stride) get their weights in fragment order as well: fp32 for HP_DTYPE_F32, fp16 (hi, lo) pairs for HP_DTYPE_F32S (every
+        // such layer); the others stay on conv32_kernel
+        // fp32 pipe, measured per layer of LW-OpenPose @ 8 x 46 x 54 (conv32_kernel -> direct, us alone | with a second stream): 3 x 3 128 -> 128
+        // 72.2 -> 58.7 | 52.6 -> 48.9; the 1 x 1 heads 512 -> 19 / 38 27.9 / 29.3 -> 26.1 / 27.4 | 18.8 / 19.6 -> 17.9 / 18.2; every wider 1 x 1
+        // layer within +-3 % or worse (64 -> 128 22.9 -> 29.0 paired, 512 -> 512 100 -> 100 alone): 1 x 1 layers wider than 64 padded outputs
+        // stay on conv32_kernel
+        // (a 3 x 3 layer the Winograd kernel will take needs no direct-form fragments: they doubled its weight bytes in HBM)
+        const bool wino_takes_it = dtype == HP_DTYPE_F32 && !dw_in_front && !switches.no_winograd32 && hp::conv32_winograd_ok(p) && !head_in_front;
+        if (dtype == HP_DTYPE_F32S || dw_in_front || (!wino_takes_it && (taps > 1 || cout_pad <= 64))) {
+            const int ck = taps == 1 ? 64 : 32, cin_s = round_up(L.cin, ck);
+            hp::conv32_params q = p;
+            q.Cin = cin_s;
+            HP_REQUIRE(!dw_in_front || (src_coff + cin_s <= tsrc.cs && hp::conv32_direct_ok(q)), HP_ERR_STATE,
+                "layer %zu: fused behind a depthwise layer but not a direct-kernel layer (engine bug)", i);
+            if (src_coff + cin_s <= tsrc.cs && hp::conv32_direct_ok(q)) {
+                std::vector<float> wide((size_t)taps * cout_pad * cin_s, 0.f);
+                for (int t = 0; t < taps; ++t)
+                    for (int co = 0; co < cout_pad; ++co)
+                        std::copy(packed.begin() + ((size_t)t * cout_pad + co) * cin_pad, packed.begin() + ((size_t)t * cout_pad + co) * cin_pad + cin_pad,
+                            wide.begin() + ((size_t)t * cout_pad + co) * cin_s);
+                void* dws = nullptr;
+                if (dtype == HP_DTYPE_F32S) {
+                    // (a BN-folded weight beyond fp16's range has no (hi, lo) split - hi would be inf - and the run-time flag only watches
+                    // activations: such an engine starts on the fp32 pipe.  ADVICE r5)
+                    for (float v : wide)
+                        if (!(std::fabs(v) <= 65504.f) && !split_off)
+                            split_off = true, ++split_fallbacks;
+                    std::vector<_Float16> ws(wide.size() * 2);
+                    hp::conv32_split_pack(wide.data(), taps, cout_pad, cin_s, ws.data());
+                    HP_TRY(upload(ws.data(), ws.size() * sizeof(_Float16), &dws));
+                    p.w_split = (const _Float16*)dws;
+                }
+                // (an HP_DTYPE_F32S engine keeps the fp32 fragments too: what it runs after a value left fp16's range)
+                std::vector<float> wf(wide.size());
+                hp::conv32_frag_pack(wide.data(), taps, cout_pad, cin_s, wf.data());
+                HP_TRY(upload(wf.data(), wf.size() * sizeof(float), &dws));
+                p.w_frag = (const float*)dws;
+                st.cin_split = cin_s;
+            }
+        }
+        st.flops = 2.0 * opix * L.cout * taps * L.cin;
+        st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cout * 4 + (double)nw * 4;
+        // HP_DTYPE_F32: 3 x 3 stride-1 layers in Winograd's F(2 x 2, 3 x 3) form - 16 MFMA products per 2 x 2 output tile and channel pair
+        // instead of 36 (conv32_winograd.hip; HP_NO_WINOGRAD32=1 is the A/B switch back to the direct kernel).  The step's `flops` stay the
+        // layer's ALGORITHMIC count (the direct form's 2 * 9 * Cin * Cout per pixel); the MFMA work issued is 16 / 36 of it (bench.py reports both).
+        if (dtype == HP_DTYPE_F32 && !dw_in_front && !switches.no_winograd32 && hp::conv32_winograd_ok(p)) {
+            std::vector<float> wu((size_t)16 * cout_pad * cin_pad);
+            hp::conv32_winograd_pack(packed.data(), cout_pad, cin_pad, wu.data());
+            void* dwu = nullptr;
+            HP_TRY(upload(wu.data(), wu.size() * sizeof(float), &dwu));
+            p.w_wino = (const float*)dwu;
+            st.wino = true;
+            st.bytes += (double)nw * 4 * (16.0 / 9 - 1);
+            // ... or, opt-in (HP_WINO_F33=1), F(3 x 3, 3 x 3): 25 products per 3 x 3 tile - 1.44 x fewer MFMA cycles, same accuracy
+            // (conv32_winograd3.hip).  Measured: it wins where its 24 x 6-pixel blocks tile the map exactly and the layer is mid-sized (256 -> 256
+            // at 32 x 24 x 24: 121 -> 87 us) and loses everywhere else - LW-OpenPose's 128 -> 128 at 8 x 46 x 54 48.6 | 28.6 us alone | paired against
+            // 45.0 (35.9 in 8 x 8 blocks) | 27.0, every layer of PifPaf's 97 / 49 / 25-row maps - because one 16-tile column per wavefront streams
+            // 3.1 x the U bytes per output pixel.  Not the default: taken by itself only on PoseProposal's exactly tiled 48 x 48 / 24 x 24
+            // stages it made configs[3] 0.6 % faster (4 353 -> 4 380 frames/s resident, two runs each) - not worth a second numeric path.
+            if (switches.wino_f33 && hp::conv32_winograd3_ok(p)) {
+                std::vector<float> wu3((size_t)25 * cout_pad * cin_pad);
+                hp::conv32_winograd3_pack(packed.data(), cout_pad, cin_pad, wu3.data());
+                void* dwu3 = nullptr;
+                HP_TRY(upload(wu3.data(), wu3.size() * sizeof(float), &dwu3));
+                p.w_wino3 = (const float*)dwu3;
+                st.bytes += (double)nw * 4 * (25.0 / 9 - 16.0 / 9);
+            }
+        }
+        if (dw_in_front) // + the depthwise taps; the tensor between the two layers costs no bytes any more
+            st.flops += 2.0 * opix * L.cin * 9, st.bytes += (double)L.cin * 10 * 4;
+        if (head_in_front) { // conv32_head_kernel: this layer's epilogue + the hidden layer in front of it
+            const hp_layer& A = layers[i - 1];
+            const size_t nwa = (size_t)A.cout * A.cin;
+            const float* wa = blob(A.w_off, nwa, "weights", i - 1);
+            std::vector<float> biasa;
+            if (!wa || !padded(A.b_off, A.cout, A.cout, "bias", biasa))
+                return HP_ERR_INVALID;
+            std::vector<float> w1f(nwa), w2p((size_t)cout_pad * L.cin, 0.f), w2f;
+            hp::conv32_frag_pack(wa, 1, A.cout, A.cin, w1f.data()); // ([1][HID][128] is the blob's own layout: HID rows of 128)
+            const int tm2 = L.cout <= 32 ? 1 : 2;
+            std::copy(w, w + nw, w2p.begin()); // [cout][HID] rows, zero rows up to 32 tm2
+            w2f.resize((size_t)32 * tm2 * L.cin);
+            hp::conv32_head_pack(w2p.data(), tm2, L.cin, w2f.data());
+            void *d1 = nullptr, *db1 = nullptr, *d2 = nullptr;
+            HP_TRY(upload(w1f.data(), w1f.size() * sizeof(float), &d1));
+            HP_TRY(upload(biasa.data(), biasa.size() * sizeof(float), &db1));
+            HP_TRY(upload(w2f.data(), w2f.size() * sizeof(float), &d2));
+            st.hh.w1_frag = (const float*)d1, st.hh.bias1 = (const float*)db1, st.hh.w2_frag = (const float*)d2, st.hh.HID = A.cout;
+            st.hh.slope1 = A.act == HP_ACT_NONE ? 1.f : A.act == HP_ACT_LEAKY ? A.act_param : 0.f;
+            st.hh.hi1 = A.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
+            p.in = tsrc.view32(src_coff);
+            st.head32 = true, st.wino = false, st.cin_split = 0;
+            st.layer = (int)i - 1, st.n_layers = 2;
+            st.flops = 2.0 * opix * ((double)A.cout * A.cin + (double)L.cout * L.cin);
+            st.bytes = (double)tsrc.H * tsrc.W * A.cin * 4 + opix * L.cout * 4 + (double)(nwa + nw) * 4;
+        }
+    } else if (L.op == HP_OP_DWCONV) {
+        HP_REQUIRE(L.kh == 3 && L.kw == 3, HP_ERR_INVALID, "layer %zu: depthwise kernels are 3x3", i);
+        HP_REQUIRE(L.cin % 4 == 0 && L.in_coff % 4 == 0 && L.out_coff % 4 == 0, HP_ERR_INVALID, "layer %zu: depthwise needs 4-aligned channels", i);
+        // (the fp16 path refuses the same set, set_act: a PReLU here would silently run as ReLU - there are no slopes in dw32_params)
+        HP_REQUIRE(L.act != HP_ACT_PRELU && L.act != HP_ACT_SIGMOID && L.act != HP_ACT_SOFTPLUS && L.res < 0, HP_ERR_INVALID,
+            "layer %zu: activation %d / a residual on a depthwise layer is not supported", i, L.act);
+        const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
+        std::vector<float> bias;
+        if (!w || !padded(L.b_off, L.cin, L.cin, "bias", bias))
+            return HP_ERR_INVALID;
+        std::vector<float> packed((size_t)9 * L.cin);
+        for (int c = 0; c < L.cin; ++c)
+            for (int t = 0; t < 9; ++t)
+                packed[(size_t)t * L.cin + c] = w[(size_t)c * 9 + t];
+        auto& p = st.dp32;
+        void *dw = nullptr, *db = nullptr;
+        HP_TRY(upload(packed.data(), packed.size() * sizeof(float), &dw));
+        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
+        p.w = (const float*)dw, p.bias = (const float*)db;
+        p.in = ti.view32(L.in_coff);
+        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.stride = L.stride, p.dil = L.dil;
+        p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
+        p.out = to.view32(L.out_coff);
+        st.flops = 2.0 * opix * L.cin * 9;
+        st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cin * 4;
+    } else { // max-pool / up-sampling
+        HP_REQUIRE(L.cin % 4 == 0 && L.in_coff % 4 == 0 && L.out_coff % 4 == 0 && (L.op == HP_OP_UPSAMPLE || L.kh == L.kw), HP_ERR_INVALID,
+            "layer %zu: pooling / up-sampling needs 4-aligned channels and a square window", i);
+        auto& p = st.pp32;
+        p.in = ti.view32(L.in_coff);
+        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.k = L.kh, p.stride = L.stride;
+        p.pad_t = L.op == HP_OP_UPSAMPLE ? 0 : g.pt, p.pad_l = L.op == HP_OP_UPSAMPLE ? 0 : g.pl;
+        p.out = to.view32(L.out_coff);
+        st.flops = 0;
+        st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cin * 4;
+    }
+    steps.push_back(st);
+    return HP_OK;
+}
+
+// fp16 (and int8) engines: one layer
+int hp_engine::lower16(size_t i)
+{
+    const hp_layer& L = layers[i];
+    const tensor_info& ti = *tensors[L.in];
+    tensor_info& to = *tensors[L.out];
+    const geo& g = geos[i];
+    step st;
+    st.layer = (int)i, st.op = L.op;
+    const double opix = (double)g.OH * g.OW;
+    if (L.op == HP_OP_CONV && L.in == 0) {
+        HP_REQUIRE(L.cin == 3 && L.in_coff == 0, HP_ERR_INVALID, "layer %zu: the network input has 3 channels", i);
+        HP_REQUIRE(L.dil == 1 && L.res < 0 && L.act != HP_ACT_PRELU, HP_ERR_INVALID, "layer %zu: unsupported first-layer options", i);
+        const size_t nw = (size_t)L.cout * L.kh * L.kw * 3;
+        const float* w = blob(L.w_off, nw, "weights", i);
+        if (!w)
+            return HP_ERR_INVALID;
+        std::vector<float> bias(round_up(L.cout, 8), 0.f);
+        if (L.b_off >= 0) {
+            const float* b = blob(L.b_off, L.cout, "bias", i);
+            if (!b)
+                return HP_ERR_INVALID;
+            std::copy(b, b + L.cout, bias.begin());
+        }
+        st.first = true;
+        auto& p = st.fp;
+        p.factor = factor, p.flip_rb = flip_rb;
+        for (int c = 0; c < 3; ++c)
+            p.mean[c] = mean[c], p.inv_std[c] = inv_std[c];
+        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cout = L.cout, p.KH = L.kh, p.KW = L.kw, p.stride = L.stride;
+        p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
+        void* dw = nullptr;
+        void* db = nullptr;
+        HP_TRY(upload(w, nw * sizeof(float), &dw));
+        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
+        p.w = (const float*)dw, p.bias = (const float*)db;
+        p.w16 = nullptr;
+        if (L.kh == L.kw && (L.kh == 3 || L.kh == 7) && L.cout % 8 == 0 && L.cout <= 64) {
+            // fragment order of first_conv_f16_kernel: kernel rows padded to ROWP (a multiple of 8), K' = KS * ROWP in steps of 16
+            const int KS = L.kh, ROWP = (KS * 3 + 7) / 8 * 8, KP = KS * ROWP, STEPS = (KP + 15) / 16, MT = L.cout <= 32 ? 1 : 2;
+            std::vector<__half> w16((size_t)MT * STEPS * 64 * 8, __float2half(0.f));
+            for (int co = 0; co < L.cout; ++co)
+                for (int ky = 0; ky < KS; ++ky)
+                    for (int r = 0; r < KS * 3; ++r) {
+                        w16[frag16(co, ky * ROWP + r, STEPS)] = __float2half(w[((size_t)co * KS + ky) * KS * 3 + r]);
+                    }
+            void* d16 = nullptr;
+            HP_TRY(upload(w16.data(), w16.size() * sizeof(__half), &d16));
+            p.w16 = (const __half*)d16;
+        }
+        p.out = to.view(L.out_coff);
+        st.flops = 2.0 * opix * L.cout * L.kh * L.kw * 3;
+        st.bytes = (double)ti.H * ti.W * 3 + opix * L.cout * 2 + nw * 4;
+    } else if (L.op == HP_OP_CONV) {
+        const int cin_pad = round_up(L.cin, 32);
+        HP_REQUIRE(L.in_coff % 8 == 0 && L.in_coff + cin_pad <= ti.cs, HP_ERR_INVALID,
+            "layer %zu: channel slice [%d,+%d) not 8-aligned / exceeds the padded stride %d", i, L.in_coff, cin_pad, ti.cs);
+        const int cout_pad = L.cout > 64 ? round_up(L.cout, 128) : 64;
+        const int taps = L.kh * L.kw;
+        const size_t nw = (size_t)L.cout * taps * L.cin;
+        const float* w = blob(L.w_off, nw, "weights", i);
+        if (!w)
+            return HP_ERR_INVALID;
+        std::vector<float> bias(cout_pad, 0.f), alpha;
+        if (L.b_off >= 0) {
+            const float* b = blob(L.b_off, L.cout, "bias", i);
+            if (!b)
+                return HP_ERR_INVALID;
+            std::copy(b, b + L.cout, bias.begin());
+        }
+        auto& p = st.cp;
+        void* dw = nullptr;
+        void* db = nullptr;
+        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
+        p.w = nullptr, p.w_layout = 0, p.bias = (const float*)db, p.alpha = nullptr;
+        if (L.act == HP_ACT_PRELU) {
+            alpha.assign(cout_pad, 0.f);
+            const float* a = blob(L.alpha_off, L.cout, "prelu slopes", i);
+            if (!a)
+                return HP_ERR_INVALID;
+            std::copy(a, a + L.cout, alpha.begin());
+            void* da = nullptr;
+            HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
+            p.alpha = (const float*)da;
+        }
+        p.in = ti.view(L.in_coff);
+        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cin = cin_pad, p.Cout = L.cout, p.Cout_pad = cout_pad;
+        p.KH = L.kh, p.KW = L.kw, p.stride = L.stride, p.dil = L.dil, p.pad_t = g.pt, p.pad_l = g.pl;
+        p.act = L.act, p.act_param = L.act_param;
+        p.res = hp::tview{ nullptr, 0, 0, 0, 0 }, p.res_before_act = L.res_before_act;
+        if (L.res >= 0)
+            p.res = tensors[L.res]->view(0);
+        p.out = to.view(L.out_coff);
+        p.out_f32 = nullptr;
+        p.dbg = nullptr;
+        for (auto& o : outputs)
+            if (o.fused_layer == (int)i)
+                p.out_f32 = o.buf->as<float>();
+        if (p.out_f32 && !tensor_is_read(L.out) && tensors[L.out]->C == L.cout)
+            p.out.p = nullptr, to.unwritten = true; // only the fp32 network output is wanted
+        HP_REQUIRE(hp::set_act(p), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv (use an output post-op)", i, L.act);
+        // weights: the launcher says which packing its kernel for this shape reads
+        p.B = max_batch, p.npix = max_batch * g.OH * g.OW;
+        p.w_layout = hp::conv_weight_layout(p);
+        std::vector<__half> packed((size_t)taps * cout_pad * cin_pad, __float2half(0.f));
+        const int KQ = cin_pad / 16;
+        for (int co = 0; co < L.cout; ++co)
+            for (int t = 0; t < taps; ++t)
+                for (int ci = 0; ci < L.cin; ++ci) {
+                    const size_t at = p.w_layout == 1
+                        ? frag16(co, ci, KQ, (size_t)t * (cout_pad / 32))
+                        : ((size_t)t * cout_pad + co) * cin_pad + ci;
+                    packed[at] = __float2half(w[((size_t)co * taps + t) * L.cin + ci]);
+                }
+        HP_TRY(upload(packed.data(), packed.size() * sizeof(__half), &dw));
+        p.w = (const __half*)dw;
+        st.flops = 2.0 * opix * L.cout * taps * L.cin;
+        st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cout * 2 + (double)nw * 2;
+        if (dtype == HP_DTYPE_I8 && hp::conv_i8_ok(L.kh, L.kw, L.stride, L.dil)) {
+            // int8 weights, symmetric per output channel: s_w[c] = max |w| / 127 (1 for an all-zero channel), q_w = clamp(rint(w / s_w[c]), -127, 127)
+            // in fp32, round-half-even; rows [tap][Cout_pad][Cin_pad] as conv_i8_kernel reads them
+            std::vector<float> s_w(L.cout);
+            std::vector<int8_t> wq((size_t)taps * cout_pad * cin_pad, 0);
+            for (int co = 0; co < L.cout; ++co) {
+                const float* wc = w + (size_t)co * taps * L.cin;
+                float m = 0.f;
+                for (size_t k = 0; k < (size_t)taps * L.cin; ++k)
+                    m = std::max(m, std::fabs(wc[k]));
+                const float sc = m > 0.f ? m / 127.f : 1.f;
+                s_w[co] = sc;
+                for (int t = 0; t < taps; ++t)
+                    for (int ci = 0; ci < L.cin; ++ci)
+                        wq[((size_t)t * cout_pad + co) * cin_pad + ci] = (int8_t)std::min(std::max(std::rint(wc[(size_t)t * L.cin + ci] / sc), -127.f), 127.f);
+            }
+            void *dq = nullptr, *dd = nullptr;
+            HP_TRY(upload(wq.data(), wq.size(), &dq));
+            const std::vector<float> zeros(cout_pad, 0.f);
+            HP_TRY(upload(zeros.data(), zeros.size() * sizeof(float), &dd));
+            st.i8 = true, st.q8.w = (const int8_t*)dq, st.q8.dq = (const float*)dd, st.i8_dq = (float*)dd, st.q8.inv_a = 0.f;
+            st.q8.w_direct = nullptr;
+            if (hp::conv_i8_direct_ok(p)) { // the same q_w in conv_i8_direct_kernel's fragment order
+                std::vector<int8_t> wd(wq.size(), 0);
+                for (int t = 0; t < taps; ++t)
+                    for (int co = 0; co < cout_pad; ++co)
+                        for (int ci = 0; ci < cin_pad; ++ci)
+                            wd[hp::conv_i8_direct_index(t, co, ci, cin_pad, cout_pad)] = wq[((size_t)t * cout_pad + co) * cin_pad + ci];
+                void* dd2 = nullptr;
+                HP_TRY(upload(wd.data(), wd.size(), &dd2));
+                st.q8.w_direct = (const int8_t*)dd2;
+            }
+            i8_sw[i] = std::move(s_w);
+        }
+    } else if (L.op == HP_OP_DWCONV) {
+        HP_REQUIRE(L.kh == 3 && L.kw == 3, HP_ERR_INVALID, "layer %zu: depthwise kernels are 3x3", i);
+        HP_REQUIRE(L.cin % 8 == 0 && L.in_coff % 8 == 0 && L.out_coff % 8 == 0, HP_ERR_INVALID, "layer %zu: depthwise needs 8-aligned channels", i);
+        const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
+        if (!w)
+            return HP_ERR_INVALID;
+        std::vector<__half> packed((size_t)9 * L.cin);
+        for (int c = 0; c < L.cin; ++c)
+            for (int t = 0; t < 9; ++t)
+                packed[(size_t)t * L.cin + c] = __float2half(w[(size_t)c * 9 + t]);
+        std::vector<float> bias(L.cin, 0.f);
+        if (L.b_off >= 0) {
+            const float* b = blob(L.b_off, L.cin, "bias", i);
+            if (!b)
+                return HP_ERR_INVALID;
+            std::copy(b, b + L.cin, bias.begin());
+        }
+        auto& p = st.dp;
+        void* dw = nullptr;
+        void* db = nullptr;
+        HP_TRY(upload(packed.data(), packed.size() * sizeof(__half), &dw));
+        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
+        p.w = (const __half*)dw, p.bias = (const float*)db;
+        p.in = ti.view(L.in_coff);
+        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.stride = L.stride, p.dil = L.dil;
+        p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param, p.halo = ti.P;
+        p.out = to.view(L.out_coff);
+        st.flops = 2.0 * opix * L.cin * 9;
+        st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cin * 2;
+    } else if (L.op == HP_OP_UPSAMPLE) {
+        HP_REQUIRE(L.cin % 8 == 0 && L.in_coff % 8 == 0 && L.out_coff % 8 == 0, HP_ERR_INVALID, "layer %zu: up-sampling needs 8-aligned channels", i);
+        auto& p = st.pp;
+        p.in = ti.view(L.in_coff);
+        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.k = L.kh, p.stride = L.stride, p.pad_t = p.pad_l = 0;
+        p.out = to.view(L.out_coff);
+        st.flops = 0;
+        st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cin * 2;
+    } else { // max-pool
+        HP_REQUIRE(L.cin % 8 == 0 && L.in_coff % 8 == 0 && L.out_coff % 8 == 0 && L.kh == L.kw, HP_ERR_INVALID, "layer %zu: bad pool", i);
+        auto& p = st.pp;
+        p.in = ti.view(L.in_coff);
+        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.k = L.kh, p.stride = L.stride;
+        p.pad_t = g.pt, p.pad_l = g.pl;
+        p.out = to.view(L.out_coff);
+        st.flops = 0;
+        st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cin * 2;
+    }
+    steps.push_back(st);
+    return HP_OK;
+}
+
+// fp16: a two-layer head (1x1 K1 -> 512 -> 1x1 <= 64) as one mlp_head_kernel launch, layers i and i + 1
+int hp_engine::lower16_head_pair(size_t i)
+{
+    const hp_layer& L = layers[i];
+    const tensor_info& ti = *tensors[L.in];
+    const geo& g = geos[i];
+    step st;
+    st.layer = (int)i, st.op = L.op;
+    const double opix = (double)g.OH * g.OW;
+    const hp_layer& Pn = layers[i + 1];
+    tensor_info& tp = *tensors[Pn.out];
+    const int K1 = L.cin, KQ1 = K1 / 16, HID = L.cout;
+    const float* w1f = blob(L.w_off, (size_t)HID * K1, "weights", i);
+    const float* w2f = blob(Pn.w_off, (size_t)Pn.cout * HID, "weights", i + 1);
+    if (!w1f || !w2f)
+        return HP_ERR_INVALID;
+    std::vector<__half> w1p((size_t)HID * K1), w2p((size_t)64 * HID, __float2half(0.f));
+    for (int m = 0; m < HID; ++m)
+        for (int k = 0; k < K1; ++k)
+            w1p[frag16(m, k, KQ1)] = __float2half(w1f[(size_t)m * K1 + k]);
+    for (int m = 0; m < Pn.cout; ++m)
+        for (int c = 0; c < HID; ++c) {
+            const int wv = c / 128, ii = (c % 128) / 32, r32 = c % 32;
+            const int hh = (r32 >> 2) & 1, r = (r32 & 3) + 4 * (r32 >> 3), ss = r >> 3, ee = r & 7;
+            w2p[((((size_t)(m / 32) * 32 + 8 * wv + 2 * ii + ss) * 64) + hh * 32 + m % 32) * 8 + ee] = __float2half(w2f[(size_t)m * HID + c]);
+        }
+    std::vector<float> b1(HID, 0.f), b2(64, 0.f), alpha;
+    if (L.b_off >= 0) {
+        const float* bb = blob(L.b_off, HID, "bias", i);
+        if (!bb)
+            return HP_ERR_INVALID;
+        std::copy(bb, bb + HID, b1.begin());
+    }
+    if (Pn.b_off >= 0) {
+        const float* bb = blob(Pn.b_off, Pn.cout, "bias", i + 1);
+        if (!bb)
+            return HP_ERR_INVALID;
+        std::copy(bb, bb + Pn.cout, b2.begin());
+    }
+    st.op = OP_MLPHEAD, st.n_layers = 2; // (covers layers i and i + 1: the passes below must see every layer a step touches)
+    auto& p = st.hp_;
+    void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
+    HP_TRY(upload(w1p.data(), w1p.size() * sizeof(__half), &d0));
+    HP_TRY(upload(b1.data(), b1.size() * sizeof(float), &d1));
+    HP_TRY(upload(w2p.data(), w2p.size() * sizeof(__half), &d2));
+    HP_TRY(upload(b2.data(), b2.size() * sizeof(float), &d3));
+    p.in = ti.view(L.in_coff);
+    p.H = ti.H, p.W = ti.W, p.K1 = K1;
+    p.w1 = (const __half*)d0, p.b1 = (const float*)d1, p.w2 = (const __half*)d2;
+    p.hi1 = L.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
+    auto& q = p.pw;
+    q.w = nullptr, q.w_layout = 0, q.bias = (const float*)d3, q.alpha = nullptr;
+    if (Pn.act == HP_ACT_PRELU) {
+        alpha.assign(64, 0.f);
+        const float* a = blob(Pn.alpha_off, Pn.cout, "prelu slopes", i + 1);
+        if (!a)
+            return HP_ERR_INVALID;
+        std::copy(a, a + Pn.cout, alpha.begin());
+        void* da = nullptr;
+        HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
+        q.alpha = (const float*)da;
+    }
+    q.H = ti.H, q.W = ti.W, q.OH = ti.H, q.OW = ti.W, q.Cin = HID, q.Cout = Pn.cout, q.Cout_pad = 64;
+    q.KH = q.KW = 1, q.stride = 1, q.dil = 1, q.pad_t = q.pad_l = 0;
+    q.act = Pn.act, q.act_param = Pn.act_param;
+    q.res = hp::tview{ nullptr, 0, 0, 0, 0 }, q.res_before_act = 0;
+    q.out = tp.view(Pn.out_coff);
+    q.out_f32 = nullptr, q.dbg = nullptr;
+    for (auto& o : outputs)
+        if (o.fused_layer == (int)i + 1)
+            q.out_f32 = o.buf->as<float>();
+    if (q.out_f32 && !tensor_is_read(Pn.out))
+        q.out.p = nullptr, tp.unwritten = true; // only the fp32 network output is wanted
+    HP_REQUIRE(hp::set_act(q), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv", i + 1, Pn.act);
+    st.flops = 2.0 * opix * HID * K1 + 2.0 * opix * Pn.cout * HID;
+    st.bytes = (double)ti.H * ti.W * K1 * 2 + opix * Pn.cout * 2 + ((double)HID * K1 + (double)Pn.cout * HID) * 2;
+    steps.push_back(st);
+    return HP_OK;
+}
+
+// fp16: a separable block (depthwise 3x3 + 1x1) as one sepconv launch, layers i and i + 1
+int hp_engine::lower16_sep_pair(size_t i)
+{
+    const hp_layer& L = layers[i];
+    const tensor_info& ti = *tensors[L.in];
+    const geo& g = geos[i];
+    step st;
+    st.layer = (int)i, st.op = L.op;
+    const double opix = (double)g.OH * g.OW;
+    const hp_layer& Pn = layers[i + 1];
+    tensor_info& tp = *tensors[Pn.out];
+    const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
+    if (!w)
+        return HP_ERR_INVALID;
+    std::vector<__half> dpacked((size_t)9 * L.cin);
+    for (int c = 0; c < L.cin; ++c)
+        for (int t = 0; t < 9; ++t)
+            dpacked[(size_t)t * L.cin + c] = __float2half(w[(size_t)c * 9 + t]);
+    std::vector<float> dbias(L.cin, 0.f);
+    if (L.b_off >= 0) {
+        const float* b = blob(L.b_off, L.cin, "bias", i);
+        if (!b)
+            return HP_ERR_INVALID;
+        std::copy(b, b + L.cin, dbias.begin());
+    }
+    const int C = L.cin, KQ = C / 16, cout_pad = round_up(Pn.cout, 128);
+    const float* pwf = blob(Pn.w_off, (size_t)Pn.cout * C, "weights", i + 1);
+    if (!pwf)
+        return HP_ERR_INVALID;
+    // MFMA-fragment order: [32-row tile][k16 step][lane = (k % 16 / 8) * 32 + m % 32][k % 8]
+    std::vector<__half> ppacked((size_t)cout_pad * C, __float2half(0.f));
+    for (int m = 0; m < Pn.cout; ++m)
+        for (int k = 0; k < C; ++k)
+            ppacked[frag16(m, k, KQ)] = __float2half(pwf[(size_t)m * C + k]);
+    std::vector<float> pbias(cout_pad, 0.f), alpha;
+    if (Pn.b_off >= 0) {
+        const float* b = blob(Pn.b_off, Pn.cout, "bias", i + 1);
+        if (!b)
+            return HP_ERR_INVALID;
+        std::copy(b, b + Pn.cout, pbias.begin());
+    }
+    st.op = OP_SEPCONV, st.n_layers = 2;
+    auto& p = st.sp;
+    void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
+    HP_TRY(upload(dpacked.data(), dpacked.size() * sizeof(__half), &d0));
+    HP_TRY(upload(dbias.data(), dbias.size() * sizeof(float), &d1));
+    HP_TRY(upload(ppacked.data(), ppacked.size() * sizeof(__half), &d2));
+    HP_TRY(upload(pbias.data(), pbias.size() * sizeof(float), &d3));
+    p.in = ti.view(L.in_coff);
+    p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = C, p.stride = L.stride, p.dil = L.dil;
+    p.pad_t = g.pt, p.pad_l = g.pl, p.halo = ti.P;
+    p.dw_w = (const __half*)d0, p.dw_bias = (const float*)d1;
+    {
+        hp::conv_params tmp{};
+        tmp.act = L.act, tmp.act_param = L.act_param, tmp.alpha = nullptr;
+        HP_REQUIRE(hp::set_act(tmp), HP_ERR_INVALID, "layer %zu: unsupported depthwise activation %d", i, L.act);
+        p.dw_slope = tmp.act_slope, p.dw_hi = tmp.act_hi;
+    }
+    auto& q = p.pw;
+    q.w = (const __half*)d2, q.bias = (const float*)d3, q.alpha = nullptr;
+    if (Pn.act == HP_ACT_PRELU) {
+        alpha.assign(cout_pad, 0.f);
+        const float* a = blob(Pn.alpha_off, Pn.cout, "prelu slopes", i + 1);
+        if (!a)
+            return HP_ERR_INVALID;
+        std::copy(a, a + Pn.cout, alpha.begin());
+        void* da = nullptr;
+        HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
+        q.alpha = (const float*)da;
+    }
+    q.H = g.OH, q.W = g.OW, q.OH = g.OH, q.OW = g.OW, q.Cin = C, q.Cout = Pn.cout, q.Cout_pad = cout_pad;
+    q.KH = q.KW = 1, q.stride = 1, q.dil = 1, q.pad_t = q.pad_l = 0;
+    q.act = Pn.act, q.act_param = Pn.act_param;
+    q.res = hp::tview{ nullptr, 0, 0, 0, 0 }, q.res_before_act = 0;
+    q.out = tp.view(Pn.out_coff);
+    q.out_f32 = nullptr, q.dbg = nullptr;
+    HP_REQUIRE(hp::set_act(q), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv", i + 1, Pn.act);
+    HP_REQUIRE(hp::sepconv_variant(p) != 0, HP_ERR_INVALID, "layer %zu: no fused separable kernel for this block (set HP_NO_FUSE=1)", i);
+    st.flops = 2.0 * opix * L.cin * 9 + 2.0 * opix * Pn.cout * C;
+    st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * Pn.cout * 2 + (double)Pn.cout * C * 2;
+    steps.push_back(st);
+    return HP_OK;
+}
+
+int hp_engine::plan_splitk()
+{
     // ---- split-K scratch: convolutions whose tiles leave CUs idle at this engine's batch (conv_splitk) share one buffer - the
     // schedule is serial on one stream, a convolution's partial sums are consumed by its own second launch
     {
         size_t need = 0;
         for (auto& st : steps) {
             size_t bytes = 0;
-            if (st.op == HP_OP_CONV && !st.first && !st.f32 && !getenv("HP_NO_SPLITK") && hp::conv_splitk(st.cp, &bytes) > 1)
+            if (st.op == HP_OP_CONV && !st.first && !st.f32 && !switches.no_splitk && hp::conv_splitk(st.cp, &bytes) > 1)
                 need = std::max(need, bytes);
         }
         if (need) {
@@ -1228,10 +1337,17 @@ int hp_engine::build(const hp_engine_desc* d)
                 }
         }
     }
+    return HP_OK;
+}
+
+int hp_engine::fuse_chains()
+{
+    const bool f32 = is_f32();
+    const bool no_fuse = fuse_off();
     // ---- chains of 128-channel convolutions (LW-OpenPose's CPM / initial / refinement stages, lw_openpose.py:106-191): consecutive
     // steps [1x1 ->] 3x3 -> 3x3 whose intermediates nobody else reads run as ONE launch with the intermediates in LDS
     // (conv_chain.hip).  HP_NO_CHAIN=1 keeps one launch per layer (A/B measurements, and hp_engine_debug_tensor on an intermediate).
-    if (!getenv("HP_NO_CHAIN") && !no_fuse && !f32) {
+    if (!switches.no_chain && !no_fuse && !f32) {
         auto plain_conv = [&](const step& st) { return st.op == HP_OP_CONV && !st.first && st.n_layers == 1; };
         // the tensor a step writes is read only by the given layers (as input or residual) and is no network output
         auto only_read_by = [&](int tensor, int la, int lb) {
@@ -1284,10 +1400,17 @@ int hp_engine::build(const hp_engine_desc* d)
             steps.erase(steps.begin() + k + 1, steps.begin() + k + n);
         }
     }
+    return HP_OK;
+}
+
+int hp_engine::fuse_bottlenecks()
+{
+    const bool f32 = is_f32();
+    const bool no_fuse = fuse_off();
     // ---- ResNet bottlenecks (configs[3] / [4]): [3x3 ->] expansion 1x1 (+ shortcut) [-> the NEXT block's reduction 1x1] as one launch
     // (conv_bottleneck.hip).  The reduction may sit one or two steps further down the schedule (behind the next stage's projection
     // shortcut, which reads the same tensor): it has no other input, so it can run here.  HP_NO_BNECK=1 keeps one launch per layer.
-    if (!getenv("HP_NO_BNECK") && !no_fuse && !f32) {
+    if (!switches.no_bneck && !no_fuse && !f32) {
         auto plain_conv = [&](const step& st) { return st.op == HP_OP_CONV && !st.first && st.n_layers == 1; };
         auto readers_other_than = [&](int tensor, int la) { // some layer other than la reads the tensor, or it is a network output
             for (size_t j = 0; j < layers.size(); ++j)
@@ -1418,7 +1541,7 @@ int hp_engine::build(const hp_engine_desc* d)
                 for (int co = 0; co < L.cout; ++co)
                     for (int t = 0; t < taps; ++t)
                         for (int ci = 0; ci < L.cin; ++ci)
-                            packed[((((size_t)t * (c.Cout_pad / 32) + co / 32) * KQ + ci / 16) * 64 + (ci % 16 / 8) * 32 + co % 32) * 8 + ci % 8]
+                            packed[frag16(co, ci, KQ, (size_t)t * (c.Cout_pad / 32))]
                                 = __float2half(w[((size_t)co * taps + t) * L.cin + ci]);
                 void* dw = nullptr;
                 HP_TRY(upload(packed.data(), packed.size() * sizeof(__half), &dw));
@@ -1460,9 +1583,16 @@ int hp_engine::build(const hp_engine_desc* d)
                 }
         }
     }
+    return HP_OK;
+}
+
+int hp_engine::fuse_sep_pairs()
+{
+    const bool f32 = is_f32();
+    const bool no_fuse = fuse_off();
     // ---- the MobileNet stem's separable blocks 32 -> 64 and 64 -> 128 (stride 2) as ONE launch, the 64-channel tensor between them (the
     // largest of the network) in LDS only (sepconv_pair_kernel).  HP_NO_SEPPAIR=1 keeps one launch per block.
-    if (!getenv("HP_NO_SEPPAIR") && !no_fuse && !f32) {
+    if (!switches.no_seppair && !no_fuse && !f32) {
         for (size_t k = 0; k + 1 < steps.size(); ++k) {
             step &a = steps[k], &b = steps[k + 1];
             if (a.op != OP_SEPCONV || b.op != OP_SEPCONV || a.sep_pair || b.sep_pair)
@@ -1489,8 +1619,14 @@ int hp_engine::build(const hp_engine_desc* d)
             steps.erase(steps.begin() + k + 1);
         }
     }
+    return HP_OK;
+}
+
+int hp_engine::pair_heads()
+{
+    const bool f32 = is_f32();
     // sibling heads (conf / paf branch of one stage: same input, same geometry, neither reads the other) share a launch
-    if (!getenv("HP_NO_PAIR_HEADS") && !f32) {
+    if (!switches.no_pair_heads && !f32) {
         for (size_t k = 0; k + 1 < steps.size(); ++k) {
             step &a = steps[k], &b = steps[k + 1];
             if (a.op != OP_MLPHEAD || b.op != OP_MLPHEAD || a.paired)
@@ -1503,6 +1639,11 @@ int hp_engine::build(const hp_engine_desc* d)
             steps.erase(steps.begin() + k + 1);
         }
     }
+    return HP_OK;
+}
+
+int hp_engine::finish(const hp_engine_desc* d)
+{
     HP_REQUIRE(!steps.empty() && steps[0].first, HP_ERR_INVALID, "engine: the first layer must be a CONV reading tensor 0");
 
     HP_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -1526,6 +1667,7 @@ int hp_engine::build(const hp_engine_desc* d)
     return HP_OK;
 }
 
+
 int hp_engine::check_int8_scales(const float* s, int n, bool allow_uncalibrated) const
 {
     HP_REQUIRE(s, HP_ERR_INVALID, "int8 scales: null vector");
@@ -1546,11 +1688,11 @@ int hp_engine::apply_int8_scales()
         if (!st.i8)
             continue;
         const float sa = i8_scale[st.layer];
-        const std::vector<float>& sw = i8_sw[st.layer];
+        const std::vector<float>& s_w = i8_sw[st.layer];
         std::vector<float> dq(st.cp.Cout_pad, 0.f);
         if (sa > 0.f)
-            for (size_t c = 0; c < sw.size(); ++c)
-                dq[c] = sa * sw[c]; // dq[c] = s_a * s_w[c], one fp32 product
+            for (size_t c = 0; c < s_w.size(); ++c)
+                dq[c] = sa * s_w[c]; // dq[c] = s_a * s_w[c], one fp32 product
         st.q8.inv_a = sa > 0.f ? 1.0f / sa : 0.f;
         HP_HIP_TRY(hipMemcpy(st.i8_dq, dq.data(), dq.size() * sizeof(float), hipMemcpyHostToDevice));
     }
@@ -1571,206 +1713,295 @@ int hp_engine::drop_graphs()
 }
 
 namespace {
-// frames [b0, ..) of a tensor view / of an fp32 NCHW output
+// frames [b0, ..) of a tensor view / of a step's fp32 launch parameters (the second half-batch of hp_engine_set_concurrency): copies, every
+// view moved by b0 images
 inline hp::tview32 at_frame(hp::tview32 v, int b0)
 {
     if (v.p)
         v.p += (long)b0 * v.img * v.cs;
     return v;
 }
+hp::conv32_params at_frame(hp::conv32_params p, int b0)
+{
+    p.in = at_frame(p.in, b0), p.out = at_frame(p.out, b0), p.res = at_frame(p.res, b0);
+    if (p.out_f32)
+        p.out_f32 += (size_t)b0 * p.Cout * p.OH * p.OW;
+    return p;
+}
+hp::dw32_params at_frame(hp::dw32_params p, int b0)
+{
+    p.in = at_frame(p.in, b0), p.out = at_frame(p.out, b0);
+    return p;
+}
+hp::pool32_params at_frame(hp::pool32_params p, int b0)
+{
+    p.in = at_frame(p.in, b0), p.out = at_frame(p.out, b0);
+    return p;
+}
+
+// conv32_kernel's residency stamps (HP_DIRECT_DBG): every block's (start, end) on the 100 MHz clock and the CU it ran on (XCC_ID, HW_ID: se_id
+// [15:13], sh_id [12], cu_id [11:8]) at h[128 + 3 b], b < 4096
+void print_conv32_residency(const unsigned long long* h)
+{
+    struct blk { unsigned long long t0, t1; unsigned cu; };
+    std::vector<blk> bl;
+    unsigned long long tmin = ~0ull, tmax = 0;
+    for (int b = 0; b < 4096; ++b) {
+        const unsigned long long t0 = h[128 + 3 * b], t1 = h[128 + 3 * b + 1], id = h[128 + 3 * b + 2];
+        if (!t0 || !t1)
+            continue;
+        bl.push_back({ t0, t1, (unsigned)(((id >> 32) & 0xf) << 8 | ((id >> 8) & 0xff)) });
+        tmin = std::min(tmin, t0), tmax = std::max(tmax, t1);
+    }
+    if (bl.empty())
+        return;
+    std::map<unsigned, std::vector<std::pair<unsigned long long, int>>> ev; // per CU: (time, +1 / -1)
+    double dsum = 0, dmin = 1e30, dmax = 0;
+    for (const auto& b : bl) {
+        ev[b.cu].push_back({ b.t0, +1 }), ev[b.cu].push_back({ b.t1, -1 });
+        const double d = (b.t1 - b.t0) * 0.01;
+        dsum += d, dmin = std::min(dmin, d), dmax = std::max(dmax, d);
+    }
+    int peak = 0;
+    std::map<int, int> blocks_per_cu, peak_hist;
+    for (auto& kv : ev) {
+        std::sort(kv.second.begin(), kv.second.end());
+        int cur = 0, pk = 0;
+        for (auto& e2 : kv.second)
+            cur += e2.second, pk = std::max(pk, cur);
+        peak = std::max(peak, pk), ++peak_hist[pk], ++blocks_per_cu[(int)kv.second.size() / 2];
+    }
+    fprintf(stderr, "  residency: %zu blocks on %zu CUs in %.2f us (first start -> last end); block duration %.2f .. %.2f us, mean %.2f; peak resident blocks per CU:",
+        bl.size(), ev.size(), (tmax - tmin) * 0.01, dmin, dmax, dsum / bl.size());
+    for (auto& kv : peak_hist)
+        fprintf(stderr, " %d x%d", kv.first, kv.second);
+    fprintf(stderr, "; blocks run per CU:");
+    for (auto& kv : blocks_per_cu)
+        fprintf(stderr, " %d x%d", kv.first, kv.second);
+    fprintf(stderr, "; active blocks at 10 %% .. 90 %% of the launch:");
+    for (int k = 1; k < 10; ++k) {
+        const unsigned long long t = tmin + (tmax - tmin) * k / 10;
+        int a = 0;
+        for (const auto& b : bl)
+            a += b.t0 <= t && t < b.t1;
+        fprintf(stderr, " %d", a);
+    }
+    // block 9 (the one with the s_memtime stamps) on the 100 MHz clock; duration histogram; mean duration per XCD; starts of the late blocks
+    fprintf(stderr, "; block 9: %.2f us", (h[128 + 3 * 9 + 1] - h[128 + 3 * 9]) * 0.01);
+    fprintf(stderr, "; durations (10 bins from min to max):");
+    int hist[10] = { 0 };
+    for (const auto& b : bl)
+        ++hist[std::min(9, (int)(((b.t1 - b.t0) * 0.01 - dmin) / std::max(1e-9, dmax - dmin) * 10))];
+    for (int k = 0; k < 10; ++k)
+        fprintf(stderr, " %d", hist[k]);
+    double xs[16] = { 0 };
+    int xn[16] = { 0 };
+    for (const auto& b : bl)
+        xs[(b.cu >> 8) & 15] += (b.t1 - b.t0) * 0.01, ++xn[(b.cu >> 8) & 15];
+    fprintf(stderr, "; mean duration per XCD:");
+    for (int k = 0; k < 16; ++k)
+        if (xn[k])
+            fprintf(stderr, " %.1f", xs[k] / xn[k]);
+    double late0 = 1e30, late_d = 0;
+    int nlate = 0;
+    for (const auto& b : bl)
+        if ((b.t0 - tmin) * 0.01 > 5.0)
+            late0 = std::min(late0, (b.t0 - tmin) * 0.01), late_d += (b.t1 - b.t0) * 0.01, ++nlate;
+    if (nlate)
+        fprintf(stderr, "; %d blocks started later than 5 us after the first (earliest at %.1f us), their mean duration %.2f us", nlate, late0, late_d / nlate);
+    fprintf(stderr, "\n");
+}
+
+// (start, end) of the first 1024 blocks on the 100 MHz clock at h[64 + 2 i]: their number, first start -> last end, the spread of their starts and durations
+struct block_spans {
+    int nb = 0;
+    unsigned long long t0 = ~0ull, t1 = 0, smax = 0, dmin = ~0ull, dmax = 0, dsum = 0;
+    explicit block_spans(const unsigned long long* h)
+    {
+        for (int i = 0; i < 1024 && h[64 + 2 * i]; ++i, ++nb) {
+            const unsigned long long d = h[65 + 2 * i] - h[64 + 2 * i];
+            t0 = std::min(t0, h[64 + 2 * i]), t1 = std::max(t1, h[65 + 2 * i]), smax = std::max(smax, h[64 + 2 * i]);
+            dmin = std::min(dmin, d), dmax = std::max(dmax, d), dsum += d;
+        }
+    }
+};
 } // namespace
+
+// HP_CONV_DBG / HP_BN_DBG / HP_CHAIN_DBG / HP_SEP_DBG / HP_DIRECT_DBG: the step's kernel launched once more with its block-timeline stamps
+// (s_memtime = shader cycles; the 100 MHz clock) written into a zeroed scratch buffer, printed to stderr per launch.  q32 = the fp32 layer's
+// parameters as just launched (nullptr for fp16 steps).  Steps without a timeline print nothing.
+int hp_engine::print_timeline(const step& st, const hp::conv32_params* q32, hipStream_t s)
+{
+    enum { NONE, CONV, BNECK, CHAIN, SEP, WINO3, WINO, DIRECT, CONV32 } kind = NONE;
+    size_t words = 0;
+    if (q32 && st.f32 && st.op == HP_OP_CONV && !st.first && !st.head32 && switches.dbg_direct) {
+        kind = st.wino ? (q32->w_wino3 ? WINO3 : WINO) : st.cin_split ? DIRECT : q32->Cin >= switches.dbg_min_cin ? CONV32 : NONE;
+        words = kind == WINO ? 128 : kind == CONV32 ? 128 + 3 * 4096 : 64;
+    } else if (!st.f32 && st.op == HP_OP_CONV && !st.first && !i8_on(st) && switches.dbg_conv && hp::conv_mfma_tile(st.cp) / 100000 == 52)
+        kind = CONV, words = 64; // the pixel-block GEMM
+    else if (st.op == OP_BNECK && switches.dbg_bn)
+        kind = BNECK, words = 64 + 2 * 1024;
+    else if (st.op == OP_CHAIN && switches.dbg_chain)
+        kind = CHAIN, words = 32;
+    else if (st.op == OP_SEPCONV && !st.sep_pair && switches.dbg_sep)
+        kind = SEP, words = 64 + 2 * 1024 + 64; // [0, 64) block 0's stamps, then (start, end) of the first 1024 blocks, then wavefront 4 of block 1
+    if (kind == NONE)
+        return HP_OK;
+    hp::dev_buf buf;
+    HP_TRY(buf.alloc(words * 8));
+    HP_HIP_TRY(hipMemset(buf.p, 0, words * 8));
+    unsigned long long* const dbg = buf.as<unsigned long long>();
+    hp::conv32_params q = q32 ? *q32 : hp::conv32_params{};
+    q.dbg = dbg;
+    const bool split = dtype == HP_DTYPE_F32S && !split_off;
+    if (kind == CONV) {
+        hp::conv_params c = st.cp;
+        c.dbg = dbg;
+        HP_HIP_TRY(hp::launch_conv_mfma(c, s));
+    } else if (kind == BNECK) {
+        hp::bneck_params b = st.bn;
+        b.ce.dbg = dbg;
+        HP_HIP_TRY(hp::launch_bottleneck(b, s));
+    } else if (kind == CHAIN) {
+        hp::chain_params c = st.ch;
+        c.c2.dbg = dbg;
+        HP_HIP_TRY(hp::launch_conv_chain(c, s));
+    } else if (kind == SEP) {
+        hp::sep_params p = st.sp;
+        p.pw.dbg = dbg;
+        HP_HIP_TRY(hp::launch_sepconv(p, s));
+    } else if (kind == WINO3)
+        HP_HIP_TRY(hp::launch_conv32_winograd3(q, s));
+    else if (kind == WINO)
+        HP_HIP_TRY(hp::launch_conv32_winograd(q, switches, s));
+    else if (kind == DIRECT)
+        HP_HIP_TRY(hp::launch_conv32_direct(q, split, s));
+    else
+        HP_HIP_TRY(hp::launch_conv32(q, switches, s));
+    HP_HIP_TRY(hipStreamSynchronize(s));
+    std::vector<unsigned long long> hv(words);
+    const unsigned long long* h = hv.data();
+    HP_HIP_TRY(hipMemcpy(hv.data(), dbg, words * 8, hipMemcpyDeviceToHost));
+    auto deltas = [h](int from, int to) {
+        for (int i = from; i < to && h[i]; ++i)
+            fprintf(stderr, " %llu", h[i] - h[i - 1]);
+    };
+    switch (kind) {
+    case CONV:
+        fprintf(stderr, "conv layer %d %d->%d tile %d consumer:", st.layer, st.cp.Cin, st.cp.Cout, hp::conv_mfma_tile(st.cp));
+        deltas(1, 32);
+        fprintf(stderr, " | producer (from consumer start %lld):", (long long)(h[32] - h[0]));
+        deltas(33, 64);
+        fprintf(stderr, "\n");
+        break;
+    case BNECK: { // block 0's phase timeline and the start / end of the first 1024 blocks
+        fprintf(stderr, "bottleneck layer %d variant %d timeline:", st.layer, hp::bottleneck_variant(st.bn));
+        deltas(1, 60);
+        const block_spans b(h);
+        if (b.nb)
+            fprintf(stderr, "\n  first %d blocks: %.2f us from first start to last end; block duration %.2f .. %.2f us, mean %.2f", b.nb, (b.t1 - b.t0) * 0.01,
+                b.dmin * 0.01, b.dmax * 0.01, b.dsum * 0.01 / b.nb);
+        fprintf(stderr, "\n");
+        break;
+    }
+    case CHAIN:
+        fprintf(stderr, "chain layer %d variant %d timeline:", st.layer, hp::conv_chain_variant(st.ch));
+        deltas(1, 32);
+        fprintf(stderr, "\n");
+        break;
+    case SEP:
+        fprintf(stderr, "sep layer %d C=%d timeline:", st.layer, st.sp.C);
+        deltas(1, 40);
+        if (h[41])
+            fprintf(stderr, " | total-to-epi0 %llu pass1 %llu epi1 %llu | total %llu", h[41] - h[0], h[42] - h[41], h[43] - h[42], h[43] - h[0]);
+        fprintf(stderr, "\n");
+        if (h[2112]) {
+            fprintf(stderr, "  wavefront 4 of block 1:");
+            for (int i = 1; i < 40 && h[2112 + i]; ++i)
+                fprintf(stderr, " %llu", h[2112 + i] - h[2112 + i - 1]);
+            fprintf(stderr, "\n");
+        }
+        if (h[64]) {
+            const block_spans b(h);
+            fprintf(stderr, "  %d blocks: first start -> last end %.2f us, starts spread over %.2f us, block duration %.2f .. %.2f us\n", b.nb,
+                (b.t1 - b.t0) * 0.01, (b.smax - b.t0) * 0.01, b.dmin * 0.01, b.dmax * 0.01);
+        }
+        break;
+    case WINO3: // block 9, thread 0
+        fprintf(stderr, "winograd3 layer %d %d->%d cycles [start | chunk 0 transformed | per chunk: patch stored, multiplied | output transformed | stored]:", st.layer, q.Cin, q.Cout);
+        deltas(1, 60);
+        fprintf(stderr, "\n");
+        break;
+    case WINO: { // block (1, 0), thread 0
+        fprintf(stderr, "winograd layer %d %d->%d tile %d cycles [start | staged, transformed, multiplied per chunk | stored]:", st.layer, q.Cin, q.Cout,
+            hp::conv32_winograd_tile(q));
+        deltas(1, 119);
+        int occ = 0;
+        (void)hp::conv32_winograd_occupancy(q, &occ);
+        fprintf(stderr, " | s_memtime ticks %llu in %llu ticks of the 100 MHz clock; blocks per CU %d\n", h[121] - h[119], h[122] - h[120], occ);
+        break;
+    }
+    case DIRECT: // block (1, 0), thread 0
+        fprintf(stderr, "direct layer %d %dx%d %d->%d tile %d cycles [start | staged, multiplied per chunk | stored]:", st.layer, q.KH, q.KW, q.Cin, q.Cout,
+            hp::conv32_direct_tile(q, split));
+        deltas(1, 64);
+        fprintf(stderr, "\n");
+        break;
+    default: // CONV32: block 9, thread 0: start | first tile staged | every 8 K-steps | stored; then every block's residency
+        fprintf(stderr, "conv32 layer %d %dx%d %d->%d tile %d cycles [start | staged | per 8 K-steps | stored]:", st.layer, q.KH, q.KW, q.Cin, q.Cout, hp::conv32_tile(q, switches));
+        deltas(1, 128);
+        fprintf(stderr, "\n");
+        print_conv32_residency(h);
+        break;
+    }
+    return HP_OK;
+}
 
 int hp_engine::run_step(step& st, const uint8_t* u8, const float* f32, int n, hipStream_t s, int b0)
 {
-    if (st.f32 && b0 > 0) {
-        // the second half-batch (hp_engine_set_concurrency): the same step on frames [b0, b0 + n) - every view moved by b0 images
-        step t = st;
-        if (t.first) {
-            t.fp32.out = at_frame(st.fp32.out, b0);
-            return run_step(t, u8 ? u8 + (size_t)b0 * in_h * in_w * 3 : nullptr, f32 ? f32 + (size_t)b0 * in_h * in_w * 3 : nullptr, n, s, 0);
-        }
-        if (t.op == HP_OP_CONV) {
-            t.cp32.in = at_frame(st.cp32.in, b0), t.cp32.out = at_frame(st.cp32.out, b0), t.cp32.res = at_frame(st.cp32.res, b0);
-            if (t.cp32.out_f32)
-                t.cp32.out_f32 += (size_t)b0 * t.cp32.Cout * t.cp32.OH * t.cp32.OW;
-        } else if (t.op == HP_OP_DWCONV)
-            t.dp32.in = at_frame(st.dp32.in, b0), t.dp32.out = at_frame(st.dp32.out, b0);
-        else
-            t.pp32.in = at_frame(st.pp32.in, b0), t.pp32.out = at_frame(st.pp32.out, b0);
-        return run_step(t, u8, f32, n, s, 0);
-    }
     if (st.f32) {
+        // b0 > 0 (the second half-batch of hp_engine_set_concurrency): the same step on frames [b0, b0 + n), launched with moved copies of its
+        // parameters; b0 = 0 launches (and keeps) the step's own
+        const size_t in_off = (size_t)b0 * in_h * in_w * 3;
+        hp::conv32_params moved;
+        hp::conv32_params& cp = b0 ? (moved = at_frame(st.cp32, b0)) : st.cp32;
         if (st.first) {
-            st.fp32.in_u8 = u8, st.fp32.in_f32 = f32, st.fp32.B = n;
-            HP_HIP_TRY(hp::launch_first_conv32(st.fp32, s));
+            hp::first_conv32_params p = st.fp32;
+            p.out = at_frame(p.out, b0);
+            p.in_u8 = u8 ? u8 + in_off : nullptr, p.in_f32 = f32 ? f32 + in_off : nullptr, p.B = n;
+            if (!b0)
+                st.fp32 = p;
+            HP_HIP_TRY(hp::launch_first_conv32(p, switches, s));
         } else if (st.op == HP_OP_CONV) {
-            st.cp32.B = n, st.cp32.npix = n * st.cp32.OH * st.cp32.OW;
+            cp.B = n, cp.npix = n * cp.OH * cp.OW;
             if (st.head32) {
-                HP_HIP_TRY(hp::launch_conv32_head(st.cp32, st.hh, s));
+                HP_HIP_TRY(hp::launch_conv32_head(cp, st.hh, s));
             } else if (st.wino) {
-                st.cp32.latency = parts > 1;
-                if (st.cp32.w_wino3) {
-                    HP_HIP_TRY(hp::launch_conv32_winograd3(st.cp32, s));
-                    static const bool dbg_w3 = getenv("HP_DIRECT_DBG") != nullptr;
-                    if (dbg_w3) { // block timeline (s_memtime, block 9, thread 0): start | chunk 0 transformed | per chunk: patch stored, multiplied | transformed out | stored
-                        unsigned long long* dbg = nullptr;
-                        HP_HIP_TRY(hipMalloc(&dbg, 64 * 8));
-                        HP_HIP_TRY(hipMemset(dbg, 0, 64 * 8));
-                        hp::conv32_params q = st.cp32;
-                        q.dbg = dbg;
-                        HP_HIP_TRY(hp::launch_conv32_winograd3(q, s));
-                        HP_HIP_TRY(hipStreamSynchronize(s));
-                        unsigned long long h[64];
-                        HP_HIP_TRY(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
-                        fprintf(stderr, "winograd3 layer %d %d->%d cycles [start | chunk 0 transformed | per chunk: patch stored, multiplied | output transformed | stored]:", st.layer, q.Cin, q.Cout);
-                        for (int i = 1; i < 60 && h[i]; ++i)
-                            fprintf(stderr, " %llu", h[i] - h[i - 1]);
-                        fprintf(stderr, "\n");
-                        (void)hipFree(dbg);
-                    }
-                } else
-                    HP_HIP_TRY(hp::launch_conv32_winograd(st.cp32, s));
-                static const bool dbg_wino = getenv("HP_DIRECT_DBG") != nullptr;
-                if (dbg_wino && !st.cp32.w_wino3) { // block timeline (s_memtime = shader cycles, block (1, 0), thread 0), printed per launch
-                    unsigned long long* dbg = nullptr;
-                    HP_HIP_TRY(hipMalloc(&dbg, 128 * 8));
-                    HP_HIP_TRY(hipMemset(dbg, 0, 128 * 8));
-                    hp::conv32_params q = st.cp32;
-                    q.dbg = dbg;
-                    HP_HIP_TRY(hp::launch_conv32_winograd(q, s));
-                    HP_HIP_TRY(hipStreamSynchronize(s));
-                    unsigned long long h[128];
-                    HP_HIP_TRY(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
-                    fprintf(stderr, "winograd layer %d %d->%d tile %d cycles [start | staged, transformed, multiplied per chunk | stored]:", st.layer, q.Cin, q.Cout,
-                        hp::conv32_winograd_tile(q));
-                    for (int i = 1; i < 119 && h[i]; ++i)
-                        fprintf(stderr, " %llu", h[i] - h[i - 1]);
-                    int occ = 0;
-                    (void)hp::conv32_winograd_occupancy(q, &occ);
-                    fprintf(stderr, " | s_memtime ticks %llu in %llu ticks of the 100 MHz clock; blocks per CU %d\n", h[121] - h[119], h[122] - h[120], occ);
-                    (void)hipFree(dbg);
-                }
+                cp.latency = parts > 1;
+                if (cp.w_wino3)
+                    HP_HIP_TRY(hp::launch_conv32_winograd3(cp, s));
+                else
+                    HP_HIP_TRY(hp::launch_conv32_winograd(cp, switches, s));
             } else if (st.cin_split) { // the direct kernel: on the fp16 pipe (HP_DTYPE_F32S until a value left fp16's range) or on the fp32 pipe
-                hp::conv32_params q = st.cp32;
+                hp::conv32_params q = cp;
                 q.Cin = st.cin_split;
                 HP_HIP_TRY(hp::launch_conv32_direct(q, dtype == HP_DTYPE_F32S && !split_off, s));
-                static const bool dbg_direct = getenv("HP_DIRECT_DBG") != nullptr;
-                if (dbg_direct) { // block timeline (s_memtime = shader cycles, block (1, 0), thread 0), printed per launch
-                    unsigned long long* dbg = nullptr;
-                    HP_HIP_TRY(hipMalloc(&dbg, 64 * 8));
-                    HP_HIP_TRY(hipMemset(dbg, 0, 64 * 8));
-                    q.dbg = dbg;
-                    HP_HIP_TRY(hp::launch_conv32_direct(q, dtype == HP_DTYPE_F32S && !split_off, s));
-                    HP_HIP_TRY(hipStreamSynchronize(s));
-                    unsigned long long h[64];
-                    HP_HIP_TRY(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
-                    fprintf(stderr, "direct layer %d %dx%d %d->%d tile %d cycles [start | staged, multiplied per chunk | stored]:", st.layer, q.KH, q.KW, q.Cin, q.Cout,
-                        hp::conv32_direct_tile(q, dtype == HP_DTYPE_F32S && !split_off));
-                    for (int i = 1; i < 64 && h[i]; ++i)
-                        fprintf(stderr, " %llu", h[i] - h[i - 1]);
-                    fprintf(stderr, "\n");
-                    (void)hipFree(dbg);
-                }
-            } else {
-                HP_HIP_TRY(hp::launch_conv32(st.cp32, s));
-                static const bool dbg_c32 = getenv("HP_DIRECT_DBG") != nullptr;
-                static const int dbg_min_cin = getenv("HP_DIRECT_DBG_MINCIN") ? atoi(getenv("HP_DIRECT_DBG_MINCIN")) : 256;
-                if (dbg_c32 && st.cp32.Cin >= dbg_min_cin) { // block timeline (s_memtime, block 9, thread 0): start | first tile staged | every 8 K-steps | stored
-                    constexpr int NDBG = 128 + 3 * 4096;
-                    unsigned long long* dbg = nullptr;
-                    HP_HIP_TRY(hipMalloc(&dbg, NDBG * 8));
-                    HP_HIP_TRY(hipMemset(dbg, 0, NDBG * 8));
-                    hp::conv32_params q = st.cp32;
-                    q.dbg = dbg;
-                    HP_HIP_TRY(hp::launch_conv32(q, s));
-                    HP_HIP_TRY(hipStreamSynchronize(s));
-                    std::vector<unsigned long long> hv(NDBG);
-                    unsigned long long* h = hv.data();
-                    HP_HIP_TRY(hipMemcpy(h, dbg, NDBG * 8, hipMemcpyDeviceToHost));
-                    fprintf(stderr, "conv32 layer %d %dx%d %d->%d tile %d cycles [start | staged | per 8 K-steps | stored]:", st.layer, q.KH, q.KW, q.Cin, q.Cout, hp::conv32_tile(q));
-                    for (int i = 1; i < 128 && h[i]; ++i)
-                        fprintf(stderr, " %llu", h[i] - h[i - 1]);
-                    fprintf(stderr, "\n");
-                    // residency: every block's (start, end) on the 100 MHz clock and the CU it ran on (XCC_ID, HW_ID: se_id [15:13], sh_id [12], cu_id [11:8])
-                    struct blk { unsigned long long t0, t1; unsigned cu; };
-                    std::vector<blk> bl;
-                    unsigned long long tmin = ~0ull, tmax = 0;
-                    for (int b = 0; b < 4096; ++b) {
-                        const unsigned long long t0 = h[128 + 3 * b], t1 = h[128 + 3 * b + 1], id = h[128 + 3 * b + 2];
-                        if (!t0 || !t1)
-                            continue;
-                        bl.push_back({ t0, t1, (unsigned)(((id >> 32) & 0xf) << 8 | ((id >> 8) & 0xff)) });
-                        tmin = std::min(tmin, t0), tmax = std::max(tmax, t1);
-                    }
-                    if (!bl.empty()) {
-                        std::map<unsigned, std::vector<std::pair<unsigned long long, int>>> ev; // per CU: (time, +1 / -1)
-                        double dsum = 0, dmin = 1e30, dmax = 0;
-                        for (const auto& b : bl) {
-                            ev[b.cu].push_back({ b.t0, +1 }), ev[b.cu].push_back({ b.t1, -1 });
-                            const double d = (b.t1 - b.t0) * 0.01;
-                            dsum += d, dmin = std::min(dmin, d), dmax = std::max(dmax, d);
-                        }
-                        int peak = 0;
-                        std::map<int, int> blocks_per_cu, peak_hist;
-                        for (auto& kv : ev) {
-                            std::sort(kv.second.begin(), kv.second.end());
-                            int cur = 0, pk = 0;
-                            for (auto& e2 : kv.second)
-                                cur += e2.second, pk = std::max(pk, cur);
-                            peak = std::max(peak, pk), ++peak_hist[pk], ++blocks_per_cu[(int)kv.second.size() / 2];
-                        }
-                        fprintf(stderr, "  residency: %zu blocks on %zu CUs in %.2f us (first start -> last end); block duration %.2f .. %.2f us, mean %.2f; peak resident blocks per CU:",
-                            bl.size(), ev.size(), (tmax - tmin) * 0.01, dmin, dmax, dsum / bl.size());
-                        for (auto& kv : peak_hist)
-                            fprintf(stderr, " %d x%d", kv.first, kv.second);
-                        fprintf(stderr, "; blocks run per CU:");
-                        for (auto& kv : blocks_per_cu)
-                            fprintf(stderr, " %d x%d", kv.first, kv.second);
-                        fprintf(stderr, "; active blocks at 10 %% .. 90 %% of the launch:");
-                        for (int k = 1; k < 10; ++k) {
-                            const unsigned long long t = tmin + (tmax - tmin) * k / 10;
-                            int a = 0;
-                            for (const auto& b : bl)
-                                a += b.t0 <= t && t < b.t1;
-                            fprintf(stderr, " %d", a);
-                        }
-                        // block 9 (the one with the s_memtime stamps) on the 100 MHz clock; duration histogram; mean duration per XCD; starts of the late blocks
-                        fprintf(stderr, "; block 9: %.2f us", (h[128 + 3 * 9 + 1] - h[128 + 3 * 9]) * 0.01);
-                        fprintf(stderr, "; durations (10 bins from min to max):");
-                        int hist[10] = { 0 };
-                        for (const auto& b : bl)
-                            ++hist[std::min(9, (int)(((b.t1 - b.t0) * 0.01 - dmin) / std::max(1e-9, dmax - dmin) * 10))];
-                        for (int k = 0; k < 10; ++k)
-                            fprintf(stderr, " %d", hist[k]);
-                        double xs[16] = { 0 };
-                        int xn[16] = { 0 };
-                        for (const auto& b : bl)
-                            xs[(b.cu >> 8) & 15] += (b.t1 - b.t0) * 0.01, ++xn[(b.cu >> 8) & 15];
-                        fprintf(stderr, "; mean duration per XCD:");
-                        for (int k = 0; k < 16; ++k)
-                            if (xn[k])
-                                fprintf(stderr, " %.1f", xs[k] / xn[k]);
-                        double late0 = 1e30, late_d = 0;
-                        int nlate = 0;
-                        for (const auto& b : bl)
-                            if ((b.t0 - tmin) * 0.01 > 5.0)
-                                late0 = std::min(late0, (b.t0 - tmin) * 0.01), late_d += (b.t1 - b.t0) * 0.01, ++nlate;
-                        if (nlate)
-                            fprintf(stderr, "; %d blocks started later than 5 us after the first (earliest at %.1f us), their mean duration %.2f us", nlate, late0, late_d / nlate);
-                        fprintf(stderr, "\n");
-                    }
-                    (void)hipFree(dbg);
-                }
-            }
+                return print_timeline(st, &q, s);
+            } else
+                HP_HIP_TRY(hp::launch_conv32(cp, switches, s));
+            return print_timeline(st, &cp, s);
         } else if (st.op == HP_OP_DWCONV) {
-            st.dp32.B = n;
-            HP_HIP_TRY(hp::launch_dwconv32(st.dp32, s));
-        } else if (st.op == HP_OP_UPSAMPLE) {
-            st.pp32.B = n;
-            HP_HIP_TRY(hp::launch_upsample32(st.pp32, s));
+            hp::dw32_params p = b0 ? at_frame(st.dp32, b0) : st.dp32;
+            p.B = n;
+            if (!b0)
+                st.dp32.B = n;
+            HP_HIP_TRY(hp::launch_dwconv32(p, switches, s));
         } else {
-            st.pp32.B = n;
-            HP_HIP_TRY(hp::launch_maxpool32(st.pp32, s));
+            hp::pool32_params p = b0 ? at_frame(st.pp32, b0) : st.pp32;
+            p.B = n;
+            if (!b0)
+                st.pp32.B = n;
+            HP_HIP_TRY(st.op == HP_OP_UPSAMPLE ? hp::launch_upsample32(p, s) : hp::launch_maxpool32(p, s));
         }
         return HP_OK;
     }
@@ -1784,117 +2015,19 @@ int hp_engine::run_step(step& st, const uint8_t* u8, const float* f32, int n, hi
     } else if (st.op == HP_OP_CONV) {
         st.cp.B = n, st.cp.npix = n * st.cp.OH * st.cp.OW;
         HP_HIP_TRY(hp::launch_conv_mfma(st.cp, s));
-        if (dbg_conv && hp::conv_mfma_tile(st.cp) / 100000 == 52) { // block timeline of the pixel-block GEMM
-            unsigned long long* dbg = nullptr;
-            HP_HIP_TRY(hipMalloc(&dbg, 64 * 8));
-            HP_HIP_TRY(hipMemset(dbg, 0, 64 * 8));
-            st.cp.dbg = dbg;
-            HP_HIP_TRY(hp::launch_conv_mfma(st.cp, s));
-            HP_HIP_TRY(hipStreamSynchronize(s));
-            unsigned long long h[64];
-            HP_HIP_TRY(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
-            fprintf(stderr, "conv layer %d %d->%d tile %d consumer:", st.layer, st.cp.Cin, st.cp.Cout, hp::conv_mfma_tile(st.cp));
-            for (int i = 1; i < 32 && h[i]; ++i)
-                fprintf(stderr, " %llu", h[i] - h[i - 1]);
-            fprintf(stderr, " | producer (from consumer start %lld):", (long long)(h[32] - h[0]));
-            for (int i = 33; i < 64 && h[i]; ++i)
-                fprintf(stderr, " %llu", h[i] - h[i - 1]);
-            fprintf(stderr, "\n");
-            st.cp.dbg = nullptr;
-            (void)hipFree(dbg);
-        }
     } else if (st.op == OP_BNECK) {
         st.bn.c3.B = st.bn.ce.B = st.bn.cr.B = n;
         HP_HIP_TRY(hp::launch_bottleneck(st.bn, s));
-        if (dbg_bn) { // block 0's phase timeline (s_memtime deltas) and the start / end of the first 1024 blocks (100 MHz clock)
-            constexpr int NDBG = 64 + 2 * 1024;
-            unsigned long long* dbg = nullptr;
-            HP_HIP_TRY(hipMalloc(&dbg, NDBG * 8));
-            HP_HIP_TRY(hipMemset(dbg, 0, NDBG * 8));
-            st.bn.ce.dbg = dbg;
-            HP_HIP_TRY(hp::launch_bottleneck(st.bn, s));
-            HP_HIP_TRY(hipStreamSynchronize(s));
-            std::vector<unsigned long long> h(NDBG);
-            HP_HIP_TRY(hipMemcpy(h.data(), dbg, NDBG * 8, hipMemcpyDeviceToHost));
-            fprintf(stderr, "bottleneck layer %d variant %d timeline:", st.layer, hp::bottleneck_variant(st.bn));
-            for (int i = 1; i < 60 && h[i]; ++i)
-                fprintf(stderr, " %llu", h[i] - h[i - 1]);
-            unsigned long long t0 = ~0ull, t1 = 0, dmin = ~0ull, dmax = 0, dsum = 0;
-            int nb = 0;
-            for (int i = 0; i < 1024 && h[64 + 2 * i]; ++i, ++nb) {
-                const unsigned long long d = h[65 + 2 * i] - h[64 + 2 * i];
-                t0 = std::min(t0, h[64 + 2 * i]), t1 = std::max(t1, h[65 + 2 * i]), dmin = std::min(dmin, d), dmax = std::max(dmax, d), dsum += d;
-            }
-            if (nb)
-                fprintf(stderr, "\n  first %d blocks: %.2f us from first start to last end; block duration %.2f .. %.2f us, mean %.2f", nb, (t1 - t0) * 0.01,
-                    dmin * 0.01, dmax * 0.01, dsum * 0.01 / nb);
-            fprintf(stderr, "\n");
-            st.bn.ce.dbg = nullptr;
-            (void)hipFree(dbg);
-        }
     } else if (st.op == OP_CHAIN) {
         st.ch.c0.B = st.ch.c1.B = st.ch.c2.B = n;
         HP_HIP_TRY(hp::launch_conv_chain(st.ch, s));
-        if (dbg_chain) { // block timeline (s_memtime deltas of block 0, thread 0), printed per launch
-            unsigned long long* dbg = nullptr;
-            HP_HIP_TRY(hipMalloc(&dbg, 32 * 8));
-            HP_HIP_TRY(hipMemset(dbg, 0, 32 * 8));
-            st.ch.c2.dbg = dbg;
-            HP_HIP_TRY(hp::launch_conv_chain(st.ch, s));
-            HP_HIP_TRY(hipStreamSynchronize(s));
-            unsigned long long h[32];
-            HP_HIP_TRY(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
-            fprintf(stderr, "chain layer %d variant %d timeline:", st.layer, hp::conv_chain_variant(st.ch));
-            for (int i = 1; i < 32 && h[i]; ++i)
-                fprintf(stderr, " %llu", h[i] - h[i - 1]);
-            fprintf(stderr, "\n");
-            st.ch.c2.dbg = nullptr;
-            (void)hipFree(dbg);
-        }
     } else if (st.op == OP_SEPCONV) {
         st.sp.B = n, st.sp.pw.B = n, st.sp.pw.npix = n * st.sp.OH * st.sp.OW;
         if (st.sep_pair) {
             st.sp2.B = n, st.sp2.pw.B = n, st.sp2.pw.npix = n * st.sp2.OH * st.sp2.OW;
             HP_HIP_TRY(hp::launch_seppair(hp::seppair_params{ st.sp, st.sp2 }, s));
-            return HP_OK;
-        }
-        HP_HIP_TRY(hp::launch_sepconv(st.sp, s));
-        if (dbg_sep) { // block timeline (s_memtime deltas of block 0, thread 0) of every separable block, printed per launch
-            unsigned long long* dbg = nullptr;
-            constexpr int NDBG = 64 + 2 * 1024 + 64; // [0, 64) block 0's stamps, then (start, end) of the first 1024 blocks (100 MHz clock)
-            HP_HIP_TRY(hipMalloc(&dbg, NDBG * 8));
-            HP_HIP_TRY(hipMemset(dbg, 0, NDBG * 8));
-            st.sp.pw.dbg = dbg;
+        } else
             HP_HIP_TRY(hp::launch_sepconv(st.sp, s));
-            HP_HIP_TRY(hipStreamSynchronize(s));
-            std::vector<unsigned long long> hbuf(NDBG);
-            unsigned long long* h = hbuf.data();
-            HP_HIP_TRY(hipMemcpy(h, dbg, NDBG * 8, hipMemcpyDeviceToHost));
-            fprintf(stderr, "sep layer %d C=%d timeline:", st.layer, st.sp.C);
-            for (int i = 1; i < 40 && h[i]; ++i)
-                fprintf(stderr, " %llu", h[i] - h[i - 1]);
-            if (h[41])
-                fprintf(stderr, " | total-to-epi0 %llu pass1 %llu epi1 %llu | total %llu", h[41] - h[0], h[42] - h[41], h[43] - h[42], h[43] - h[0]);
-            fprintf(stderr, "\n");
-            if (h[2112]) {
-                fprintf(stderr, "  wavefront 4 of block 1:");
-                for (int i = 1; i < 40 && h[2112 + i]; ++i)
-                    fprintf(stderr, " %llu", h[2112 + i] - h[2112 + i - 1]);
-                fprintf(stderr, "\n");
-            }
-            if (h[64]) {
-                unsigned long long t0 = ~0ull, t1 = 0, dmin = ~0ull, dmax = 0, smax = 0;
-                int nb = 0;
-                for (int i = 0; i < 1024 && h[64 + 2 * i]; ++i, ++nb) {
-                    t0 = std::min(t0, h[64 + 2 * i]), t1 = std::max(t1, h[65 + 2 * i]), smax = std::max(smax, h[64 + 2 * i]);
-                    dmin = std::min(dmin, h[65 + 2 * i] - h[64 + 2 * i]), dmax = std::max(dmax, h[65 + 2 * i] - h[64 + 2 * i]);
-                }
-                fprintf(stderr, "  %d blocks: first start -> last end %.2f us, starts spread over %.2f us, block duration %.2f .. %.2f us\n", nb,
-                    (t1 - t0) * 0.01, (smax - t0) * 0.01, dmin * 0.01, dmax * 0.01);
-            }
-            st.sp.pw.dbg = nullptr;
-            (void)hipFree(dbg);
-        }
     } else if (st.op == OP_MLPHEAD) {
         st.hp_.B = n, st.hp_.pw.B = n;
         if (st.paired) {
@@ -1912,7 +2045,7 @@ int hp_engine::run_step(step& st, const uint8_t* u8, const float* f32, int n, hi
         st.pp.B = n;
         HP_HIP_TRY(hp::launch_maxpool(st.pp, s));
     }
-    return HP_OK;
+    return print_timeline(st, nullptr, s);
 }
 
 int hp_engine::enqueue_range(const uint8_t* u8, const float* f32, int b0, int n, hipStream_t s)
@@ -1921,17 +2054,11 @@ int hp_engine::enqueue_range(const uint8_t* u8, const float* f32, int b0, int n,
         step& st = steps[i];
         // two fused heads in a row that read the same tensor (LW-OpenPose's heat-map and PAF heads of a stage): one grid (conv32_head.hip)
         if (st.f32 && st.head32 && i + 1 < steps.size() && steps[i + 1].f32 && steps[i + 1].head32) {
-            step a = st, b = steps[i + 1];
-            for (step* t : { &a, &b }) {
-                t->cp32.B = n, t->cp32.npix = n * t->cp32.OH * t->cp32.OW;
-                if (b0 > 0) {
-                    t->cp32.in = at_frame(t->cp32.in, b0), t->cp32.out = at_frame(t->cp32.out, b0), t->cp32.res = at_frame(t->cp32.res, b0);
-                    if (t->cp32.out_f32)
-                        t->cp32.out_f32 += (size_t)b0 * t->cp32.Cout * t->cp32.OH * t->cp32.OW;
-                }
-            }
-            if (hp::conv32_head_pair_ok(a.cp32, b.cp32)) {
-                HP_HIP_TRY(hp::launch_conv32_head_pair(a.cp32, a.hh, b.cp32, b.hh, s));
+            hp::conv32_params a = at_frame(st.cp32, b0), b = at_frame(steps[i + 1].cp32, b0);
+            for (hp::conv32_params* q : { &a, &b })
+                q->B = n, q->npix = n * q->OH * q->OW;
+            if (hp::conv32_head_pair_ok(a, b, switches)) {
+                HP_HIP_TRY(hp::launch_conv32_head_pair(a, st.hh, b, steps[i + 1].hh, s));
                 ++i;
                 continue;
             }
@@ -1947,6 +2074,34 @@ int hp_engine::enqueue_range(const uint8_t* u8, const float* f32, int b0, int n,
             else
                 HP_HIP_TRY(hp::launch_output_transform(ti.view(o.coff), n, o.H, o.W, o.x, dst, s));
         }
+    return HP_OK;
+}
+
+int hp_engine::step_tile(const step& st) const
+{
+    if (st.op == OP_SEPCONV)
+        return 4000000 + (st.sep_pair ? 20 : hp::sepconv_variant(st.sp));
+    if (st.op == OP_MLPHEAD)
+        return 6000000 + st.hp_.K1;
+    if (st.op == OP_CHAIN)
+        return 7000000 + hp::conv_chain_variant(st.ch);
+    if (st.op == OP_BNECK)
+        return 9000000 + hp::bottleneck_variant(st.bn);
+    if (st.op != HP_OP_CONV || st.first)
+        return 0;
+    if (!st.f32)
+        return i8_on(st) ? hp::conv_i8_tile(st.cp) : hp::conv_mfma_tile(st.cp);
+    return st.head32 ? hp::conv32_head_tile(st.hh.HID, st.cp32.Cout)
+        : st.wino    ? hp::conv32_winograd_tile(st.cp32)
+        : st.cin_split ? hp::conv32_direct_tile(st.cp32, dtype == HP_DTYPE_F32S && !split_off)
+                     : hp::conv32_tile(st.cp32, switches);
+}
+
+int hp_engine::stage_profile_input()
+{
+    const size_t need = (size_t)max_batch * in_h * in_w * 3 * sizeof(float); // (only timing matters)
+    if (in_stage.bytes < need)
+        HP_TRY(in_stage.alloc(need));
     return HP_OK;
 }
 
@@ -1981,12 +2136,30 @@ int hp_engine::enqueue(const uint8_t* u8, const float* f32, int n, hipStream_t s
     return HP_OK;
 }
 
+hp::engine_switches hp::read_engine_switches()
+{
+    auto on = [](const char* name) { return getenv(name) != nullptr; };
+    auto num = [](const char* name, int unset) { const char* v = getenv(name); return v ? atoi(v) : unset; };
+    engine_switches w;
+    w.no_fuse = on("HP_NO_FUSE"), w.no_fuse_head = num("HP_NO_FUSE_HEAD", 0) != 0, w.no_splitk = on("HP_NO_SPLITK");
+    w.no_chain = on("HP_NO_CHAIN"), w.no_bneck = on("HP_NO_BNECK"), w.no_seppair = on("HP_NO_SEPPAIR"), w.no_pair_heads = on("HP_NO_PAIR_HEADS");
+    w.fuse32 = on("HP_FUSE32"), w.no_fuse32 = on("HP_NO_FUSE32"), w.no_head32 = on("HP_NO_HEAD32"), w.no_arena = on("HP_NO_ARENA");
+    w.no_winograd32 = on("HP_NO_WINOGRAD32"), w.wino_f33 = num("HP_WINO_F33", 0) == 1, w.wino_tall = num("HP_WINO_TALL", 1) != 0;
+    w.wino_nc = num("HP_WINO_NC", 0), w.head_pair32 = num("HP_HEAD_PAIR", 1) != 0;
+    w.c32_wk = num("HP_C32_WK", -1), w.c32_bn160 = num("HP_C32_BN160", -1), w.dw32_px = num("HP_DW32_PX", 0);
+    w.lane_epilogue = num("HP_LANE_EPILOGUE", 0), w.first_conv_verify = on("HP_FIRST_CONV_VERIFY");
+    w.dbg_conv = on("HP_CONV_DBG"), w.dbg_bn = on("HP_BN_DBG"), w.dbg_chain = on("HP_CHAIN_DBG"), w.dbg_sep = on("HP_SEP_DBG");
+    w.dbg_direct = on("HP_DIRECT_DBG"), w.dbg_min_cin = num("HP_DIRECT_DBG_MINCIN", 256);
+    return w;
+}
+
 extern "C" {
 
 int hp_engine_create(hp_engine** out, const hp_engine_desc* desc)
 {
     HP_REQUIRE(out && desc, HP_ERR_INVALID, "hp_engine_create: null argument");
     std::unique_ptr<hp_engine> e(new hp_engine());
+    e->switches = hp::read_engine_switches();
     try { // descriptions come from files (hp_engine_load, ONNX import): absurd sizes must come back as error codes
         HP_TRY(e->build(desc));
     } catch (const std::exception& ex) {
@@ -2444,10 +2617,7 @@ int hp_engine_debug_tensor(hp_engine* e, int tensor, int n, float* host, int sha
 int hp_engine_profile(hp_engine* e, int n, int iters, hp_layer_time* out, int cap, int* n_out)
 {
     HP_REQUIRE(e && n >= 1 && n <= e->max_batch && iters >= 1 && n_out, HP_ERR_INVALID, "hp_engine_profile: bad argument");
-    // a zero-filled synthetic input: only timing matters here
-    const size_t need = (size_t)e->max_batch * e->in_h * e->in_w * 3 * sizeof(float);
-    if (e->in_stage.bytes < need)
-        HP_TRY(e->in_stage.alloc(need));
+    HP_TRY(e->stage_profile_input());
     const uint8_t* u8 = e->in_stage.as<uint8_t>();
     int k = 0;
     for (auto& st : e->steps) {
@@ -2461,12 +2631,7 @@ int hp_engine_profile(hp_engine* e, int n, int iters, hp_layer_time* out, int ca
         HP_HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
         if (out && k < cap) {
             out[k].layer = st.layer, out[k].op = st.op;
-            out[k].tile = st.op == OP_SEPCONV ? 4000000 + (st.sep_pair ? 20 : hp::sepconv_variant(st.sp))
-                : st.op == OP_MLPHEAD        ? 6000000 + st.hp_.K1
-                : st.op == OP_CHAIN          ? 7000000 + hp::conv_chain_variant(st.ch)
-                : st.op == OP_BNECK          ? 9000000 + hp::bottleneck_variant(st.bn)
-                : (st.op == HP_OP_CONV && !st.first) ? (st.f32 ? (st.head32 ? hp::conv32_head_tile(st.hh.HID, st.cp32.Cout) : st.wino ? hp::conv32_winograd_tile(st.cp32) : st.cin_split ? hp::conv32_direct_tile(st.cp32, e->dtype == HP_DTYPE_F32S && !e->split_off) : hp::conv32_tile(st.cp32)) : e->i8_on(st) ? hp::conv_i8_tile(st.cp) : hp::conv_mfma_tile(st.cp))
-                                                    : 0;
+            out[k].tile = e->step_tile(st);
             out[k].ms = ms / iters;
             out[k].flops = st.flops * n, out[k].bytes = st.bytes * n;
         }
@@ -2487,10 +2652,8 @@ int hp_engine_profile_pair(hp_engine* e, hp_engine* f, int n, int iters, hp_laye
         HP_REQUIRE(e->steps[i].op == f->steps[i].op && e->steps[i].layer == f->steps[i].layer && e->steps[i].flops == f->steps[i].flops
                 && e->steps[i].bytes == f->steps[i].bytes,
             HP_ERR_INVALID, "hp_engine_profile_pair: the engines' schedules differ at step %zu", i);
-    const size_t need = (size_t)e->max_batch * e->in_h * e->in_w * 3 * sizeof(float);
-    for (hp_engine* g : { e, f })
-        if (g->in_stage.bytes < need)
-            HP_TRY(g->in_stage.alloc(need));
+    HP_TRY(e->stage_profile_input());
+    HP_TRY(f->stage_profile_input());
     int k = 0;
     for (size_t i = 0; i < e->steps.size(); ++i) {
         auto &sa = e->steps[i], &sb = f->steps[i];
@@ -2514,12 +2677,7 @@ int hp_engine_profile_pair(hp_engine* e, hp_engine* f, int n, int iters, hp_laye
         if (out && k < cap) {
             auto& st = sa;
             out[k].layer = st.layer, out[k].op = st.op;
-            out[k].tile = st.op == OP_SEPCONV ? 4000000 + (st.sep_pair ? 20 : hp::sepconv_variant(st.sp))
-                : st.op == OP_MLPHEAD        ? 6000000 + st.hp_.K1
-                : st.op == OP_CHAIN          ? 7000000 + hp::conv_chain_variant(st.ch)
-                : st.op == OP_BNECK          ? 9000000 + hp::bottleneck_variant(st.bn)
-                : (st.op == HP_OP_CONV && !st.first) ? (st.f32 ? (st.head32 ? hp::conv32_head_tile(st.hh.HID, st.cp32.Cout) : st.wino ? hp::conv32_winograd_tile(st.cp32) : st.cin_split ? hp::conv32_direct_tile(st.cp32, e->dtype == HP_DTYPE_F32S && !e->split_off) : hp::conv32_tile(st.cp32)) : e->i8_on(st) ? hp::conv_i8_tile(st.cp) : hp::conv_mfma_tile(st.cp))
-                                                    : 0;
+            out[k].tile = e->step_tile(st);
             out[k].ms = std::max(m0, m1) / (2 * iters);
             out[k].flops = st.flops * n, out[k].bytes = st.bytes * n;
         }
@@ -2532,9 +2690,7 @@ int hp_engine_profile_pair(hp_engine* e, hp_engine* f, int n, int iters, hp_laye
 int hp_engine_profile_sequence(hp_engine* e, int n, int iters, hp_layer_time* out, int cap, int* n_out)
 {
     HP_REQUIRE(e && n >= 1 && n <= e->max_batch && iters >= 1 && n_out, HP_ERR_INVALID, "hp_engine_profile_sequence: bad argument");
-    const size_t need = (size_t)e->max_batch * e->in_h * e->in_w * 3 * sizeof(float);
-    if (e->in_stage.bytes < need)
-        HP_TRY(e->in_stage.alloc(need));
+    HP_TRY(e->stage_profile_input());
     const uint8_t* u8 = e->in_stage.as<uint8_t>();
     const size_t ns = e->steps.size();
     // one (start, stop) event pair per step; the launch itself records them (hipExtLaunchKernelGGL), so they bracket the
@@ -2572,12 +2728,7 @@ int hp_engine_profile_sequence(hp_engine* e, int n, int iters, hp_layer_time* ou
     for (auto& st : e->steps) {
         if (out && k < cap) {
             out[k].layer = st.layer, out[k].op = st.op;
-            out[k].tile = st.op == OP_SEPCONV ? 4000000 + (st.sep_pair ? 20 : hp::sepconv_variant(st.sp))
-                : st.op == OP_MLPHEAD        ? 6000000 + st.hp_.K1
-                : st.op == OP_CHAIN          ? 7000000 + hp::conv_chain_variant(st.ch)
-                : st.op == OP_BNECK          ? 9000000 + hp::bottleneck_variant(st.bn)
-                : (st.op == HP_OP_CONV && !st.first) ? (st.f32 ? (st.head32 ? hp::conv32_head_tile(st.hh.HID, st.cp32.Cout) : st.wino ? hp::conv32_winograd_tile(st.cp32) : st.cin_split ? hp::conv32_direct_tile(st.cp32, e->dtype == HP_DTYPE_F32S && !e->split_off) : hp::conv32_tile(st.cp32)) : e->i8_on(st) ? hp::conv_i8_tile(st.cp) : hp::conv_mfma_tile(st.cp))
-                                                    : 0;
+            out[k].tile = e->step_tile(st);
             out[k].ms = (float)(acc[k] / iters);
             out[k].flops = st.flops * n, out[k].bytes = st.bytes * n;
         }

@@ -99,6 +99,38 @@ struct host_buf {
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// The engine's environment switches ("Engine switches"), read once by read_engine_switches() when hp_engine_create or
+// hp_engine_load makes an engine: its schedule, its launches and the graphs it captures follow the environment of that moment.  Host-only:
+// the launchers and pickers that consult one get it as an argument.  Unset = the default below.
+struct engine_switches {
+    bool no_fuse = false;        // HP_NO_FUSE: no fused launches (separable blocks, heads, chains, bottlenecks, pairs)
+    bool no_fuse_head = false;   // HP_NO_FUSE_HEAD: fp16 heads as two launches (mlp_head_variant)
+    bool no_splitk = false;      // HP_NO_SPLITK: fp16 convolutions without split-K
+    bool no_chain = false;       // HP_NO_CHAIN: no conv_chain launches
+    bool no_bneck = false;       // HP_NO_BNECK: no bottleneck launches
+    bool no_seppair = false;     // HP_NO_SEPPAIR: no two-block separable launches
+    bool no_pair_heads = false;  // HP_NO_PAIR_HEADS: fp16 sibling heads as two launches
+    bool fuse32 = false;         // HP_FUSE32: depthwise + pointwise fusion on HP_DTYPE_F32 engines too (always on for F32S)
+    bool no_fuse32 = false;      // HP_NO_FUSE32: no depthwise + pointwise fusion on fp32 engines
+    bool no_head32 = false;      // HP_NO_HEAD32: fp32 1 x 1 head pairs as two launches
+    bool no_arena = false;       // HP_NO_ARENA: every fp32 activation tensor in its own allocation
+    bool no_winograd32 = false;  // HP_NO_WINOGRAD32: no fp32 Winograd layers
+    bool wino_f33 = false;       // HP_WINO_F33=1: F(3 x 3, 3 x 3) where it applies (opt-in)
+    bool wino_tall = true;       // HP_WINO_TALL=0: the per-image Winograd form instead of the tall one
+    int wino_nc = 0;             // HP_WINO_NC=1 | 2: force the Winograd column tiles per block (0: by the engine's mode)
+    bool head_pair32 = true;     // HP_HEAD_PAIR=0: fp32 sibling heads as two launches instead of one grid
+    int c32_wk = -1;             // HP_C32_WK: 0 = no conv32_wk_kernel, 1 = every layer of its shape, -1 = by size
+    int c32_bn160 = -1;          // HP_C32_BN160: 0 = no 64 x 160 tiles, 1 | 176 = every layer on 64 x 160 | 64 x 176, -1 = by size
+    int dw32_px = 0;             // HP_DW32_PX: 1 = one depthwise column per thread, 2 = column pairs always, 0 = by size
+    int lane_epilogue = 0;       // HP_LANE_EPILOGUE: conv32_params::lane_epilogue
+    bool first_conv_verify = false; // HP_FIRST_CONV_VERIFY: first_conv32_kernel compares its LDS with global memory (first_conv32_verify_counts)
+    // block timelines printed per launch (s_memtime stamps; tools/*_timeline.py)
+    bool dbg_conv = false, dbg_bn = false, dbg_chain = false, dbg_sep = false; // HP_CONV_DBG, HP_BN_DBG, HP_CHAIN_DBG, HP_SEP_DBG
+    bool dbg_direct = false;     // HP_DIRECT_DBG: the fp32 direct, Winograd and conv32 kernels
+    int dbg_min_cin = 256;       // HP_DIRECT_DBG_MINCIN: conv32 layers with fewer input channels print nothing
+};
+engine_switches read_engine_switches();
+
 // Host worker pool for the order-dependent parser tails (PoseProposal limb selection / merge, PifPaf grow / soft-NMS): frames are
 // independent, so hp_*_collect hands frame indices to a few persistent threads, the way the reference replicates its parser per
 // pool thread (include/hyperpose/utility/thread_pool.hpp:21, include/hyperpose/stream/stream.hpp:139-144).  The calling thread
