@@ -7,6 +7,9 @@
 //   * media: binary PPM (P6) images - one file, or every *.ppm of a directory - and `synthetic:<n>:<w>x<h>` (seeded frames); results are
 //     written as `<saving_prefix>_<id>.ppm` with the skeletons drawn (hp::draw_human) and blended with weight alpha.  With OpenCV
 //     (-DHYPERPOSE_USE_OPENCV) any cv::imread format works; videos / the camera need cv::VideoCapture and are refused without it.
+//   * video frames (addition): `--source=<file>.yuv` reads raw planar YUV 4:2:0 (I420, e.g. `ffmpeg -pix_fmt yuv420p -f rawvideo`) frames of
+//     `--yuv_w` x `--yuv_h`; `--yuv` converts any other source to NV12 first.  Either way the operator runtime hands the engine
+//     hyperpose::yuv420_frame batches (colour conversion fused into the resize on the GPU); the BGR pictures are only drawn on.
 //   * `--model`: .onnx, a serialized engine (anything else), or `builtin:<arch>` (hp_model_archs(); synthetic weights).
 // build: g++ -std=c++17 -O2 -Iinclude examples/cli.cpp -Lhyperpose_amd -lhp_hip -lpthread -Wl,-rpath,$PWD/hyperpose_amd -o hyperpose-cli
 #include <hyperpose/hyperpose.hpp>
@@ -42,6 +45,8 @@ static std::string FLAGS_saving_prefix = "output";
 static bool FLAGS_logging = false;
 static bool FLAGS_half = false; // addition: data_type::kHALF engines (the reference CLI always builds data_type::kFLOAT ones)
 static bool FLAGS_int8 = false; // addition: data_type::kINT8 engines, calibrated on the first batch of the source
+static bool FLAGS_yuv = false;  // addition: feed the engine YUV 4:2:0 frames (dnn::tensorrt::inference(std::vector<yuv420_frame>)); implied by a .yuv source
+static int FLAGS_yuv_w = 0, FLAGS_yuv_h = 0; // frame size of a raw .yuv source
 
 static std::ostream& cli_log() { return std::cout << "[HyperPose::CLI] "; }
 
@@ -49,8 +54,9 @@ static bool parse_flags(int argc, char** argv)
 {
     std::map<std::string, std::string*> sflags = { { "model", &FLAGS_model }, { "post", &FLAGS_post }, { "source", &FLAGS_source },
         { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix } };
-    std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size } };
-    std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 } };
+    std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size },
+        { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h } };
+    std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 }, { "yuv", &FLAGS_yuv } };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a.rfind("--", 0) != 0 && a.rfind("-", 0) == 0)
@@ -152,6 +158,56 @@ static void add_weighted(cv::Mat& mat, double alpha, const cv::Mat& background)
         d[i] = (uint8_t)std::min(255.0, std::max(0.0, v));
     }
 }
+// ---- YUV 4:2:0 frames (host side; the engine converts on the GPU, these helpers only make inputs and pictures to draw on)
+struct yuv_buffer {
+    int format = HP_YUV_NV12, w = 0, h = 0;
+    std::vector<uint8_t> data; // w*h*3/2 bytes, tightly packed
+    hp::yuv420_frame frame() const { return hp::yuv420_frame::packed(format, data.data(), w, h); }
+};
+static std::vector<yuv_buffer> g_yuv; // one per image, same order, when the engine is fed YUV
+
+// BT.601 limited range, chroma = mean of its 2 x 2 pixels (what an encoder's input conversion does)
+static yuv_buffer bgr_to_nv12(const cv::Mat& m)
+{
+    yuv_buffer out;
+    out.format = HP_YUV_NV12, out.w = m.cols, out.h = m.rows;
+    out.data.resize((size_t)m.cols * m.rows * 3 / 2);
+    const uint8_t* d = hp::detail::mat_data(m);
+    const int w = m.cols, h = m.rows;
+    auto q = [](double v) { return (uint8_t)std::min(255.0, std::max(0.0, std::nearbyint(v))); };
+    for (int y = 0; y < h; y += 2)
+        for (int x = 0; x < w; x += 2) {
+            double su = 0, sv = 0;
+            for (int dy = 0; dy < 2; ++dy)
+                for (int dx = 0; dx < 2; ++dx) {
+                    const uint8_t* p = d + ((size_t)(y + dy) * w + x + dx) * 3;
+                    const double b = p[0], g = p[1], r = p[2];
+                    out.data[(size_t)(y + dy) * w + x + dx] = q(16.0 + (65.481 * r + 128.553 * g + 24.966 * b) / 255.0);
+                    su += 128.0 + (-37.797 * r - 74.203 * g + 112.0 * b) / 255.0;
+                    sv += 128.0 + (112.0 * r - 93.786 * g - 18.214 * b) / 255.0;
+                }
+            uint8_t* c = out.data.data() + (size_t)w * h + (size_t)(y / 2) * w + x;
+            c[0] = q(su / 4), c[1] = q(sv / 4);
+        }
+    return out;
+}
+// cv::cvtColor(COLOR_YUV2BGR_I420): the picture the skeletons are drawn on
+static cv::Mat i420_to_bgr(const yuv_buffer& f)
+{
+    cv::Mat m(f.h, f.w, CV_8UC3);
+    uint8_t* d = const_cast<uint8_t*>(hp::detail::mat_data(m));
+    const uint8_t *Y = f.data.data(), *U = Y + (size_t)f.w * f.h, *V = U + (size_t)(f.w / 2) * (f.h / 2);
+    auto sat = [](int v) { return (uint8_t)std::min(255, std::max(0, v)); };
+    for (int y = 0; y < f.h; ++y)
+        for (int x = 0; x < f.w; ++x) {
+            const size_t c = (size_t)(y / 2) * (f.w / 2) + x / 2;
+            const int yy = std::max(0, Y[(size_t)y * f.w + x] - 16) * 1220542 + (1 << 19), u = U[c] - 128, v = V[c] - 128;
+            uint8_t* p = d + ((size_t)y * f.w + x) * 3;
+            p[0] = sat((yy + 2116026 * u) >> 20), p[1] = sat((yy - 852492 * v - 409993 * u) >> 20), p[2] = sat((yy + 1673527 * v) >> 20);
+        }
+    return m;
+}
+
 static std::vector<cv::Mat> load_source()
 {
     std::vector<cv::Mat> images;
@@ -176,6 +232,25 @@ static std::vector<cv::Mat> load_source()
     if (match_suffix(".jpg") || match_suffix(".jpeg") || match_suffix(".png"))
         return { cv::imread(FLAGS_source) };
 #endif
+    if (match_suffix(".yuv")) { // raw I420 frames, back to back
+        if (FLAGS_yuv_w <= 0 || FLAGS_yuv_h <= 0 || FLAGS_yuv_w % 2 || FLAGS_yuv_h % 2) {
+            cli_log() << "ERROR: a .yuv source needs --yuv_w and --yuv_h (even numbers): raw video carries no header\n";
+            return {};
+        }
+        std::ifstream f(FLAGS_source, std::ios::binary);
+        const size_t bytes = (size_t)FLAGS_yuv_w * FLAGS_yuv_h * 3 / 2;
+        for (;;) {
+            yuv_buffer b;
+            b.format = HP_YUV_I420, b.w = FLAGS_yuv_w, b.h = FLAGS_yuv_h;
+            b.data.resize(bytes);
+            if (!f.read((char*)b.data.data(), bytes))
+                break;
+            images.push_back(i420_to_bgr(b));
+            g_yuv.push_back(std::move(b));
+        }
+        FLAGS_yuv = true;
+        return images;
+    }
     if (match_suffix(".ppm")) {
         cv::Mat m;
         if (read_ppm(FLAGS_source, m))
@@ -266,6 +341,19 @@ int main(int argc, char** argv)
                   << ")" << std::endl;
         std::exit(-1);
     }
+    if (FLAGS_yuv && g_yuv.empty()) { // --yuv on a BGR source: the frames as a hardware decoder would deliver them
+        for (const auto& m : images) {
+            if (m.cols % 2 || m.rows % 2) {
+                cli_log() << "ERROR: --yuv needs frames of even width and height (4:2:0), got " << m.cols << " x " << m.rows << "\n";
+                return 1;
+            }
+            g_yuv.push_back(bgr_to_nv12(m));
+        }
+    }
+    if (FLAGS_yuv && FLAGS_runtime == kSTREAM) {
+        cli_log() << "WARNING: the stream runtime carries cv::Mat frames (stream.hpp); YUV frames go through --runtime=" kOPERATOR "\n";
+        FLAGS_runtime = kOPERATOR;
+    }
     if (FLAGS_imshow) {
         FLAGS_imshow = false;
         cli_log() << "--imshow needs a display and OpenCV's highgui: results go to files only\n";
@@ -274,7 +362,13 @@ int main(int argc, char** argv)
     auto engine = build_engine();
     if (FLAGS_int8 && !engine.calibrated()) { // calibration is never implicit in the engine: the CLI asks for it and says so
         const size_t n = std::min(images.size(), (size_t)FLAGS_max_batch_size);
-        engine.calibrate(std::vector<cv::Mat>(images.begin(), images.begin() + n));
+        if (FLAGS_yuv) {
+            std::vector<hp::yuv420_frame> frames;
+            for (size_t i = 0; i < n; ++i)
+                frames.push_back(g_yuv[i].frame());
+            engine.calibrate(frames);
+        } else
+            engine.calibrate(std::vector<cv::Mat>(images.begin(), images.begin() + n));
         std::cerr << "--int8: calibrated the kINT8 engine on the first " << n << " frame(s) of the source (MinMax)" << std::endl;
     }
     any_parser parser = build_parser(engine);
@@ -306,7 +400,11 @@ int main(int argc, char** argv)
         const size_t step = (size_t)std::max(1, FLAGS_max_batch_size);
         for (size_t first = 0; first < images.size(); first += step) {
             std::vector<cv::Mat> batch(images.begin() + first, images.begin() + std::min(images.size(), first + step));
-            const auto maps = engine.inference(batch);
+            std::vector<hp::yuv420_frame> yuv_batch;
+            if (FLAGS_yuv)
+                for (size_t k = 0; k < batch.size(); ++k)
+                    yuv_batch.push_back(g_yuv[first + k].frame());
+            const auto maps = FLAGS_yuv ? engine.inference(yuv_batch) : engine.inference(batch);
             for (size_t k = 0; k < batch.size(); ++k) {
                 const auto poses = std::visit([&](auto& op) { return op.process(maps[k]); }, parser);
                 render(batch[k], poses, FLAGS_keep_ratio);

@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(HERE, "libhp_hip.so")
 
 HP_OK = 0
 HP_ERR_INVALID, HP_ERR_HIP, HP_ERR_CAPACITY, HP_ERR_STATE, HP_ERR_NO_DEVICE = -1, -2, -3, -4, -5
+HP_YUV_NV12, HP_YUV_I420 = 0, 1
+YUV_FORMATS = {"nv12": HP_YUV_NV12, "i420": HP_YUV_I420}
 
 
 class HpError(RuntimeError):
@@ -51,6 +53,7 @@ _lib = None
 SYMBOLS = [
     "hp_init", "hp_device_count", "hp_last_error", "hp_version", "hp_malloc", "hp_free", "hp_malloc_host",
     "hp_free_host", "hp_memcpy_h2d", "hp_memcpy_d2h", "hp_device_synchronize", "hp_stream_wait_stream", "hp_dist_unique_id", "hp_dist_init", "hp_dist_destroy", "hp_dist_broadcast_weights", "hp_dist_shard", "hp_preproc_u8hwc_to_f32nchw", "hp_resize_u8c3", "hp_letterbox_u8c3", "hp_letterbox_inner", "hp_resume_ratio",
+    "hp_resize_yuv420", "hp_letterbox_yuv420", "hp_pipeline_submit_yuv",
     "hp_paf_create", "hp_paf_stream", "hp_paf_destroy", "hp_paf_set_conf_thresh", "hp_paf_set_paf_thresh", "hp_paf_process_batch",
     "hp_paf_enqueue", "hp_paf_collect", "hp_paf_debug_peaks", "hp_paf_debug_conns", "hp_paf_debug_maps", "hp_paf_debug_sort",
     "hp_pifpaf_create", "hp_pifpaf_destroy", "hp_pifpaf_process_batch", "hp_pifpaf_stream", "hp_pifpaf_enqueue", "hp_pifpaf_collect", "hp_pifpaf_decode_flags",

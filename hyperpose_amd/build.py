@@ -26,6 +26,8 @@ UNITS = [
     ("hp_runtime.cpp", []),
     ("preproc.hip", ["-ffp-contract=off"]),
     ("resize.hip", ["-ffp-contract=off"]),
+    # -fno-slp-vectorize, as for conv_fp32.hip below: the coefficient derivation is fp32 and runs next to the engines' kernels
+    ("resize_yuv.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("paf_parser.hip", ["-ffp-contract=off"]),
     ("ppn_parser.hip", ["-ffp-contract=off"]),
     ("pifpaf_parser.hip", ["-ffp-contract=off"]),

@@ -5,6 +5,8 @@
 // (paf_parser.hip) are enqueued back to back on ONE HIP stream of one of `n_pipes` engine+parser pairs, and only the
 // humans come back.  Several batches are in flight (one per pipe); results are returned in submission order, like the
 // reference's queues.  resume_ratio is applied on the way out when the aspect ratio was kept.
+// Frames arrive as 8-bit BGR (hp_pipeline_submit) or as YUV 4:2:0 video frames (hp_pipeline_submit_yuv: half the bytes over PCIe, colour
+// conversion fused into the resize, resize_yuv.hip); both end in infer_and_parse().
 #include "hp_common.hpp"
 
 #include <cstring>
@@ -24,6 +26,16 @@ struct pipe_t {
     int n = 0;              // frames in flight (0 = free)
     std::vector<int> w, h;
 };
+
+// pinned memory (hp_malloc_host / hipHostMalloc) is copied straight from where it lies; anything else through staging
+bool is_pinned(const void* ptr)
+{
+    hipPointerAttribute_t attr;
+    const bool pinned = hipPointerGetAttributes(&attr, ptr) == hipSuccess && attr.type == hipMemoryTypeHost;
+    if (!pinned)
+        (void)hipGetLastError();
+    return pinned;
+}
 
 } // namespace
 
@@ -49,6 +61,10 @@ struct hp_pipeline {
         }
     }
 };
+
+namespace {
+int infer_and_parse(hp_pipeline* pl, pipe_t& p, int n);
+}
 
 extern "C" {
 
@@ -129,11 +145,7 @@ int hp_pipeline_submit(hp_pipeline* pl, const uint8_t* const* frames, const int*
         HP_REQUIRE(bytes <= pl->max_frame_bytes, HP_ERR_CAPACITY, "hp_pipeline_submit: frame %d (%dx%d) exceeds max_frame_bytes %zu", i,
             widths[i], heights[i], pl->max_frame_bytes);
         offs[i] = off;
-        // pinned memory (hp_malloc_host / hipHostMalloc) is copied straight from where it lies; anything else through staging
-        hipPointerAttribute_t attr;
-        const bool pinned = hipPointerGetAttributes(&attr, frames[i]) == hipSuccess && attr.type == hipMemoryTypeHost;
-        if (!pinned)
-            (void)hipGetLastError();
+        const bool pinned = is_pinned(frames[i]);
         const uint8_t* src = frames[i];
         if (!pinned) {
             memcpy(p.stage.as<uint8_t>() + off, frames[i], bytes);
@@ -168,6 +180,63 @@ int hp_pipeline_submit(hp_pipeline* pl, const uint8_t* const* frames, const int*
         else
             HP_TRY(hp_resize_u8c3(src, p.w[i], p.h[i], p.w[i] * 3, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
     }
+    return infer_and_parse(pl, p, n);
+}
+
+int hp_pipeline_submit_yuv(hp_pipeline* pl, int format, const uint8_t* const* frames, const int* widths, const int* heights, int n)
+{
+    HP_REQUIRE(pl && frames && widths && heights, HP_ERR_INVALID, "hp_pipeline_submit_yuv: null argument");
+    HP_REQUIRE(format == HP_YUV_NV12 || format == HP_YUV_I420, HP_ERR_INVALID, "hp_pipeline_submit_yuv: unknown format %d", format);
+    HP_REQUIRE(n >= 1 && n <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_submit_yuv: batch %d > max_batch %d", n, pl->max_batch);
+    HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "hp_pipeline_submit_yuv: all %d pipes are busy, collect first", pl->n_pipes);
+    pipe_t& p = pl->pipes[pl->head];
+    const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
+    for (int i = 0; i < n; ++i) { // everything is checked before the first copy is enqueued
+        HP_REQUIRE(frames[i] && widths[i] > 0 && heights[i] > 0, HP_ERR_INVALID, "hp_pipeline_submit_yuv: frame %d is empty", i);
+        HP_REQUIRE(widths[i] % 2 == 0 && heights[i] % 2 == 0, HP_ERR_INVALID, "hp_pipeline_submit_yuv: frame %d is %d x %d, 4:2:0 frames need even sizes", i,
+            widths[i], heights[i]);
+        HP_REQUIRE((size_t)widths[i] * heights[i] * 3 / 2 <= pl->max_frame_bytes, HP_ERR_CAPACITY, "hp_pipeline_submit_yuv: frame %d (%dx%d) exceeds max_frame_bytes %zu", i,
+            widths[i], heights[i], pl->max_frame_bytes);
+    }
+    // all copies first, then all kernels, as the BGR submit does: the stream changes between the copy engine and the compute queue once
+    // per batch, not once per frame.  One copy of the 1.5-byte form per frame; the fused conversion + resize then writes the network's
+    // slot - a network-sized frame takes the same road (the kernel converts and nothing else): there is no BGR form of it anywhere to copy
+    size_t off = 0;
+    std::vector<size_t> offs(n);
+    for (int i = 0; i < n; ++i) {
+        const size_t bytes = (size_t)widths[i] * heights[i] * 3 / 2;
+        const uint8_t* src = frames[i];
+        if (!is_pinned(frames[i])) {
+            memcpy(p.stage.as<uint8_t>() + off, frames[i], bytes);
+            src = p.stage.as<uint8_t>() + off;
+        }
+        HP_HIP_TRY(hipMemcpyAsync(p.raw.as<uint8_t>() + off, src, bytes, hipMemcpyHostToDevice, p.s));
+        offs[i] = off, p.w[i] = widths[i], p.h[i] = heights[i];
+        off += (bytes + 255) & ~(size_t)255;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int w = p.w[i], h = p.h[i];
+        const size_t luma = (size_t)w * h;
+        const uint8_t* raw = p.raw.as<uint8_t>() + offs[i];
+        uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * net_frame;
+        const uint8_t *u = raw + luma, *v = format == HP_YUV_I420 ? u + luma / 4 : nullptr;
+        const int uv_stride = format == HP_YUV_NV12 ? w : w / 2;
+        if (pl->keep_ratio)
+            HP_TRY(hp_letterbox_yuv420(format, raw, w, u, v, uv_stride, w, h, dst, pl->in_w, pl->in_h, pl->in_w * 3, 0, 0, 0, p.s));
+        else
+            HP_TRY(hp_resize_yuv420(format, raw, w, u, v, uv_stride, w, h, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
+    }
+    return infer_and_parse(pl, p, n);
+}
+
+} // extern "C"
+
+namespace {
+
+// the part of a submit that does not depend on how the frames arrived: p.net holds n network-sized BGR frames (in stream order on p.s)
+// -> conv stack -> the pipeline's parser, and the pipe joins the ring of batches in flight
+int infer_and_parse(hp_pipeline* pl, pipe_t& p, int n)
+{
     HP_TRY(hp_engine_infer_u8(p.eng, p.net.as<uint8_t>(), n, 1, p.s));
     const char* name = nullptr;
     if (pl->kind == HP_PARSER_PAF) {
@@ -201,6 +270,10 @@ int hp_pipeline_submit(hp_pipeline* pl, const uint8_t* const* frames, const int*
     ++pl->inflight;
     return HP_OK;
 }
+
+} // namespace
+
+extern "C" {
 
 int hp_pipeline_collect(hp_pipeline* pl, hp_human* out, int cap_per_frame, int* n_out, int* n_frames)
 {

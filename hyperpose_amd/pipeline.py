@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import HUMAN_DTYPE, Human, check, lib
+from ._lib import HUMAN_DTYPE, YUV_FORMATS, Human, check, lib
 from .engine import _DTYPES, EngineDesc, Layer, OutputDesc
 
 
@@ -76,6 +76,24 @@ class Pipeline:
     def submit_ptrs(self, ptrs, ws, hs, n: int) -> None:
         """Pre-marshalled form for hot loops (pinned frames allocated with hp_malloc_host)."""
         check(lib().hp_pipeline_submit(self._h, ptrs, ws, hs, n))
+
+    def submit_yuv(self, frames, fmt: str = "nv12") -> None:
+        """frames: list of [h*3/2, w] uint8 YUV 4:2:0 arrays (the layout cv2 and ffmpeg use: Y rows, then the chroma rows; even w and h),
+        ``fmt`` "nv12" or "i420".  They go up in their 1.5-byte form and are converted to BGR inside the resize kernel."""
+        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        n = len(frames)
+        for f in frames:
+            if f.ndim != 2 or f.shape[0] % 3:
+                raise ValueError(f"submit_yuv: a frame must be a [h*3/2, w] array, got shape {f.shape}")
+        ptrs = (C.POINTER(C.c_uint8) * n)(*[f.ctypes.data_as(C.POINTER(C.c_uint8)) for f in frames])
+        ws = (C.c_int * n)(*[f.shape[1] for f in frames])
+        hs = (C.c_int * n)(*[f.shape[0] * 2 // 3 for f in frames])
+        check(lib().hp_pipeline_submit_yuv(self._h, YUV_FORMATS[fmt], ptrs, ws, hs, n))
+        self._keep = frames
+
+    def submit_yuv_ptrs(self, fmt: str, ptrs, ws, hs, n: int) -> None:
+        """Pre-marshalled form of ``submit_yuv`` for hot loops (pinned frames allocated with hp_malloc_host)."""
+        check(lib().hp_pipeline_submit_yuv(self._h, YUV_FORMATS[fmt], ptrs, ws, hs, n))
 
     def collect(self):
         """Humans of the oldest batch in flight: list (per frame) of Human structure arrays."""

@@ -103,6 +103,32 @@ def images_u8(rng: np.random.Generator, batch: int, h: int, w: int) -> np.ndarra
     return rng.integers(0, 256, size=(batch, h, w, 3), dtype=np.uint8)
 
 
+def bgr_to_yuv420(frames: np.ndarray, fmt: str = "nv12") -> np.ndarray:
+    """BGR frames ``[..., h, w, 3]`` u8 (even h, w) -> YUV 4:2:0 frames ``[..., h*3/2, w]`` u8 in the layout decoders, cv2 and ffmpeg use:
+    ``h`` rows of Y, then ``h/2`` rows of interleaved (U, V) pairs ("nv12") or ``h/4`` rows holding the U plane and ``h/4`` the V plane
+    ("i420").  Float BT.601 limited-range forward transform, chroma = the mean of its 2 x 2 pixels, rounded.  Only an input generator for
+    tests and benchmarks: the conversion the library itself performs is the opposite direction (hp_resize_yuv420)."""
+    if fmt not in ("nv12", "i420"):
+        raise ValueError(f"bgr_to_yuv420: fmt {fmt!r} is not 'nv12' or 'i420'")
+    f = np.asarray(frames)
+    h, w = f.shape[-3], f.shape[-2]
+    if f.shape[-1] != 3 or h % 2 or w % 2:
+        raise ValueError(f"bgr_to_yuv420: frames must be [..., h, w, 3] with even h and w, got {f.shape}")
+    lead = f.shape[:-3]
+    b, g, r = (f[..., c].astype(np.float64) for c in range(3))
+    y = 16.0 + (65.481 * r + 128.553 * g + 24.966 * b) / 255.0
+    u = 128.0 + (-37.797 * r - 74.203 * g + 112.0 * b) / 255.0
+    v = 128.0 + (112.0 * r - 93.786 * g - 18.214 * b) / 255.0
+    sub = lambda p: p.reshape(*lead, h // 2, 2, w // 2, 2).mean(axis=(-3, -1))
+    q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)
+    y, u, v = q(y), q(sub(u)), q(sub(v))
+    if fmt == "nv12":
+        chroma = np.stack([u, v], axis=-1).reshape(*lead, h // 2, w)
+    else:
+        chroma = np.concatenate([u.reshape(*lead, -1), v.reshape(*lead, -1)], axis=-1).reshape(*lead, h // 2, w)  # U plane, then V plane
+    return np.ascontiguousarray(np.concatenate([y, chroma], axis=-2))
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # PoseProposal synthetic tensors (SURVEY.md 8d "PPN synthetic"): reference src/pose_proposal.cpp:12-41.
 COCOPAIR_STD = [(1, 8), (8, 9), (9, 10), (1, 11), (11, 12), (12, 13), (1, 2), (2, 3), (3, 4), (1, 5), (5, 6), (6, 7),

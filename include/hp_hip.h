@@ -112,6 +112,20 @@ void hp_letterbox_inner(int sw, int sh, int dw, int dh, int* inner_w, int* inner
 /* resume_ratio on n humans in place (host memory): undo the letterbox for (src = frame size, dst = network size) */
 void hp_resume_ratio(hp_human* humans, int n, int src_w, int src_h, int dst_w, int dst_h);
 
+/* ---- video frames as decoders deliver them: YUV 4:2:0 in DEVICE memory -> the same 8-bit BGR HWC result as "convert the whole frame
+ * with cv::cvtColor(COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_I420), then hp_resize_u8c3 / hp_letterbox_u8c3", bit for bit, in one kernel
+ * (hyperpose_amd/csrc/resize_yuv.hip).  Conversion is OpenCV's 8-bit fixed-point BT.601 limited-range form, chroma replicated over its
+ * 2 x 2 luma pixels (restated from the constants; parity unpinned: no OpenCV in the build image).  Planes are addressed by separate
+ * pointers and byte strides, so decoder surfaces with padded pitch work.  Width and height must be even (HP_ERR_INVALID otherwise).
+ *   HP_YUV_NV12  Y plane (sh rows), dev_u = ONE plane of sh/2 rows of sw/2 interleaved (U, V) byte pairs; dev_v is ignored
+ *   HP_YUV_I420  Y plane, dev_u and dev_v = two planes of sh/2 rows of sw/2 bytes, both with row stride uv_stride
+ * (values from 2 on are free for other sub-samplings, bit depths and matrices) */
+enum { HP_YUV_NV12 = 0, HP_YUV_I420 = 1 };
+int hp_resize_yuv420(int format, const uint8_t* dev_y, int y_stride, const uint8_t* dev_u, const uint8_t* dev_v, int uv_stride,
+                     int sw, int sh, uint8_t* dev_dst, int dw, int dh, int dst_stride, void* stream);
+int hp_letterbox_yuv420(int format, const uint8_t* dev_y, int y_stride, const uint8_t* dev_u, const uint8_t* dev_v, int uv_stride,
+                        int sw, int sh, uint8_t* dev_dst, int dw, int dh, int dst_stride, int b, int g, int r, void* stream);
+
 /* ---- hyperpose::parser::paf (include/hyperpose/operator/parser/paf.hpp:17-93, src/paf.cpp) -------- */
 typedef struct hp_paf hp_paf;
 
@@ -415,6 +429,11 @@ int hp_pipeline_create(hp_pipeline** out, const hp_engine_desc* desc, int n_pipe
 void hp_pipeline_destroy(hp_pipeline* p);
 /* HP_ERR_STATE when all pipes are busy (collect first) */
 int hp_pipeline_submit(hp_pipeline* p, const uint8_t* const* frames, const int* widths, const int* heights, int n);
+/* The same for YUV 4:2:0 frames (format = HP_YUV_NV12 / HP_YUV_I420): every frame is ONE contiguous, tightly packed buffer of
+ * width*height*3/2 bytes (Y plane, then the UV plane or the U and V planes), width and height even.  One H2D copy of the 1.5-byte form per
+ * frame, then the fused conversion + resize writes the network's slot (network-sized frames get the conversion alone).  max_frame_bytes
+ * bounds width*height*3/2 here.  BGR and YUV submits may alternate on one pipeline; hp_pipeline_collect does not tell them apart. */
+int hp_pipeline_submit_yuv(hp_pipeline* p, int format, const uint8_t* const* frames, const int* widths, const int* heights, int n);
 /* waits for the OLDEST batch in flight; out[i * cap_per_frame + j], n_out[i] for i < *n_frames */
 int hp_pipeline_collect(hp_pipeline* p, hp_human* out, int cap_per_frame, int* n_out, int* n_frames);
 int hp_pipeline_in_flight(const hp_pipeline* p);

@@ -10,7 +10,8 @@
 // calibrator over the given frames) or after loading a serialized engine that was calibrated; kINT32 / kBOOL have no meaning for these
 // networks and are refused like an engine-build failure.  Frames of any size are resized on
 // the DEVICE exactly as the reference does on the host: cv::resize (INTER_LINEAR) or, with keep_ratio, non_scaling_resize
-// (src/tensorrt.cpp:446-451, src/data.cpp:53-69) through hp_resize_u8c3 / hp_letterbox_u8c3.
+// (src/tensorrt.cpp:446-451, src/data.cpp:53-69) through hp_resize_u8c3 / hp_letterbox_u8c3.  Addition: inference / calibrate also take
+// std::vector<yuv420_frame> (NV12 / I420 video frames, utility/data.hpp), converted inside the resize kernel (hp_resize_yuv420).
 #pragma once
 #include <atomic>
 #include <cstdint>
@@ -189,6 +190,29 @@ namespace dnn {
             return collect(inputs.size());
         }
 
+        /// Addition: the same call for video frames in the decoder's own form (utility/data.hpp, yuv420_frame: NV12 or I420 in host memory).
+        /// Every frame is uploaded in its 1.5-byte form and brought to the network's size by the fused conversion + resize kernel
+        /// (hp_resize_yuv420, or hp_letterbox_yuv420 when keep_ratio): the maps equal those of the cv::Mat overload on the frames
+        /// converted with cv::cvtColor(COLOR_YUV2BGR_NV12 / _I420), bit for bit.  Same over-size-batch exception, same calibration rule.
+        std::vector<internal_t> inference(const std::vector<yuv420_frame>& inputs)
+        {
+            require_calibrated();
+            if (inputs.size() > (size_t)m_max_batch_size)
+                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(inputs.size()) + " Max@" + std::to_string(m_max_batch_size));
+            if (inputs.empty())
+                return {};
+            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
+            if (!m_dev_net && hp_malloc((void**)&m_dev_net, net_frame * m_max_batch_size) != HP_OK)
+                fatal(hp_last_error());
+            retire_last_batch();
+            std::vector<uint8_t> scratch;
+            for (size_t i = 0; i < inputs.size(); ++i)
+                yuv_frame_to_device(inputs[i], m_dev_net + i * net_frame, scratch);
+            if (hp_engine_infer_u8(m_engine, m_dev_net, (int)inputs.size(), 1, nullptr) != HP_OK)
+                fatal(hp_last_error());
+            return collect(inputs.size());
+        }
+
         /// data_type::kINT8: TensorRT's MinMax calibration (an IInt8MinMaxCalibrator fed with these frames).  Frames of any size are brought to
         /// the network's size exactly as inference() does; any number of frames (the engine runs them in max_batch_size chunks).  Replaces
         /// every per-layer activation scale; calibration is never implicit.
@@ -209,6 +233,26 @@ namespace dnn {
                     fatal("hyperpose::dnn::tensorrt::calibrate: empty image");
                 frame_to_device(frames[i], all + i * net_frame, scratch);
             }
+            const int rc = hp_device_synchronize() == HP_OK ? hp_engine_calibrate_u8(m_engine, all, (int)frames.size(), 1) : HP_ERR_HIP;
+            hp_free(all);
+            if (rc != HP_OK)
+                fatal(hp_last_error());
+        }
+        /// Addition: calibration from YUV 4:2:0 frames, brought to the network's size exactly as inference(std::vector<yuv420_frame>) does
+        void calibrate(const std::vector<yuv420_frame>& frames)
+        {
+            if (hp_engine_dtype(m_engine) != HP_DTYPE_I8)
+                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: only data_type::kINT8 engines are calibrated");
+            if (frames.empty())
+                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: no frames");
+            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
+            retire_last_batch();
+            uint8_t* all = nullptr;
+            if (hp_malloc((void**)&all, net_frame * frames.size()) != HP_OK)
+                fatal(hp_last_error());
+            std::vector<uint8_t> scratch;
+            for (size_t i = 0; i < frames.size(); ++i)
+                yuv_frame_to_device(frames[i], all + i * net_frame, scratch);
             const int rc = hp_device_synchronize() == HP_OK ? hp_engine_calibrate_u8(m_engine, all, (int)frames.size(), 1) : HP_ERR_HIP;
             hp_free(all);
             if (rc != HP_OK)
@@ -294,6 +338,47 @@ namespace dnn {
                       hp_engine_stream(m_engine))
                 : hp_resize_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3,
                       hp_engine_stream(m_engine));
+            if (rc != HP_OK || hp_engine_synchronize(m_engine) != HP_OK) // m_dev_raw is re-used by the next frame
+                fatal(hp_last_error());
+        }
+        // the same for a YUV 4:2:0 frame: its planes are packed without row padding into ONE upload of width*height*3/2 bytes, then the fused
+        // conversion + resize (or letterbox) writes dst; a network-sized frame gets the conversion alone
+        void yuv_frame_to_device(const yuv420_frame& f, uint8_t* dst, std::vector<uint8_t>& scratch)
+        {
+            if (f.empty() || (f.format == HP_YUV_I420 && !f.v))
+                fatal("hyperpose::dnn::tensorrt: empty YUV frame");
+            if (f.format != HP_YUV_NV12 && f.format != HP_YUV_I420)
+                throw std::logic_error("hyperpose: yuv420_frame::format must be HP_YUV_NV12 or HP_YUV_I420");
+            if (f.width % 2 || f.height % 2)
+                throw std::logic_error("hyperpose: YUV 4:2:0 frames need even width and height");
+            const bool nv12 = f.format == HP_YUV_NV12;
+            const size_t w = (size_t)f.width, h = (size_t)f.height, luma = w * h, bytes = luma * 3 / 2, crow = nv12 ? w : w / 2;
+            if ((size_t)f.y_stride < w || (size_t)f.uv_stride < crow)
+                throw std::logic_error("hyperpose: yuv420_frame stride smaller than a row");
+            scratch.resize(bytes);
+            for (size_t r = 0; r < h; ++r)
+                std::memcpy(scratch.data() + r * w, f.y + r * (size_t)f.y_stride, w);
+            for (size_t r = 0; r < h / 2; ++r) {
+                std::memcpy(scratch.data() + luma + r * crow, f.u + r * (size_t)f.uv_stride, crow);
+                if (!nv12)
+                    std::memcpy(scratch.data() + luma + luma / 4 + r * crow, f.v + r * (size_t)f.uv_stride, crow);
+            }
+            if (bytes > m_raw_bytes) {
+                if (m_dev_raw)
+                    hp_free(m_dev_raw);
+                m_dev_raw = nullptr, m_raw_bytes = 0;
+                if (hp_malloc((void**)&m_dev_raw, bytes) != HP_OK)
+                    fatal(hp_last_error());
+                m_raw_bytes = bytes;
+            }
+            if (hp_memcpy_h2d(m_dev_raw, scratch.data(), bytes) != HP_OK)
+                fatal(hp_last_error());
+            const uint8_t *du = m_dev_raw + luma, *dv = nv12 ? nullptr : du + luma / 4;
+            const int rc = m_keep_ratio
+                ? hp_letterbox_yuv420(f.format, m_dev_raw, f.width, du, dv, (int)crow, f.width, f.height, dst, m_inp_size.width, m_inp_size.height,
+                      m_inp_size.width * 3, 0, 0, 0, hp_engine_stream(m_engine))
+                : hp_resize_yuv420(f.format, m_dev_raw, f.width, du, dv, (int)crow, f.width, f.height, dst, m_inp_size.width, m_inp_size.height,
+                      m_inp_size.width * 3, hp_engine_stream(m_engine));
             if (rc != HP_OK || hp_engine_synchronize(m_engine) != HP_OK) // m_dev_raw is re-used by the next frame
                 fatal(hp_last_error());
         }

@@ -104,6 +104,31 @@ private:
 
 using internal_t = std::vector<feature_map_t>;
 
+/// Addition: one video frame as a decoder delivers it - YUV 4:2:0, 8 bits per sample, in HOST memory, planes addressed by their own
+/// pointers and row strides in bytes (decoder surfaces with padded pitch work; no OpenCV needed).  `format` is HP_YUV_NV12 (`u` = the
+/// plane of interleaved (U, V) pairs, `v` unused) or HP_YUV_I420 (`u`, `v` = two planes of height/2 rows of width/2 bytes).  width and
+/// height must be even.  dnn::tensorrt::inference / calibrate take a vector of these next to their cv::Mat forms; the frame goes to the
+/// device in its 1.5-byte form and is converted (cv::cvtColor COLOR_YUV2BGR_NV12 / _I420 arithmetic) inside the resize kernel.
+struct yuv420_frame {
+    int format = HP_YUV_NV12;
+    const uint8_t* y = nullptr;
+    const uint8_t* u = nullptr;
+    const uint8_t* v = nullptr;
+    int y_stride = 0, uv_stride = 0;
+    int width = 0, height = 0;
+    /// a contiguous, tightly packed frame of width*height*3/2 bytes (what cv2 / ffmpeg rawvideo hand out)
+    static yuv420_frame packed(int format, const uint8_t* data, int width, int height)
+    {
+        yuv420_frame f;
+        f.format = format, f.y = data, f.width = width, f.height = height, f.y_stride = width;
+        f.u = data + (size_t)width * height;
+        f.uv_stride = format == HP_YUV_NV12 ? width : width / 2;
+        f.v = format == HP_YUV_NV12 ? nullptr : f.u + (size_t)(width / 2) * (height / 2);
+        return f;
+    }
+    bool empty() const { return !y || !u || width <= 0 || height <= 0; }
+};
+
 // ---- free functions of the reference's data.hpp (:58-67), evaluated by the same device code as the engine's own pre-processing
 namespace detail {
     struct dev_ptr { // scoped hp_malloc
