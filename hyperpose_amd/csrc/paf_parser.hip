@@ -11,14 +11,17 @@
 //                          rows: up-sample (INTER_AREA semantics) -> 17-tap row filter through LDS ->
 //                          symmetric column filter out of a register window -> 3x3 max / threshold on a
 //                          4-row LDS ring; append peaks with an atomic.
-//   2. paf_sort_kernel     grid (18 parts, frames): rank-sort each part's peaks into the reference's scan
-//                          order so that peak ids equal the reference's running index.
-//   3. paf_limbs_kernel    grid (19 limbs, frames): the limb's two PAF source channels live in LDS; one
-//                          thread per (peak a, peak b) pair evaluates the 10-sample line integral by
-//                          interpolating the un-up-sampled PAF on the fly; rank-sort of the surviving
-//                          candidates and a wave-ballot greedy bipartite assignment.
-//   4. paf_assemble_kernel grid (frames): one wavefront walks the connections in reference order; the
-//                          "which humans touch this connection" scan is a ballot over up to 256 humans.
+//   2. paf_score_kernel    grid (64 + 18 blocks, frames): rank-sort of each part's peaks into the reference's scan
+//                          order, so that peak ids equal the reference's running index (the last 18 blocks);
+//                          then the frame's (peak a, peak b) pairs, limb after limb, in tiles dealt out to the
+//                          blocks: the limb's two PAF source channels live in LDS, one thread per pair
+//                          evaluates the 10-sample line integral by interpolating the un-up-sampled PAF on
+//                          the fly; the surviving candidates go to a per-limb list in device memory.
+//   3. paf_connect_kernel  grid (19 limbs, frames): rank-sort of the limb's candidates and a wave-ballot
+//                          greedy bipartite assignment.
+//   4. paf_assemble_kernel grid (frames): one wavefront walks the connections in reference order, a whole
+//                          limb in parallel where its connections cannot influence each other; otherwise
+//                          "which humans touch this connection" is a ballot over the humans, 64 at a time.
 // Only `hp_human`s (<= 292 B each) come back over PCIe.
 //
 // Every floating-point expression keeps the operand order and the (non-fused) rounding of the CPU
@@ -344,29 +347,7 @@ __global__ __launch_bounds__(PEAK_THREADS) void paf_peaks_kernel(const float* __
 }
 
 // ---------------------------------------------------------------------------------------------------
-// 2. order every part's peaks by scan position (row-major), i.e. the reference's push_back order.
-__global__ __launch_bounds__(256) void paf_sort_kernel(const dpeak* __restrict__ plist, const int* __restrict__ pcount,
-    int peak_cap, dpeak* __restrict__ sorted)
-{
-    extern __shared__ __attribute__((aligned(16))) int s_lin[];
-    const int k = blockIdx.x, f = blockIdx.y;
-    const int n = min(pcount[f * HP_COCO_N_PARTS + k], peak_cap);
-    const dpeak* in = plist + ((size_t)f * HP_COCO_N_PARTS + k) * peak_cap;
-    dpeak* out = sorted + ((size_t)f * HP_COCO_N_PARTS + k) * peak_cap;
-    for (int i = threadIdx.x; i < n; i += blockDim.x)
-        s_lin[i] = in[i].lin;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int me = s_lin[i];
-        int rank = 0;
-        for (int j = 0; j < n; ++j)
-            rank += (s_lin[j] < me);
-        out[rank] = in[i];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// 3. get_connection_candidates + get_connections (paf.cpp:93-144, :234-272) for one limb of one frame.
+// 2 + 3. get_connection_candidates + get_connections (paf.cpp:93-144, :234-272).
 struct cand_t {
     float score;
     int ab;  // (a << 16) | b, indices inside the two part lists
@@ -380,14 +361,14 @@ struct cand_t {
 // (2 * floor(log2 n)) is exhausted libstdc++ heap-sorts the range it is looking at (`std::__partial_sort(first, last, last)` =
 // __heap_select + __sort_heap: __make_heap, then __pop_heap down to one element, both through __adjust_heap / __push_heap); that is
 // restated too (`used_heap` reports that it ran).  Returns false only if the explicit stack overflowed (impossible: depth <= 2 log2 n).
-__device__ void libstdcxx_adjust_heap(int* v, const cand_t* c, int first, int hole, int len, int value)
+__device__ void libstdcxx_adjust_heap(int* v, const float* c, int first, int hole, int len, int value)
 {
     // bits/stl_heap.h __adjust_heap(first, holeIndex, len, value, comp) followed by __push_heap; comp(a, b) = a.score > b.score
     const int top = hole;
     int child = hole;
     while (child < (len - 1) / 2) {
         child = 2 * (child + 1);
-        if (c[v[first + child]].score > c[v[first + child - 1]].score)
+        if (c[v[first + child]] > c[v[first + child - 1]])
             --child;
         v[first + hole] = v[first + child];
         hole = child;
@@ -398,7 +379,7 @@ __device__ void libstdcxx_adjust_heap(int* v, const cand_t* c, int first, int ho
         hole = child - 1;
     }
     int parent = (hole - 1) / 2;
-    while (hole > top && c[v[first + parent]].score > c[value].score) {
+    while (hole > top && c[v[first + parent]] > c[value]) {
         v[first + hole] = v[first + parent];
         hole = parent;
         parent = (hole - 1) / 2;
@@ -406,7 +387,7 @@ __device__ void libstdcxx_adjust_heap(int* v, const cand_t* c, int first, int ho
     v[first + hole] = value;
 }
 
-__device__ void libstdcxx_heap_sort_greater(int* v, const cand_t* c, int first, int last)
+__device__ void libstdcxx_heap_sort_greater(int* v, const float* c, int first, int last)
 {
     const int len = last - first;
     if (len >= 2) // __make_heap
@@ -424,9 +405,9 @@ __device__ void libstdcxx_heap_sort_greater(int* v, const cand_t* c, int first, 
     }
 }
 
-__device__ bool libstdcxx_sort_greater(int* v, int n, const cand_t* c, bool* used_heap = nullptr)
+__device__ bool libstdcxx_sort_greater(int* v, int n, const float* c, bool* used_heap = nullptr)
 {
-#define HP_GT(i, j) (c[v[i]].score > c[v[j]].score)
+#define HP_GT(i, j) (c[v[i]] > c[v[j]])
 #define HP_SWAP(i, j)                                                                                             \
     {                                                                                                             \
         const int t_ = v[i];                                                                                      \
@@ -498,13 +479,13 @@ __device__ bool libstdcxx_sort_greater(int* v, int n, const cand_t* c, bool* use
     const int head = n > 16 ? 16 : n;
     for (int i = 1; i < head; ++i) {
         const int val = v[i];
-        if (c[val].score > c[v[0]].score) {
+        if (c[val] > c[v[0]]) {
             for (int k = i; k > 0; --k)
                 v[k] = v[k - 1];
             v[0] = val;
         } else {
             int k = i;
-            while (c[val].score > c[v[k - 1]].score) {
+            while (c[val] > c[v[k - 1]]) {
                 v[k] = v[k - 1];
                 --k;
             }
@@ -514,7 +495,7 @@ __device__ bool libstdcxx_sort_greater(int* v, int n, const cand_t* c, bool* use
     for (int i = head; i < n; ++i) {
         const int val = v[i];
         int k = i;
-        while (k > 0 && c[val].score > c[v[k - 1]].score) { // (k > 0 never decides after a completed introsort loop; kept as a guard)
+        while (k > 0 && c[val] > c[v[k - 1]]) { // (k > 0 never decides after a completed introsort loop; kept as a guard)
             v[k] = v[k - 1];
             --k;
         }
@@ -539,26 +520,251 @@ __global__ void paf_debug_sort_kernel(const float* __restrict__ scores, int n, c
     __syncthreads();
     if (threadIdx.x == 0) {
         bool heap = false;
-        const bool ok = libstdcxx_sort_greater(order, n, cand, &heap);
+        const bool ok = libstdcxx_sort_greater(order, n, scores, &heap);
         *flag = (heap ? 1 : 0) | (ok ? 0 : 2);
     }
 }
 
-// LIMB_THREADS threads per (limb, frame): the pair loop is the kernel's time, a block is alone on its CU (19 x frames blocks), and what a frame of
-// dense maps costs is its LARGEST limb (a part with 300 maxima on both ends is 90 000 pairs): sixteen wavefronts - four per SIMD - walk the pairs
-// four times as wide and cover each other's LDS / division latencies (round 6; four wavefronts before)
+// The limb step is two launches (it was one block per (limb, frame) that scored, sorted and assigned: a launch lasted as long as its LARGEST
+// limb - on dense maps a part with 300 maxima on both ends is 90 000 pairs, 88 trips of a 1024-thread pair loop, while the average limb is 3).
+//
+// 2. paf_score_kernel, grid (SCORE_BLOCKS + 18, frames): the n1 x n2 pair index space of every limb of a frame is cut into tiles of SCORE_TILE
+// pairs, the frame's tiles - limb after limb - are dealt out to its SCORE_BLOCKS blocks in equal contiguous runs, and a block that gets none
+// leaves before staging anything.  A sparse frame costs one block per limb as before (19 tiles); in a dense frame a 90 000-pair limb is
+// spread over most of the frame's blocks and the blocks of a frame finish together, whatever the sizes of its limbs.  (Tried first: 32 blocks
+// per (limb, frame), each taking every 32nd tile of 1024 pairs - 4864 blocks per batch of 8, nearly all of them empty, cost 20 us per launch on
+// sparse frames against 11 us for the whole former kernel.)  The per-pair code is the one the single kernel had: the limb's two PAF planes
+// and the up-sampling tables in LDS, the same expressions in the same order.  Surviving candidates are appended to the (limb, frame)'s list in
+// device memory through one counter; they carry seq = ia * n2 + ib, the reference's generation order, whatever the tiling.
+constexpr int SCORE_THREADS = 256;
+constexpr int SCORE_TILE = 512;   // pairs per tile: two trips of the block's pair loop
+constexpr int SCORE_BLOCKS = 64;  // scoring blocks per frame
+// how many of the n scan positions in `lin` (LDS, 16-byte aligned, filled up to a multiple of four with INT_MAX) lie before `me`: four per
+// LDS access, the accesses independent of each other (one position per access made a dependent LDS round trip of every comparison)
+__device__ __forceinline__ int rank_of(const int* lin, int n, int me)
+{
+    int rank = 0;
+#pragma unroll 4
+    for (int j = 0; j < (n + 3) / 4; ++j) {
+        const int4 v = reinterpret_cast<const int4*>(lin)[j];
+        rank += (v.x < me) + (v.y < me) + (v.z < me) + (v.w < me);
+    }
+    return rank;
+}
+__device__ __forceinline__ void pad_lin(int* lin, int n, int tid)
+{
+    if (tid < 4 && n + tid < ((n + 3) & ~3))
+        lin[n + tid] = 0x7fffffff;
+}
+__global__ __launch_bounds__(SCORE_THREADS) void paf_score_kernel(const float* __restrict__ paf, geom_t g, float paf_thresh,
+    const dpeak* __restrict__ plist, dpeak* __restrict__ sorted, const int* __restrict__ pcount, int peak_cap, int cand_cap,
+    cand_t* __restrict__ cands, int* __restrict__ cand_count)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    __shared__ int s_np[HP_COCO_N_PARTS];
+    const int tid = threadIdx.x;
+    const int f = blockIdx.y;
+    if (tid < HP_COCO_N_PARTS)
+        s_np[tid] = min(pcount[f * HP_COCO_N_PARTS + tid], peak_cap);
+    const int plane = g.R * g.Cc;
+    // LDS behind the two planes and the up-sampling tables: the two part lists of the limb at hand - scan positions as they arrive, (x, y) as
+    // they arrive, (x, y) in scan order
+    int* s_lin1 = reinterpret_cast<int*>(smem) + ((2 * plane + 3 * g.UW + 4 * g.UH + 3) & ~3), *s_lin2 = s_lin1 + peak_cap; // [peak_cap] each
+    int2* s_raw1 = reinterpret_cast<int2*>(s_lin2 + peak_cap), *s_raw2 = s_raw1 + peak_cap;
+    int2* s_A = s_raw2 + peak_cap, *s_B = s_A + peak_cap;
+    __syncthreads();
+    // ---- order every part's peaks by scan position (row-major), i.e. the reference's push_back order, so that peak ids equal the
+    // reference's running index: the frame's last 18 blocks do nothing else, block SCORE_BLOCKS + k writes part k's list for the connect
+    // / assemble kernels.  (A launch of its own until the limb step became two launches: 5 us plus a dispatch gap in the stream.)  The
+    // scoring blocks do not wait for these lists: each orders the two parts of its limb itself, in LDS, below.
+    if (blockIdx.x >= SCORE_BLOCKS) {
+        const int k = blockIdx.x - SCORE_BLOCKS, n = s_np[k];
+        const dpeak* in = plist + ((size_t)f * HP_COCO_N_PARTS + k) * peak_cap;
+        dpeak* out = sorted + ((size_t)f * HP_COCO_N_PARTS + k) * peak_cap;
+        dpeak first{ 0, 0, 0.f, 0 };
+        for (int i = tid; i < n; i += SCORE_THREADS) {
+            const dpeak pk = in[i];
+            s_lin1[i] = pk.lin;
+            if (i == tid)
+                first = pk;
+        }
+        pad_lin(s_lin1, n, tid);
+        __syncthreads();
+        for (int i = tid; i < n; i += SCORE_THREADS)
+            out[rank_of(s_lin1, n, s_lin1[i])] = i == tid ? first : in[i];
+        return;
+    }
+    auto tiles_of = [&](int l) { return (s_np[c_pairs[l][0]] * s_np[c_pairs[l][1]] + SCORE_TILE - 1) / SCORE_TILE; }; // n1 * n2 <= 2048 * 2048
+    int total = 0;
+    for (int l = 0; l < HP_COCO_N_PAIRS; ++l)
+        total += tiles_of(l);
+    // this block's run of the frame's tiles (total <= 19 * 8192: the products fit an int)
+    const int it0 = (int)blockIdx.x * total / SCORE_BLOCKS, it1 = ((int)blockIdx.x + 1) * total / SCORE_BLOCKS;
+    if (it0 >= it1) // (uniform over the block)
+        return;
+
+    float* s_px = smem;            // PAF x-channel of this limb, [R][Cc]
+    float* s_py = smem + plane;    // PAF y-channel
+    // the up-sampling tables of geom_t, staged once per block (round 6): every sample of every candidate pair used to read seven of them
+    // from global memory - 140 dependent L1 / L2 round trips per pair; a frame of dense maps (the network's own output under random weights:
+    // ~55 peaks per part, ~2 900 pairs per limb) spent 259 us here against 12 us on a frame with people.  Same values, same expressions.
+    int* s_ofs_x = reinterpret_cast<int*>(smem + 2 * plane); // [UW]
+    float* s_c0_x = reinterpret_cast<float*>(s_ofs_x + g.UW), *s_c1_x = s_c0_x + g.UW;
+    int* s_ofs_y0 = reinterpret_cast<int*>(s_c1_x + g.UW), *s_ofs_y1 = s_ofs_y0 + g.UH; // [UH]
+    float* s_c0_y = reinterpret_cast<float*>(s_ofs_y1 + g.UH), *s_c1_y = s_c0_y + g.UH;
+    for (int i = tid; i < g.UW; i += SCORE_THREADS)
+        s_ofs_x[i] = g.ofs_x[i], s_c0_x[i] = g.c0_x[i], s_c1_x[i] = g.c1_x[i];
+    for (int i = tid; i < g.UH; i += SCORE_THREADS)
+        s_ofs_y0[i] = g.ofs_y0[i], s_ofs_y1[i] = g.ofs_y1[i], s_c0_y[i] = g.c0_y[i], s_c1_y[i] = g.c1_y[i];
+    int pair_id = 0, first = 0, staged = -1; // the limb tile `it` belongs to, that limb's first tile, the limb whose planes are in LDS
+    for (int it = it0; it < it1; ++it) {
+        for (int t; it >= first + (t = tiles_of(pair_id)); ++pair_id)
+            first += t;
+        if (pair_id != staged) {
+            if (staged >= 0)
+                __syncthreads(); // every thread is done with the previous limb's planes
+            staged = pair_id;
+            const int ch1 = c_pairs_net[pair_id][0], ch2 = c_pairs_net[pair_id][1];
+            const int q1 = c_pairs[pair_id][0], q2 = c_pairs[pair_id][1], m1 = s_np[q1], m2 = s_np[q2];
+            const dpeak* in1 = plist + ((size_t)f * HP_COCO_N_PARTS + q1) * peak_cap;
+            const dpeak* in2 = plist + ((size_t)f * HP_COCO_N_PARTS + q2) * peak_cap;
+            for (int i = tid; i < m1; i += SCORE_THREADS) {
+                const dpeak pk = in1[i];
+                s_lin1[i] = pk.lin, s_raw1[i] = make_int2(pk.x, pk.y);
+            }
+            for (int i = tid; i < m2; i += SCORE_THREADS) {
+                const dpeak pk = in2[i];
+                s_lin2[i] = pk.lin, s_raw2[i] = make_int2(pk.x, pk.y);
+            }
+            pad_lin(s_lin1, m1, tid), pad_lin(s_lin2, m2, tid);
+            // the two planes in as few memory round trips as possible: 16-byte loads, four per thread and plane in flight (the simple loop paid
+            // one dependent round trip per 256 floats: most of this kernel's time)
+            const float* src = paf + (size_t)f * g.L2 * plane;
+            const float* sx = src + (size_t)ch1 * plane;
+            const float* sy = src + (size_t)ch2 * plane;
+            if (plane % 4 == 0 && ((size_t)paf & 15) == 0) {
+                const int n4 = plane / 4;
+                for (int base = 0; base < n4; base += 4 * SCORE_THREADS) {
+                    float4 vx[4], vy[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int i = min(base + k * SCORE_THREADS + tid, n4 - 1);
+                        vx[k] = reinterpret_cast<const float4*>(sx)[i];
+                        vy[k] = reinterpret_cast<const float4*>(sy)[i];
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int i = base + k * SCORE_THREADS + tid;
+                        if (i < n4) {
+                            reinterpret_cast<float4*>(s_px)[i] = vx[k];
+                            reinterpret_cast<float4*>(s_py)[i] = vy[k];
+                        }
+                    }
+                }
+            } else {
+                for (int base = 0; base < plane; base += 4 * SCORE_THREADS) {
+                    float vx[4], vy[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int i = min(base + k * SCORE_THREADS + tid, plane - 1);
+                        vx[k] = sx[i], vy[k] = sy[i];
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int i = base + k * SCORE_THREADS + tid;
+                        if (i < plane)
+                            s_px[i] = vx[k], s_py[i] = vy[k];
+                    }
+                }
+            }
+            __syncthreads();
+            for (int i = tid; i < m1; i += SCORE_THREADS) // the limb's two part lists in scan order
+                s_A[rank_of(s_lin1, m1, s_lin1[i])] = s_raw1[i];
+            for (int i = tid; i < m2; i += SCORE_THREADS)
+                s_B[rank_of(s_lin2, m2, s_lin2[i])] = s_raw2[i];
+            __syncthreads();
+        }
+
+        const int p1 = c_pairs[pair_id][0], p2 = c_pairs[pair_id][1];
+        const int n1 = s_np[p1], n2 = s_np[p2], npairs = n1 * n2;
+        cand_t* out = cands + ((size_t)f * HP_COCO_N_PAIRS + pair_id) * cand_cap;
+        int* out_n = cand_count + f * HP_COCO_N_PAIRS + pair_id;
+        const int tile = (it - first) * SCORE_TILE;
+        for (int idx = tile + tid; idx < min(npairs, tile + SCORE_TILE); idx += SCORE_THREADS) {
+            const int ia = idx / n2, ib = idx - ia * n2;
+            const int2 a = s_A[ia], b = s_B[ib];
+            const int dx = b.x - a.x, dy = b.y - a.y;
+            const float norm = sqrtf((float)(dx * dx + dy * dy)); // std::sqrt(int l2) narrowed to float, paf.cpp:104
+            if (norm < 1e-12)
+                continue;
+            float vx = (float)dx, vy = (float)dy;
+            vx /= norm;
+            vy /= norm;
+            const float step_x = (b.x - a.x) / float(STEP_PAF);
+            const float step_y = (b.y - a.y) / float(STEP_PAF);
+            float scores = 0.0f;
+            int criterion1 = 0;
+#pragma unroll
+            for (int i = 0; i < STEP_PAF; ++i) {
+                const int lx = static_cast<int>(a.x + i * step_x + 0.5); // roundpaf, paf.cpp:74
+                const int ly = static_cast<int>(a.y + i * step_y + 0.5);
+                // up_at(s_px, 0, g, ly, lx) and up_at(s_py, 0, g, ly, lx) with the tables in LDS and read once for both planes
+                const int sxo = s_ofs_x[lx], r0 = s_ofs_y0[ly] * g.Cc + sxo, r1 = s_ofs_y1[ly] * g.Cc + sxo;
+                const float cy0 = s_c0_y[ly], cy1 = s_c1_y[ly];
+                float px, py;
+                if (lx < g.vmax_x) {
+                    const float a0 = s_c0_x[lx], a1 = s_c1_x[lx];
+                    const float hx0 = s_px[r0] * a0 + s_px[r0 + 1] * a1, hx1 = s_px[r1] * a0 + s_px[r1 + 1] * a1;
+                    const float hy0 = s_py[r0] * a0 + s_py[r0 + 1] * a1, hy1 = s_py[r1] * a0 + s_py[r1 + 1] * a1;
+                    px = hx0 * cy0 + hx1 * cy1, py = hy0 * cy0 + hy1 * cy1;
+                } else {
+                    const float hx0 = s_px[r0] * 1.f, hx1 = s_px[r1] * 1.f, hy0 = s_py[r0] * 1.f, hy1 = s_py[r1] * 1.f;
+                    px = hx0 * cy0 + hx1 * cy1, py = hy0 * cy0 + hy1 * cy1;
+                }
+                const float score = vx * px + vy * py;
+                scores += score;
+                if (score > paf_thresh)
+                    criterion1 += 1;
+            }
+            const float criterion2 = scores / STEP_PAF + fmin(0.0, 0.5 * g.feat_height / norm - 1.0); // paf.cpp:129
+            if (criterion1 > THRESH_VECTOR_CNT1 && criterion2 > 0) {
+                const int pos = atomicAdd(out_n, 1); // (keeps counting past cand_cap: the connect kernel reports the overflow)
+                if (pos < cand_cap) {
+                    cand_t c;
+                    c.score = criterion2;
+                    c.ab = (ia << 16) | ib;
+                    c.seq = idx;
+                    out[pos] = c;
+                }
+            }
+        }
+    }
+}
+
+// 3. paf_connect_kernel, grid (19 limbs, frames): get_connections (paf.cpp:234-272) on the limb's candidate list.  The candidates arrive in
+// no particular order (whichever scoring block got to the counter first); nothing below depends on it: the rank is a total order on
+// (score, seq), the tie path orders by seq before it runs libstdc++'s algorithm, and s_order only translates list slots.  (A list that
+// overflowed cand_cap holds an arbitrary subset; that batch is parsed again with doubled lists, or reported truncated at the hard limit.)
+// The block is the counter's last reader and leaves it zero for the next batch.
 constexpr int LIMB_THREADS = 1024;
-__global__ __launch_bounds__(LIMB_THREADS) void paf_limbs_kernel(const float* __restrict__ paf, geom_t g, float paf_thresh,
-    const dpeak* __restrict__ sorted, const int* __restrict__ pcount, int peak_cap, int cand_cap,
-    dconn* __restrict__ conns, int* __restrict__ conn_count, int* __restrict__ flags)
+__global__ __launch_bounds__(LIMB_THREADS) void paf_connect_kernel(const cand_t* __restrict__ cands, int* __restrict__ cand_count, int cand_cap,
+    const int* __restrict__ pcount, int peak_cap, dconn* __restrict__ conns, int* __restrict__ conn_count, int* __restrict__ flags)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ int s_ncand;
     const int tid = threadIdx.x;
     const int pair_id = blockIdx.x, f = blockIdx.y;
     const int p1 = c_pairs[pair_id][0], p2 = c_pairs[pair_id][1];
-    const int ch1 = c_pairs_net[pair_id][0], ch2 = c_pairs_net[pair_id][1];
-
+    // the counter, the part counts and every thread's first candidate are requested together, before the counter is known (the list is
+    // allocated whatever it holds): one memory round trip instead of three dependent ones - most of this kernel's time on sparse frames
+    const cand_t* in = cands + ((size_t)f * HP_COCO_N_PAIRS + pair_id) * cand_cap;
+    cand_t mine{ 0.f, 0, 0 };
+    if (tid < cand_cap)
+        mine = in[tid];
+    if (tid == 0) {
+        s_ncand = cand_count[f * HP_COCO_N_PAIRS + pair_id];
+        cand_count[f * HP_COCO_N_PAIRS + pair_id] = 0;
+    }
     int start1 = 0, start2 = 0;
     for (int c = 0; c < HP_COCO_N_PARTS; ++c) {
         const int nc = min(pcount[f * HP_COCO_N_PARTS + c], peak_cap);
@@ -569,146 +775,56 @@ __global__ __launch_bounds__(LIMB_THREADS) void paf_limbs_kernel(const float* __
     }
     const int n1 = min(pcount[f * HP_COCO_N_PARTS + p1], peak_cap);
     const int n2 = min(pcount[f * HP_COCO_N_PARTS + p2], peak_cap);
-
-    const int plane = g.R * g.Cc;
-    float* s_px = smem;            // PAF x-channel of this limb, [R][Cc]
-    float* s_py = smem + plane;    // PAF y-channel
-    cand_t* s_cand = reinterpret_cast<cand_t*>(smem + 2 * plane); // [cand_cap]
-    int* s_order = reinterpret_cast<int*>(s_cand + cand_cap);     // [cand_cap] sorted position -> candidate
-    // the up-sampling tables of geom_t, staged once per block (round 6): every sample of every candidate pair used to read seven of them
-    // from global memory - 140 dependent L1 / L2 round trips per pair; a frame of dense maps (the network's own output under random weights:
-    // ~55 peaks per part, ~2 900 pairs per limb) spent 259 us here against 12 us on a frame with people.  Same values, same expressions.
-    int* s_ofs_x = s_order + cand_cap;                 // [UW]
-    float* s_c0_x = reinterpret_cast<float*>(s_ofs_x + g.UW), *s_c1_x = s_c0_x + g.UW;
-    int* s_ofs_y0 = reinterpret_cast<int*>(s_c1_x + g.UW), *s_ofs_y1 = s_ofs_y0 + g.UH; // [UH]
-    float* s_c0_y = reinterpret_cast<float*>(s_ofs_y1 + g.UH), *s_c1_y = s_c0_y + g.UH;
-    if (n1 > 0 && n2 > 0) {
-        for (int i = tid; i < g.UW; i += LIMB_THREADS)
-            s_ofs_x[i] = g.ofs_x[i], s_c0_x[i] = g.c0_x[i], s_c1_x[i] = g.c1_x[i];
-        for (int i = tid; i < g.UH; i += LIMB_THREADS)
-            s_ofs_y0[i] = g.ofs_y0[i], s_ofs_y1[i] = g.ofs_y1[i], s_c0_y[i] = g.c0_y[i], s_c1_y[i] = g.c1_y[i];
-    }
-
-    if (tid == 0)
-        s_ncand = 0;
-    if (n1 > 0 && n2 > 0) {
-        // the two planes in as few memory round trips as possible: 16-byte loads, four per thread and plane in flight (the simple loop paid
-        // one dependent round trip per 256 floats: most of this kernel's time)
-        const float* src = paf + (size_t)f * g.L2 * plane;
-        const float* sx = src + (size_t)ch1 * plane;
-        const float* sy = src + (size_t)ch2 * plane;
-        if (plane % 4 == 0 && ((size_t)paf & 15) == 0) {
-            const int n4 = plane / 4;
-            for (int base = 0; base < n4; base += 4 * LIMB_THREADS) {
-                float4 vx[4], vy[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = min(base + k * LIMB_THREADS + tid, n4 - 1);
-                    vx[k] = reinterpret_cast<const float4*>(sx)[i];
-                    vy[k] = reinterpret_cast<const float4*>(sy)[i];
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = base + k * LIMB_THREADS + tid;
-                    if (i < n4) {
-                        reinterpret_cast<float4*>(s_px)[i] = vx[k];
-                        reinterpret_cast<float4*>(s_py)[i] = vy[k];
-                    }
-                }
-            }
-        } else {
-            for (int base = 0; base < plane; base += 4 * LIMB_THREADS) {
-                float vx[4], vy[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = min(base + k * LIMB_THREADS + tid, plane - 1);
-                    vx[k] = sx[i], vy[k] = sy[i];
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = base + k * LIMB_THREADS + tid;
-                    if (i < plane)
-                        s_px[i] = vx[k], s_py[i] = vy[k];
-                }
-            }
-        }
-    }
-    __syncthreads();
-
-    const dpeak* A = sorted + ((size_t)f * HP_COCO_N_PARTS + p1) * peak_cap;
-    const dpeak* B = sorted + ((size_t)f * HP_COCO_N_PARTS + p2) * peak_cap;
-    const int npairs = n1 * n2;
-    for (int idx = tid; idx < npairs; idx += blockDim.x) {
-        const int ia = idx / n2, ib = idx - ia * n2;
-        const dpeak a = A[ia], b = B[ib];
-        const int dx = b.x - a.x, dy = b.y - a.y;
-        const float norm = sqrtf((float)(dx * dx + dy * dy)); // std::sqrt(int l2) narrowed to float, paf.cpp:104
-        if (norm < 1e-12)
-            continue;
-        float vx = (float)dx, vy = (float)dy;
-        vx /= norm;
-        vy /= norm;
-        const float step_x = (b.x - a.x) / float(STEP_PAF);
-        const float step_y = (b.y - a.y) / float(STEP_PAF);
-        float scores = 0.0f;
-        int criterion1 = 0;
-#pragma unroll
-        for (int i = 0; i < STEP_PAF; ++i) {
-            const int lx = static_cast<int>(a.x + i * step_x + 0.5); // roundpaf, paf.cpp:74
-            const int ly = static_cast<int>(a.y + i * step_y + 0.5);
-            // up_at(s_px, 0, g, ly, lx) and up_at(s_py, 0, g, ly, lx) with the tables in LDS and read once for both planes
-            const int sxo = s_ofs_x[lx], r0 = s_ofs_y0[ly] * g.Cc + sxo, r1 = s_ofs_y1[ly] * g.Cc + sxo;
-            const float cy0 = s_c0_y[ly], cy1 = s_c1_y[ly];
-            float px, py;
-            if (lx < g.vmax_x) {
-                const float a0 = s_c0_x[lx], a1 = s_c1_x[lx];
-                const float hx0 = s_px[r0] * a0 + s_px[r0 + 1] * a1, hx1 = s_px[r1] * a0 + s_px[r1 + 1] * a1;
-                const float hy0 = s_py[r0] * a0 + s_py[r0 + 1] * a1, hy1 = s_py[r1] * a0 + s_py[r1 + 1] * a1;
-                px = hx0 * cy0 + hx1 * cy1, py = hy0 * cy0 + hy1 * cy1;
-            } else {
-                const float hx0 = s_px[r0] * 1.f, hx1 = s_px[r1] * 1.f, hy0 = s_py[r0] * 1.f, hy1 = s_py[r1] * 1.f;
-                px = hx0 * cy0 + hx1 * cy1, py = hy0 * cy0 + hy1 * cy1;
-            }
-            const float score = vx * px + vy * py;
-            scores += score;
-            if (score > paf_thresh)
-                criterion1 += 1;
-        }
-        const float criterion2 = scores / STEP_PAF + fmin(0.0, 0.5 * g.feat_height / norm - 1.0); // paf.cpp:129
-        if (criterion1 > THRESH_VECTOR_CNT1 && criterion2 > 0) {
-            const int pos = atomicAdd(&s_ncand, 1);
-            if (pos < cand_cap) {
-                s_cand[pos].score = criterion2;
-                s_cand[pos].ab = (ia << 16) | ib;
-                s_cand[pos].seq = idx;
-            }
-        }
-    }
     __syncthreads();
     int n = s_ncand;
+    if (n == 0) { // (uniform) no candidate, no connection
+        if (tid == 0)
+            conn_count[f * HP_COCO_N_PAIRS + pair_id] = 0;
+        return;
+    }
     if (n > cand_cap) {
         if (tid == 0)
             atomicOr(flags + f, 2);
         n = cand_cap;
     }
 
+    // the list as structure of arrays: the ranking below reads nothing but scores, four per LDS access
+    float* s_score = smem;                                 // [cand_cap]
+    int* s_ab = reinterpret_cast<int*>(smem) + cand_cap;   // [cand_cap]
+    int* s_seq = s_ab + cand_cap;                          // [cand_cap]
+    int* s_order = s_seq + cand_cap;                       // [cand_cap] sorted position -> candidate
+    __shared__ int s_ties;
+    for (int i = tid; i < n; i += LIMB_THREADS) {
+        const cand_t c = i == tid ? mine : in[i];
+        s_score[i] = c.score, s_ab[i] = c.ab, s_seq[i] = c.seq;
+    }
+    if (tid < 4 && n + tid < ((n + 3) & ~3))
+        s_score[n + tid] = 0.f; // fills the last group of four: every candidate's score is > 0 (criterion2), so these neither exceed nor equal one
+    if (tid == 0)
+        s_ties = 0;
+    __syncthreads();
+
     // std::sort(..., std::greater) (paf.cpp:249): rank by (score desc, generation order asc).  Without equal scores that IS the
     // result of any correct sort.  With equal scores the reference's order is whatever libstdc++'s std::sort leaves: up to 16
     // candidates it is a plain insertion sort (stable = generation order, what the ranks give); beyond that introsort's
     // partitioning decides, and the limb is re-sorted below by the same algorithm on one lane.
-    __shared__ int s_ties;
-    if (tid == 0)
-        s_ties = 0;
-    __syncthreads();
+    // (The rank used to be one loop over array-of-structures candidates, three LDS reads per comparison: 58 us per launch on dense maps,
+    // more than the pair loop.  The generation order is only looked at by candidates that have an equal.)
     bool tie = false;
-    for (int i = tid; i < n; i += blockDim.x) {
-        const float sc = s_cand[i].score;
-        const int sq = s_cand[i].seq;
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {
-            const float sj = s_cand[j].score;
-            rank += (sj > sc) || (sj == sc && s_cand[j].seq < sq);
-            tie |= sj == sc && j != i;
+    const int n4 = (n + 3) / 4;
+    for (int i = tid; i < n; i += LIMB_THREADS) {
+        const float sc = s_score[i];
+        int rank = 0, eq = 0;
+        for (int j = 0; j < n4; ++j) {
+            const float4 v = reinterpret_cast<const float4*>(s_score)[j];
+            rank += (v.x > sc) + (v.y > sc) + (v.z > sc) + (v.w > sc);
+            eq += (v.x == sc) + (v.y == sc) + (v.z == sc) + (v.w == sc);
+        }
+        if (eq > 1) { // (eq counts the candidate itself)
+            tie = true;
+            const int sq = s_seq[i];
+            for (int j = 0; j < n; ++j)
+                rank += s_score[j] == sc && s_seq[j] < sq;
         }
         s_order[rank] = i;
     }
@@ -717,15 +833,15 @@ __global__ __launch_bounds__(LIMB_THREADS) void paf_limbs_kernel(const float* __
     __syncthreads();
     if (s_ties && n > 16) {
         // generation order first (the vector std::sort receives, paf.cpp:108-141), then libstdc++'s algorithm on it
-        for (int i = tid; i < n; i += blockDim.x) {
-            const int sq = s_cand[i].seq;
+        for (int i = tid; i < n; i += LIMB_THREADS) {
+            const int sq = s_seq[i];
             int rank = 0;
             for (int j = 0; j < n; ++j)
-                rank += s_cand[j].seq < sq;
+                rank += s_seq[j] < sq;
             s_order[rank] = i;
         }
         __syncthreads();
-        if (tid == 0 && !libstdcxx_sort_greater(s_order, n, s_cand))
+        if (tid == 0 && !libstdcxx_sort_greater(s_order, n, s_score))
             atomicOr(flags + f, 8); // (unreachable: the explicit stack of the restated introsort cannot overflow)
         __syncthreads();
     }
@@ -744,10 +860,10 @@ __global__ __launch_bounds__(LIMB_THREADS) void paf_limbs_kernel(const float* __
             int a = 0, b = 0;
             float sc = 0.f;
             if (valid) {
-                const cand_t c = s_cand[s_order[i]];
-                a = c.ab >> 16;
-                b = c.ab & 0xffff;
-                sc = c.score;
+                const int k = s_order[i], ab = s_ab[k];
+                a = ab >> 16;
+                b = ab & 0xffff;
+                sc = s_score[k];
             }
             const unsigned w1 = __shfl(used1, a >> 5), w2 = __shfl(used2, b >> 5);
             bool alive = valid && !((w1 >> (a & 31)) & 1u) && !((w2 >> (b & 31)) & 1u);
@@ -1078,10 +1194,49 @@ __global__ __launch_bounds__(64) void paf_assemble_kernel(const dpeak* __restric
             reg_done = true;
         }
     }
+    // ---- the walk on the LDS tables (a frame with more than 64 fragments: crowds, dense maps).  The whole-limb-in-parallel rule of the
+    // register walk holds here as well, with the humans taken in slices of 64: a limb qualifies when no human holds anything at p2 and no two
+    // humans hold the same peak at p1 (s_owner: peak id at p1 -> human).  Its connections then go 64 per step - connection c in lane c looks
+    // its owner up and attaches to it (every human is touched by at most one connection: no conflicts), or opens a new human at nh + its
+    // prefix count in connection order - instead of one per step with a scan over all humans each.  On dense maps that is 17 of the 19 limbs.
+    // Same operations on the same operands as the sequential walk below, which the other limbs keep.
+    auto clean_owner = [&](int n_h, int part) { // (while the humans' ids at `part` are still the ones s_owner was filled from)
+        for (int s = 0; s * 64 < n_h; ++s) {
+            const int h = s * 64 + lane;
+            const int id1 = h < n_h ? s_parts[h * HP_COCO_N_PARTS + part] : -1;
+            if (id1 >= 0 && id1 < ASM_PEAK_CAP)
+                s_owner[id1] = -1;
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
     for (int pair_id = 0; pair_id < HP_COCO_N_PAIRS && !reg_done; ++pair_id) {
         const int p1 = c_pairs[pair_id][0], p2 = c_pairs[pair_id][1];
         const int cbase = s_cstart[pair_id], nc = s_cstart[pair_id + 1] - cbase;
         const dconn* cl = conns + ((size_t)f * HP_COCO_N_PAIRS + pair_id) * peak_cap;
+        if (nc == 0)
+            continue;
+        const int nh0 = nh; // the humans s_owner is filled from
+        bool par_ok = true;
+        for (int s = 0; s * 64 < nh0; ++s) {
+            const int h = s * 64 + lane;
+            const bool in = h < nh0;
+            const int hs = in ? h : 0;
+            const int id1 = s_parts[hs * HP_COCO_N_PARTS + p1], id2 = s_parts[hs * HP_COCO_N_PARTS + p2];
+            if (__ballot(in & ((id2 != -1) | (id1 >= ASM_PEAK_CAP))) != 0ull)
+                par_ok = false; // (the slices go on: clean_owner below then finds nothing it did not expect)
+            if (par_ok && in && id1 >= 0)
+                s_owner[id1] = h;
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (int s = 0; s * 64 < nh0 && par_ok; ++s) {
+            const int h = s * 64 + lane;
+            const int id1 = h < nh0 ? s_parts[h * HP_COCO_N_PARTS + p1] : -1;
+            const bool dup = id1 >= 0 && s_owner[id1] != h;
+            if (__ballot(dup) != 0ull)
+                par_ok = false;
+        }
+        if (!par_ok)
+            clean_owner(nh0, p1);
         for (int cb = 0; cb < nc; cb += 64) {
             // 64 connections at a time: lane i fetches connection cb + i and the scores of its two peaks, so that the serial walk
             // below reads them with v_readlane instead of paying an LDS round trip per dependent access
@@ -1092,6 +1247,36 @@ __global__ __launch_bounds__(64) void paf_assemble_kernel(const dpeak* __restric
                 my_sc1 = peak_score(p1, mine.cid1), my_sc2 = peak_score(p2, mine.cid2); // all_peaks[cid].score
             }
             const int nb = min(64, nc - cb);
+            if (par_ok) {
+                const bool cv = lane < nb;
+                int h = -1;
+                if (cv && mine.cid1 >= 0 && mine.cid1 < ASM_PEAK_CAP)
+                    h = s_owner[mine.cid1];
+                const bool isnew = cv && h < 0 && pair_id <= 16; // !is_virtual_pair (coco.hpp:6)
+                const unsigned long long nm = __ballot(isnew);
+                const int nnew = __popcll(nm);
+                if (nh + nnew <= MAXH) {
+                    if (cv && h >= 0) { // humans[h].parts[p2] (unset) != cid2: attach (paf.cpp:170-176)
+                        s_parts[h * HP_COCO_N_PARTS + p2] = mine.cid2;
+                        s_n[h] += 1;
+                        s_score[h] += my_sc2 + mine.score;
+                    }
+                    if (isnew) {
+                        const int k = nh + __popcll(nm & ((1ull << lane) - 1ull));
+#pragma unroll
+                        for (int r = 0; r < HP_COCO_N_PARTS; ++r)
+                            s_parts[k * HP_COCO_N_PARTS + r] = r == p1 ? mine.cid1 : (r == p2 ? mine.cid2 : -1);
+                        s_n[k] = 2;
+                        s_score[k] = my_sc1 + my_sc2 + mine.score;
+                    }
+                    nh += nnew;
+                    __builtin_amdgcn_wave_barrier();
+                    continue;
+                }
+                // the table would fill up inside this chunk: the sequential walk drops exactly the humans past MAXH (and sets the flag)
+                clean_owner(nh0, p1);
+                par_ok = false;
+            }
             for (int ci = 0; ci < nb; ++ci) {
                 dconn conn;
                 conn.cid1 = __builtin_amdgcn_readlane(mine.cid1, ci), conn.cid2 = __builtin_amdgcn_readlane(mine.cid2, ci);
@@ -1169,6 +1354,8 @@ __global__ __launch_bounds__(64) void paf_assemble_kernel(const dpeak* __restric
                 __builtin_amdgcn_wave_barrier();
             }
         }
+        if (par_ok) // (a parallel limb never writes part p1 of the humans 0 .. nh0 - 1)
+            clean_owner(nh0, p1);
     }
     __syncthreads();
     if (overflow && lane == 0)
@@ -1318,11 +1505,11 @@ struct hp_paf {
     geom_t g{};
     gauss_t gk{};
     int BH = 0, CW = 0, strips = 0, bands = 0, src_rows_cap = 0; // peaks kernel tiling
-    size_t peaks_lds = 0, limbs_lds = 0;
+    size_t peaks_lds = 0, score_lds = 0, connect_lds = 0;
 
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
-    hp::dev_buf tables, plist, sorted, pcount, pcount_last, conns, conn_count, flags, in_conf, in_paf;
+    hp::dev_buf tables, plist, sorted, pcount, pcount_last, cands, cand_count, conns, conn_count, flags, in_conf, in_paf;
     hp::host_buf h_humans, h_counts; // h_counts: [n_humans(max_batch) | flags(max_batch)], written by the assemble kernel
     int pending = 0; // frames of the enqueued, not yet collected batch
     int last_n = 0;  // frames of the last completed batch (debug taps)
@@ -1336,15 +1523,21 @@ struct hp_paf {
 // The reference's lists are std::vectors (src/post_process.hpp:171-193, src/paf.cpp:108-141): they grow.  Here they start at sizes
 // that fit every realistic frame (512 peaks per part, 2048 candidates per limb, 128 humans) and hp_paf_collect re-parses a batch
 // with doubled lists when a frame overflowed one.  Hard limits (reported as HP_ERR_CAPACITY, results truncated): 2048 peaks per
-// part (the greedy pass keeps its "used" sets in 64 x 32-bit lane registers), the candidates that fit the CU's LDS next to the two PAF
-// planes (~8000 at 46x54), 1024 skeleton fragments alive or merged per frame (MAXH), 1024 humans returned.
+// part (the greedy pass keeps its "used" sets in 64 x 32-bit lane registers), the candidates of one limb that the connect kernel can
+// rank in a CU's LDS (CAND_CAP_MAX = 9984: 16 bytes each in 156 KB, whatever the map size - the PAF planes are staged by the scoring
+// kernel, whose own LDS bounds the map size), 1024 skeleton fragments alive or merged per frame (MAXH), 1024 humans returned.
 constexpr int PEAK_CAP_MAX = 2048, HUMAN_CAP_MAX = 1024;
+constexpr int CAND_CAP_MAX = 156 * 1024 / (int)(sizeof(cand_t) + sizeof(int));
 int hp_paf::alloc_lists()
 {
-    limbs_lds = (size_t)4 * 2 * g.R * g.Cc + (size_t)cand_cap * (sizeof(cand_t) + sizeof(int)) + (size_t)4 * (3 * g.UW + 4 * g.UH); // planes, candidates, up-sampling tables
-    HP_REQUIRE(limbs_lds <= 160 * 1024, HP_ERR_INVALID, "paf: feature map too large for LDS tiling");
-    HP_HIP_TRY(hipFuncSetAttribute((const void*)paf_limbs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)limbs_lds));
+    score_lds = (size_t)4 * ((2 * g.R * g.Cc + 3 * g.UW + 4 * g.UH + 3) & ~3) + (size_t)peak_cap * (2 * sizeof(int) + 4 * sizeof(int2)); // planes, up-sampling tables, two part lists
+    HP_REQUIRE(score_lds <= 160 * 1024, HP_ERR_INVALID, "paf: feature map too large for LDS tiling");
+    connect_lds = (size_t)cand_cap * (sizeof(cand_t) + sizeof(int)); // candidates, their order
+    HP_REQUIRE(cand_cap <= CAND_CAP_MAX, HP_ERR_INVALID, "paf: candidate list too large for LDS");
+    HP_HIP_TRY(hipFuncSetAttribute((const void*)paf_score_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)score_lds));
+    HP_HIP_TRY(hipFuncSetAttribute((const void*)paf_connect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)connect_lds));
     const size_t B = max_batch;
+    HP_TRY(cands.alloc(B * HP_COCO_N_PAIRS * cand_cap * sizeof(cand_t)));
     HP_TRY(plist.alloc(B * HP_COCO_N_PARTS * peak_cap * sizeof(dpeak)));
     HP_TRY(sorted.alloc(B * HP_COCO_N_PARTS * peak_cap * sizeof(dpeak)));
     HP_TRY(conns.alloc(B * HP_COCO_N_PAIRS * peak_cap * sizeof(dconn)));
@@ -1418,10 +1611,13 @@ int hp_paf::shape(const int cs[3], const int ps[3])
     HP_TRY(pcount.alloc(B * HP_COCO_N_PARTS * sizeof(int)));
     HP_TRY(pcount_last.alloc(B * HP_COCO_N_PARTS * sizeof(int)));
     HP_TRY(conn_count.alloc(B * HP_COCO_N_PAIRS * sizeof(int)));
+    HP_TRY(cand_count.alloc(B * HP_COCO_N_PAIRS * sizeof(int)));
     HP_TRY(flags.alloc(B * sizeof(int)));
     HP_TRY(h_counts.alloc(2 * B * sizeof(int)));
-    // invariant between batches: peak counters and overflow flags are zero (the assemble kernel restores it)
+    // invariant between batches: peak counters and overflow flags are zero (the assemble kernel restores it), and so are the candidate
+    // counters (the connect kernel does)
     HP_HIP_TRY(hipMemsetAsync(pcount.p, 0, B * HP_COCO_N_PARTS * sizeof(int), stream)); // (own stream: see the table upload above)
+    HP_HIP_TRY(hipMemsetAsync(cand_count.p, 0, B * HP_COCO_N_PAIRS * sizeof(int), stream));
     HP_HIP_TRY(hipMemsetAsync(flags.p, 0, B * sizeof(int), stream));
     HP_HIP_TRY(hipStreamSynchronize(stream));
     memset(h_counts.p, 0, 2 * B * sizeof(int));
@@ -1496,12 +1692,13 @@ static int launch_peaks(hp_paf* p, int n, const float* dev_conf, hipStream_t s, 
 int hp_paf::launch(int n, const float* dev_conf, const float* dev_paf, hipStream_t s)
 {
     hp_paf* p = this;
-    // (pcount / flags are zero here: zeroed at creation and re-zeroed by every assemble launch)
+    // (pcount / flags / cand_count are zero here: zeroed at creation and re-zeroed by every assemble / connect launch)
     HP_TRY(launch_peaks(p, n, dev_conf, s, nullptr, nullptr, HP_COCO_N_PARTS));
-    hipLaunchKernelGGL(paf_sort_kernel, dim3(HP_COCO_N_PARTS, n), dim3(256), p->peak_cap * sizeof(int), s,
-        p->plist.as<dpeak>(), p->pcount.as<int>(), p->peak_cap, p->sorted.as<dpeak>());
-    hipLaunchKernelGGL(paf_limbs_kernel, dim3(HP_COCO_N_PAIRS, n), dim3(LIMB_THREADS), p->limbs_lds, s, dev_paf, p->g, p->paf_thresh,
-        p->sorted.as<dpeak>(), p->pcount.as<int>(), p->peak_cap, p->cand_cap, p->conns.as<dconn>(), p->conn_count.as<int>(),
+    hipLaunchKernelGGL(paf_score_kernel, dim3(SCORE_BLOCKS + HP_COCO_N_PARTS, n), dim3(SCORE_THREADS), p->score_lds, s, dev_paf, p->g,
+        p->paf_thresh, p->plist.as<dpeak>(), p->sorted.as<dpeak>(), p->pcount.as<int>(), p->peak_cap, p->cand_cap, p->cands.as<cand_t>(),
+        p->cand_count.as<int>());
+    hipLaunchKernelGGL(paf_connect_kernel, dim3(HP_COCO_N_PAIRS, n), dim3(LIMB_THREADS), p->connect_lds, s, p->cands.as<cand_t>(),
+        p->cand_count.as<int>(), p->cand_cap, p->pcount.as<int>(), p->peak_cap, p->conns.as<dconn>(), p->conn_count.as<int>(),
         p->flags.as<int>());
     hipLaunchKernelGGL(paf_assemble_kernel, dim3(n), dim3(64), 0, s, p->sorted.as<dpeak>(), p->pcount.as<int>(), p->peak_cap,
         p->conns.as<dconn>(), p->conn_count.as<int>(), p->res_w, p->res_h, p->h_humans.as<hp_human>(), p->h_counts.as<int>(),
@@ -1542,8 +1739,7 @@ int hp_paf_collect(hp_paf* p, hp_human* out, int cap_per_frame, int* n_out)
             max_h = std::max(max_h, p->h_counts.as<int>()[f]);
         }
         // a list overflowed somewhere in the batch: grow what can grow and parse the batch again (the reference's vectors just grow)
-        const size_t planes = (size_t)4 * 2 * p->g.R * p->g.Cc + (size_t)4 * (3 * p->g.UW + 4 * p->g.UH), per_cand = sizeof(cand_t) + sizeof(int); // (+ the up-sampling tables)
-        const int cand_max = (int)((156 * 1024 - planes) / per_cand);
+        const int cand_max = CAND_CAP_MAX;
         // the new capacities are computed into locals and committed only together with the buffers that match them: leaving the loop
         // (round limit) or failing to allocate must not leave caps larger than plist / sorted / conns / h_humans
         if (round >= 6)
