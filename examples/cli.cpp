@@ -12,6 +12,13 @@
 //     `--yuv_matrix=bt601|bt709|bt2020` and `--yuv_range=limited|full` (defaults bt601, limited); `--yuv` converts any other source to
 //     NV12 first.  Either way the operator runtime hands the engine hyperpose::yuv_frame batches (colour conversion fused into the resize
 //     on the GPU); the BGR pictures, converted on the host with the same table (hp_yuv_coefficients), are only drawn on.
+//   * writing video back (addition): `--saving_yuv=<file>`, for a .yuv source or `--yuv`: every frame is uploaded in its own format, inference
+//     runs on it as a device-resident frame, the skeletons are drawn on the device surface (hp::draw_humans, opacity = alpha; alpha == 0 -> 1)
+//     and the annotated frames are appended to <file> as raw frames of the same format; <file>.humans receives, per frame, an int32 count and
+//     that many 292-byte hp_human records in the frame's coordinates (what was drawn).  The PPM output is unchanged.
+//   * `--synthetic_humans=<n>` (addition, default 0): n seeded stand-in humans are added to every frame's parser output before anything is drawn -
+//     the built-in models carry synthetic weights and find nobody, so this is what makes a demonstration (or a test) of the drawing paths show
+//     something; operator runtime only.  A warning says that the pictures and the count are not the model's result.
 //   * `--model`: .onnx, a serialized engine (anything else), or `builtin:<arch>` (hp_model_archs(); synthetic weights).
 // build: g++ -std=c++17 -O2 -Iinclude examples/cli.cpp -Lhyperpose_amd -lhp_hip -lpthread -Wl,-rpath,$PWD/hyperpose_amd -o hyperpose-cli
 #include <hyperpose/hyperpose.hpp>
@@ -23,6 +30,7 @@
 #include <fstream>
 #include <iostream>
 #include <map>
+#include <memory>
 #include <string_view>
 #include <variant>
 
@@ -50,17 +58,21 @@ static bool FLAGS_int8 = false; // addition: data_type::kINT8 engines, calibrate
 static bool FLAGS_yuv = false;  // addition: feed the engine video frames (dnn::tensorrt::inference(std::vector<yuv_frame>)); implied by a .yuv source
 static int FLAGS_yuv_w = 0, FLAGS_yuv_h = 0; // frame size of a raw .yuv source
 static std::string FLAGS_yuv_format = "i420", FLAGS_yuv_matrix = "bt601", FLAGS_yuv_range = "limited"; // layout and colours of a raw .yuv source
+static std::string FLAGS_saving_yuv; // addition: append the frames, annotated on the device in their own format, to this file
+static int FLAGS_synthetic_humans = 0; // addition: stand-in humans added to every frame's poses (see the head of the file)
+static bool g_yuv_from_file = false; // the frames came from a .yuv source (else --yuv made NV12 ones)
 static int g_yuv_format = HP_YUV_I420, g_yuv_matrix = HP_YUV_BT601, g_yuv_range = HP_YUV_LIMITED;      // the same, parsed
 
+static const char* FLAGS_yuv_format_written() { return g_yuv_from_file ? FLAGS_yuv_format.c_str() : "nv12"; }
 static std::ostream& cli_log() { return std::cout << "[HyperPose::CLI] "; }
 
 static bool parse_flags(int argc, char** argv)
 {
     std::map<std::string, std::string*> sflags = { { "model", &FLAGS_model }, { "post", &FLAGS_post }, { "source", &FLAGS_source },
-        { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix }, { "yuv_format", &FLAGS_yuv_format },
+        { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix }, { "saving_yuv", &FLAGS_saving_yuv }, { "yuv_format", &FLAGS_yuv_format },
         { "yuv_matrix", &FLAGS_yuv_matrix }, { "yuv_range", &FLAGS_yuv_range } };
     std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size },
-        { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h } };
+        { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h }, { "synthetic_humans", &FLAGS_synthetic_humans } };
     std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 }, { "yuv", &FLAGS_yuv } };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -303,7 +315,7 @@ static std::vector<cv::Mat> load_source()
             images.push_back(yuv_to_bgr(b));
             g_yuv.push_back(std::move(b));
         }
-        FLAGS_yuv = true;
+        FLAGS_yuv = g_yuv_from_file = true;
         return images;
     }
     if (match_suffix(".ppm")) {
@@ -330,6 +342,24 @@ static std::vector<cv::Mat> load_source()
         }
     }
     return images;
+}
+
+// --synthetic_humans: n humans of frame `frame`, every part but a few present, spread over the picture (and a little beyond it)
+static void add_synthetic_humans(std::vector<hp::human_t>& poses, size_t frame, int n)
+{
+    unsigned s = 9001u + (unsigned)frame * 7919u;
+    auto next = [&] { return (s = s * 1664525u + 1013904223u, (float)(s >> 8) / (float)(1 << 24)); };
+    for (int i = 0; i < n; ++i) {
+        hp::human_t h{};
+        h.score = 1;
+        const float cx = 0.05f + 0.9f * next(), cy = 0.1f + 0.8f * next();
+        for (int k = 0; k < hp::COCO_N_PARTS; ++k) {
+            const float x = cx + 0.2f * (next() - 0.5f), y = cy + 0.4f * (next() - 0.5f);
+            if (next() < 0.85f)
+                h.parts[k] = hp::body_part_t{ true, x, y, 1.f };
+        }
+        poses.push_back(h);
+    }
 }
 
 // the three post-processing operators behind one value (the `--post` flag picks the alternative)
@@ -383,6 +413,14 @@ int main(int argc, char** argv)
         cli_log() << "WARNING: --alpha=" << FLAGS_alpha << " is outside [0, 1]; using " << inside << "\n";
         FLAGS_alpha = inside;
     }
+    // --saving_yuv is settled from the flags alone, before anything touches the device
+    if (!FLAGS_saving_yuv.empty() && !FLAGS_yuv && !has_suffix(FLAGS_source, ".yuv")) {
+        cli_log() << "ERROR: --saving_yuv writes video frames: it needs a .yuv source or --yuv\n";
+        return 1;
+    }
+    if (FLAGS_synthetic_humans > 0)
+        cli_log() << "WARNING: --synthetic_humans=" << FLAGS_synthetic_humans << ": " << FLAGS_synthetic_humans
+                  << " made-up humans are added to every frame's poses; the pictures and the human count below are NOT the model's result\n";
     if (hp_init(0) != HP_OK) {
         cli_log() << "ERROR: " << hp_last_error() << "\n";
         return 2;
@@ -408,6 +446,15 @@ int main(int argc, char** argv)
     if (FLAGS_yuv && FLAGS_runtime == kSTREAM) {
         cli_log() << "WARNING: the stream runtime carries cv::Mat frames (stream.hpp); YUV frames go through --runtime=" kOPERATOR "\n";
         FLAGS_runtime = kOPERATOR;
+    }
+    std::ofstream yuv_out, humans_out;
+    if (!FLAGS_saving_yuv.empty()) {
+        yuv_out.open(FLAGS_saving_yuv, std::ios::binary | std::ios::trunc);
+        humans_out.open(FLAGS_saving_yuv + ".humans", std::ios::binary | std::ios::trunc);
+        if (!yuv_out || !humans_out) {
+            cli_log() << "ERROR: cannot write " << FLAGS_saving_yuv << "\n";
+            return 1;
+        }
     }
     if (FLAGS_imshow) {
         FLAGS_imshow = false;
@@ -456,12 +503,42 @@ int main(int argc, char** argv)
         for (size_t first = 0; first < images.size(); first += step) {
             std::vector<cv::Mat> batch(images.begin() + first, images.begin() + std::min(images.size(), first + step));
             std::vector<hp::yuv_frame> yuv_batch;
+            std::vector<std::unique_ptr<hp::detail::dev_ptr>> surfaces; // --saving_yuv: the frames as device-resident surfaces
             if (FLAGS_yuv)
-                for (size_t k = 0; k < batch.size(); ++k)
-                    yuv_batch.push_back(g_yuv[first + k].frame());
+                for (size_t k = 0; k < batch.size(); ++k) {
+                    const yuv_buffer& b = g_yuv[first + k];
+                    if (!yuv_out.is_open()) {
+                        yuv_batch.push_back(b.frame());
+                        continue;
+                    }
+                    surfaces.push_back(std::make_unique<hp::detail::dev_ptr>(b.data.size()));
+                    if (!surfaces.back()->p || hp_memcpy_h2d(surfaces.back()->p, b.data.data(), b.data.size()) != HP_OK) {
+                        cli_log() << "ERROR: " << hp_last_error() << "\n";
+                        return 2;
+                    }
+                    yuv_batch.push_back(hp::yuv_frame::packed(b.format, surfaces.back()->p, b.w, b.h, b.matrix, b.range, true));
+                }
             const auto maps = FLAGS_yuv ? engine.inference(yuv_batch) : engine.inference(batch);
             for (size_t k = 0; k < batch.size(); ++k) {
-                const auto poses = std::visit([&](auto& op) { return op.process(maps[k]); }, parser);
+                auto poses = std::visit([&](auto& op) { return op.process(maps[k]); }, parser);
+                add_synthetic_humans(poses, first + k, FLAGS_synthetic_humans);
+                if (yuv_out.is_open()) { // annotate the surface where it lies, in its own format, and append it to the file
+                    std::vector<hp::human_t> drawn = poses;
+                    if (FLAGS_keep_ratio)
+                        for (auto& pose : drawn)
+                            hp::resume_ratio(pose, batch[k].size(), engine.input_size());
+                    hp::draw_humans(yuv_batch[k], drawn, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
+                    std::vector<uint8_t> annotated(g_yuv[first + k].data.size());
+                    if (hp_device_synchronize() != HP_OK || hp_memcpy_d2h(annotated.data(), surfaces[k]->p, annotated.size()) != HP_OK) {
+                        cli_log() << "ERROR: " << hp_last_error() << "\n";
+                        return 2;
+                    }
+                    yuv_out.write((const char*)annotated.data(), annotated.size());
+                    const auto records = hp::detail::to_c_humans(drawn);
+                    const int32_t count = (int32_t)records.size();
+                    humans_out.write((const char*)&count, sizeof(count));
+                    humans_out.write((const char*)records.data(), records.size() * sizeof(hp_human));
+                }
                 render(batch[k], poses, FLAGS_keep_ratio);
             }
         }
@@ -482,5 +559,13 @@ int main(int argc, char** argv)
     const auto ms = std::chrono::duration<double, std::milli>(clk_t::now() - beg).count();
     std::cout << images.size() << " images got processed in " << ms << " ms, FPS = " << 1000. * images.size() / ms << " (" << n_humans
               << " humans, " << n_written << " files written as " << FLAGS_saving_prefix << "_<id>.ppm)\n";
+    if (yuv_out.is_open()) {
+        yuv_out.flush(), humans_out.flush();
+        if (!yuv_out || !humans_out) {
+            cli_log() << "ERROR: writing " << FLAGS_saving_yuv << " failed\n";
+            return 3;
+        }
+        std::cout << images.size() << " annotated " << FLAGS_yuv_format_written() << " frames appended to " << FLAGS_saving_yuv << "\n";
+    }
     return n_written == images.size() ? 0 : 3;
 }

@@ -57,9 +57,15 @@ class YuvImage(C.Structure):
                 ("plane", C.c_void_p * 3), ("stride", C.c_int32 * 3)]
 
 
+class OverlayPrim(C.Structure):
+    """hp_overlay_prim"""
+    _fields_ = [(k, C.c_int32) for k in ("kind", "x0", "y0", "x1", "y1", "t", "colour", "human")]
+
+
 PART_DTYPE = np.dtype([("has_value", "<i4"), ("x", "<f4"), ("y", "<f4"), ("score", "<f4")])
 HUMAN_DTYPE = np.dtype({"names": ["parts", "score"], "formats": [(PART_DTYPE, 18), "<f4"]})
 PEAK_DTYPE = np.dtype([("part_id", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4"), ("id", "<i4")])
+OVERLAY_PRIM_DTYPE = np.dtype([(k, "<i4") for k in ("kind", "x0", "y0", "x1", "y1", "t", "colour", "human")])
 CONN_DTYPE = np.dtype([("pair_id", "<i4"), ("cid1", "<i4"), ("cid2", "<i4"), ("score", "<f4")])
 assert HUMAN_DTYPE.itemsize == C.sizeof(Human) == 292
 
@@ -71,6 +77,8 @@ SYMBOLS = [
     "hp_free_host", "hp_memcpy_h2d", "hp_memcpy_d2h", "hp_device_synchronize", "hp_stream_wait_stream", "hp_dist_unique_id", "hp_dist_init", "hp_dist_destroy", "hp_dist_broadcast_weights", "hp_dist_shard", "hp_preproc_u8hwc_to_f32nchw", "hp_resize_u8c3", "hp_letterbox_u8c3", "hp_letterbox_inner", "hp_resume_ratio",
     "hp_resize_yuv420", "hp_letterbox_yuv420", "hp_pipeline_submit_yuv",
     "hp_resize_yuv", "hp_letterbox_yuv", "hp_yuv_coefficients", "hp_yuv_packed_bytes", "hp_yuv_plane_layout", "hp_pipeline_submit_yuv_images",
+    "hp_overlay_create", "hp_overlay_destroy", "hp_overlay_primitives", "hp_yuv_colours", "hp_overlay_draw_u8c3", "hp_overlay_draw_yuv",
+    "hp_overlay_draw_u8c3_host", "hp_overlay_draw_yuv_host",
     "hp_paf_create", "hp_paf_stream", "hp_paf_destroy", "hp_paf_set_conf_thresh", "hp_paf_set_paf_thresh", "hp_paf_process_batch",
     "hp_paf_enqueue", "hp_paf_collect", "hp_paf_debug_peaks", "hp_paf_debug_conns", "hp_paf_debug_maps", "hp_paf_debug_sort",
     "hp_pifpaf_create", "hp_pifpaf_destroy", "hp_pifpaf_process_batch", "hp_pifpaf_stream", "hp_pifpaf_enqueue", "hp_pifpaf_collect", "hp_pifpaf_decode_flags",

@@ -29,6 +29,8 @@ UNITS = [
     # -fno-slp-vectorize, as for conv_fp32.hip below: the coefficient derivation is fp32 and runs next to the engines' kernels
     ("resize_yuv.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("resize_yuv_formats.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # the primitive list is fp32 with no fused operations (csrc/overlay.hpp); the kernels are integer
+    ("overlay.hip", ["-ffp-contract=off"]),
     ("paf_parser.hip", ["-ffp-contract=off"]),
     ("ppn_parser.hip", ["-ffp-contract=off"]),
     ("pifpaf_parser.hip", ["-ffp-contract=off"]),

@@ -77,20 +77,10 @@ __global__ __launch_bounds__(256) void resize_yuv_word16_kernel(const rz_geom g,
 
 template <class Taps> void fill_taps(Taps& t, const hp_yuv_image& im, const hp_yuv::layout& l, const int32_t k[7])
 {
-    const uint8_t *p0 = (const uint8_t*)im.plane[0], *p1 = (const uint8_t*)im.plane[1], *p2 = (const uint8_t*)im.plane[2];
+    const hp_yuv::sample_map m = hp_yuv::map_samples(im, l);
     t.sx = l.sx, t.sy = l.sy, t.shift = l.shift;
-    t.y_stride = im.stride[0];
-    if (l.planes == 1) { // YUY2: Y0 U Y1 V, UYVY: U Y0 V Y1
-        const bool yuy2 = im.format == HP_YUV_YUY2;
-        t.y = p0 + (yuy2 ? 0 : 1), t.u = p0 + (yuy2 ? 1 : 0), t.v = p0 + (yuy2 ? 3 : 2);
-        t.c_stride = im.stride[0], t.c_step = 4, t.v_extra = 0;
-    } else if (l.planes == 2) {
-        t.y = p0, t.u = p1, t.v = p1 + l.sample_bytes;
-        t.c_stride = im.stride[1], t.c_step = 2 * l.sample_bytes, t.v_extra = 0;
-    } else {
-        t.y = p0, t.u = p1, t.v = p2;
-        t.c_stride = im.stride[1], t.c_step = l.sample_bytes, t.v_extra = im.stride[2] - im.stride[1];
-    }
+    t.y = m.y, t.u = m.u, t.v = m.v;
+    t.y_stride = m.y_stride, t.c_stride = m.c_stride, t.c_step = m.c_step, t.v_extra = m.v_extra;
     t.y_off = k[0], t.c_off = k[1], t.cy = k[2], t.cub = k[3], t.cug = k[4], t.cvg = k[5], t.cvr = k[6];
 }
 
@@ -125,7 +115,7 @@ int launch_resize_yuv_image(const hp_yuv_image* im, const char* who, uint8_t* ds
 
 } // namespace
 
-int hp_yuv::validate(const hp_yuv_image* im, const char* who, bool kernel_reads)
+int hp_yuv::validate(const hp_yuv_image* im, const char* who, bool kernel_access)
 {
     HP_REQUIRE(im, HP_ERR_INVALID, "%s: null image", who);
     const hp_yuv::layout* l = hp_yuv::layout_of(im->format);
@@ -141,7 +131,7 @@ int hp_yuv::validate(const hp_yuv_image* im, const char* who, bool kernel_reads)
         HP_REQUIRE(im->plane[k], HP_ERR_INVALID, "%s: %s: plane %d is null", who, l->name, k);
         HP_REQUIRE(im->stride[k] > 0 && (size_t)im->stride[k] >= hp_yuv::row_bytes(*l, k, im->width), HP_ERR_INVALID,
             "%s: %s: stride %d of plane %d is smaller than a row (%zu bytes)", who, l->name, im->stride[k], k, hp_yuv::row_bytes(*l, k, im->width));
-        HP_REQUIRE(!kernel_reads || l->sample_bytes == 1 || (im->stride[k] % 2 == 0 && (uintptr_t)im->plane[k] % 2 == 0), HP_ERR_INVALID,
+        HP_REQUIRE(!kernel_access || l->sample_bytes == 1 || (im->stride[k] % 2 == 0 && (uintptr_t)im->plane[k] % 2 == 0), HP_ERR_INVALID,
             "%s: %s: plane %d (16-bit words) needs an even address and an even stride", who, l->name, k);
     }
     return HP_OK;

@@ -38,9 +38,38 @@ inline size_t row_bytes(const layout& l, int k, int w)
 }
 inline int rows(const layout& l, int k, int h) { return k == 0 ? h : h >> l.sy; }
 
+// Where the samples of an image lie, in bytes: the address of the first Y, U and V sample (semi-planar and packed layouts: inside the same
+// plane), the row strides, and the steps between horizontally neighbouring samples.  Luma pixel (x, y) is at y + y * y_stride + x * y_step,
+// its chroma at u | v + (y >> sy) * c_stride + (x >> sx) * c_step (the V plane of a planar frame: + (y >> sy) * v_extra, its own pitch).
+// The one statement of "YUY2 is Y0 U Y1 V, UYVY is U Y0 V Y1, semi-planar pairs are (U, V)": the resize kernels read through it
+// (resize_yuv_formats.hip) and the overlay kernels write through it (overlay.hip).
+struct sample_map {
+    const uint8_t *y, *u, *v;
+    int y_stride, c_stride, v_extra;
+    int y_step, c_step;
+};
+inline sample_map map_samples(const hp_yuv_image& im, const layout& l)
+{
+    const uint8_t *p0 = (const uint8_t*)im.plane[0], *p1 = (const uint8_t*)im.plane[1], *p2 = (const uint8_t*)im.plane[2];
+    sample_map m;
+    m.y_stride = im.stride[0];
+    if (l.planes == 1) {
+        const bool yuy2 = im.format == HP_YUV_YUY2;
+        m.y = p0 + (yuy2 ? 0 : 1), m.u = p0 + (yuy2 ? 1 : 0), m.v = p0 + (yuy2 ? 3 : 2);
+        m.c_stride = im.stride[0], m.y_step = 2, m.c_step = 4, m.v_extra = 0;
+    } else if (l.planes == 2) {
+        m.y = p0, m.u = p1, m.v = p1 + l.sample_bytes;
+        m.c_stride = im.stride[1], m.y_step = l.sample_bytes, m.c_step = 2 * l.sample_bytes, m.v_extra = 0;
+    } else {
+        m.y = p0, m.u = p1, m.v = p2;
+        m.c_stride = im.stride[1], m.y_step = l.sample_bytes, m.c_step = l.sample_bytes, m.v_extra = im.stride[2] - im.stride[1];
+    }
+    return m;
+}
+
 // format, matrix, range, size, planes and strides of one image; `who` starts the message.  HP_OK or HP_ERR_INVALID (message set).
-// `kernel_reads`: the planes are read by the kernel where they lie, so 16-bit words need even addresses and strides; false for host
-// frames, which are re-packed byte by byte before the kernel sees them
-int validate(const hp_yuv_image* im, const char* who, bool kernel_reads = true);
+// `kernel_access`: a kernel reads (resize) or writes (overlay) the planes where they lie, so 16-bit words need even addresses and strides;
+// false for host frames, which are re-packed byte by byte before a kernel sees them or are painted bytewise by the overlay's host twin
+int validate(const hp_yuv_image* im, const char* who, bool kernel_access = true);
 
 } // namespace hp_yuv

@@ -6,7 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import YUV_FORMATS, YUV_LAYOUTS, YUV_MATRICES, YUV_RANGES, DevBuf, YuvImage, as_ptr, check, lib
+from ._lib import (HUMAN_DTYPE, OVERLAY_PRIM_DTYPE, YUV_FORMATS, YUV_LAYOUTS, YUV_MATRICES, YUV_RANGES, DevBuf, Human, OverlayPrim, YuvImage, as_ptr,
+                   check, lib)
 
 
 def resize(src_dev, sw: int, sh: int, dst_dev, dw: int, dh: int, stream=None, src_stride=None, dst_stride=None) -> None:
@@ -184,3 +185,86 @@ def resize_yuv_host(frame_planes, dw: int, dh: int, fmt: str = "nv12", matrix: s
     resize_yuv(yuv_image(fmt, [b.ptr for b in bufs], strides, w, h, matrix, range), dst, dw, dh, keep_ratio, bgcolor)
     check(lib().hp_device_synchronize())
     return dst.to_numpy(np.uint8, (dh, dw, 3))
+
+
+# ---- writing back: skeletons painted into frames (hp_overlay_*; the rules are stated in csrc/overlay.hpp and DESIGN.md 1.1) -------------
+
+def _humans(humans) -> np.ndarray:
+    return np.ascontiguousarray(humans, HUMAN_DTYPE).reshape(-1)
+
+
+def overlay_primitives(humans, w: int, h: int, thickness: int = 0) -> np.ndarray:
+    """``hp_overlay_primitives``: the primitive list of a frame's humans (OVERLAY_PRIM_DTYPE records, in painting order)."""
+    hs = _humans(humans)
+    out = np.zeros(max(1, 37 * len(hs)), OVERLAY_PRIM_DTYPE)
+    n = check(lib().hp_overlay_primitives(hs.ctypes.data_as(C.POINTER(Human)), len(hs), int(w), int(h), int(thickness),
+                                          out.ctypes.data_as(C.POINTER(OverlayPrim)), len(out)))
+    return out[:n]
+
+
+def yuv_colours(matrix: str = "bt601", range: str = "limited", depth: int = 8) -> np.ndarray:
+    """``hp_yuv_colours``: the 19 skeleton colours as ``depth``-bit (Y, U, V), int32 [19, 3]."""
+    out = np.zeros((19, 3), np.int32)
+    check(lib().hp_yuv_colours(YUV_MATRICES[matrix], YUV_RANGES[range], int(depth), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+class Overlay:
+    """``hp_overlay``: the handle the device entry points draw through (pinned staging slots and device lists for ``max_humans`` per call)."""
+
+    def __init__(self, max_humans: int = 64):
+        self.h = C.c_void_p()
+        self.max_humans = int(max_humans)
+        check(lib().hp_overlay_create(C.byref(self.h), self.max_humans))
+
+    def close(self):
+        if self.h:
+            lib().hp_overlay_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_overlay = None
+
+
+def _default_overlay(n: int) -> Overlay:
+    global _overlay
+    if _overlay is None or _overlay.max_humans < n:
+        _overlay = Overlay(max(64, n))
+    return _overlay
+
+
+def draw_humans(target, humans, opacity: float = 1.0, thickness: int = 0, w=None, h=None, stride=None, stream=None, overlay=None) -> None:
+    """Paint the skeletons of ``humans`` (HUMAN_DTYPE, in the frame's normalised coordinates) into a frame in DEVICE memory, in place and
+    stream-ordered: ``target`` is a ``YuvImage`` whose planes are device pointers (``hp_overlay_draw_yuv``) or a device buffer of 8-bit BGR
+    with ``w``, ``h`` and optionally ``stride`` in bytes (``hp_overlay_draw_u8c3``)."""
+    hs = _humans(humans)
+    ov = overlay or _default_overlay(len(hs))
+    hp, s = hs.ctypes.data_as(C.POINTER(Human)), C.c_void_p(stream) if stream else None
+    if isinstance(target, YuvImage):
+        check(lib().hp_overlay_draw_yuv(ov.h, C.byref(target), hp, len(hs), C.c_float(opacity), int(thickness), s))
+    else:
+        check(lib().hp_overlay_draw_u8c3(ov.h, as_ptr(target), int(w), int(h), int(stride or w * 3), hp, len(hs), C.c_float(opacity), int(thickness), s))
+
+
+def draw_humans_host(frame, humans, fmt=None, matrix: str = "bt601", range: str = "limited", opacity: float = 1.0, thickness: int = 0) -> None:
+    """The same picture on a frame in HOST memory, in place, no device needed: ``frame`` is a uint8 array [h, w, 3] (BGR, ``fmt`` None) or the
+    list of 2-D plane arrays ``yuv_planes`` returns (``fmt`` names the layout).  Rows may be padded (views of wider arrays); samples must be
+    contiguous within a row."""
+    hs = _humans(humans)
+    hp = hs.ctypes.data_as(C.POINTER(Human))
+    if fmt is None:
+        assert frame.dtype == np.uint8 and frame.ndim == 3 and frame.shape[2] == 3 and frame.strides[1:] == (3, 1) and frame.flags.writeable
+        check(lib().hp_overlay_draw_u8c3_host(C.c_void_p(frame.ctypes.data), frame.shape[1], frame.shape[0], frame.strides[0], hp, len(hs),
+                                              C.c_float(opacity), int(thickness)))
+        return
+    for p in frame:
+        assert p.ndim == 2 and p.strides[1] == p.itemsize and p.flags.writeable
+    w, h = yuv_size_of_planes(fmt, frame)
+    im = yuv_image(fmt, [p.ctypes.data for p in frame], [p.strides[0] for p in frame], w, h, matrix, range)
+    check(lib().hp_overlay_draw_yuv_host(C.byref(im), hp, len(hs), C.c_float(opacity), int(thickness)))

@@ -164,6 +164,47 @@ size_t hp_yuv_packed_bytes(int format, int width, int height);
  * either pointer may be NULL (host only) */
 int hp_yuv_plane_layout(int format, int k, int width, int height, size_t* row_bytes, int* rows);
 
+/* ---- writing back: the skeletons of a frame's humans painted into a DEVICE-resident frame, 8-bit BGR or any hp_yuv_image layout in the frame's
+ * own colour space and bit depth (hyperpose_amd/csrc/overlay.hip) - the last stage of the reference's stream, draw_human + writer
+ * (src/stream.cpp:114-147), for frames that never leave the device.  The picture is defined by exact integer rules, stated once in
+ * hyperpose_amd/csrc/overlay.hpp and DESIGN.md 1.1 (it is NOT cv::line / cv::circle's anti-alias-free raster, and says so):
+ *   primitives   per human, in order: limbs pair_id 0..18 whose two parts are present, as capsules, then parts 0..17, as discs; a part is present
+ *                when has_value and x, y are finite; points are int(x * w), int(y * h) in fp32; T = thickness when > 0 (<= 16384), else the
+ *                reference's max(1, int(sqrtf((e - w) * (s - n) * (w * h))) / 32) per human; a primitive with a point outside [-8192, 16383] is
+ *                dropped; a disc has (x1, y1) = (x0, y0)
+ *   coverage     int64, p = (x - x0, y - y0), d = (x1 - x0, y1 - y0), L = d.d, s = p.d.  capsule: L == 0 or s <= 0: 4 p.p <= T^2; s >= L:
+ *                4 (p - d).(p - d) <= T^2; else 4 (p.x d.y - p.y d.x)^2 <= T^2 L.  disc: p.p <= T^2.  The last covering primitive wins.
+ *   samples      w = nearbyint(opacity * 256); a covered sample becomes (c * w + old * (256 - w) + 128) >> 8 (w == 256: c); a chroma sample is written
+ *                when any of the 1 x 1 / 2 x 1 / 2 x 2 pixels it covers is, with the colour of the last primitive covering any of them; nothing
+ *                else is read or written (row padding included).  YUV colours: hp_yuv_colours.
+ * The handle owns pinned staging slots and device lists for up to max_humans humans per call; a draw call only ENQUEUES on `stream` (NULL = the
+ * default stream) and does not wait for the previous call.  Frames follow hp_resize_yuv's rules (sizes per layout, strides cover a row, even
+ * planes / strides for the 16-bit layouts); also HP_ERR_INVALID, with a message that names the format and nothing launched: opacity outside
+ * (0, 1], n > max_humans, width or height over 8192.  n == 0 is HP_OK and launches nothing. */
+typedef struct hp_overlay hp_overlay;
+typedef struct hp_overlay_prim {
+    int32_t kind; /* 0 capsule, 1 disc */
+    int32_t x0, y0, x1, y1, t;
+    int32_t colour; /* 0..18 */
+    int32_t human;
+} hp_overlay_prim;
+int hp_overlay_create(hp_overlay** out, int max_humans);
+void hp_overlay_destroy(hp_overlay* o);
+/* host only: the primitive list; returns the count (or a negative HP_ERR_*), writes at most cap entries */
+int hp_overlay_primitives(const hp_human* humans, int n, int w, int h, int thickness, hp_overlay_prim* out, int cap);
+/* host only: the 19 colours of draw_human as d-bit (Y, U, V) for a matrix / range / depth (8 or 10): Y' = Kr R + Kg G + Kb B on [0, 1],
+ * Cb = (B - Y') / (2 (1 - Kb)), Cr = (R - Y') / (2 (1 - Kr)), float64; limited: Y = nearbyint((16 + 219 Y') 2^(d-8)), C = nearbyint((128 + 224 Cx) 2^(d-8));
+ * full: Y = nearbyint(Y' (2^d - 1)), C = nearbyint(2^(d-1) + Cx (2^d - 1)); clipped to [0, 2^d - 1] */
+int hp_yuv_colours(int matrix, int range, int depth, int32_t out[19][3]);
+/* device frames, written in place; humans in host memory, already in the FRAME's normalised coordinates (after resume_ratio) */
+int hp_overlay_draw_u8c3(hp_overlay* o, uint8_t* dev_bgr, int w, int h, int stride, const hp_human* humans, int n, float opacity, int thickness,
+                         void* stream);
+int hp_overlay_draw_yuv(hp_overlay* o, const hp_yuv_image* frame /* planes in DEVICE memory, WRITTEN */, const hp_human* humans, int n, float opacity,
+                        int thickness, void* stream);
+/* the same picture on frames in HOST memory (plain C++, the integer rules above; no device needed) */
+int hp_overlay_draw_u8c3_host(uint8_t* bgr, int w, int h, int stride, const hp_human* humans, int n, float opacity, int thickness);
+int hp_overlay_draw_yuv_host(const hp_yuv_image* frame, const hp_human* humans, int n, float opacity, int thickness);
+
 /* ---- hyperpose::parser::paf (include/hyperpose/operator/parser/paf.hpp:17-93, src/paf.cpp) -------- */
 typedef struct hp_paf hp_paf;
 

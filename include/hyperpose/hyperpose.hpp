@@ -7,3 +7,4 @@
 #include "stream/stream.hpp"
 #include "utility/data.hpp"
 #include "utility/human.hpp"
+#include "utility/overlay.hpp"

@@ -1,0 +1,83 @@
+// hyperpose::draw_humans — addition: the skeletons of a frame's humans painted into a video frame where it lies, in the frame's own layout,
+// colour space and bit depth (hp_overlay_*, include/hp_hip.h).  The device-side counterpart of draw_human (human.hpp, untouched): a
+// yuv_frame with `on_device` set, or a device_bgr picture, is painted by one kernel launch on `stream` (asynchronous, stream-ordered); a
+// yuv_frame in host memory is painted by the library's host twin, which gives the same bytes.  The picture is defined by exact integer rules
+//  - capsules of width T for limbs, discs of radius T for parts, T by draw_human's rule unless `thickness` > 0, the last
+// primitive wins, `opacity` in (0, 1] blends - and is not cv::line / cv::circle's raster.  Humans are in the FRAME's normalised coordinates
+// (after resume_ratio).  Errors of the C ABI (bad layout, opacity outside (0, 1], frames over 8192 x 8192) throw std::logic_error.
+#pragma once
+#include <algorithm>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "data.hpp"
+#include "human.hpp"
+
+namespace hyperpose {
+
+/// an 8-bit BGR HWC picture in device memory, rows `stride` bytes apart (0 = packed rows)
+struct device_bgr {
+    uint8_t* ptr = nullptr;
+    int width = 0, height = 0, stride = 0;
+};
+
+namespace detail {
+    inline std::vector<hp_human> to_c_humans(const std::vector<human_t>& humans)
+    {
+        std::vector<hp_human> out(humans.size());
+        for (size_t i = 0; i < humans.size(); ++i) {
+            for (int k = 0; k < COCO_N_PARTS; ++k) {
+                const auto& p = humans[i].parts[k];
+                out[i].parts[k] = hp_body_part{ p.has_value ? 1 : 0, p.x, p.y, p.score };
+            }
+            out[i].score = humans[i].score;
+        }
+        return out;
+    }
+    // the calling thread's hp_overlay handle, grown when a frame has more humans than it was made for (one handle = one thread, hp_hip.h).
+    // It is released when the thread ends; for the main thread that is before objects of static storage duration are destroyed
+    // ([basic.start.term]), hence before the HIP runtime's own teardown, and hp_overlay_destroy ignores what a late call returns
+    inline hp_overlay* overlay_handle(size_t n_humans)
+    {
+        struct holder {
+            hp_overlay* h = nullptr;
+            size_t cap = 0;
+            ~holder() { hp_overlay_destroy(h); }
+        };
+        thread_local holder t;
+        if (!t.h || t.cap < n_humans) {
+            hp_overlay_destroy(t.h);
+            t.h = nullptr, t.cap = std::max<size_t>(64, n_humans);
+            if (hp_overlay_create(&t.h, (int)t.cap) != HP_OK)
+                throw std::runtime_error(std::string("hyperpose::draw_humans: ") + hp_last_error());
+        }
+        return t.h;
+    }
+    inline void overlay_check(int rc)
+    {
+        if (rc != HP_OK)
+            throw std::logic_error(std::string("hyperpose::draw_humans: ") + hp_last_error());
+    }
+} // namespace detail
+
+/// `frame.plane[]` is WRITTEN (the struct declares it const because the engine only reads it)
+inline void draw_humans(yuv_frame& frame, const std::vector<human_t>& humans, float opacity = 1, int thickness = 0, void* stream = nullptr)
+{
+    const auto list = detail::to_c_humans(humans);
+    const hp_yuv_image im = frame.image();
+    if (frame.on_device)
+        detail::overlay_check(hp_overlay_draw_yuv(detail::overlay_handle(list.size()), &im, list.data(), (int)list.size(), opacity, thickness, stream));
+    else
+        detail::overlay_check(hp_overlay_draw_yuv_host(&im, list.data(), (int)list.size(), opacity, thickness));
+}
+
+inline void draw_humans(const device_bgr& picture, const std::vector<human_t>& humans, float opacity = 1, int thickness = 0, void* stream = nullptr)
+{
+    const auto list = detail::to_c_humans(humans);
+    detail::overlay_check(hp_overlay_draw_u8c3(detail::overlay_handle(list.size()), picture.ptr, picture.width, picture.height,
+        picture.stride ? picture.stride : picture.width * 3, list.data(), (int)list.size(), opacity, thickness, stream));
+}
+
+} // namespace hyperpose
