@@ -21,18 +21,23 @@
 //             CU, the staging / transform of a pixel tile shared by 128 channels - 44.6 us alone against 46.3 for a 128 -> 128 layer at
 //             8 x 46 x 54, but 31.5 against 28.8 with a second stream (its phases are in step inside the one block).
 //             (The first form - 32 channels x 16 tiles per wavefront - read 2 KB of A per eight MFMAs: 68 us alone.)
-//   K loop  = chunks of 16 input channels.  The chunk's 18 x 10 halo patch arrives from HBM as fp32 (requested two chunks ahead, into
-//             registers), goes to LDS, is transformed cooperatively (a wavefront = ONE row of Bt d B for 16 tiles, lane = (tile, 4-channel
+//   K loop  = chunks of 16 input channels.  The chunk's 18 x 10 halo patch (19 rows in a block that holds an image boundary: see "rows form" in
+//             the kernel) arrives from HBM as fp32 (requested two chunks ahead, into registers), goes to LDS, is
+//             transformed cooperatively (a wavefront = ONE row of Bt d B for 16 tiles, lane = (tile, 4-channel
 //             quad): 8 LDS reads, 8 vector additions, 4 LDS writes) into V[pos][tile][16 channels].  MW = 4 (PIPE): two V buffers, the
 //             transform of chunk c + 1 cut into 16 pieces that sit inside the 16 MFMA steps of chunk c (46.6 -> 44.3 us alone, 28.9 -> 27.0
 //             with a second stream; the unpipelined form is no longer launched); MW = 8: one buffer, the transform between two barriers;
 //   MFMA    = per position one step of 16 channels: lane (row / tile, kq) holds channels 4 kq .. 4 kq + 3 of its row (A, 1 KB from L2 in
 //             fragment order, six steps ahead) / tile (B, two ds_read_b128 from V) and feeds element e to MFMA e - 8 MFMAs of 32 cycles per step;
-//   output  = At M A per lane from its own registers (lane (tile, kq) holds channels 4 kq + r at all 16 positions), written into a slab the
-//             block shares ([128 pixels][16 MW channels]), then the row-major epilogue of conv32_epilogue.hpp: whole pixel rows.
-// Block timeline (tools/direct_timeline.py f32; shader cycles at 2.2 GHz, MW = 4, PIPE, 128 -> 128 at 8 x 46 x 54, two blocks per CU): start +
-// chunk 0's transform 5.7 k | per chunk: patch stored 0.6 - 1.2 k, multiplied 7.4 - 8.0 k (8.2 k = the pipe's time for the two blocks' 2 x 128
-// MFMAs per SIMD: the loop is at the pipe's rate) | output transform + stores 17 k.  89 k cycles per block of which 2 x 32.8 k are MFMA issue.
+//   output  = bias, slopes and the residual quads of all of the wavefront's pixel rows are requested right behind the K loop; then At M A per
+//             lane from its own registers (lane (tile, kq) holds channels 4 kq + r at all 16 positions), written into a slab the block shares
+//             ([128 pixels][16 MW channels]), then the row-major epilogue (the arithmetic of conv32_epilogue.hpp): whole pixel rows, the stores
+//             of all passes back to back.
+// Block timeline (tools/direct_timeline.py f32; shader cycles at 2.2 GHz, MW = 4, PIPE, 128 -> 128 at 8 x 46 x 54, 322 blocks, two per CU; medians
+// of 34 launches, profiles/winograd_phases.json): chunk 0 staged 2.5 k | transformed, chunk 1's patch stored 2.6 k | per chunk: multiplied 7.2 -
+// 8.7 k (chunk 0: 6.4 k; 8.2 k = the pipe's time for the two blocks' 2 x 128 MFMAs per SIMD: the loop is at the pipe's rate), next patch stored
+// 0.4 - 1.0 k | epilogue requests 2.1 k (3.1 k with a residual) | output transform 1.5 k | stores 5.4 k.  81 - 82 k cycles per block, with or
+// without a residual (before: 85 k without, 89 k with one), of which 2 x 32.8 k are MFMA issue.
 #include "conv_fp32.hpp"
 
 #include "conv32_epilogue.hpp"
@@ -46,6 +51,8 @@ namespace hp {
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) float gfloat; // global memory, said to the compiler
+typedef __attribute__((address_space(1))) f32x4 gf32x4;
 
 constexpr int WCK = 16;                        // input channels per chunk
 constexpr int HALO_W = 10;                     // halo patch of the 16 NC x 8 pixel tile: (8 NC + 2) x 10 pixels
@@ -56,8 +63,10 @@ constexpr int VP = 24 * 4;                     // V row (one tile, 16 channels) 
 template <int MW, int NC = 2>
 struct wino_geom {
     static constexpr int NT = 64 * MW;
-    static constexpr int HALO_H = 8 * NC + 2;
-    static constexpr int RAW_Q = HALO_H * HALO_W * 4; // float4 quads of the halo patch (64 bytes per pixel): 720 | 400
+    static constexpr int TB = 4 * NC;                 // tile rows of a block
+    static constexpr int HALO_H = 8 * NC + 2;         // patch rows of a block inside one image
+    static constexpr int PATCH_H = HALO_H + 1;        // ... of a block that holds an image boundary (rows form, even H): the tiles at the boundary share one row
+    static constexpr int RAW_Q = PATCH_H * HALO_W * 4; // float4 quads of the halo patch (64 bytes per pixel): 760 | 440
     static constexpr int NQ = (RAW_Q + NT - 1) / NT;  // quads per thread and chunk
     static constexpr int RAW_BYTES = NQ * NT * 16;    // + room for the surplus threads' (discarded) quads: the store to LDS has no branch
     static constexpr int NI = 4 * NC / MW;            // transform items (row of Bt d B, 16 tiles) per wavefront and chunk
@@ -65,7 +74,7 @@ struct wino_geom {
     static constexpr int TMS = MW / 2;                // the block's output slab: [64 NC pixel rows][16 MW channels + 4] = rows_geom<TMS>
     static constexpr int SLAB_PITCH = rows_geom<TMS>::PITCH, SLAB_BYTES = 64 * NC * SLAB_PITCH * 4;
     static constexpr int VPOS = 16 * NC * VP, VBUF = 16 * VPOS; // one position (16 NC tiles), all 16 positions
-    static constexpr int LDS_BYTES = RAW_BYTES + (VBUF > SLAB_BYTES ? VBUF : SLAB_BYTES); // MW = 4: 61440 (two blocks per CU), MW = 8: 83968 (one)
+    static constexpr int LDS_BYTES = RAW_BYTES + (VBUF > SLAB_BYTES ? VBUF : SLAB_BYTES);
     // the pipelined form (MW = 4): two V buffers without padding - 64 bytes per tile, the 16-byte quad index XOR-ed with a function of the
     // tile so that the transform's ds_write_b128 and the MFMA's ds_read_b128 (same lane -> (tile, quad) map) stay conflict-free
     static constexpr int PVPOS = 16 * NC * 64, PVBUF = 16 * PVPOS;                  // 32768 | 16384 bytes per buffer
@@ -81,11 +90,11 @@ __device__ __forceinline__ long tvw_off(const tview32& t, int b, int y, int x)
 
 // PIPE: the input transform of chunk c + 1 runs inside the MFMA steps of chunk c (two V buffers): see "K loop" above
 template <int MW, bool PIPE, int NC = 2>
-__global__ __launch_bounds__(64 * MW, MW == 8 ? 1 : NC == 1 ? 3 : 2) void conv32_winograd_kernel(const conv32_params p, int tiles_x, int tiles_y, int vh)
+__global__ __launch_bounds__(64 * MW, MW == 8 ? 1 : NC == 1 ? 3 : 2) void conv32_winograd_kernel(const conv32_params p, int tiles_x, int tiles_y, int vh, int T)
 {
     static_assert(!PIPE || MW == 4, "the pipelined form is the four-wavefront one");
     using G = wino_geom<MW, NC>;
-    constexpr int NT = G::NT, NQ = G::NQ, SLAB_PITCH = G::SLAB_PITCH, RAW_Q = G::RAW_Q, VPOS = G::VPOS;
+    constexpr int NT = G::NT, NQ = G::NQ, SLAB_PITCH = G::SLAB_PITCH, VPOS = G::VPOS;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[]; // G::LDS_BYTES
     unsigned char* const raw = lds;
     unsigned char* const vb = lds + G::RAW_BYTES;
@@ -98,7 +107,16 @@ __global__ __launch_bounds__(64 * MW, MW == 8 ? 1 : NC == 1 ? 3 : 2) void conv32
     // 14 rows of a 446-row image (28 blocks of 16 rows) instead of one three-quarters-empty block per image (32).  vh is even, so every 2 x 2
     // Winograd tile covers the same rows of every image: the same bits as the per-image form, whatever the batch.  Output rows that fall on
     // separator rows are computed and not stored.
-    const int NG = p.Cout_pad / (16 * MW), ntiles = tiles_x * tiles_y * (vh ? 1 : p.B);
+    // T > 0, the "rows" form: tile rows numbered per image - T = ceil(H / 2) of them each, tile row r = rows 2 (r % T), 2 (r % T) + 1 of image
+    // r / T - so the grid holds the B T tile rows that exist and no separator rows (8 x 23 = 184 tile rows are 23 blocks of 16 pixel rows, not
+    // 24).  T >= the block's tile rows: a block holds at most one image boundary, after its first kb tile rows.  The tile row below the boundary
+    // needs a row of zeros (its image's top halo row) and then its rows 0 - 2, the tile row above it ends with rows H - 2, H - 1, the bottom halo
+    // row H (zeros) and, where H is odd, a fourth row that only feeds an output row that does not exist.  One halo row is as good as the other:
+    // even H - the lower tile row starts ON the upper one's last patch row (the bottom halo row) and goes on with its own rows 0 - 2: a patch of
+    // G::PATCH_H = G::HALO_H + 1 rows, the lower tile rows one patch row further down; odd H - it starts on the upper one's third row (the bottom
+    // halo row) and its row 0 takes the place of the row nobody needs: G::HALO_H rows, no shift at all.  The same tiles of every image, the same
+    // arithmetic on the same values: the same bits as the per-image form.
+    const int NG = p.Cout_pad / (16 * MW), ntiles = tiles_x * tiles_y * (vh || T ? 1 : p.B);
     const int Hin = vh ? (p.B - 1) * vh + p.H : p.H; // rows 0 .. Hin - 1; row Hin = the (last) image's bottom halo row
     const int bj = blockIdx.x >> 3, by = bj % NG;
     int t = (bj / NG) * 8 + (blockIdx.x & 7);
@@ -122,16 +140,28 @@ __global__ __launch_bounds__(64 * MW, MW == 8 ? 1 : NC == 1 ? 3 : 2) void conv32
     // ---- staging geometry: quad q of a chunk = (halo pixel q / 4, channels 4 (q % 4) ..); halo pixel (hy, hx) = image pixel (y0 - 1 + hy, x0 - 1 + hx).
     // The tensor's zero halo is the convolution's padding; pixels further out (ragged last tiles, the fourth patch row / column of an odd-sized
     // map) are clamped to it and zeroed - they only feed outputs that are never stored
+    // Rows form: patch rows 0 .. ylow - 1 are rows ly0 .. of image img0 (down to its bottom halo row), patch rows from ylow on are rows 0 .. of
+    // image img0 + 1, whose tile rows start at patch row 2 j + sh (kb = TB: no boundary in this block); tile rows past the last image read
+    // zeros.  The other forms: one run of rows (kb = TB) of image b
+    int kb = G::TB, sh = 0, img0 = b, ly0 = y0 - 1, l0 = 0;
+    if (T) {
+        const int r0 = ty * G::TB;
+        img0 = r0 / T, l0 = r0 - img0 * T, ly0 = 2 * l0 - 1;
+        kb = min(T - l0, G::TB), sh = kb < G::TB && !(p.H & 1);
+    }
+    const int Hlim = T ? p.H : Hin, ylow = kb < G::TB ? 2 * kb + 1 + sh : G::PATCH_H;
+    const int nvalid = (G::HALO_H + sh) * HALO_W * 4; // the quads this block needs
     long goff[NQ];
     bool qok[NQ];
 #pragma unroll
     for (int i = 0; i < NQ; ++i) {
-        const int q = min(tid + i * NT, RAW_Q - 1);
+        const int q = min(tid + i * NT, nvalid - 1);
         const int hp = q >> 2, c4 = q & 3;
         const int hy = hp / HALO_W, hx = hp - hy * HALO_W;
-        const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-        qok[i] = y <= Hin && x <= p.W;
-        goff[i] = tvw_off(p.in, b, min(y, Hin), min(x, p.W)) + c4 * 4;
+        const bool below = hy >= ylow;
+        const int bi = below ? img0 + 1 : img0, y = below ? hy - ylow : ly0 + hy, x = x0 - 1 + hx;
+        qok[i] = y <= Hlim && x <= p.W && bi < p.B;
+        goff[i] = tvw_off(p.in, min(bi, p.B - 1), min(y, Hlim), min(x, p.W)) + c4 * 4;
     }
     f32x4 stage[NQ];
     auto gload = [&](int c) {
@@ -144,6 +174,11 @@ __global__ __launch_bounds__(64 * MW, MW == 8 ? 1 : NC == 1 ? 3 : 2) void conv32
         for (int i = 0; i < NQ; ++i)
             *reinterpret_cast<f32x4*>(raw + (tid + i * NT) * 16) = qok[i] ? stage[i] : f32x4{ 0.f, 0.f, 0.f, 0.f };
     };
+    // the patch row of a block's tile row: two rows per tile row, and sh more below the image boundary (rows form)
+    auto tile_src = [&](int tile, int quad) {
+        const int tr = tile >> 2;
+        return raw + ((2 * tr + (tr >= kb ? sh : 0)) * HALO_W + 2 * (tile & 3)) * RAW_PB + quad * 16;
+    };
     // ---- input transform: item of a wavefront = (row i of Bt d B, 16 of the 32 tiles); lane (tile, quad) like the MFMA's B read.  Row i of
     // T = Bt d combines two patch rows; V[i][.] = T[i][.] B
     auto transform = [&]() {
@@ -153,20 +188,20 @@ __global__ __launch_bounds__(64 * MW, MW == 8 ? 1 : NC == 1 ? 3 : 2) void conv32
             const int quad = lane >> 4, tile = (NC == 2 ? (item & 1) * 16 : 0) + (lane & 15);
             const int ra = i == 0 ? 0 : i == 2 ? 2 : 1, rb = i == 0 ? 2 : i == 1 ? 2 : i == 2 ? 1 : 3;
             const float sg = i == 1 ? 1.f : -1.f;
-            const unsigned char* const src = raw + ((2 * (tile >> 2)) * HALO_W + 2 * (tile & 3)) * RAW_PB + quad * 16;
-            f32x4 T[4];
+            const unsigned char* const src = tile_src(tile, quad);
+            f32x4 Td[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const f32x4 a = *reinterpret_cast<const f32x4*>(src + (ra * HALO_W + j) * RAW_PB);
                 const f32x4 bq = *reinterpret_cast<const f32x4*>(src + (rb * HALO_W + j) * RAW_PB);
-                T[j] = a + sg * bq; // (an exact sign change, then one rounded addition)
+                Td[j] = a + sg * bq; // (an exact sign change, then one rounded addition)
             }
             constexpr int PS = PIPE ? G::PVPOS : VPOS;
             unsigned char* const dst = PIPE ? vb + (i * 4) * PS + tile * 64 + ((quad ^ ((4 - (tile >> 2)) & 3)) * 16) : vb + (i * 4) * PS + tile * VP + quad * 16;
-            *reinterpret_cast<f32x4*>(dst) = T[0] - T[2];
-            *reinterpret_cast<f32x4*>(dst + PS) = T[1] + T[2];
-            *reinterpret_cast<f32x4*>(dst + 2 * PS) = T[2] - T[1];
-            *reinterpret_cast<f32x4*>(dst + 3 * PS) = T[1] - T[3];
+            *reinterpret_cast<f32x4*>(dst) = Td[0] - Td[2];
+            *reinterpret_cast<f32x4*>(dst + PS) = Td[1] + Td[2];
+            *reinterpret_cast<f32x4*>(dst + 2 * PS) = Td[2] - Td[1];
+            *reinterpret_cast<f32x4*>(dst + 3 * PS) = Td[1] - Td[3];
         }
     };
     // the same transform in pieces, one per MFMA step (PIPE): item k = 0 in steps 0 - 7, k = 1 in steps 8 - 15 of the PREVIOUS chunk's
@@ -179,7 +214,7 @@ __global__ __launch_bounds__(64 * MW, MW == 8 ? 1 : NC == 1 ? 3 : 2) void conv32
         const int item = wave + k * MW, i = NC == 2 ? item >> 1 : item;
         const int quad = lane >> 4, tile = (NC == 2 ? (item & 1) * 16 : 0) + (lane & 15);
         const int ra = i == 0 ? 0 : i == 2 ? 2 : 1, rb = i == 0 ? 2 : i == 1 ? 2 : i == 2 ? 1 : 3;
-        const unsigned char* const src = raw + ((2 * (tile >> 2)) * HALO_W + 2 * (tile & 3)) * RAW_PB + quad * 16;
+        const unsigned char* const src = tile_src(tile, quad);
         if (ps < 4) {
             ta[ps] = *reinterpret_cast<const f32x4*>(src + (ra * HALO_W + ps) * RAW_PB);
             tb[ps] = *reinterpret_cast<const f32x4*>(src + (rb * HALO_W + ps) * RAW_PB);
@@ -215,25 +250,33 @@ __global__ __launch_bounds__(64 * MW, MW == 8 ? 1 : NC == 1 ? 3 : 2) void conv32
     constexpr int BPOS = PIPE ? G::PVPOS : VPOS, BNT = PIPE ? 16 * 64 : 16 * VP; // B fragment strides: position, second column tile
 
     gload(0);
-#pragma unroll
-    for (int a = 0; a < AHEAD; ++a)
-        aload(a, a);
     if constexpr (PIPE) { // chunk 0's transform is the one that nothing hides
+#pragma unroll
+        for (int a = 0; a < AHEAD; ++a)
+            aload(a, a);
         to_lds();
         gload(1);
         lds_barrier();
+        HP_STAMP();
         transform();
+        lds_barrier(); // V[0] is complete and every wavefront has left the patch
+        to_lds();      // chunk 1's patch
+        gload(2);
+        lds_barrier(); // chunk 1's patch is complete
+        HP_STAMP();
+    } else {
+#pragma unroll
+        for (int a = 0; a < AHEAD; ++a)
+            aload(a, a);
     }
     int s = 0;
 #pragma unroll 1
     for (int c = 0; c < nch; ++c) {
-        if constexpr (PIPE)
-            lds_barrier(); // V[c & 1] is complete and every wavefront has left the patch (transform c) and V[(c + 1) & 1] (chunk c - 1's MFMAs)
-        to_lds();     // PIPE: chunk c + 1's patch; else chunk c's (the previous chunk's transform is behind every wavefront: its second barrier)
-        gload(PIPE ? c + 2 : c + 1); // (past the last chunk: a harmless re-read of it)
-        lds_barrier(); // the patch is complete (!PIPE: AND every wavefront has left the previous chunk's MFMAs: V may be overwritten)
-        HP_STAMP();
         if constexpr (!PIPE) {
+            to_lds();      // chunk c's patch (the previous chunk's transform is behind every wavefront: its second barrier)
+            gload(c + 1);  // (past the last chunk: a harmless re-read of it)
+            lds_barrier(); // the patch is complete AND every wavefront has left the previous chunk's MFMAs: V may be overwritten
+            HP_STAMP();
             transform();
             lds_barrier();
             HP_STAMP();
@@ -273,10 +316,77 @@ __global__ __launch_bounds__(64 * MW, MW == 8 ? 1 : NC == 1 ? 3 : 2) void conv32
             ++s;
         }
         HP_STAMP();
+        if constexpr (PIPE) { // the hand-over of chunk c + 2's patch (chunk c + 1's is in LDS, transformed under the steps above)
+            if (c + 1 < nch) {
+                lds_barrier(); // V[(c + 1) & 1] is complete and every wavefront has left the patch (transform c + 1) and V[c & 1] (chunk c's MFMAs)
+                to_lds();
+                gload(c + 3); // (past the last chunk: a harmless re-read of it)
+                lds_barrier(); // the patch is complete
+                HP_STAMP();
+            }
+        }
     }
 
     // ---- output transform Y = At M A, per lane: tile 16 nt + (lane & 15), channels 16 wave + 4 kq + r; then whole pixel rows through the
     // block's slab.  Slab row (a * 2 + bb) * 32 + tile = output pixel (2 tile_y + a, 2 tile_x + bb) of the block's 16 x 8
+    // The epilogue's inputs first (the ring, the B fragments, the transform's quads and the stage set are dead: their registers hold these
+    // now): wavefront w drains slab rows RPW w .. in NPASS passes of RPP pixel rows, lane (row, c4) = channels 4 c4 .. of its row.  Bias, slopes
+    // and the residual quads of ALL passes are requested here, so that the output transform and the slab exchange run under those loads.
+    int tid_o = tid;
+    asm volatile("" : "+v"(tid_o)); // (the lane's coordinates once more from the thread id: kept across the K loop they cost it registers)
+    const int lane_o = tid_o & 63, btile_o = lane_o & 15, kq_o = lane_o >> 4;
+    using R = rows_geom<G::TMS>;
+    constexpr int RPW = 64 * NC / MW, NPASS = RPW / R::RPP;
+    static_assert(RPW % R::RPP == 0, "slab rows per pass");
+    const int dc4 = lane_o % R::LPR, dm = by * 16 * MW + dc4 * 4;
+    // No branch depends on the lane between the first request and the last (a divergent branch is a join at which hipcc waits for every load
+    // in flight): clamped addresses instead, every lane loads, the quad path where Cout is whole quads (then a lane's quad is all or nothing)
+    const bool dany = dm < p.Cout, quads = (p.Cout & 3) == 0;
+    const bool out_vec = quads && ((p.out.coff | p.out.cs) & 3) == 0, res_vec = quads && ((p.res.coff | p.res.cs) & 3) == 0;
+    const int dmc = dany ? dm : 0;
+    int dpix[NPASS], rpix[NPASS]; // the pixel's index in p.out / p.res (images of t.img pixels, rows of t.wp)
+    bool dok[NPASS];
+#pragma unroll
+    for (int k = 0; k < NPASS; ++k) {
+        const int rr = wave * RPW + k * R::RPP + lane_o / R::LPR, ab = rr / (16 * NC), tile = rr % (16 * NC), tr = tile >> 2;
+        const int ox = x0 + 2 * (tile & 3) + (ab & 1);
+        int oy, ob;
+        if (T) // rows form: the block's tile row tr = tile row l0 + tr of image img0, or tr - kb of the next one
+            ob = tr >= kb ? img0 + 1 : img0, oy = 2 * (tr >= kb ? tr - kb : l0 + tr) + (ab >> 1);
+        else { // tall form: row oy of the batch = row oy % vh of image oy / vh
+            oy = y0 + 2 * tr + (ab >> 1);
+            ob = vh ? oy / vh : b, oy -= vh ? ob * vh : 0;
+        }
+        dok[k] = oy < p.OH && ox < p.OW && ob < p.B && dany;
+        const int oyc = min(oy, p.OH - 1), oxc = min(ox, p.OW - 1), obc = min(ob, p.B - 1);
+        dpix[k] = (obc * p.out.img + oyc * p.out.wp) + oxc;
+        rpix[k] = (obc * p.res.img + oyc * p.res.wp) + oxc;
+    }
+    f32x4 dres[NPASS];
+#pragma unroll
+    for (int k = 0; k < NPASS; ++k)
+        dres[k] = f32x4{ 0.f, 0.f, 0.f, 0.f };
+    // (global_load, not flat_load: a flat request counts as LDS traffic too, which the barriers below wait for)
+    const gfloat* const gres = (const gfloat*)p.res.p;
+    gfloat* const gout = (gfloat*)p.out.p;
+    if (gres) {
+        if (res_vec) {
+#pragma unroll
+            for (int k = 0; k < NPASS; ++k)
+                dres[k] = *reinterpret_cast<const gf32x4*>(gres + ((long)rpix[k] * p.res.cs + p.res.coff + dmc));
+        } else {
+#pragma unroll
+            for (int k = 0; k < NPASS; ++k)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) // (channels past Cout: a re-read of the last one, never stored)
+                    dres[k][e] = gres[(long)rpix[k] * p.res.cs + p.res.coff + min(dm + e, p.Cout - 1)];
+        }
+    }
+    // (dm + 3 < Cout_pad: dm is a multiple of 4 below the padded channel count, which is a multiple of 64)
+    const f32x4 dbs = *(const gf32x4*)(p.bias + dm);
+    f32x4 dsl = { p.act_slope, p.act_slope, p.act_slope, p.act_slope };
+    if (p.alpha)
+        dsl = *(const gf32x4*)(p.alpha + dm);
     lds_barrier(); // every wavefront is done with V, which the slab lies over (MW = 8: and beyond)
     HP_STAMP();
     float* const slab = reinterpret_cast<float*>(vb);
@@ -291,25 +401,48 @@ __global__ __launch_bounds__(64 * MW, MW == 8 ? 1 : NC == 1 ? 3 : 2) void conv32
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             const f32x4 y0v = S[a][0] + S[a][1] + S[a][2], y1v = S[a][1] - S[a][2] - S[a][3];
-            *reinterpret_cast<f32x4*>(slab + ((a * 2 + 0) * (16 * NC) + nt * 16 + btile) * SLAB_PITCH + wave * 16 + kq * 4) = y0v;
-            *reinterpret_cast<f32x4*>(slab + ((a * 2 + 1) * (16 * NC) + nt * 16 + btile) * SLAB_PITCH + wave * 16 + kq * 4) = y1v;
+            *reinterpret_cast<f32x4*>(slab + ((a * 2 + 0) * (16 * NC) + nt * 16 + btile_o) * SLAB_PITCH + wave * 16 + kq_o * 4) = y0v;
+            *reinterpret_cast<f32x4*>(slab + ((a * 2 + 1) * (16 * NC) + nt * 16 + btile_o) * SLAB_PITCH + wave * 16 + kq_o * 4) = y1v;
         }
     }
     HP_STAMP();
     lds_barrier(); // the slab holds all 16 MW channels of the block's 128 pixels; wavefront w stores rows (128 / MW) w ..
     HP_STAMP();
-    constexpr int RPW = 64 * NC / MW;
-    conv32_drain_rows<G::TMS, RPW>(p, slab + wave * RPW * SLAB_PITCH, lane, by * 16 * MW, [&](int r, bool& ok, long& ooff, long& roff) {
-        const int rr = wave * RPW + r, ab = rr / (16 * NC), tile = rr % (16 * NC);
-        int oy = y0 + 2 * (tile >> 2) + (ab >> 1), ob = b;
-        const int ox = x0 + 2 * (tile & 3) + (ab & 1);
-        if (vh) // tall form: row oy of the batch = row oy % vh of image oy / vh
-            ob = oy / vh, oy -= ob * vh;
-        ok = oy < p.OH && ox < p.OW && ob < p.B;
-        const int oyc = min(oy, p.OH - 1), oxc = min(ox, p.OW - 1), obc = min(ob, p.B - 1);
-        ooff = tvw_off(p.out, obc, oyc, oxc);
-        roff = p.res.p ? tvw_off(p.res, obc, oyc, oxc) : 0;
-    });
+    // the arithmetic of conv32_drain_rows per element (bias, residual before or after the activation, clamp, slope); the stores of all passes
+    // back to back
+    const float* const wslab = slab + (wave * RPW + lane_o / R::LPR) * SLAB_PITCH + dc4 * 4;
+    f32x4 dv[NPASS];
+#pragma unroll
+    for (int k = 0; k < NPASS; ++k)
+        dv[k] = *reinterpret_cast<const f32x4*>(wslab + k * R::RPP * SLAB_PITCH);
+#pragma unroll
+    for (int k = 0; k < NPASS; ++k) {
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float x = dv[k][e] + dbs[e];
+            if (p.res.p && p.res_before_act)
+                x += dres[k][e];
+            x = x > 0.f ? fminf(x, p.act_hi) : x * dsl[e];
+            if (p.res.p && !p.res_before_act)
+                x += dres[k][e];
+            o[e] = x;
+        }
+        dv[k] = o;
+    }
+    if (out_vec) {
+#pragma unroll
+        for (int k = 0; k < NPASS; ++k)
+            if (dok[k])
+                *reinterpret_cast<gf32x4*>(gout + ((long)dpix[k] * p.out.cs + p.out.coff + dm)) = dv[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NPASS; ++k)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (dok[k] && dm + e < p.Cout)
+                    gout[(long)dpix[k] * p.out.cs + p.out.coff + dm + e] = dv[k][e];
+    }
     HP_STAMP();
 #undef HP_STAMP
     if (p.dbg && bx == 1 && by == 0 && tid == 0) // slots 119 - 122: the shader clock and the constant 100 MHz clock at the start / end
@@ -365,7 +498,7 @@ void conv32_winograd_pack(const float* packed, int cout_pad, int cin, float* out
 }
 
 template <int MW, bool PIPE, int NC = 2>
-static hipError_t launch_wino_case(const conv32_params& q, dim3 grid, int tiles_x, int tiles_y, int vh, hipStream_t s)
+static hipError_t launch_wino_case(const conv32_params& q, dim3 grid, int tiles_x, int tiles_y, int vh, int rows, hipStream_t s)
 {
     constexpr int lds = PIPE ? wino_geom<MW, NC>::PLDS_BYTES : wino_geom<MW, NC>::LDS_BYTES;
     static bool granted = false;
@@ -375,7 +508,7 @@ static hipError_t launch_wino_case(const conv32_params& q, dim3 grid, int tiles_
             return e;
         granted = true;
     }
-    HP_LAUNCH((conv32_winograd_kernel<MW, PIPE, NC>), grid, dim3(64 * MW), lds, s, q, tiles_x, tiles_y, vh);
+    HP_LAUNCH((conv32_winograd_kernel<MW, PIPE, NC>), grid, dim3(64 * MW), lds, s, q, tiles_x, tiles_y, vh, rows);
     return hipGetLastError();
 }
 
@@ -412,8 +545,13 @@ hipError_t launch_conv32_winograd(const conv32_params& p, const engine_switches&
     constexpr int mw = 4;
     const int tiles_x = (p.OW + 7) / 8;
     const int nc = winograd_nc(p, sw, tiles_x * ((p.OH + 15) / 16) * p.B * (p.Cout_pad / 64)), bh = 8 * nc;
-    int tiles_y = (p.OH + bh - 1) / bh, vh = winograd_tall(p, sw), images = p.B;
-    if (vh) {
+    int tiles_y = (p.OH + bh - 1) / bh, vh = winograd_tall(p, sw), images = p.B, rows = 0;
+    // the rows form (tile rows numbered per image: see the kernel) where an image has at least a block's tile rows and the batch's tile rows
+    // are fewer blocks than the images' own; it reads what the per-image form reads, whatever lies between two images
+    const int T = (p.OH + 1) / 2, rows_y = (p.B * T + 4 * nc - 1) / (4 * nc);
+    if (sw.wino_tall && p.B > 1 && T >= 4 * nc && rows_y < tiles_y * p.B)
+        tiles_y = rows_y, images = 1, rows = T, vh = 0;
+    else if (vh) { // fewer tile rows per image: the tall form
         const int tall_y = ((p.B - 1) * vh + p.H + bh - 1) / bh;
         if (tall_y < tiles_y * p.B)
             tiles_y = tall_y, images = 1;
@@ -422,8 +560,8 @@ hipError_t launch_conv32_winograd(const conv32_params& p, const engine_switches&
     }
     const dim3 grid((tiles_x * tiles_y * images + 7) / 8 * 8 * (p.Cout_pad / (16 * mw))); // XCD-aware 1-D order: see the kernel
     if (nc == 1)
-        return launch_wino_case<4, true, 1>(p, grid, tiles_x, tiles_y, vh, s);
-    return launch_wino_case<4, true>(p, grid, tiles_x, tiles_y, vh, s);
+        return launch_wino_case<4, true, 1>(p, grid, tiles_x, tiles_y, vh, rows, s);
+    return launch_wino_case<4, true>(p, grid, tiles_x, tiles_y, vh, rows, s);
 }
 
 hipError_t conv32_winograd_occupancy(const conv32_params&, int* blocks_per_cu)

@@ -1933,7 +1933,7 @@ int hp_engine::print_timeline(const step& st, const hp::conv32_params* q32, hipS
         fprintf(stderr, "\n");
         break;
     case WINO: { // block (1, 0), thread 0
-        fprintf(stderr, "winograd layer %d %d->%d tile %d cycles [start | staged, transformed, multiplied per chunk | stored]:", st.layer, q.Cin, q.Cout,
+        fprintf(stderr, "winograd layer %d %d->%d tile %d cycles [chunk 0 staged | transformed, chunk 1 stored | per chunk: multiplied, next patch stored | epilogue requests | output transform | slab complete | stored]:", st.layer, q.Cin, q.Cout,
             hp::conv32_winograd_tile(q));
         deltas(1, 119);
         int occ = 0;
