@@ -518,7 +518,7 @@ __global__ __launch_bounds__(256) void conv32_wk_kernel(const conv32_params p)
     const int fr = lane & 15, kq = lane >> 4;
     const int rrow = lane >> 3, rc = lane & 7; // row form: lane = (pixel rrow of 8, 16-byte chunk rc of 8) of a half tile
     const bool out_vec = ((p.out.coff | p.out.cs) & 3) == 0;
-    const bool res_vec = p.res.p && ((p.res.coff | p.res.cs) & 3) == 0 && p.res.cs >= p.Cout_pad; // (whole channel quads readable for every group of the padded matrix)
+    const bool res_vec = p.res.p && ((p.res.coff | p.res.cs) & 3) == 0 && p.res.coff + p.Cout_pad <= p.res.cs; // (whole channel quads readable for every group of the padded matrix, from the view's first channel on)
     const bool res_pre = p.res.p && p.res_before_act, res_post = p.res.p && !p.res_before_act;
     f32x4 bsr[2], slr[2];
 #pragma unroll

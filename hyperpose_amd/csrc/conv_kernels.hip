@@ -2297,14 +2297,33 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const dw_params p, int t
 #undef HP_DW_LOAD
 }
 
+// Loads per thread of dwconv3x3_kernel's halo tile (8 channel chunks of an 8 x 8 output tile's input window over 256 threads): the kernel
+// is instantiated for up to DW_MAX_NLD of them - stride 2 with dilation 2 (and wider) is beyond it
+constexpr int DW_MAX_NLD = 10;
+static int dw_halo_loads(const dw_params& p)
+{
+    const int IH = (DW_TH - 1) * p.stride + 2 * p.dil + 1, IW = (DW_TW - 1) * p.stride + 2 * p.dil + 1;
+    return (IH * IW * DW_CG + 255) / 256;
+}
+
+// whether launch_dwconv3x3 has a form for this layer - the launcher's own test, which the engine asks when it is built rather than at the
+// first inference: a piecewise-linear activation (none / relu / relu6 / leaky) and a halo tile the kernel is instantiated for
+bool dwconv3x3_ok(const dw_params& p)
+{
+    conv_params tmp{};
+    tmp.act = p.act, tmp.act_param = p.act_param, tmp.alpha = nullptr;
+    return p.act != ACT_PRELU && set_act(tmp) && dw_halo_loads(p) <= DW_MAX_NLD;
+}
+
 hipError_t launch_dwconv3x3(const dw_params& p_in, hipStream_t s)
 {
+    if (!dwconv3x3_ok(p_in))
+        return hipErrorInvalidValue;
     dw_params p = p_in;
     {   // piecewise-linear activations only (none / relu / relu6 / leaky), as y = v > 0 ? min(v, hi) : v * slope
         conv_params tmp{};
         tmp.act = p.act, tmp.act_param = p.act_param, tmp.alpha = nullptr;
-        if (p.act == ACT_PRELU || !set_act(tmp))
-            return hipErrorInvalidValue;
+        set_act(tmp);
         p.act_slope = tmp.act_slope, p.act_hi = tmp.act_hi;
     }
     const int tiles_x = (p.OW + DW_TW - 1) / DW_TW, tiles_y = (p.OH + DW_TH - 1) / DW_TH;
@@ -2312,16 +2331,14 @@ hipError_t launch_dwconv3x3(const dw_params& p_in, hipStream_t s)
     const int IH = (DW_TH - 1) * p.stride + 2 * p.dil + 1, IW = (DW_TW - 1) * p.stride + 2 * p.dil + 1;
     const size_t lds = (size_t)IH * IW * DW_CG * 16 + 72 * 16;
     const int total = tiles_x * tiles_y * cgroups * p.B;
-    const int nld = (IH * IW * DW_CG + 255) / 256;
+    const int nld = dw_halo_loads(p);
     const dim3 grid(std::min(total, 256 * 12));
     if (nld <= 4)
         HP_LAUNCH((dwconv3x3_kernel<4>), grid, dim3(256), lds, s, p, tiles_x, tiles_y, cgroups, total);
     else if (nld <= 5)
         HP_LAUNCH((dwconv3x3_kernel<5>), grid, dim3(256), lds, s, p, tiles_x, tiles_y, cgroups, total);
-    else if (nld <= 10)
-        HP_LAUNCH((dwconv3x3_kernel<10>), grid, dim3(256), lds, s, p, tiles_x, tiles_y, cgroups, total);
-    else
-        return hipErrorInvalidValue;
+    else // (nld <= DW_MAX_NLD: dwconv3x3_ok)
+        HP_LAUNCH((dwconv3x3_kernel<DW_MAX_NLD>), grid, dim3(256), lds, s, p, tiles_x, tiles_y, cgroups, total);
     return hipGetLastError();
 }
 

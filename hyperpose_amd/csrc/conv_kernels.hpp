@@ -111,6 +111,7 @@ struct dw_params {
 };
 // Depthwise 3x3 (VALU, HBM/L2-bound): one thread = one output pixel x 8 channels.
 hipError_t launch_dwconv3x3(const dw_params& p, hipStream_t s);
+bool dwconv3x3_ok(const dw_params& p); // the kernel has a form for this activation / stride / dilation (p.act, p.act_param, p.stride, p.dil)
 
 // Depthwise 3x3 + pointwise 1x1 fused (sepconv_kernel).  `pw` describes the pointwise half exactly like a 1x1
 // conv_params (Cin = C, bias, activation, out, OH/OW/npix) except that pw.w holds the weights in MFMA-fragment order:

@@ -389,6 +389,9 @@ int hp_engine::validate_and_infer(const hp_engine_desc* d)
         }
         if (L.op != HP_OP_CONV)
             HP_REQUIRE(L.cin == L.cout, HP_ERR_INVALID, "layer %zu: depthwise/pool need cin == cout", i);
+        // (only the dense convolutions' epilogues add a residual: on a depthwise / pooling layer it would be dropped without a word)
+        if (L.op != HP_OP_CONV)
+            HP_REQUIRE(L.res < 0, HP_ERR_INVALID, "layer %zu: a residual on a depthwise / pooling layer is not supported", i);
         if (L.op != HP_OP_MAXPOOL && L.op != HP_OP_UPSAMPLE && L.in != 0) {
             // halo this consumer needs on its input: SAME padding before / after in both dimensions
             const int pb_y = std::max((g.OH - 1) * L.stride + (L.kh - 1) * L.dil + 1 - ti.H - g.pt, 0);
@@ -590,7 +593,12 @@ int hp_engine::bind_outputs(const hp_engine_desc* d)
         for (size_t i = 0; i < layers.size(); ++i)
             if (layers[i].out == o.tensor && layers[i].out_coff < o.coff + o.channels && layers[i].out_coff + layers[i].cout > o.coff)
                 ++writers, last = (int)i;
-        if (writers == 1 && layers[last].op == HP_OP_CONV && layers[last].in != 0 && layers[last].out_coff == o.coff
+        // (a convolution carries ONE fp32 pointer: where the same range is exported under several names the first takes it, the others
+        // stay with the conversion kernel - which keeps the fp16 / fp32 tensor alive, tensor_is_read)
+        bool taken = false;
+        for (const auto& o2 : outputs)
+            taken = taken || (&o2 != &o && o2.fused_layer == last && last >= 0);
+        if (writers == 1 && !taken && layers[last].op == HP_OP_CONV && layers[last].in != 0 && layers[last].out_coff == o.coff
             && layers[last].cout == o.channels && o.act == HP_ACT_NONE && o.plain())
             o.fused_layer = last;
     }
@@ -1126,6 +1134,7 @@ int hp_engine::lower16(size_t i)
         p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.stride = L.stride, p.dil = L.dil;
         p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param, p.halo = ti.P;
         p.out = to.view(L.out_coff);
+        HP_REQUIRE(hp::dwconv3x3_ok(p), HP_ERR_INVALID, "layer %zu: no depthwise kernel for activation %d at stride %d, dilation %d", i, L.act, L.stride, L.dil);
         st.flops = 2.0 * opix * L.cin * 9;
         st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cin * 2;
     } else if (L.op == HP_OP_UPSAMPLE) {

@@ -306,7 +306,9 @@ enum { HP_ACT_NONE = 0, HP_ACT_RELU = 1, HP_ACT_RELU6 = 2, HP_ACT_LEAKY = 3, HP_
 typedef struct hp_layer {
     int32_t op;              /* HP_OP_* */
     int32_t in, in_coff;     /* tensor read (0 = network input) and its first channel */
-    int32_t res;             /* residual tensor added in the epilogue, or -1 */
+    int32_t res;             /* residual tensor (its channels [0, cout)) added in the epilogue, or -1.  HP_OP_CONV only: hp_engine_create refuses a
+                              * residual on a depthwise / pooling / up-sampling layer (HP_ERR_INVALID) - their kernels have no such epilogue.  It also
+                              * refuses a depthwise layer no kernel serves: PReLU / sigmoid / softplus, or (fp16 / int8 engines) stride 2 with dilation 2 */
     int32_t res_before_act;  /* 1: act(conv + res) (ResNet); 0: act(conv) + res (LW-OpenPose blocks) */
     int32_t out, out_coff;   /* tensor written and its first channel (concat by offset) */
     int32_t cin, cout;

@@ -38,6 +38,19 @@ def test_ref_net_matches_direct_torch_on_lw_openpose():
     assert out["conf"].std() > 0
 
 
+def test_signed_pool_cases_have_negative_borders():
+    """The inputs of test_engine_gpu.py::test_max_pool_on_signed_input: every border of every pooled map is negative in many channels, and a
+    pool that padded with zero instead of -inf would differ from the oracle far beyond the GPU test's tolerance."""
+    import test_engine_gpu as G
+    for h, w in ((11, 9), (12, 8), (1, 5)):
+        net, outs, fr = G.signed_pool_case(h, w)
+        ref, tens = ref_net.run(net.layers, outs, net.blob(), frames_u8=fr, match_fp16=True, return_tensors=True)
+        G.assert_negative_borders(ref)
+        a = torch.from_numpy(tens[1])
+        zero_padded = F.max_pool2d(F.pad(a, (1, 1, 1, 1)), 3, 1).numpy()   # what a zero halo would give for the 3x3 stride-1 pool
+        assert np.abs(zero_padded - ref["p1"]).max() > 0.05 * np.abs(ref["p1"]).max()
+
+
 def test_lw_openpose_flops_match_survey():
     # SURVEY.md Appendix C: MobilenetDilated + LW head @368x432 = 23.39 GFLOP/frame (11.593 dense + 0.100 dw GMAC)
     m = E.Model("lw_openpose_mobilenet", 432, 368)

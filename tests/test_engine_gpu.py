@@ -217,6 +217,36 @@ def test_depthwise_pool_residual_concat_prelu(hp):
     _check(got, ref, 2)
 
 
+def signed_pool_case(h, w):
+    """Max pools 2x2 / 2, 3x3 / 2 (into a concat offset) and 3x3 / 1 on a LEAKY(0.5) convolution's output: whole channels are negative."""
+    net = Net(21)
+    a = net.conv(0, 3, 32, 3, 1, act=E.ACT_LEAKY, act_param=0.5)
+    p2 = net.conv(a, 32, 32, 2, 2, op=E.OP_MAXPOOL, act=E.ACT_NONE)
+    cat = net.new_tensor()
+    net.conv(p2, 32, 8, 1, act=E.ACT_NONE, out=cat, out_coff=0)
+    net.conv(a, 32, 32, 3, 2, op=E.OP_MAXPOOL, act=E.ACT_NONE, out=cat, out_coff=8)
+    p1 = net.conv(a, 32, 32, 3, 1, op=E.OP_MAXPOOL, act=E.ACT_NONE)
+    return net, [Out("p2", p2, 0, 32), Out("cat", cat, 0, 40), Out("p3", cat, 8, 32), Out("p1", p1, 0, 32)], _frames(2, h, w, seed=h * w)
+
+
+def assert_negative_borders(ref):
+    """A border window whose real values are all negative is where padding with the tensor's zero halo instead of -inf would win."""
+    for nm in ("p2", "p3", "p1"):
+        r = ref[nm]
+        for edge in (r[:, :, 0, :], r[:, :, -1, :], r[:, :, :, 0], r[:, :, :, -1]):
+            assert (edge < 0).mean() > 0.1, (nm, float((edge < 0).mean()))
+
+
+@pytest.mark.parametrize("h,w", [(11, 9), (12, 8), (1, 5)])
+def test_max_pool_on_signed_input(hp, h, w):
+    """maxpool_kernel pads with -inf (as the oracle does), not with the zero halo its input tensor has in HBM: odd maps (SAME pads before and
+    after), even maps (after only) and a one-row map, every output border negative in many channels."""
+    net, outs, fr = signed_pool_case(h, w)
+    _, got, ref = _run_both(net, outs, fr, h, w)
+    assert_negative_borders(ref)
+    _check(got, ref, 2)
+
+
 @pytest.mark.parametrize("kind,scale,c,h,w", [(0, 2, 32, 11, 9), (1, 2, 32, 11, 9), (1, 3, 16, 7, 10), (0, 4, 8, 5, 6), (1, 2, 72, 23, 27)])
 def test_upsample(hp, kind, scale, c, h, w):
     """HP_OP_UPSAMPLE (nearest / bilinear with half-pixel centres) vs torch.nn.functional.interpolate, also into a channel offset."""

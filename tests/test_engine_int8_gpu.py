@@ -168,6 +168,68 @@ def test_int8_layer_matches_the_quantization_contract(hp, case):
     assert tiles[li] == (8900000 + k if direct else tiles[li]) and 8000000 <= tiles[li] < 9000000, tiles[li]   # conv_i8_direct / conv_i8_kernel
 
 
+# Signed, tying, saturating inputs.  The cases above quantize relu outputs with a calibrated scale: q_x is never negative, x / s_a never
+# lands on a .5 and never passes 127.  Here the layer in front has no activation and the scale is set by hand to a power of two below the
+# calibrated one, 2^floor(log2(max|x| / 127)): x / s_a is then exact in fp32 (no rounding before the rint), a few per cent of the fp16 inputs sit
+# exactly between two integers (half of them above an even one: half-up, half-away and half-even all differ) and about 1 % lie beyond each
+# end of [-127, 127] - the sign handling, the round-half-even and the clamp of quant1, in the generic kernel's loader and in the direct
+# kernel's halo loader, at the bit level.  (cin, cout, k, stride): two shapes of conv_i8_kernel, two of conv_i8_direct_kernel.
+SIGNED_CASES = [dict(cin=64, cout=128, k=1), dict(cin=64, cout=64, k=3, stride=2), dict(cin=128, cout=128, k=3), dict(cin=128, cout=128, k=7)]
+SIGNED_H, SIGNED_W, SIGNED_N = 23, 29, 3
+
+
+def signed_case(case):
+    """The graph (first layer without activation -> the layer under test -> a reader), its frames and its calibration frames."""
+    net = Net(case["cin"] * 7 + 128 + 3)
+    t0 = net.conv(0, 3, case["cin"], 3, 1, act=E.ACT_NONE)
+    t = net.conv(t0, case["cin"], case["cout"], case["k"], case.get("stride", 1))
+    z = net.conv(t, case["cout"], 8, 1)
+    return net, t0, t, z, _frames(SIGNED_N, SIGNED_H, SIGNED_W, seed=131), _frames(4, SIGNED_H, SIGNED_W, seed=99)
+
+
+def dyadic_scale(s_calibrated):
+    """The largest power of two <= the calibrated scale max|x| / 127."""
+    return np.float32(2.0 ** np.floor(np.log2(float(s_calibrated))))
+
+
+def assert_input_shares(x, s_a):
+    """Conditions on the INPUT of the layer under test (x = the stored fp16 values, s_a a power of two), not on the kernel: enough negative
+    values, values beyond both clamps and exact ties that a wrong sign, clamp or rounding mode cannot hide below _fp16_gate's 0.1 %."""
+    v = x.astype(np.float32) * (np.float32(1) / np.float32(s_a))
+    assert np.array_equal(v.astype(np.float64), x.astype(np.float64) / float(s_a)), "x / s_a is not exact: s_a is no power of two"
+    tie = np.abs(v - np.floor(v) - 0.5) == 0
+    shares = dict(negative=float((v < 0).mean()), low=float((v <= -127.5).mean()), high=float((v >= 127.5).mean()), ties=float(tie.mean()),
+                  ties_even_floor=float((tie & (np.floor(v) % 2 == 0)).mean()))
+    print("input shares:", {k: round(s, 5) for k, s in shares.items()})
+    assert shares["negative"] >= 0.30 and shares["low"] >= 0.003 and shares["high"] >= 0.003 and shares["ties"] >= 0.01, shares
+    return shares
+
+
+@pytest.mark.parametrize("case", SIGNED_CASES, ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items()))
+def test_int8_layer_on_signed_tying_saturating_inputs(hp, case):
+    cin, cout, k, stride = case["cin"], case["cout"], case["k"], case.get("stride", 1)
+    net, t0, t, z, fr, calib = signed_case(case)
+    n, blob, li = SIGNED_N, net.blob(), 1
+    L = net.layers[li]
+    eng = E.Engine(net.layers, [Out("y", t, 0, cout).c(), Out("z", z, 0, 8).c()], blob, SIGNED_W, SIGNED_H, n, dtype="i8")
+    eng.calibrate(calib)
+    s = eng.int8_scales
+    assert s[0] == 0 and s[li] > 0
+    s[li] = dyadic_scale(s[li])
+    eng.int8_scales = s
+    assert eng.int8_scales[li] == s[li]
+    got = eng.inference(fr)
+    x = eng.debug_tensor(t0, n)
+    assert_input_shares(x, s[li])
+    v = _emulate(L, x, blob, s[li])
+    _fp16_gate(eng.debug_tensor(t, n), v.astype(np.float16))
+    y = np.stack([dict(g)["y"] for g in got])
+    scale = float(np.abs(v).max()) + 1e-6
+    assert np.abs(y - v).max() <= 2e-6 * scale + 1e-6, "fused fp32 output copy vs the unrounded emulation"
+    tiles = {q["layer"]: q["tile"] for q in eng.profile(n, 1)}
+    assert tiles[li] == (8900000 + k if (k in (3, 7) and stride == 1 and cout > 64) else tiles[li]) and 8000000 <= tiles[li] < 9000000, tiles[li]
+
+
 def test_uncovered_geometry_stays_fp16(hp):
     """A 1 x 1 stride-3 layer has no int8 kernel: scale 0 after calibration, a scale > 0 for it is refused."""
     net = Net(3)
