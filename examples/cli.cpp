@@ -12,6 +12,9 @@
 //     `--yuv_matrix=bt601|bt709|bt2020` and `--yuv_range=limited|full` (defaults bt601, limited); `--yuv` converts any other source to
 //     NV12 first.  Either way the operator runtime hands the engine hyperpose::yuv_frame batches (colour conversion fused into the resize
 //     on the GPU); the BGR pictures, converted on the host with the same table (hp_yuv_coefficients), are only drawn on.
+//   * tiled inference (addition): `--tiles=<columns>x<rows> [--tile_overlap=<px>] [--tile_full]`: every frame - BGR or --yuv / .yuv, with or
+//     without --saving_yuv - is inferred on overlapping tiles (one engine call per frame, engine.inference(frame, regions)) and the humans
+//     are merged in the frame's coordinates (hp::plan_tiles / to_frame / merge_humans; stream runtime: stream.set_tiling);
 //   * writing video back (addition): `--saving_yuv=<file>`, for a .yuv source or `--yuv`: every frame is uploaded in its own format, inference
 //     runs on it as a device-resident frame, the skeletons are drawn on the device surface (hp::draw_humans, opacity = alpha; alpha == 0 -> 1)
 //     and the annotated frames are appended to <file> as raw frames of the same format; <file>.humans receives, per frame, an int32 count and
@@ -58,6 +61,11 @@ static bool FLAGS_int8 = false; // addition: data_type::kINT8 engines, calibrate
 static bool FLAGS_yuv = false;  // addition: feed the engine video frames (dnn::tensorrt::inference(std::vector<yuv_frame>)); implied by a .yuv source
 static int FLAGS_yuv_w = 0, FLAGS_yuv_h = 0; // frame size of a raw .yuv source
 static std::string FLAGS_yuv_format = "i420", FLAGS_yuv_matrix = "bt601", FLAGS_yuv_range = "limited"; // layout and colours of a raw .yuv source
+static std::string FLAGS_tiles;      // addition: --tiles CxR: inference on C x R overlapping tiles of every frame, the humans merged (hp::tiling)
+static int FLAGS_tile_overlap = 64;  // ... pixels neighbouring tiles share at least
+static bool FLAGS_tile_full = false; // ... plus the whole frame as one more region
+static bool g_tiled = false;
+static hp::tiling g_tiling;
 static std::string FLAGS_saving_yuv; // addition: append the frames, annotated on the device in their own format, to this file
 static int FLAGS_synthetic_humans = 0; // addition: stand-in humans added to every frame's poses (see the head of the file)
 static bool g_yuv_from_file = false; // the frames came from a .yuv source (else --yuv made NV12 ones)
@@ -69,11 +77,11 @@ static std::ostream& cli_log() { return std::cout << "[HyperPose::CLI] "; }
 static bool parse_flags(int argc, char** argv)
 {
     std::map<std::string, std::string*> sflags = { { "model", &FLAGS_model }, { "post", &FLAGS_post }, { "source", &FLAGS_source },
-        { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix }, { "saving_yuv", &FLAGS_saving_yuv }, { "yuv_format", &FLAGS_yuv_format },
+        { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix }, { "saving_yuv", &FLAGS_saving_yuv }, { "tiles", &FLAGS_tiles }, { "yuv_format", &FLAGS_yuv_format },
         { "yuv_matrix", &FLAGS_yuv_matrix }, { "yuv_range", &FLAGS_yuv_range } };
-    std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size },
+    std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size }, { "tile_overlap", &FLAGS_tile_overlap },
         { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h }, { "synthetic_humans", &FLAGS_synthetic_humans } };
-    std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 }, { "yuv", &FLAGS_yuv } };
+    std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 }, { "yuv", &FLAGS_yuv }, { "tile_full", &FLAGS_tile_full } };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a.rfind("--", 0) != 0 && a.rfind("-", 0) == 0)
@@ -112,6 +120,21 @@ static bool parse_flags(int argc, char** argv)
             cli_log() << "ERROR: unknown command line flag '" << name << "'\n";
             return false;
         }
+    }
+    if (!FLAGS_tiles.empty()) { // --tiles CxR, both counts >= 1
+        int c = 0, r = 0;
+        char x = 0, rest = 0;
+        if (std::sscanf(FLAGS_tiles.c_str(), "%d%c%d%c", &c, &x, &r, &rest) != 3 || (x != 'x' && x != 'X') || c < 1 || r < 1 || c * r + (FLAGS_tile_full ? 1 : 0) > 64
+            || FLAGS_tile_overlap < 0) {
+            cli_log() << "ERROR: --tiles=" << FLAGS_tiles << " --tile_overlap=" << FLAGS_tile_overlap
+                      << ": expected --tiles=<columns>x<rows> with both counts >= 1, at most 64 regions, and an overlap >= 0\n";
+            return false;
+        }
+        g_tiled = true;
+        g_tiling.cols = c, g_tiling.rows = r, g_tiling.overlap_x = g_tiling.overlap_y = FLAGS_tile_overlap, g_tiling.with_full = FLAGS_tile_full;
+    } else if (FLAGS_tile_full) {
+        cli_log() << "ERROR: --tile_full adds the whole frame to the tiles of --tiles=<columns>x<rows>\n";
+        return false;
     }
     // the three enumerated flags: a value outside the list is refused with the list
     auto pick = [](const char* flag, const std::string& value, const std::vector<std::pair<const char*, int>>& names, int& out) {
@@ -418,6 +441,11 @@ int main(int argc, char** argv)
         cli_log() << "ERROR: --saving_yuv writes video frames: it needs a .yuv source or --yuv\n";
         return 1;
     }
+    if (g_tiled && g_tiling.regions() > FLAGS_max_batch_size) {
+        cli_log() << "ERROR: --tiles=" << FLAGS_tiles << (FLAGS_tile_full ? " --tile_full" : "") << " makes " << g_tiling.regions()
+                  << " regions per frame, more than --max_batch_size=" << FLAGS_max_batch_size << "\n";
+        return 1;
+    }
     if (FLAGS_synthetic_humans > 0)
         cli_log() << "WARNING: --synthetic_humans=" << FLAGS_synthetic_humans << ": " << FLAGS_synthetic_humans
                   << " made-up humans are added to every frame's poses; the pictures and the human count below are NOT the model's result\n";
@@ -496,6 +524,22 @@ int main(int argc, char** argv)
         n_written += write_ppm(FLAGS_saving_prefix + "_" + std::to_string(n_written) + ".ppm", img);
     };
 
+    // --tiles: one frame's regions in one engine call, every region parsed on its own, the poses brought back to the frame and merged
+    auto tiled_poses = [&](const cv::Mat& frame, const hp::yuv_frame* yuv) {
+        const std::vector<cv::Rect> regions = hp::plan_tiles(frame.size(), g_tiling, yuv ? yuv->format : -1);
+        const auto maps = yuv ? engine.inference(*yuv, regions) : engine.inference(frame, regions);
+        std::vector<hp::human_t> all;
+        std::vector<int> region_of;
+        for (size_t r = 0; r < regions.size(); ++r)
+            for (auto pose : std::visit([&](auto& op) { return op.process(maps[r]); }, parser)) {
+                if (FLAGS_keep_ratio)
+                    hp::resume_ratio(pose, cv::Size(regions[r].width, regions[r].height), engine.input_size());
+                hp::to_frame(pose, regions[r], frame.size());
+                all.push_back(pose), region_of.push_back((int)r);
+            }
+        return regions.size() == 1 ? all : hp::merge_humans(all, region_of, frame.size(), g_tiling.min_common, g_tiling.tol);
+    };
+
     auto beg = clk_t::now();
     if (FLAGS_runtime == kOPERATOR) {
         // operator API: one batch at a time - engine.inference(batch) -> one internal_t per frame -> parser.process(internal_t)
@@ -518,13 +562,13 @@ int main(int argc, char** argv)
                     }
                     yuv_batch.push_back(hp::yuv_frame::packed(b.format, surfaces.back()->p, b.w, b.h, b.matrix, b.range, true));
                 }
-            const auto maps = FLAGS_yuv ? engine.inference(yuv_batch) : engine.inference(batch);
+            const auto maps = g_tiled ? std::vector<hp::internal_t>{} : FLAGS_yuv ? engine.inference(yuv_batch) : engine.inference(batch);
             for (size_t k = 0; k < batch.size(); ++k) {
-                auto poses = std::visit([&](auto& op) { return op.process(maps[k]); }, parser);
+                auto poses = g_tiled ? tiled_poses(batch[k], FLAGS_yuv ? &yuv_batch[k] : nullptr) : std::visit([&](auto& op) { return op.process(maps[k]); }, parser);
                 add_synthetic_humans(poses, first + k, FLAGS_synthetic_humans);
                 if (yuv_out.is_open()) { // annotate the surface where it lies, in its own format, and append it to the file
                     std::vector<hp::human_t> drawn = poses;
-                    if (FLAGS_keep_ratio)
+                    if (FLAGS_keep_ratio && !g_tiled) // (tiled poses are in the frame's coordinates already)
                         for (auto& pose : drawn)
                             hp::resume_ratio(pose, batch[k].size(), engine.input_size());
                     hp::draw_humans(yuv_batch[k], drawn, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
@@ -539,7 +583,7 @@ int main(int argc, char** argv)
                     humans_out.write((const char*)&count, sizeof(count));
                     humans_out.write((const char*)records.data(), records.size() * sizeof(hp_human));
                 }
-                render(batch[k], poses, FLAGS_keep_ratio);
+                render(batch[k], poses, FLAGS_keep_ratio && !g_tiled);
             }
         }
     } else {
@@ -547,6 +591,8 @@ int main(int argc, char** argv)
         std::visit(
             [&](auto& op) {
                 auto stream = hp::make_stream(engine, op, true, FLAGS_keep_ratio);
+                if (g_tiled)
+                    stream.set_tiling(g_tiling);
                 stream.async() << images;
                 auto sink = [&](size_t, const cv::Mat& frame, const std::vector<hp::human_t>& poses) {
                     cv::Mat img = clone(frame);

@@ -62,6 +62,20 @@ class OverlayPrim(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("kind", "x0", "y0", "x1", "y1", "t", "colour", "human")]
 
 
+class Roi(C.Structure):
+    """hp_roi: a region of a frame in source pixels"""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class Tiling(C.Structure):
+    """hp_tiling"""
+    _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("overlap_x", C.c_int32), ("overlap_y", C.c_int32), ("with_full", C.c_int32),
+                ("min_common", C.c_int32), ("tol", C.c_double)]
+
+
+# the mirrors' merge defaults (HP_TILING_DEFAULT_* in include/hp_hip.h)
+TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL = 3, 0.08
+
 PART_DTYPE = np.dtype([("has_value", "<i4"), ("x", "<f4"), ("y", "<f4"), ("score", "<f4")])
 HUMAN_DTYPE = np.dtype({"names": ["parts", "score"], "formats": [(PART_DTYPE, 18), "<f4"]})
 PEAK_DTYPE = np.dtype([("part_id", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4"), ("id", "<i4")])
@@ -89,6 +103,7 @@ SYMBOLS = [
     "hp_model_input_size",
     "hp_model_destroy", "hp_model_archs", "hp_model_layers", "hp_model_outputs", "hp_model_num_weights",
     "hp_model_preproc", "hp_model_flops_per_frame", "hp_model_init_weights", "hp_engine_create_from_model", "hp_engine_create_from_model_dtype", "hp_engine_dtype", "hp_engine_calibrate_u8", "hp_engine_int8_scales", "hp_engine_set_int8_scales", "hp_engine_split_fallbacks", "hp_engine_device_bytes", "hp_engine_save", "hp_engine_load", "hp_pipeline_create", "hp_pipeline_create_ex", "hp_pipeline_destroy", "hp_pipeline_submit", "hp_pipeline_collect", "hp_pipeline_in_flight",
+    "hp_resize_rois_u8c3", "hp_resize_rois_yuv", "hp_yuv_roi_alignment", "hp_tile_plan", "hp_humans_to_frame", "hp_humans_merge", "hp_pipeline_set_tiling",
 ]
 
 
@@ -103,6 +118,7 @@ def lib() -> C.CDLL:
         L.hp_last_error.restype = C.c_char_p
         L.hp_version.restype = C.c_char_p
         L.hp_yuv_packed_bytes.restype = C.c_size_t
+        L.hp_humans_to_frame.restype = None
         _lib = L
     return _lib
 

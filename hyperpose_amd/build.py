@@ -29,6 +29,10 @@ UNITS = [
     # -fno-slp-vectorize, as for conv_fp32.hip below: the coefficient derivation is fp32 and runs next to the engines' kernels
     ("resize_yuv.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("resize_yuv_formats.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # many regions of one frame per launch: resize_device.hpp's arithmetic again, so the same flags as the per-frame units
+    ("resize_rois.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # planner / map-back / merge of tiled inference: host doubles that tests/tiles_ref.py restates bit for bit
+    ("tiles.cpp", ["-ffp-contract=off"]),
     # the primitive list is fp32 with no fused operations (csrc/overlay.hpp); the kernels are integer
     ("overlay.hip", ["-ffp-contract=off"]),
     ("paf_parser.hip", ["-ffp-contract=off"]),

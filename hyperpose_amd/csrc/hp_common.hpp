@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/hp_hip.h"
 
@@ -98,6 +99,9 @@ struct host_buf {
 };
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// tiles.cpp: hp_humans_merge without its capacity rule - the kept humans in kept order (hp_pipeline_collect in tiled mode)
+int merge_humans(const hp_human* in, const int32_t* region_of, int n, int frame_w, int frame_h, int min_common, double tol, std::vector<hp_human>& kept);
 
 // The engine's environment switches ("Engine switches"), read once by read_engine_switches() when hp_engine_create or
 // hp_engine_load makes an engine: its schedule, its launches and the graphs it captures follow the environment of that moment.  Host-only:

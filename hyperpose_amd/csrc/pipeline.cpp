@@ -8,6 +8,9 @@
 // Frames arrive as 8-bit BGR (hp_pipeline_submit) or as YUV 4:2:0 video frames (hp_pipeline_submit_yuv: half the bytes over PCIe, colour
 // conversion fused into the resize, resize_yuv.hip) or as hp_yuv_image descriptions of any layout, in host or in device memory
 // (hp_pipeline_submit_yuv_images, resize_yuv_formats.hip); all end in infer_and_parse().
+// Tiled mode (hp_pipeline_set_tiling): a frame becomes its R regions in R consecutive slots of the batch - one hp_resize_rois_* call per
+// frame (resize_rois.hip) instead of the per-frame resize - and hp_pipeline_collect maps every region's humans back to the frame and
+// merges them (tiles.cpp).  The BGR and the hp_yuv_image submit have a tiled twin below; with tiling off nothing of this runs.
 #include "hp_common.hpp"
 #include "yuv_formats.hpp"
 
@@ -27,6 +30,8 @@ struct pipe_t {
     hp::dev_buf raw, net;   // frames as submitted; frames at network size [max_batch][in_h][in_w][3]
     int n = 0;              // frames in flight (0 = free)
     std::vector<int> w, h;
+    int regions = 0;        // tiled batch: regions per frame (0 = an untiled batch), p.n / regions frames
+    std::vector<hp_roi> roi; // tiled batch: the region of every slot
 };
 
 // pinned memory (hp_malloc_host / hipHostMalloc) is copied straight from where it lies; anything else through staging
@@ -46,6 +51,11 @@ struct hp_pipeline {
     size_t max_frame_bytes = 0;
     std::vector<pipe_t> pipes;
     int head = 0, tail = 0, inflight = 0; // ring over the pipes
+    bool tiled = false;
+    hp_tiling tiling{};
+    std::vector<hp_human> slot_humans, cand, kept; // tiled collect: the parser's per-slot lists, one frame's candidates, its merged humans
+    std::vector<int> slot_n;
+    std::vector<int32_t> cand_region;
 
     ~hp_pipeline()
     {
@@ -66,6 +76,10 @@ struct hp_pipeline {
 
 namespace {
 int infer_and_parse(hp_pipeline* pl, pipe_t& p, int n);
+int submit_tiled(hp_pipeline* pl, const uint8_t* const* frames, const int* widths, const int* heights, int n);
+int submit_tiled_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, int n, int on_device);
+int collect_tiled(hp_pipeline* pl, pipe_t& p, hp_human* out, int cap_per_frame, int* n_out, int* n_frames);
+int upload_yuv_images(hp_pipeline* pl, pipe_t& p, const hp_yuv_image* frames, int n, std::vector<hp_yuv_image>& dev);
 }
 
 extern "C" {
@@ -117,6 +131,7 @@ int hp_pipeline_create_ex(hp_pipeline** out, const hp_engine_desc* desc, const h
         HP_TRY(p.raw.alloc((pl->max_frame_bytes + 256) * desc->max_batch));
         HP_TRY(p.net.alloc(net_frame * desc->max_batch));
         p.w.assign(desc->max_batch, 0), p.h.assign(desc->max_batch, 0);
+        p.roi.assign(desc->max_batch, hp_roi{ 0, 0, 0, 0 });
     }
     // the feature maps the parsers read, by the reference's convention: outputs sorted by name (src/tensorrt.cpp:405) = the parsers'
     // argument order: PAF (conf, paf), src/paf.cpp:300; PifPaf (paf, pif), src/pifpaf.cpp:7; PoseProposal 7 tensors, src/pose_proposal.cpp:12-20
@@ -131,9 +146,29 @@ void hp_pipeline_destroy(hp_pipeline* pl) { delete pl; }
 
 int hp_pipeline_in_flight(const hp_pipeline* pl) { return pl ? pl->inflight : 0; }
 
+int hp_pipeline_set_tiling(hp_pipeline* pl, const hp_tiling* t)
+{
+    HP_REQUIRE(pl, HP_ERR_INVALID, "hp_pipeline_set_tiling: null pipeline");
+    HP_REQUIRE(pl->inflight == 0, HP_ERR_STATE, "hp_pipeline_set_tiling: %d batches are in flight, collect first", pl->inflight);
+    if (!t) {
+        pl->tiled = false;
+        return HP_OK;
+    }
+    hp_roi probe[64]; // the plan of a frame of the network's size: every rule that does not depend on the frame is checked now
+    const int R = hp_tile_plan(t, pl->in_w, pl->in_h, 1, 1, probe, 64);
+    if (R < 0)
+        return R;
+    HP_REQUIRE(R <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_set_tiling: %d regions per frame > max_batch %d", R, pl->max_batch);
+    HP_REQUIRE(t->min_common >= 1 && t->tol >= 0., HP_ERR_INVALID, "hp_pipeline_set_tiling: min_common %d (>= 1), tol %g (>= 0)", t->min_common, t->tol);
+    pl->tiling = *t, pl->tiled = true;
+    return HP_OK;
+}
+
 int hp_pipeline_submit(hp_pipeline* pl, const uint8_t* const* frames, const int* widths, const int* heights, int n)
 {
     HP_REQUIRE(pl && frames && widths && heights, HP_ERR_INVALID, "hp_pipeline_submit: null argument");
+    if (pl->tiled)
+        return submit_tiled(pl, frames, widths, heights, n);
     HP_REQUIRE(n >= 1 && n <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_submit: batch %d > max_batch %d", n, pl->max_batch);
     HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "hp_pipeline_submit: all %d pipes are busy, collect first", pl->n_pipes);
     pipe_t& p = pl->pipes[pl->head];
@@ -188,6 +223,7 @@ int hp_pipeline_submit(hp_pipeline* pl, const uint8_t* const* frames, const int*
 int hp_pipeline_submit_yuv(hp_pipeline* pl, int format, const uint8_t* const* frames, const int* widths, const int* heights, int n)
 {
     HP_REQUIRE(pl && frames && widths && heights, HP_ERR_INVALID, "hp_pipeline_submit_yuv: null argument");
+    HP_REQUIRE(!pl->tiled, HP_ERR_STATE, "hp_pipeline_submit_yuv: not available in tiled mode, submit hp_yuv_image frames with hp_pipeline_submit_yuv_images");
     HP_REQUIRE(format == HP_YUV_NV12 || format == HP_YUV_I420, HP_ERR_INVALID, "hp_pipeline_submit_yuv: unknown format %d", format);
     HP_REQUIRE(n >= 1 && n <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_submit_yuv: batch %d > max_batch %d", n, pl->max_batch);
     HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "hp_pipeline_submit_yuv: all %d pipes are busy, collect first", pl->n_pipes);
@@ -234,6 +270,8 @@ int hp_pipeline_submit_yuv(hp_pipeline* pl, int format, const uint8_t* const* fr
 int hp_pipeline_submit_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, int n, int on_device)
 {
     HP_REQUIRE(pl && frames, HP_ERR_INVALID, "hp_pipeline_submit_yuv_images: null argument");
+    if (pl->tiled)
+        return submit_tiled_yuv_images(pl, frames, n, on_device);
     HP_REQUIRE(n >= 1 && n <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_submit_yuv_images: batch %d > max_batch %d", n, pl->max_batch);
     HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "hp_pipeline_submit_yuv_images: all %d pipes are busy, collect first", pl->n_pipes);
     pipe_t& p = pl->pipes[pl->head];
@@ -244,36 +282,11 @@ int hp_pipeline_submit_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, i
             "hp_pipeline_submit_yuv_images: frame %d (%s, %dx%d, %zu bytes) exceeds max_frame_bytes %zu", i, hp_yuv::layout_of(frames[i].format)->name,
             frames[i].width, frames[i].height, hp_yuv_packed_bytes(frames[i].format, frames[i].width, frames[i].height), pl->max_frame_bytes);
     }
-    // host frames: all copies first, then all kernels (see hp_pipeline_submit_yuv).  `dev` describes each frame as the kernel will read it:
-    // the caller's surface for a device frame, the tightly packed copy in p.raw for a host frame
-    std::vector<hp_yuv_image> dev(frames, frames + n);
-    size_t off = 0;
-    for (int i = 0; i < n && !on_device; ++i) {
-        const hp_yuv_image& f = frames[i];
-        const hp_yuv::layout& l = *hp_yuv::layout_of(f.format);
-        const size_t bytes = hp_yuv_packed_bytes(f.format, f.width, f.height);
-        // one contiguous, tightly packed buffer (what hp_pipeline_submit_yuv takes) in pinned memory goes up from where it lies
-        bool tight = true;
-        size_t at = 0;
-        for (int k = 0; k < l.planes; ++k) {
-            const size_t row = hp_yuv::row_bytes(l, k, f.width);
-            tight = tight && (size_t)f.stride[k] == row && (const uint8_t*)f.plane[k] == (const uint8_t*)f.plane[0] + at;
-            dev[i].plane[k] = p.raw.as<uint8_t>() + off + at, dev[i].stride[k] = (int32_t)row;
-            at += row * hp_yuv::rows(l, k, f.height);
-        }
-        const uint8_t* src = (const uint8_t*)f.plane[0];
-        if (!tight || !is_pinned(src)) {
-            uint8_t* to = p.stage.as<uint8_t>() + off;
-            src = to;
-            for (int k = 0; k < l.planes; ++k) {
-                const size_t row = hp_yuv::row_bytes(l, k, f.width);
-                for (int r = 0; r < hp_yuv::rows(l, k, f.height); ++r, to += row)
-                    memcpy(to, (const uint8_t*)f.plane[k] + (size_t)r * f.stride[k], row);
-            }
-        }
-        HP_HIP_TRY(hipMemcpyAsync(p.raw.as<uint8_t>() + off, src, bytes, hipMemcpyHostToDevice, p.s));
-        off += (bytes + 255) & ~(size_t)255;
-    }
+    std::vector<hp_yuv_image> dev;
+    if (on_device)
+        dev.assign(frames, frames + n);
+    else
+        HP_TRY(upload_yuv_images(pl, p, frames, n, dev));
     for (int i = 0; i < n; ++i) {
         uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * net_frame;
         p.w[i] = frames[i].width, p.h[i] = frames[i].height;
@@ -321,10 +334,175 @@ int infer_and_parse(hp_pipeline* pl, pipe_t& p, int n)
         HP_TRY(hp_engine_output(p.eng, 1, &name, b, &dpif));
         HP_TRY(hp_pifpaf_enqueue(p.pifpaf, n, dpaf, dpif, b[1], b[2], p.s));
     }
-    p.n = n;
+    p.n = n, p.regions = 0; // (a tiled submit sets p.regions after this returns)
     pl->head = (pl->head + 1) % pl->n_pipes;
     ++pl->inflight;
     return HP_OK;
+}
+
+// host frames of hp_pipeline_submit_yuv_images: every frame's planes tightly packed into p.raw (one copy per frame, enqueued on p.s);
+// `dev` describes each frame as a kernel will read it there
+int upload_yuv_images(hp_pipeline* pl, pipe_t& p, const hp_yuv_image* frames, int n, std::vector<hp_yuv_image>& dev)
+{
+    // host frames: all copies first, then all kernels (see hp_pipeline_submit_yuv).  `dev` describes each frame as the kernel will read it:
+    // the caller's surface for a device frame, the tightly packed copy in p.raw for a host frame
+    dev.assign(frames, frames + n);
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        const hp_yuv_image& f = frames[i];
+        const hp_yuv::layout& l = *hp_yuv::layout_of(f.format);
+        const size_t bytes = hp_yuv_packed_bytes(f.format, f.width, f.height);
+        // one contiguous, tightly packed buffer (what hp_pipeline_submit_yuv takes) in pinned memory goes up from where it lies
+        bool tight = true;
+        size_t at = 0;
+        for (int k = 0; k < l.planes; ++k) {
+            const size_t row = hp_yuv::row_bytes(l, k, f.width);
+            tight = tight && (size_t)f.stride[k] == row && (const uint8_t*)f.plane[k] == (const uint8_t*)f.plane[0] + at;
+            dev[i].plane[k] = p.raw.as<uint8_t>() + off + at, dev[i].stride[k] = (int32_t)row;
+            at += row * hp_yuv::rows(l, k, f.height);
+        }
+        const uint8_t* src = (const uint8_t*)f.plane[0];
+        if (!tight || !is_pinned(src)) {
+            uint8_t* to = p.stage.as<uint8_t>() + off;
+            src = to;
+            for (int k = 0; k < l.planes; ++k) {
+                const size_t row = hp_yuv::row_bytes(l, k, f.width);
+                for (int r = 0; r < hp_yuv::rows(l, k, f.height); ++r, to += row)
+                    memcpy(to, (const uint8_t*)f.plane[k] + (size_t)r * f.stride[k], row);
+            }
+        }
+        HP_HIP_TRY(hipMemcpyAsync(p.raw.as<uint8_t>() + off, src, bytes, hipMemcpyHostToDevice, p.s));
+        off += (bytes + 255) & ~(size_t)255;
+    }
+    return HP_OK;
+}
+
+int tiled_regions(const hp_pipeline* pl) { return pl->tiling.cols * pl->tiling.rows + pl->tiling.with_full; }
+
+// what every tiled submit checks first: n frames of R regions fit a batch, and a pipe is free
+int tiled_admit(hp_pipeline* pl, const char* who, int n)
+{
+    const int R = tiled_regions(pl);
+    HP_REQUIRE(n >= 1 && n <= pl->max_batch / R, HP_ERR_CAPACITY, "%s: %d frames of %d regions each > max_batch %d (at most %d frames per submit)", who, n, R,
+        pl->max_batch, pl->max_batch / R);
+    HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "%s: all %d pipes are busy, collect first", who, pl->n_pipes);
+    return HP_OK;
+}
+
+int submit_tiled(hp_pipeline* pl, const uint8_t* const* frames, const int* widths, const int* heights, int n)
+{
+    HP_TRY(tiled_admit(pl, "hp_pipeline_submit", n));
+    pipe_t& p = pl->pipes[pl->head];
+    const int R = tiled_regions(pl);
+    const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
+    for (int i = 0; i < n; ++i) { // everything is checked before the first copy is enqueued
+        HP_REQUIRE(frames[i] && widths[i] > 0 && heights[i] > 0, HP_ERR_INVALID, "hp_pipeline_submit: frame %d is empty", i);
+        HP_REQUIRE((size_t)widths[i] * heights[i] * 3 <= pl->max_frame_bytes, HP_ERR_CAPACITY, "hp_pipeline_submit: frame %d (%dx%d) exceeds max_frame_bytes %zu", i,
+            widths[i], heights[i], pl->max_frame_bytes);
+        const int rc = hp_tile_plan(&pl->tiling, widths[i], heights[i], 1, 1, &p.roi[(size_t)i * R], R);
+        if (rc < 0)
+            return rc;
+    }
+    size_t off = 0;
+    std::vector<size_t> offs(n);
+    for (int i = 0; i < n; ++i) {
+        const size_t bytes = (size_t)widths[i] * heights[i] * 3;
+        const uint8_t* src = frames[i];
+        if (!is_pinned(frames[i])) {
+            memcpy(p.stage.as<uint8_t>() + off, frames[i], bytes);
+            src = p.stage.as<uint8_t>() + off;
+        }
+        HP_HIP_TRY(hipMemcpyAsync(p.raw.as<uint8_t>() + off, src, bytes, hipMemcpyHostToDevice, p.s));
+        offs[i] = off, p.w[i] = widths[i], p.h[i] = heights[i];
+        off += (bytes + 255) & ~(size_t)255;
+    }
+    for (int i = 0; i < n; ++i)
+        HP_TRY(hp_resize_rois_u8c3(p.raw.as<uint8_t>() + offs[i], p.w[i], p.h[i], p.w[i] * 3, &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0,
+            p.net.as<uint8_t>() + (size_t)i * R * net_frame, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s));
+    HP_TRY(infer_and_parse(pl, p, n * R));
+    p.regions = R;
+    return HP_OK;
+}
+
+int submit_tiled_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, int n, int on_device)
+{
+    HP_TRY(tiled_admit(pl, "hp_pipeline_submit_yuv_images", n));
+    pipe_t& p = pl->pipes[pl->head];
+    const int R = tiled_regions(pl);
+    const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
+    for (int i = 0; i < n; ++i) { // everything is checked before the first copy is enqueued
+        HP_TRY(hp_yuv::validate(&frames[i], "hp_pipeline_submit_yuv_images", on_device != 0));
+        HP_REQUIRE(on_device || hp_yuv_packed_bytes(frames[i].format, frames[i].width, frames[i].height) <= pl->max_frame_bytes, HP_ERR_CAPACITY,
+            "hp_pipeline_submit_yuv_images: frame %d (%s, %dx%d, %zu bytes) exceeds max_frame_bytes %zu", i, hp_yuv::layout_of(frames[i].format)->name,
+            frames[i].width, frames[i].height, hp_yuv_packed_bytes(frames[i].format, frames[i].width, frames[i].height), pl->max_frame_bytes);
+        int ax = 1, ay = 1;
+        HP_TRY(hp_yuv_roi_alignment(frames[i].format, &ax, &ay));
+        const int rc = hp_tile_plan(&pl->tiling, frames[i].width, frames[i].height, ax, ay, &p.roi[(size_t)i * R], R);
+        if (rc < 0)
+            return rc;
+    }
+    std::vector<hp_yuv_image> dev;
+    if (on_device)
+        dev.assign(frames, frames + n);
+    else
+        HP_TRY(upload_yuv_images(pl, p, frames, n, dev));
+    for (int i = 0; i < n; ++i) {
+        p.w[i] = frames[i].width, p.h[i] = frames[i].height;
+        HP_TRY(hp_resize_rois_yuv(&dev[i], &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, p.net.as<uint8_t>() + (size_t)i * R * net_frame, pl->in_w,
+            pl->in_h, pl->in_w * 3, net_frame, p.s));
+    }
+    HP_TRY(infer_and_parse(pl, p, n * R));
+    p.regions = R;
+    return HP_OK;
+}
+
+// hp_pipeline_collect of a tiled batch: the parser's lists of all slots, then per frame resume_ratio per region (keep_ratio), the way back
+// to the frame and the merge.  A frame of ONE region has nothing to merge and keeps the parser's order: a 1 x 1 tiling is tiling off.
+int collect_tiled(hp_pipeline* pl, pipe_t& p, hp_human* out, int cap_per_frame, int* n_out, int* n_frames)
+{
+    HP_REQUIRE(cap_per_frame > 0, HP_ERR_INVALID, "hp_pipeline_collect: cap_per_frame %d", cap_per_frame);
+    const int slots = p.n, R = p.regions, frames = slots / R, cap = cap_per_frame;
+    pl->slot_humans.resize((size_t)slots * cap);
+    pl->slot_n.resize(slots);
+    hp_human* sh = pl->slot_humans.data();
+    int rc = pl->kind == HP_PARSER_PAF ? hp_paf_collect(p.paf, sh, cap, pl->slot_n.data())
+        : pl->kind == HP_PARSER_PPN    ? hp_ppn_collect(p.ppn, sh, cap, pl->slot_n.data())
+                                       : hp_pifpaf_collect(p.pifpaf, sh, cap, pl->slot_n.data());
+    p.n = 0, p.regions = 0;
+    pl->tail = (pl->tail + 1) % pl->n_pipes;
+    --pl->inflight;
+    *n_frames = frames;
+    if (rc != HP_OK && rc != HP_ERR_CAPACITY)
+        return rc;
+    for (int f = 0; f < frames; ++f) {
+        pl->cand.clear(), pl->cand_region.clear();
+        for (int r = 0; r < R; ++r) {
+            const int slot = f * R + r, cnt = std::min(pl->slot_n[slot], cap);
+            hp_human* hs = sh + (size_t)slot * cap;
+            const hp_roi& roi = p.roi[slot];
+            if (pl->keep_ratio)
+                hp_resume_ratio(hs, cnt, roi.w, roi.h, pl->in_w, pl->in_h);
+            hp_humans_to_frame(hs, cnt, &roi, p.w[f], p.h[f]);
+            pl->cand.insert(pl->cand.end(), hs, hs + cnt);
+            pl->cand_region.insert(pl->cand_region.end(), cnt, r);
+        }
+        int total = (int)pl->cand.size();
+        const hp_human* from = pl->cand.data();
+        if (R == 1)
+            total = pl->slot_n[f]; // the parser's own count, as an untiled collect reports it
+        else {
+            HP_TRY(hp::merge_humans(pl->cand.data(), pl->cand_region.data(), total, p.w[f], p.h[f], pl->tiling.min_common, pl->tiling.tol, pl->kept));
+            total = (int)pl->kept.size(), from = pl->kept.data();
+        }
+        n_out[f] = total;
+        if (out && std::min(total, cap) > 0)
+            memcpy(out + (size_t)f * cap, from, sizeof(hp_human) * std::min(total, cap));
+        if (total > cap && rc == HP_OK) {
+            hp::set_error("hp_pipeline_collect: frame %d has %d humans after the merge, room for %d", f, total, cap);
+            rc = HP_ERR_CAPACITY;
+        }
+    }
+    return rc;
 }
 
 } // namespace
@@ -336,6 +514,8 @@ int hp_pipeline_collect(hp_pipeline* pl, hp_human* out, int cap_per_frame, int* 
     HP_REQUIRE(pl && n_out && n_frames, HP_ERR_INVALID, "hp_pipeline_collect: null argument");
     HP_REQUIRE(pl->inflight > 0, HP_ERR_STATE, "hp_pipeline_collect: nothing in flight");
     pipe_t& p = pl->pipes[pl->tail];
+    if (p.regions)
+        return collect_tiled(pl, p, out, cap_per_frame, n_out, n_frames);
     const int n = p.n;
     const int rc = pl->kind == HP_PARSER_PAF ? hp_paf_collect(p.paf, out, cap_per_frame, n_out)
         : pl->kind == HP_PARSER_PPN        ? hp_ppn_collect(p.ppn, out, cap_per_frame, n_out)

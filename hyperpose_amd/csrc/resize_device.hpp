@@ -2,6 +2,8 @@
 // oracle/resize_oracle.cpp), shared by the kernels that differ only in where a source pixel's (b, g, r) come from:
 //   bgr_taps     an 8-bit BGR HWC frame                                  (resize.hip,     resize_u8c3_kernel)
 //   yuv420_taps  a YUV 4:2:0 frame, converted as the pixel is fetched    (resize_yuv.hip, resize_yuv420_kernel)
+//   yuv_taps<>   any hp_yuv_image layout (resize_yuv_device.hpp)             (resize_yuv_formats.hip; resize_rois.hip: many regions of one frame,
+//                                                                         every Taps type moved to a region's origin with Taps::at)
 // A `Taps` type has  __device__ void load(int x, int y, int (&c)[3]) const  returning the B, G, R of source pixel (x, y), each in 0..255.
 // resize_pixel() derives the source coordinates and the 11-bit coefficients of one output pixel, fetches at most 2 x 2 taps through
 // Taps::load and writes the pixel; rz_prepare() is the host side: argument checks and the choice between the three modes.
@@ -30,6 +32,8 @@ struct bgr_taps {
         const uint8_t* s = src + (size_t)y * stride + x * 3;
         c[0] = s[0], c[1] = s[1], c[2] = s[2];
     }
+    // the taps of the sub-image whose pixel (0, 0) is this frame's (rx, ry) (resize_rois.hip)
+    __device__ __forceinline__ bgr_taps at(int rx, int ry) const { return bgr_taps{ src + (size_t)ry * stride + rx * 3, stride }; }
 };
 
 __device__ __forceinline__ short sat_short_rn(float v)

@@ -20,8 +20,7 @@
 //     resize_yuv_word16_kernel    16-bit words, value = (word >> shift) & 1023  P010 (shift 6) I010 (shift 0)
 // Each keeps the shape of resize_yuv420_kernel: one thread = one output pixel, 32 x 8 pixels per block of 256 threads, byte / 16-bit
 // loads whose neighbours in a wavefront fall into the same few cache lines.
-#include "resize_device.hpp"
-#include "yuv_formats.hpp"
+#include "resize_yuv_device.hpp"
 
 #include <cstring>
 
@@ -29,39 +28,7 @@ namespace {
 
 using namespace hp_resize;
 
-constexpr int YUV_SHIFT = 20;
-
-__device__ __forceinline__ int sat8(int v) { return min(max(v, 0), 255); }
-
-template <int SAMPLE_BYTES, int Y_STEP> struct yuv_taps {
-    const uint8_t *y, *u, *v; // byte address of the first Y, U and V sample (semi-planar and packed: inside the same plane)
-    int y_stride, c_stride;   // row strides in bytes (c_stride: the U plane's, or the plane U and V share)
-    int v_extra;              // V plane's row stride - c_stride: a planar frame may give its V plane a pitch of its own (0 otherwise)
-    int c_step;               // bytes between horizontally neighbouring chroma samples
-    int sx, sy;               // chroma shifts
-    int shift;                // 16-bit samples: right shift before the 10-bit mask
-    int y_off, c_off, cy, cub, cug, cvg, cvr;
-    __device__ __forceinline__ int sample(const uint8_t* p) const
-    {
-        if constexpr (SAMPLE_BYTES == 2)
-            return (*reinterpret_cast<const uint16_t*>(p) >> shift) & 1023;
-        else
-            return *p;
-    }
-    __device__ __forceinline__ void load(int px, int py, int (&c)[3]) const
-    {
-        const size_t at = (size_t)(py >> sy) * c_stride + (size_t)(px >> sx) * c_step;
-        const int Y = sample(y + (size_t)py * y_stride + (size_t)px * (Y_STEP * SAMPLE_BYTES));
-        const int U = sample(u + at) - c_off, V = sample(v + at + (ptrdiff_t)(py >> sy) * v_extra) - c_off;
-        // 24-bit multiplies (full rate; a 32-bit v_mul_lo_u32 is not), exact here: every coefficient is below 2^23 (the largest, CUB of
-        // BT.2020 limited, is 2 245 836), the samples are below 2^10, and the low 32 bits of the product are the product (|sum| <= 5.81e8).
-        // resize_yuv420_kernel gets the same instructions from its literal constants
-        const int yy = __mul24(max(0, Y - y_off), cy) + (1 << (YUV_SHIFT - 1));
-        c[0] = sat8((yy + __mul24(cub, U)) >> YUV_SHIFT);
-        c[1] = sat8((yy + __mul24(cvg, V) + __mul24(cug, U)) >> YUV_SHIFT);
-        c[2] = sat8((yy + __mul24(cvr, V)) >> YUV_SHIFT);
-    }
-};
+// yuv_taps<> and fill_taps(): resize_yuv_device.hpp, shared with the multi-region kernels of resize_rois.hip
 
 template <class Taps> __device__ __forceinline__ void resize_yuv_body(const rz_geom& g, const Taps& t)
 {
@@ -74,15 +41,6 @@ template <class Taps> __device__ __forceinline__ void resize_yuv_body(const rz_g
 __global__ __launch_bounds__(256) void resize_yuv_planar8_kernel(const rz_geom g, const yuv_taps<1, 1> t) { resize_yuv_body(g, t); }
 __global__ __launch_bounds__(256) void resize_yuv_packed8_kernel(const rz_geom g, const yuv_taps<1, 2> t) { resize_yuv_body(g, t); }
 __global__ __launch_bounds__(256) void resize_yuv_word16_kernel(const rz_geom g, const yuv_taps<2, 1> t) { resize_yuv_body(g, t); }
-
-template <class Taps> void fill_taps(Taps& t, const hp_yuv_image& im, const hp_yuv::layout& l, const int32_t k[7])
-{
-    const hp_yuv::sample_map m = hp_yuv::map_samples(im, l);
-    t.sx = l.sx, t.sy = l.sy, t.shift = l.shift;
-    t.y = m.y, t.u = m.u, t.v = m.v;
-    t.y_stride = m.y_stride, t.c_stride = m.c_stride, t.c_step = m.c_step, t.v_extra = m.v_extra;
-    t.y_off = k[0], t.c_off = k[1], t.cy = k[2], t.cub = k[3], t.cug = k[4], t.cvg = k[5], t.cvr = k[6];
-}
 
 int launch_resize_yuv_image(const hp_yuv_image* im, const char* who, uint8_t* dst, int dw, int dh, int dst_stride, bool letterbox, const int bg[3],
     hipStream_t s)

@@ -6,8 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HUMAN_DTYPE, OVERLAY_PRIM_DTYPE, YUV_FORMATS, YUV_LAYOUTS, YUV_MATRICES, YUV_RANGES, DevBuf, Human, OverlayPrim, YuvImage, as_ptr,
-                   check, lib)
+from ._lib import (HUMAN_DTYPE, OVERLAY_PRIM_DTYPE, TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL, YUV_FORMATS, YUV_LAYOUTS, YUV_MATRICES, YUV_RANGES,
+                   DevBuf, Human, OverlayPrim, Roi, Tiling, YuvImage, as_ptr, check, lib)
 
 
 def resize(src_dev, sw: int, sh: int, dst_dev, dw: int, dh: int, stream=None, src_stride=None, dst_stride=None) -> None:
@@ -185,6 +185,75 @@ def resize_yuv_host(frame_planes, dw: int, dh: int, fmt: str = "nv12", matrix: s
     resize_yuv(yuv_image(fmt, [b.ptr for b in bufs], strides, w, h, matrix, range), dst, dw, dh, keep_ratio, bgcolor)
     check(lib().hp_device_synchronize())
     return dst.to_numpy(np.uint8, (dh, dw, 3))
+
+
+# ---- regions and tiles: many regions of one frame per launch, the tile planner, the way back and the merge (include/hp_hip.h) -----------
+
+def _rois(rois):
+    rois = [tuple(int(v) for v in r) for r in rois]
+    return (Roi * max(1, len(rois)))(*[Roi(*r) for r in rois]), len(rois)
+
+
+def yuv_roi_alignment(fmt: str):
+    """``hp_yuv_roi_alignment``: (ax, ay) a region's x / w and y / h must be multiples of in this layout."""
+    ax, ay = C.c_int(), C.c_int()
+    check(lib().hp_yuv_roi_alignment(YUV_LAYOUTS[fmt][0], C.byref(ax), C.byref(ay)))
+    return ax.value, ay.value
+
+
+def resize_rois(src, rois, dst_dev, dw: int, dh: int, keep_ratio: bool = False, bgcolor=(0, 0, 0), sw=None, sh=None, src_stride=None,
+                dst_stride=None, slot_stride=None, stream=None) -> None:
+    """``hp_resize_rois_u8c3`` / ``hp_resize_rois_yuv``: the regions ``rois`` [(x, y, w, h)] of ONE device frame - 8-bit BGR (``src`` a device
+    buffer, with ``sw``, ``sh`` and optionally ``src_stride``) or a ``YuvImage`` with device planes - to ``len(rois)`` slots of ``dst_dev``,
+    slot i at byte ``i * slot_stride`` (default: slots back to back), each what ``resize`` / ``letterbox`` give on the cut-out region."""
+    arr, n = _rois(rois)
+    ds = int(dst_stride or dw * 3)
+    ss = C.c_size_t(int(slot_stride if slot_stride is not None else ds * dh))
+    s = C.c_void_p(stream) if stream else None
+    bg = [int(c) for c in bgcolor]
+    if isinstance(src, YuvImage):
+        check(lib().hp_resize_rois_yuv(C.byref(src), arr, n, int(bool(keep_ratio)), bg[0], bg[1], bg[2], as_ptr(dst_dev), int(dw), int(dh), ds, ss, s))
+    else:
+        check(lib().hp_resize_rois_u8c3(as_ptr(src), int(sw), int(sh), int(src_stride or sw * 3), arr, n, int(bool(keep_ratio)), bg[0], bg[1], bg[2],
+                                        as_ptr(dst_dev), int(dw), int(dh), ds, ss, s))
+
+
+def tiling(cols: int, rows: int, overlap=(0, 0), with_full: bool = False, min_common: int = TILING_DEFAULT_MIN_COMMON,
+           tol: float = TILING_DEFAULT_TOL) -> Tiling:
+    """An ``hp_tiling``; ``overlap`` is one number or (ox, oy)."""
+    ox, oy = overlap if isinstance(overlap, (list, tuple)) else (overlap, overlap)
+    return Tiling(int(cols), int(rows), int(ox), int(oy), int(bool(with_full)), int(min_common), float(tol))
+
+
+def plan_tiles(frame_w: int, frame_h: int, cols: int, rows: int, overlap=(0, 0), with_full: bool = False, fmt=None, align=None, cap: int = 64):
+    """``hp_tile_plan``: the regions [(x, y, w, h)] of a frame, the whole frame first when ``with_full``, then the tiles row-major.  ``fmt`` names a
+    YUV layout whose alignment the tiles keep (``align`` = (ax, ay) gives it directly; default (1, 1): BGR)."""
+    ax, ay = align if align is not None else (yuv_roi_alignment(fmt) if fmt else (1, 1))
+    t = tiling(cols, rows, overlap, with_full)
+    out = (Roi * max(1, int(cap)))()
+    n = check(lib().hp_tile_plan(C.byref(t), int(frame_w), int(frame_h), int(ax), int(ay), out, int(cap)))
+    return [(out[i].x, out[i].y, out[i].w, out[i].h) for i in range(n)]
+
+
+def humans_to_frame(humans, roi, frame_w: int, frame_h: int) -> np.ndarray:
+    """``hp_humans_to_frame`` on a copy: humans normalised to the region ``roi`` (x, y, w, h) -> normalised to the frame."""
+    hs = _humans(humans).copy()
+    r = Roi(*[int(v) for v in roi])
+    lib().hp_humans_to_frame(hs.ctypes.data_as(C.POINTER(Human)), len(hs), C.byref(r), int(frame_w), int(frame_h))
+    return hs
+
+
+def merge_humans(humans, region_of, frame_w: int, frame_h: int, min_common: int = TILING_DEFAULT_MIN_COMMON, tol: float = TILING_DEFAULT_TOL,
+                 cap=None) -> np.ndarray:
+    """``hp_humans_merge``: ``humans`` (frame coordinates) with the region index each came from -> the merged humans, in kept order."""
+    hs = _humans(humans)
+    reg = np.ascontiguousarray(region_of, np.int32).reshape(-1)
+    assert len(reg) == len(hs)
+    cap = len(hs) if cap is None else int(cap)
+    out = np.zeros(max(1, cap), HUMAN_DTYPE)
+    n = check(lib().hp_humans_merge(hs.ctypes.data_as(C.POINTER(Human)), reg.ctypes.data_as(C.POINTER(C.c_int32)), len(hs), int(frame_w), int(frame_h),
+                                    int(min_common), C.c_double(tol), out.ctypes.data_as(C.POINTER(Human)), cap))
+    return out[:n]
 
 
 # ---- writing back: skeletons painted into frames (hp_overlay_*; the rules are stated in csrc/overlay.hpp and DESIGN.md 1.1) -------------

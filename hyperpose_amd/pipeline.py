@@ -6,7 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import HUMAN_DTYPE, YUV_FORMATS, YUV_LAYOUTS, Human, YuvImage, check, lib
+from ._lib import (HUMAN_DTYPE, TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL, YUV_FORMATS, YUV_LAYOUTS, Human, YuvImage,
+                   check, lib)
 from .engine import _DTYPES, EngineDesc, Layer, OutputDesc
 
 
@@ -62,6 +63,19 @@ class Pipeline:
     @property
     def in_flight(self) -> int:
         return lib().hp_pipeline_in_flight(self._h)
+
+    def set_tiling(self, cols=None, rows=None, overlap=(0, 0), with_full: bool = False, min_common: int = TILING_DEFAULT_MIN_COMMON,
+                   tol: float = TILING_DEFAULT_TOL) -> None:
+        """``hp_pipeline_set_tiling``: from now on a submitted frame is cut into ``cols`` x ``rows`` tiles that share at least ``overlap`` =
+        (ox, oy) pixels (plus the whole frame when ``with_full``), every region takes one slot of the batch - a submit carries at most
+        ``max_batch // regions`` frames - and ``collect`` returns the merged humans of each frame in the frame's coordinates.
+        ``set_tiling(None)`` turns it off.  Not while batches are in flight."""
+        from . import frontend
+        if cols is None:
+            check(lib().hp_pipeline_set_tiling(self._h, None))
+            return
+        t = frontend.tiling(cols, rows, overlap, with_full, min_common, tol)
+        check(lib().hp_pipeline_set_tiling(self._h, C.byref(t)))
 
     def submit(self, frames) -> None:
         """frames: list of [h, w, 3] uint8 BGR arrays (any sizes), at most max_batch."""

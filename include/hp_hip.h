@@ -164,6 +164,65 @@ size_t hp_yuv_packed_bytes(int format, int width, int height);
  * either pointer may be NULL (host only) */
 int hp_yuv_plane_layout(int format, int k, int width, int height, size_t* row_bytes, int* rows);
 
+/* ---- regions and tiles: inference on overlapping tiles of a frame much larger than the network's input ("sliced inference"), so that
+ * small people keep enough pixels (hyperpose_amd/csrc/resize_rois.hip, tiles.cpp; DESIGN.md 1.1 "Regions and tiles").
+ *
+ * hp_resize_rois_*: n regions (1 .. 64, a HOST array) of one DEVICE frame to n slots of dev_dst, slot i at dev_dst + i * slot_stride, in
+ * ceil(n / 16) launches; the call only enqueues.  Slot i holds, byte for byte, what hp_resize_u8c3 / hp_resize_yuv (keep_ratio == 0) or
+ * hp_letterbox_u8c3 / hp_letterbox_yuv with (b, g, r) (keep_ratio != 0) give on region i cut out into a frame of its own (the w x h
+ * sub-image; for YUV the sub-planes of every plane, same matrix, range and depth): mode and letterbox inner size are picked per region,
+ * taps clamp at the region's edges and no pixel outside a region is read.  Bytes of dev_dst beyond dw * 3 in a row and beyond dh rows in
+ * a slot are not written.  HP_ERR_INVALID, nothing launched and dev_dst untouched: n outside 1 .. 64; a region empty or not inside the
+ * frame; for YUV a region whose x / w (y / h) is no multiple of the layout's alignment (hp_yuv_roi_alignment; the message names the
+ * format and the region); slot_stride < dh * dst_stride; whatever hp_resize_yuv rejects for the frame itself. */
+typedef struct hp_roi { int32_t x, y, w, h; } hp_roi; /* source pixels, inside the frame */
+int hp_resize_rois_u8c3(const uint8_t* dev_src, int sw, int sh, int src_stride, const hp_roi* rois /* host */, int n, int keep_ratio,
+                        int b, int g, int r, uint8_t* dev_dst, int dw, int dh, int dst_stride, size_t slot_stride, void* stream);
+int hp_resize_rois_yuv(const hp_yuv_image* src /* device planes */, const hp_roi* rois, int n, int keep_ratio, int b, int g, int r,
+                       uint8_t* dev_dst, int dw, int dh, int dst_stride, size_t slot_stride, void* stream);
+/* host only: what a region's x and w (ax) and y and h (ay) must be multiples of: 4:2:0 -> 2, 2; 4:2:2 planar and packed -> 2, 1; I444 -> 1, 1 */
+int hp_yuv_roi_alignment(int format, int* ax, int* ay);
+
+/* The tile planner, the way back and the merge: host only, plain C++, deterministic; integers and IEEE doubles, no fused operations.
+ *
+ * hp_tile_plan, per axis (W the frame's size, c the tile count, a the alignment, o = align_up(overlap, a): the overlap asked for, rounded
+ * up to the alignment so that tiles which may only start at multiples of a still share at least `overlap` pixels):
+ *     tw  = min(W, align_up(ceil_div(W + (c - 1) * o, c), a))
+ *     x_i = align_down(i * (W - tw) / (c - 1), a)  (integer division; 0 when c == 1),  x_{c-1} = W - tw
+ * so the tiles cover the frame exactly and neighbours share at least `overlap` pixels wherever tw < W.  Regions are written row-major
+ * (all tiles of the first row of tiles, left to right, then the next row), after the whole frame when with_full.  Returns the region
+ * count; HP_ERR_INVALID for W % a != 0 (either axis), counts < 1, a negative overlap or cols * rows + with_full > 64; HP_ERR_CAPACITY
+ * when cap is smaller than the count (nothing is written).
+ *
+ * hp_humans_to_frame: humans normalised to a region (after hp_resume_ratio(region size -> network size) when letterboxed, exactly as for
+ * a whole frame) -> normalised to the frame: for every part with has_value,  x = (float)((roi.x + (double)x * roi.w) / frame_w),  y
+ * likewise.  For a region equal to the frame this is the identity on every float (x * W is exact in a double, and so is the quotient).
+ *
+ * hp_humans_merge: in[i] (frame coordinates) came from region region_of[i] (0 .. 63).  A part is present when has_value != 0; its pixel
+ * position is px = (double)x * frame_w, py = (double)y * frame_h.  Candidates are taken by human score descending, then region
+ * ascending, then index ascending, and walked once with a kept list K (empty at first).  Candidate c fuses into the first k of K, in
+ * kept order, for which  (1) k holds no contribution from c's region yet (two people the parser separated inside one tile are never
+ * fused),  (2) the parts present in both number m >= min_common,  (3) sum_j d_j <= tol * m * max(s(k), s(c)),  where d_j =
+ * sqrt(dx * dx + dy * dy) of common part j (summed by ascending part index) and s(h) = max(max px - min px, max py - min py) over h's
+ * present parts; the right side is evaluated as (tol * m) * max.  Fusing: a part k lacks is copied from c; where both have it the
+ * higher part score wins and a tie keeps k's; k keeps its human score and gains c's region; later candidates see the fused k.  A
+ * candidate that fuses nowhere is appended to K.  Returns the number kept, written to out in kept order; HP_ERR_CAPACITY when that
+ * exceeds cap (the first cap are written); HP_ERR_INVALID for a region outside 0 .. 63, min_common < 1 or a tol that is negative or NaN.
+ * Defaults of the mirrors (a product decision, no part of the contract): min_common = 3, tol = 0.08 - two detections are one person
+ * when at least three joints coincide to within 8 % of the larger one's extent on average. */
+#define HP_TILING_DEFAULT_MIN_COMMON 3
+#define HP_TILING_DEFAULT_TOL 0.08
+typedef struct hp_tiling {
+    int32_t cols, rows;            /* >= 1, cols*rows + with_full <= 64 */
+    int32_t overlap_x, overlap_y;  /* pixels two neighbouring tiles share at least */
+    int32_t with_full;             /* 1: the whole frame is region 0, the tiles follow row-major */
+    int32_t min_common; double tol;/* merge rule above */
+} hp_tiling;
+int hp_tile_plan(const hp_tiling* t, int frame_w, int frame_h, int ax, int ay, hp_roi* out, int cap); /* returns the region count */
+void hp_humans_to_frame(hp_human* humans, int n, const hp_roi* roi, int frame_w, int frame_h);
+int hp_humans_merge(const hp_human* in, const int32_t* region_of, int n, int frame_w, int frame_h, int min_common, double tol,
+                    hp_human* out, int cap); /* returns the count kept */
+
 /* ---- writing back: the skeletons of a frame's humans painted into a DEVICE-resident frame, 8-bit BGR or any hp_yuv_image layout in the frame's
  * own colour space and bit depth (hyperpose_amd/csrc/overlay.hip) - the last stage of the reference's stream, draw_human + writer
  * (src/stream.cpp:114-147), for frames that never leave the device.  The picture is defined by exact integer rules, stated once in
@@ -526,6 +585,15 @@ int hp_pipeline_submit_yuv_images(hp_pipeline* p, const hp_yuv_image* frames, in
 /* waits for the OLDEST batch in flight; out[i * cap_per_frame + j], n_out[i] for i < *n_frames */
 int hp_pipeline_collect(hp_pipeline* p, hp_human* out, int cap_per_frame, int* n_out, int* n_frames);
 int hp_pipeline_in_flight(const hp_pipeline* p);
+/* Tiled mode ("regions and tiles" above); t == NULL turns it off (the default), HP_ERR_STATE while batches are in flight, HP_ERR_CAPACITY when
+ * R = cols * rows + with_full exceeds max_batch.  With tiling on, every frame of hp_pipeline_submit and hp_pipeline_submit_yuv_images (host or
+ * device planes) becomes its R regions - planned for the frame's own size and its layout's alignment - in R consecutive slots of the batch,
+ * written by ONE hp_resize_rois_* call per frame; a submit carries at most max_batch / R frames (HP_ERR_CAPACITY beyond that) and
+ * hp_pipeline_submit_yuv returns HP_ERR_STATE.  hp_pipeline_collect parses all slots and, per frame, applies hp_resume_ratio per region (when the
+ * aspect ratio is kept), hp_humans_to_frame and hp_humans_merge(min_common, tol): *n_frames counts frames and the humans are in the frame's
+ * normalised coordinates, ready for hp_overlay_draw_*.  A frame of one region (1 x 1 tiles, no whole frame) has nothing to merge and keeps the
+ * parser's order: it is returned exactly as with tiling off.  Every parser kind works: the tail is shared. */
+int hp_pipeline_set_tiling(hp_pipeline* p, const hp_tiling* t);
 
 #ifdef __cplusplus
 }

@@ -238,6 +238,64 @@ namespace dnn {
             return collect(inputs.size());
         }
 
+        /// Addition: many regions of ONE frame in one call (tiled inference: hyperpose::plan_tiles, to_frame, merge_humans).  One packet per
+        /// region, each equal, bit for bit, to inference() of that region cut out into a cv::Mat of its own: the frame goes up once and
+        /// all regions are brought to the network's size by one hp_resize_rois_u8c3 call.  regions.size() <= max_batch_size
+        /// (std::logic_error beyond); a region that is empty or not inside the frame is a std::logic_error too.
+        std::vector<internal_t> inference(const cv::Mat& frame, const std::vector<cv::Rect>& regions)
+        {
+            require_calibrated();
+            if (regions.size() > (size_t)m_max_batch_size)
+                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(regions.size()) + " Max@" + std::to_string(m_max_batch_size));
+            if (regions.empty())
+                return {};
+            if (frame.empty())
+                fatal("hyperpose::dnn::tensorrt::inference: empty image");
+            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
+            if (!m_dev_net && hp_malloc((void**)&m_dev_net, net_frame * m_max_batch_size) != HP_OK)
+                fatal(hp_last_error());
+            retire_last_batch();
+            std::vector<uint8_t> scratch;
+            const uint8_t* src = detail::mat_bytes(frame, scratch);
+            const size_t bytes = (size_t)frame.cols * frame.rows * 3;
+            reserve_raw(bytes);
+            if (hp_memcpy_h2d(m_dev_raw, src, bytes) != HP_OK)
+                fatal(hp_last_error());
+            const std::vector<hp_roi> rois = to_rois(regions);
+            if (hp_resize_rois_u8c3(m_dev_raw, frame.cols, frame.rows, frame.cols * 3, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net,
+                    m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
+                != HP_OK)
+                throw std::logic_error(hp_last_error());
+            if (hp_engine_infer_u8(m_engine, m_dev_net, (int)rois.size(), 1, nullptr) != HP_OK)
+                fatal(hp_last_error());
+            return collect(rois.size());
+        }
+
+        /// The same for a yuv_frame (host planes are uploaded once, a device-resident surface is read where it lies; hp_resize_rois_yuv):
+        /// the regions keep the layout's alignment (hyperpose::plan_tiles(size, tiling, frame.format) plans them so).
+        std::vector<internal_t> inference(const yuv_frame& frame, const std::vector<cv::Rect>& regions)
+        {
+            require_calibrated();
+            if (regions.size() > (size_t)m_max_batch_size)
+                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(regions.size()) + " Max@" + std::to_string(m_max_batch_size));
+            if (regions.empty())
+                return {};
+            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
+            if (!m_dev_net && hp_malloc((void**)&m_dev_net, net_frame * m_max_batch_size) != HP_OK)
+                fatal(hp_last_error());
+            retire_last_batch();
+            std::vector<uint8_t> scratch;
+            const hp_yuv_image im = yuv_image_on_device(frame, scratch);
+            const std::vector<hp_roi> rois = to_rois(regions);
+            if (hp_resize_rois_yuv(&im, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width, m_inp_size.height,
+                    m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
+                != HP_OK)
+                throw std::logic_error(hp_last_error());
+            if (hp_engine_infer_u8(m_engine, m_dev_net, (int)rois.size(), 1, nullptr) != HP_OK)
+                fatal(hp_last_error());
+            return collect(rois.size());
+        }
+
         /// data_type::kINT8: TensorRT's MinMax calibration (an IInt8MinMaxCalibrator fed with these frames).  Frames of any size are brought to
         /// the network's size exactly as inference() does; any number of frames (the engine runs them in max_batch_size chunks).  Replaces
         /// every per-layer activation scale; calibration is never implicit.
@@ -431,6 +489,16 @@ namespace dnn {
         // hp_yuv_packed_bytes, a device frame is read where it lies; then hp_resize_yuv / hp_letterbox_yuv writes dst
         void yuv_image_to_device(const yuv_frame& f, uint8_t* dst, std::vector<uint8_t>& scratch)
         {
+            const hp_yuv_image im = yuv_image_on_device(f, scratch);
+            const int rc = m_keep_ratio
+                ? hp_letterbox_yuv(&im, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, 0, 0, 0, hp_engine_stream(m_engine))
+                : hp_resize_yuv(&im, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, hp_engine_stream(m_engine));
+            if (rc != HP_OK || hp_engine_synchronize(m_engine) != HP_OK) // m_dev_raw is re-used by the next frame
+                fatal(hp_last_error());
+        }
+        // the checks of a yuv_frame and its description as a kernel reads it: the caller's surface, or the packed copy in m_dev_raw
+        hp_yuv_image yuv_image_on_device(const yuv_frame& f, std::vector<uint8_t>& scratch)
+        {
             const int planes = yuv_frame::plane_count(f.format);
             if (planes == 0)
                 throw std::logic_error("hyperpose: yuv_frame::format must be one of HP_YUV_NV12 .. HP_YUV_I444");
@@ -467,11 +535,25 @@ namespace dnn {
                 if (hp_memcpy_h2d(m_dev_raw, scratch.data(), bytes) != HP_OK)
                     fatal(hp_last_error());
             }
-            const int rc = m_keep_ratio
-                ? hp_letterbox_yuv(&im, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, 0, 0, 0, hp_engine_stream(m_engine))
-                : hp_resize_yuv(&im, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, hp_engine_stream(m_engine));
-            if (rc != HP_OK || hp_engine_synchronize(m_engine) != HP_OK) // m_dev_raw is re-used by the next frame
+            return im;
+        }
+        void reserve_raw(size_t bytes)
+        {
+            if (bytes <= m_raw_bytes)
+                return;
+            if (m_dev_raw)
+                hp_free(m_dev_raw);
+            m_dev_raw = nullptr, m_raw_bytes = 0;
+            if (hp_malloc((void**)&m_dev_raw, bytes) != HP_OK)
                 fatal(hp_last_error());
+            m_raw_bytes = bytes;
+        }
+        static std::vector<hp_roi> to_rois(const std::vector<cv::Rect>& regions)
+        {
+            std::vector<hp_roi> r;
+            for (const cv::Rect& q : regions)
+                r.push_back(hp_roi{ q.x, q.y, q.width, q.height });
+            return r;
         }
         [[noreturn]] static void fatal(const char* msg)
         {

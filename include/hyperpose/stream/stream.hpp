@@ -56,7 +56,7 @@ public:
     hip_stream(const dnn::builtin_model& model, cv::Size input_size, int max_batch_size = 8, bool keep_ratio = false,
         int n_pipes = 4, cv::Size max_frame = cv::Size(1920, 1080), float conf_thresh = 0.05f, float paf_thresh = 0.05f,
         double factor = 1. / 255, bool flip_rgb = true, data_type dtype = data_type::kFLOAT)
-        : m_max_batch(max_batch_size)
+        : m_max_batch(max_batch_size), m_engine_batch(max_batch_size)
     {
         dnn::tensorrt engine(model, input_size, max_batch_size, keep_ratio, dtype, factor, flip_rgb);
         hp_parser_desc pd{};
@@ -66,7 +66,7 @@ public:
     // replicate an existing engine (any model source) behind any of the three parsers
     hip_stream(hp_engine* engine, const hp_parser_desc& parser, int max_batch_size, bool keep_ratio, int n_pipes = 4,
         cv::Size max_frame = cv::Size(1920, 1080))
-        : m_max_batch(max_batch_size)
+        : m_max_batch(max_batch_size), m_engine_batch(max_batch_size)
     {
         init(engine, parser, max_batch_size, keep_ratio, n_pipes, max_frame);
     }
@@ -76,7 +76,16 @@ public:
     size_t in_flight() const { return (size_t)hp_pipeline_in_flight(m_pl); }
     size_t truncated() const { return m_truncated.load(); }
     int n_pipes() const { return m_pipes; }
-    int max_batch() const { return m_max_batch; }
+    int max_batch() const { return m_max_batch; } // frames per push (in tiled mode: what is left of the batch after every frame's regions)
+
+    // hp_pipeline_set_tiling: every frame pushed from now on is inferred on its tiles and comes back with the merged humans, in the frame's
+    // coordinates (utility/data.hpp, tiling); nullptr turns it off.  Not while batches are in flight (std::runtime_error).
+    void set_tiling(const tiling* t)
+    {
+        const hp_tiling c = t ? t->c_form() : hp_tiling{};
+        detail::hp_check(hp_pipeline_set_tiling(m_pl, t ? &c : nullptr));
+        m_max_batch = t ? m_engine_batch / t->regions() : m_engine_batch;
+    }
 
     // one batch (<= max_batch_size frames, any sizes); throws when every pipe is busy
     void push(const std::vector<cv::Mat>& frames)
@@ -130,7 +139,8 @@ private:
         m_n.resize(max_batch_size);
     }
     hp_pipeline* m_pl = nullptr;
-    int m_max_batch, m_pipes = 0;
+    std::atomic<int> m_max_batch;
+    int m_engine_batch, m_pipes = 0;
     std::atomic<size_t> m_truncated{ 0 };
     std::vector<hp_human> m_out;
     std::vector<int> m_n;
@@ -239,6 +249,12 @@ public:
     size_t processed_num() const noexcept { return m_ingest.load(); }
     /// frames whose pose list was cut at a hard capacity of the device parser (reported, the stream keeps running)
     size_t truncated_num() const noexcept { return m_gpu.truncated(); }
+
+    /// Addition: tiled inference for frames much larger than the network's input (utility/data.hpp, tiling; hp_pipeline_set_tiling): every
+    /// frame is inferred on its overlapping tiles and the sinks receive the merged humans in the frame's coordinates.  Call it before the
+    /// first input is connected: the tiling cannot change while batches are in flight (std::runtime_error).
+    void set_tiling(const tiling& t) { m_gpu.set_tiling(&t); }
+    void clear_tiling() { m_gpu.set_tiling(nullptr); }
 
 private:
     struct item {

@@ -21,6 +21,13 @@ struct Size {
     bool operator==(const Size& o) const { return width == o.width && height == o.height; }
     bool operator!=(const Size& o) const { return !(*this == o); }
 };
+struct Rect {
+    int x = 0, y = 0, width = 0, height = 0;
+    Rect() = default;
+    Rect(int x_, int y_, int w, int h) : x(x_), y(y_), width(w), height(h) {}
+    int area() const { return width * height; }
+    bool operator==(const Rect& o) const { return x == o.x && y == o.y && width == o.width && height == o.height; }
+};
 // Minimal continuous 8-bit 3-channel image (rows x cols x 3, BGR), shared ownership like cv::Mat.
 class Mat {
 public:

@@ -17,6 +17,39 @@
 
 namespace hyperpose {
 
+/// Addition: tiled inference (include/hp_hip.h, "regions and tiles").  A frame much larger than the network's input is cut into cols x rows
+/// tiles that share at least `overlap` pixels (plus, with_full, the whole frame as region 0), every region is inferred at the network's
+/// size, and the humans are mapped back to the frame (to_frame) and merged (merge_humans, utility/human.hpp).  min_common / tol: two
+/// detections from different regions are one person when at least min_common joints are present in both and their mean distance is
+/// at most tol times the larger one's extent; the defaults are HP_TILING_DEFAULT_*.
+struct tiling {
+    int cols = 1, rows = 1;
+    int overlap_x = 0, overlap_y = 0;
+    bool with_full = false;
+    int min_common = HP_TILING_DEFAULT_MIN_COMMON;
+    double tol = HP_TILING_DEFAULT_TOL;
+    int regions() const { return cols * rows + (with_full ? 1 : 0); }
+    hp_tiling c_form() const { return hp_tiling{ cols, rows, overlap_x, overlap_y, with_full ? 1 : 0, min_common, tol }; }
+};
+
+/// hp_tile_plan: the regions of a `size` frame, the whole frame first when t.with_full, then the tiles row-major.  `yuv_format`: the
+/// HP_YUV_* layout whose chroma alignment the tiles keep (-1: none, a BGR frame).  Throws std::invalid_argument on a plan the rules refuse.
+inline std::vector<cv::Rect> plan_tiles(cv::Size size, const tiling& t, int yuv_format = -1)
+{
+    int ax = 1, ay = 1;
+    if (yuv_format >= 0 && hp_yuv_roi_alignment(yuv_format, &ax, &ay) != HP_OK)
+        throw std::invalid_argument(hp_last_error());
+    const hp_tiling c = t.c_form();
+    hp_roi out[64];
+    const int n = hp_tile_plan(&c, size.width, size.height, ax, ay, out, 64);
+    if (n < 0)
+        throw std::invalid_argument(hp_last_error());
+    std::vector<cv::Rect> r;
+    for (int i = 0; i < n; ++i)
+        r.emplace_back(out[i].x, out[i].y, out[i].w, out[i].h);
+    return r;
+}
+
 namespace detail {
     // The output tensors of ONE dnn::tensorrt::inference call while they still lie in the engine's device buffers.  The reference copies
     // every tensor of every image to the host before it returns (src/tensorrt.cpp:423-428) and the parser copies nothing back; here the

@@ -7,8 +7,11 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <stdexcept>
 #include <utility>
+#include <vector>
 
+#include "../../hp_hip.h"
 #include "cv_min.hpp"
 
 namespace hyperpose {
@@ -45,6 +48,44 @@ inline void resume_ratio(human_t_<J>& human, cv::Size src, cv::Size dst)
         for (auto& par : human.parts)
             par.y *= yratio;
     }
+}
+
+// ---- Addition: tiled inference (include/hp_hip.h, "regions and tiles"; the rules are stated there, once) -------------------------------
+// to_frame: a human normalised to `region` of a `frame`-sized picture (after resume_ratio(region size, network size) when the aspect
+// ratio was kept) -> normalised to the frame; the identity when the region is the frame.  The arithmetic of hp_humans_to_frame.
+template <size_t J>
+inline void to_frame(human_t_<J>& human, cv::Rect region, cv::Size frame)
+{
+    for (auto& par : human.parts)
+        if (par.has_value) {
+            par.x = (float)((region.x + (double)par.x * region.width) / frame.width);
+            par.y = (float)((region.y + (double)par.y * region.height) / frame.height);
+        }
+}
+
+// merge_humans (hp_humans_merge): humans[i], in frame coordinates, came from region region_of[i]; returns the merged list in kept order
+inline std::vector<human_t> merge_humans(const std::vector<human_t>& humans, const std::vector<int>& region_of, cv::Size frame,
+    int min_common = HP_TILING_DEFAULT_MIN_COMMON, double tol = HP_TILING_DEFAULT_TOL)
+{
+    if (humans.size() != region_of.size())
+        throw std::invalid_argument("hyperpose::merge_humans: one region index per human");
+    std::vector<hp_human> in(humans.size()), out(humans.size());
+    for (size_t i = 0; i < humans.size(); ++i) {
+        in[i].score = humans[i].score;
+        for (int k = 0; k < COCO_N_PARTS; ++k)
+            in[i].parts[k] = hp_body_part{ humans[i].parts[k].has_value ? 1 : 0, humans[i].parts[k].x, humans[i].parts[k].y, humans[i].parts[k].score };
+    }
+    std::vector<int32_t> reg(region_of.begin(), region_of.end());
+    const int n = hp_humans_merge(in.data(), reg.data(), (int)in.size(), frame.width, frame.height, min_common, tol, out.data(), (int)out.size());
+    if (n < 0)
+        throw std::invalid_argument(hp_last_error());
+    std::vector<human_t> r(n);
+    for (int i = 0; i < n; ++i) {
+        r[i].score = out[i].score;
+        for (int k = 0; k < COCO_N_PARTS; ++k)
+            r[i].parts[k] = body_part_t{ out[i].parts[k].has_value != 0, out[i].parts[k].x, out[i].parts[k].y, out[i].parts[k].score };
+    }
+    return r;
 }
 
 // ---- draw_human (reference include/hyperpose/utility/human.hpp:36-42, src/human.cpp:7-39, colours src/color.hpp:16-36, limb table
