@@ -14,6 +14,7 @@
 #include "conv_i8.hpp"
 #include "conv_kernels.hpp"
 #include "hp_common.hpp"
+#include "weight_pack.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -121,10 +122,11 @@ constexpr int OP_SEPCONV = 100; // schedule-only op codes (not part of the hp_la
 constexpr int OP_MLPHEAD = 101;
 constexpr int OP_CHAIN = 102;
 constexpr int OP_BNECK = 103;
+// a single dense layer's launch, as the schedule rewrites look for it
+inline bool plain_conv(const step& st) { return st.op == HP_OP_CONV && !st.first && st.n_layers == 1; }
 
-// element (m, k) of a K-wide fp16 matrix in MFMA fragment order: [32-row tile][16-wide k step][lane = (k % 16 / 8) * 32 + m % 32][k % 8],
-// KQ = K / 16 steps; tile0 = 32-row tiles in front of the matrix (a convolution's earlier taps)
-inline size_t frag16(size_t m, size_t k, size_t KQ, size_t tile0 = 0) { return (((tile0 + m / 32) * KQ + k / 16) * 64 + (k % 16 / 8) * 32 + m % 32) * 8 + k % 8; }
+constexpr hp::tview NO_RES{ nullptr, 0, 0, 0, 0 }; // conv_params::res of a layer without a residual
+constexpr hp::tview32 NO_RES32{ nullptr, 0, 0, 0, 0 };
 
 void same_pad(int in, int k, int stride, int dil, int& out, int& pad_before)
 {
@@ -227,10 +229,26 @@ struct hp_engine {
     int bind_outputs(const hp_engine_desc* d);
     int plan_activations();
     int lower_layers();
-    int lower32(size_t i);
-    int lower16(size_t i);
+    int lower_single(size_t i);
+    // ... fp32 engines: one step per layer, or per fused pair (described at its second layer)
+    int lower32_conv(size_t i, step& st);
+    int lower32_dw_in_front(size_t i, step& st);
+    int lower32_winograd_forms(size_t i, step& st, const std::vector<float>& packed);
+    int lower32_direct_forms(size_t i, step& st, const std::vector<float>& packed, int room);
+    int lower32_head_in_front(size_t i, step& st, const float* w);
+    int lower32_dw(size_t i, step& st);
+    // ... fp16 and int8 engines: one layer, a two-layer head, a separable block
+    int lower16_first(size_t i, step& st);
+    int lower16_conv(size_t i, step& st);
+    int lower16_i8(size_t i, step& st, const float* w);
+    int lower16_dw(size_t i, step& st);
     int lower16_head_pair(size_t i);
     int lower16_sep_pair(size_t i);
+    // ... what the two precisions share (P: the fp16 / fp32 parameter struct of the same launch)
+    template <typename P>
+    int lower_first(size_t i, step& st, P& p, const float*& w);
+    template <typename P>
+    int lower_pool(size_t i, step& st, P& p);
     int plan_splitk();
     int fuse_chains();
     int fuse_bottlenecks();
@@ -245,8 +263,29 @@ struct hp_engine {
     // per-layer plan, its int8 layers replace single launches of it
     bool fuse_off() const { return dtype == HP_DTYPE_I8 || switches.no_fuse; }
     bool tensor_is_read(int t) const; // some layer reads it (input or residual), or an un-fused output conversion will
+    // what every fusion asks before it keeps tensor t out of HBM: exactly one layer writes it, no layer but la / lb reads it (as input or
+    // residual) and no bound network output exports it
+    bool private_to(int t, int la, int lb) const;
     const float* blob(int64_t off, size_t n, const char* what, size_t layer) const; // weights_blob[off, off + n), or nullptr + error
     int upload(const void* src, size_t bytes, void** dst); // a new weight buffer holding src
+    // ... what the lowerings repeat: a packed vector uploaded; n blob floats zero-padded to n_pad (off < 0: all zeros) fetched / uploaded;
+    // a layer's PReLU slopes (nullptr without PReLU); its residual view; the fp32 network output its epilogue writes
+    template <typename T>
+    int upload(const std::vector<T>& v, const T*& dst)
+    {
+        void* d = nullptr;
+        HP_TRY(upload(v.data(), v.size() * sizeof(T), &d));
+        dst = static_cast<const T*>(d);
+        return HP_OK;
+    }
+    bool fetch_padded(int64_t off, size_t n, size_t n_pad, const char* what, size_t layer, std::vector<float>& v) const;
+    int upload_padded(int64_t off, size_t n, size_t n_pad, const char* what, size_t layer, const float*& dst);
+    int upload_prelu(size_t layer, int n_pad, const float*& alpha);
+    hp::tview res_view(int t) const { return t >= 0 ? tensors[t]->view(0) : NO_RES; }
+    hp::tview32 res_view32(int t) const { return t >= 0 ? tensors[t]->view32(0) : NO_RES32; }
+    template <typename V>
+    float* fused_output(size_t layer, bool whole_tensor_only, V& out);
+    int pointwise_params(size_t layer, int H, int W, int cout_pad, hp::conv_params& q); // the 1 x 1 second half of a fused fp16 pair
     // host_src != nullptr (eager launches of a host batch): every range copies ITS frames to the device on ITS stream first (frame_bytes each)
     int enqueue(const uint8_t* u8, const float* f32, int n, hipStream_t s, const void* host_src = nullptr, size_t frame_bytes = 0);
     int run_step(step& st, const uint8_t* u8, const float* f32, int n, hipStream_t s, int b0 = 0);
@@ -274,6 +313,20 @@ const float* hp_engine::blob(int64_t off, size_t n, const char* what, size_t lay
         return nullptr;
     }
     return weights_blob.data() + off;
+}
+
+bool hp_engine::private_to(int t, int la, int lb) const
+{
+    int writers = 0;
+    for (size_t j = 0; j < layers.size(); ++j) {
+        if ((int)j != la && (int)j != lb && (layers[j].in == t || layers[j].res == t))
+            return false;
+        writers += layers[j].out == t;
+    }
+    for (const auto& o : outputs)
+        if (o.tensor == t)
+            return false;
+    return writers == 1;
 }
 
 int hp_engine::upload(const void* src, size_t bytes, void** dst)
@@ -407,44 +460,52 @@ int hp_engine::mark_pair_fusions(const hp_engine_desc* d)
     const bool f32 = is_f32();
     const bool no_fuse = fuse_off();
     fuse_next.assign(layers.size(), fuse_kind::none);
+    // ---- what the four rules below share, for A = layer i and B = layer i + 1
+    // B is a plain stride-1 1 x 1 that consumes all of A's output (A writes the whole tensor, at channel 0) and writes elsewhere
+    auto pointwise_behind = [&](const hp_layer& A, const hp_layer& B) {
+        return A.in != 0 && A.out_coff == 0 && tensors[A.out]->C == A.cout && B.op == HP_OP_CONV && B.kh == 1 && B.kw == 1 && B.stride == 1
+            && B.in == A.out && B.in_coff == 0 && B.cin == A.cout && B.out != A.out;
+    };
+    // layer j does not pad and the map keeps its size (a padded 1x1 - ONNX pads - changes it: the fused launches assume it does not)
+    auto keeps_map = [&](size_t j) {
+        return geos[j].OH == tensors[layers[j].in]->H && geos[j].OW == tensors[layers[j].in]->W && geos[j].pt == 0 && geos[j].pl == 0;
+    };
+    // (the outputs are not bound yet, pass 3: the description's own list)
+    auto is_output = [&](int t) {
+        for (int o = 0; o < d->n_outputs; ++o)
+            if (d->outputs[o].tensor == t)
+                return true;
+        return false;
+    };
+    // A's output is private to the pair: written by A alone, read by B alone, no network output - it is never materialised
+    auto private_to_pair = [&](size_t i) { return private_to(layers[i].out, (int)i + 1, (int)i + 1) && !is_output(layers[i].out); };
+    auto dw3x3 = [](const hp_layer& A) { return A.op == HP_OP_DWCONV && A.kh == 3 && A.kw == 3; };
+    auto conv1x1 = [](const hp_layer& A) { return A.op == HP_OP_CONV && A.kh == 1 && A.kw == 1 && A.stride == 1 && A.res < 0; };
+    auto post_op_act = [](const hp_layer& B) { return B.act == HP_ACT_SIGMOID || B.act == HP_ACT_SOFTPLUS; };
+    auto fuse = [&](size_t i, fuse_kind k) { fuse_next[i] = k, tensors[layers[i].out]->elided = true; };
     // ---- separable blocks: a depthwise layer whose only consumer is the next layer, a plain 1x1 convolution, runs
     // as ONE launch (sepconv_kernel) and its output tensor is never materialised.  HP_NO_FUSE=1 keeps the two launches.
     if (!no_fuse && !f32) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
-            if (A.op != HP_OP_DWCONV || A.kh != 3 || A.kw != 3 || A.in == 0 || A.out_coff != 0 || A.in_coff % 8)
+            if (!dw3x3(A) || A.in_coff % 8 || !pointwise_behind(A, Bn) || Bn.res >= 0 || Bn.cout % 8 || Bn.out_coff % 8)
                 continue;
-            if (Bn.op != HP_OP_CONV || Bn.kh != 1 || Bn.kw != 1 || Bn.stride != 1 || Bn.in != A.out || Bn.in_coff != 0 || Bn.cin != A.cout
-                || Bn.res >= 0 || Bn.out == A.out || Bn.cout % 8 || Bn.out_coff % 8)
-                continue;
-            if ((A.act != HP_ACT_RELU && A.act != HP_ACT_RELU6) || Bn.act == HP_ACT_SIGMOID || Bn.act == HP_ACT_SOFTPLUS)
+            if ((A.act != HP_ACT_RELU && A.act != HP_ACT_RELU6) || post_op_act(Bn))
                 continue; // the fused kernel evaluates the depthwise activation as one clamp
-            if (tensors[A.out]->C != A.cout)
-                continue;
             {   // the fused kernel is configured for TF-SAME geometry: explicit pads must reproduce it, the 1x1 half must not pad at all
                 int oh, ow, pt, pl;
                 same_pad(tensors[A.in]->H, 3, A.stride, A.dil, oh, pt);
                 same_pad(tensors[A.in]->W, 3, A.stride, A.dil, ow, pl);
-                if (geos[i].OH != oh || geos[i].OW != ow || geos[i].pt != pt || geos[i].pl != pl)
-                    continue;
-                if (geos[i + 1].OH != oh || geos[i + 1].OW != ow || geos[i + 1].pt != 0 || geos[i + 1].pl != 0)
+                if (geos[i].OH != oh || geos[i].OW != ow || geos[i].pt != pt || geos[i].pl != pl || !keeps_map(i + 1))
                     continue;
             }
-            bool sole = true;
-            for (size_t j = 0; j < layers.size(); ++j)
-                if (j != i + 1 && (layers[j].in == A.out || layers[j].res == A.out || (j != i && layers[j].out == A.out)))
-                    sole = false;
-            for (int o = 0; o < d->n_outputs; ++o)
-                if (d->outputs[o].tensor == A.out || d->outputs[o].tensor == Bn.out)
-                    sole = false; // network outputs keep the generic epilogue (fp32 NCHW copy)
-            if (!sole)
-                continue;
+            if (!private_to_pair(i) || is_output(Bn.out))
+                continue; // network outputs keep the generic epilogue (fp32 NCHW copy): this rule alone also refuses B's tensor as one
             const int cout_pad = round_up(Bn.cout, 128);
             const int variant = hp::sepconv_variant_for(A.cin, cout_pad, A.stride, A.dil, Bn.cout);
             if (!variant || (Bn.cout <= 64 && variant != 7))
                 continue; // (<= 64 output channels idle half of the general fused kernels' wavefronts - slower than two launches - except in the dedicated 32-channel form)
-            fuse_next[i] = fuse_kind::sep;
-            tensors[A.out]->elided = true;
+            fuse(i, fuse_kind::sep);
         }
     }
     // ---- fp32 engines: the same pairing for conv32_direct_kernel's depthwise-fused forms (stride 1, dilation 1 | 2, whole 64-channel chunks;
@@ -460,25 +521,15 @@ int hp_engine::mark_pair_fusions(const hp_engine_desc* d)
     if (f32 && !no_fuse && !switches.no_fuse32 && (dtype == HP_DTYPE_F32S || switches.fuse32)) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
-            if (A.op != HP_OP_DWCONV || A.kh != 3 || A.kw != 3 || A.in == 0 || A.out_coff != 0 || A.in_coff % 4 || A.stride != 1 || (A.dil != 1 && A.dil != 2)
-                || A.cin % 64 || A.res >= 0)
+            if (!dw3x3(A) || A.in_coff % 4 || A.stride != 1 || (A.dil != 1 && A.dil != 2) || A.cin % 64 || A.res >= 0)
                 continue;
             if (A.act != HP_ACT_NONE && A.act != HP_ACT_RELU && A.act != HP_ACT_RELU6 && A.act != HP_ACT_LEAKY)
                 continue;
-            if (Bn.op != HP_OP_CONV || Bn.kh != 1 || Bn.kw != 1 || Bn.stride != 1 || Bn.in != A.out || Bn.in_coff != 0 || Bn.cin != A.cout || Bn.out == A.out
-                || Bn.res == A.out)
+            if (!pointwise_behind(A, Bn) || Bn.res == A.out)
                 continue;
-            if (tensors[A.out]->C != A.cout || geos[i].OH != tensors[A.in]->H || geos[i].OW != tensors[A.in]->W || geos[i].pt != A.dil || geos[i].pl != A.dil
-                || geos[i + 1].OH != geos[i].OH || geos[i + 1].OW != geos[i].OW || geos[i + 1].pt || geos[i + 1].pl)
+            if (geos[i].OH != tensors[A.in]->H || geos[i].OW != tensors[A.in]->W || geos[i].pt != A.dil || geos[i].pl != A.dil || !keeps_map(i + 1))
                 continue; // TF-SAME geometry of a stride-1 3 x 3: the map keeps its size, the padding is the dilation; the 1 x 1 half does not pad
-            bool sole = true;
-            for (size_t j = 0; j < layers.size(); ++j)
-                if (j != i + 1 && (layers[j].in == A.out || layers[j].res == A.out || (j != i && layers[j].out == A.out)))
-                    sole = false;
-            for (int o = 0; o < d->n_outputs; ++o)
-                if (d->outputs[o].tensor == A.out)
-                    sole = false;
-            if (!sole)
+            if (!private_to_pair(i))
                 continue;
             // the 1 x 1 half as pass 2 will describe it, to ask the kernel family whether a fused form exists for its size
             hp::conv32_params q{};
@@ -487,38 +538,23 @@ int hp_engine::mark_pair_fusions(const hp_engine_desc* d)
             // (an HP_DTYPE_F32S engine must also be able to run the block on the fp32 pipe: where it goes when a value leaves fp16's range)
             if (!hp::conv32_dw_fusable(q, false, A.dil) || (dtype == HP_DTYPE_F32S && !hp::conv32_dw_fusable(q, true, A.dil)))
                 continue;
-            fuse_next[i] = fuse_kind::sep32;
-            tensors[A.out]->elided = true;
+            fuse(i, fuse_kind::sep32);
         }
     }
     // ---- two-layer heads: 1x1 K1 -> 512 (relu) whose only consumer is the next layer, a 1x1 512 -> <= 64 channels
     if (!no_fuse && !f32) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
-            if (A.op != HP_OP_CONV || A.kh != 1 || A.kw != 1 || A.stride != 1 || A.in == 0 || A.res >= 0 || A.out_coff != 0 || A.in_coff % 8
-                || (A.act != HP_ACT_RELU && A.act != HP_ACT_RELU6))
+            if (!conv1x1(A) || A.in_coff % 8 || (A.act != HP_ACT_RELU && A.act != HP_ACT_RELU6))
                 continue;
-            if (Bn.op != HP_OP_CONV || Bn.kh != 1 || Bn.kw != 1 || Bn.stride != 1 || Bn.in != A.out || Bn.in_coff != 0 || Bn.cin != A.cout
-                || Bn.res >= 0 || Bn.out == A.out || Bn.act == HP_ACT_SIGMOID || Bn.act == HP_ACT_SOFTPLUS)
+            if (!pointwise_behind(A, Bn) || Bn.res >= 0 || post_op_act(Bn) || !keeps_map(i) || !keeps_map(i + 1))
                 continue;
-            if (tensors[A.out]->C != A.cout || !hp::mlp_head_variant(A.cin, A.cout, Bn.cout, switches.no_fuse_head))
+            if (!hp::mlp_head_variant(A.cin, A.cout, Bn.cout, switches.no_fuse_head))
                 continue;
-            if (geos[i].OH != tensors[A.in]->H || geos[i].OW != tensors[A.in]->W || geos[i].pt || geos[i].pl || geos[i + 1].OH != geos[i].OH
-                || geos[i + 1].OW != geos[i].OW || geos[i + 1].pt || geos[i + 1].pl)
-                continue; // a padded 1x1 (ONNX pads) changes the map size: the fused head assumes it does not
             if (i > 0 && (fuse_next[i - 1] == fuse_kind::sep))
                 continue; // already the pointwise half of a separable block
-            bool sole = true;
-            for (size_t j = 0; j < layers.size(); ++j)
-                if (j != i + 1 && (layers[j].in == A.out || layers[j].res == A.out || (j != i && layers[j].out == A.out)))
-                    sole = false;
-            for (int o = 0; o < d->n_outputs; ++o)
-                if (d->outputs[o].tensor == A.out)
-                    sole = false;
-            if (!sole)
-                continue;
-            fuse_next[i] = fuse_kind::head;
-            tensors[A.out]->elided = true;
+            if (private_to_pair(i))
+                fuse(i, fuse_kind::head);
         }
     }
     // ---- HP_DTYPE_F32: the same two-layer heads for conv32_head_kernel (1 x 1 128 -> HID, ReLU family, sole consumer a 1 x 1 HID -> <= 64
@@ -526,30 +562,16 @@ int hp_engine::mark_pair_fusions(const hp_engine_desc* d)
     if (dtype == HP_DTYPE_F32 && !no_fuse && !switches.no_head32) {
         for (size_t i = 0; i + 1 < layers.size(); ++i) {
             const hp_layer &A = layers[i], &Bn = layers[i + 1];
-            if (A.op != HP_OP_CONV || A.kh != 1 || A.kw != 1 || A.stride != 1 || A.in == 0 || A.res >= 0 || A.out_coff != 0 || A.in_coff % 4
-                || (A.act != HP_ACT_NONE && A.act != HP_ACT_RELU && A.act != HP_ACT_RELU6 && A.act != HP_ACT_LEAKY))
+            if (!conv1x1(A) || A.in_coff % 4 || (A.act != HP_ACT_NONE && A.act != HP_ACT_RELU && A.act != HP_ACT_RELU6 && A.act != HP_ACT_LEAKY))
                 continue;
-            if (Bn.op != HP_OP_CONV || Bn.kh != 1 || Bn.kw != 1 || Bn.stride != 1 || Bn.in != A.out || Bn.in_coff != 0 || Bn.cin != A.cout || Bn.res >= 0
-                || Bn.out == A.out || Bn.act == HP_ACT_SIGMOID || Bn.act == HP_ACT_SOFTPLUS)
+            if (!pointwise_behind(A, Bn) || Bn.res >= 0 || post_op_act(Bn) || !keeps_map(i) || !keeps_map(i + 1))
                 continue;
-            if (tensors[A.out]->C != A.cout || !hp::conv32_head_ok(A.cin, A.cout, Bn.cout) || A.in_coff + A.cin > round_up(tensors[A.in]->C, 32))
+            if (!hp::conv32_head_ok(A.cin, A.cout, Bn.cout) || A.in_coff + A.cin > round_up(tensors[A.in]->C, 32))
                 continue;
-            if (geos[i].OH != tensors[A.in]->H || geos[i].OW != tensors[A.in]->W || geos[i].pt || geos[i].pl || geos[i + 1].OH != geos[i].OH
-                || geos[i + 1].OW != geos[i].OW || geos[i + 1].pt || geos[i + 1].pl)
-                continue; // a padded 1x1 (ONNX pads) changes the map size: the fused head assumes it does not
             if ((i > 0 && (fuse_next[i - 1] == fuse_kind::sep32)) || (fuse_next[i] == fuse_kind::sep32))
                 continue;
-            bool sole = true;
-            for (size_t j = 0; j < layers.size(); ++j)
-                if (j != i + 1 && (layers[j].in == A.out || layers[j].res == A.out || (j != i && layers[j].out == A.out)))
-                    sole = false;
-            for (int o = 0; o < d->n_outputs; ++o)
-                if (d->outputs[o].tensor == A.out)
-                    sole = false;
-            if (!sole)
-                continue;
-            fuse_next[i] = fuse_kind::head32;
-            tensors[A.out]->elided = true;
+            if (private_to_pair(i))
+                fuse(i, fuse_kind::head32);
         }
     }
     return HP_OK;
@@ -682,557 +704,464 @@ int hp_engine::plan_activations()
     return HP_OK;
 }
 
+bool hp_engine::fetch_padded(int64_t off, size_t n, size_t n_pad, const char* what, size_t layer, std::vector<float>& v) const
+{
+    const float* src = off < 0 ? nullptr : blob(off, n, what, layer);
+    if (off >= 0 && !src)
+        return false;
+    v = hp::wpack::padded(src, n, n_pad);
+    return true;
+}
+
+int hp_engine::upload_padded(int64_t off, size_t n, size_t n_pad, const char* what, size_t layer, const float*& dst)
+{
+    std::vector<float> v;
+    if (!fetch_padded(off, n, n_pad, what, layer, v))
+        return HP_ERR_INVALID;
+    return upload(v, dst);
+}
+
+int hp_engine::upload_prelu(size_t layer, int n_pad, const float*& alpha)
+{
+    const hp_layer& L = layers[layer];
+    alpha = nullptr;
+    if (L.act != HP_ACT_PRELU)
+        return HP_OK;
+    HP_REQUIRE(L.alpha_off >= 0, HP_ERR_INVALID, "layer %zu: PReLU without slopes", layer);
+    return upload_padded(L.alpha_off, L.cout, n_pad, "prelu slopes", layer, alpha);
+}
+
+// The fp32 network output the layer's epilogue writes (bind_outputs), or nullptr.  With one, a tensor nobody reads is not written at all
+// (`out.p` cleared) - whole_tensor_only: unless the layer writes a slice of a wider tensor
+template <typename V>
+float* hp_engine::fused_output(size_t layer, bool whole_tensor_only, V& out)
+{
+    const hp_layer& L = layers[layer];
+    float* f32 = nullptr;
+    for (auto& o : outputs)
+        if (o.fused_layer == (int)layer)
+            f32 = o.buf->as<float>();
+    if (f32 && !tensor_is_read(L.out) && (!whole_tensor_only || tensors[L.out]->C == L.cout))
+        out.p = nullptr, tensors[L.out]->unwritten = true; // only the fp32 network output is wanted
+    return f32;
+}
+
+// The second layer of a fused fp16 pair (a separable block's pointwise layer, a head's output layer) as a 1 x 1 conv_params on an H x W map:
+// bias and slopes padded to cout_pad, activation, outputs.  q.w is the caller's.
+int hp_engine::pointwise_params(size_t layer, int H, int W, int cout_pad, hp::conv_params& q)
+{
+    const hp_layer& Pn = layers[layer];
+    HP_TRY(upload_padded(Pn.b_off, Pn.cout, cout_pad, "bias", layer, q.bias));
+    HP_TRY(upload_prelu(layer, cout_pad, q.alpha));
+    q.H = H, q.W = W, q.OH = H, q.OW = W, q.Cin = Pn.cin, q.Cout = Pn.cout, q.Cout_pad = cout_pad;
+    q.KH = q.KW = 1, q.stride = 1, q.dil = 1, q.pad_t = q.pad_l = 0;
+    q.act = Pn.act, q.act_param = Pn.act_param;
+    q.res = NO_RES, q.res_before_act = 0;
+    q.out = tensors[Pn.out]->view(Pn.out_coff);
+    q.out_f32 = fused_output(layer, false, q.out), q.dbg = nullptr;
+    HP_REQUIRE(hp::set_act(q), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv", layer, Pn.act);
+    return HP_OK;
+}
+
 int hp_engine::lower_layers()
 {
     i8_sw.assign(layers.size(), {});
     for (size_t i = 0; i < layers.size(); ++i) {
-        const hp_layer& L = layers[i];
-        if (is_f32()) {
-            HP_TRY(lower32(i));
-        } else if (L.op == HP_OP_CONV && L.in != 0 && fuse_next[i] == fuse_kind::head) {
-            HP_TRY(lower16_head_pair(i));
-            ++i; // the second convolution is part of this step
-        } else if (!(L.op == HP_OP_CONV && L.in == 0) && L.op == HP_OP_DWCONV && fuse_next[i] == fuse_kind::sep) {
-            HP_TRY(lower16_sep_pair(i));
-            ++i; // the pointwise layer is part of this step
+        if (fuse_next[i] == fuse_kind::head || fuse_next[i] == fuse_kind::sep) { // the fp16 pairs: one step, described here
+            HP_TRY(fuse_next[i] == fuse_kind::head ? lower16_head_pair(i) : lower16_sep_pair(i));
+            ++i; // the second layer is part of this step
         } else
-            HP_TRY(lower16(i));
+            HP_TRY(lower_single(i));
     }
     return HP_OK;
 }
 
-// HP_DTYPE_F32 / F32S: one fp32 launch per layer (conv_fp32.hip), or per fused pair (described at its second layer)
-int hp_engine::lower32(size_t i)
+namespace {
+inline void set_view(hp::tview& v, const tensor_info& t, int coff) { v = t.view(coff); }
+inline void set_view(hp::tview32& v, const tensor_info& t, int coff) { v = t.view32(coff); }
+} // namespace
+
+// The 3-channel first convolution, for first_conv_params and first_conv32_params alike: the fp32 weights [Cout][KH][KW][3] as the blob has
+// them (`w`), the bias, pre-processing and geometry
+template <typename P>
+int hp_engine::lower_first(size_t i, step& st, P& p, const float*& w)
 {
     const hp_layer& L = layers[i];
     const tensor_info& ti = *tensors[L.in];
-    tensor_info& to = *tensors[L.out];
     const geo& g = geos[i];
-    step st;
-    st.layer = (int)i, st.op = L.op;
+    HP_REQUIRE(L.cin == 3 && L.in_coff == 0, HP_ERR_INVALID, "layer %zu: the network input has 3 channels", i);
+    HP_REQUIRE(L.dil == 1 && L.res < 0 && L.act != HP_ACT_PRELU, HP_ERR_INVALID, "layer %zu: unsupported first-layer options", i);
+    const size_t nw = (size_t)L.cout * L.kh * L.kw * 3;
+    w = blob(L.w_off, nw, "weights", i);
+    if (!w)
+        return HP_ERR_INVALID;
+    st.first = true;
+    p.factor = factor, p.flip_rb = flip_rb;
+    for (int c = 0; c < 3; ++c)
+        p.mean[c] = mean[c], p.inv_std[c] = inv_std[c];
+    p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cout = L.cout, p.KH = L.kh, p.KW = L.kw, p.stride = L.stride;
+    p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
+    void* dw = nullptr;
+    HP_TRY(upload(w, nw * sizeof(float), &dw));
+    p.w = (const float*)dw;
+    HP_TRY(upload_padded(L.b_off, L.cout, round_up(L.cout, 8), "bias", i, p.bias));
+    set_view(p.out, *tensors[L.out], L.out_coff);
     const double opix = (double)g.OH * g.OW;
-    // ---- HP_DTYPE_F32: one fp32 launch per layer (conv_fp32.hip), weights uploaded as they are
-    st.f32 = true;
-    if ((fuse_next[i] == fuse_kind::sep32) || (fuse_next[i] == fuse_kind::head32)) // the first half of a fused pair: described at the 1 x 1 layer that follows
+    st.flops = 2.0 * opix * L.cout * L.kh * L.kw * 3;
+    st.bytes = (double)ti.H * ti.W * 3 + opix * L.cout * sizeof(*p.out.p) + nw * 4;
+    return HP_OK;
+}
+
+// Max-pool / up-sampling, for pool_params and pool32_params alike: 16-byte channel groups (8 halves, 4 floats); up-sampling does not pad
+template <typename P>
+int hp_engine::lower_pool(size_t i, step& st, P& p)
+{
+    const hp_layer& L = layers[i];
+    const tensor_info& ti = *tensors[L.in];
+    const geo& g = geos[i];
+    const int elem = sizeof(*p.in.p), align = 16 / elem;
+    const bool up = L.op == HP_OP_UPSAMPLE;
+    HP_REQUIRE(L.cin % align == 0 && L.in_coff % align == 0 && L.out_coff % align == 0 && (up || L.kh == L.kw), HP_ERR_INVALID,
+        "layer %zu: pooling / up-sampling needs %d-aligned channels and a square window", i, align);
+    set_view(p.in, ti, L.in_coff);
+    p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.k = L.kh, p.stride = L.stride;
+    p.pad_t = up ? 0 : g.pt, p.pad_l = up ? 0 : g.pl;
+    set_view(p.out, *tensors[L.out], L.out_coff);
+    st.flops = 0;
+    st.bytes = (double)ti.H * ti.W * L.cin * elem + (double)g.OH * g.OW * L.cin * elem; // (whole numbers: exact in any order)
+    return HP_OK;
+}
+
+// One layer as one step.  HP_DTYPE_F32 / F32S: an fp32 launch (conv_fp32.hip), which for a fused pair is described at its second layer
+int hp_engine::lower_single(size_t i)
+{
+    const hp_layer& L = layers[i];
+    step st;
+    st.layer = (int)i, st.op = L.op, st.f32 = is_f32();
+    if (st.f32 && (fuse_next[i] == fuse_kind::sep32 || fuse_next[i] == fuse_kind::head32)) // the first half of a fused pair: described at the 1 x 1 layer that follows
         return HP_OK;
+    const float* w = nullptr;
+    if (L.op == HP_OP_CONV && L.in == 0)
+        HP_TRY(st.f32 ? lower_first(i, st, st.fp32, w) : lower16_first(i, st));
+    else if (L.op == HP_OP_CONV)
+        HP_TRY(st.f32 ? lower32_conv(i, st) : lower16_conv(i, st));
+    else if (L.op == HP_OP_DWCONV)
+        HP_TRY(st.f32 ? lower32_dw(i, st) : lower16_dw(i, st));
+    else
+        HP_TRY(st.f32 ? lower_pool(i, st, st.pp32) : lower_pool(i, st, st.pp));
+    steps.push_back(st);
+    return HP_OK;
+}
+
+// a dense fp32 layer: conv32_kernel's rows, then the forms of the other kernels that take it
+int hp_engine::lower32_conv(size_t i, step& st)
+{
+    const hp_layer& L = layers[i];
+    const tensor_info& ti = *tensors[L.in];
+    const geo& g = geos[i];
+    const double opix = (double)g.OH * g.OW;
     const bool dw_in_front = i > 0 && (fuse_next[i - 1] == fuse_kind::sep32);
     const bool head_in_front = i > 0 && (fuse_next[i - 1] == fuse_kind::head32);
-    auto padded = [&](int64_t off, int n, int n_pad, const char* what, std::vector<float>& v) -> bool {
-        v.assign(n_pad, 0.f);
-        if (off < 0)
-            return true;
-        const float* src = blob(off, n, what, i);
-        if (!src)
-            return false;
-        std::copy(src, src + n, v.begin());
-        return true;
-    };
-    if (L.op == HP_OP_CONV && L.in == 0) {
-        HP_REQUIRE(L.cin == 3 && L.in_coff == 0, HP_ERR_INVALID, "layer %zu: the network input has 3 channels", i);
-        HP_REQUIRE(L.dil == 1 && L.res < 0 && L.act != HP_ACT_PRELU, HP_ERR_INVALID, "layer %zu: unsupported first-layer options", i);
-        const size_t nw = (size_t)L.cout * L.kh * L.kw * 3;
-        const float* w = blob(L.w_off, nw, "weights", i);
-        std::vector<float> bias;
-        if (!w || !padded(L.b_off, L.cout, round_up(L.cout, 8), "bias", bias))
-            return HP_ERR_INVALID;
-        st.first = true;
-        auto& p = st.fp32;
-        p.factor = factor, p.flip_rb = flip_rb;
-        for (int c = 0; c < 3; ++c)
-            p.mean[c] = mean[c], p.inv_std[c] = inv_std[c];
-        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cout = L.cout, p.KH = L.kh, p.KW = L.kw, p.stride = L.stride;
-        p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
-        void *dw = nullptr, *db = nullptr;
-        HP_TRY(upload(w, nw * sizeof(float), &dw));
-        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-        p.w = (const float*)dw, p.bias = (const float*)db;
-        p.out = to.view32(L.out_coff);
-        st.flops = 2.0 * opix * L.cout * L.kh * L.kw * 3;
-        st.bytes = (double)ti.H * ti.W * 3 + opix * L.cout * 4 + nw * 4;
-    } else if (L.op == HP_OP_CONV) {
-        const int cin_pad = round_up(L.cin, 16), cout_pad = round_up(L.cout, 64), taps = L.kh * L.kw;
-        // (behind a fused depthwise layer the tensor this layer "reads" is never materialised: what the kernel reads is the depthwise input)
-        const tensor_info& tsrc = (dw_in_front || head_in_front) ? *tensors[layers[i - 1].in] : ti;
-        const int src_coff = (dw_in_front || head_in_front) ? layers[i - 1].in_coff : L.in_coff;
-        HP_REQUIRE(src_coff % 4 == 0 && src_coff + (head_in_front ? layers[i - 1].cin : cin_pad) <= tsrc.cs, HP_ERR_INVALID,
-            "layer %zu: channel slice [%d,+%d) not 4-aligned / exceeds the padded stride %d", i, src_coff, cin_pad, tsrc.cs);
-        const size_t nw = (size_t)L.cout * taps * L.cin;
-        const float* w = blob(L.w_off, nw, "weights", i);
-        std::vector<float> bias, alpha;
-        if (!w || !padded(L.b_off, L.cout, cout_pad, "bias", bias))
-            return HP_ERR_INVALID;
-        auto& p = st.cp32;
-        p.alpha = nullptr;
-        if (L.act == HP_ACT_PRELU) {
-            HP_REQUIRE(L.alpha_off >= 0, HP_ERR_INVALID, "layer %zu: PReLU without slopes", i);
-            if (!padded(L.alpha_off, L.cout, cout_pad, "prelu slopes", alpha))
-                return HP_ERR_INVALID;
-            void* da = nullptr;
-            HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
-            p.alpha = (const float*)da;
-        }
-        std::vector<float> packed((size_t)taps * cout_pad * cin_pad, 0.f);
-        for (int co = 0; co < L.cout; ++co)
-            for (int t = 0; t < taps; ++t)
-                std::copy(w + ((size_t)co * taps + t) * L.cin, w + ((size_t)co * taps + t + 1) * L.cin, packed.begin() + ((size_t)t * cout_pad + co) * cin_pad);
-        void *dw = nullptr, *db = nullptr;
-        HP_TRY(upload(packed.data(), packed.size() * sizeof(float), &dw));
-        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-        p.w = (const float*)dw, p.bias = (const float*)db;
-        p.in = ti.view32(L.in_coff);
-        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cin = cin_pad, p.Cout = L.cout, p.Cout_pad = cout_pad;
-        p.KH = L.kh, p.KW = L.kw, p.stride = L.stride, p.dil = L.dil, p.pad_t = g.pt, p.pad_l = g.pl;
-        p.dw_w = nullptr, p.dw_dil = 0, p.dw_slope = 1.f, p.dw_hi = __builtin_huge_valf();
-        if (dw_in_front) { // conv32_direct_kernel's fused form: `in` is the depthwise layer's input, its weights ride along as [9][C] + [C]
-            const hp_layer& D = layers[i - 1];
-            const float* dwf = blob(D.w_off, (size_t)D.cin * 9, "weights", i - 1);
-            std::vector<float> dbias;
-            if (!dwf || !padded(D.b_off, D.cin, D.cin, "bias", dbias))
-                return HP_ERR_INVALID;
-            std::vector<float> dpack((size_t)10 * D.cin);
-            for (int c = 0; c < D.cin; ++c) {
-                for (int t = 0; t < 9; ++t)
-                    dpack[(size_t)t * D.cin + c] = dwf[(size_t)c * 9 + t];
-                dpack[(size_t)9 * D.cin + c] = dbias[c];
-            }
-            void* ddw = nullptr;
-            HP_TRY(upload(dpack.data(), dpack.size() * sizeof(float), &ddw));
-            p.dw_w = (const float*)ddw, p.dw_dil = D.dil;
-            p.dw_slope = D.act == HP_ACT_NONE ? 1.f : D.act == HP_ACT_LEAKY ? D.act_param : 0.f;
-            p.dw_hi = D.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
-            p.in = tensors[D.in]->view32(D.in_coff);
-            st.layer = (int)i - 1, st.n_layers = 2;
-        }
-        p.act = L.act, p.act_param = L.act_param;
-        p.res = hp::tview32{ nullptr, 0, 0, 0, 0 }, p.res_before_act = L.res_before_act;
-        if (L.res >= 0)
-            p.res = tensors[L.res]->view32(0);
-        p.out = to.view32(L.out_coff);
-        p.out_f32 = nullptr;
-        for (auto& o : outputs)
-            if (o.fused_layer == (int)i)
-                p.out_f32 = o.buf->as<float>();
-        if (p.out_f32 && !tensor_is_read(L.out) && tensors[L.out]->C == L.cout)
-            p.out.p = nullptr, to.unwritten = true; // only the fp32 network output is wanted
-        HP_REQUIRE(hp::set_act32(p), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv (use an output post-op)", i, L.act);
-        p.B = max_batch, p.npix = p.pick_npix = max_batch * g.OH * g.OW;
-        p.w_split = nullptr, p.w_frag = nullptr, p.w_wino = nullptr, p.w_wino3 = nullptr, p.ovf = ovf_dev, p.dbg = nullptr;
-        p.lane_epilogue = switches.lane_epilogue;
-        // The layers conv32_direct_kernel covers (square 1 x 1 / 3 x 3, stride 1, whole 32- / 64-channel chunks inside the buffer's
-        // channel stride) get their weights in fragment order as well: fp32 for HP_DTYPE_F32, fp16 (hi, lo) pairs for HP_DTYPE_F32S (every
-        // such layer); the others stay on conv32_kernel
-        // fp32 pipe, measured per layer of LW-OpenPose @ 8 x 46 x 54 (conv32_kernel -> direct, us alone | with a second stream): 3 x 3 128 -> 128
-        // 72.2 -> 58.7 | 52.6 -> 48.9; the 1 x 1 heads 512 -> 19 / 38 27.9 / 29.3 -> 26.1 / 27.4 | 18.8 / 19.6 -> 17.9 / 18.2; every wider 1 x 1
-        // layer within +-3 % or worse (64 -> 128 22.9 -> 29.0 paired, 512 -> 512 100 -> 100 alone): 1 x 1 layers wider than 64 padded outputs
-        // stay on conv32_kernel
-        // (a 3 x 3 layer the Winograd kernel will take needs no direct-form fragments: they doubled its weight bytes in HBM)
-        const bool wino_takes_it = dtype == HP_DTYPE_F32 && !dw_in_front && !switches.no_winograd32 && hp::conv32_winograd_ok(p) && !head_in_front;
-        if (dtype == HP_DTYPE_F32S || dw_in_front || (!wino_takes_it && (taps > 1 || cout_pad <= 64))) {
-            const int ck = taps == 1 ? 64 : 32, cin_s = round_up(L.cin, ck);
-            hp::conv32_params q = p;
-            q.Cin = cin_s;
-            HP_REQUIRE(!dw_in_front || (src_coff + cin_s <= tsrc.cs && hp::conv32_direct_ok(q)), HP_ERR_STATE,
-                "layer %zu: fused behind a depthwise layer but not a direct-kernel layer (engine bug)", i);
-            if (src_coff + cin_s <= tsrc.cs && hp::conv32_direct_ok(q)) {
-                std::vector<float> wide((size_t)taps * cout_pad * cin_s, 0.f);
-                for (int t = 0; t < taps; ++t)
-                    for (int co = 0; co < cout_pad; ++co)
-                        std::copy(packed.begin() + ((size_t)t * cout_pad + co) * cin_pad, packed.begin() + ((size_t)t * cout_pad + co) * cin_pad + cin_pad,
-                            wide.begin() + ((size_t)t * cout_pad + co) * cin_s);
-                void* dws = nullptr;
-                if (dtype == HP_DTYPE_F32S) {
-                    // (a BN-folded weight beyond fp16's range has no (hi, lo) split - hi would be inf - and the run-time flag only watches
-                    // activations: such an engine starts on the fp32 pipe.  ADVICE r5)
-                    for (float v : wide)
-                        if (!(std::fabs(v) <= 65504.f) && !split_off)
-                            split_off = true, ++split_fallbacks;
-                    std::vector<_Float16> ws(wide.size() * 2);
-                    hp::conv32_split_pack(wide.data(), taps, cout_pad, cin_s, ws.data());
-                    HP_TRY(upload(ws.data(), ws.size() * sizeof(_Float16), &dws));
-                    p.w_split = (const _Float16*)dws;
-                }
-                // (an HP_DTYPE_F32S engine keeps the fp32 fragments too: what it runs after a value left fp16's range)
-                std::vector<float> wf(wide.size());
-                hp::conv32_frag_pack(wide.data(), taps, cout_pad, cin_s, wf.data());
-                HP_TRY(upload(wf.data(), wf.size() * sizeof(float), &dws));
-                p.w_frag = (const float*)dws;
-                st.cin_split = cin_s;
-            }
-        }
-        st.flops = 2.0 * opix * L.cout * taps * L.cin;
-        st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cout * 4 + (double)nw * 4;
-        // HP_DTYPE_F32: 3 x 3 stride-1 layers in Winograd's F(2 x 2, 3 x 3) form - 16 MFMA products per 2 x 2 output tile and channel pair
-        // instead of 36 (conv32_winograd.hip; HP_NO_WINOGRAD32=1 is the A/B switch back to the direct kernel).  The step's `flops` stay the
-        // layer's ALGORITHMIC count (the direct form's 2 * 9 * Cin * Cout per pixel); the MFMA work issued is 16 / 36 of it (bench.py reports both).
-        if (dtype == HP_DTYPE_F32 && !dw_in_front && !switches.no_winograd32 && hp::conv32_winograd_ok(p)) {
-            std::vector<float> wu((size_t)16 * cout_pad * cin_pad);
-            hp::conv32_winograd_pack(packed.data(), cout_pad, cin_pad, wu.data());
-            void* dwu = nullptr;
-            HP_TRY(upload(wu.data(), wu.size() * sizeof(float), &dwu));
-            p.w_wino = (const float*)dwu;
-            st.wino = true;
-            st.bytes += (double)nw * 4 * (16.0 / 9 - 1);
-            // ... or, opt-in (HP_WINO_F33=1), F(3 x 3, 3 x 3): 25 products per 3 x 3 tile - 1.44 x fewer MFMA cycles, same accuracy
-            // (conv32_winograd3.hip).  Measured: it wins where its 24 x 6-pixel blocks tile the map exactly and the layer is mid-sized (256 -> 256
-            // at 32 x 24 x 24: 121 -> 87 us) and loses everywhere else - LW-OpenPose's 128 -> 128 at 8 x 46 x 54 48.6 | 28.6 us alone | paired against
-            // 45.0 (35.9 in 8 x 8 blocks) | 27.0, every layer of PifPaf's 97 / 49 / 25-row maps - because one 16-tile column per wavefront streams
-            // 3.1 x the U bytes per output pixel.  Not the default: taken by itself only on PoseProposal's exactly tiled 48 x 48 / 24 x 24
-            // stages it made configs[3] 0.6 % faster (4 353 -> 4 380 frames/s resident, two runs each) - not worth a second numeric path.
-            if (switches.wino_f33 && hp::conv32_winograd3_ok(p)) {
-                std::vector<float> wu3((size_t)25 * cout_pad * cin_pad);
-                hp::conv32_winograd3_pack(packed.data(), cout_pad, cin_pad, wu3.data());
-                void* dwu3 = nullptr;
-                HP_TRY(upload(wu3.data(), wu3.size() * sizeof(float), &dwu3));
-                p.w_wino3 = (const float*)dwu3;
-                st.bytes += (double)nw * 4 * (25.0 / 9 - 16.0 / 9);
-            }
-        }
-        if (dw_in_front) // + the depthwise taps; the tensor between the two layers costs no bytes any more
-            st.flops += 2.0 * opix * L.cin * 9, st.bytes += (double)L.cin * 10 * 4;
-        if (head_in_front) { // conv32_head_kernel: this layer's epilogue + the hidden layer in front of it
-            const hp_layer& A = layers[i - 1];
-            const size_t nwa = (size_t)A.cout * A.cin;
-            const float* wa = blob(A.w_off, nwa, "weights", i - 1);
-            std::vector<float> biasa;
-            if (!wa || !padded(A.b_off, A.cout, A.cout, "bias", biasa))
-                return HP_ERR_INVALID;
-            std::vector<float> w1f(nwa), w2p((size_t)cout_pad * L.cin, 0.f), w2f;
-            hp::conv32_frag_pack(wa, 1, A.cout, A.cin, w1f.data()); // ([1][HID][128] is the blob's own layout: HID rows of 128)
-            const int tm2 = L.cout <= 32 ? 1 : 2;
-            std::copy(w, w + nw, w2p.begin()); // [cout][HID] rows, zero rows up to 32 tm2
-            w2f.resize((size_t)32 * tm2 * L.cin);
-            hp::conv32_head_pack(w2p.data(), tm2, L.cin, w2f.data());
-            void *d1 = nullptr, *db1 = nullptr, *d2 = nullptr;
-            HP_TRY(upload(w1f.data(), w1f.size() * sizeof(float), &d1));
-            HP_TRY(upload(biasa.data(), biasa.size() * sizeof(float), &db1));
-            HP_TRY(upload(w2f.data(), w2f.size() * sizeof(float), &d2));
-            st.hh.w1_frag = (const float*)d1, st.hh.bias1 = (const float*)db1, st.hh.w2_frag = (const float*)d2, st.hh.HID = A.cout;
-            st.hh.slope1 = A.act == HP_ACT_NONE ? 1.f : A.act == HP_ACT_LEAKY ? A.act_param : 0.f;
-            st.hh.hi1 = A.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
-            p.in = tsrc.view32(src_coff);
-            st.head32 = true, st.wino = false, st.cin_split = 0;
-            st.layer = (int)i - 1, st.n_layers = 2;
-            st.flops = 2.0 * opix * ((double)A.cout * A.cin + (double)L.cout * L.cin);
-            st.bytes = (double)tsrc.H * tsrc.W * A.cin * 4 + opix * L.cout * 4 + (double)(nwa + nw) * 4;
-        }
-    } else if (L.op == HP_OP_DWCONV) {
-        HP_REQUIRE(L.kh == 3 && L.kw == 3, HP_ERR_INVALID, "layer %zu: depthwise kernels are 3x3", i);
-        HP_REQUIRE(L.cin % 4 == 0 && L.in_coff % 4 == 0 && L.out_coff % 4 == 0, HP_ERR_INVALID, "layer %zu: depthwise needs 4-aligned channels", i);
-        // (the fp16 path refuses the same set, set_act: a PReLU here would silently run as ReLU - there are no slopes in dw32_params)
-        HP_REQUIRE(L.act != HP_ACT_PRELU && L.act != HP_ACT_SIGMOID && L.act != HP_ACT_SOFTPLUS && L.res < 0, HP_ERR_INVALID,
-            "layer %zu: activation %d / a residual on a depthwise layer is not supported", i, L.act);
-        const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
-        std::vector<float> bias;
-        if (!w || !padded(L.b_off, L.cin, L.cin, "bias", bias))
-            return HP_ERR_INVALID;
-        std::vector<float> packed((size_t)9 * L.cin);
-        for (int c = 0; c < L.cin; ++c)
-            for (int t = 0; t < 9; ++t)
-                packed[(size_t)t * L.cin + c] = w[(size_t)c * 9 + t];
-        auto& p = st.dp32;
-        void *dw = nullptr, *db = nullptr;
-        HP_TRY(upload(packed.data(), packed.size() * sizeof(float), &dw));
-        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-        p.w = (const float*)dw, p.bias = (const float*)db;
-        p.in = ti.view32(L.in_coff);
-        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.stride = L.stride, p.dil = L.dil;
-        p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
-        p.out = to.view32(L.out_coff);
-        st.flops = 2.0 * opix * L.cin * 9;
-        st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cin * 4;
-    } else { // max-pool / up-sampling
-        HP_REQUIRE(L.cin % 4 == 0 && L.in_coff % 4 == 0 && L.out_coff % 4 == 0 && (L.op == HP_OP_UPSAMPLE || L.kh == L.kw), HP_ERR_INVALID,
-            "layer %zu: pooling / up-sampling needs 4-aligned channels and a square window", i);
-        auto& p = st.pp32;
-        p.in = ti.view32(L.in_coff);
-        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.k = L.kh, p.stride = L.stride;
-        p.pad_t = L.op == HP_OP_UPSAMPLE ? 0 : g.pt, p.pad_l = L.op == HP_OP_UPSAMPLE ? 0 : g.pl;
-        p.out = to.view32(L.out_coff);
-        st.flops = 0;
-        st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cin * 4;
-    }
-    steps.push_back(st);
+    const int cin_pad = round_up(L.cin, 16), cout_pad = round_up(L.cout, 64), taps = L.kh * L.kw;
+    // (behind a fused depthwise / hidden layer the tensor this layer "reads" is never materialised: what the kernel reads is THAT layer's input)
+    const hp_layer& S = (dw_in_front || head_in_front) ? layers[i - 1] : L;
+    const tensor_info& tsrc = *tensors[S.in];
+    HP_REQUIRE(S.in_coff % 4 == 0 && S.in_coff + (head_in_front ? S.cin : cin_pad) <= tsrc.cs, HP_ERR_INVALID,
+        "layer %zu: channel slice [%d,+%d) not 4-aligned / exceeds the padded stride %d", i, S.in_coff, cin_pad, tsrc.cs);
+    const size_t nw = (size_t)L.cout * taps * L.cin;
+    const float* w = blob(L.w_off, nw, "weights", i);
+    if (!w)
+        return HP_ERR_INVALID;
+    auto& p = st.cp32;
+    HP_TRY(upload_padded(L.b_off, L.cout, cout_pad, "bias", i, p.bias));
+    HP_TRY(upload_prelu(i, cout_pad, p.alpha));
+    const std::vector<float> packed = hp::wpack::dense32_rows(w, L.cout, taps, L.cin, cout_pad, cin_pad);
+    HP_TRY(upload(packed, p.w));
+    p.in = ti.view32(L.in_coff);
+    p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cin = cin_pad, p.Cout = L.cout, p.Cout_pad = cout_pad;
+    p.KH = L.kh, p.KW = L.kw, p.stride = L.stride, p.dil = L.dil, p.pad_t = g.pt, p.pad_l = g.pl;
+    p.dw_w = nullptr, p.dw_dil = 0, p.dw_slope = 1.f, p.dw_hi = __builtin_huge_valf();
+    st.flops = 2.0 * opix * L.cout * taps * L.cin;
+    st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cout * 4 + (double)nw * 4;
+    if (dw_in_front)
+        HP_TRY(lower32_dw_in_front(i, st));
+    p.act = L.act, p.act_param = L.act_param;
+    p.res = res_view32(L.res), p.res_before_act = L.res_before_act;
+    p.out = tensors[L.out]->view32(L.out_coff);
+    p.out_f32 = fused_output(i, true, p.out);
+    HP_REQUIRE(hp::set_act32(p), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv (use an output post-op)", i, L.act);
+    p.B = max_batch, p.npix = p.pick_npix = max_batch * g.OH * g.OW;
+    p.w_split = nullptr, p.w_frag = nullptr, p.w_wino = nullptr, p.w_wino3 = nullptr, p.ovf = ovf_dev, p.dbg = nullptr;
+    p.lane_epilogue = switches.lane_epilogue;
+    // the weight forms of the kernels beside conv32_kernel; each looks at the filled p and says whether it applies
+    HP_TRY(lower32_winograd_forms(i, st, packed));
+    HP_TRY(lower32_direct_forms(i, st, packed, tsrc.cs - S.in_coff));
+    if (head_in_front)
+        HP_TRY(lower32_head_in_front(i, st, w));
     return HP_OK;
 }
 
-// fp16 (and int8) engines: one layer
-int hp_engine::lower16(size_t i)
+// conv32_direct_kernel's fused form behind depthwise layer i - 1: `in` is that layer's input, its weights ride along as [9][C] + [C]
+int hp_engine::lower32_dw_in_front(size_t i, step& st)
+{
+    const hp_layer &D = layers[i - 1], &L = layers[i];
+    auto& p = st.cp32;
+    const float* dwf = blob(D.w_off, (size_t)D.cin * 9, "weights", i - 1);
+    std::vector<float> dbias;
+    if (!dwf || !fetch_padded(D.b_off, D.cin, D.cin, "bias", i - 1, dbias))
+        return HP_ERR_INVALID;
+    HP_TRY(upload(hp::wpack::dw_taps32_bias(dwf, dbias.data(), D.cin), p.dw_w));
+    p.dw_dil = D.dil;
+    p.dw_slope = D.act == HP_ACT_NONE ? 1.f : D.act == HP_ACT_LEAKY ? D.act_param : 0.f;
+    p.dw_hi = D.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
+    p.in = tensors[D.in]->view32(D.in_coff);
+    st.layer = (int)i - 1, st.n_layers = 2;
+    // + the depthwise taps; the tensor between the two layers costs no bytes any more
+    st.flops += 2.0 * ((double)geos[i].OH * geos[i].OW) * L.cin * 9, st.bytes += (double)L.cin * 10 * 4;
+    return HP_OK;
+}
+
+// HP_DTYPE_F32: 3 x 3 stride-1 layers in Winograd's F(2 x 2, 3 x 3) form - 16 MFMA products per 2 x 2 output tile and channel pair
+// instead of 36 (conv32_winograd.hip; HP_NO_WINOGRAD32=1 is the A/B switch back to the direct kernel).  The step's `flops` stay the
+// layer's ALGORITHMIC count (the direct form's 2 * 9 * Cin * Cout per pixel); the MFMA work issued is 16 / 36 of it (bench.py reports both).
+// (Never a layer with a depthwise or hidden layer fused in front: those are 1 x 1.)
+int hp_engine::lower32_winograd_forms(size_t i, step& st, const std::vector<float>& packed)
+{
+    auto& p = st.cp32;
+    if (dtype != HP_DTYPE_F32 || switches.no_winograd32 || !hp::conv32_winograd_ok(p))
+        return HP_OK;
+    const double wbytes = (double)layers[i].cout * 9 * layers[i].cin * 4; // the layer's own weights
+    std::vector<float> wu((size_t)16 * p.Cout_pad * p.Cin);
+    hp::conv32_winograd_pack(packed.data(), p.Cout_pad, p.Cin, wu.data());
+    HP_TRY(upload(wu, p.w_wino));
+    st.wino = true;
+    st.bytes += wbytes * (16.0 / 9 - 1);
+    // ... or, opt-in (HP_WINO_F33=1), F(3 x 3, 3 x 3): 25 products per 3 x 3 tile - 1.44 x fewer MFMA cycles, same accuracy
+    // (conv32_winograd3.hip).  Measured: it wins where its 24 x 6-pixel blocks tile the map exactly and the layer is mid-sized (256 -> 256
+    // at 32 x 24 x 24: 121 -> 87 us) and loses everywhere else - LW-OpenPose's 128 -> 128 at 8 x 46 x 54 48.6 | 28.6 us alone | paired against
+    // 45.0 (35.9 in 8 x 8 blocks) | 27.0, every layer of PifPaf's 97 / 49 / 25-row maps - because one 16-tile column per wavefront streams
+    // 3.1 x the U bytes per output pixel.  Not the default: taken by itself only on PoseProposal's exactly tiled 48 x 48 / 24 x 24
+    // stages it made configs[3] 0.6 % faster (4 353 -> 4 380 frames/s resident, two runs each) - not worth a second numeric path.
+    if (switches.wino_f33 && hp::conv32_winograd3_ok(p)) {
+        std::vector<float> wu3((size_t)25 * p.Cout_pad * p.Cin);
+        hp::conv32_winograd3_pack(packed.data(), p.Cout_pad, p.Cin, wu3.data());
+        HP_TRY(upload(wu3, p.w_wino3));
+        st.bytes += wbytes * (25.0 / 9 - 16.0 / 9);
+    }
+    return HP_OK;
+}
+
+// The layers conv32_direct_kernel covers (square 1 x 1 / 3 x 3, stride 1, whole 32- / 64-channel chunks inside the `room` channels the buffer
+// has from the slice's first one) get their weights in fragment order as well: fp32 for HP_DTYPE_F32, fp16 (hi, lo) pairs for HP_DTYPE_F32S
+// (every such layer); the others stay on conv32_kernel
+// fp32 pipe, measured per layer of LW-OpenPose @ 8 x 46 x 54 (conv32_kernel -> direct, us alone | with a second stream): 3 x 3 128 -> 128
+// 72.2 -> 58.7 | 52.6 -> 48.9; the 1 x 1 heads 512 -> 19 / 38 27.9 / 29.3 -> 26.1 / 27.4 | 18.8 / 19.6 -> 17.9 / 18.2; every wider 1 x 1
+// layer within +-3 % or worse (64 -> 128 22.9 -> 29.0 paired, 512 -> 512 100 -> 100 alone): 1 x 1 layers wider than 64 padded outputs
+// stay on conv32_kernel
+// (a 3 x 3 layer the Winograd kernel has taken needs no direct-form fragments: they doubled its weight bytes in HBM)
+int hp_engine::lower32_direct_forms(size_t i, step& st, const std::vector<float>& packed, int room)
+{
+    auto& p = st.cp32;
+    const int taps = p.KH * p.KW, cout_pad = p.Cout_pad;
+    const bool dw_in_front = p.dw_w != nullptr;
+    if (dtype != HP_DTYPE_F32S && !dw_in_front && (p.w_wino || (taps == 1 && cout_pad > 64)))
+        return HP_OK;
+    const int ck = taps == 1 ? 64 : 32, cin_s = round_up(layers[i].cin, ck);
+    hp::conv32_params q = p;
+    q.Cin = cin_s;
+    const bool direct = cin_s <= room && hp::conv32_direct_ok(q);
+    HP_REQUIRE(!dw_in_front || direct, HP_ERR_STATE, "layer %zu: fused behind a depthwise layer but not a direct-kernel layer (engine bug)", i);
+    if (!direct)
+        return HP_OK;
+    const std::vector<float> wide = hp::wpack::restride32(packed, taps, cout_pad, p.Cin, cin_s);
+    if (dtype == HP_DTYPE_F32S) {
+        // (a BN-folded weight beyond fp16's range has no (hi, lo) split - hi would be inf - and the run-time flag only watches
+        // activations: such an engine starts on the fp32 pipe.  ADVICE r5)
+        for (float v : wide)
+            if (!(std::fabs(v) <= 65504.f) && !split_off)
+                split_off = true, ++split_fallbacks;
+        std::vector<_Float16> ws(wide.size() * 2);
+        hp::conv32_split_pack(wide.data(), taps, cout_pad, cin_s, ws.data());
+        HP_TRY(upload(ws, p.w_split));
+    }
+    // (an HP_DTYPE_F32S engine keeps the fp32 fragments too: what it runs after a value left fp16's range)
+    std::vector<float> wf(wide.size());
+    hp::conv32_frag_pack(wide.data(), taps, cout_pad, cin_s, wf.data());
+    HP_TRY(upload(wf, p.w_frag));
+    st.cin_split = cin_s;
+    return HP_OK;
+}
+
+// conv32_head_kernel: this layer's epilogue + the hidden layer i - 1 in front of it
+int hp_engine::lower32_head_in_front(size_t i, step& st, const float* w)
+{
+    const hp_layer &A = layers[i - 1], &L = layers[i];
+    const tensor_info& tsrc = *tensors[A.in];
+    const double opix = (double)geos[i].OH * geos[i].OW;
+    auto& p = st.cp32;
+    const size_t nwa = (size_t)A.cout * A.cin, nw = (size_t)L.cout * L.cin;
+    const float* wa = blob(A.w_off, nwa, "weights", i - 1);
+    if (!wa)
+        return HP_ERR_INVALID;
+    HP_TRY(upload_padded(A.b_off, A.cout, A.cout, "bias", i - 1, st.hh.bias1));
+    std::vector<float> w1f(nwa);
+    hp::conv32_frag_pack(wa, 1, A.cout, A.cin, w1f.data()); // ([1][HID][128] is the blob's own layout: HID rows of 128)
+    const int tm2 = L.cout <= 32 ? 1 : 2;
+    const std::vector<float> w2p = hp::wpack::padded(w, nw, (size_t)p.Cout_pad * L.cin); // [cout][HID] rows, zero rows up to 32 tm2
+    std::vector<float> w2f((size_t)32 * tm2 * L.cin);
+    hp::conv32_head_pack(w2p.data(), tm2, L.cin, w2f.data());
+    HP_TRY(upload(w1f, st.hh.w1_frag));
+    HP_TRY(upload(w2f, st.hh.w2_frag));
+    st.hh.HID = A.cout;
+    st.hh.slope1 = A.act == HP_ACT_NONE ? 1.f : A.act == HP_ACT_LEAKY ? A.act_param : 0.f;
+    st.hh.hi1 = A.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
+    p.in = tsrc.view32(A.in_coff);
+    st.head32 = true, st.wino = false, st.cin_split = 0;
+    st.layer = (int)i - 1, st.n_layers = 2;
+    st.flops = 2.0 * opix * ((double)A.cout * A.cin + (double)L.cout * L.cin);
+    st.bytes = (double)tsrc.H * tsrc.W * A.cin * 4 + opix * L.cout * 4 + (double)(nwa + nw) * 4;
+    return HP_OK;
+}
+
+int hp_engine::lower32_dw(size_t i, step& st)
 {
     const hp_layer& L = layers[i];
     const tensor_info& ti = *tensors[L.in];
-    tensor_info& to = *tensors[L.out];
     const geo& g = geos[i];
-    step st;
-    st.layer = (int)i, st.op = L.op;
     const double opix = (double)g.OH * g.OW;
-    if (L.op == HP_OP_CONV && L.in == 0) {
-        HP_REQUIRE(L.cin == 3 && L.in_coff == 0, HP_ERR_INVALID, "layer %zu: the network input has 3 channels", i);
-        HP_REQUIRE(L.dil == 1 && L.res < 0 && L.act != HP_ACT_PRELU, HP_ERR_INVALID, "layer %zu: unsupported first-layer options", i);
-        const size_t nw = (size_t)L.cout * L.kh * L.kw * 3;
-        const float* w = blob(L.w_off, nw, "weights", i);
-        if (!w)
-            return HP_ERR_INVALID;
-        std::vector<float> bias(round_up(L.cout, 8), 0.f);
-        if (L.b_off >= 0) {
-            const float* b = blob(L.b_off, L.cout, "bias", i);
-            if (!b)
-                return HP_ERR_INVALID;
-            std::copy(b, b + L.cout, bias.begin());
-        }
-        st.first = true;
-        auto& p = st.fp;
-        p.factor = factor, p.flip_rb = flip_rb;
-        for (int c = 0; c < 3; ++c)
-            p.mean[c] = mean[c], p.inv_std[c] = inv_std[c];
-        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cout = L.cout, p.KH = L.kh, p.KW = L.kw, p.stride = L.stride;
-        p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
-        void* dw = nullptr;
-        void* db = nullptr;
-        HP_TRY(upload(w, nw * sizeof(float), &dw));
-        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-        p.w = (const float*)dw, p.bias = (const float*)db;
-        p.w16 = nullptr;
-        if (L.kh == L.kw && (L.kh == 3 || L.kh == 7) && L.cout % 8 == 0 && L.cout <= 64) {
-            // fragment order of first_conv_f16_kernel: kernel rows padded to ROWP (a multiple of 8), K' = KS * ROWP in steps of 16
-            const int KS = L.kh, ROWP = (KS * 3 + 7) / 8 * 8, KP = KS * ROWP, STEPS = (KP + 15) / 16, MT = L.cout <= 32 ? 1 : 2;
-            std::vector<__half> w16((size_t)MT * STEPS * 64 * 8, __float2half(0.f));
-            for (int co = 0; co < L.cout; ++co)
-                for (int ky = 0; ky < KS; ++ky)
-                    for (int r = 0; r < KS * 3; ++r) {
-                        w16[frag16(co, ky * ROWP + r, STEPS)] = __float2half(w[((size_t)co * KS + ky) * KS * 3 + r]);
-                    }
-            void* d16 = nullptr;
-            HP_TRY(upload(w16.data(), w16.size() * sizeof(__half), &d16));
-            p.w16 = (const __half*)d16;
-        }
-        p.out = to.view(L.out_coff);
-        st.flops = 2.0 * opix * L.cout * L.kh * L.kw * 3;
-        st.bytes = (double)ti.H * ti.W * 3 + opix * L.cout * 2 + nw * 4;
-    } else if (L.op == HP_OP_CONV) {
-        const int cin_pad = round_up(L.cin, 32);
-        HP_REQUIRE(L.in_coff % 8 == 0 && L.in_coff + cin_pad <= ti.cs, HP_ERR_INVALID,
-            "layer %zu: channel slice [%d,+%d) not 8-aligned / exceeds the padded stride %d", i, L.in_coff, cin_pad, ti.cs);
-        const int cout_pad = L.cout > 64 ? round_up(L.cout, 128) : 64;
-        const int taps = L.kh * L.kw;
-        const size_t nw = (size_t)L.cout * taps * L.cin;
-        const float* w = blob(L.w_off, nw, "weights", i);
-        if (!w)
-            return HP_ERR_INVALID;
-        std::vector<float> bias(cout_pad, 0.f), alpha;
-        if (L.b_off >= 0) {
-            const float* b = blob(L.b_off, L.cout, "bias", i);
-            if (!b)
-                return HP_ERR_INVALID;
-            std::copy(b, b + L.cout, bias.begin());
-        }
-        auto& p = st.cp;
-        void* dw = nullptr;
-        void* db = nullptr;
-        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-        p.w = nullptr, p.w_layout = 0, p.bias = (const float*)db, p.alpha = nullptr;
-        if (L.act == HP_ACT_PRELU) {
-            alpha.assign(cout_pad, 0.f);
-            const float* a = blob(L.alpha_off, L.cout, "prelu slopes", i);
-            if (!a)
-                return HP_ERR_INVALID;
-            std::copy(a, a + L.cout, alpha.begin());
-            void* da = nullptr;
-            HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
-            p.alpha = (const float*)da;
-        }
-        p.in = ti.view(L.in_coff);
-        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cin = cin_pad, p.Cout = L.cout, p.Cout_pad = cout_pad;
-        p.KH = L.kh, p.KW = L.kw, p.stride = L.stride, p.dil = L.dil, p.pad_t = g.pt, p.pad_l = g.pl;
-        p.act = L.act, p.act_param = L.act_param;
-        p.res = hp::tview{ nullptr, 0, 0, 0, 0 }, p.res_before_act = L.res_before_act;
-        if (L.res >= 0)
-            p.res = tensors[L.res]->view(0);
-        p.out = to.view(L.out_coff);
-        p.out_f32 = nullptr;
-        p.dbg = nullptr;
-        for (auto& o : outputs)
-            if (o.fused_layer == (int)i)
-                p.out_f32 = o.buf->as<float>();
-        if (p.out_f32 && !tensor_is_read(L.out) && tensors[L.out]->C == L.cout)
-            p.out.p = nullptr, to.unwritten = true; // only the fp32 network output is wanted
-        HP_REQUIRE(hp::set_act(p), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv (use an output post-op)", i, L.act);
-        // weights: the launcher says which packing its kernel for this shape reads
-        p.B = max_batch, p.npix = max_batch * g.OH * g.OW;
-        p.w_layout = hp::conv_weight_layout(p);
-        std::vector<__half> packed((size_t)taps * cout_pad * cin_pad, __float2half(0.f));
-        const int KQ = cin_pad / 16;
-        for (int co = 0; co < L.cout; ++co)
-            for (int t = 0; t < taps; ++t)
-                for (int ci = 0; ci < L.cin; ++ci) {
-                    const size_t at = p.w_layout == 1
-                        ? frag16(co, ci, KQ, (size_t)t * (cout_pad / 32))
-                        : ((size_t)t * cout_pad + co) * cin_pad + ci;
-                    packed[at] = __float2half(w[((size_t)co * taps + t) * L.cin + ci]);
-                }
-        HP_TRY(upload(packed.data(), packed.size() * sizeof(__half), &dw));
-        p.w = (const __half*)dw;
-        st.flops = 2.0 * opix * L.cout * taps * L.cin;
-        st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cout * 2 + (double)nw * 2;
-        if (dtype == HP_DTYPE_I8 && hp::conv_i8_ok(L.kh, L.kw, L.stride, L.dil)) {
-            // int8 weights, symmetric per output channel: s_w[c] = max |w| / 127 (1 for an all-zero channel), q_w = clamp(rint(w / s_w[c]), -127, 127)
-            // in fp32, round-half-even; rows [tap][Cout_pad][Cin_pad] as conv_i8_kernel reads them
-            std::vector<float> s_w(L.cout);
-            std::vector<int8_t> wq((size_t)taps * cout_pad * cin_pad, 0);
-            for (int co = 0; co < L.cout; ++co) {
-                const float* wc = w + (size_t)co * taps * L.cin;
-                float m = 0.f;
-                for (size_t k = 0; k < (size_t)taps * L.cin; ++k)
-                    m = std::max(m, std::fabs(wc[k]));
-                const float sc = m > 0.f ? m / 127.f : 1.f;
-                s_w[co] = sc;
-                for (int t = 0; t < taps; ++t)
-                    for (int ci = 0; ci < L.cin; ++ci)
-                        wq[((size_t)t * cout_pad + co) * cin_pad + ci] = (int8_t)std::min(std::max(std::rint(wc[(size_t)t * L.cin + ci] / sc), -127.f), 127.f);
-            }
-            void *dq = nullptr, *dd = nullptr;
-            HP_TRY(upload(wq.data(), wq.size(), &dq));
-            const std::vector<float> zeros(cout_pad, 0.f);
-            HP_TRY(upload(zeros.data(), zeros.size() * sizeof(float), &dd));
-            st.i8 = true, st.q8.w = (const int8_t*)dq, st.q8.dq = (const float*)dd, st.i8_dq = (float*)dd, st.q8.inv_a = 0.f;
-            st.q8.w_direct = nullptr;
-            if (hp::conv_i8_direct_ok(p)) { // the same q_w in conv_i8_direct_kernel's fragment order
-                std::vector<int8_t> wd(wq.size(), 0);
-                for (int t = 0; t < taps; ++t)
-                    for (int co = 0; co < cout_pad; ++co)
-                        for (int ci = 0; ci < cin_pad; ++ci)
-                            wd[hp::conv_i8_direct_index(t, co, ci, cin_pad, cout_pad)] = wq[((size_t)t * cout_pad + co) * cin_pad + ci];
-                void* dd2 = nullptr;
-                HP_TRY(upload(wd.data(), wd.size(), &dd2));
-                st.q8.w_direct = (const int8_t*)dd2;
-            }
-            i8_sw[i] = std::move(s_w);
-        }
-    } else if (L.op == HP_OP_DWCONV) {
-        HP_REQUIRE(L.kh == 3 && L.kw == 3, HP_ERR_INVALID, "layer %zu: depthwise kernels are 3x3", i);
-        HP_REQUIRE(L.cin % 8 == 0 && L.in_coff % 8 == 0 && L.out_coff % 8 == 0, HP_ERR_INVALID, "layer %zu: depthwise needs 8-aligned channels", i);
-        const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
-        if (!w)
-            return HP_ERR_INVALID;
-        std::vector<__half> packed((size_t)9 * L.cin);
-        for (int c = 0; c < L.cin; ++c)
-            for (int t = 0; t < 9; ++t)
-                packed[(size_t)t * L.cin + c] = __float2half(w[(size_t)c * 9 + t]);
-        std::vector<float> bias(L.cin, 0.f);
-        if (L.b_off >= 0) {
-            const float* b = blob(L.b_off, L.cin, "bias", i);
-            if (!b)
-                return HP_ERR_INVALID;
-            std::copy(b, b + L.cin, bias.begin());
-        }
-        auto& p = st.dp;
-        void* dw = nullptr;
-        void* db = nullptr;
-        HP_TRY(upload(packed.data(), packed.size() * sizeof(__half), &dw));
-        HP_TRY(upload(bias.data(), bias.size() * sizeof(float), &db));
-        p.w = (const __half*)dw, p.bias = (const float*)db;
-        p.in = ti.view(L.in_coff);
-        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.stride = L.stride, p.dil = L.dil;
-        p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param, p.halo = ti.P;
-        p.out = to.view(L.out_coff);
-        HP_REQUIRE(hp::dwconv3x3_ok(p), HP_ERR_INVALID, "layer %zu: no depthwise kernel for activation %d at stride %d, dilation %d", i, L.act, L.stride, L.dil);
-        st.flops = 2.0 * opix * L.cin * 9;
-        st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cin * 2;
-    } else if (L.op == HP_OP_UPSAMPLE) {
-        HP_REQUIRE(L.cin % 8 == 0 && L.in_coff % 8 == 0 && L.out_coff % 8 == 0, HP_ERR_INVALID, "layer %zu: up-sampling needs 8-aligned channels", i);
-        auto& p = st.pp;
-        p.in = ti.view(L.in_coff);
-        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.k = L.kh, p.stride = L.stride, p.pad_t = p.pad_l = 0;
-        p.out = to.view(L.out_coff);
-        st.flops = 0;
-        st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cin * 2;
-    } else { // max-pool
-        HP_REQUIRE(L.cin % 8 == 0 && L.in_coff % 8 == 0 && L.out_coff % 8 == 0 && L.kh == L.kw, HP_ERR_INVALID, "layer %zu: bad pool", i);
-        auto& p = st.pp;
-        p.in = ti.view(L.in_coff);
-        p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.k = L.kh, p.stride = L.stride;
-        p.pad_t = g.pt, p.pad_l = g.pl;
-        p.out = to.view(L.out_coff);
-        st.flops = 0;
-        st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cin * 2;
-    }
-    steps.push_back(st);
+    HP_REQUIRE(L.kh == 3 && L.kw == 3, HP_ERR_INVALID, "layer %zu: depthwise kernels are 3x3", i);
+    HP_REQUIRE(L.cin % 4 == 0 && L.in_coff % 4 == 0 && L.out_coff % 4 == 0, HP_ERR_INVALID, "layer %zu: depthwise needs 4-aligned channels", i);
+    // (the fp16 path refuses the same set, set_act: a PReLU here would silently run as ReLU - there are no slopes in dw32_params)
+    HP_REQUIRE(L.act != HP_ACT_PRELU && L.act != HP_ACT_SIGMOID && L.act != HP_ACT_SOFTPLUS && L.res < 0, HP_ERR_INVALID,
+        "layer %zu: activation %d / a residual on a depthwise layer is not supported", i, L.act);
+    const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
+    if (!w)
+        return HP_ERR_INVALID;
+    auto& p = st.dp32;
+    HP_TRY(upload(hp::wpack::dw_taps32(w, L.cin), p.w));
+    HP_TRY(upload_padded(L.b_off, L.cin, L.cin, "bias", i, p.bias));
+    p.in = ti.view32(L.in_coff);
+    p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.stride = L.stride, p.dil = L.dil;
+    p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
+    p.out = tensors[L.out]->view32(L.out_coff);
+    st.flops = 2.0 * opix * L.cin * 9;
+    st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cin * 4;
+    return HP_OK;
+}
+
+// ---- fp16 (and int8) engines
+int hp_engine::lower16_first(size_t i, step& st)
+{
+    const hp_layer& L = layers[i];
+    auto& p = st.fp;
+    const float* w = nullptr;
+    HP_TRY(lower_first(i, st, p, w));
+    p.w16 = nullptr;
+    if (L.kh == L.kw && (L.kh == 3 || L.kh == 7) && L.cout % 8 == 0 && L.cout <= 64) // the shapes first_conv_f16_kernel has: fp16 fragments beside the fp32 weights
+        HP_TRY(upload(hp::wpack::first_conv_frag16(w, L.cout, L.kh), p.w16));
+    return HP_OK;
+}
+
+int hp_engine::lower16_conv(size_t i, step& st)
+{
+    const hp_layer& L = layers[i];
+    const tensor_info& ti = *tensors[L.in];
+    const geo& g = geos[i];
+    const double opix = (double)g.OH * g.OW;
+    const int cin_pad = round_up(L.cin, 32);
+    HP_REQUIRE(L.in_coff % 8 == 0 && L.in_coff + cin_pad <= ti.cs, HP_ERR_INVALID,
+        "layer %zu: channel slice [%d,+%d) not 8-aligned / exceeds the padded stride %d", i, L.in_coff, cin_pad, ti.cs);
+    const int cout_pad = L.cout > 64 ? round_up(L.cout, 128) : 64;
+    const int taps = L.kh * L.kw;
+    const size_t nw = (size_t)L.cout * taps * L.cin;
+    const float* w = blob(L.w_off, nw, "weights", i);
+    if (!w)
+        return HP_ERR_INVALID;
+    auto& p = st.cp;
+    HP_TRY(upload_padded(L.b_off, L.cout, cout_pad, "bias", i, p.bias));
+    HP_TRY(upload_prelu(i, cout_pad, p.alpha));
+    p.in = ti.view(L.in_coff);
+    p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cin = cin_pad, p.Cout = L.cout, p.Cout_pad = cout_pad;
+    p.KH = L.kh, p.KW = L.kw, p.stride = L.stride, p.dil = L.dil, p.pad_t = g.pt, p.pad_l = g.pl;
+    p.act = L.act, p.act_param = L.act_param;
+    p.res = res_view(L.res), p.res_before_act = L.res_before_act;
+    p.out = tensors[L.out]->view(L.out_coff);
+    p.out_f32 = fused_output(i, true, p.out);
+    p.dbg = nullptr;
+    HP_REQUIRE(hp::set_act(p), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv (use an output post-op)", i, L.act);
+    // weights: the launcher says which packing its kernel for this shape reads
+    p.B = max_batch, p.npix = max_batch * g.OH * g.OW;
+    p.w_layout = hp::conv_weight_layout(p);
+    HP_TRY(upload(hp::wpack::dense16(w, L.cout, taps, L.cin, cout_pad, cin_pad, p.w_layout), p.w));
+    st.flops = 2.0 * opix * L.cout * taps * L.cin;
+    st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cout * 2 + (double)nw * 2;
+    if (dtype == HP_DTYPE_I8 && hp::conv_i8_ok(L.kh, L.kw, L.stride, L.dil))
+        HP_TRY(lower16_i8(i, st, w));
+    return HP_OK;
+}
+
+// HP_DTYPE_I8: the int8 launch beside the layer's fp16 one (st.cp): q_w, its per-channel scales, dq (zeros until apply_int8_scales)
+int hp_engine::lower16_i8(size_t i, step& st, const float* w)
+{
+    const hp_layer& L = layers[i];
+    const auto& p = st.cp;
+    const int taps = L.kh * L.kw;
+    hp::wpack::i8_rows r = hp::wpack::quantize_rows(w, L.cout, taps, L.cin, p.Cout_pad, p.Cin);
+    HP_TRY(upload(r.q, st.q8.w));
+    HP_TRY(upload(std::vector<float>(p.Cout_pad, 0.f), st.q8.dq));
+    st.i8 = true, st.i8_dq = const_cast<float*>(st.q8.dq), st.q8.inv_a = 0.f;
+    st.q8.w_direct = nullptr;
+    if (hp::conv_i8_direct_ok(p)) // the same q_w in conv_i8_direct_kernel's fragment order
+        HP_TRY(upload(hp::wpack::i8_direct(r.q, taps, p.Cout_pad, p.Cin), st.q8.w_direct));
+    i8_sw[i] = std::move(r.s_w);
+    return HP_OK;
+}
+
+int hp_engine::lower16_dw(size_t i, step& st)
+{
+    const hp_layer& L = layers[i];
+    const tensor_info& ti = *tensors[L.in];
+    const geo& g = geos[i];
+    const double opix = (double)g.OH * g.OW;
+    HP_REQUIRE(L.kh == 3 && L.kw == 3, HP_ERR_INVALID, "layer %zu: depthwise kernels are 3x3", i);
+    HP_REQUIRE(L.cin % 8 == 0 && L.in_coff % 8 == 0 && L.out_coff % 8 == 0, HP_ERR_INVALID, "layer %zu: depthwise needs 8-aligned channels", i);
+    const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
+    if (!w)
+        return HP_ERR_INVALID;
+    auto& p = st.dp;
+    HP_TRY(upload(hp::wpack::dw_taps16(w, L.cin), p.w));
+    HP_TRY(upload_padded(L.b_off, L.cin, L.cin, "bias", i, p.bias));
+    p.in = ti.view(L.in_coff);
+    p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.stride = L.stride, p.dil = L.dil;
+    p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param, p.halo = ti.P;
+    p.out = tensors[L.out]->view(L.out_coff);
+    HP_REQUIRE(hp::dwconv3x3_ok(p), HP_ERR_INVALID, "layer %zu: no depthwise kernel for activation %d at stride %d, dilation %d", i, L.act, L.stride, L.dil);
+    st.flops = 2.0 * opix * L.cin * 9;
+    st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * L.cin * 2;
     return HP_OK;
 }
 
 // fp16: a two-layer head (1x1 K1 -> 512 -> 1x1 <= 64) as one mlp_head_kernel launch, layers i and i + 1
 int hp_engine::lower16_head_pair(size_t i)
 {
-    const hp_layer& L = layers[i];
+    const hp_layer &L = layers[i], &Pn = layers[i + 1];
     const tensor_info& ti = *tensors[L.in];
-    const geo& g = geos[i];
-    step st;
-    st.layer = (int)i, st.op = L.op;
-    const double opix = (double)g.OH * g.OW;
-    const hp_layer& Pn = layers[i + 1];
-    tensor_info& tp = *tensors[Pn.out];
-    const int K1 = L.cin, KQ1 = K1 / 16, HID = L.cout;
+    const double opix = (double)geos[i].OH * geos[i].OW;
+    const int K1 = L.cin, HID = L.cout;
     const float* w1f = blob(L.w_off, (size_t)HID * K1, "weights", i);
     const float* w2f = blob(Pn.w_off, (size_t)Pn.cout * HID, "weights", i + 1);
     if (!w1f || !w2f)
         return HP_ERR_INVALID;
-    std::vector<__half> w1p((size_t)HID * K1), w2p((size_t)64 * HID, __float2half(0.f));
-    for (int m = 0; m < HID; ++m)
-        for (int k = 0; k < K1; ++k)
-            w1p[frag16(m, k, KQ1)] = __float2half(w1f[(size_t)m * K1 + k]);
-    for (int m = 0; m < Pn.cout; ++m)
-        for (int c = 0; c < HID; ++c) {
-            const int wv = c / 128, ii = (c % 128) / 32, r32 = c % 32;
-            const int hh = (r32 >> 2) & 1, r = (r32 & 3) + 4 * (r32 >> 3), ss = r >> 3, ee = r & 7;
-            w2p[((((size_t)(m / 32) * 32 + 8 * wv + 2 * ii + ss) * 64) + hh * 32 + m % 32) * 8 + ee] = __float2half(w2f[(size_t)m * HID + c]);
-        }
-    std::vector<float> b1(HID, 0.f), b2(64, 0.f), alpha;
-    if (L.b_off >= 0) {
-        const float* bb = blob(L.b_off, HID, "bias", i);
-        if (!bb)
-            return HP_ERR_INVALID;
-        std::copy(bb, bb + HID, b1.begin());
-    }
-    if (Pn.b_off >= 0) {
-        const float* bb = blob(Pn.b_off, Pn.cout, "bias", i + 1);
-        if (!bb)
-            return HP_ERR_INVALID;
-        std::copy(bb, bb + Pn.cout, b2.begin());
-    }
-    st.op = OP_MLPHEAD, st.n_layers = 2; // (covers layers i and i + 1: the passes below must see every layer a step touches)
+    step st;
+    st.layer = (int)i, st.op = OP_MLPHEAD, st.n_layers = 2; // (covers layers i and i + 1: the passes below must see every layer a step touches)
     auto& p = st.hp_;
-    void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-    HP_TRY(upload(w1p.data(), w1p.size() * sizeof(__half), &d0));
-    HP_TRY(upload(b1.data(), b1.size() * sizeof(float), &d1));
-    HP_TRY(upload(w2p.data(), w2p.size() * sizeof(__half), &d2));
-    HP_TRY(upload(b2.data(), b2.size() * sizeof(float), &d3));
+    HP_TRY(upload(hp::wpack::dense16(w1f, HID, 1, K1, HID, K1, 1), p.w1));
+    HP_TRY(upload_padded(L.b_off, HID, HID, "bias", i, p.b1));
+    HP_TRY(upload(hp::wpack::head_w2(w2f, Pn.cout, HID), p.w2));
     p.in = ti.view(L.in_coff);
     p.H = ti.H, p.W = ti.W, p.K1 = K1;
-    p.w1 = (const __half*)d0, p.b1 = (const float*)d1, p.w2 = (const __half*)d2;
     p.hi1 = L.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
-    auto& q = p.pw;
-    q.w = nullptr, q.w_layout = 0, q.bias = (const float*)d3, q.alpha = nullptr;
-    if (Pn.act == HP_ACT_PRELU) {
-        alpha.assign(64, 0.f);
-        const float* a = blob(Pn.alpha_off, Pn.cout, "prelu slopes", i + 1);
-        if (!a)
-            return HP_ERR_INVALID;
-        std::copy(a, a + Pn.cout, alpha.begin());
-        void* da = nullptr;
-        HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
-        q.alpha = (const float*)da;
-    }
-    q.H = ti.H, q.W = ti.W, q.OH = ti.H, q.OW = ti.W, q.Cin = HID, q.Cout = Pn.cout, q.Cout_pad = 64;
-    q.KH = q.KW = 1, q.stride = 1, q.dil = 1, q.pad_t = q.pad_l = 0;
-    q.act = Pn.act, q.act_param = Pn.act_param;
-    q.res = hp::tview{ nullptr, 0, 0, 0, 0 }, q.res_before_act = 0;
-    q.out = tp.view(Pn.out_coff);
-    q.out_f32 = nullptr, q.dbg = nullptr;
-    for (auto& o : outputs)
-        if (o.fused_layer == (int)i + 1)
-            q.out_f32 = o.buf->as<float>();
-    if (q.out_f32 && !tensor_is_read(Pn.out))
-        q.out.p = nullptr, tp.unwritten = true; // only the fp32 network output is wanted
-    HP_REQUIRE(hp::set_act(q), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv", i + 1, Pn.act);
+    HP_TRY(pointwise_params(i + 1, ti.H, ti.W, 64, p.pw)); // (pw.w stays null: the kernel reads w2)
     st.flops = 2.0 * opix * HID * K1 + 2.0 * opix * Pn.cout * HID;
     st.bytes = (double)ti.H * ti.W * K1 * 2 + opix * Pn.cout * 2 + ((double)HID * K1 + (double)Pn.cout * HID) * 2;
     steps.push_back(st);
@@ -1242,83 +1171,34 @@ int hp_engine::lower16_head_pair(size_t i)
 // fp16: a separable block (depthwise 3x3 + 1x1) as one sepconv launch, layers i and i + 1
 int hp_engine::lower16_sep_pair(size_t i)
 {
-    const hp_layer& L = layers[i];
+    const hp_layer &L = layers[i], &Pn = layers[i + 1];
     const tensor_info& ti = *tensors[L.in];
     const geo& g = geos[i];
-    step st;
-    st.layer = (int)i, st.op = L.op;
     const double opix = (double)g.OH * g.OW;
-    const hp_layer& Pn = layers[i + 1];
-    tensor_info& tp = *tensors[Pn.out];
-    const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
-    if (!w)
-        return HP_ERR_INVALID;
-    std::vector<__half> dpacked((size_t)9 * L.cin);
-    for (int c = 0; c < L.cin; ++c)
-        for (int t = 0; t < 9; ++t)
-            dpacked[(size_t)t * L.cin + c] = __float2half(w[(size_t)c * 9 + t]);
-    std::vector<float> dbias(L.cin, 0.f);
-    if (L.b_off >= 0) {
-        const float* b = blob(L.b_off, L.cin, "bias", i);
-        if (!b)
-            return HP_ERR_INVALID;
-        std::copy(b, b + L.cin, dbias.begin());
-    }
-    const int C = L.cin, KQ = C / 16, cout_pad = round_up(Pn.cout, 128);
+    const int C = L.cin, cout_pad = round_up(Pn.cout, 128);
+    const float* w = blob(L.w_off, (size_t)C * 9, "weights", i);
     const float* pwf = blob(Pn.w_off, (size_t)Pn.cout * C, "weights", i + 1);
-    if (!pwf)
+    if (!w || !pwf)
         return HP_ERR_INVALID;
-    // MFMA-fragment order: [32-row tile][k16 step][lane = (k % 16 / 8) * 32 + m % 32][k % 8]
-    std::vector<__half> ppacked((size_t)cout_pad * C, __float2half(0.f));
-    for (int m = 0; m < Pn.cout; ++m)
-        for (int k = 0; k < C; ++k)
-            ppacked[frag16(m, k, KQ)] = __float2half(pwf[(size_t)m * C + k]);
-    std::vector<float> pbias(cout_pad, 0.f), alpha;
-    if (Pn.b_off >= 0) {
-        const float* b = blob(Pn.b_off, Pn.cout, "bias", i + 1);
-        if (!b)
-            return HP_ERR_INVALID;
-        std::copy(b, b + Pn.cout, pbias.begin());
-    }
-    st.op = OP_SEPCONV, st.n_layers = 2;
+    step st;
+    st.layer = (int)i, st.op = OP_SEPCONV, st.n_layers = 2;
     auto& p = st.sp;
-    void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-    HP_TRY(upload(dpacked.data(), dpacked.size() * sizeof(__half), &d0));
-    HP_TRY(upload(dbias.data(), dbias.size() * sizeof(float), &d1));
-    HP_TRY(upload(ppacked.data(), ppacked.size() * sizeof(__half), &d2));
-    HP_TRY(upload(pbias.data(), pbias.size() * sizeof(float), &d3));
+    HP_TRY(upload(hp::wpack::dw_taps16(w, C), p.dw_w));
+    HP_TRY(upload_padded(L.b_off, C, C, "bias", i, p.dw_bias));
+    HP_TRY(upload(hp::wpack::dense16(pwf, Pn.cout, 1, C, cout_pad, C, 1), p.pw.w));
     p.in = ti.view(L.in_coff);
     p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = C, p.stride = L.stride, p.dil = L.dil;
     p.pad_t = g.pt, p.pad_l = g.pl, p.halo = ti.P;
-    p.dw_w = (const __half*)d0, p.dw_bias = (const float*)d1;
     {
         hp::conv_params tmp{};
         tmp.act = L.act, tmp.act_param = L.act_param, tmp.alpha = nullptr;
         HP_REQUIRE(hp::set_act(tmp), HP_ERR_INVALID, "layer %zu: unsupported depthwise activation %d", i, L.act);
         p.dw_slope = tmp.act_slope, p.dw_hi = tmp.act_hi;
     }
-    auto& q = p.pw;
-    q.w = (const __half*)d2, q.bias = (const float*)d3, q.alpha = nullptr;
-    if (Pn.act == HP_ACT_PRELU) {
-        alpha.assign(cout_pad, 0.f);
-        const float* a = blob(Pn.alpha_off, Pn.cout, "prelu slopes", i + 1);
-        if (!a)
-            return HP_ERR_INVALID;
-        std::copy(a, a + Pn.cout, alpha.begin());
-        void* da = nullptr;
-        HP_TRY(upload(alpha.data(), alpha.size() * sizeof(float), &da));
-        q.alpha = (const float*)da;
-    }
-    q.H = g.OH, q.W = g.OW, q.OH = g.OH, q.OW = g.OW, q.Cin = C, q.Cout = Pn.cout, q.Cout_pad = cout_pad;
-    q.KH = q.KW = 1, q.stride = 1, q.dil = 1, q.pad_t = q.pad_l = 0;
-    q.act = Pn.act, q.act_param = Pn.act_param;
-    q.res = hp::tview{ nullptr, 0, 0, 0, 0 }, q.res_before_act = 0;
-    q.out = tp.view(Pn.out_coff);
-    q.out_f32 = nullptr, q.dbg = nullptr;
-    HP_REQUIRE(hp::set_act(q), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv", i + 1, Pn.act);
+    HP_TRY(pointwise_params(i + 1, g.OH, g.OW, cout_pad, p.pw));
     HP_REQUIRE(hp::sepconv_variant(p) != 0, HP_ERR_INVALID, "layer %zu: no fused separable kernel for this block (set HP_NO_FUSE=1)", i);
-    st.flops = 2.0 * opix * L.cin * 9 + 2.0 * opix * Pn.cout * C;
-    st.bytes = (double)ti.H * ti.W * L.cin * 2 + opix * Pn.cout * 2 + (double)Pn.cout * C * 2;
+    st.flops = 2.0 * opix * C * 9 + 2.0 * opix * Pn.cout * C;
+    st.bytes = (double)ti.H * ti.W * C * 2 + opix * Pn.cout * 2 + (double)Pn.cout * C * 2;
     steps.push_back(st);
     return HP_OK;
 }
@@ -1357,20 +1237,6 @@ int hp_engine::fuse_chains()
     // steps [1x1 ->] 3x3 -> 3x3 whose intermediates nobody else reads run as ONE launch with the intermediates in LDS
     // (conv_chain.hip).  HP_NO_CHAIN=1 keeps one launch per layer (A/B measurements, and hp_engine_debug_tensor on an intermediate).
     if (!switches.no_chain && !no_fuse && !f32) {
-        auto plain_conv = [&](const step& st) { return st.op == HP_OP_CONV && !st.first && st.n_layers == 1; };
-        // the tensor a step writes is read only by the given layers (as input or residual) and is no network output
-        auto only_read_by = [&](int tensor, int la, int lb) {
-            for (size_t j = 0; j < layers.size(); ++j)
-                if ((int)j != la && (int)j != lb && (layers[j].in == tensor || layers[j].res == tensor))
-                    return false;
-            for (const auto& o : outputs)
-                if (o.tensor == tensor)
-                    return false;
-            int writers = 0;
-            for (const auto& L2 : layers)
-                writers += L2.out == tensor;
-            return writers == 1;
-        };
         for (size_t k = 0; k + 1 < steps.size(); ++k) {
             if (!plain_conv(steps[k]) || !plain_conv(steps[k + 1]))
                 continue;
@@ -1381,7 +1247,7 @@ int hp_engine::fuse_chains()
                 const int l0 = steps[k].layer, l1 = steps[k + 1].layer, l2 = steps[k + 2].layer;
                 const hp_layer &A = layers[l0], &Bn = layers[l1], &Cn = layers[l2];
                 if (Bn.in == A.out && Bn.in_coff == A.out_coff && Cn.in == Bn.out && Cn.in_coff == Bn.out_coff && A.res < 0 && Bn.res < 0
-                    && (Cn.res < 0 || Cn.res == A.out) && A.out_coff == 0 && only_read_by(A.out, l1, l2) && only_read_by(Bn.out, l2, l2)) {
+                    && (Cn.res < 0 || Cn.res == A.out) && A.out_coff == 0 && private_to(A.out, l1, l2) && private_to(Bn.out, l2, l2)) {
                     ch.c0 = steps[k].cp, ch.c1 = steps[k + 1].cp, ch.c2 = steps[k + 2].cp;
                     ch.has_c0 = 1, ch.res_mode = Cn.res >= 0 ? 3 : 0;
                     n = 3;
@@ -1390,7 +1256,7 @@ int hp_engine::fuse_chains()
             if (!n && steps[k].cp.KH == 3) {
                 const int l1 = steps[k].layer, l2 = steps[k + 1].layer;
                 const hp_layer &Bn = layers[l1], &Cn = layers[l2];
-                if (Cn.in == Bn.out && Cn.in_coff == Bn.out_coff && !(Bn.res >= 0 && Cn.res >= 0) && only_read_by(Bn.out, l2, l2)
+                if (Cn.in == Bn.out && Cn.in_coff == Bn.out_coff && !(Bn.res >= 0 && Cn.res >= 0) && private_to(Bn.out, l2, l2)
                     && Cn.res != Bn.out) {
                     ch.c1 = steps[k].cp, ch.c2 = steps[k + 1].cp;
                     ch.has_c0 = 0, ch.res_mode = Bn.res >= 0 ? 1 : Cn.res >= 0 ? 2 : 0;
@@ -1420,16 +1286,6 @@ int hp_engine::fuse_bottlenecks()
     // (conv_bottleneck.hip).  The reduction may sit one or two steps further down the schedule (behind the next stage's projection
     // shortcut, which reads the same tensor): it has no other input, so it can run here.  HP_NO_BNECK=1 keeps one launch per layer.
     if (!switches.no_bneck && !no_fuse && !f32) {
-        auto plain_conv = [&](const step& st) { return st.op == HP_OP_CONV && !st.first && st.n_layers == 1; };
-        auto readers_other_than = [&](int tensor, int la) { // some layer other than la reads the tensor, or it is a network output
-            for (size_t j = 0; j < layers.size(); ++j)
-                if ((int)j != la && (layers[j].in == tensor || layers[j].res == tensor))
-                    return true;
-            for (const auto& o : outputs)
-                if (o.tensor == tensor)
-                    return true;
-            return false;
-        };
         for (size_t k = 0; k < steps.size(); ++k) {
             if (!plain_conv(steps[k]))
                 continue;
@@ -1437,10 +1293,7 @@ int hp_engine::fuse_bottlenecks()
             size_t ke = k; // the expansion's step
             if (steps[k].cp.KH == 3 && k + 1 < steps.size() && plain_conv(steps[k + 1]) && steps[k + 1].cp.KH == 1) {
                 const hp_layer &A = layers[steps[k].layer], &E = layers[steps[k + 1].layer];
-                int writers = 0;
-                for (const auto& L2 : layers)
-                    writers += L2.out == A.out;
-                if (E.in == A.out && E.in_coff == A.out_coff && A.res < 0 && writers == 1 && !readers_other_than(A.out, steps[k + 1].layer)) {
+                if (E.in == A.out && E.in_coff == A.out_coff && A.res < 0 && private_to(A.out, steps[k + 1].layer, steps[k + 1].layer)) {
                     bn.c3 = steps[k].cp, bn.has_c3 = 1;
                     ke = k + 1;
                 }
@@ -1470,34 +1323,29 @@ int hp_engine::fuse_bottlenecks()
             // computed inside the launch instead of written by one launch and read by the next
             size_t kp = steps.size();
             if (E.res >= 0 && bn.ce.Cin == 64 && E.res_before_act) {
-                int writers = 0;
-                for (const auto& L2 : layers)
-                    writers += L2.out == E.res;
+                const bool res_private = private_to(E.res, steps[ke].layer, steps[ke].layer);
                 for (size_t j = 0; j < k && kp == steps.size(); ++j) {
                     if (!plain_conv(steps[j]) || layers[steps[j].layer].out != E.res)
                         continue;
                     const hp_layer& P = layers[steps[j].layer];
-                    if (steps[j].cp.KH == 1 && steps[j].cp.stride == 1 && P.res < 0 && P.out_coff == 0 && P.act == HP_ACT_NONE && writers == 1
-                        && !readers_other_than(E.res, steps[ke].layer))
+                    if (steps[j].cp.KH == 1 && steps[j].cp.stride == 1 && P.res < 0 && P.out_coff == 0 && P.act == HP_ACT_NONE && res_private)
                         kp = j;
                 }
             }
             const hp::tview res_view = bn.ce.res;
             if (kp < steps.size())
-                bn.cp = steps[kp].cp, bn.has_cp = 1, bn.ce.res = hp::tview{ nullptr, 0, 0, 0, 0 };
+                bn.cp = steps[kp].cp, bn.has_cp = 1, bn.ce.res = NO_RES;
             // ... and the block's own reduction reads the same block input and feeds only this 3x3: computed on the 3x3's halo tile
             size_t k0 = steps.size();
             if (kp < steps.size() && bn.has_c3) {
                 const hp_layer &A3 = layers[steps[k].layer], &P = layers[steps[kp].layer];
-                int writers = 0;
-                for (const auto& L2 : layers)
-                    writers += L2.out == A3.in;
+                const bool in_private = private_to(A3.in, steps[k].layer, steps[k].layer);
                 for (size_t j = 0; j < k && k0 == steps.size(); ++j) {
                     if (!plain_conv(steps[j]) || layers[steps[j].layer].out != A3.in)
                         continue;
                     const hp_layer& R = layers[steps[j].layer];
                     if (steps[j].cp.KH == 1 && steps[j].cp.stride == 1 && R.res < 0 && R.out_coff == 0 && A3.in_coff == 0 && R.in == P.in && R.in_coff == P.in_coff
-                        && writers == 1 && !readers_other_than(A3.in, steps[k].layer))
+                        && in_private)
                         k0 = j;
                 }
                 if (k0 < steps.size())
@@ -1525,7 +1373,7 @@ int hp_engine::fuse_bottlenecks()
                     if (((drop & 1) && !had_cr) || ((drop & 2) && !had_c0) || ((drop & 4) && !had_cp))
                         continue;
                     bn.has_cr = had_cr && !(drop & 1), bn.has_cp = had_cp && !(drop & 4), bn.has_c0 = had_c0 && !(drop & 2) && bn.has_cp;
-                    bn.ce.res = bn.has_cp ? hp::tview{ nullptr, 0, 0, 0, 0 } : res_view;
+                    bn.ce.res = bn.has_cp ? NO_RES : res_view;
                     ok = hp::bottleneck_variant(bn) != 0;
                 }
                 if (!ok)
@@ -1542,20 +1390,11 @@ int hp_engine::fuse_bottlenecks()
                 if (had == 1)
                     return HP_OK;
                 const hp_layer& L = layers[layer];
-                const int taps = L.kh * L.kw, KQ = c.Cin / 16;
+                const int taps = L.kh * L.kw;
                 const float* w = blob(L.w_off, (size_t)L.cout * taps * L.cin, "weights", (size_t)layer);
                 if (!w)
                     return HP_ERR_INVALID;
-                std::vector<__half> packed((size_t)taps * c.Cout_pad * c.Cin, __float2half(0.f));
-                for (int co = 0; co < L.cout; ++co)
-                    for (int t = 0; t < taps; ++t)
-                        for (int ci = 0; ci < L.cin; ++ci)
-                            packed[frag16(co, ci, KQ, (size_t)t * (c.Cout_pad / 32))]
-                                = __float2half(w[((size_t)co * taps + t) * L.cin + ci]);
-                void* dw = nullptr;
-                HP_TRY(upload(packed.data(), packed.size() * sizeof(__half), &dw));
-                c.w = (const __half*)dw;
-                return HP_OK;
+                return upload(hp::wpack::dense16(w, L.cout, taps, L.cin, c.Cout_pad, c.Cin, 1), c.w);
             };
             if (bn.has_c3)
                 HP_TRY(repack(bn.c3, lay3, steps[k].layer));
@@ -1609,17 +1448,9 @@ int hp_engine::fuse_sep_pairs()
             const hp_layer &Pa = layers[a.layer + 1], &Db = layers[b.layer];
             if (Db.in != Pa.out || Db.in_coff != Pa.out_coff)
                 continue;
-            bool private_tensor = true; // nobody but block b's depthwise layer reads it and it is no network output
-            for (size_t j = 0; j < layers.size(); ++j)
-                if ((int)j != b.layer && (layers[j].in == Pa.out || layers[j].res == Pa.out))
-                    private_tensor = false;
-            for (const auto& o : outputs)
-                private_tensor = private_tensor && o.tensor != Pa.out;
-            int writers = 0;
-            for (const auto& L2 : layers)
-                writers += L2.out == Pa.out;
             hp::seppair_params pp{ a.sp, b.sp };
-            if (!private_tensor || writers != 1 || !hp::seppair_variant(pp))
+            // (nobody but block b's depthwise layer reads the tensor in between, block a alone writes it, and it is no network output)
+            if (!private_to(Pa.out, b.layer, b.layer) || !hp::seppair_variant(pp))
                 continue;
             a.sp2 = b.sp, a.sep_pair = true, a.n_layers += b.n_layers;
             a.flops += b.flops;
