@@ -99,7 +99,7 @@ SYMBOLS = [
     "hp_ppn_create", "hp_ppn_destroy", "hp_ppn_set_thresholds", "hp_ppn_process_batch", "hp_ppn_stream", "hp_ppn_enqueue", "hp_ppn_collect", "hp_ppn_decode_flags",
     "hp_engine_create", "hp_engine_destroy", "hp_engine_max_batch", "hp_engine_describe", "hp_engine_input_size", "hp_engine_infer_u8",
     "hp_engine_infer_f32", "hp_engine_synchronize", "hp_engine_stream", "hp_engine_set_graph", "hp_engine_set_concurrency", "hp_engine_arena_info", "hp_debug_first_conv_verify", "hp_engine_concurrency", "hp_engine_num_outputs",
-    "hp_engine_output", "hp_engine_output_to_host", "hp_engine_debug_tensor", "hp_engine_profile", "hp_engine_profile_sequence", "hp_engine_profile_pair", "hp_model_build", "hp_model_from_onnx", "hp_model_from_onnx_file", "hp_model_weights",
+    "hp_engine_output", "hp_engine_output_to_host", "hp_engine_debug_tensor", "hp_engine_debug_raw_tensor", "hp_engine_profile", "hp_engine_profile_sequence", "hp_engine_profile_pair", "hp_model_build", "hp_model_from_onnx", "hp_model_from_onnx_file", "hp_model_weights",
     "hp_model_input_size",
     "hp_model_destroy", "hp_model_archs", "hp_model_layers", "hp_model_outputs", "hp_model_num_weights",
     "hp_model_preproc", "hp_model_flops_per_frame", "hp_model_init_weights", "hp_engine_create_from_model", "hp_engine_create_from_model_dtype", "hp_engine_dtype", "hp_engine_calibrate_u8", "hp_engine_int8_scales", "hp_engine_set_int8_scales", "hp_engine_split_fallbacks", "hp_engine_device_bytes", "hp_engine_save", "hp_engine_load", "hp_pipeline_create", "hp_pipeline_create_ex", "hp_pipeline_destroy", "hp_pipeline_submit", "hp_pipeline_collect", "hp_pipeline_in_flight",
@@ -119,6 +119,8 @@ def lib() -> C.CDLL:
         L.hp_version.restype = C.c_char_p
         L.hp_yuv_packed_bytes.restype = C.c_size_t
         L.hp_humans_to_frame.restype = None
+        L.hp_engine_debug_raw_tensor.restype = C.c_int
+        L.hp_engine_debug_raw_tensor.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
         _lib = L
     return _lib
 

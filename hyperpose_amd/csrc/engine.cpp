@@ -2454,6 +2454,27 @@ int hp_engine_debug_tensor(hp_engine* e, int tensor, int n, float* host, int sha
     return HP_OK;
 }
 
+int hp_engine_debug_raw_tensor(hp_engine* e, int tensor, void* host, size_t cap_bytes, int geom[8])
+{
+    HP_REQUIRE(e && geom && tensor > 0 && tensor < (int)e->tensors.size() && e->tensors[tensor] && e->tensors[tensor]->defined, HP_ERR_INVALID,
+        "hp_engine_debug_raw_tensor: bad tensor %d", tensor);
+    const tensor_info& ti = *e->tensors[tensor];
+    HP_REQUIRE(!ti.unwritten, HP_ERR_STATE, "hp_engine_debug_raw_tensor: tensor %d exists only as the fp32 network output", tensor);
+    HP_REQUIRE(!ti.elided, HP_ERR_STATE, "hp_engine_debug_raw_tensor: tensor %d lives only inside a fused launch (HP_NO_FUSE=1 materialises it)", tensor);
+    // (a tensor of the activation arena is NOT refused: what lies in the shared buffer outside the interior is every tenant's padding)
+    const bool f32 = e->is_f32();
+    const int rows = f32 ? ti.rows32() : ti.H + 2 * ti.P;
+    const int esz = f32 ? (int)sizeof(float) : (int)sizeof(__half);
+    geom[0] = ti.H, geom[1] = ti.W, geom[2] = ti.C, geom[3] = ti.cs, geom[4] = ti.P, geom[5] = rows, geom[6] = esz, geom[7] = e->max_batch;
+    if (!host)
+        return HP_OK;
+    const size_t bytes = (size_t)e->max_batch * rows * (ti.W + 2 * ti.P) * ti.cs * esz;
+    HP_REQUIRE(ti.base<void>() && cap_bytes >= bytes, HP_ERR_INVALID, "hp_engine_debug_raw_tensor: tensor %d takes %zu bytes, the host buffer has %zu", tensor, bytes, cap_bytes);
+    HP_TRY(hp_engine_synchronize(e));
+    HP_HIP_TRY(hipMemcpy(host, ti.base<void>(), bytes, hipMemcpyDeviceToHost));
+    return HP_OK;
+}
+
 int hp_engine_profile(hp_engine* e, int n, int iters, hp_layer_time* out, int cap, int* n_out)
 {
     HP_REQUIRE(e && n >= 1 && n <= e->max_batch && iters >= 1 && n_out, HP_ERR_INVALID, "hp_engine_profile: bad argument");

@@ -305,6 +305,17 @@ class Engine:
         check(lib().hp_engine_debug_tensor(self._h, tensor, n, out.ctypes.data_as(C.POINTER(C.c_float)), shape))
         return out
 
+    def debug_raw(self, tensor: int):
+        """The tensor's whole buffer as it lies in HBM (hp_engine_debug_raw_tensor): an array [max_batch, rows, W + 2P, cs] of float16
+        or float32 - halo, separator rows and pad channels included - and the geometry as a dict."""
+        g = (C.c_int * 8)()
+        check(lib().hp_engine_debug_raw_tensor(self._h, int(tensor), None, 0, g))
+        geom = dict(zip(("H", "W", "C", "cs", "P", "rows", "elem_bytes", "max_batch"), (int(v) for v in g)))
+        out = np.empty((geom["max_batch"], geom["rows"], geom["W"] + 2 * geom["P"], geom["cs"]),
+                       np.float16 if geom["elem_bytes"] == 2 else np.float32)
+        check(lib().hp_engine_debug_raw_tensor(self._h, int(tensor), out.ctypes.data_as(C.c_void_p), out.nbytes, g))
+        return out, geom
+
     def profile(self, n: int, iters: int = 10, in_sequence: bool = False, pair: "Engine | None" = None):
         """Per-step device times: each step launched back to back (default) or the whole schedule in order with events in
         between (``in_sequence``: the cache state of a real inference; agrees with rocprofv3's per-kernel averages), or - ``pair`` =

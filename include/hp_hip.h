@@ -472,6 +472,12 @@ int hp_engine_load(hp_engine** out, const char* path, int max_batch);
 int hp_engine_output_to_host(hp_engine* e, int i, int n, float* host); /* synchronises, then D2H */
 /* Read back an internal fp16 NHWC tensor as fp32 NCHW [n][C][H][W] (layer-wise parity tests only). */
 int hp_engine_debug_tensor(hp_engine* e, int tensor, int n, float* host, int shape[3]);
+/* The tensor's whole buffer as it lies in HBM (write-footprint tests only): [max_batch][rows][W + 2P][cs] elements, halo, separator rows
+ * and pad channels included, all max_batch images whatever the last batch was.  geom = { H, W, C, cs, P, rows per image (H + 2P; fp32
+ * engines: made even when P > 0), bytes per element (2: fp16, also in HP_DTYPE_I8 engines, 4: fp32), max_batch }.  host == NULL: the
+ * geometry only.  Synchronises the engine first.  Tensors of the activation arena are shown too (the buffer then holds its last tenant);
+ * HP_ERR_STATE for a tensor that is never materialised (fused away, or only the fp32 network output), HP_ERR_INVALID for a bad id. */
+int hp_engine_debug_raw_tensor(hp_engine* e, int tensor, void* host, size_t cap_bytes, int geom[8]);
 
 /* Per-layer device time (ms, averaged over iters) measured with HIP events on the engine stream for batch n:
  * the numbers the roofline report is built from.  flops = 2*MACs of the layer for that batch. */

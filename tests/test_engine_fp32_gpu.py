@@ -10,6 +10,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import footprint
 from hyperpose_amd import engine as E
 from hyperpose_amd import synth
 from oracle import ref_net
@@ -51,6 +52,7 @@ def _run32(net, outs, frames, h, w, f32_input=False, dtype="f32", **kw):
         for nm, arr in got[b]:
             _close32(arr, ref[nm][b], nm)
     assert eng.split_fallbacks == 0
+    footprint.assert_zero_outside(eng, footprint.tensor_ids(net.layers), len(frames))   # halo, separator rows, pad channels
     return eng, got, ref
 
 

@@ -7,6 +7,7 @@ rounding flips: |err| <= 2e-3 * max|ref| + 1e-3.  Against the pure fp32 oracle t
 import numpy as np
 import pytest
 
+import footprint
 from hyperpose_amd import engine as E
 from oracle import ref_net
 
@@ -79,6 +80,7 @@ def _run_both(net, outs, frames, h, w, max_batch=None, f32=False, **kw):
         ref = ref_net.run(net.layers, outs, blob, frames_u8=frames, match_fp16=True,
                           factor=kw.get("factor", 1 / 255), flip_rb=kw.get("flip_rgb", True),
                           mean=kw.get("mean", (0, 0, 0)), inv_std=kw.get("inv_std", (1, 1, 1)))
+    footprint.assert_zero_outside(eng, footprint.tensor_ids(net.layers), len(frames))   # halo, pad channels: what no output shows
     return eng, got, ref
 
 

@@ -25,6 +25,7 @@ import zlib
 import numpy as np
 import pytest
 
+import footprint
 from hyperpose_amd import _lib
 from hyperpose_amd import engine as E
 from oracle import ref_net
@@ -655,6 +656,7 @@ def check_case(monkeypatch, fam, g, want=None):
     ref, tens = ref_net.run(net.layers, g.outs, net.blob(), frames_u8=frames, match_fp16=f16, return_tensors=True)
     eng = _engine(monkeypatch, g, fam, fam.env)
     got = eng.inference(frames)
+    footprint.assert_zero_outside(eng, footprint.tensor_ids(net.layers), n, fam.name)
     prof = eng.profile(n, 1)
     fired = fam.sig(prof)
     print(f"{fam.name} {_pid(g.P if g.P[0] else None)}: fired {fired}, expected {want}")

@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import footprint
 from hyperpose_amd import _lib
 from hyperpose_amd import engine as E
 from oracle import ref_net
@@ -152,6 +153,7 @@ def test_int8_layer_matches_the_quantization_contract(hp, case):
     s = eng.int8_scales
     assert s[0] == 0 and s[li] > 0
     got = eng.inference(fr)
+    footprint.assert_zero_outside(eng, footprint.tensor_ids(net.layers), n)
     x = eng.debug_tensor(t0, n)
     r = eng.debug_tensor(res, n) if res >= 0 else None
     v = _emulate(L, x, blob, s[li], r)
@@ -219,6 +221,7 @@ def test_int8_layer_on_signed_tying_saturating_inputs(hp, case):
     eng.int8_scales = s
     assert eng.int8_scales[li] == s[li]
     got = eng.inference(fr)
+    footprint.assert_zero_outside(eng, footprint.tensor_ids(net.layers), n)
     x = eng.debug_tensor(t0, n)
     assert_input_shares(x, s[li])
     v = _emulate(L, x, blob, s[li])
