@@ -1,25 +1,17 @@
-// conv_kernels.hip — hand-written gfx950 kernels for the backbone + head convolution stack.
+// conv_kernels.hip — hand-written gfx950 kernels for the backbone + head convolution stack of the fp16 engine.
 //
 // Replaces the TensorRT engine the reference builds and runs at src/tensorrt.cpp:121-252 / :393; layer
 // semantics (TF "SAME" padding, folded BatchNorm, activation placement) follow the Python model
 // definitions the reference exports from (hyperpose/Model/backbones.py, openpose/model/lw_openpose.py, ...).
 //
-//   conv_mfma_kernel    dense k x k conv as implicit GEMM:  D[cout][pixel] = sum_{tap,cin} W[tap][cout][cin] * X[pixel@tap][cin]
-//                       v_mfma_f32_32x32x16_f16, A = weights, B = activations (both K-contiguous in HBM: packed
-//                       weights [tap][cout][cin], activations NHWC), fp32 accumulate.  256 threads = 2x2 wavefronts,
-//                       block tile BM x BN x BK, global->register->LDS staging with the loads of K-step s+2 in
-//                       flight while step s computes, ONE barrier per K-step, XOR-swizzled LDS rows so that
-//                       ds_read_b128 fragment reads are bank-conflict free, XCD-aware block->tile mapping.
-//   conv3x3_halo_kernel the 3x3 / stride 1 case (44 % of LW-OpenPose's conv time): an 8x16-pixel output tile and its
-//                       1-pixel halo are staged in LDS ONCE and re-used by all 9 taps (L2 traffic per block drops
-//                       from 9 activation tiles to 1.4), only the weights stream through a prefetched LDS ring.
-//   Both share one epilogue: each lane owns 4 consecutive output channels of a pixel -> 8-byte NHWC stores; bias,
-//   piecewise-linear activation, residual add and the fp32 NCHW copy for the parsers are fused.
-//   first_conv_kernel   3-channel network input (u8 HWC or f32 NCHW): pre-processing (x factor, BGR->RGB, mean/std)
-//                       fused into the load, fp32 math, HBM-bound.
-//   dwconv3x3_kernel    depthwise 3x3, one thread = one pixel x 8 channels (16-byte loads/stores), HBM/L2-bound.
+//   dense (conv_pick.hpp decides which): conv_mfma_kernel (any k x k as implicit GEMM, weights in rows), conv3x3_direct_kernel,
+//     conv_direct_kernel + conv_direct_finish_kernel, conv1x1_small_kernel, conv1x1_big_kernel (weights in MFMA-fragment order)
+//   first convolution: first_conv_kernel, first_conv_f16_kernel          depthwise: dwconv3x3_kernel
+//   fused separable blocks: sepconv_slot_kernel, sepconv_pipe_kernel, sepconv_pipe3_kernel, sepconv_small_kernel, sepconv_pair_kernel
+//   fused two-layer head: mlp_head_kernel, mlp_head_pair_kernel          maxpool_kernel, upsample_kernel, output_transform_kernel
 // Activations carry a zero halo in HBM (conv_kernels.hpp), so taps in the padding are ordinary loads.
 #include "conv_device.hpp"
+#include "conv_pick.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -1342,69 +1334,6 @@ __global__ __launch_bounds__(512) void conv_direct_finish_kernel(const conv_para
     conv_epilogue_staged<1, K0>(p, mine, blockIdx.y * 128 + wm * 32, lane, lds + wave * stage_geom<1>::SLAB, pb, py, px, pv);
 }
 
-// fast epilogue (aligned fp16 NHWC vectors) when every 8-channel chunk is whole and 16-byte aligned
-static bool fast_epilogue(const conv_params& p)
-{
-    return p.out.p && !p.out_f32 && p.Cout % 8 == 0 && p.out.coff % 8 == 0 && p.out.cs % 8 == 0
-        && (!p.res.p || (p.res.coff % 8 == 0 && p.res.cs % 8 == 0));
-}
-
-static bool use_halo(const conv_params& p);
-static bool use_small1x1(const conv_params& p);
-static int big1x1_variant(const conv_params& p);
-static bool fast_epilogue(const conv_params& p);
-// conv_direct_kernel (8 wavefronts, 128 output channels x 16x12 pixels per block, any square kernel / chunked Cin) serves this layer:
-// 0 = no, otherwise the channel chunk CK (128 or 64).
-static int use_gdirect(const conv_params& p)
-{
-    if (p.KH != p.KW || (p.KH != 3 && p.KH != 5 && p.KH != 7) || p.stride != 1 || p.dil != 1 || p.pad_t != p.KH / 2
-        || p.pad_l != p.KH / 2 || p.OH != p.H || p.OW != p.W || p.Cin % 64 || p.Cout_pad % 128 || p.in.coff % 8 || !fast_epilogue(p))
-        return 0;
-    if (p.KH == 3 && p.Cin <= 128)
-        return 0; // (these stay with conv3x3_direct_kernel, whose half-size blocks share a CU at batch 8)
-    // maps smaller than two tiles: the generic implicit GEMM packs pixels of several images into one tile - worth more than the halo
-    // re-use unless K is long (measured at 12 x 12: 512 -> 512 57 -> 45 us, 2048 -> 512 212 -> 163 us on this kernel)
-    if ((long)p.OH * p.OW < 256 && p.Cin < 256)
-        return 0;
-    // 3x3 on maps the 16 x 12 tiles cover badly (49 x 49: 20 tiles for 12.5 tiles of pixels, 25 x 25: 6 for 3.3): the generic kernel has no
-    // tiles to round up to (measured at batch 64: 256 channels at 49 x 49 253 -> 223 us, 512 channels at 25 x 25 276 -> 220 us)
-    if (p.KH == 3 && (double)p.OH * p.OW < 0.68 * ((p.OH + 15) / 16 * 16) * ((p.OW + 11) / 12 * 12))
-        return 0;
-    // 128-channel chunks only where ONE chunk is the whole input (7x7 / 5x5 x 128: a 101 / 82 KB tile, single-buffered); everything
-    // else runs on double-buffered 64-channel chunks (the 128-channel form of that pipeline needs more than 256 registers)
-    // (measured: 7x7 x 128 as two pipelined 64-channel chunks is 10 % slower than as one 128-channel chunk - the chunk barrier waits for
-    // the wavefronts that lose the matrix-pipe arbitration)
-    return p.Cin == 128 ? 128 : 64;
-}
-// 1: the weights of this convolution are to be packed in MFMA-fragment order for conv3x3_direct_kernel / conv_direct_kernel
-int conv_weight_layout(const conv_params& p)
-{
-    if (use_small1x1(p) && fast_epilogue(p))
-        return 1;
-    if (big1x1_variant(p) && fast_epilogue(p))
-        return 1;
-    if (use_gdirect(p))
-        return 1;
-    return use_halo(p) && fast_epilogue(p) ? 1 : 0;
-}
-
-static bool use_halo(const conv_params& p)
-{
-    return p.KH == 3 && p.KW == 3 && p.stride == 1 && p.dil == 1 && p.pad_t == 1 && p.pad_l == 1 && (p.Cin == 128 || p.Cin == 64)
-        && p.Cout_pad % 64 == 0 && p.in.coff % 8 == 0;
-}
-
-template <int BM, int BN, int BK>
-static hipError_t launch_tile(const conv_params& p, hipStream_t s)
-{
-    dim3 grid(((p.npix + BN - 1) / BN) * (p.Cout_pad / BM));
-    if (fast_epilogue(p))
-        HP_LAUNCH((conv_mfma_kernel<BM, BN, BK, 0>), grid, dim3(256), 0, s, p);
-    else
-        HP_LAUNCH((conv_mfma_kernel<BM, BN, BK, 1>), grid, dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
 bool set_act(conv_params& p)
 {
     const float inf = __builtin_huge_valf();
@@ -1669,88 +1598,37 @@ __global__ __launch_bounds__(512) void conv1x1_big_kernel(const conv_params p)
 #undef HP_BSTAMP
 }
 
-// which (TM, NTP) the pixel-block GEMM runs a layer with: TM * 1000 + NTP, or 0 when the layer is not its kind
-static int big1x1_variant(const conv_params& p)
-{
-    // (any stride: a strided 1x1 is the same GEMM over every stride-th pixel - the producers gather them; ResNet's projection shortcuts)
-    if (p.KH != 1 || p.KW != 1 || p.stride < 1 || p.pad_t || p.pad_l || p.OH != (p.H + p.stride - 1) / p.stride
-        || p.OW != (p.W + p.stride - 1) / p.stride || p.Cin % 256 /* four-chunk ring */ || p.Cout_pad % 128 || p.Cout % 8 || p.in.coff % 8
-        || p.in.cs - p.in.coff < p.Cin)
-        return 0;
-    // (TM, NTP) by a small cost model: blocks are dealt to the 256 CUs in rounds (two blocks share a CU when each needs <= 256
-    // registers); a round costs its MFMAs at ~80 % pipe efficiency plus ~6 k cycles of prologue / epilogue; 64-pixel blocks (NTP = 2)
-    // pull twice the weights per MFMA through the texture path
-    // (TM, NTP): measured over the ResNet-50 bottlenecks at 193^2 .. 12^2 pixels and LW-OpenPose's pointwise layers (sweep of all
-    // instances, tools/profile_layers.py): 64 pixels x 256 output channels wins or ties almost everywhere - 118 registers and 72 KB
-    // of LDS let TWO blocks share a CU, so one block's prologue (first chunk from HBM) and epilogue (stores) sit under the other's
-    // MFMAs; wider or taller blocks run alone on their CU and pay both phases in full.  128-row blocks where the output has no
-    // 256-row groups.
-    // ... except where that grid is barely more than one block per CU (ResNet's reductions on 24 x 24 / 12 x 12 maps at batch 32: 288 / 144
-    // blocks): 128-row blocks halve the last, nearly empty round (25.5 -> 21.4 us, 22.8 -> 19.2 us; a higher threshold loses with two streams)
-    if (p.Cout_pad % 256 == 0 && (long)((p.npix + 63) / 64) * (p.Cout_pad / 256) < 320)
-        return 1002;
-    if (p.Cout_pad % 256 == 0)
-        return 2002;
-    const long blocks4 = (long)((p.npix + 127) / 128) * (p.Cout_pad / 128);
-    return blocks4 >= 1024 ? 1004 : 1002;
-}
+// The dense launcher and its three questions (conv_kernels.hpp): thin readers of the one choice conv_pick.hpp makes.
+int conv_weight_layout(const conv_params& p) { return pick::weight_layout(p); }
+int conv_mfma_tile(const conv_params& p) { return pick::tile(p); }
+int conv_splitk(const conv_params& p, size_t* scratch_bytes) { return pick::splitk(p, scratch_bytes); }
 
-static bool use_small1x1(const conv_params& p)
+template <int BM, int BN>
+static hipError_t launch_tile(const conv_params& p, const conv_choice& c, hipStream_t s)
 {
-    return p.KH == 1 && p.KW == 1 && p.stride == 1 && p.Cout_pad % 128 == 0 && p.Cout_pad <= 512
-        && (p.Cout_pad == 128 || p.Cin <= 128) // (wider outputs only where the layer is HBM-bound: K <= 128)
-        && (p.Cin == 64 || p.Cin == 128 || p.Cin == 192 || p.Cin == 256)
-        && p.in.coff % 8 == 0 && p.in.cs - p.in.coff >= p.Cin && p.OH == p.H && p.OW == p.W;
-}
-
-int conv_mfma_tile(const conv_params& p)
-{
-    if (p.w_layout == 1 && p.KH == 1 && !use_small1x1(p))
-        return 5200000 + big1x1_variant(p); // conv1x1_big_kernel<TM, NTP>
-    if (p.w_layout == 1 && p.KH == 1)
-        return 5100000 + p.Cin; // conv1x1_small_kernel
-    if (p.w_layout == 1 && use_gdirect(p))
-        return 6000000 + p.Cin * 1000 + p.KH * p.KW; // conv_direct_kernel
-    if (p.w_layout == 1)
-        return 5000000 + 64 * 1000 + 192;
-    const int BM = (p.Cout_pad % 128 == 0) ? 128 : 64;
-    // prefer the 128-pixel tile only when it still fills the 256 CUs at least once
-    const long blocks128 = (long)((p.npix + 127) / 128) * (p.Cout_pad / BM);
-    const int BN = blocks128 >= 256 ? 128 : 64;
-    return BM * 1000 + BN;
-}
-
-// split-K for the chunk-pipelined 3x3 instance when its tiles leave CUs idle (configs[3]: 12 x 12 maps at batch 32 = 32 tiles x 4
-// output-channel groups = 128 blocks; the 2048 -> 512 head convolution alone is 8 % of that network's conv time)
-int conv_splitk(const conv_params& p, size_t* scratch_bytes)
-{
-    if (scratch_bytes)
-        *scratch_bytes = 0;
-    if (p.w_layout != 1 || p.KH != 3 || use_gdirect(p) != 64)
-        return 1;
-    const int nchunks = p.Cin / 64;
-    const long blocks = (long)((p.OW + 11) / 12) * ((p.OH + 15) / 16) * p.B * (p.Cout_pad / 128);
-    int ks = 1;
-    if (blocks <= 64 && nchunks >= 8 && nchunks % 4 == 0)
-        ks = 4;
-    else if (blocks <= 160 && nchunks >= 4 && nchunks % 2 == 0)
-        ks = 2;
-    if (ks > 1 && scratch_bytes)
-        *scratch_bytes = (size_t)ks * blocks * 8 * 3 * 4 * 64 * sizeof(float4); // [z][slot][wave][K0 = 3][4][64 lanes] float4
-    return ks;
+    dim3 grid(((p.npix + BN - 1) / BN) * (p.Cout_pad / BM));
+    if (c.BK == 64 && c.EPI == 0)
+        HP_LAUNCH((conv_mfma_kernel<BM, BN, 64, 0>), grid, dim3(256), 0, s, p);
+    else if (c.BK == 64)
+        HP_LAUNCH((conv_mfma_kernel<BM, BN, 64, 1>), grid, dim3(256), 0, s, p);
+    else if (c.EPI == 0)
+        HP_LAUNCH((conv_mfma_kernel<BM, BN, 32, 0>), grid, dim3(256), 0, s, p);
+    else
+        HP_LAUNCH((conv_mfma_kernel<BM, BN, 32, 1>), grid, dim3(256), 0, s, p);
+    return hipGetLastError();
 }
 
 hipError_t launch_conv_mfma(const conv_params& p, hipStream_t s)
 {
-    if (p.w_layout == 1 && p.KH == 1 && !use_small1x1(p)) {
-        const int v = big1x1_variant(p);
-        if (!v || !fast_epilogue(p))
-            return hipErrorInvalidValue;
-        const int TM = v / 1000, NTP = v % 1000;
-        const int ptiles = (p.npix + 32 * NTP - 1) / (32 * NTP);
-        const dim3 grid((ptiles + 7) / 8 * 8 * (p.Cout_pad / (128 * TM)));
+    const conv_choice c = pick_conv(p, p.w_layout);
+    if (!c.ok)
+        return hipErrorInvalidValue; // fragment-ordered weights only fit the kernels that read them
+    switch (c.form) {
+    case CONV_BIG1X1: {
+        const int ptiles = (p.npix + 32 * c.NTP - 1) / (32 * c.NTP);
+        const dim3 grid((ptiles + 7) / 8 * 8 * (p.Cout_pad / (128 * c.TM)));
 #define HP_BIG(TM_, NTP_) HP_LAUNCH((conv1x1_big_kernel<TM_, NTP_>), grid, dim3(512), 0, s, p)
-        switch (v) { // (the instances big1x1_variant hands out; wider / taller ones were swept and lost: see there)
+        switch (c.TM * 1000 + c.NTP) { // (the instances big1x1_variant, conv_pick.hpp, hands out; wider / taller ones were swept and lost: see there)
         case 2002: HP_BIG(2, 2); break;
         case 1004: HP_BIG(1, 4); break;
         default: HP_BIG(1, 2); break;
@@ -1758,11 +1636,9 @@ hipError_t launch_conv_mfma(const conv_params& p, hipStream_t s)
 #undef HP_BIG
         return hipGetLastError();
     }
-    if (p.w_layout == 1 && p.KH == 1) {
-        if (!(use_small1x1(p) && fast_epilogue(p)))
-            return hipErrorInvalidValue;
+    case CONV_SMALL1X1: {
         const dim3 grid((p.npix + 63) / 64);
-        switch (p.Cin) {
+        switch (c.KP) {
         case 64: HP_LAUNCH((conv1x1_small_kernel<64>), grid, dim3(256), 0, s, p); break;
         case 128: HP_LAUNCH((conv1x1_small_kernel<128>), grid, dim3(256), 0, s, p); break;
         case 192: HP_LAUNCH((conv1x1_small_kernel<192>), grid, dim3(256), 0, s, p); break;
@@ -1770,22 +1646,22 @@ hipError_t launch_conv_mfma(const conv_params& p, hipStream_t s)
         }
         return hipGetLastError();
     }
-    if (p.w_layout == 1 && use_gdirect(p)) {
-        const int ck = use_gdirect(p), nchunks = p.Cin / ck;
+    case CONV_DIRECT: {
+        const int nchunks = c.nchunks;
         const int tiles_x = (p.OW + 11) / 12, tiles_y = (p.OH + 15) / 16;
         const dim3 grid(tiles_x * tiles_y * p.B, p.Cout_pad / 128);
 #define HP_GD(KS, CK, NBUF) HP_LAUNCH((conv_direct_kernel<KS, CK, NBUF>), grid, dim3(512), 0, s, p, tiles_x, tiles_y, nchunks)
-        if (p.KH == 7 && ck == 128)
+        if (c.KS == 7 && c.CK == 128)
             HP_GD(7, 128, 1);
-        else if (p.KH == 7)
+        else if (c.KS == 7)
             HP_GD(7, 64, 2);
-        else if (p.KH == 5 && ck == 128)
+        else if (c.KS == 5 && c.CK == 128)
             HP_GD(5, 128, 1);
-        else if (p.KH == 5)
+        else if (c.KS == 5)
             HP_GD(5, 64, 2);
-        else if (ck == 128)
+        else if (c.CK == 128)
             HP_GD(3, 128, 1);
-        else if (nchunks == 1)
+        else if (c.NBUF == 1)
             HP_GD(3, 64, 1);
         else if (p.ksplit > 1 && p.splitk && nchunks % p.ksplit == 0) { // (the engine sized the scratch for its largest batch)
             const dim3 grid3(grid.x, grid.y, p.ksplit);
@@ -1802,27 +1678,24 @@ hipError_t launch_conv_mfma(const conv_params& p, hipStream_t s)
 #undef HP_GD
         return hipGetLastError();
     }
-    if (p.w_layout == 1) {
-        if (!(use_halo(p) && fast_epilogue(p)))
-            return hipErrorInvalidValue; // fragment-ordered weights only fit the direct kernel
+    case CONV_HALO: {
         const int tiles_x = (p.OW + 11) / 12, tiles_y = (p.OH + 15) / 16;
         dim3 grid(tiles_x * tiles_y * p.B, p.Cout_pad / 64);
-        if (p.Cin == 128)
+        if (c.CIN == 128)
             HP_LAUNCH((conv3x3_direct_kernel<128, 16>), grid, dim3(256), 0, s, p, tiles_x, tiles_y);
         else
             HP_LAUNCH((conv3x3_direct_kernel<64, 16>), grid, dim3(256), 0, s, p, tiles_x, tiles_y);
         return hipGetLastError();
     }
-    const int t = conv_mfma_tile(p);
-    const int BM = t / 1000, BN = t % 1000;
-    const bool k64 = (p.Cin % 64 == 0);
-    if (BM == 128 && BN == 128)
-        return k64 ? launch_tile<128, 128, 64>(p, s) : launch_tile<128, 128, 32>(p, s);
-    if (BM == 128 && BN == 64)
-        return k64 ? launch_tile<128, 64, 64>(p, s) : launch_tile<128, 64, 32>(p, s);
-    if (BM == 64 && BN == 128)
-        return k64 ? launch_tile<64, 128, 64>(p, s) : launch_tile<64, 128, 32>(p, s);
-    return k64 ? launch_tile<64, 64, 64>(p, s) : launch_tile<64, 64, 32>(p, s);
+    default:
+        if (c.BM == 128 && c.BN == 128)
+            return launch_tile<128, 128>(p, c, s);
+        if (c.BM == 128 && c.BN == 64)
+            return launch_tile<128, 64>(p, c, s);
+        if (c.BM == 64 && c.BN == 128)
+            return launch_tile<64, 128>(p, c, s);
+        return launch_tile<64, 64>(p, c, s);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------
