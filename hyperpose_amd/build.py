@@ -54,6 +54,7 @@ UNITS = [
     # epilogue / quantization must not turn into packed fp32 FMAs
     ("conv_i8.hip", ["-fno-slp-vectorize"]),
     ("engine.cpp", []),
+    ("engine_timeline.cpp", []),  # host text only: the HP_*_DBG timelines decoded (tests/cpp/engine_timeline.cpp)
     ("models.cpp", []),
     ("onnx_import.cpp", []),
     ("pipeline.cpp", []),

@@ -13,6 +13,7 @@
 #include "conv_fp32.hpp"
 #include "conv_i8.hpp"
 #include "conv_kernels.hpp"
+#include "engine_timeline.hpp"
 #include "hp_common.hpp"
 #include "weight_pack.hpp"
 
@@ -21,6 +22,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <variant>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -73,39 +75,90 @@ struct out_info {
     std::unique_ptr<hp::dev_buf> buf;
 };
 
-struct step {
-    int layer;
-    int op;
-    bool first = false; // direct 3-channel conv
-    hp::conv_params cp{};
-    hp::first_conv_params fp{};
-    hp::dw_params dp{};
-    hp::pool_params pp{};
-    hp::sep_params sp{}; // op == OP_SEPCONV: depthwise layer `layer` fused with the pointwise layer `layer + 1`
-    hp::sep_params sp2{}; // ... and, when `sep_pair`, the NEXT separable block (layers `layer + 2`, `layer + 3`) in the same launch
-    bool sep_pair = false;
-    hp::head_params hp_{}; // op == OP_MLPHEAD: 1x1 conv `layer` (-> 512, relu) fused with the 1x1 conv `layer + 1`
-    hp::head_params hp2_{}; // ... and, when `paired`, the sibling head on the same input (layers `layer + 2`, `layer + 3`)
-    bool paired = false;
-    hp::chain_params ch{}; // op == OP_CHAIN: [1x1 ->] 3x3 -> 3x3 on 128 channels in one launch (conv_chain.hip), layers `layer` ..
-    hp::bneck_params bn{}; // op == OP_BNECK: [3x3 ->] expansion 1x1 + shortcut [-> the next block's reduction 1x1] (conv_bottleneck.hip)
-    // HP_DTYPE_F32 engines (conv_fp32.hip): one launch per layer, `op` = the layer's op, `f32` set
-    bool f32 = false;
-    hp::conv32_params cp32{};
-    hp::first_conv32_params fp32{};
-    hp::dw32_params dp32{};
-    hp::pool32_params pp32{};
-    bool wino = false;     // HP_DTYPE_F32: a 3 x 3 stride-1 layer on conv32_winograd_kernel (cp32.w_wino)
-    bool head32 = false;   // HP_DTYPE_F32: 1 x 1 128 -> HID -> 1 x 1 HID -> C2 in one launch (conv32_head.hip): cp32 = the second layer's epilogue, hh = the first layer
-    hp::head32_hidden hh{};
-    int cin_split = 0;     // fp32 engines: input channels as conv32_direct_kernel reads them (whole chunks), 0 = the layer stays on conv32_kernel
-    int n_layers = 1;      // consecutive layers this step covers
+// What the engine can launch: one value per kernel family and form.  Set by the lowering or fusion pass that decides it (lower_layers, fuse_*,
+// pair_heads) and never changed afterwards.  Two decisions are left to every launch, because they depend on what it is bound to:
+// an int8-capable dense conv runs conv_i8 only while its scale is positive (hp_engine::bound), and two adjacent fp32 heads share a grid when
+// conv32_head_pair_ok says so for the batch (hp_engine::launch_head_pair32).
+enum class launch_kind : char {
+    // fp16 (and int8) engines
+    first16,
+    conv16,
+    dw16,
+    maxpool16,
+    upsample16,
+    sep,       // depthwise layer `layer` fused with the pointwise layer `layer + 1`
+    sep_pair,  // ... and the NEXT separable block (layers `layer + 2`, `layer + 3`) in the same launch
+    head,      // 1x1 conv `layer` (-> 512, relu) fused with the 1x1 conv `layer + 1`
+    head_pair, // ... and the sibling head on the same input (layers `layer + 2`, `layer + 3`)
+    chain,     // [1x1 ->] 3x3 -> 3x3 on 128 channels in one launch (conv_chain.hip), layers `layer` ..
+    bneck,     // [3x3 ->] expansion 1x1 + shortcut [-> the next block's reduction 1x1] (conv_bottleneck.hip)
+    // HP_DTYPE_F32 / F32S engines (conv_fp32.hip): one launch per layer or fused pair
+    first32,
+    conv32,
+    wino2,  // a 3 x 3 stride-1 layer on conv32_winograd_kernel (cp.w_wino)
+    wino3,  // ... on the opt-in F(3 x 3, 3 x 3) kernel (cp.w_wino3)
+    direct, // conv32_direct_kernel, which reads `cin_split` input channels (whole chunks)
+    head32, // 1 x 1 128 -> HID -> 1 x 1 HID -> C2 in one launch (conv32_head.hip): cp = the second layer's epilogue, hh = the first layer
+    dw32,
+    maxpool32,
+    upsample32,
+};
+// the payloads that are more than one parameter struct of conv_kernels.hpp / conv_fp32.hpp
+struct conv16_launch {
+    hp::conv_params cp;
     // HP_DTYPE_I8 engines: a layer conv_i8_kernel covers keeps its fp16 launch (cp) and gets the int8 one beside it; which of the two runs
     // is the layer's entry of hp_engine::i8_scale (> 0: int8 with that activation scale, 0: fp16)
-    bool i8 = false;
-    hp::conv_i8_params q8{}; // q8.c is refreshed from cp at every launch; q8.dq points at i8_dq
-    float* i8_dq = nullptr;  // device [cp.Cout_pad]: s_a * s_w[c], rewritten by hp_engine::apply_int8_scales
+    hp::conv_i8_params q8; // q8.c is cp as bound at every launch; q8.dq points at i8_dq
+    float* i8_dq;          // device [cp.Cout_pad]: s_a * s_w[c], rewritten by hp_engine::apply_int8_scales
+    bool i8;               // in the schedule: the layer has an int8 launch; in a bound copy: this launch is the int8 one
+};
+struct sep_pair_launch {
+    hp::sep_params a, b;
+};
+struct head_pair_launch {
+    hp::head_params a, b;
+};
+struct conv32_launch { // conv32, wino2, wino3, direct
+    hp::conv32_params cp;
+    int cin_split; // direct: what the launch sets cp.Cin to
+};
+struct head32_launch {
+    hp::conv32_params cp;
+    hp::head32_hidden hh;
+};
+using launch_payload = std::variant<std::monostate, hp::first_conv_params, conv16_launch, hp::dw_params, hp::pool_params, hp::sep_params, sep_pair_launch,
+    hp::head_params, head_pair_launch, hp::chain_params, hp::bneck_params, hp::first_conv32_params, conv32_launch, head32_launch, hp::dw32_params,
+    hp::pool32_params>;
+
+// One launch of the schedule.  `p` holds the parameters of `kind` as build() described them for max_batch frames; a launch binds a copy of them
+// to its frames (bind), the schedule itself is const while the engine runs.
+struct step {
+    int layer;
+    int op;           // the layer's op, or one of the schedule-only codes below
+    launch_kind kind;
+    launch_payload p;
+    int n_layers = 1; // consecutive layers this step covers
     double flops = 0, bytes = 0; // per frame
+    template <typename T>
+    T& set(launch_kind k) // (zeroed parameters of a new kind)
+    {
+        kind = k;
+        return p.emplace<T>();
+    }
+    // typed access: the wrong kind throws std::bad_variant_access (hp_engine_create turns it into an error), it never reads zeros
+    template <typename T>
+    T& as() { return std::get<T>(p); }
+    template <typename T>
+    const T& as() const { return std::get<T>(p); }
+    hp::conv_params& cp() { return as<conv16_launch>().cp; } // the dense fp16 conv the schedule rewrites look at
+    const hp::conv_params& cp() const { return as<conv16_launch>().cp; }
+    hp::conv32_params& cp32() { return as<conv32_launch>().cp; }
+    const conv16_launch* int8() const // the layer's int8 launch, if it has one
+    {
+        const auto* c = std::get_if<conv16_launch>(&p);
+        return c && c->i8 ? c : nullptr;
+    }
+    conv16_launch* int8() { return const_cast<conv16_launch*>(static_cast<const step*>(this)->int8()); }
 };
 struct geo { // a layer's output size and the padding in front of its first row / column
     int OH, OW, pt, pl;
@@ -123,7 +176,7 @@ constexpr int OP_MLPHEAD = 101;
 constexpr int OP_CHAIN = 102;
 constexpr int OP_BNECK = 103;
 // a single dense layer's launch, as the schedule rewrites look for it
-inline bool plain_conv(const step& st) { return st.op == HP_OP_CONV && !st.first && st.n_layers == 1; }
+inline bool plain_conv(const step& st) { return st.kind == launch_kind::conv16 && st.n_layers == 1; }
 
 constexpr hp::tview NO_RES{ nullptr, 0, 0, 0, 0 }; // conv_params::res of a layer without a residual
 constexpr hp::tview32 NO_RES32{ nullptr, 0, 0, 0, 0 };
@@ -148,7 +201,7 @@ struct hp_engine {
     // (ineligible, or kept in fp16 by the caller), -1 eligible but not calibrated yet (such an engine does not infer).
     std::vector<float> i8_scale;
     std::vector<std::vector<float>> i8_sw; // per layer: the per-output-channel weight scales s_w[c] (empty for ineligible layers)
-    bool i8_on(const step& st) const { return st.i8 && i8_scale[st.layer] > 0.f; }
+    bool i8_on(const step& st) const { return st.int8() && i8_scale[st.layer] > 0.f; }
     bool i8_eligible(int layer) const { return !i8_sw[layer].empty(); }
     int check_int8_scales(const float* s, int n, bool allow_uncalibrated) const;
     int apply_int8_scales(); // dq / inv_a of every int8 step from i8_scale; the caller has synchronised and dropped the graphs
@@ -235,7 +288,7 @@ struct hp_engine {
     int lower32_dw_in_front(size_t i, step& st);
     int lower32_winograd_forms(size_t i, step& st, const std::vector<float>& packed);
     int lower32_direct_forms(size_t i, step& st, const std::vector<float>& packed, int room);
-    int lower32_head_in_front(size_t i, step& st, const float* w);
+    int lower32_head_in_front(size_t i, step& st, const float* w); // (turns the step's conv32_launch into a head32_launch)
     int lower32_dw(size_t i, step& st);
     // ... fp16 and int8 engines: one layer, a two-layer head, a separable block
     int lower16_first(size_t i, step& st);
@@ -287,12 +340,20 @@ struct hp_engine {
     float* fused_output(size_t layer, bool whole_tensor_only, V& out);
     int pointwise_params(size_t layer, int H, int W, int cout_pad, hp::conv_params& q); // the 1 x 1 second half of a fused fp16 pair
     // host_src != nullptr (eager launches of a host batch): every range copies ITS frames to the device on ITS stream first (frame_bytes each)
-    int enqueue(const uint8_t* u8, const float* f32, int n, hipStream_t s, const void* host_src = nullptr, size_t frame_bytes = 0);
-    int run_step(step& st, const uint8_t* u8, const float* f32, int n, hipStream_t s, int b0 = 0);
-    int print_timeline(const step& st, const hp::conv32_params* q32, hipStream_t s); // HP_*_DBG block timelines of the step just launched (q32: an fp32 layer's launch)
-    int step_tile(const step& st) const; // hp_layer_time::tile: which kernel form the step launches (0: ops with one form)
-    int stage_profile_input();           // in_stage as the hp_engine_profile* calls' synthetic max_batch input
-    int enqueue_range(const uint8_t* u8, const float* f32, int b0, int n, hipStream_t s);
+    // ---- running the schedule: const, `steps` is written by build(), apply_int8_scales() and nobody else
+    int enqueue(const uint8_t* u8, const float* f32, int n, hipStream_t s, const void* host_src = nullptr, size_t frame_bytes = 0) const;
+    int enqueue_range(const uint8_t* u8, const float* f32, int b0, int n, hipStream_t s) const;
+    // the step's parameters for frames [b0, b0 + n) of the batch at u8 / f32, as its launch gets them (and whether it is the int8 launch)
+    launch_payload bound(const step& st, const uint8_t* u8, const float* f32, int n, int b0) const;
+    int launch(launch_kind kind, launch_payload& bound, hipStream_t s, unsigned long long* dbg) const; // dbg: the launch's block-timeline stamps, or nullptr
+    int launch_head_pair32(size_t i, int n, int b0, hipStream_t s, bool* done) const; // fp32 heads i and i + 1 in one grid, where the bound batch allows it
+    int run_step(const step& st, const uint8_t* u8, const float* f32, int n, hipStream_t s, int b0 = 0) const;
+    bool timeline_of(const step& st, const launch_payload& bound, hp::timeline_kind& kind, hp::timeline_header& hd) const; // which HP_*_DBG timeline the switches ask for
+    int trace_step(const step& st, launch_payload& bound, hipStream_t s) const; // ... launched once more with its stamps, printed to stderr
+    int tile_of(launch_kind kind, const launch_payload& bound) const;
+    int step_tile(const step& st, int n) const; // hp_layer_time::tile: which kernel form the step launches on n frames (0: ops with one form)
+    void fill_row(hp_layer_time* out, int k, int cap, const step& st, int n, float ms) const; // a profile row
+    int stage_profile_input();                  // in_stage as the hp_engine_profile* calls' synthetic max_batch input
 };
 
 bool hp_engine::tensor_is_read(int t) const
@@ -795,7 +856,6 @@ int hp_engine::lower_first(size_t i, step& st, P& p, const float*& w)
     w = blob(L.w_off, nw, "weights", i);
     if (!w)
         return HP_ERR_INVALID;
-    st.first = true;
     p.factor = factor, p.flip_rb = flip_rb;
     for (int c = 0; c < 3; ++c)
         p.mean[c] = mean[c], p.inv_std[c] = inv_std[c];
@@ -837,18 +897,21 @@ int hp_engine::lower_single(size_t i)
 {
     const hp_layer& L = layers[i];
     step st;
-    st.layer = (int)i, st.op = L.op, st.f32 = is_f32();
-    if (st.f32 && (fuse_next[i] == fuse_kind::sep32 || fuse_next[i] == fuse_kind::head32)) // the first half of a fused pair: described at the 1 x 1 layer that follows
+    st.layer = (int)i, st.op = L.op;
+    const bool f32 = is_f32();
+    if (f32 && (fuse_next[i] == fuse_kind::sep32 || fuse_next[i] == fuse_kind::head32)) // the first half of a fused pair: described at the 1 x 1 layer that follows
         return HP_OK;
     const float* w = nullptr;
     if (L.op == HP_OP_CONV && L.in == 0)
-        HP_TRY(st.f32 ? lower_first(i, st, st.fp32, w) : lower16_first(i, st));
+        HP_TRY(f32 ? lower_first(i, st, st.set<hp::first_conv32_params>(launch_kind::first32), w) : lower16_first(i, st));
     else if (L.op == HP_OP_CONV)
-        HP_TRY(st.f32 ? lower32_conv(i, st) : lower16_conv(i, st));
+        HP_TRY(f32 ? lower32_conv(i, st) : lower16_conv(i, st));
     else if (L.op == HP_OP_DWCONV)
-        HP_TRY(st.f32 ? lower32_dw(i, st) : lower16_dw(i, st));
+        HP_TRY(f32 ? lower32_dw(i, st) : lower16_dw(i, st));
+    else if (const bool up = L.op == HP_OP_UPSAMPLE; f32)
+        HP_TRY(lower_pool(i, st, st.set<hp::pool32_params>(up ? launch_kind::upsample32 : launch_kind::maxpool32)));
     else
-        HP_TRY(st.f32 ? lower_pool(i, st, st.pp32) : lower_pool(i, st, st.pp));
+        HP_TRY(lower_pool(i, st, st.set<hp::pool_params>(up ? launch_kind::upsample16 : launch_kind::maxpool16)));
     steps.push_back(st);
     return HP_OK;
 }
@@ -872,7 +935,7 @@ int hp_engine::lower32_conv(size_t i, step& st)
     const float* w = blob(L.w_off, nw, "weights", i);
     if (!w)
         return HP_ERR_INVALID;
-    auto& p = st.cp32;
+    auto& p = st.set<conv32_launch>(launch_kind::conv32).cp;
     HP_TRY(upload_padded(L.b_off, L.cout, cout_pad, "bias", i, p.bias));
     HP_TRY(upload_prelu(i, cout_pad, p.alpha));
     const std::vector<float> packed = hp::wpack::dense32_rows(w, L.cout, taps, L.cin, cout_pad, cin_pad);
@@ -896,7 +959,7 @@ int hp_engine::lower32_conv(size_t i, step& st)
     // the weight forms of the kernels beside conv32_kernel; each looks at the filled p and says whether it applies
     HP_TRY(lower32_winograd_forms(i, st, packed));
     HP_TRY(lower32_direct_forms(i, st, packed, tsrc.cs - S.in_coff));
-    if (head_in_front)
+    if (head_in_front) // (last: it replaces the payload `p` refers to)
         HP_TRY(lower32_head_in_front(i, st, w));
     return HP_OK;
 }
@@ -905,7 +968,7 @@ int hp_engine::lower32_conv(size_t i, step& st)
 int hp_engine::lower32_dw_in_front(size_t i, step& st)
 {
     const hp_layer &D = layers[i - 1], &L = layers[i];
-    auto& p = st.cp32;
+    auto& p = st.cp32();
     const float* dwf = blob(D.w_off, (size_t)D.cin * 9, "weights", i - 1);
     std::vector<float> dbias;
     if (!dwf || !fetch_padded(D.b_off, D.cin, D.cin, "bias", i - 1, dbias))
@@ -927,14 +990,14 @@ int hp_engine::lower32_dw_in_front(size_t i, step& st)
 // (Never a layer with a depthwise or hidden layer fused in front: those are 1 x 1.)
 int hp_engine::lower32_winograd_forms(size_t i, step& st, const std::vector<float>& packed)
 {
-    auto& p = st.cp32;
+    auto& p = st.cp32();
     if (dtype != HP_DTYPE_F32 || switches.no_winograd32 || !hp::conv32_winograd_ok(p))
         return HP_OK;
     const double wbytes = (double)layers[i].cout * 9 * layers[i].cin * 4; // the layer's own weights
     std::vector<float> wu((size_t)16 * p.Cout_pad * p.Cin);
     hp::conv32_winograd_pack(packed.data(), p.Cout_pad, p.Cin, wu.data());
     HP_TRY(upload(wu, p.w_wino));
-    st.wino = true;
+    st.kind = launch_kind::wino2;
     st.bytes += wbytes * (16.0 / 9 - 1);
     // ... or, opt-in (HP_WINO_F33=1), F(3 x 3, 3 x 3): 25 products per 3 x 3 tile - 1.44 x fewer MFMA cycles, same accuracy
     // (conv32_winograd3.hip).  Measured: it wins where its 24 x 6-pixel blocks tile the map exactly and the layer is mid-sized (256 -> 256
@@ -946,6 +1009,7 @@ int hp_engine::lower32_winograd_forms(size_t i, step& st, const std::vector<floa
         std::vector<float> wu3((size_t)25 * p.Cout_pad * p.Cin);
         hp::conv32_winograd3_pack(packed.data(), p.Cout_pad, p.Cin, wu3.data());
         HP_TRY(upload(wu3, p.w_wino3));
+        st.kind = launch_kind::wino3;
         st.bytes += wbytes * (25.0 / 9 - 16.0 / 9);
     }
     return HP_OK;
@@ -961,7 +1025,7 @@ int hp_engine::lower32_winograd_forms(size_t i, step& st, const std::vector<floa
 // (a 3 x 3 layer the Winograd kernel has taken needs no direct-form fragments: they doubled its weight bytes in HBM)
 int hp_engine::lower32_direct_forms(size_t i, step& st, const std::vector<float>& packed, int room)
 {
-    auto& p = st.cp32;
+    auto& p = st.cp32();
     const int taps = p.KH * p.KW, cout_pad = p.Cout_pad;
     const bool dw_in_front = p.dw_w != nullptr;
     if (dtype != HP_DTYPE_F32S && !dw_in_front && (p.w_wino || (taps == 1 && cout_pad > 64)))
@@ -988,7 +1052,7 @@ int hp_engine::lower32_direct_forms(size_t i, step& st, const std::vector<float>
     std::vector<float> wf(wide.size());
     hp::conv32_frag_pack(wide.data(), taps, cout_pad, cin_s, wf.data());
     HP_TRY(upload(wf, p.w_frag));
-    st.cin_split = cin_s;
+    st.kind = launch_kind::direct, st.as<conv32_launch>().cin_split = cin_s;
     return HP_OK;
 }
 
@@ -998,25 +1062,26 @@ int hp_engine::lower32_head_in_front(size_t i, step& st, const float* w)
     const hp_layer &A = layers[i - 1], &L = layers[i];
     const tensor_info& tsrc = *tensors[A.in];
     const double opix = (double)geos[i].OH * geos[i].OW;
-    auto& p = st.cp32;
+    const hp::conv32_params second = st.cp32(); // (the other forms the layer had are dropped with the conv32_launch)
+    auto& hd = st.set<head32_launch>(launch_kind::head32);
+    auto& p = hd.cp = second;
     const size_t nwa = (size_t)A.cout * A.cin, nw = (size_t)L.cout * L.cin;
     const float* wa = blob(A.w_off, nwa, "weights", i - 1);
     if (!wa)
         return HP_ERR_INVALID;
-    HP_TRY(upload_padded(A.b_off, A.cout, A.cout, "bias", i - 1, st.hh.bias1));
+    HP_TRY(upload_padded(A.b_off, A.cout, A.cout, "bias", i - 1, hd.hh.bias1));
     std::vector<float> w1f(nwa);
     hp::conv32_frag_pack(wa, 1, A.cout, A.cin, w1f.data()); // ([1][HID][128] is the blob's own layout: HID rows of 128)
     const int tm2 = L.cout <= 32 ? 1 : 2;
     const std::vector<float> w2p = hp::wpack::padded(w, nw, (size_t)p.Cout_pad * L.cin); // [cout][HID] rows, zero rows up to 32 tm2
     std::vector<float> w2f((size_t)32 * tm2 * L.cin);
     hp::conv32_head_pack(w2p.data(), tm2, L.cin, w2f.data());
-    HP_TRY(upload(w1f, st.hh.w1_frag));
-    HP_TRY(upload(w2f, st.hh.w2_frag));
-    st.hh.HID = A.cout;
-    st.hh.slope1 = A.act == HP_ACT_NONE ? 1.f : A.act == HP_ACT_LEAKY ? A.act_param : 0.f;
-    st.hh.hi1 = A.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
+    HP_TRY(upload(w1f, hd.hh.w1_frag));
+    HP_TRY(upload(w2f, hd.hh.w2_frag));
+    hd.hh.HID = A.cout;
+    hd.hh.slope1 = A.act == HP_ACT_NONE ? 1.f : A.act == HP_ACT_LEAKY ? A.act_param : 0.f;
+    hd.hh.hi1 = A.act == HP_ACT_RELU6 ? 6.f : __builtin_huge_valf();
     p.in = tsrc.view32(A.in_coff);
-    st.head32 = true, st.wino = false, st.cin_split = 0;
     st.layer = (int)i - 1, st.n_layers = 2;
     st.flops = 2.0 * opix * ((double)A.cout * A.cin + (double)L.cout * L.cin);
     st.bytes = (double)tsrc.H * tsrc.W * A.cin * 4 + opix * L.cout * 4 + (double)(nwa + nw) * 4;
@@ -1037,7 +1102,7 @@ int hp_engine::lower32_dw(size_t i, step& st)
     const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
     if (!w)
         return HP_ERR_INVALID;
-    auto& p = st.dp32;
+    auto& p = st.set<hp::dw32_params>(launch_kind::dw32);
     HP_TRY(upload(hp::wpack::dw_taps32(w, L.cin), p.w));
     HP_TRY(upload_padded(L.b_off, L.cin, L.cin, "bias", i, p.bias));
     p.in = ti.view32(L.in_coff);
@@ -1053,7 +1118,7 @@ int hp_engine::lower32_dw(size_t i, step& st)
 int hp_engine::lower16_first(size_t i, step& st)
 {
     const hp_layer& L = layers[i];
-    auto& p = st.fp;
+    auto& p = st.set<hp::first_conv_params>(launch_kind::first16);
     const float* w = nullptr;
     HP_TRY(lower_first(i, st, p, w));
     p.w16 = nullptr;
@@ -1077,7 +1142,7 @@ int hp_engine::lower16_conv(size_t i, step& st)
     const float* w = blob(L.w_off, nw, "weights", i);
     if (!w)
         return HP_ERR_INVALID;
-    auto& p = st.cp;
+    auto& p = st.set<conv16_launch>(launch_kind::conv16).cp;
     HP_TRY(upload_padded(L.b_off, L.cout, cout_pad, "bias", i, p.bias));
     HP_TRY(upload_prelu(i, cout_pad, p.alpha));
     p.in = ti.view(L.in_coff);
@@ -1104,15 +1169,16 @@ int hp_engine::lower16_conv(size_t i, step& st)
 int hp_engine::lower16_i8(size_t i, step& st, const float* w)
 {
     const hp_layer& L = layers[i];
-    const auto& p = st.cp;
+    auto& c = st.as<conv16_launch>();
+    const auto& p = c.cp;
     const int taps = L.kh * L.kw;
     hp::wpack::i8_rows r = hp::wpack::quantize_rows(w, L.cout, taps, L.cin, p.Cout_pad, p.Cin);
-    HP_TRY(upload(r.q, st.q8.w));
-    HP_TRY(upload(std::vector<float>(p.Cout_pad, 0.f), st.q8.dq));
-    st.i8 = true, st.i8_dq = const_cast<float*>(st.q8.dq), st.q8.inv_a = 0.f;
-    st.q8.w_direct = nullptr;
+    HP_TRY(upload(r.q, c.q8.w));
+    HP_TRY(upload(std::vector<float>(p.Cout_pad, 0.f), c.q8.dq));
+    c.i8 = true, c.i8_dq = const_cast<float*>(c.q8.dq), c.q8.inv_a = 0.f;
+    c.q8.w_direct = nullptr;
     if (hp::conv_i8_direct_ok(p)) // the same q_w in conv_i8_direct_kernel's fragment order
-        HP_TRY(upload(hp::wpack::i8_direct(r.q, taps, p.Cout_pad, p.Cin), st.q8.w_direct));
+        HP_TRY(upload(hp::wpack::i8_direct(r.q, taps, p.Cout_pad, p.Cin), c.q8.w_direct));
     i8_sw[i] = std::move(r.s_w);
     return HP_OK;
 }
@@ -1128,7 +1194,7 @@ int hp_engine::lower16_dw(size_t i, step& st)
     const float* w = blob(L.w_off, (size_t)L.cin * 9, "weights", i);
     if (!w)
         return HP_ERR_INVALID;
-    auto& p = st.dp;
+    auto& p = st.set<hp::dw_params>(launch_kind::dw16);
     HP_TRY(upload(hp::wpack::dw_taps16(w, L.cin), p.w));
     HP_TRY(upload_padded(L.b_off, L.cin, L.cin, "bias", i, p.bias));
     p.in = ti.view(L.in_coff);
@@ -1154,7 +1220,7 @@ int hp_engine::lower16_head_pair(size_t i)
         return HP_ERR_INVALID;
     step st;
     st.layer = (int)i, st.op = OP_MLPHEAD, st.n_layers = 2; // (covers layers i and i + 1: the passes below must see every layer a step touches)
-    auto& p = st.hp_;
+    auto& p = st.set<hp::head_params>(launch_kind::head);
     HP_TRY(upload(hp::wpack::dense16(w1f, HID, 1, K1, HID, K1, 1), p.w1));
     HP_TRY(upload_padded(L.b_off, HID, HID, "bias", i, p.b1));
     HP_TRY(upload(hp::wpack::head_w2(w2f, Pn.cout, HID), p.w2));
@@ -1182,7 +1248,7 @@ int hp_engine::lower16_sep_pair(size_t i)
         return HP_ERR_INVALID;
     step st;
     st.layer = (int)i, st.op = OP_SEPCONV, st.n_layers = 2;
-    auto& p = st.sp;
+    auto& p = st.set<hp::sep_params>(launch_kind::sep);
     HP_TRY(upload(hp::wpack::dw_taps16(w, C), p.dw_w));
     HP_TRY(upload_padded(L.b_off, C, C, "bias", i, p.dw_bias));
     HP_TRY(upload(hp::wpack::dense16(pwf, Pn.cout, 1, C, cout_pad, C, 1), p.pw.w));
@@ -1211,7 +1277,7 @@ int hp_engine::plan_splitk()
         size_t need = 0;
         for (auto& st : steps) {
             size_t bytes = 0;
-            if (st.op == HP_OP_CONV && !st.first && !st.f32 && !switches.no_splitk && hp::conv_splitk(st.cp, &bytes) > 1)
+            if (st.kind == launch_kind::conv16 && !switches.no_splitk && hp::conv_splitk(st.cp(), &bytes) > 1)
                 need = std::max(need, bytes);
         }
         if (need) {
@@ -1219,10 +1285,10 @@ int hp_engine::plan_splitk()
             HP_TRY(weight_bufs.back()->alloc(need));
             void* const d = weight_bufs.back()->p;
             for (auto& st : steps)
-                if (st.op == HP_OP_CONV && !st.first && !st.f32) {
-                    const int ks = hp::conv_splitk(st.cp, nullptr);
+                if (st.kind == launch_kind::conv16) {
+                    const int ks = hp::conv_splitk(st.cp(), nullptr);
                     if (ks > 1)
-                        st.cp.ksplit = ks, st.cp.splitk = (float*)d;
+                        st.cp().ksplit = ks, st.cp().splitk = (float*)d;
                 }
         }
     }
@@ -1242,23 +1308,23 @@ int hp_engine::fuse_chains()
                 continue;
             hp::chain_params ch{};
             int n = 0;
-            const bool three = k + 2 < steps.size() && plain_conv(steps[k + 2]) && steps[k].cp.KH == 1;
+            const bool three = k + 2 < steps.size() && plain_conv(steps[k + 2]) && steps[k].cp().KH == 1;
             if (three) {
                 const int l0 = steps[k].layer, l1 = steps[k + 1].layer, l2 = steps[k + 2].layer;
                 const hp_layer &A = layers[l0], &Bn = layers[l1], &Cn = layers[l2];
                 if (Bn.in == A.out && Bn.in_coff == A.out_coff && Cn.in == Bn.out && Cn.in_coff == Bn.out_coff && A.res < 0 && Bn.res < 0
                     && (Cn.res < 0 || Cn.res == A.out) && A.out_coff == 0 && private_to(A.out, l1, l2) && private_to(Bn.out, l2, l2)) {
-                    ch.c0 = steps[k].cp, ch.c1 = steps[k + 1].cp, ch.c2 = steps[k + 2].cp;
+                    ch.c0 = steps[k].cp(), ch.c1 = steps[k + 1].cp(), ch.c2 = steps[k + 2].cp();
                     ch.has_c0 = 1, ch.res_mode = Cn.res >= 0 ? 3 : 0;
                     n = 3;
                 }
             }
-            if (!n && steps[k].cp.KH == 3) {
+            if (!n && steps[k].cp().KH == 3) {
                 const int l1 = steps[k].layer, l2 = steps[k + 1].layer;
                 const hp_layer &Bn = layers[l1], &Cn = layers[l2];
                 if (Cn.in == Bn.out && Cn.in_coff == Bn.out_coff && !(Bn.res >= 0 && Cn.res >= 0) && private_to(Bn.out, l2, l2)
                     && Cn.res != Bn.out) {
-                    ch.c1 = steps[k].cp, ch.c2 = steps[k + 1].cp;
+                    ch.c1 = steps[k].cp(), ch.c2 = steps[k + 1].cp();
                     ch.has_c0 = 0, ch.res_mode = Bn.res >= 0 ? 1 : Cn.res >= 0 ? 2 : 0;
                     n = 2;
                 }
@@ -1266,7 +1332,7 @@ int hp_engine::fuse_chains()
             if (!n || !hp::conv_chain_variant(ch))
                 continue;
             step& a = steps[k];
-            a.op = OP_CHAIN, a.ch = ch, a.n_layers = n;
+            a.op = OP_CHAIN, a.set<hp::chain_params>(launch_kind::chain) = ch, a.n_layers = n;
             for (int q = 1; q < n; ++q) {
                 a.flops += steps[k + q].flops;
                 tensors[layers[steps[k + q].layer].in]->elided = true; // allocated (pass 1) but never written
@@ -1291,20 +1357,20 @@ int hp_engine::fuse_bottlenecks()
                 continue;
             hp::bneck_params bn{};
             size_t ke = k; // the expansion's step
-            if (steps[k].cp.KH == 3 && k + 1 < steps.size() && plain_conv(steps[k + 1]) && steps[k + 1].cp.KH == 1) {
+            if (steps[k].cp().KH == 3 && k + 1 < steps.size() && plain_conv(steps[k + 1]) && steps[k + 1].cp().KH == 1) {
                 const hp_layer &A = layers[steps[k].layer], &E = layers[steps[k + 1].layer];
                 if (E.in == A.out && E.in_coff == A.out_coff && A.res < 0 && private_to(A.out, steps[k + 1].layer, steps[k + 1].layer)) {
-                    bn.c3 = steps[k].cp, bn.has_c3 = 1;
+                    bn.c3 = steps[k].cp(), bn.has_c3 = 1;
                     ke = k + 1;
                 }
             }
-            if (steps[ke].cp.KH != 1 || steps[ke].cp.Cout != 4 * steps[ke].cp.Cin)
+            if (steps[ke].cp().KH != 1 || steps[ke].cp().Cout != 4 * steps[ke].cp().Cin)
                 continue;
-            bn.ce = steps[ke].cp;
+            bn.ce = steps[ke].cp();
             const hp_layer& E = layers[steps[ke].layer];
             size_t kr = 0; // the reduction's step
             for (size_t j = ke + 1; j < steps.size() && j <= ke + 2 && !kr; ++j) {
-                if (!plain_conv(steps[j]) || steps[j].cp.KH != 1 || steps[j].cp.stride != 1)
+                if (!plain_conv(steps[j]) || steps[j].cp().KH != 1 || steps[j].cp().stride != 1)
                     continue;
                 const hp_layer& R = layers[steps[j].layer];
                 if (R.in != E.out || R.in_coff != E.out_coff || R.res >= 0)
@@ -1318,7 +1384,7 @@ int hp_engine::fuse_bottlenecks()
                     kr = j;
             }
             if (kr)
-                bn.cr = steps[kr].cp, bn.has_cr = 1;
+                bn.cr = steps[kr].cp(), bn.has_cr = 1;
             // the block's shortcut is a projection of the block input that nobody else reads (the first block of a stage at stride 1):
             // computed inside the launch instead of written by one launch and read by the next
             size_t kp = steps.size();
@@ -1328,13 +1394,13 @@ int hp_engine::fuse_bottlenecks()
                     if (!plain_conv(steps[j]) || layers[steps[j].layer].out != E.res)
                         continue;
                     const hp_layer& P = layers[steps[j].layer];
-                    if (steps[j].cp.KH == 1 && steps[j].cp.stride == 1 && P.res < 0 && P.out_coff == 0 && P.act == HP_ACT_NONE && res_private)
+                    if (steps[j].cp().KH == 1 && steps[j].cp().stride == 1 && P.res < 0 && P.out_coff == 0 && P.act == HP_ACT_NONE && res_private)
                         kp = j;
                 }
             }
             const hp::tview res_view = bn.ce.res;
             if (kp < steps.size())
-                bn.cp = steps[kp].cp, bn.has_cp = 1, bn.ce.res = NO_RES;
+                bn.cp = steps[kp].cp(), bn.has_cp = 1, bn.ce.res = NO_RES;
             // ... and the block's own reduction reads the same block input and feeds only this 3x3: computed on the 3x3's halo tile
             size_t k0 = steps.size();
             if (kp < steps.size() && bn.has_c3) {
@@ -1344,12 +1410,12 @@ int hp_engine::fuse_bottlenecks()
                     if (!plain_conv(steps[j]) || layers[steps[j].layer].out != A3.in)
                         continue;
                     const hp_layer& R = layers[steps[j].layer];
-                    if (steps[j].cp.KH == 1 && steps[j].cp.stride == 1 && R.res < 0 && R.out_coff == 0 && A3.in_coff == 0 && R.in == P.in && R.in_coff == P.in_coff
+                    if (steps[j].cp().KH == 1 && steps[j].cp().stride == 1 && R.res < 0 && R.out_coff == 0 && A3.in_coff == 0 && R.in == P.in && R.in_coff == P.in_coff
                         && in_private)
                         k0 = j;
                 }
                 if (k0 < steps.size())
-                    bn.c0 = steps[k0].cp, bn.has_c0 = 1;
+                    bn.c0 = steps[k0].cp(), bn.has_c0 = 1;
             }
             // the stand-alone kernels of some of these shapes (256 -> 64 on the generic implicit GEMM) read row-major weights: the
             // fused kernel wants them in fragment order
@@ -1408,7 +1474,7 @@ int hp_engine::fuse_bottlenecks()
             step& a = steps[k];
             const double fl = (bn.has_c3 ? steps[ke].flops : 0) + (kr ? steps[kr].flops : 0) + (bn.has_cp ? steps[kp].flops : 0) + (bn.has_c0 ? steps[k0].flops : 0);
             const double by = (bn.has_c3 ? steps[ke].bytes : 0) + (kr ? steps[kr].bytes : 0);
-            a.op = OP_BNECK, a.bn = bn, a.n_layers = 1 + bn.has_c3 + bn.has_cr + bn.has_cp + bn.has_c0;
+            a.op = OP_BNECK, a.set<hp::bneck_params>(launch_kind::bneck) = bn, a.n_layers = 1 + bn.has_c3 + bn.has_cr + bn.has_cp + bn.has_c0;
             a.flops += fl, a.bytes += by;
             if (bn.has_c3)
                 tensors[layers[steps[ke].layer].in]->elided = true; // the 3x3's output: allocated (pass 1) but never written
@@ -1443,18 +1509,18 @@ int hp_engine::fuse_sep_pairs()
     if (!switches.no_seppair && !no_fuse && !f32) {
         for (size_t k = 0; k + 1 < steps.size(); ++k) {
             step &a = steps[k], &b = steps[k + 1];
-            if (a.op != OP_SEPCONV || b.op != OP_SEPCONV || a.sep_pair || b.sep_pair)
+            if (a.kind != launch_kind::sep || b.kind != launch_kind::sep)
                 continue;
             const hp_layer &Pa = layers[a.layer + 1], &Db = layers[b.layer];
             if (Db.in != Pa.out || Db.in_coff != Pa.out_coff)
                 continue;
-            hp::seppair_params pp{ a.sp, b.sp };
+            const hp::seppair_params pp{ a.as<hp::sep_params>(), b.as<hp::sep_params>() };
             // (nobody but block b's depthwise layer reads the tensor in between, block a alone writes it, and it is no network output)
             if (!private_to(Pa.out, b.layer, b.layer) || !hp::seppair_variant(pp))
                 continue;
-            a.sp2 = b.sp, a.sep_pair = true, a.n_layers += b.n_layers;
+            a.set<sep_pair_launch>(launch_kind::sep_pair) = { pp.a, pp.b }, a.n_layers += b.n_layers;
             a.flops += b.flops;
-            a.bytes = a.bytes + b.bytes - 2.0 * (double)a.sp.OH * a.sp.OW * Pa.cout * 2; // the tensor in between is neither written nor read
+            a.bytes = a.bytes + b.bytes - 2.0 * (double)pp.a.OH * pp.a.OW * Pa.cout * 2; // the tensor in between is neither written nor read
             tensors[Pa.out]->elided = true; // allocated (pass 1) but never written
             steps.erase(steps.begin() + k + 1);
         }
@@ -1469,12 +1535,12 @@ int hp_engine::pair_heads()
     if (!switches.no_pair_heads && !f32) {
         for (size_t k = 0; k + 1 < steps.size(); ++k) {
             step &a = steps[k], &b = steps[k + 1];
-            if (a.op != OP_MLPHEAD || b.op != OP_MLPHEAD || a.paired)
+            if (a.kind != launch_kind::head || b.kind != launch_kind::head)
                 continue;
-            const auto &x = a.hp_, &y = b.hp_;
+            const hp::head_params x = a.as<hp::head_params>(), y = b.as<hp::head_params>();
             if (x.in.p != y.in.p || x.in.coff != y.in.coff || x.K1 != y.K1 || x.H != y.H || x.W != y.W || x.pw.Cout > 64 || y.pw.Cout > 64)
                 continue;
-            a.hp2_ = b.hp_, a.paired = true, a.n_layers += b.n_layers;
+            a.set<head_pair_launch>(launch_kind::head_pair) = { x, y }, a.n_layers += b.n_layers;
             a.flops += b.flops, a.bytes += b.bytes;
             steps.erase(steps.begin() + k + 1);
         }
@@ -1484,7 +1550,7 @@ int hp_engine::pair_heads()
 
 int hp_engine::finish(const hp_engine_desc* d)
 {
-    HP_REQUIRE(!steps.empty() && steps[0].first, HP_ERR_INVALID, "engine: the first layer must be a CONV reading tensor 0");
+    HP_REQUIRE(!steps.empty() && (steps[0].kind == launch_kind::first16 || steps[0].kind == launch_kind::first32), HP_ERR_INVALID, "engine: the first layer must be a CONV reading tensor 0");
 
     HP_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     HP_HIP_TRY(hipEventCreate(&ev0));
@@ -1525,16 +1591,17 @@ int hp_engine::check_int8_scales(const float* s, int n, bool allow_uncalibrated)
 int hp_engine::apply_int8_scales()
 {
     for (auto& st : steps) {
-        if (!st.i8)
+        conv16_launch* const c = st.int8();
+        if (!c)
             continue;
         const float sa = i8_scale[st.layer];
         const std::vector<float>& s_w = i8_sw[st.layer];
-        std::vector<float> dq(st.cp.Cout_pad, 0.f);
+        std::vector<float> dq(c->cp.Cout_pad, 0.f);
         if (sa > 0.f)
             for (size_t c = 0; c < s_w.size(); ++c)
                 dq[c] = sa * s_w[c]; // dq[c] = s_a * s_w[c], one fp32 product
-        st.q8.inv_a = sa > 0.f ? 1.0f / sa : 0.f;
-        HP_HIP_TRY(hipMemcpy(st.i8_dq, dq.data(), dq.size() * sizeof(float), hipMemcpyHostToDevice));
+        c->q8.inv_a = sa > 0.f ? 1.0f / sa : 0.f;
+        HP_HIP_TRY(hipMemcpy(c->i8_dq, dq.data(), dq.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     return HP_OK;
 }
@@ -1553,357 +1620,289 @@ int hp_engine::drop_graphs()
 }
 
 namespace {
-// frames [b0, ..) of a tensor view / of a step's fp32 launch parameters (the second half-batch of hp_engine_set_concurrency): copies, every
-// view moved by b0 images
-inline hp::tview32 at_frame(hp::tview32 v, int b0)
+// ---- bind(P, n, b0): a copy of a launch's parameters for frames [b0, b0 + n) of the batch: B (and npix, where the struct has it) for n frames,
+// every activation view and out_f32 moved by b0 frames.  One overload per parameter struct, the generic one for those that are alike.
+// (b0 > 0 is the second half-batch of hp_engine_set_concurrency, which the fp32 engines have: hp_engine::halves_ok.)
+template <typename V> // tview / tview32
+V at_frame(V v, int b0)
 {
     if (v.p)
         v.p += (long)b0 * v.img * v.cs;
     return v;
 }
-hp::conv32_params at_frame(hp::conv32_params p, int b0)
+template <typename P> // conv_params / conv32_params as a member of a fused launch: everything but npix, which those kernels do not read
+P frames(P p, int n, int b0)
 {
+    p.B = n;
     p.in = at_frame(p.in, b0), p.out = at_frame(p.out, b0), p.res = at_frame(p.res, b0);
     if (p.out_f32)
         p.out_f32 += (size_t)b0 * p.Cout * p.OH * p.OW;
     return p;
 }
-hp::dw32_params at_frame(hp::dw32_params p, int b0)
+template <typename P> // depthwise, max-pool, up-sampling of both precisions: one input and one output view
+P bind(P p, int n, int b0)
 {
+    p.B = n;
     p.in = at_frame(p.in, b0), p.out = at_frame(p.out, b0);
     return p;
 }
-hp::pool32_params at_frame(hp::pool32_params p, int b0)
+template <typename P> // the first convolutions of both precisions read the call's batch (u8 HWC or f32 NCHW, `frame` elements per image)
+P bind(P p, const uint8_t* u8, const float* f32, size_t frame, int n, int b0)
 {
-    p.in = at_frame(p.in, b0), p.out = at_frame(p.out, b0);
+    p.B = n;
+    p.in_u8 = u8 ? u8 + b0 * frame : nullptr, p.in_f32 = f32 ? f32 + b0 * frame : nullptr;
+    p.out = at_frame(p.out, b0);
     return p;
 }
-
-// conv32_kernel's residency stamps (HP_DIRECT_DBG): every block's (start, end) on the 100 MHz clock and the CU it ran on (XCC_ID, HW_ID: se_id
-// [15:13], sh_id [12], cu_id [11:8]) at h[128 + 3 b], b < 4096
-void print_conv32_residency(const unsigned long long* h)
+hp::conv_params bind(hp::conv_params p, int n, int b0)
 {
-    struct blk { unsigned long long t0, t1; unsigned cu; };
-    std::vector<blk> bl;
-    unsigned long long tmin = ~0ull, tmax = 0;
-    for (int b = 0; b < 4096; ++b) {
-        const unsigned long long t0 = h[128 + 3 * b], t1 = h[128 + 3 * b + 1], id = h[128 + 3 * b + 2];
-        if (!t0 || !t1)
-            continue;
-        bl.push_back({ t0, t1, (unsigned)(((id >> 32) & 0xf) << 8 | ((id >> 8) & 0xff)) });
-        tmin = std::min(tmin, t0), tmax = std::max(tmax, t1);
-    }
-    if (bl.empty())
-        return;
-    std::map<unsigned, std::vector<std::pair<unsigned long long, int>>> ev; // per CU: (time, +1 / -1)
-    double dsum = 0, dmin = 1e30, dmax = 0;
-    for (const auto& b : bl) {
-        ev[b.cu].push_back({ b.t0, +1 }), ev[b.cu].push_back({ b.t1, -1 });
-        const double d = (b.t1 - b.t0) * 0.01;
-        dsum += d, dmin = std::min(dmin, d), dmax = std::max(dmax, d);
-    }
-    int peak = 0;
-    std::map<int, int> blocks_per_cu, peak_hist;
-    for (auto& kv : ev) {
-        std::sort(kv.second.begin(), kv.second.end());
-        int cur = 0, pk = 0;
-        for (auto& e2 : kv.second)
-            cur += e2.second, pk = std::max(pk, cur);
-        peak = std::max(peak, pk), ++peak_hist[pk], ++blocks_per_cu[(int)kv.second.size() / 2];
-    }
-    fprintf(stderr, "  residency: %zu blocks on %zu CUs in %.2f us (first start -> last end); block duration %.2f .. %.2f us, mean %.2f; peak resident blocks per CU:",
-        bl.size(), ev.size(), (tmax - tmin) * 0.01, dmin, dmax, dsum / bl.size());
-    for (auto& kv : peak_hist)
-        fprintf(stderr, " %d x%d", kv.first, kv.second);
-    fprintf(stderr, "; blocks run per CU:");
-    for (auto& kv : blocks_per_cu)
-        fprintf(stderr, " %d x%d", kv.first, kv.second);
-    fprintf(stderr, "; active blocks at 10 %% .. 90 %% of the launch:");
-    for (int k = 1; k < 10; ++k) {
-        const unsigned long long t = tmin + (tmax - tmin) * k / 10;
-        int a = 0;
-        for (const auto& b : bl)
-            a += b.t0 <= t && t < b.t1;
-        fprintf(stderr, " %d", a);
-    }
-    // block 9 (the one with the s_memtime stamps) on the 100 MHz clock; duration histogram; mean duration per XCD; starts of the late blocks
-    fprintf(stderr, "; block 9: %.2f us", (h[128 + 3 * 9 + 1] - h[128 + 3 * 9]) * 0.01);
-    fprintf(stderr, "; durations (10 bins from min to max):");
-    int hist[10] = { 0 };
-    for (const auto& b : bl)
-        ++hist[std::min(9, (int)(((b.t1 - b.t0) * 0.01 - dmin) / std::max(1e-9, dmax - dmin) * 10))];
-    for (int k = 0; k < 10; ++k)
-        fprintf(stderr, " %d", hist[k]);
-    double xs[16] = { 0 };
-    int xn[16] = { 0 };
-    for (const auto& b : bl)
-        xs[(b.cu >> 8) & 15] += (b.t1 - b.t0) * 0.01, ++xn[(b.cu >> 8) & 15];
-    fprintf(stderr, "; mean duration per XCD:");
-    for (int k = 0; k < 16; ++k)
-        if (xn[k])
-            fprintf(stderr, " %.1f", xs[k] / xn[k]);
-    double late0 = 1e30, late_d = 0;
-    int nlate = 0;
-    for (const auto& b : bl)
-        if ((b.t0 - tmin) * 0.01 > 5.0)
-            late0 = std::min(late0, (b.t0 - tmin) * 0.01), late_d += (b.t1 - b.t0) * 0.01, ++nlate;
-    if (nlate)
-        fprintf(stderr, "; %d blocks started later than 5 us after the first (earliest at %.1f us), their mean duration %.2f us", nlate, late0, late_d / nlate);
-    fprintf(stderr, "\n");
+    p = frames(p, n, b0), p.npix = n * p.OH * p.OW;
+    return p;
 }
-
-// (start, end) of the first 1024 blocks on the 100 MHz clock at h[64 + 2 i]: their number, first start -> last end, the spread of their starts and durations
-struct block_spans {
-    int nb = 0;
-    unsigned long long t0 = ~0ull, t1 = 0, smax = 0, dmin = ~0ull, dmax = 0, dsum = 0;
-    explicit block_spans(const unsigned long long* h)
-    {
-        for (int i = 0; i < 1024 && h[64 + 2 * i]; ++i, ++nb) {
-            const unsigned long long d = h[65 + 2 * i] - h[64 + 2 * i];
-            t0 = std::min(t0, h[64 + 2 * i]), t1 = std::max(t1, h[65 + 2 * i]), smax = std::max(smax, h[64 + 2 * i]);
-            dmin = std::min(dmin, d), dmax = std::max(dmax, d), dsum += d;
-        }
-    }
-};
+hp::conv32_params bind(hp::conv32_params p, int n, int b0)
+{
+    p = frames(p, n, b0), p.npix = n * p.OH * p.OW;
+    return p;
+}
+hp::sep_params bind(hp::sep_params p, int n, int b0)
+{
+    p.B = n, p.in = at_frame(p.in, b0);
+    p.pw = frames(p.pw, n, b0), p.pw.npix = n * p.OH * p.OW;
+    return p;
+}
+hp::head_params bind(hp::head_params p, int n, int b0)
+{
+    p.B = n, p.in = at_frame(p.in, b0);
+    p.pw = frames(p.pw, n, b0);
+    return p;
+}
+hp::chain_params bind(hp::chain_params p, int n, int b0)
+{
+    for (hp::conv_params* c : { &p.c0, &p.c1, &p.c2 })
+        *c = frames(*c, n, b0);
+    return p;
+}
+hp::bneck_params bind(hp::bneck_params p, int n, int b0)
+{
+    for (hp::conv_params* c : { &p.c3, &p.ce, &p.cr, &p.cp, &p.c0 })
+        *c = frames(*c, n, b0);
+    return p;
+}
 } // namespace
 
-// HP_CONV_DBG / HP_BN_DBG / HP_CHAIN_DBG / HP_SEP_DBG / HP_DIRECT_DBG: the step's kernel launched once more with its block-timeline stamps
-// (s_memtime = shader cycles; the 100 MHz clock) written into a zeroed scratch buffer, printed to stderr per launch.  q32 = the fp32 layer's
-// parameters as just launched (nullptr for fp16 steps).  Steps without a timeline print nothing.
-int hp_engine::print_timeline(const step& st, const hp::conv32_params* q32, hipStream_t s)
+launch_payload hp_engine::bound(const step& st, const uint8_t* u8, const float* f32, int n, int b0) const
 {
-    enum { NONE, CONV, BNECK, CHAIN, SEP, WINO3, WINO, DIRECT, CONV32 } kind = NONE;
-    size_t words = 0;
-    if (q32 && st.f32 && st.op == HP_OP_CONV && !st.first && !st.head32 && switches.dbg_direct) {
-        kind = st.wino ? (q32->w_wino3 ? WINO3 : WINO) : st.cin_split ? DIRECT : q32->Cin >= switches.dbg_min_cin ? CONV32 : NONE;
-        words = kind == WINO ? 128 : kind == CONV32 ? 128 + 3 * 4096 : 64;
-    } else if (!st.f32 && st.op == HP_OP_CONV && !st.first && !i8_on(st) && switches.dbg_conv && hp::conv_mfma_tile(st.cp) / 100000 == 52)
-        kind = CONV, words = 64; // the pixel-block GEMM
-    else if (st.op == OP_BNECK && switches.dbg_bn)
-        kind = BNECK, words = 64 + 2 * 1024;
-    else if (st.op == OP_CHAIN && switches.dbg_chain)
-        kind = CHAIN, words = 32;
-    else if (st.op == OP_SEPCONV && !st.sep_pair && switches.dbg_sep)
-        kind = SEP, words = 64 + 2 * 1024 + 64; // [0, 64) block 0's stamps, then (start, end) of the first 1024 blocks, then wavefront 4 of block 1
-    if (kind == NONE)
-        return HP_OK;
-    hp::dev_buf buf;
-    HP_TRY(buf.alloc(words * 8));
-    HP_HIP_TRY(hipMemset(buf.p, 0, words * 8));
-    unsigned long long* const dbg = buf.as<unsigned long long>();
-    hp::conv32_params q = q32 ? *q32 : hp::conv32_params{};
-    q.dbg = dbg;
-    const bool split = dtype == HP_DTYPE_F32S && !split_off;
-    if (kind == CONV) {
-        hp::conv_params c = st.cp;
-        c.dbg = dbg;
-        HP_HIP_TRY(hp::launch_conv_mfma(c, s));
-    } else if (kind == BNECK) {
-        hp::bneck_params b = st.bn;
-        b.ce.dbg = dbg;
-        HP_HIP_TRY(hp::launch_bottleneck(b, s));
-    } else if (kind == CHAIN) {
-        hp::chain_params c = st.ch;
-        c.c2.dbg = dbg;
-        HP_HIP_TRY(hp::launch_conv_chain(c, s));
-    } else if (kind == SEP) {
-        hp::sep_params p = st.sp;
-        p.pw.dbg = dbg;
-        HP_HIP_TRY(hp::launch_sepconv(p, s));
-    } else if (kind == WINO3)
-        HP_HIP_TRY(hp::launch_conv32_winograd3(q, s));
-    else if (kind == WINO)
-        HP_HIP_TRY(hp::launch_conv32_winograd(q, switches, s));
-    else if (kind == DIRECT)
-        HP_HIP_TRY(hp::launch_conv32_direct(q, split, s));
-    else
-        HP_HIP_TRY(hp::launch_conv32(q, switches, s));
-    HP_HIP_TRY(hipStreamSynchronize(s));
-    std::vector<unsigned long long> hv(words);
-    const unsigned long long* h = hv.data();
-    HP_HIP_TRY(hipMemcpy(hv.data(), dbg, words * 8, hipMemcpyDeviceToHost));
-    auto deltas = [h](int from, int to) {
-        for (int i = from; i < to && h[i]; ++i)
-            fprintf(stderr, " %llu", h[i] - h[i - 1]);
-    };
+    const size_t frame = (size_t)in_h * in_w * 3;
+    switch (st.kind) {
+    case launch_kind::first16: return bind(st.as<hp::first_conv_params>(), u8, f32, frame, n, b0);
+    case launch_kind::conv16: {
+        conv16_launch c = st.as<conv16_launch>();
+        c.cp = bind(c.cp, n, b0);
+        if ((c.i8 = i8_on(st))) // (calibration zeroes the scales for a while: not a property of the schedule)
+            c.q8.c = c.cp;
+        return c;
+    }
+    case launch_kind::dw16: return bind(st.as<hp::dw_params>(), n, b0);
+    case launch_kind::maxpool16:
+    case launch_kind::upsample16: return bind(st.as<hp::pool_params>(), n, b0);
+    case launch_kind::sep: return bind(st.as<hp::sep_params>(), n, b0);
+    case launch_kind::sep_pair: return sep_pair_launch{ bind(st.as<sep_pair_launch>().a, n, b0), bind(st.as<sep_pair_launch>().b, n, b0) };
+    case launch_kind::head: return bind(st.as<hp::head_params>(), n, b0);
+    case launch_kind::head_pair: return head_pair_launch{ bind(st.as<head_pair_launch>().a, n, b0), bind(st.as<head_pair_launch>().b, n, b0) };
+    case launch_kind::chain: return bind(st.as<hp::chain_params>(), n, b0);
+    case launch_kind::bneck: return bind(st.as<hp::bneck_params>(), n, b0);
+    case launch_kind::first32: return bind(st.as<hp::first_conv32_params>(), u8, f32, frame, n, b0);
+    case launch_kind::conv32:
+    case launch_kind::wino2:
+    case launch_kind::wino3:
+    case launch_kind::direct: {
+        conv32_launch c = st.as<conv32_launch>();
+        c.cp = bind(c.cp, n, b0);
+        if (st.kind == launch_kind::direct)
+            c.cp.Cin = c.cin_split;
+        else if (st.kind != launch_kind::conv32)
+            c.cp.latency = parts > 1;
+        return c;
+    }
+    case launch_kind::head32: return head32_launch{ bind(st.as<head32_launch>().cp, n, b0), st.as<head32_launch>().hh };
+    case launch_kind::dw32: return bind(st.as<hp::dw32_params>(), n, b0);
+    case launch_kind::maxpool32:
+    case launch_kind::upsample32: return bind(st.as<hp::pool32_params>(), n, b0);
+    }
+    return {};
+}
+
+// The one place that knows which launcher a kind has.  dbg != nullptr: the HP_*_DBG relaunch, the family's debug field set on the bound copy.
+int hp_engine::launch(launch_kind kind, launch_payload& b, hipStream_t s, unsigned long long* dbg) const
+{
+    const bool split = dtype == HP_DTYPE_F32S && !split_off; // the direct kernel: on the fp16 pipe until a value left fp16's range, then on the fp32 pipe
     switch (kind) {
-    case CONV:
-        fprintf(stderr, "conv layer %d %d->%d tile %d consumer:", st.layer, st.cp.Cin, st.cp.Cout, hp::conv_mfma_tile(st.cp));
-        deltas(1, 32);
-        fprintf(stderr, " | producer (from consumer start %lld):", (long long)(h[32] - h[0]));
-        deltas(33, 64);
-        fprintf(stderr, "\n");
-        break;
-    case BNECK: { // block 0's phase timeline and the start / end of the first 1024 blocks
-        fprintf(stderr, "bottleneck layer %d variant %d timeline:", st.layer, hp::bottleneck_variant(st.bn));
-        deltas(1, 60);
-        const block_spans b(h);
-        if (b.nb)
-            fprintf(stderr, "\n  first %d blocks: %.2f us from first start to last end; block duration %.2f .. %.2f us, mean %.2f", b.nb, (b.t1 - b.t0) * 0.01,
-                b.dmin * 0.01, b.dmax * 0.01, b.dsum * 0.01 / b.nb);
-        fprintf(stderr, "\n");
+    case launch_kind::first16: HP_HIP_TRY(hp::launch_first_conv(std::get<hp::first_conv_params>(b), s)); break;
+    case launch_kind::conv16: {
+        auto& c = std::get<conv16_launch>(b);
+        c.cp.dbg = dbg;
+        HP_HIP_TRY(c.i8 ? hp::launch_conv_i8(c.q8, s) : hp::launch_conv_mfma(c.cp, s));
         break;
     }
-    case CHAIN:
-        fprintf(stderr, "chain layer %d variant %d timeline:", st.layer, hp::conv_chain_variant(st.ch));
-        deltas(1, 32);
-        fprintf(stderr, "\n");
+    case launch_kind::dw16: HP_HIP_TRY(hp::launch_dwconv3x3(std::get<hp::dw_params>(b), s)); break;
+    case launch_kind::maxpool16: HP_HIP_TRY(hp::launch_maxpool(std::get<hp::pool_params>(b), s)); break;
+    case launch_kind::upsample16: HP_HIP_TRY(hp::launch_upsample(std::get<hp::pool_params>(b), s)); break;
+    case launch_kind::sep:
+        std::get<hp::sep_params>(b).pw.dbg = dbg;
+        HP_HIP_TRY(hp::launch_sepconv(std::get<hp::sep_params>(b), s));
         break;
-    case SEP:
-        fprintf(stderr, "sep layer %d C=%d timeline:", st.layer, st.sp.C);
-        deltas(1, 40);
-        if (h[41])
-            fprintf(stderr, " | total-to-epi0 %llu pass1 %llu epi1 %llu | total %llu", h[41] - h[0], h[42] - h[41], h[43] - h[42], h[43] - h[0]);
-        fprintf(stderr, "\n");
-        if (h[2112]) {
-            fprintf(stderr, "  wavefront 4 of block 1:");
-            for (int i = 1; i < 40 && h[2112 + i]; ++i)
-                fprintf(stderr, " %llu", h[2112 + i] - h[2112 + i - 1]);
-            fprintf(stderr, "\n");
-        }
-        if (h[64]) {
-            const block_spans b(h);
-            fprintf(stderr, "  %d blocks: first start -> last end %.2f us, starts spread over %.2f us, block duration %.2f .. %.2f us\n", b.nb,
-                (b.t1 - b.t0) * 0.01, (b.smax - b.t0) * 0.01, b.dmin * 0.01, b.dmax * 0.01);
-        }
+    case launch_kind::sep_pair: HP_HIP_TRY(hp::launch_seppair(hp::seppair_params{ std::get<sep_pair_launch>(b).a, std::get<sep_pair_launch>(b).b }, s)); break;
+    case launch_kind::head: HP_HIP_TRY(hp::launch_mlp_head(std::get<hp::head_params>(b), s)); break;
+    case launch_kind::head_pair: HP_HIP_TRY(hp::launch_mlp_head_pair(std::get<head_pair_launch>(b).a, std::get<head_pair_launch>(b).b, s)); break;
+    case launch_kind::chain:
+        std::get<hp::chain_params>(b).c2.dbg = dbg;
+        HP_HIP_TRY(hp::launch_conv_chain(std::get<hp::chain_params>(b), s));
         break;
-    case WINO3: // block 9, thread 0
-        fprintf(stderr, "winograd3 layer %d %d->%d cycles [start | chunk 0 transformed | per chunk: patch stored, multiplied | output transformed | stored]:", st.layer, q.Cin, q.Cout);
-        deltas(1, 60);
-        fprintf(stderr, "\n");
+    case launch_kind::bneck:
+        std::get<hp::bneck_params>(b).ce.dbg = dbg;
+        HP_HIP_TRY(hp::launch_bottleneck(std::get<hp::bneck_params>(b), s));
         break;
-    case WINO: { // block (1, 0), thread 0
-        fprintf(stderr, "winograd layer %d %d->%d tile %d cycles [chunk 0 staged | transformed, chunk 1 stored | per chunk: multiplied, next patch stored | epilogue requests | output transform | slab complete | stored]:", st.layer, q.Cin, q.Cout,
-            hp::conv32_winograd_tile(q));
-        deltas(1, 119);
-        int occ = 0;
-        (void)hp::conv32_winograd_occupancy(q, &occ);
-        fprintf(stderr, " | s_memtime ticks %llu in %llu ticks of the 100 MHz clock; blocks per CU %d\n", h[121] - h[119], h[122] - h[120], occ);
+    case launch_kind::first32: HP_HIP_TRY(hp::launch_first_conv32(std::get<hp::first_conv32_params>(b), switches, s)); break;
+    case launch_kind::conv32:
+    case launch_kind::wino2:
+    case launch_kind::wino3:
+    case launch_kind::direct: {
+        hp::conv32_params& cp = std::get<conv32_launch>(b).cp;
+        cp.dbg = dbg;
+        HP_HIP_TRY(kind == launch_kind::conv32 ? hp::launch_conv32(cp, switches, s)
+                : kind == launch_kind::wino2   ? hp::launch_conv32_winograd(cp, switches, s)
+                : kind == launch_kind::wino3   ? hp::launch_conv32_winograd3(cp, s)
+                                               : hp::launch_conv32_direct(cp, split, s));
         break;
     }
-    case DIRECT: // block (1, 0), thread 0
-        fprintf(stderr, "direct layer %d %dx%d %d->%d tile %d cycles [start | staged, multiplied per chunk | stored]:", st.layer, q.KH, q.KW, q.Cin, q.Cout,
-            hp::conv32_direct_tile(q, split));
-        deltas(1, 64);
-        fprintf(stderr, "\n");
-        break;
-    default: // CONV32: block 9, thread 0: start | first tile staged | every 8 K-steps | stored; then every block's residency
-        fprintf(stderr, "conv32 layer %d %dx%d %d->%d tile %d cycles [start | staged | per 8 K-steps | stored]:", st.layer, q.KH, q.KW, q.Cin, q.Cout, hp::conv32_tile(q, switches));
-        deltas(1, 128);
-        fprintf(stderr, "\n");
-        print_conv32_residency(h);
-        break;
+    case launch_kind::head32: HP_HIP_TRY(hp::launch_conv32_head(std::get<head32_launch>(b).cp, std::get<head32_launch>(b).hh, s)); break;
+    case launch_kind::dw32: HP_HIP_TRY(hp::launch_dwconv32(std::get<hp::dw32_params>(b), switches, s)); break;
+    case launch_kind::maxpool32: HP_HIP_TRY(hp::launch_maxpool32(std::get<hp::pool32_params>(b), s)); break;
+    case launch_kind::upsample32: HP_HIP_TRY(hp::launch_upsample32(std::get<hp::pool32_params>(b), s)); break;
     }
     return HP_OK;
 }
 
-int hp_engine::run_step(step& st, const uint8_t* u8, const float* f32, int n, hipStream_t s, int b0)
+// hp_layer_time::tile of a bound launch: exactly the struct its launcher gets
+int hp_engine::tile_of(launch_kind kind, const launch_payload& b) const
 {
-    if (st.f32) {
-        // b0 > 0 (the second half-batch of hp_engine_set_concurrency): the same step on frames [b0, b0 + n), launched with moved copies of its
-        // parameters; b0 = 0 launches (and keeps) the step's own
-        const size_t in_off = (size_t)b0 * in_h * in_w * 3;
-        hp::conv32_params moved;
-        hp::conv32_params& cp = b0 ? (moved = at_frame(st.cp32, b0)) : st.cp32;
-        if (st.first) {
-            hp::first_conv32_params p = st.fp32;
-            p.out = at_frame(p.out, b0);
-            p.in_u8 = u8 ? u8 + in_off : nullptr, p.in_f32 = f32 ? f32 + in_off : nullptr, p.B = n;
-            if (!b0)
-                st.fp32 = p;
-            HP_HIP_TRY(hp::launch_first_conv32(p, switches, s));
-        } else if (st.op == HP_OP_CONV) {
-            cp.B = n, cp.npix = n * cp.OH * cp.OW;
-            if (st.head32) {
-                HP_HIP_TRY(hp::launch_conv32_head(cp, st.hh, s));
-            } else if (st.wino) {
-                cp.latency = parts > 1;
-                if (cp.w_wino3)
-                    HP_HIP_TRY(hp::launch_conv32_winograd3(cp, s));
-                else
-                    HP_HIP_TRY(hp::launch_conv32_winograd(cp, switches, s));
-            } else if (st.cin_split) { // the direct kernel: on the fp16 pipe (HP_DTYPE_F32S until a value left fp16's range) or on the fp32 pipe
-                hp::conv32_params q = cp;
-                q.Cin = st.cin_split;
-                HP_HIP_TRY(hp::launch_conv32_direct(q, dtype == HP_DTYPE_F32S && !split_off, s));
-                return print_timeline(st, &q, s);
-            } else
-                HP_HIP_TRY(hp::launch_conv32(cp, switches, s));
-            return print_timeline(st, &cp, s);
-        } else if (st.op == HP_OP_DWCONV) {
-            hp::dw32_params p = b0 ? at_frame(st.dp32, b0) : st.dp32;
-            p.B = n;
-            if (!b0)
-                st.dp32.B = n;
-            HP_HIP_TRY(hp::launch_dwconv32(p, switches, s));
-        } else {
-            hp::pool32_params p = b0 ? at_frame(st.pp32, b0) : st.pp32;
-            p.B = n;
-            if (!b0)
-                st.pp32.B = n;
-            HP_HIP_TRY(st.op == HP_OP_UPSAMPLE ? hp::launch_upsample32(p, s) : hp::launch_maxpool32(p, s));
-        }
-        return HP_OK;
+    switch (kind) {
+    case launch_kind::conv16: {
+        const auto& c = std::get<conv16_launch>(b);
+        return c.i8 ? hp::conv_i8_tile(c.cp) : hp::conv_mfma_tile(c.cp);
     }
-    if (st.first) {
-        st.fp.in_u8 = u8, st.fp.in_f32 = f32, st.fp.B = n;
-        HP_HIP_TRY(hp::launch_first_conv(st.fp, s));
-    } else if (st.op == HP_OP_CONV && i8_on(st)) {
-        st.cp.B = n, st.cp.npix = n * st.cp.OH * st.cp.OW;
-        st.q8.c = st.cp;
-        HP_HIP_TRY(hp::launch_conv_i8(st.q8, s));
-    } else if (st.op == HP_OP_CONV) {
-        st.cp.B = n, st.cp.npix = n * st.cp.OH * st.cp.OW;
-        HP_HIP_TRY(hp::launch_conv_mfma(st.cp, s));
-    } else if (st.op == OP_BNECK) {
-        st.bn.c3.B = st.bn.ce.B = st.bn.cr.B = n;
-        HP_HIP_TRY(hp::launch_bottleneck(st.bn, s));
-    } else if (st.op == OP_CHAIN) {
-        st.ch.c0.B = st.ch.c1.B = st.ch.c2.B = n;
-        HP_HIP_TRY(hp::launch_conv_chain(st.ch, s));
-    } else if (st.op == OP_SEPCONV) {
-        st.sp.B = n, st.sp.pw.B = n, st.sp.pw.npix = n * st.sp.OH * st.sp.OW;
-        if (st.sep_pair) {
-            st.sp2.B = n, st.sp2.pw.B = n, st.sp2.pw.npix = n * st.sp2.OH * st.sp2.OW;
-            HP_HIP_TRY(hp::launch_seppair(hp::seppair_params{ st.sp, st.sp2 }, s));
-        } else
-            HP_HIP_TRY(hp::launch_sepconv(st.sp, s));
-    } else if (st.op == OP_MLPHEAD) {
-        st.hp_.B = n, st.hp_.pw.B = n;
-        if (st.paired) {
-            st.hp2_.B = n, st.hp2_.pw.B = n;
-            HP_HIP_TRY(hp::launch_mlp_head_pair(st.hp_, st.hp2_, s));
-        } else
-            HP_HIP_TRY(hp::launch_mlp_head(st.hp_, s));
-    } else if (st.op == HP_OP_DWCONV) {
-        st.dp.B = n;
-        HP_HIP_TRY(hp::launch_dwconv3x3(st.dp, s));
-    } else if (st.op == HP_OP_UPSAMPLE) {
-        st.pp.B = n;
-        HP_HIP_TRY(hp::launch_upsample(st.pp, s));
-    } else {
-        st.pp.B = n;
-        HP_HIP_TRY(hp::launch_maxpool(st.pp, s));
+    case launch_kind::sep: return 4000000 + hp::sepconv_variant(std::get<hp::sep_params>(b));
+    case launch_kind::sep_pair: return 4000000 + 20;
+    case launch_kind::head: return 6000000 + std::get<hp::head_params>(b).K1;
+    case launch_kind::head_pair: return 6000000 + std::get<head_pair_launch>(b).a.K1;
+    case launch_kind::chain: return 7000000 + hp::conv_chain_variant(std::get<hp::chain_params>(b));
+    case launch_kind::bneck: return 9000000 + hp::bottleneck_variant(std::get<hp::bneck_params>(b));
+    case launch_kind::conv32: return hp::conv32_tile(std::get<conv32_launch>(b).cp, switches);
+    case launch_kind::wino2:
+    case launch_kind::wino3: return hp::conv32_winograd_tile(std::get<conv32_launch>(b).cp);
+    case launch_kind::direct: return hp::conv32_direct_tile(std::get<conv32_launch>(b).cp, dtype == HP_DTYPE_F32S && !split_off);
+    case launch_kind::head32: return hp::conv32_head_tile(std::get<head32_launch>(b).hh.HID, std::get<head32_launch>(b).cp.Cout);
+    default: return 0; // first convolutions, depthwise, pooling, up-sampling: one form each
     }
-    return print_timeline(st, nullptr, s);
 }
 
-int hp_engine::enqueue_range(const uint8_t* u8, const float* f32, int b0, int n, hipStream_t s)
+int hp_engine::step_tile(const step& st, int n) const { return tile_of(st.kind, bound(st, nullptr, nullptr, n, 0)); }
+
+// HP_CONV_DBG / HP_BN_DBG / HP_CHAIN_DBG / HP_SEP_DBG / HP_DIRECT_DBG: which block timeline, if any, the switches ask for on this step, and
+// the numbers its text quotes (engine_timeline.hpp).  Kinds without a case have no timeline.
+bool hp_engine::timeline_of(const step& st, const launch_payload& b, hp::timeline_kind& kind, hp::timeline_header& hd) const
+{
+    hd = hp::timeline_header{};
+    hd.layer = st.layer;
+    switch (st.kind) {
+    case launch_kind::conv16: { // the pixel-block GEMM
+        const auto& c = std::get<conv16_launch>(b);
+        if (c.i8 || !switches.dbg_conv || hp::conv_mfma_tile(c.cp) / 100000 != 52)
+            return false;
+        kind = hp::timeline_kind::conv, hd.cin = c.cp.Cin, hd.cout = c.cp.Cout, hd.tile = hp::conv_mfma_tile(c.cp);
+        return true;
+    }
+    case launch_kind::bneck:
+        kind = hp::timeline_kind::bneck, hd.tile = hp::bottleneck_variant(std::get<hp::bneck_params>(b));
+        return switches.dbg_bn;
+    case launch_kind::chain:
+        kind = hp::timeline_kind::chain, hd.tile = hp::conv_chain_variant(std::get<hp::chain_params>(b));
+        return switches.dbg_chain;
+    case launch_kind::sep:
+        kind = hp::timeline_kind::sep, hd.cin = std::get<hp::sep_params>(b).C;
+        return switches.dbg_sep;
+    case launch_kind::conv32:
+    case launch_kind::wino2:
+    case launch_kind::wino3:
+    case launch_kind::direct: {
+        const hp::conv32_params& q = std::get<conv32_launch>(b).cp;
+        if (!switches.dbg_direct || (st.kind == launch_kind::conv32 && q.Cin < switches.dbg_min_cin))
+            return false;
+        kind = st.kind == launch_kind::conv32 ? hp::timeline_kind::conv32
+            : st.kind == launch_kind::wino2   ? hp::timeline_kind::wino
+            : st.kind == launch_kind::wino3   ? hp::timeline_kind::wino3
+                                              : hp::timeline_kind::direct;
+        hd.cin = q.Cin, hd.cout = q.Cout, hd.kh = q.KH, hd.kw = q.KW, hd.tile = tile_of(st.kind, b);
+        if (st.kind == launch_kind::wino2)
+            (void)hp::conv32_winograd_occupancy(q, &hd.blocks_per_cu);
+        return true;
+    }
+    default: return false;
+    }
+}
+
+// ... the step's kernel launched once more with its block-timeline stamps (s_memtime = shader cycles; the 100 MHz clock) written into a zeroed
+// scratch buffer, printed to stderr per launch
+int hp_engine::trace_step(const step& st, launch_payload& b, hipStream_t s) const
+{
+    hp::timeline_kind kind;
+    hp::timeline_header hd;
+    if (!timeline_of(st, b, kind, hd))
+        return HP_OK;
+    const size_t words = hp::timeline_words(kind);
+    hp::dev_buf buf;
+    HP_TRY(buf.alloc(words * 8));
+    HP_HIP_TRY(hipMemset(buf.p, 0, words * 8));
+    HP_TRY(launch(st.kind, b, s, buf.as<unsigned long long>()));
+    HP_HIP_TRY(hipStreamSynchronize(s));
+    std::vector<unsigned long long> hv(words);
+    HP_HIP_TRY(hipMemcpy(hv.data(), buf.p, words * 8, hipMemcpyDeviceToHost));
+    hp::print_timeline(stderr, kind, hd, hv.data());
+    return HP_OK;
+}
+
+int hp_engine::run_step(const step& st, const uint8_t* u8, const float* f32, int n, hipStream_t s, int b0) const
+{
+    launch_payload b = bound(st, u8, f32, n, b0);
+    HP_TRY(launch(st.kind, b, s, nullptr));
+    return trace_step(st, b, s);
+}
+
+// two fused fp32 heads in a row that read the same tensor (LW-OpenPose's heat-map and PAF heads of a stage): one grid (conv32_head.hip), where
+// the kernel takes the pair at this batch.  Not a build pass: the schedule and the profile rows keep the two heads apart.
+int hp_engine::launch_head_pair32(size_t i, int n, int b0, hipStream_t s, bool* done) const
+{
+    *done = false;
+    if (i + 1 >= steps.size() || steps[i].kind != launch_kind::head32 || steps[i + 1].kind != launch_kind::head32)
+        return HP_OK;
+    const auto &ha = steps[i].as<head32_launch>(), &hb = steps[i + 1].as<head32_launch>();
+    const hp::conv32_params a = bind(ha.cp, n, b0), b = bind(hb.cp, n, b0);
+    if (!hp::conv32_head_pair_ok(a, b, switches))
+        return HP_OK;
+    HP_HIP_TRY(hp::launch_conv32_head_pair(a, ha.hh, b, hb.hh, s));
+    *done = true;
+    return HP_OK;
+}
+
+int hp_engine::enqueue_range(const uint8_t* u8, const float* f32, int b0, int n, hipStream_t s) const
 {
     for (size_t i = 0; i < steps.size(); ++i) {
-        step& st = steps[i];
-        // two fused heads in a row that read the same tensor (LW-OpenPose's heat-map and PAF heads of a stage): one grid (conv32_head.hip)
-        if (st.f32 && st.head32 && i + 1 < steps.size() && steps[i + 1].f32 && steps[i + 1].head32) {
-            hp::conv32_params a = at_frame(st.cp32, b0), b = at_frame(steps[i + 1].cp32, b0);
-            for (hp::conv32_params* q : { &a, &b })
-                q->B = n, q->npix = n * q->OH * q->OW;
-            if (hp::conv32_head_pair_ok(a, b, switches)) {
-                HP_HIP_TRY(hp::launch_conv32_head_pair(a, st.hh, b, steps[i + 1].hh, s));
-                ++i;
-                continue;
-            }
-        }
-        HP_TRY(run_step(st, u8, f32, n, s, b0));
+        bool paired = false;
+        HP_TRY(launch_head_pair32(i, n, b0, s, &paired));
+        if (paired)
+            ++i;
+        else
+            HP_TRY(run_step(steps[i], u8, f32, n, s, b0));
     }
     for (auto& o : outputs)
         if (o.fused_layer < 0) {
@@ -1917,24 +1916,14 @@ int hp_engine::enqueue_range(const uint8_t* u8, const float* f32, int b0, int n,
     return HP_OK;
 }
 
-int hp_engine::step_tile(const step& st) const
+void hp_engine::fill_row(hp_layer_time* out, int k, int cap, const step& st, int n, float ms) const
 {
-    if (st.op == OP_SEPCONV)
-        return 4000000 + (st.sep_pair ? 20 : hp::sepconv_variant(st.sp));
-    if (st.op == OP_MLPHEAD)
-        return 6000000 + st.hp_.K1;
-    if (st.op == OP_CHAIN)
-        return 7000000 + hp::conv_chain_variant(st.ch);
-    if (st.op == OP_BNECK)
-        return 9000000 + hp::bottleneck_variant(st.bn);
-    if (st.op != HP_OP_CONV || st.first)
-        return 0;
-    if (!st.f32)
-        return i8_on(st) ? hp::conv_i8_tile(st.cp) : hp::conv_mfma_tile(st.cp);
-    return st.head32 ? hp::conv32_head_tile(st.hh.HID, st.cp32.Cout)
-        : st.wino    ? hp::conv32_winograd_tile(st.cp32)
-        : st.cin_split ? hp::conv32_direct_tile(st.cp32, dtype == HP_DTYPE_F32S && !split_off)
-                     : hp::conv32_tile(st.cp32, switches);
+    if (!out || k >= cap)
+        return;
+    out[k].layer = st.layer, out[k].op = st.op;
+    out[k].tile = step_tile(st, n);
+    out[k].ms = ms;
+    out[k].flops = st.flops * n, out[k].bytes = st.bytes * n;
 }
 
 int hp_engine::stage_profile_input()
@@ -1945,7 +1934,7 @@ int hp_engine::stage_profile_input()
     return HP_OK;
 }
 
-int hp_engine::enqueue(const uint8_t* u8, const float* f32, int n, hipStream_t s, const void* host_src, size_t frame_bytes)
+int hp_engine::enqueue(const uint8_t* u8, const float* f32, int n, hipStream_t s, const void* host_src, size_t frame_bytes) const
 {
     unsigned char* const dev_in = u8 ? (unsigned char*)u8 : (unsigned char*)f32;
     auto h2d = [&](int b0, int cnt, hipStream_t st) -> int {
@@ -2320,7 +2309,7 @@ int hp_engine_calibrate_u8(hp_engine* e, const uint8_t* hwc_bgr, int n, int on_d
         }
         HP_TRY(e->enqueue(src, nullptr, cnt, e->stream));
         for (const auto& st : e->steps) {
-            if (!st.i8)
+            if (!st.int8())
                 continue;
             const hp_layer& L = e->layers[st.layer];
             const auto& ti = *e->tensors[L.in];
@@ -2481,7 +2470,7 @@ int hp_engine_profile(hp_engine* e, int n, int iters, hp_layer_time* out, int ca
     HP_TRY(e->stage_profile_input());
     const uint8_t* u8 = e->in_stage.as<uint8_t>();
     int k = 0;
-    for (auto& st : e->steps) {
+    for (const step& st : e->steps) {
         HP_TRY(e->run_step(st, u8, nullptr, n, e->stream)); // warm
         HP_HIP_TRY(hipEventRecord(e->ev0, e->stream));
         for (int it = 0; it < iters; ++it)
@@ -2490,13 +2479,7 @@ int hp_engine_profile(hp_engine* e, int n, int iters, hp_layer_time* out, int ca
         HP_HIP_TRY(hipEventSynchronize(e->ev1));
         float ms = 0;
         HP_HIP_TRY(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-        if (out && k < cap) {
-            out[k].layer = st.layer, out[k].op = st.op;
-            out[k].tile = e->step_tile(st);
-            out[k].ms = ms / iters;
-            out[k].flops = st.flops * n, out[k].bytes = st.bytes * n;
-        }
-        ++k;
+        e->fill_row(out, k++, cap, st, n, ms / iters);
     }
     *n_out = k;
     return HP_OK;
@@ -2517,7 +2500,7 @@ int hp_engine_profile_pair(hp_engine* e, hp_engine* f, int n, int iters, hp_laye
     HP_TRY(f->stage_profile_input());
     int k = 0;
     for (size_t i = 0; i < e->steps.size(); ++i) {
-        auto &sa = e->steps[i], &sb = f->steps[i];
+        const step &sa = e->steps[i], &sb = f->steps[i];
         HP_TRY(e->run_step(sa, e->in_stage.as<uint8_t>(), nullptr, n, e->stream));
         HP_TRY(f->run_step(sb, f->in_stage.as<uint8_t>(), nullptr, n, f->stream));
         HP_HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2535,14 +2518,7 @@ int hp_engine_profile_pair(hp_engine* e, hp_engine* f, int n, int iters, hp_laye
         float m0 = 0, m1 = 0;
         HP_HIP_TRY(hipEventElapsedTime(&m0, e->ev0, e->ev1));
         HP_HIP_TRY(hipEventElapsedTime(&m1, f->ev0, f->ev1));
-        if (out && k < cap) {
-            auto& st = sa;
-            out[k].layer = st.layer, out[k].op = st.op;
-            out[k].tile = e->step_tile(st);
-            out[k].ms = std::max(m0, m1) / (2 * iters);
-            out[k].flops = st.flops * n, out[k].bytes = st.bytes * n;
-        }
-        ++k;
+        e->fill_row(out, k++, cap, sa, n, std::max(m0, m1) / (2 * iters));
     }
     *n_out = k;
     return HP_OK;
@@ -2586,13 +2562,8 @@ int hp_engine_profile_sequence(hp_engine* e, int n, int iters, hp_layer_time* ou
     }
     HP_REQUIRE(rc == HP_OK, rc, "hp_engine_profile_sequence: launch or event failure");
     int k = 0;
-    for (auto& st : e->steps) {
-        if (out && k < cap) {
-            out[k].layer = st.layer, out[k].op = st.op;
-            out[k].tile = e->step_tile(st);
-            out[k].ms = (float)(acc[k] / iters);
-            out[k].flops = st.flops * n, out[k].bytes = st.bytes * n;
-        }
+    for (const step& st : e->steps) {
+        e->fill_row(out, k, cap, st, n, (float)(acc[k] / iters));
         ++k;
     }
     *n_out = k;
