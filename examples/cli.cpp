@@ -12,6 +12,11 @@
 //     `--yuv_matrix=bt601|bt709|bt2020` and `--yuv_range=limited|full` (defaults bt601, limited); `--yuv` converts any other source to
 //     NV12 first.  Either way the operator runtime hands the engine hyperpose::yuv_frame batches (colour conversion fused into the resize
 //     on the GPU); the BGR pictures, converted on the host with the same table (hp_yuv_coefficients), are only drawn on.
+//   * HDR video (addition): `--yuv_transfer=sdr|pq|hlg` (default sdr) `[--hdr_peak=<cd/m2> --hdr_white=<cd/m2> --hdr_keep_primaries]`, only with
+//     a .yuv source in a 10-bit layout (`--yuv_format=p010|i010`): the frames are HDR10 (pq) or HLG and are tone-mapped to SDR sRGB inside the
+//     fused resize (engine.set_tonemap; hp::hdr, defaults 1000 / 203, BT.2020 primaries converted to BT.709 unless --hdr_keep_primaries); the
+//     pictures drawn on are converted on the host by the same rule (hp_tonemap_convert_host), and with --saving_yuv the skeletons are drawn with
+//     the HDR colours (graphics white at --hdr_white);
 //   * tiled inference (addition): `--tiles=<columns>x<rows> [--tile_overlap=<px>] [--tile_full]`: every frame - BGR or --yuv / .yuv, with or
 //     without --saving_yuv - is inferred on overlapping tiles (one engine call per frame, engine.inference(frame, regions)) and the humans
 //     are merged in the frame's coordinates (hp::plan_tiles / to_frame / merge_humans; stream runtime: stream.set_tiling);
@@ -61,6 +66,11 @@ static bool FLAGS_int8 = false; // addition: data_type::kINT8 engines, calibrate
 static bool FLAGS_yuv = false;  // addition: feed the engine video frames (dnn::tensorrt::inference(std::vector<yuv_frame>)); implied by a .yuv source
 static int FLAGS_yuv_w = 0, FLAGS_yuv_h = 0; // frame size of a raw .yuv source
 static std::string FLAGS_yuv_format = "i420", FLAGS_yuv_matrix = "bt601", FLAGS_yuv_range = "limited"; // layout and colours of a raw .yuv source
+static std::string FLAGS_yuv_transfer = "sdr"; // addition: pq | hlg: the 10-bit frames of a .yuv source are HDR10 / HLG (hp::hdr)
+static double FLAGS_hdr_peak = HP_HDR_DEFAULT_PEAK, FLAGS_hdr_white = HP_HDR_DEFAULT_WHITE; // ... the tone curve's parameters, cd/m2
+static bool FLAGS_hdr_keep_primaries = false;  // ... leave the BT.2020 primaries as they are
+static bool g_hdr_on = false;
+static hp::hdr g_hdr;
 static std::string FLAGS_tiles;      // addition: --tiles CxR: inference on C x R overlapping tiles of every frame, the humans merged (hp::tiling)
 static int FLAGS_tile_overlap = 64;  // ... pixels neighbouring tiles share at least
 static bool FLAGS_tile_full = false; // ... plus the whole frame as one more region
@@ -78,10 +88,12 @@ static bool parse_flags(int argc, char** argv)
 {
     std::map<std::string, std::string*> sflags = { { "model", &FLAGS_model }, { "post", &FLAGS_post }, { "source", &FLAGS_source },
         { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix }, { "saving_yuv", &FLAGS_saving_yuv }, { "tiles", &FLAGS_tiles }, { "yuv_format", &FLAGS_yuv_format },
-        { "yuv_matrix", &FLAGS_yuv_matrix }, { "yuv_range", &FLAGS_yuv_range } };
+        { "yuv_matrix", &FLAGS_yuv_matrix }, { "yuv_range", &FLAGS_yuv_range }, { "yuv_transfer", &FLAGS_yuv_transfer } };
+    std::map<std::string, double*> dflags = { { "alpha", &FLAGS_alpha }, { "hdr_peak", &FLAGS_hdr_peak }, { "hdr_white", &FLAGS_hdr_white } };
     std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size }, { "tile_overlap", &FLAGS_tile_overlap },
         { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h }, { "synthetic_humans", &FLAGS_synthetic_humans } };
-    std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 }, { "yuv", &FLAGS_yuv }, { "tile_full", &FLAGS_tile_full } };
+    std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 }, { "yuv", &FLAGS_yuv }, { "tile_full", &FLAGS_tile_full },
+        { "hdr_keep_primaries", &FLAGS_hdr_keep_primaries } };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a.rfind("--", 0) != 0 && a.rfind("-", 0) == 0)
@@ -114,8 +126,8 @@ static bool parse_flags(int argc, char** argv)
             *sflags[name] = value;
         else if (iflags.count(name))
             *iflags[name] = std::atoi(value.c_str());
-        else if (name == "alpha")
-            FLAGS_alpha = std::atof(value.c_str());
+        else if (dflags.count(name))
+            *dflags[name] = std::atof(value.c_str());
         else {
             cli_log() << "ERROR: unknown command line flag '" << name << "'\n";
             return false;
@@ -149,6 +161,30 @@ static bool parse_flags(int argc, char** argv)
         cli_log() << "ERROR: --" << flag << "=" << value << " is not one of " << all << "\n";
         return false;
     };
+    int transfer = 0;
+    if (!pick("yuv_transfer", FLAGS_yuv_transfer, { { "sdr", 0 }, { "pq", HP_TRC_PQ }, { "hlg", HP_TRC_HLG } }, transfer))
+        return false;
+    if (transfer != 0) { // HDR: a 10-bit .yuv source, and a description the library accepts (its message names what is wrong)
+        const bool from_file = FLAGS_source.size() >= 4 && FLAGS_source.compare(FLAGS_source.size() - 4, 4, ".yuv") == 0;
+        if (!from_file || (FLAGS_yuv_format != "p010" && FLAGS_yuv_format != "i010")) {
+            cli_log() << "ERROR: --yuv_transfer=" << FLAGS_yuv_transfer << " needs a .yuv source in a 10-bit layout (--yuv_format=p010|i010), got --yuv_format="
+                      << FLAGS_yuv_format << (from_file ? "" : " and no .yuv source") << "\n";
+            return false;
+        }
+        g_hdr.transfer = transfer, g_hdr.to_bt709 = !FLAGS_hdr_keep_primaries, g_hdr.peak_nits = (float)FLAGS_hdr_peak, g_hdr.white_nits = (float)FLAGS_hdr_white;
+        const hp_hdr_desc d = g_hdr.c_form();
+        std::vector<uint16_t> lin(1024);
+        std::vector<uint8_t> out(4096);
+        int32_t m[9];
+        if (hp_tonemap_tables(&d, lin.data(), m, out.data()) != HP_OK) {
+            cli_log() << "ERROR: --hdr_peak=" << FLAGS_hdr_peak << " --hdr_white=" << FLAGS_hdr_white << ": " << hp_last_error() << "\n";
+            return false;
+        }
+        g_hdr_on = true;
+    } else if (FLAGS_hdr_keep_primaries || FLAGS_hdr_peak != HP_HDR_DEFAULT_PEAK || FLAGS_hdr_white != HP_HDR_DEFAULT_WHITE) {
+        cli_log() << "ERROR: --hdr_peak / --hdr_white / --hdr_keep_primaries describe the frames of --yuv_transfer=pq|hlg\n";
+        return false;
+    }
     return pick("yuv_format", FLAGS_yuv_format, { { "i420", HP_YUV_I420 }, { "nv12", HP_YUV_NV12 }, { "p010", HP_YUV_P010 }, { "i010", HP_YUV_I010 },
                                                     { "nv16", HP_YUV_NV16 }, { "i422", HP_YUV_I422 }, { "yuy2", HP_YUV_YUY2 }, { "uyvy", HP_YUV_UYVY }, { "i444", HP_YUV_I444 } }, g_yuv_format)
         && pick("yuv_matrix", FLAGS_yuv_matrix, { { "bt601", HP_YUV_BT601 }, { "bt709", HP_YUV_BT709 }, { "bt2020", HP_YUV_BT2020 } }, g_yuv_matrix)
@@ -254,6 +290,15 @@ static cv::Mat yuv_to_bgr(const yuv_buffer& f)
     cv::Mat m(f.h, f.w, CV_8UC3);
     uint8_t* d = const_cast<uint8_t*>(hp::detail::mat_data(m));
     const hp::yuv_frame v = f.frame();
+    if (g_hdr_on) { // an HDR frame: the picture the network is given (hp_tonemap_convert_host is the whole-frame twin of the kernels)
+        const hp_yuv_image im = v.image();
+        const hp_hdr_desc desc = g_hdr.c_form();
+        if (hp_tonemap_convert_host(&im, &desc, d, f.w * 3) != HP_OK) {
+            cli_log() << "ERROR: " << hp_last_error() << "\n";
+            std::exit(-1);
+        }
+        return m;
+    }
     const int planes = hp::yuv_frame::plane_count(f.format);
     // sample width and chroma sub-sampling as hp_yuv_plane_layout states them: bytes per luma row / width; chroma samples per row and
     // chroma rows against the luma plane's
@@ -490,6 +535,8 @@ int main(int argc, char** argv)
     }
 
     auto engine = build_engine();
+    if (g_hdr_on)
+        engine.set_tonemap(g_hdr);
     if (FLAGS_int8 && !engine.calibrated()) { // calibration is never implicit in the engine: the CLI asks for it and says so
         const size_t n = std::min(images.size(), (size_t)FLAGS_max_batch_size);
         if (FLAGS_yuv) {
@@ -571,7 +618,10 @@ int main(int argc, char** argv)
                     if (FLAGS_keep_ratio && !g_tiled) // (tiled poses are in the frame's coordinates already)
                         for (auto& pose : drawn)
                             hp::resume_ratio(pose, batch[k].size(), engine.input_size());
-                    hp::draw_humans(yuv_batch[k], drawn, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
+                    if (g_hdr_on)
+                        hp::draw_humans(yuv_batch[k], drawn, g_hdr, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
+                    else
+                        hp::draw_humans(yuv_batch[k], drawn, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
                     std::vector<uint8_t> annotated(g_yuv[first + k].data.size());
                     if (hp_device_synchronize() != HP_OK || hp_memcpy_d2h(annotated.data(), surfaces[k]->p, annotated.size()) != HP_OK) {
                         cli_log() << "ERROR: " << hp_last_error() << "\n";

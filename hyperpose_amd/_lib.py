@@ -67,6 +67,17 @@ class Roi(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
 
 
+class HdrDesc(C.Structure):
+    """hp_hdr_desc"""
+    _fields_ = [("transfer", C.c_int32), ("to_bt709", C.c_int32), ("peak_nits", C.c_float), ("white_nits", C.c_float)]
+
+
+HP_TRC_PQ, HP_TRC_HLG = 1, 2
+HDR_TRANSFERS = {"pq": HP_TRC_PQ, "hlg": HP_TRC_HLG}
+# the mirrors' tone-map defaults (HP_HDR_DEFAULT_* in include/hp_hip.h)
+HDR_DEFAULT_PEAK, HDR_DEFAULT_WHITE = 1000.0, 203.0
+
+
 class Tiling(C.Structure):
     """hp_tiling"""
     _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("overlap_x", C.c_int32), ("overlap_y", C.c_int32), ("with_full", C.c_int32),
@@ -103,6 +114,8 @@ SYMBOLS = [
     "hp_model_input_size",
     "hp_model_destroy", "hp_model_archs", "hp_model_layers", "hp_model_outputs", "hp_model_num_weights",
     "hp_model_preproc", "hp_model_flops_per_frame", "hp_model_init_weights", "hp_engine_create_from_model", "hp_engine_create_from_model_dtype", "hp_engine_dtype", "hp_engine_calibrate_u8", "hp_engine_int8_scales", "hp_engine_set_int8_scales", "hp_engine_split_fallbacks", "hp_engine_device_bytes", "hp_engine_save", "hp_engine_load", "hp_pipeline_create", "hp_pipeline_create_ex", "hp_pipeline_destroy", "hp_pipeline_submit", "hp_pipeline_collect", "hp_pipeline_in_flight",
+    "hp_tonemap_tables", "hp_tonemap_create", "hp_tonemap_destroy", "hp_resize_yuv_hdr", "hp_letterbox_yuv_hdr", "hp_resize_rois_yuv_hdr",
+    "hp_tonemap_convert_host", "hp_yuv_colours_hdr", "hp_overlay_set_transfer", "hp_overlay_draw_yuv_host_hdr", "hp_pipeline_set_tonemap",
     "hp_resize_rois_u8c3", "hp_resize_rois_yuv", "hp_yuv_roi_alignment", "hp_tile_plan", "hp_humans_to_frame", "hp_humans_merge", "hp_pipeline_set_tiling",
 ]
 

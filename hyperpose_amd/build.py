@@ -31,6 +31,10 @@ UNITS = [
     ("resize_yuv_formats.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # many regions of one frame per launch: resize_device.hpp's arithmetic again, so the same flags as the per-frame units
     ("resize_rois.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # PQ / HLG 10-bit frames: the same resize arithmetic once more (the kernels' pixel path is integer; the flags are the front end's)
+    ("resize_yuv_hdr.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # the tone-map tables, float64 without fused operations: tests/hdr_ref.py derives them a second time
+    ("tonemap.cpp", ["-ffp-contract=off"]),
     # planner / map-back / merge of tiled inference: host doubles that tests/tiles_ref.py restates bit for bit
     ("tiles.cpp", ["-ffp-contract=off"]),
     # the primitive list is fp32 with no fused operations (csrc/overlay.hpp); the kernels are integer

@@ -33,6 +33,7 @@
 // builds the list in the next pinned slot, enqueues one hipMemcpyAsync and the kernel on the caller's stream and records the slot's event;
 // it waits (on the host) only if that slot's use SLOTS calls ago has not finished.
 #include "overlay.hpp"
+#include "tonemap.hpp"
 #include "yuv_formats.hpp"
 
 #include <algorithm>
@@ -290,6 +291,8 @@ struct hp_overlay {
     hipEvent_t done[SLOTS] = {};
     bool used[SLOTS] = {};
     int next = 0;
+    bool hdr = false;       // hp_overlay_set_transfer: 10-bit frames are PQ / HLG and take hp_yuv_colours_hdr's table
+    hp_hdr_desc transfer {};
     ~hp_overlay()
     {
         for (auto& e : done)
@@ -334,7 +337,8 @@ int describe_bgr(frame_desc& f, const char* who, uint8_t* bgr, int w, int h, int
     return HP_OK;
 }
 
-int describe_yuv(frame_desc& f, const char* who, const hp_yuv_image* im, bool kernel_access, const hp_human* humans, int n, float opacity, int thickness)
+int describe_yuv(frame_desc& f, const char* who, const hp_yuv_image* im, bool kernel_access, const hp_human* humans, int n, float opacity, int thickness,
+    const hp_hdr_desc* transfer = nullptr)
 {
     HP_TRY(hp_yuv::validate(im, who, kernel_access));
     const hp_yuv::layout& l = *hp_yuv::layout_of(im->format);
@@ -342,6 +346,8 @@ int describe_yuv(frame_desc& f, const char* who, const hp_yuv_image* im, bool ke
     f.bgr = false, f.name = l.name, f.w = im->width, f.h = im->height, f.sx = l.sx, f.sy = l.sy;
     f.sample_bytes = l.sample_bytes, f.shift = l.shift, f.planes = l.planes;
     f.map = hp_yuv::map_samples(*im, l);
+    if (transfer && l.sample_bytes == 2) // an HDR frame: graphics white at white_nits instead of full-scale code values
+        return hp_yuv_colours_hdr(im->matrix, im->range, transfer, f.colours);
     return yuv_colours(im->matrix, im->range, l.sample_bytes == 2 ? 10 : 8, f.colours);
 }
 
@@ -532,7 +538,7 @@ int hp_overlay_draw_yuv(hp_overlay* o, const hp_yuv_image* frame, const hp_human
 {
     HP_REQUIRE(o, HP_ERR_INVALID, "hp_overlay_draw_yuv: null handle");
     frame_desc f;
-    HP_TRY(describe_yuv(f, "hp_overlay_draw_yuv", frame, true, humans, n, opacity, thickness));
+    HP_TRY(describe_yuv(f, "hp_overlay_draw_yuv", frame, true, humans, n, opacity, thickness, o->hdr ? &o->transfer : nullptr));
     return draw_device(o, "hp_overlay_draw_yuv", f, humans, n, opacity, thickness, (hipStream_t)stream);
 }
 
@@ -547,6 +553,24 @@ int hp_overlay_draw_yuv_host(const hp_yuv_image* frame, const hp_human* humans, 
 {
     frame_desc f;
     HP_TRY(describe_yuv(f, "hp_overlay_draw_yuv_host", frame, false, humans, n, opacity, thickness));
+    return draw_host(f, humans, n, opacity, thickness);
+}
+
+int hp_overlay_set_transfer(hp_overlay* o, const hp_hdr_desc* d)
+{
+    HP_REQUIRE(o, HP_ERR_INVALID, "hp_overlay_set_transfer: null handle");
+    if (d)
+        HP_TRY(hp_hdr::check_desc(d, "hp_overlay_set_transfer"));
+    o->hdr = d != nullptr;
+    if (d)
+        o->transfer = *d;
+    return HP_OK;
+}
+
+int hp_overlay_draw_yuv_host_hdr(const hp_yuv_image* frame, const hp_hdr_desc* d, const hp_human* humans, int n, float opacity, int thickness)
+{
+    frame_desc f;
+    HP_TRY(describe_yuv(f, "hp_overlay_draw_yuv_host_hdr", frame, false, humans, n, opacity, thickness, d));
     return draw_host(f, humans, n, opacity, thickness);
 }
 

@@ -11,6 +11,8 @@
 // Tiled mode (hp_pipeline_set_tiling): a frame becomes its R regions in R consecutive slots of the batch - one hp_resize_rois_* call per
 // frame (resize_rois.hip) instead of the per-frame resize - and hp_pipeline_collect maps every region's humans back to the frame and
 // merges them (tiles.cpp).  The BGR and the hp_yuv_image submit have a tiled twin below; with tiling off nothing of this runs.
+// HDR input (hp_pipeline_set_tonemap): while set, the P010 / I010 frames of hp_pipeline_submit_yuv_images take the *_hdr twin of their resize call
+// (resize_yuv_hdr.hip); nothing else changes, and 8-bit frames of the same batch go the SDR way.
 #include "hp_common.hpp"
 #include "yuv_formats.hpp"
 
@@ -56,6 +58,10 @@ struct hp_pipeline {
     std::vector<hp_human> slot_humans, cand, kept; // tiled collect: the parser's per-slot lists, one frame's candidates, its merged humans
     std::vector<int> slot_n;
     std::vector<int32_t> cand_region;
+    hp_tonemap* tonemap = nullptr; // set: 10-bit hp_yuv_image frames are PQ / HLG and are tone-mapped while they are resized
+
+    // the tone-map of a frame, or null for the SDR path
+    const hp_tonemap* tonemap_for(const hp_yuv_image& f) const { return tonemap && hp_yuv::layout_of(f.format)->sample_bytes == 2 ? tonemap : nullptr; }
 
     ~hp_pipeline()
     {
@@ -71,6 +77,7 @@ struct hp_pipeline {
             if (p.eng)
                 hp_engine_destroy(p.eng);
         }
+        hp_tonemap_destroy(tonemap);
     }
 };
 
@@ -161,6 +168,18 @@ int hp_pipeline_set_tiling(hp_pipeline* pl, const hp_tiling* t)
     HP_REQUIRE(R <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_set_tiling: %d regions per frame > max_batch %d", R, pl->max_batch);
     HP_REQUIRE(t->min_common >= 1 && t->tol >= 0., HP_ERR_INVALID, "hp_pipeline_set_tiling: min_common %d (>= 1), tol %g (>= 0)", t->min_common, t->tol);
     pl->tiling = *t, pl->tiled = true;
+    return HP_OK;
+}
+
+int hp_pipeline_set_tonemap(hp_pipeline* pl, const hp_hdr_desc* d)
+{
+    HP_REQUIRE(pl, HP_ERR_INVALID, "hp_pipeline_set_tonemap: null pipeline");
+    HP_REQUIRE(pl->inflight == 0, HP_ERR_STATE, "hp_pipeline_set_tonemap: %d batches are in flight, collect first", pl->inflight);
+    hp_tonemap* next = nullptr;
+    if (d)
+        HP_TRY(hp_tonemap_create(&next, d)); // a refused description leaves the pipeline as it was
+    hp_tonemap_destroy(pl->tonemap);
+    pl->tonemap = next;
     return HP_OK;
 }
 
@@ -290,10 +309,13 @@ int hp_pipeline_submit_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, i
     for (int i = 0; i < n; ++i) {
         uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * net_frame;
         p.w[i] = frames[i].width, p.h[i] = frames[i].height;
+        const hp_tonemap* tm = pl->tonemap_for(dev[i]);
         if (pl->keep_ratio)
-            HP_TRY(hp_letterbox_yuv(&dev[i], dst, pl->in_w, pl->in_h, pl->in_w * 3, 0, 0, 0, p.s));
+            HP_TRY(tm ? hp_letterbox_yuv_hdr(&dev[i], tm, dst, pl->in_w, pl->in_h, pl->in_w * 3, 0, 0, 0, p.s)
+                      : hp_letterbox_yuv(&dev[i], dst, pl->in_w, pl->in_h, pl->in_w * 3, 0, 0, 0, p.s));
         else
-            HP_TRY(hp_resize_yuv(&dev[i], dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
+            HP_TRY(tm ? hp_resize_yuv_hdr(&dev[i], tm, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s)
+                      : hp_resize_yuv(&dev[i], dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
     }
     return infer_and_parse(pl, p, n);
 }
@@ -448,8 +470,10 @@ int submit_tiled_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, int n, 
         HP_TRY(upload_yuv_images(pl, p, frames, n, dev));
     for (int i = 0; i < n; ++i) {
         p.w[i] = frames[i].width, p.h[i] = frames[i].height;
-        HP_TRY(hp_resize_rois_yuv(&dev[i], &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, p.net.as<uint8_t>() + (size_t)i * R * net_frame, pl->in_w,
-            pl->in_h, pl->in_w * 3, net_frame, p.s));
+        uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * R * net_frame;
+        const hp_tonemap* tm = pl->tonemap_for(dev[i]);
+        HP_TRY(tm ? hp_resize_rois_yuv_hdr(&dev[i], tm, &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s)
+                  : hp_resize_rois_yuv(&dev[i], &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s));
     }
     HP_TRY(infer_and_parse(pl, p, n * R));
     p.regions = R;

@@ -27,11 +27,17 @@ template <int SAMPLE_BYTES, int Y_STEP> struct yuv_taps {
         else
             return *p;
     }
-    __device__ __forceinline__ void load(int px, int py, int (&c)[3]) const
+    // the samples of source pixel (px, py): Y as stored, U and V with c_off subtracted (also what yuv_hdr_taps, resize_yuv_hdr.hip, starts from)
+    __device__ __forceinline__ void fetch(int px, int py, int& Y, int& U, int& V) const
     {
         const size_t at = (size_t)(py >> sy) * c_stride + (size_t)(px >> sx) * c_step;
-        const int Y = sample(y + (size_t)py * y_stride + (size_t)px * (Y_STEP * SAMPLE_BYTES));
-        const int U = sample(u + at) - c_off, V = sample(v + at + (ptrdiff_t)(py >> sy) * v_extra) - c_off;
+        Y = sample(y + (size_t)py * y_stride + (size_t)px * (Y_STEP * SAMPLE_BYTES));
+        U = sample(u + at) - c_off, V = sample(v + at + (ptrdiff_t)(py >> sy) * v_extra) - c_off;
+    }
+    __device__ __forceinline__ void load(int px, int py, int (&c)[3]) const
+    {
+        int Y, U, V;
+        fetch(px, py, Y, U, V);
         // 24-bit multiplies (full rate; a 32-bit v_mul_lo_u32 is not), exact here: every coefficient is below 2^23 (the largest, CUB of
         // BT.2020 limited, is 2 245 836), the samples are below 2^10, and the low 32 bits of the product are the product (|sum| <= 5.81e8).
         // resize_yuv420_kernel gets the same instructions from its literal constants

@@ -6,8 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HUMAN_DTYPE, OVERLAY_PRIM_DTYPE, TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL, YUV_FORMATS, YUV_LAYOUTS, YUV_MATRICES, YUV_RANGES,
-                   DevBuf, Human, OverlayPrim, Roi, Tiling, YuvImage, as_ptr, check, lib)
+from ._lib import (HDR_DEFAULT_PEAK, HDR_DEFAULT_WHITE, HDR_TRANSFERS, HUMAN_DTYPE, OVERLAY_PRIM_DTYPE, TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL,
+                   YUV_FORMATS, YUV_LAYOUTS, YUV_MATRICES, YUV_RANGES, DevBuf, HdrDesc, Human, OverlayPrim, Roi, Tiling, YuvImage, as_ptr, check, lib)
 
 
 def resize(src_dev, sw: int, sh: int, dst_dev, dw: int, dh: int, stream=None, src_stride=None, dst_stride=None) -> None:
@@ -166,25 +166,86 @@ def yuv_upload(planes, fmt: str, pitch=0, fill: int = 0xA5):
     return bufs, strides
 
 
-def resize_yuv(im: YuvImage, dst_dev, dw: int, dh: int, keep_ratio: bool = False, bgcolor=(0, 0, 0), stream=None, dst_stride=None) -> None:
-    """``hp_resize_yuv`` / ``hp_letterbox_yuv`` on an image whose planes are in device memory."""
+def resize_yuv(im: YuvImage, dst_dev, dw: int, dh: int, keep_ratio: bool = False, bgcolor=(0, 0, 0), stream=None, dst_stride=None, tonemap=None) -> None:
+    """``hp_resize_yuv`` / ``hp_letterbox_yuv`` on an image whose planes are in device memory; with ``tonemap`` (a ``Tonemap``) their HDR twins
+    ``hp_resize_yuv_hdr`` / ``hp_letterbox_yuv_hdr``: the frame is PQ / HLG P010 or I010."""
     s = C.c_void_p(stream) if stream else None
+    L, tm = lib(), ([tonemap.h] if tonemap is not None else [])
     if keep_ratio:
-        check(lib().hp_letterbox_yuv(C.byref(im), as_ptr(dst_dev), dw, dh, dst_stride or dw * 3, int(bgcolor[0]), int(bgcolor[1]), int(bgcolor[2]), s))
+        call = L.hp_letterbox_yuv_hdr if tm else L.hp_letterbox_yuv
+        check(call(C.byref(im), *tm, as_ptr(dst_dev), dw, dh, dst_stride or dw * 3, int(bgcolor[0]), int(bgcolor[1]), int(bgcolor[2]), s))
     else:
-        check(lib().hp_resize_yuv(C.byref(im), as_ptr(dst_dev), dw, dh, dst_stride or dw * 3, s))
+        check((L.hp_resize_yuv_hdr if tm else L.hp_resize_yuv)(C.byref(im), *tm, as_ptr(dst_dev), dw, dh, dst_stride or dw * 3, s))
 
 
 def resize_yuv_host(frame_planes, dw: int, dh: int, fmt: str = "nv12", matrix: str = "bt601", range: str = "limited", keep_ratio: bool = False,
-                    bgcolor=(0, 0, 0), pitch: int = 0) -> np.ndarray:
+                    bgcolor=(0, 0, 0), pitch=0, tonemap=None) -> np.ndarray:
     """Convenience for tests: a host frame (its list of 2-D plane arrays, see ``yuv_planes``) -> device -> converted + resized -> host.
     ``pitch`` > 0 pads every plane row by that many bytes on the device."""
     w, h = yuv_size_of_planes(fmt, frame_planes)
     bufs, strides = yuv_upload(frame_planes, fmt, pitch)
     dst = DevBuf(dw * dh * 3)
-    resize_yuv(yuv_image(fmt, [b.ptr for b in bufs], strides, w, h, matrix, range), dst, dw, dh, keep_ratio, bgcolor)
+    resize_yuv(yuv_image(fmt, [b.ptr for b in bufs], strides, w, h, matrix, range), dst, dw, dh, keep_ratio, bgcolor, tonemap=tonemap)
     check(lib().hp_device_synchronize())
     return dst.to_numpy(np.uint8, (dh, dw, 3))
+
+
+# ---- HDR video in: PQ / HLG 10-bit frames tone-mapped inside the fused resize (include/hp_hip.h; the rule: csrc/tonemap.hpp, DESIGN.md 1.1) -----
+
+def hdr_desc(transfer: str = "pq", to_bt709: bool = True, peak_nits: float = HDR_DEFAULT_PEAK, white_nits: float = HDR_DEFAULT_WHITE) -> HdrDesc:
+    """An ``hp_hdr_desc``; ``transfer`` is "pq" or "hlg" (or the raw code, for tests of the refusals)."""
+    return HdrDesc(HDR_TRANSFERS.get(transfer, transfer), int(bool(to_bt709)), float(peak_nits), float(white_nits))
+
+
+def tonemap_tables(transfer: str = "pq", to_bt709: bool = True, peak_nits: float = HDR_DEFAULT_PEAK, white_nits: float = HDR_DEFAULT_WHITE):
+    """``hp_tonemap_tables``: (A uint16 [1024], M int32 [3, 3], O uint8 [4096]), the tables every pixel of an HDR frame goes through."""
+    d = hdr_desc(transfer, to_bt709, peak_nits, white_nits)
+    lin, m, out = np.zeros(1024, np.uint16), np.zeros((3, 3), np.int32), np.zeros(4096, np.uint8)
+    check(lib().hp_tonemap_tables(C.byref(d), lin.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return lin, m, out
+
+
+class Tonemap:
+    """``hp_tonemap``: the tables of one description in device memory, what ``resize_yuv(..., tonemap=)`` and ``resize_rois(..., tonemap=)`` take."""
+
+    def __init__(self, transfer: str = "pq", to_bt709: bool = True, peak_nits: float = HDR_DEFAULT_PEAK, white_nits: float = HDR_DEFAULT_WHITE):
+        self.h = C.c_void_p()
+        self.desc = hdr_desc(transfer, to_bt709, peak_nits, white_nits)
+        check(lib().hp_tonemap_create(C.byref(self.h), C.byref(self.desc)))
+
+    def close(self):
+        if self.h:
+            lib().hp_tonemap_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def tonemap_host(frame_planes, fmt: str, matrix: str = "bt2020", range: str = "limited", transfer: str = "pq", to_bt709: bool = True,
+                 peak_nits: float = HDR_DEFAULT_PEAK, white_nits: float = HDR_DEFAULT_WHITE) -> np.ndarray:
+    """``hp_tonemap_convert_host``: a P010 / I010 frame in host memory (its list of 2-D plane arrays; rows may be padded) -> [h, w, 3] uint8 BGR,
+    no device needed."""
+    for p in frame_planes:
+        assert p.ndim == 2 and p.strides[1] == p.itemsize
+    w, h = yuv_size_of_planes(fmt, frame_planes)
+    im = yuv_image(fmt, [p.ctypes.data for p in frame_planes], [p.strides[0] for p in frame_planes], w, h, matrix, range)
+    d = hdr_desc(transfer, to_bt709, peak_nits, white_nits)
+    out = np.empty((h, w, 3), np.uint8)
+    check(lib().hp_tonemap_convert_host(C.byref(im), C.byref(d), out.ctypes.data_as(C.c_void_p), w * 3))
+    return out
+
+
+def yuv_colours_hdr(matrix: str = "bt2020", range: str = "limited", transfer: str = "pq", to_bt709: bool = True,
+                    peak_nits: float = HDR_DEFAULT_PEAK, white_nits: float = HDR_DEFAULT_WHITE) -> np.ndarray:
+    """``hp_yuv_colours_hdr``: the 19 skeleton colours as 10-bit (Y, U, V) of a PQ / HLG frame, graphics white at ``white_nits``; int32 [19, 3]."""
+    d = hdr_desc(transfer, to_bt709, peak_nits, white_nits)
+    out = np.zeros((19, 3), np.int32)
+    check(lib().hp_yuv_colours_hdr(YUV_MATRICES[matrix], YUV_RANGES[range], C.byref(d), out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 # ---- regions and tiles: many regions of one frame per launch, the tile planner, the way back and the merge (include/hp_hip.h) -----------
@@ -202,7 +263,7 @@ def yuv_roi_alignment(fmt: str):
 
 
 def resize_rois(src, rois, dst_dev, dw: int, dh: int, keep_ratio: bool = False, bgcolor=(0, 0, 0), sw=None, sh=None, src_stride=None,
-                dst_stride=None, slot_stride=None, stream=None) -> None:
+                dst_stride=None, slot_stride=None, stream=None, tonemap=None) -> None:
     """``hp_resize_rois_u8c3`` / ``hp_resize_rois_yuv``: the regions ``rois`` [(x, y, w, h)] of ONE device frame - 8-bit BGR (``src`` a device
     buffer, with ``sw``, ``sh`` and optionally ``src_stride``) or a ``YuvImage`` with device planes - to ``len(rois)`` slots of ``dst_dev``,
     slot i at byte ``i * slot_stride`` (default: slots back to back), each what ``resize`` / ``letterbox`` give on the cut-out region."""
@@ -211,7 +272,10 @@ def resize_rois(src, rois, dst_dev, dw: int, dh: int, keep_ratio: bool = False, 
     ss = C.c_size_t(int(slot_stride if slot_stride is not None else ds * dh))
     s = C.c_void_p(stream) if stream else None
     bg = [int(c) for c in bgcolor]
-    if isinstance(src, YuvImage):
+    if isinstance(src, YuvImage) and tonemap is not None:  # a PQ / HLG P010 or I010 frame
+        check(lib().hp_resize_rois_yuv_hdr(C.byref(src), tonemap.h, arr, n, int(bool(keep_ratio)), bg[0], bg[1], bg[2], as_ptr(dst_dev), int(dw), int(dh),
+                                           ds, ss, s))
+    elif isinstance(src, YuvImage):
         check(lib().hp_resize_rois_yuv(C.byref(src), arr, n, int(bool(keep_ratio)), bg[0], bg[1], bg[2], as_ptr(dst_dev), int(dw), int(dh), ds, ss, s))
     else:
         check(lib().hp_resize_rois_u8c3(as_ptr(src), int(sw), int(sh), int(src_stride or sw * 3), arr, n, int(bool(keep_ratio)), bg[0], bg[1], bg[2],
@@ -286,6 +350,12 @@ class Overlay:
         self.max_humans = int(max_humans)
         check(lib().hp_overlay_create(C.byref(self.h), self.max_humans))
 
+    def set_transfer(self, transfer=None, to_bt709: bool = True, peak_nits: float = HDR_DEFAULT_PEAK, white_nits: float = HDR_DEFAULT_WHITE) -> None:
+        """``hp_overlay_set_transfer``: 10-bit frames drawn through this handle are "pq" / "hlg" frames and get ``yuv_colours_hdr``'s colours;
+        ``None`` means SDR again."""
+        d = None if transfer is None else hdr_desc(transfer, to_bt709, peak_nits, white_nits)
+        check(lib().hp_overlay_set_transfer(self.h, C.byref(d) if d is not None else None))
+
     def close(self):
         if self.h:
             lib().hp_overlay_destroy(self.h)
@@ -321,7 +391,8 @@ def draw_humans(target, humans, opacity: float = 1.0, thickness: int = 0, w=None
         check(lib().hp_overlay_draw_u8c3(ov.h, as_ptr(target), int(w), int(h), int(stride or w * 3), hp, len(hs), C.c_float(opacity), int(thickness), s))
 
 
-def draw_humans_host(frame, humans, fmt=None, matrix: str = "bt601", range: str = "limited", opacity: float = 1.0, thickness: int = 0) -> None:
+def draw_humans_host(frame, humans, fmt=None, matrix: str = "bt601", range: str = "limited", opacity: float = 1.0, thickness: int = 0,
+                     hdr=None) -> None:
     """The same picture on a frame in HOST memory, in place, no device needed: ``frame`` is a uint8 array [h, w, 3] (BGR, ``fmt`` None) or the
     list of 2-D plane arrays ``yuv_planes`` returns (``fmt`` names the layout).  Rows may be padded (views of wider arrays); samples must be
     contiguous within a row."""
@@ -336,4 +407,7 @@ def draw_humans_host(frame, humans, fmt=None, matrix: str = "bt601", range: str 
         assert p.ndim == 2 and p.strides[1] == p.itemsize and p.flags.writeable
     w, h = yuv_size_of_planes(fmt, frame)
     im = yuv_image(fmt, [p.ctypes.data for p in frame], [p.strides[0] for p in frame], w, h, matrix, range)
+    if hdr is not None:  # an ``hdr_desc``: the frame is PQ / HLG (``hp_overlay_draw_yuv_host_hdr``)
+        check(lib().hp_overlay_draw_yuv_host_hdr(C.byref(im), C.byref(hdr), hp, len(hs), C.c_float(opacity), int(thickness)))
+        return
     check(lib().hp_overlay_draw_yuv_host(C.byref(im), hp, len(hs), C.c_float(opacity), int(thickness)))

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HUMAN_DTYPE, TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL, YUV_FORMATS, YUV_LAYOUTS, Human, YuvImage,
+from ._lib import (HDR_DEFAULT_PEAK, HDR_DEFAULT_WHITE, HUMAN_DTYPE, TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL, YUV_FORMATS, YUV_LAYOUTS, Human, YuvImage,
                    check, lib)
 from .engine import _DTYPES, EngineDesc, Layer, OutputDesc
 
@@ -76,6 +76,17 @@ class Pipeline:
             return
         t = frontend.tiling(cols, rows, overlap, with_full, min_common, tol)
         check(lib().hp_pipeline_set_tiling(self._h, C.byref(t)))
+
+    def set_tonemap(self, transfer=None, to_bt709: bool = True, peak_nits: float = HDR_DEFAULT_PEAK, white_nits: float = HDR_DEFAULT_WHITE) -> None:
+        """``hp_pipeline_set_tonemap``: from now on the P010 / I010 frames of ``submit_yuv_images`` are ``transfer`` = "pq" or "hlg" frames and are
+        tone-mapped to SDR sRGB while they are resized (include/hp_hip.h, "HDR video in"); 8-bit frames are converted as before.
+        ``set_tonemap(None)`` turns it off.  Not while batches are in flight."""
+        from . import frontend
+        if transfer is None:
+            check(lib().hp_pipeline_set_tonemap(self._h, None))
+            return
+        d = frontend.hdr_desc(transfer, to_bt709, peak_nits, white_nits)
+        check(lib().hp_pipeline_set_tonemap(self._h, C.byref(d)))
 
     def submit(self, frames) -> None:
         """frames: list of [h, w, 3] uint8 BGR arrays (any sizes), at most max_batch."""

@@ -223,6 +223,48 @@ void hp_humans_to_frame(hp_human* humans, int n, const hp_roi* roi, int frame_w,
 int hp_humans_merge(const hp_human* in, const int32_t* region_of, int n, int frame_w, int frame_h, int min_common, double tol,
                     hp_human* out, int cap); /* returns the count kept */
 
+/* ---- HDR video in: PQ (SMPTE ST 2084) and HLG (BT.2100) 10-bit frames - HDR10 / HLG as a Main10 decoder hands them out, P010 or I010 with the BT.2020
+ * matrix - tone-mapped to the network's 8-bit sRGB BGR input inside the fused resize (hyperpose_amd/csrc/resize_yuv_hdr.hip; the rule is stated once in
+ * csrc/tonemap.hpp and DESIGN.md 1.1).  hp_yuv_image does not grow: the HDR description travels beside it.  Per source pixel, with Y, U, V the 10-bit
+ * samples and k = hp_yuv_coefficients(matrix, range, 10), everything int32 with arithmetic shifts:
+ *   1. R'G'B' at 10 bits    u = U - c_off, v = V - c_off, yy = max(0, Y - y_off) * CY + (1 << 17);  E_B = sat10((yy + CUB*u) >> 18),
+ *                           E_G = sat10((yy + CVG*v + CUG*u) >> 18), E_R = sat10((yy + CVR*v) >> 18), sat10 clamps to [0, 1023]; full scale is 1020 (255 * 4)
+ *   2. SDR linear light     L_c = A[E_c] per channel, A[i] = rint(65535 * tm(nits(min(i, 1020) / 1020.0))), uint16 [1024]
+ *                           PQ:  nits(e) = 10000 * EOTF_ST2084(e) (m1 = 2610/16384, m2 = 128 * 2523/4096, c1 = 3424/4096, c2 = 32 * 2413/4096, c3 = 32 * 2392/4096)
+ *                           HLG: nits(e) = 1000 * invOETF_BT2100(e)^1.2 (a = 0.17883277, b = 0.28466892, c = 0.55991073): the system gamma of a 1000 cd/m2
+ *                                display applied PER CHANNEL - an approximation of BT.2100's OOTF, which scales R, G, B by a power of their luminance
+ *                           tm(L): x = L / white_nits, p = peak_nits / white_nits, tm = min(1, x * (1 + x / (p * p)) / (1 + x)): extended Reinhard, applied
+ *                                per channel (not on luminance, so saturated highlights desaturate), monotone, tm(peak_nits) = 1
+ *   3. primaries            when to_bt709:  (R, G, B) = clamp((M * (L_R, L_G, L_B) + 2048) >> 12, 0, 65535), M = rint(4096 * M_2020->709), M_2020->709 =
+ *                           inv(RGB709->XYZ) * RGB2020->XYZ from the two sets of chromaticities and D65 in double:
+ *                           M = { 6801, -2407, -298,  -510, 4640, -34,  -74, -412, 4582 }, every row sums to 4096 (greys stay grey)
+ *   4. sRGB bytes           c8 = O[value >> 4], O[j] = rint(255 * sRGB_OETF((16 * j + 7.5) / 65535.0)), uint8 [4096]
+ * and the output equals, byte for byte, "convert the whole frame to 8-bit BGR by this rule (hp_tonemap_convert_host), then hp_resize_u8c3 /
+ * hp_letterbox_u8c3": conversion happens per tap, the resize arithmetic is the one every other feed has.  The defaults below are a product decision
+ * (BT.2408 reference white, a 1000 cd/m2 grade), no part of the contract.  HP_ERR_INVALID, with a message that names the argument, and nothing launched:
+ * a transfer other than HP_TRC_PQ / HP_TRC_HLG; peak_nits or white_nits not finite, or not 0 < white_nits <= peak_nits <= 10000; an 8-bit layout given to
+ * a *_hdr call (the message names the format); a null handle; whatever the SDR twin of the call refuses. */
+enum { HP_TRC_PQ = 1, HP_TRC_HLG = 2 };
+#define HP_HDR_DEFAULT_PEAK 1000.0f
+#define HP_HDR_DEFAULT_WHITE 203.0f
+typedef struct hp_hdr_desc {
+    int32_t transfer, to_bt709; /* HP_TRC_*; to_bt709 != 0: step 3 (BT.2020 primaries -> BT.709), 0: the channels are taken as they are */
+    float peak_nits, white_nits;
+} hp_hdr_desc;
+/* host only: the ONE statement of the three tables (as hp_yuv_coefficients is of the matrix); m is row-major, the identity * 4096 when to_bt709 == 0 */
+int hp_tonemap_tables(const hp_hdr_desc* d, uint16_t lin[1024], int32_t m[9], uint8_t out[4096]);
+/* the handle owns the tables in device memory (6 KiB), immutable after create; destroy waits for the device */
+typedef struct hp_tonemap hp_tonemap;
+int hp_tonemap_create(hp_tonemap** out, const hp_hdr_desc* d);
+void hp_tonemap_destroy(hp_tonemap* t);
+/* the HDR twins of hp_resize_yuv / hp_letterbox_yuv / hp_resize_rois_yuv for P010 / I010 frames: same argument rules, they only enqueue */
+int hp_resize_yuv_hdr(const hp_yuv_image* src /* device planes */, const hp_tonemap* t, uint8_t* dev_dst, int dw, int dh, int dst_stride, void* stream);
+int hp_letterbox_yuv_hdr(const hp_yuv_image* src, const hp_tonemap* t, uint8_t* dev_dst, int dw, int dh, int dst_stride, int b, int g, int r, void* stream);
+int hp_resize_rois_yuv_hdr(const hp_yuv_image* src, const hp_tonemap* t, const hp_roi* rois, int n, int keep_ratio, int b, int g, int r,
+                           uint8_t* dev_dst, int dw, int dh, int dst_stride, size_t slot_stride, void* stream);
+/* the whole-frame conversion in plain C++, no device: a P010 / I010 frame in HOST memory (any address, any stride that covers a row) -> 8-bit BGR HWC */
+int hp_tonemap_convert_host(const hp_yuv_image* host_frame, const hp_hdr_desc* d, uint8_t* bgr, int stride);
+
 /* ---- writing back: the skeletons of a frame's humans painted into a DEVICE-resident frame, 8-bit BGR or any hp_yuv_image layout in the frame's
  * own colour space and bit depth (hyperpose_amd/csrc/overlay.hip) - the last stage of the reference's stream, draw_human + writer
  * (src/stream.cpp:114-147), for frames that never leave the device.  The picture is defined by exact integer rules, stated once in
@@ -263,6 +305,16 @@ int hp_overlay_draw_yuv(hp_overlay* o, const hp_yuv_image* frame /* planes in DE
 /* the same picture on frames in HOST memory (plain C++, the integer rules above; no device needed) */
 int hp_overlay_draw_u8c3_host(uint8_t* bgr, int w, int h, int stride, const hp_human* humans, int n, float opacity, int thickness);
 int hp_overlay_draw_yuv_host(const hp_yuv_image* frame, const hp_human* humans, int n, float opacity, int thickness);
+/* Drawing on HDR frames.  hp_yuv_colours paints "red" at the code for 10 000 cd/m2 of a PQ frame; hp_yuv_colours_hdr gives draw_human's 19 colours as
+ * graphics white at white_nits (BT.2408), 10-bit (Y, U, V), all in float64 then nearbyint: sRGB EOTF of c / 255 per channel; when to_bt709 the inverse
+ * of the (unrounded) primaries matrix above, clipped at 0; times white_nits; the inverse PQ EOTF of nits / 10000, or for HLG (nits / 1000)^(1 / 1.2)
+ * followed by the HLG OETF; then the Y'CbCr formulas of hp_yuv_colours at depth 10.  peak_nits takes no part.  Host only.
+ * hp_overlay_set_transfer: d == NULL means SDR (the default).  While set, hp_overlay_draw_yuv uses that table on the 10-bit layouts (8-bit frames and
+ * BGR are painted as before); hp_overlay_draw_yuv_host_hdr is the host twin (d == NULL: hp_overlay_draw_yuv_host).  The kernels are the same: colours
+ * are a host table packed into the primitives. */
+int hp_yuv_colours_hdr(int matrix, int range, const hp_hdr_desc* d, int32_t out[19][3]);
+int hp_overlay_set_transfer(hp_overlay* o, const hp_hdr_desc* d);
+int hp_overlay_draw_yuv_host_hdr(const hp_yuv_image* frame, const hp_hdr_desc* d, const hp_human* humans, int n, float opacity, int thickness);
 
 /* ---- hyperpose::parser::paf (include/hyperpose/operator/parser/paf.hpp:17-93, src/paf.cpp) -------- */
 typedef struct hp_paf hp_paf;
@@ -600,6 +652,10 @@ int hp_pipeline_in_flight(const hp_pipeline* p);
  * normalised coordinates, ready for hp_overlay_draw_*.  A frame of one region (1 x 1 tiles, no whole frame) has nothing to merge and keeps the
  * parser's order: it is returned exactly as with tiling off.  Every parser kind works: the tail is shared. */
 int hp_pipeline_set_tiling(hp_pipeline* p, const hp_tiling* t);
+/* HDR input ("HDR video in" above); d == NULL turns it off (the default), HP_ERR_STATE while batches are in flight.  While set, every P010 / I010 frame
+ * of hp_pipeline_submit_yuv_images - host or device planes, tiled or not - goes through hp_resize_yuv_hdr / hp_letterbox_yuv_hdr / hp_resize_rois_yuv_hdr
+ * with the tables of d; 8-bit frames of the same batch take the SDR path unchanged.  The pipeline owns its hp_tonemap. */
+int hp_pipeline_set_tonemap(hp_pipeline* p, const hp_hdr_desc* d);
 
 #ifdef __cplusplus
 }

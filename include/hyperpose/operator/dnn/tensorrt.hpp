@@ -145,11 +145,31 @@ namespace dnn {
                 hp_free(m_dev_raw);
             if (m_dev_net)
                 hp_free(m_dev_net);
+            hp_tonemap_destroy(m_tonemap);
             hp_engine_destroy(m_engine);
             hp_model_destroy(m_model);
         }
 
         inline int max_batch_size() noexcept { return m_max_batch_size; }
+
+        /// Addition: HDR input (utility/data.hpp, hdr; hp_tonemap_create).  While set, the 10-bit yuv_frames (HP_YUV_P010 / HP_YUV_I010) of
+        /// inference(std::vector<yuv_frame>), calibrate(std::vector<yuv_frame>) and inference(yuv_frame, regions) are PQ / HLG frames and are
+        /// tone-mapped to SDR sRGB while they are resized (hp_resize_yuv_hdr, hp_letterbox_yuv_hdr, hp_resize_rois_yuv_hdr); 8-bit frames take
+        /// the SDR calls as before.  A description the C ABI refuses is a std::logic_error and leaves the previous one in place.
+        void set_tonemap(const hdr& h)
+        {
+            const hp_hdr_desc d = h.c_form();
+            hp_tonemap* next = nullptr;
+            if (hp_tonemap_create(&next, &d) != HP_OK)
+                throw std::logic_error(hp_last_error());
+            hp_tonemap_destroy(m_tonemap);
+            m_tonemap = next;
+        }
+        void clear_tonemap()
+        {
+            hp_tonemap_destroy(m_tonemap);
+            m_tonemap = nullptr;
+        }
         inline cv::Size input_size() noexcept { return m_inp_size; }
 
         /// src/tensorrt.cpp:436-461: every image is brought to the network's size (cv::resize, or non_scaling_resize when keep_ratio)
@@ -287,9 +307,12 @@ namespace dnn {
             std::vector<uint8_t> scratch;
             const hp_yuv_image im = yuv_image_on_device(frame, scratch);
             const std::vector<hp_roi> rois = to_rois(regions);
-            if (hp_resize_rois_yuv(&im, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width, m_inp_size.height,
-                    m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
-                != HP_OK)
+            const hp_tonemap* tm = tonemap_for(frame);
+            const int rc = tm ? hp_resize_rois_yuv_hdr(&im, tm, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width,
+                                    m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
+                              : hp_resize_rois_yuv(&im, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width,
+                                    m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine));
+            if (rc != HP_OK)
                 throw std::logic_error(hp_last_error());
             if (hp_engine_infer_u8(m_engine, m_dev_net, (int)rois.size(), 1, nullptr) != HP_OK)
                 fatal(hp_last_error());
@@ -486,13 +509,18 @@ namespace dnn {
                 fatal(hp_last_error());
         }
         // the same for a yuv_frame of any layout: a host frame's planes are packed without row padding into ONE upload of
-        // hp_yuv_packed_bytes, a device frame is read where it lies; then hp_resize_yuv / hp_letterbox_yuv writes dst
+        // hp_yuv_packed_bytes, a device frame is read where it lies; then hp_resize_yuv / hp_letterbox_yuv - for a 10-bit frame under
+        // set_tonemap their *_hdr twins - writes dst
         void yuv_image_to_device(const yuv_frame& f, uint8_t* dst, std::vector<uint8_t>& scratch)
         {
             const hp_yuv_image im = yuv_image_on_device(f, scratch);
-            const int rc = m_keep_ratio
-                ? hp_letterbox_yuv(&im, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, 0, 0, 0, hp_engine_stream(m_engine))
-                : hp_resize_yuv(&im, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, hp_engine_stream(m_engine));
+            const int w = m_inp_size.width, h = m_inp_size.height;
+            void* s = hp_engine_stream(m_engine);
+            int rc;
+            if (const hp_tonemap* tm = tonemap_for(f))
+                rc = m_keep_ratio ? hp_letterbox_yuv_hdr(&im, tm, dst, w, h, w * 3, 0, 0, 0, s) : hp_resize_yuv_hdr(&im, tm, dst, w, h, w * 3, s);
+            else
+                rc = m_keep_ratio ? hp_letterbox_yuv(&im, dst, w, h, w * 3, 0, 0, 0, s) : hp_resize_yuv(&im, dst, w, h, w * 3, s);
             if (rc != HP_OK || hp_engine_synchronize(m_engine) != HP_OK) // m_dev_raw is re-used by the next frame
                 fatal(hp_last_error());
         }
@@ -536,6 +564,11 @@ namespace dnn {
                     fatal(hp_last_error());
             }
             return im;
+        }
+        // the tone-map of a frame: set_tonemap's for the 10-bit layouts, none (the SDR calls) otherwise
+        const hp_tonemap* tonemap_for(const yuv_frame& f) const
+        {
+            return m_tonemap && (f.format == HP_YUV_P010 || f.format == HP_YUV_I010) ? m_tonemap : nullptr;
         }
         void reserve_raw(size_t bytes)
         {
@@ -615,6 +648,7 @@ namespace dnn {
         size_t m_raw_bytes = 0;
         uint8_t* m_dev_net = nullptr; // the batch at network size
         uint8_t* m_host_net = nullptr; // ... and its pinned staging copy on the host
+        hp_tonemap* m_tonemap = nullptr; // set_tonemap: the tables of the HDR description in device memory
         std::shared_ptr<std::atomic<uint64_t>> m_calls; // bumped whenever the engine's output buffers are about to be overwritten
         std::weak_ptr<detail::device_batch> m_last;
     };

@@ -87,6 +87,14 @@ public:
         m_max_batch = t ? m_engine_batch / t->regions() : m_engine_batch;
     }
 
+    // hp_pipeline_set_tonemap: 10-bit yuv_frames pushed from now on are PQ / HLG frames (utility/data.hpp, hdr); nullptr turns it off.  Not while
+    // batches are in flight (std::runtime_error)
+    void set_tonemap(const hdr* h)
+    {
+        const hp_hdr_desc c = h ? h->c_form() : hp_hdr_desc{};
+        detail::hp_check(hp_pipeline_set_tonemap(m_pl, h ? &c : nullptr));
+    }
+
     // one batch (<= max_batch_size frames, any sizes); throws when every pipe is busy
     void push(const std::vector<cv::Mat>& frames)
     {
@@ -255,6 +263,11 @@ public:
     /// first input is connected: the tiling cannot change while batches are in flight (std::runtime_error).
     void set_tiling(const tiling& t) { m_gpu.set_tiling(&t); }
     void clear_tiling() { m_gpu.set_tiling(nullptr); }
+
+    /// Addition: HDR input (utility/data.hpp, hdr; hp_pipeline_set_tonemap): the P010 / I010 yuv_frames the inputs deliver are PQ / HLG frames and
+    /// are tone-mapped to SDR sRGB inside the fused resize; 8-bit frames are converted as before.  Like the tiling, not while batches are in flight.
+    void set_tonemap(const hdr& h) { m_gpu.set_tonemap(&h); }
+    void clear_tonemap() { m_gpu.set_tonemap(nullptr); }
 
 private:
     struct item {

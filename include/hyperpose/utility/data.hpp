@@ -32,6 +32,17 @@ struct tiling {
     hp_tiling c_form() const { return hp_tiling{ cols, rows, overlap_x, overlap_y, with_full ? 1 : 0, min_common, tol }; }
 };
 
+/// Addition: HDR input (include/hp_hip.h, "HDR video in").  The description of a stream of PQ (HDR10) or HLG 10-bit frames - P010 / I010 yuv_frames -
+/// that dnn::tensorrt::set_tonemap, the stream's set_tonemap and draw_humans take: which transfer function the code values follow, whether the
+/// BT.2020 primaries are converted to BT.709, and the tone curve's two parameters (the defaults are HP_HDR_DEFAULT_*: BT.2408 reference white, a
+/// 1000 cd/m2 grade).  The tone curve and the HLG system gamma are applied per channel, an approximation the header states.
+struct hdr {
+    int transfer = HP_TRC_PQ; // HP_TRC_PQ or HP_TRC_HLG
+    bool to_bt709 = true;
+    float peak_nits = HP_HDR_DEFAULT_PEAK, white_nits = HP_HDR_DEFAULT_WHITE;
+    hp_hdr_desc c_form() const { return hp_hdr_desc{ transfer, to_bt709 ? 1 : 0, peak_nits, white_nits }; }
+};
+
 /// hp_tile_plan: the regions of a `size` frame, the whole frame first when t.with_full, then the tiles row-major.  `yuv_format`: the
 /// HP_YUV_* layout whose chroma alignment the tiles keep (-1: none, a BGR frame).  Throws std::invalid_argument on a plan the rules refuse.
 inline std::vector<cv::Rect> plan_tiles(cv::Size size, const tiling& t, int yuv_format = -1)

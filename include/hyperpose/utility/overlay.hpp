@@ -73,6 +73,23 @@ inline void draw_humans(yuv_frame& frame, const std::vector<human_t>& humans, fl
         detail::overlay_check(hp_overlay_draw_yuv_host(&im, list.data(), (int)list.size(), opacity, thickness));
 }
 
+/// The same on an HDR frame (utility/data.hpp, hdr): a P010 / I010 frame is painted with graphics white at `h.white_nits` in the frame's transfer
+/// function (hp_yuv_colours_hdr) instead of full-scale code values; an 8-bit frame is painted as above.
+inline void draw_humans(yuv_frame& frame, const std::vector<human_t>& humans, const hdr& h, float opacity = 1, int thickness = 0, void* stream = nullptr)
+{
+    const auto list = detail::to_c_humans(humans);
+    const hp_yuv_image im = frame.image();
+    const hp_hdr_desc d = h.c_form();
+    if (frame.on_device) {
+        hp_overlay* o = detail::overlay_handle(list.size());
+        detail::overlay_check(hp_overlay_set_transfer(o, &d));
+        const int rc = hp_overlay_draw_yuv(o, &im, list.data(), (int)list.size(), opacity, thickness, stream);
+        hp_overlay_set_transfer(o, nullptr); // the thread's handle serves the SDR overloads too
+        detail::overlay_check(rc);
+    } else
+        detail::overlay_check(hp_overlay_draw_yuv_host_hdr(&im, &d, list.data(), (int)list.size(), opacity, thickness));
+}
+
 inline void draw_humans(const device_bgr& picture, const std::vector<human_t>& humans, float opacity = 1, int thickness = 0, void* stream = nullptr)
 {
     const auto list = detail::to_c_humans(humans);

@@ -19,7 +19,11 @@ name) go through hp_pipeline_submit_yuv_images from pinned host memory - P010 mo
 `<layout>-device` submits the same frames as device-resident surfaces uploaded before the timed region (no H2D copy at all).  The record
 of all of them is profiles/yuv_formats_bench.json:
 
-    python tools/yuv_input_bench.py --formats bgr,nv12,nv12-image,p010,yuy2,nv12-device,p010-device --out profiles/yuv_formats_bench.json
+    python tools/yuv_input_bench.py --formats bgr,nv12,nv12-image,p010,yuy2,nv12-device,p010-device,p010-hdr,p010-hdr-device --out profiles/yuv_formats_bench.json
+
+`<layout>-hdr` and `<layout>-hdr-device` (10-bit layouts) are the very bytes of `<layout>` / `<layout>-device` on a pipeline with
+Pipeline.set_tonemap("pq"): the frames go through resize_yuv_hdr_kernel instead of resize_yuv_word16_kernel.  Each HDR feed is reported against its
+SDR twin: the ratio of the medians, the difference in frames/s and whether it lies within the larger of the two feeds' own spreads.
 """
 from __future__ import annotations
 
@@ -45,7 +49,7 @@ FRAME_W, FRAME_H = 1280, 720
 class Feed:
     """One pipeline fed from pinned host memory with pre-marshalled pointers, as bench.py's HostFed does."""
 
-    def __init__(self, model, weights, cfg, frames: np.ndarray, fmt: str, layout: str = None, on_device: bool = False):
+    def __init__(self, model, weights, cfg, frames: np.ndarray, fmt: str, layout: str = None, on_device: bool = False, hdr: bool = False):
         """`frames`: [batch, bytes...] uint8, one tightly packed frame per row.  `fmt` "bgr" / "nv12" are the two legacy calls; with `layout`
         the frames go through hp_pipeline_submit_yuv_images (BT.601 limited), from pinned host memory or, `on_device`, from device memory."""
         from hyperpose_amd import _lib, frontend
@@ -77,6 +81,8 @@ class Feed:
                 self.images[i] = frontend.yuv_image(layout, planes, strides, FRAME_W, FRAME_H)
         self.pl = Pipeline(model, weights, max_batch=b, n_pipes=cfg["pipes"], keep_ratio=True, max_frame_wh=(FRAME_W, FRAME_H), parser=cfg["parser"],
                            dtype=cfg["dtype"])
+        if hdr:
+            self.pl.set_tonemap("pq")
         self.humans = 0
         self.first = None  # the humans of the first batch collected (the two feeds are compared on it)
 
@@ -144,7 +150,8 @@ def kernel_times(stats_dir: str) -> dict:
         with open(path, newline="") as f:
             for row in csv.DictReader(f):
                 name = row.get("Name", "")
-                for key in ("resize_u8c3_kernel", "resize_yuv420_kernel", "resize_yuv_planar8_kernel", "resize_yuv_packed8_kernel", "resize_yuv_word16_kernel"):
+                for key in ("resize_u8c3_kernel", "resize_yuv420_kernel", "resize_yuv_planar8_kernel", "resize_yuv_packed8_kernel", "resize_yuv_word16_kernel",
+                            "resize_yuv_hdr_kernel"):
                     if key in name:
                         out[key] = {"calls": int(row["Calls"]), "average_us": round(float(row["AverageNs"]) / 1e3, 2),
                                     "min_us": round(float(row["MinNs"]) / 1e3, 2), "max_us": round(float(row["MaxNs"]) / 1e3, 2)}
@@ -193,13 +200,15 @@ def main(argv=None) -> int:
             feeds[name], kernels[name] = Feed(model, weights, cfg, nv12, "nv12"), "resize_yuv420_kernel"
         else:
             layout = name.split("-")[0]
-            if layout not in _lib.YUV_LAYOUTS or name.split("-")[1:] not in ([], ["image"], ["device"]):
-                ap.error(f"--formats: {name!r} is not bgr, nv12, <layout>, <layout>-image or <layout>-device")
+            hdr = "hdr" in name.split("-")[1:]
+            if layout not in _lib.YUV_LAYOUTS or name.split("-")[1:] not in ([], ["image"], ["device"], ["hdr"], ["hdr", "device"]) or (
+                    hdr and _lib.YUV_LAYOUTS[layout][2] != 2):
+                ap.error(f"--formats: {name!r} is not bgr, nv12, <layout>, <layout>-image, <layout>-device or, for a 10-bit layout, <layout>-hdr[-device]")
             # NV12 feeds carry the legacy feed's very bytes (same humans); the other layouts the same pictures through the input generator
             packed = nv12.reshape(batch, -1) if layout == "nv12" else np.stack(
                 [np.concatenate([p.view(np.uint8).ravel() for p in f]) for f in synth.bgr_to_yuv(big, layout)])
-            feeds[name] = Feed(model, weights, cfg, packed, name, layout=layout, on_device=name.endswith("-device"))
-            kernels[name] = {1: "resize_yuv_packed8_kernel"}.get(_lib.YUV_LAYOUTS[layout][1], "resize_yuv_word16_kernel" if _lib.YUV_LAYOUTS[layout][2] == 2
+            feeds[name] = Feed(model, weights, cfg, packed, name, layout=layout, on_device=name.endswith("-device"), hdr=hdr)
+            kernels[name] = "resize_yuv_hdr_kernel" if hdr else {1: "resize_yuv_packed8_kernel"}.get(_lib.YUV_LAYOUTS[layout][1], "resize_yuv_word16_kernel" if _lib.YUV_LAYOUTS[layout][2] == 2
                                                                else "resize_yuv_planar8_kernel")
     chunk = max(2 * cfg["pipes"], 4)
     rounds = {name: [] for name in names}
@@ -227,6 +236,14 @@ def main(argv=None) -> int:
                 rec[f"{name}_over_{base}"] = round(rec[name]["frames_per_s_median"] / rec[base]["frames_per_s_median"], 4)
                 key = "nv12_not_slower_within_spread" if (name, base) == ("nv12", "bgr") else f"{name}_not_slower_than_{base}_within_spread"
                 rec[key] = bool(rec[name]["frames_per_s_median"] >= rec[base]["frames_per_s_median"] - margin)
+    for name in names:  # every HDR feed against its SDR twin
+        twin = name.replace("-hdr", "")
+        if twin != name and twin in names:
+            a, b = rec[name], rec[twin]
+            yard = max(a["spread"], b["spread"])
+            rec[f"{name}_over_{twin}"] = round(a["frames_per_s_median"] / b["frames_per_s_median"], 4)
+            rec[f"{name}_minus_{twin}_frames_per_s"] = round(a["frames_per_s_median"] - b["frames_per_s_median"], 1)
+            rec[f"{name}_within_larger_spread_of_{twin}"] = bool(abs(a["frames_per_s_median"] - b["frames_per_s_median"]) <= yard)
     for f in feeds.values():
         f.close()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
