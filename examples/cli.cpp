@@ -20,6 +20,10 @@
 //   * tiled inference (addition): `--tiles=<columns>x<rows> [--tile_overlap=<px>] [--tile_full]`: every frame - BGR or --yuv / .yuv, with or
 //     without --saving_yuv - is inferred on overlapping tiles (one engine call per frame, engine.inference(frame, regions)) and the humans
 //     are merged in the frame's coordinates (hp::plan_tiles / to_frame / merge_humans; stream runtime: stream.set_tiling);
+//   * upright input (addition): `--rotate=0|90|180|270` (the clockwise turn that brings the stored picture upright: a container's rotate tag) and
+//     `--hflip` (the stored picture is mirrored left-right): the frames of every source, in both runtimes, are read upright inside the resize
+//     (engine.set_orientation / stream.set_orientation; hp::orientation).  Pictures and --saving_yuv frames stay in stored orientation, the
+//     skeletons are drawn through hp::to_stored; <file>.humans holds the upright records.  Tiles are planned on the upright frame;
 //   * writing video back (addition): `--saving_yuv=<file>`, for a .yuv source or `--yuv`: every frame is uploaded in its own format, inference
 //     runs on it as a device-resident frame, the skeletons are drawn on the device surface (hp::draw_humans, opacity = alpha; alpha == 0 -> 1)
 //     and the annotated frames are appended to <file> as raw frames of the same format; <file>.humans receives, per frame, an int32 count and
@@ -76,6 +80,9 @@ static int FLAGS_tile_overlap = 64;  // ... pixels neighbouring tiles share at l
 static bool FLAGS_tile_full = false; // ... plus the whole frame as one more region
 static bool g_tiled = false;
 static hp::tiling g_tiling;
+static int FLAGS_rotate = 0;       // addition: --rotate=0|90|180|270: clockwise degrees that bring the stored frames upright (hp::orientation)
+static bool FLAGS_hflip = false;   // ... the stored frames are mirrored left-right
+static hp::orientation g_orient;
 static std::string FLAGS_saving_yuv; // addition: append the frames, annotated on the device in their own format, to this file
 static int FLAGS_synthetic_humans = 0; // addition: stand-in humans added to every frame's poses (see the head of the file)
 static bool g_yuv_from_file = false; // the frames came from a .yuv source (else --yuv made NV12 ones)
@@ -91,9 +98,9 @@ static bool parse_flags(int argc, char** argv)
         { "yuv_matrix", &FLAGS_yuv_matrix }, { "yuv_range", &FLAGS_yuv_range }, { "yuv_transfer", &FLAGS_yuv_transfer } };
     std::map<std::string, double*> dflags = { { "alpha", &FLAGS_alpha }, { "hdr_peak", &FLAGS_hdr_peak }, { "hdr_white", &FLAGS_hdr_white } };
     std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size }, { "tile_overlap", &FLAGS_tile_overlap },
-        { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h }, { "synthetic_humans", &FLAGS_synthetic_humans } };
+        { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h }, { "synthetic_humans", &FLAGS_synthetic_humans }, { "rotate", &FLAGS_rotate } };
     std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 }, { "yuv", &FLAGS_yuv }, { "tile_full", &FLAGS_tile_full },
-        { "hdr_keep_primaries", &FLAGS_hdr_keep_primaries } };
+        { "hdr_keep_primaries", &FLAGS_hdr_keep_primaries }, { "hflip", &FLAGS_hflip } };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a.rfind("--", 0) != 0 && a.rfind("-", 0) == 0)
@@ -124,7 +131,15 @@ static bool parse_flags(int argc, char** argv)
         }
         if (sflags.count(name))
             *sflags[name] = value;
-        else if (iflags.count(name))
+        else if (name == "rotate") { // an enumerated number: anything else, "90deg" or an empty value included, is refused with the list
+            char* end = nullptr;
+            const long v = std::strtol(value.c_str(), &end, 10);
+            if (value.empty() || *end || (v != 0 && v != 90 && v != 180 && v != 270)) {
+                cli_log() << "ERROR: --rotate=" << value << " is not one of 0|90|180|270 (clockwise degrees that bring the stored picture upright)\n";
+                return false;
+            }
+            FLAGS_rotate = (int)v;
+        } else if (iflags.count(name))
             *iflags[name] = std::atoi(value.c_str());
         else if (dflags.count(name))
             *dflags[name] = std::atof(value.c_str());
@@ -133,6 +148,7 @@ static bool parse_flags(int argc, char** argv)
             return false;
         }
     }
+    g_orient = hp::orientation{ FLAGS_rotate / 90, FLAGS_hflip };
     if (!FLAGS_tiles.empty()) { // --tiles CxR, both counts >= 1
         int c = 0, r = 0;
         char x = 0, rest = 0;
@@ -537,6 +553,7 @@ int main(int argc, char** argv)
     auto engine = build_engine();
     if (g_hdr_on)
         engine.set_tonemap(g_hdr);
+    engine.set_orientation(g_orient); // (from here on every frame the engine is given is a stored frame, calibration frames included)
     if (FLAGS_int8 && !engine.calibrated()) { // calibration is never implicit in the engine: the CLI asks for it and says so
         const size_t n = std::min(images.size(), (size_t)FLAGS_max_batch_size);
         if (FLAGS_yuv) {
@@ -556,15 +573,18 @@ int main(int argc, char** argv)
 
     using clk_t = std::chrono::high_resolution_clock;
     size_t n_humans = 0, n_written = 0;
-    auto render = [&](cv::Mat& img, const std::vector<hp::human_t>& poses, bool resume) {
+    // `img` is the picture as stored, `poses` are normalised to the upright frame: resume_ratio runs on the upright size, to_stored brings
+    // the records to the picture
+    auto render = [&](cv::Mat& img, std::vector<hp::human_t> poses, bool resume) {
         cv::Mat background;
         if (FLAGS_alpha > 0)
             background = clone(img);
-        for (auto pose : poses) {
-            if (resume)
-                hp::resume_ratio(pose, img.size(), engine.input_size());
+        if (resume)
+            for (auto& pose : poses)
+                hp::resume_ratio(pose, hp::oriented_size(img.size(), g_orient), engine.input_size());
+        hp::to_stored(poses, g_orient);
+        for (const auto& pose : poses)
             hp::draw_human(img, pose);
-        }
         if (FLAGS_alpha > 0)
             add_weighted(img, FLAGS_alpha, background);
         n_humans += poses.size();
@@ -572,19 +592,21 @@ int main(int argc, char** argv)
     };
 
     // --tiles: one frame's regions in one engine call, every region parsed on its own, the poses brought back to the frame and merged
-    auto tiled_poses = [&](const cv::Mat& frame, const hp::yuv_frame* yuv) {
-        const std::vector<cv::Rect> regions = hp::plan_tiles(frame.size(), g_tiling, yuv ? yuv->format : -1);
-        const auto maps = yuv ? engine.inference(*yuv, regions) : engine.inference(frame, regions);
+    // (with --rotate / --hflip the regions, and the poses returned, are in the upright frame's coordinates)
+    auto tiled_poses = [&](const cv::Mat& stored, const hp::yuv_frame* yuv) {
+        const cv::Size frame = hp::oriented_size(stored.size(), g_orient);
+        const std::vector<cv::Rect> regions = hp::plan_tiles(frame, g_tiling, yuv ? yuv->format : -1, g_orient);
+        const auto maps = yuv ? engine.inference(*yuv, regions) : engine.inference(stored, regions);
         std::vector<hp::human_t> all;
         std::vector<int> region_of;
         for (size_t r = 0; r < regions.size(); ++r)
             for (auto pose : std::visit([&](auto& op) { return op.process(maps[r]); }, parser)) {
                 if (FLAGS_keep_ratio)
                     hp::resume_ratio(pose, cv::Size(regions[r].width, regions[r].height), engine.input_size());
-                hp::to_frame(pose, regions[r], frame.size());
+                hp::to_frame(pose, regions[r], frame);
                 all.push_back(pose), region_of.push_back((int)r);
             }
-        return regions.size() == 1 ? all : hp::merge_humans(all, region_of, frame.size(), g_tiling.min_common, g_tiling.tol);
+        return regions.size() == 1 ? all : hp::merge_humans(all, region_of, frame, g_tiling.min_common, g_tiling.tol);
     };
 
     auto beg = clk_t::now();
@@ -617,11 +639,12 @@ int main(int argc, char** argv)
                     std::vector<hp::human_t> drawn = poses;
                     if (FLAGS_keep_ratio && !g_tiled) // (tiled poses are in the frame's coordinates already)
                         for (auto& pose : drawn)
-                            hp::resume_ratio(pose, batch[k].size(), engine.input_size());
+                            hp::resume_ratio(pose, hp::oriented_size(batch[k].size(), g_orient), engine.input_size());
+                    // `drawn` stays upright (it is what <file>.humans records); the surface is the stored frame
                     if (g_hdr_on)
-                        hp::draw_humans(yuv_batch[k], drawn, g_hdr, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
+                        hp::draw_humans(yuv_batch[k], drawn, g_orient, g_hdr, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
                     else
-                        hp::draw_humans(yuv_batch[k], drawn, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
+                        hp::draw_humans(yuv_batch[k], drawn, g_orient, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
                     std::vector<uint8_t> annotated(g_yuv[first + k].data.size());
                     if (hp_device_synchronize() != HP_OK || hp_memcpy_d2h(annotated.data(), surfaces[k]->p, annotated.size()) != HP_OK) {
                         cli_log() << "ERROR: " << hp_last_error() << "\n";
@@ -643,6 +666,7 @@ int main(int argc, char** argv)
                 auto stream = hp::make_stream(engine, op, true, FLAGS_keep_ratio);
                 if (g_tiled)
                     stream.set_tiling(g_tiling);
+                stream.set_orientation(g_orient);
                 stream.async() << images;
                 auto sink = [&](size_t, const cv::Mat& frame, const std::vector<hp::human_t>& poses) {
                     cv::Mat img = clone(frame);

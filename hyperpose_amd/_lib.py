@@ -117,6 +117,8 @@ SYMBOLS = [
     "hp_tonemap_tables", "hp_tonemap_create", "hp_tonemap_destroy", "hp_resize_yuv_hdr", "hp_letterbox_yuv_hdr", "hp_resize_rois_yuv_hdr",
     "hp_tonemap_convert_host", "hp_yuv_colours_hdr", "hp_overlay_set_transfer", "hp_overlay_draw_yuv_host_hdr", "hp_pipeline_set_tonemap",
     "hp_resize_rois_u8c3", "hp_resize_rois_yuv", "hp_yuv_roi_alignment", "hp_tile_plan", "hp_humans_to_frame", "hp_humans_merge", "hp_pipeline_set_tiling",
+    "hp_resize_oriented_u8c3", "hp_resize_oriented_yuv", "hp_resize_rois_oriented_u8c3", "hp_resize_rois_oriented_yuv", "hp_oriented_size",
+    "hp_orientation_from_exif", "hp_orient_roi", "hp_orient_u8c3_host", "hp_humans_orient", "hp_pipeline_set_orientation",
 ]
 
 

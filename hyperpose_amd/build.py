@@ -33,6 +33,10 @@ UNITS = [
     ("resize_rois.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # PQ / HLG 10-bit frames: the same resize arithmetic once more (the kernels' pixel path is integer; the flags are the front end's)
     ("resize_yuv_hdr.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # stored-turned / mirrored frames read upright: every feed's Taps behind a coordinate map, the same arithmetic and flags once more
+    ("resize_oriented.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # the host side of HP_ORIENT_*: the humans' fp32 formulas must not fuse (tests/orient_ref.py restates them)
+    ("orientation.cpp", ["-ffp-contract=off"]),
     # the tone-map tables, float64 without fused operations: tests/hdr_ref.py derives them a second time
     ("tonemap.cpp", ["-ffp-contract=off"]),
     # planner / map-back / merge of tiled inference: host doubles that tests/tiles_ref.py restates bit for bit

@@ -13,6 +13,8 @@
 // merges them (tiles.cpp).  The BGR and the hp_yuv_image submit have a tiled twin below; with tiling off nothing of this runs.
 // HDR input (hp_pipeline_set_tonemap): while set, the P010 / I010 frames of hp_pipeline_submit_yuv_images take the *_hdr twin of their resize call
 // (resize_yuv_hdr.hip); nothing else changes, and 8-bit frames of the same batch go the SDR way.
+// Upright input (hp_pipeline_set_orientation): while a non-zero code is set the submitted frames are STORED frames; every resize call above is replaced by
+// its oriented twin (resize_oriented.hip), and everything after it - letterbox, tiles, resume_ratio, the merge - sees the upright uw x uh frame.
 #include "hp_common.hpp"
 #include "yuv_formats.hpp"
 
@@ -58,6 +60,7 @@ struct hp_pipeline {
     std::vector<hp_human> slot_humans, cand, kept; // tiled collect: the parser's per-slot lists, one frame's candidates, its merged humans
     std::vector<int> slot_n;
     std::vector<int32_t> cand_region;
+    int orientation = HP_ORIENT_NONE; // non-zero: submitted frames are stored turned / mirrored, p.w / p.h and the regions are the upright frame's
     hp_tonemap* tonemap = nullptr; // set: 10-bit hp_yuv_image frames are PQ / HLG and are tone-mapped while they are resized
 
     // the tone-map of a frame, or null for the SDR path
@@ -183,6 +186,15 @@ int hp_pipeline_set_tonemap(hp_pipeline* pl, const hp_hdr_desc* d)
     return HP_OK;
 }
 
+int hp_pipeline_set_orientation(hp_pipeline* pl, int orientation)
+{
+    HP_REQUIRE(pl, HP_ERR_INVALID, "hp_pipeline_set_orientation: null pipeline");
+    HP_REQUIRE(orientation >= 0 && orientation <= 7, HP_ERR_INVALID, "hp_pipeline_set_orientation: orientation %d is no HP_ORIENT_* code (0 .. 7)", orientation);
+    HP_REQUIRE(pl->inflight == 0, HP_ERR_STATE, "hp_pipeline_set_orientation: %d batches are in flight, collect first", pl->inflight);
+    pl->orientation = orientation;
+    return HP_OK;
+}
+
 int hp_pipeline_submit(hp_pipeline* pl, const uint8_t* const* frames, const int* widths, const int* heights, int n)
 {
     HP_REQUIRE(pl && frames && widths && heights, HP_ERR_INVALID, "hp_pipeline_submit: null argument");
@@ -209,7 +221,8 @@ int hp_pipeline_submit(hp_pipeline* pl, const uint8_t* const* frames, const int*
         }
         // a frame that already has the network's size needs no geometry: cv::resize to the same size is a copy (src/tensorrt.cpp:446-451)
         // and non_scaling_resize at ratio 1 fills the whole target (src/data.cpp:53-69) -> H2D straight into the network's input slot
-        direct[i] = widths[i] == pl->in_w && heights[i] == pl->in_h;
+        // (a stored frame that is turned or mirrored always goes through the oriented kernel)
+        direct[i] = widths[i] == pl->in_w && heights[i] == pl->in_h && pl->orientation == HP_ORIENT_NONE;
         uint8_t* dst = direct[i] ? p.net.as<uint8_t>() + (size_t)i * net_frame : p.raw.as<uint8_t>() + off;
         // consecutive network-sized frames that are also consecutive in (pinned) host memory go in ONE copy
         int run = 1;
@@ -231,7 +244,11 @@ int hp_pipeline_submit(hp_pipeline* pl, const uint8_t* const* frames, const int*
             continue;
         uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * net_frame;
         const uint8_t* src = p.raw.as<uint8_t>() + offs[i];
-        if (pl->keep_ratio)
+        if (pl->orientation != HP_ORIENT_NONE) { // p.w / p.h hold the stored size until here, the upright size from here on
+            const int sw = p.w[i], sh = p.h[i];
+            HP_TRY(hp_oriented_size(pl->orientation, sw, sh, &p.w[i], &p.h[i]));
+            HP_TRY(hp_resize_oriented_u8c3(src, sw, sh, sw * 3, pl->orientation, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
+        } else if (pl->keep_ratio)
             HP_TRY(hp_letterbox_u8c3(src, p.w[i], p.h[i], p.w[i] * 3, dst, pl->in_w, pl->in_h, pl->in_w * 3, 0, 0, 0, p.s));
         else
             HP_TRY(hp_resize_u8c3(src, p.w[i], p.h[i], p.w[i] * 3, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
@@ -243,6 +260,8 @@ int hp_pipeline_submit_yuv(hp_pipeline* pl, int format, const uint8_t* const* fr
 {
     HP_REQUIRE(pl && frames && widths && heights, HP_ERR_INVALID, "hp_pipeline_submit_yuv: null argument");
     HP_REQUIRE(!pl->tiled, HP_ERR_STATE, "hp_pipeline_submit_yuv: not available in tiled mode, submit hp_yuv_image frames with hp_pipeline_submit_yuv_images");
+    HP_REQUIRE(pl->orientation == HP_ORIENT_NONE, HP_ERR_STATE,
+        "hp_pipeline_submit_yuv: not available while an orientation is set, submit hp_yuv_image frames with hp_pipeline_submit_yuv_images");
     HP_REQUIRE(format == HP_YUV_NV12 || format == HP_YUV_I420, HP_ERR_INVALID, "hp_pipeline_submit_yuv: unknown format %d", format);
     HP_REQUIRE(n >= 1 && n <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_submit_yuv: batch %d > max_batch %d", n, pl->max_batch);
     HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "hp_pipeline_submit_yuv: all %d pipes are busy, collect first", pl->n_pipes);
@@ -310,7 +329,10 @@ int hp_pipeline_submit_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, i
         uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * net_frame;
         p.w[i] = frames[i].width, p.h[i] = frames[i].height;
         const hp_tonemap* tm = pl->tonemap_for(dev[i]);
-        if (pl->keep_ratio)
+        if (pl->orientation != HP_ORIENT_NONE) {
+            HP_TRY(hp_oriented_size(pl->orientation, frames[i].width, frames[i].height, &p.w[i], &p.h[i]));
+            HP_TRY(hp_resize_oriented_yuv(&dev[i], tm, pl->orientation, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
+        } else if (pl->keep_ratio)
             HP_TRY(tm ? hp_letterbox_yuv_hdr(&dev[i], tm, dst, pl->in_w, pl->in_h, pl->in_w * 3, 0, 0, 0, p.s)
                       : hp_letterbox_yuv(&dev[i], dst, pl->in_w, pl->in_h, pl->in_w * 3, 0, 0, 0, p.s));
         else
@@ -421,7 +443,9 @@ int submit_tiled(hp_pipeline* pl, const uint8_t* const* frames, const int* width
         HP_REQUIRE(frames[i] && widths[i] > 0 && heights[i] > 0, HP_ERR_INVALID, "hp_pipeline_submit: frame %d is empty", i);
         HP_REQUIRE((size_t)widths[i] * heights[i] * 3 <= pl->max_frame_bytes, HP_ERR_CAPACITY, "hp_pipeline_submit: frame %d (%dx%d) exceeds max_frame_bytes %zu", i,
             widths[i], heights[i], pl->max_frame_bytes);
-        const int rc = hp_tile_plan(&pl->tiling, widths[i], heights[i], 1, 1, &p.roi[(size_t)i * R], R);
+        int uw = 0, uh = 0; // the tiles are planned on the upright frame
+        HP_TRY(hp_oriented_size(pl->orientation, widths[i], heights[i], &uw, &uh));
+        const int rc = hp_tile_plan(&pl->tiling, uw, uh, 1, 1, &p.roi[(size_t)i * R], R);
         if (rc < 0)
             return rc;
     }
@@ -435,12 +459,13 @@ int submit_tiled(hp_pipeline* pl, const uint8_t* const* frames, const int* width
             src = p.stage.as<uint8_t>() + off;
         }
         HP_HIP_TRY(hipMemcpyAsync(p.raw.as<uint8_t>() + off, src, bytes, hipMemcpyHostToDevice, p.s));
-        offs[i] = off, p.w[i] = widths[i], p.h[i] = heights[i];
+        offs[i] = off;
+        HP_TRY(hp_oriented_size(pl->orientation, widths[i], heights[i], &p.w[i], &p.h[i]));
         off += (bytes + 255) & ~(size_t)255;
     }
-    for (int i = 0; i < n; ++i)
-        HP_TRY(hp_resize_rois_u8c3(p.raw.as<uint8_t>() + offs[i], p.w[i], p.h[i], p.w[i] * 3, &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0,
-            p.net.as<uint8_t>() + (size_t)i * R * net_frame, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s));
+    for (int i = 0; i < n; ++i) // (orientation 0 forwards to hp_resize_rois_u8c3)
+        HP_TRY(hp_resize_rois_oriented_u8c3(p.raw.as<uint8_t>() + offs[i], widths[i], heights[i], widths[i] * 3, pl->orientation, &p.roi[(size_t)i * R], R,
+            pl->keep_ratio, 0, 0, 0, p.net.as<uint8_t>() + (size_t)i * R * net_frame, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s));
     HP_TRY(infer_and_parse(pl, p, n * R));
     p.regions = R;
     return HP_OK;
@@ -459,7 +484,11 @@ int submit_tiled_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, int n, 
             frames[i].width, frames[i].height, hp_yuv_packed_bytes(frames[i].format, frames[i].width, frames[i].height), pl->max_frame_bytes);
         int ax = 1, ay = 1;
         HP_TRY(hp_yuv_roi_alignment(frames[i].format, &ax, &ay));
-        const int rc = hp_tile_plan(&pl->tiling, frames[i].width, frames[i].height, ax, ay, &p.roi[(size_t)i * R], R);
+        int uw = 0, uh = 0; // the tiles are planned on the upright frame; behind a quarter turn its x axis is the stored y axis
+        HP_TRY(hp_oriented_size(pl->orientation, frames[i].width, frames[i].height, &uw, &uh));
+        if (pl->orientation & 1)
+            std::swap(ax, ay);
+        const int rc = hp_tile_plan(&pl->tiling, uw, uh, ax, ay, &p.roi[(size_t)i * R], R);
         if (rc < 0)
             return rc;
     }
@@ -469,11 +498,15 @@ int submit_tiled_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, int n, 
     else
         HP_TRY(upload_yuv_images(pl, p, frames, n, dev));
     for (int i = 0; i < n; ++i) {
-        p.w[i] = frames[i].width, p.h[i] = frames[i].height;
+        HP_TRY(hp_oriented_size(pl->orientation, frames[i].width, frames[i].height, &p.w[i], &p.h[i]));
         uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * R * net_frame;
         const hp_tonemap* tm = pl->tonemap_for(dev[i]);
-        HP_TRY(tm ? hp_resize_rois_yuv_hdr(&dev[i], tm, &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s)
-                  : hp_resize_rois_yuv(&dev[i], &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s));
+        if (pl->orientation != HP_ORIENT_NONE)
+            HP_TRY(hp_resize_rois_oriented_yuv(&dev[i], tm, pl->orientation, &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h,
+                pl->in_w * 3, net_frame, p.s));
+        else
+            HP_TRY(tm ? hp_resize_rois_yuv_hdr(&dev[i], tm, &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s)
+                      : hp_resize_rois_yuv(&dev[i], &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s));
     }
     HP_TRY(infer_and_parse(pl, p, n * R));
     p.regions = R;

@@ -1,0 +1,258 @@
+// resize_oriented.hip — hp_resize_oriented_* / hp_resize_rois_oriented_*: the fused resize of every feed (8-bit BGR, every SDR hp_yuv_image layout,
+// PQ / HLG 10-bit) reading a frame that is stored turned and / or mirrored (include/hp_hip.h, HP_ORIENT_*), so that the network sees it upright
+// without a rotation pass over the full-resolution surface.  The contract: the bytes written equal "convert the whole stored frame to 8-bit BGR by
+// the feed's own rule, orient it (hp_orient_u8c3_host), then hp_resize_u8c3 / hp_letterbox_u8c3 from uw x uh".  Nothing of the arithmetic is
+// restated: the kernels are resize_pixel() / resize_rois_body() over oriented_taps<Taps> (resize_oriented_device.hpp), which maps an upright
+// pixel to its stored one and lets the feed's Taps fetch it.  Mode, letterbox inner size and the region table are picked from the UPRIGHT size.
+//
+// Orientation 0 never reaches this unit's kernels: every call forwards to its un-oriented twin (same kernels, same bytes, same refusals).
+//
+// Kernels (256 threads, one thread = one output pixel):
+//     resize_oriented_{u8c3,planar8,packed8,word16,hdr}_kernel<COLS>   one frame per launch, both thread maps (resize_oriented_device.hpp)
+//     resize_rois_oriented_{u8c3,planar8,packed8,word16,hdr}_kernel    up to 16 upright regions per launch (resize_rois_body's map: lanes along rows)
+// The HDR kernels always stage the tone-map tables in LDS (resize_yuv_hdr.hip's default placement).
+//
+// Which thread map a per-frame call takes is decided by oriented_cols() below from the code alone; HP_ORIENT_MAP=rows|cols (read
+// at the first call) forces one for measurements (tools/orientation_bench.py; DESIGN.md 1.1 "Orientation" holds both columns).
+#include "resize_oriented_device.hpp"
+#include "resize_yuv_hdr_device.hpp"
+
+#include <cstdlib>
+
+namespace {
+
+using namespace hp_resize;
+
+template <bool COLS, class Taps> __device__ __forceinline__ void resize_oriented_body(const rz_geom& g, const Taps& t)
+{
+    int x, y;
+    oriented_pixel_of_thread<COLS>(x, y);
+    if (x >= g.dw || y >= g.dh)
+        return;
+    resize_pixel(g, t, x, y);
+}
+
+template <bool COLS> __global__ __launch_bounds__(256) void resize_oriented_u8c3_kernel(const rz_geom g, const oriented_taps<bgr_taps> t)
+{
+    resize_oriented_body<COLS>(g, t);
+}
+template <bool COLS> __global__ __launch_bounds__(256) void resize_oriented_planar8_kernel(const rz_geom g, const oriented_taps<yuv_taps<1, 1>> t)
+{
+    resize_oriented_body<COLS>(g, t);
+}
+template <bool COLS> __global__ __launch_bounds__(256) void resize_oriented_packed8_kernel(const rz_geom g, const oriented_taps<yuv_taps<1, 2>> t)
+{
+    resize_oriented_body<COLS>(g, t);
+}
+template <bool COLS> __global__ __launch_bounds__(256) void resize_oriented_word16_kernel(const rz_geom g, const oriented_taps<yuv_taps<2, 1>> t)
+{
+    resize_oriented_body<COLS>(g, t);
+}
+template <bool COLS> __global__ __launch_bounds__(256) void resize_oriented_hdr_kernel(const rz_geom g, oriented_taps<yuv_hdr_taps> t)
+{
+    __shared__ uint2 tables[hp_hdr::TABLE_BYTES / sizeof(uint2)];
+    stage_tables<true>(t.in, tables);
+    resize_oriented_body<COLS>(g, t);
+}
+
+__global__ __launch_bounds__(256) void resize_rois_oriented_u8c3_kernel(const roi_batch b, const oriented_taps<bgr_taps> t) { resize_rois_body(b, t); }
+__global__ __launch_bounds__(256) void resize_rois_oriented_planar8_kernel(const roi_batch b, const oriented_taps<yuv_taps<1, 1>> t) { resize_rois_body(b, t); }
+__global__ __launch_bounds__(256) void resize_rois_oriented_packed8_kernel(const roi_batch b, const oriented_taps<yuv_taps<1, 2>> t) { resize_rois_body(b, t); }
+__global__ __launch_bounds__(256) void resize_rois_oriented_word16_kernel(const roi_batch b, const oriented_taps<yuv_taps<2, 1>> t) { resize_rois_body(b, t); }
+__global__ __launch_bounds__(256) void resize_rois_oriented_hdr_kernel(const roi_batch b, oriented_taps<yuv_hdr_taps> t)
+{
+    __shared__ uint2 tables[hp_hdr::TABLE_BYTES / sizeof(uint2)];
+    stage_tables<true>(t.in, tables);
+    resize_rois_body(b, t);
+}
+
+// The thread map of a per-frame call, from the code alone (never from the data).  Measured on the MI355X for bgr, nv12, yuy2 and p010-hdr
+// (profiles/orientation_bench.json, DESIGN.md 1.1 "Orientation"; us per launch, rows / cols):
+//     a quarter turn   1280 x 720 -> 1440 x 2560 (device-bound)   55.1 / 39.0   78.2 / 32.7   78.2 / 44.3   82.9 / 40.5     COLS, by 1.4 - 2.4 x
+//                      letter-boxed into 432 x 368 (launch-bound)  4.10 / 3.70   5.16 / 3.71   5.17 / 4.40   5.67 / 4.77    COLS again
+//     half turn, mirror  -> 2560 x 1440                            20.4 / 71.9   22.3 / 92.0   26.4 / 94.6   33.9 / 97.9     ROWS, by 2.9 - 4.1 x
+// Shrinking and enlarging agree, so the geometry does not enter the rule: lanes run along whichever destination axis is the stored x axis.
+bool oriented_cols(int code)
+{
+    static const int forced = [] {
+        const char* e = getenv("HP_ORIENT_MAP");
+        return !e ? -1 : strcmp(e, "cols") == 0 ? 1 : strcmp(e, "rows") == 0 ? 0 : -1;
+    }();
+    if (forced >= 0)
+        return forced != 0;
+    return (code & 1) != 0;
+}
+
+template <class Taps> oriented_taps<Taps> orient(const Taps& in, int code, int sw, int sh)
+{
+    oriented_taps<Taps> t{ in, 0, 0, code };
+    oriented_origin(code, hp_roi{ 0, 0, sw, sh }, t.ox, t.oy);
+    return t;
+}
+
+#define HP_LAUNCH_ORIENTED(kernel, g, t, code, s)                                                           \
+    do {                                                                                                    \
+        const bool cols_ = oriented_cols(code);                                                             \
+        if (cols_)                                                                                          \
+            hipLaunchKernelGGL(kernel<true>, oriented_grid(g, true), dim3(256), 0, s, g, t);                \
+        else                                                                                                \
+            hipLaunchKernelGGL(kernel<false>, oriented_grid(g, false), dim3(256), 0, s, g, t);              \
+        HP_HIP_TRY(hipGetLastError());                                                                      \
+    } while (0)
+
+// the geometry of a per-frame call: the resize runs from the upright size
+int prepare_frame(int code, int sw, int sh, int keep_ratio, const int bg[3], uint8_t* dst, int dw, int dh, int dst_stride, rz_geom& g)
+{
+    int uw = 0, uh = 0;
+    HP_TRY(hp_oriented_size(code, sw, sh, &uw, &uh));
+    int iw = dw, ih = dh;
+    if (keep_ratio)
+        hp_letterbox_inner(uw, uh, dw, dh, &iw, &ih);
+    return rz_prepare(g, uw, uh, dst, dw, dh, dst_stride, iw, ih, bg);
+}
+
+// the region table of a rois call: checked and sorted as upright regions of the upright frame (for a turned frame the alignment pair is swapped,
+// which is the stored rectangle's alignment), then every entry's origin becomes the stored corner its walk starts from
+int prepare_oriented_rois(const char* who, const char* format, int code, int sw, int sh, int ax, int ay, const hp_roi* rois, int n, int keep_ratio,
+    uint8_t* dst, int dw, int dh, int dst_stride, size_t slot_stride, const int bg[3], roi_geom (&geom)[ROIS_MAX])
+{
+    int uw = 0, uh = 0;
+    HP_TRY(hp_oriented_size(code, sw, sh, &uw, &uh));
+    const bool turned = (code & 1) != 0;
+    HP_TRY(prepare_rois(who, format, uw, uh, turned ? ay : ax, turned ? ax : ay, rois, n, keep_ratio, dst, dw, dh, dst_stride, slot_stride, bg, geom));
+    for (int k = 0; k < n; ++k) {
+        const hp_roi upright{ geom[k].x, geom[k].y, geom[k].sw, geom[k].sh };
+        hp_roi stored;
+        HP_TRY(hp_orient_roi(&upright, code, sw, sh, &stored));
+        oriented_origin(code, stored, geom[k].x, geom[k].y);
+    }
+    return HP_OK;
+}
+
+#define HP_CHECK_ORIENTATION(who, code) \
+    HP_REQUIRE(hp_orient::valid(code), HP_ERR_INVALID, "%s: orientation %d is no HP_ORIENT_* code (0 .. 7)", who, code)
+
+} // namespace
+
+extern "C" {
+
+int hp_resize_oriented_u8c3(const uint8_t* dev_src, int sw, int sh, int src_stride, int orientation, int keep_ratio, int b, int g, int r,
+    uint8_t* dev_dst, int dw, int dh, int dst_stride, void* stream)
+{
+    HP_CHECK_ORIENTATION("hp_resize_oriented_u8c3", orientation);
+    if (orientation == HP_ORIENT_NONE)
+        return keep_ratio ? hp_letterbox_u8c3(dev_src, sw, sh, src_stride, dev_dst, dw, dh, dst_stride, b, g, r, stream)
+                          : hp_resize_u8c3(dev_src, sw, sh, src_stride, dev_dst, dw, dh, dst_stride, stream);
+    HP_REQUIRE(dev_src && sw > 0 && sh > 0, HP_ERR_INVALID, "hp_resize_oriented_u8c3: BGR: empty source");
+    HP_REQUIRE(src_stride >= sw * 3, HP_ERR_INVALID, "hp_resize_oriented_u8c3: BGR: row stride smaller than a row");
+    const int bg[3] = { b, g, r };
+    rz_geom geom;
+    HP_TRY(prepare_frame(orientation, sw, sh, keep_ratio, bg, dev_dst, dw, dh, dst_stride, geom));
+    const auto t = orient(bgr_taps{ dev_src, src_stride }, orientation, sw, sh);
+    HP_LAUNCH_ORIENTED(resize_oriented_u8c3_kernel, geom, t, orientation, (hipStream_t)stream);
+    return HP_OK;
+}
+
+int hp_resize_oriented_yuv(const hp_yuv_image* src, const hp_tonemap* tm, int orientation, int keep_ratio, int b, int g, int r, uint8_t* dev_dst,
+    int dw, int dh, int dst_stride, void* stream)
+{
+    const char* who = "hp_resize_oriented_yuv";
+    HP_CHECK_ORIENTATION(who, orientation);
+    if (orientation == HP_ORIENT_NONE) {
+        if (tm)
+            return keep_ratio ? hp_letterbox_yuv_hdr(src, tm, dev_dst, dw, dh, dst_stride, b, g, r, stream)
+                              : hp_resize_yuv_hdr(src, tm, dev_dst, dw, dh, dst_stride, stream);
+        return keep_ratio ? hp_letterbox_yuv(src, dev_dst, dw, dh, dst_stride, b, g, r, stream) : hp_resize_yuv(src, dev_dst, dw, dh, dst_stride, stream);
+    }
+    const int bg[3] = { b, g, r };
+    const hipStream_t s = (hipStream_t)stream;
+    rz_geom geom;
+    if (tm) {
+        yuv_hdr_taps in;
+        HP_TRY(prepare_hdr(who, src, tm, in)); // refuses an 8-bit layout by name
+        HP_TRY(prepare_frame(orientation, src->width, src->height, keep_ratio, bg, dev_dst, dw, dh, dst_stride, geom));
+        const auto t = orient(in, orientation, src->width, src->height);
+        HP_LAUNCH_ORIENTED(resize_oriented_hdr_kernel, geom, t, orientation, s);
+        return HP_OK;
+    }
+    HP_TRY(hp_yuv::validate(src, who));
+    const hp_yuv::layout& l = *hp_yuv::layout_of(src->format);
+    int32_t k[7];
+    HP_TRY(hp_yuv_coefficients(src->matrix, src->range, l.sample_bytes == 2 ? 10 : 8, k));
+    HP_TRY(prepare_frame(orientation, src->width, src->height, keep_ratio, bg, dev_dst, dw, dh, dst_stride, geom));
+    if (l.sample_bytes == 2) {
+        yuv_taps<2, 1> in;
+        fill_taps(in, *src, l, k);
+        const auto t = orient(in, orientation, src->width, src->height);
+        HP_LAUNCH_ORIENTED(resize_oriented_word16_kernel, geom, t, orientation, s);
+    } else if (l.planes == 1) {
+        yuv_taps<1, 2> in;
+        fill_taps(in, *src, l, k);
+        const auto t = orient(in, orientation, src->width, src->height);
+        HP_LAUNCH_ORIENTED(resize_oriented_packed8_kernel, geom, t, orientation, s);
+    } else {
+        yuv_taps<1, 1> in;
+        fill_taps(in, *src, l, k);
+        const auto t = orient(in, orientation, src->width, src->height);
+        HP_LAUNCH_ORIENTED(resize_oriented_planar8_kernel, geom, t, orientation, s);
+    }
+    return HP_OK;
+}
+
+int hp_resize_rois_oriented_u8c3(const uint8_t* dev_src, int sw, int sh, int src_stride, int orientation, const hp_roi* rois, int n, int keep_ratio,
+    int b, int g, int r, uint8_t* dev_dst, int dw, int dh, int dst_stride, size_t slot_stride, void* stream)
+{
+    const char* who = "hp_resize_rois_oriented_u8c3";
+    HP_CHECK_ORIENTATION(who, orientation);
+    if (orientation == HP_ORIENT_NONE)
+        return hp_resize_rois_u8c3(dev_src, sw, sh, src_stride, rois, n, keep_ratio, b, g, r, dev_dst, dw, dh, dst_stride, slot_stride, stream);
+    HP_REQUIRE(dev_src && sw > 0 && sh > 0, HP_ERR_INVALID, "%s: BGR: empty source", who);
+    HP_REQUIRE(src_stride >= sw * 3, HP_ERR_INVALID, "%s: BGR: row stride smaller than a row", who);
+    const int bg[3] = { b, g, r };
+    roi_geom geom[ROIS_MAX];
+    HP_TRY(prepare_oriented_rois(who, "BGR", orientation, sw, sh, 1, 1, rois, n, keep_ratio, dev_dst, dw, dh, dst_stride, slot_stride, bg, geom));
+    const oriented_taps<bgr_taps> t{ bgr_taps{ dev_src, src_stride }, 0, 0, orientation };
+    return launch_rois(resize_rois_oriented_u8c3_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, (hipStream_t)stream);
+}
+
+int hp_resize_rois_oriented_yuv(const hp_yuv_image* src, const hp_tonemap* tm, int orientation, const hp_roi* rois, int n, int keep_ratio, int b, int g,
+    int r, uint8_t* dev_dst, int dw, int dh, int dst_stride, size_t slot_stride, void* stream)
+{
+    const char* who = "hp_resize_rois_oriented_yuv";
+    HP_CHECK_ORIENTATION(who, orientation);
+    if (orientation == HP_ORIENT_NONE)
+        return tm ? hp_resize_rois_yuv_hdr(src, tm, rois, n, keep_ratio, b, g, r, dev_dst, dw, dh, dst_stride, slot_stride, stream)
+                  : hp_resize_rois_yuv(src, rois, n, keep_ratio, b, g, r, dev_dst, dw, dh, dst_stride, slot_stride, stream);
+    const int bg[3] = { b, g, r };
+    const hipStream_t s = (hipStream_t)stream;
+    roi_geom geom[ROIS_MAX];
+    yuv_hdr_taps hdr;
+    if (tm)
+        HP_TRY(prepare_hdr(who, src, tm, hdr));
+    else
+        HP_TRY(hp_yuv::validate(src, who));
+    const hp_yuv::layout& l = *hp_yuv::layout_of(src->format);
+    HP_TRY(prepare_oriented_rois(who, l.name, orientation, src->width, src->height, 1 << l.sx, 1 << l.sy, rois, n, keep_ratio, dev_dst, dw, dh, dst_stride,
+        slot_stride, bg, geom));
+    if (tm) {
+        const oriented_taps<yuv_hdr_taps> t{ hdr, 0, 0, orientation };
+        return launch_rois(resize_rois_oriented_hdr_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, s);
+    }
+    int32_t k[7];
+    HP_TRY(hp_yuv_coefficients(src->matrix, src->range, l.sample_bytes == 2 ? 10 : 8, k));
+    if (l.sample_bytes == 2) {
+        oriented_taps<yuv_taps<2, 1>> t{ {}, 0, 0, orientation };
+        fill_taps(t.in, *src, l, k);
+        return launch_rois(resize_rois_oriented_word16_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, s);
+    }
+    if (l.planes == 1) {
+        oriented_taps<yuv_taps<1, 2>> t{ {}, 0, 0, orientation };
+        fill_taps(t.in, *src, l, k);
+        return launch_rois(resize_rois_oriented_packed8_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, s);
+    }
+    oriented_taps<yuv_taps<1, 1>> t{ {}, 0, 0, orientation };
+    fill_taps(t.in, *src, l, k);
+    return launch_rois(resize_rois_oriented_planar8_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, s);
+}
+
+} // extern "C"

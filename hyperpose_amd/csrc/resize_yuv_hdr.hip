@@ -1,8 +1,8 @@
 // resize_yuv_hdr.hip — hp_resize_yuv_hdr / hp_letterbox_yuv_hdr / hp_resize_rois_yuv_hdr: a PQ or HLG 10-bit frame (P010 / I010, read where it
 // lies) straight to the network's 8-bit sRGB BGR input, tone-mapped as each tap is fetched.  The rule is csrc/tonemap.hpp's convert() - the one the
 // host twin (tonemap.cpp) runs - so the output equals "hp_tonemap_convert_host, then hp_resize_u8c3 / hp_letterbox_u8c3" byte for byte; the resize
-// arithmetic is resize_device.hpp's resize_pixel(), the addressing is yuv_taps<2, 1>'s, the region table is resize_rois_device.hpp's.  This file adds
-// the Taps type that ends in table reads instead of sat8, and the handle that owns the tables.
+// arithmetic is resize_device.hpp's resize_pixel(), the addressing is yuv_taps<2, 1>'s, the region table is resize_rois_device.hpp's.  The Taps type that
+// ends in table reads instead of sat8 is resize_yuv_hdr_device.hpp's; this file adds the kernels and the handle that owns the tables.
 //
 // Two kernels, each the shape of its SDR twin (one thread = one output pixel, 32 x 8 pixels per block of 256 threads; regions: blockIdx.z):
 //     resize_yuv_hdr_kernel        one frame per launch          (resize_yuv_word16_kernel)
@@ -18,8 +18,7 @@
 //              gather of 64 different addresses is served cache line by cache line
 // The default is LDS; HP_HDR_TABLES=global (read at the first call) selects the other for measurements (tools/yuv_kernel_bench.py; DESIGN.md 1.1
 // holds both figures).
-#include "resize_rois_device.hpp"
-#include "tonemap.hpp"
+#include "resize_yuv_hdr_device.hpp"
 
 #include <cstdlib>
 #include <memory>
@@ -28,39 +27,7 @@ namespace {
 
 using namespace hp_resize;
 
-struct yuv_hdr_taps : yuv_taps<2, 1> {
-    const uint16_t* lin; // A [1024]: device memory as launched; an LDS kernel points both at its block's copy
-    const uint8_t* out;  // O [4096]
-    int m[9];
-    int primaries;
-    __device__ __forceinline__ void load(int px, int py, int (&c)[3]) const
-    {
-        int Y, U, V;
-        fetch(px, py, Y, U, V);
-        hp_hdr::convert(Y, U, V, y_off, cy, cub, cug, cvg, cvr, lin, m, primaries != 0, out, c);
-    }
-    __device__ __forceinline__ yuv_hdr_taps at(int rx, int ry) const
-    {
-        yuv_hdr_taps t = *this;
-        static_cast<yuv_taps<2, 1>&>(t) = yuv_taps<2, 1>::at(rx, ry);
-        return t;
-    }
-};
-
-// the block's copy of the tables: all 256 threads take part (before any of them leaves), 8 bytes per thread and step
-template <bool LDS> __device__ __forceinline__ void stage_tables(yuv_hdr_taps& t, uint2* lds)
-{
-    if constexpr (LDS) {
-        const uint2* src = reinterpret_cast<const uint2*>(t.lin); // A, then O, in one allocation (hp_tonemap::dev)
-#pragma unroll
-        for (int i = 0; i < (int)(hp_hdr::TABLE_BYTES / sizeof(uint2) / 256); ++i)
-            lds[i * 256 + threadIdx.x] = src[i * 256 + threadIdx.x];
-        __syncthreads();
-        t.lin = reinterpret_cast<const uint16_t*>(lds);
-        t.out = reinterpret_cast<const uint8_t*>(lds) + hp_hdr::LIN_N * sizeof(uint16_t);
-    }
-}
-static_assert(hp_hdr::TABLE_BYTES % (sizeof(uint2) * 256) == 0, "stage_tables: a whole number of 8-byte steps per thread");
+// yuv_hdr_taps, stage_tables() and prepare_hdr(): resize_yuv_hdr_device.hpp, shared with the oriented kernels of resize_oriented.hip
 
 template <bool LDS> __global__ __launch_bounds__(256) void resize_yuv_hdr_kernel(const rz_geom g, yuv_hdr_taps t)
 {
@@ -86,21 +53,6 @@ bool tables_in_lds()
         return !(e && strcmp(e, "global") == 0);
     }();
     return lds;
-}
-
-// the checks every HDR call makes first, and the taps of the frame
-int prepare_hdr(const char* who, const hp_yuv_image* im, const hp_tonemap* tm, yuv_hdr_taps& t)
-{
-    HP_REQUIRE(tm, HP_ERR_INVALID, "%s: null hp_tonemap handle", who);
-    HP_TRY(hp_hdr::check_frame(im, who, true));
-    int32_t k[7];
-    HP_TRY(hp_yuv_coefficients(im->matrix, im->range, 10, k));
-    fill_taps(t, *im, *hp_yuv::layout_of(im->format), k);
-    t.lin = static_cast<const uint16_t*>(tm->dev);
-    t.out = static_cast<const uint8_t*>(tm->dev) + hp_hdr::LIN_N * sizeof(uint16_t);
-    memcpy(t.m, tm->m, sizeof(t.m));
-    t.primaries = tm->desc.to_bt709 != 0;
-    return HP_OK;
 }
 
 int launch_frame(const char* who, const hp_yuv_image* im, const hp_tonemap* tm, uint8_t* dst, int dw, int dh, int dst_stride, bool letterbox, const int bg[3],

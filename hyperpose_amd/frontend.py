@@ -248,6 +248,60 @@ def yuv_colours_hdr(matrix: str = "bt2020", range: str = "limited", transfer: st
     return out
 
 
+# ---- upright input: stored frames that are turned and / or mirrored (HP_ORIENT_* in include/hp_hip.h; DESIGN.md 1.1 "Orientation") -------------
+
+def oriented_size(orientation: int, sw: int, sh: int):
+    """``hp_oriented_size``: (uw, uh) of the upright frame of a stored ``sw`` x ``sh`` frame."""
+    uw, uh = C.c_int(), C.c_int()
+    check(lib().hp_oriented_size(int(orientation), int(sw), int(sh), C.byref(uw), C.byref(uh)))
+    return uw.value, uh.value
+
+
+def orientation_from_exif(exif: int) -> int:
+    """``hp_orientation_from_exif``: the HP_ORIENT_* code of EXIF orientation 1 .. 8."""
+    return check(lib().hp_orientation_from_exif(int(exif)))
+
+
+def orient_roi(roi, orientation: int, sw: int, sh: int):
+    """``hp_orient_roi``: the stored rectangle (x, y, w, h) an upright region covers."""
+    u, st = Roi(*[int(v) for v in roi]), Roi()
+    check(lib().hp_orient_roi(C.byref(u), int(orientation), int(sw), int(sh), C.byref(st)))
+    return st.x, st.y, st.w, st.h
+
+
+def orient_host(img: np.ndarray, orientation: int, dst_pitch: int = 0) -> np.ndarray:
+    """``hp_orient_u8c3_host``: the materialised upright frame of a stored [h, w, 3] uint8 BGR image (rows may be padded: a view of a wider
+    array), no device needed.  ``dst_pitch`` > 0 pads the result's rows by that many bytes (returned as a view of the padded array)."""
+    assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3 and img.strides[1:] == (3, 1)
+    sh, sw = img.shape[:2]
+    uw, uh = oriented_size(orientation, sw, sh)
+    out = np.full((uh, uw * 3 + int(dst_pitch)), 0xA5, np.uint8)
+    check(lib().hp_orient_u8c3_host(C.c_void_p(img.ctypes.data), sw, sh, img.strides[0], int(orientation), C.c_void_p(out.ctypes.data), out.strides[0]))
+    return out[:, :uw * 3].reshape(uh, uw, 3)
+
+
+def humans_orient(humans, orientation: int, to_stored: bool) -> np.ndarray:
+    """``hp_humans_orient`` on a copy: humans normalised to the upright frame -> to the stored frame (``to_stored``), or back."""
+    hs = _humans(humans).copy()
+    check(lib().hp_humans_orient(hs.ctypes.data_as(C.POINTER(Human)), len(hs), int(orientation), int(bool(to_stored))))
+    return hs
+
+
+def resize_oriented(src, dst_dev, dw: int, dh: int, orientation: int, keep_ratio: bool = False, bgcolor=(0, 0, 0), sw=None, sh=None, src_stride=None,
+                    dst_stride=None, stream=None, tonemap=None) -> None:
+    """``hp_resize_oriented_u8c3`` / ``hp_resize_oriented_yuv``: a STORED device frame - 8-bit BGR (``src`` a device buffer, with ``sw``, ``sh`` as
+    stored and optionally ``src_stride``) or a ``YuvImage`` with device planes (with ``tonemap`` a PQ / HLG frame) - read upright and resized
+    (letterboxed with ``bgcolor`` when ``keep_ratio``) to ``dw`` x ``dh``."""
+    s = C.c_void_p(stream) if stream else None
+    bg = [int(c) for c in bgcolor]
+    if isinstance(src, YuvImage):
+        check(lib().hp_resize_oriented_yuv(C.byref(src), tonemap.h if tonemap is not None else None, int(orientation), int(bool(keep_ratio)), bg[0], bg[1],
+                                           bg[2], as_ptr(dst_dev), int(dw), int(dh), int(dst_stride or dw * 3), s))
+    else:
+        check(lib().hp_resize_oriented_u8c3(as_ptr(src), int(sw), int(sh), int(src_stride or sw * 3), int(orientation), int(bool(keep_ratio)), bg[0], bg[1],
+                                            bg[2], as_ptr(dst_dev), int(dw), int(dh), int(dst_stride or dw * 3), s))
+
+
 # ---- regions and tiles: many regions of one frame per launch, the tile planner, the way back and the merge (include/hp_hip.h) -----------
 
 def _rois(rois):
@@ -263,7 +317,7 @@ def yuv_roi_alignment(fmt: str):
 
 
 def resize_rois(src, rois, dst_dev, dw: int, dh: int, keep_ratio: bool = False, bgcolor=(0, 0, 0), sw=None, sh=None, src_stride=None,
-                dst_stride=None, slot_stride=None, stream=None, tonemap=None) -> None:
+                dst_stride=None, slot_stride=None, stream=None, tonemap=None, orientation=None) -> None:
     """``hp_resize_rois_u8c3`` / ``hp_resize_rois_yuv``: the regions ``rois`` [(x, y, w, h)] of ONE device frame - 8-bit BGR (``src`` a device
     buffer, with ``sw``, ``sh`` and optionally ``src_stride``) or a ``YuvImage`` with device planes - to ``len(rois)`` slots of ``dst_dev``,
     slot i at byte ``i * slot_stride`` (default: slots back to back), each what ``resize`` / ``letterbox`` give on the cut-out region."""
@@ -272,6 +326,14 @@ def resize_rois(src, rois, dst_dev, dw: int, dh: int, keep_ratio: bool = False, 
     ss = C.c_size_t(int(slot_stride if slot_stride is not None else ds * dh))
     s = C.c_void_p(stream) if stream else None
     bg = [int(c) for c in bgcolor]
+    if orientation is not None:  # ``hp_resize_rois_oriented_*``: a stored frame (``sw`` x ``sh`` as stored), ``rois`` in UPRIGHT coordinates
+        if isinstance(src, YuvImage):
+            check(lib().hp_resize_rois_oriented_yuv(C.byref(src), tonemap.h if tonemap is not None else None, int(orientation), arr, n,
+                                                    int(bool(keep_ratio)), bg[0], bg[1], bg[2], as_ptr(dst_dev), int(dw), int(dh), ds, ss, s))
+        else:
+            check(lib().hp_resize_rois_oriented_u8c3(as_ptr(src), int(sw), int(sh), int(src_stride or sw * 3), int(orientation), arr, n,
+                                                     int(bool(keep_ratio)), bg[0], bg[1], bg[2], as_ptr(dst_dev), int(dw), int(dh), ds, ss, s))
+        return
     if isinstance(src, YuvImage) and tonemap is not None:  # a PQ / HLG P010 or I010 frame
         check(lib().hp_resize_rois_yuv_hdr(C.byref(src), tonemap.h, arr, n, int(bool(keep_ratio)), bg[0], bg[1], bg[2], as_ptr(dst_dev), int(dw), int(dh),
                                            ds, ss, s))

@@ -88,6 +88,13 @@ class Pipeline:
         d = frontend.hdr_desc(transfer, to_bt709, peak_nits, white_nits)
         check(lib().hp_pipeline_set_tonemap(self._h, C.byref(d)))
 
+    def set_orientation(self, orientation: int = 0) -> None:
+        """``hp_pipeline_set_orientation``: from now on the frames of ``submit`` and ``submit_yuv_images`` are STORED frames, turned and / or
+        mirrored as the HP_ORIENT_* code ``orientation`` (0 .. 7, ``frontend.orientation_from_exif``) says; they are read upright inside the resize
+        and ``collect`` returns humans normalised to the upright frame (``frontend.humans_orient`` takes them to the stored frame).  0 turns it
+        off.  Not while batches are in flight; ``submit_yuv`` is refused while an orientation is set."""
+        check(lib().hp_pipeline_set_orientation(self._h, int(orientation)))
+
     def submit(self, frames) -> None:
         """frames: list of [h, w, 3] uint8 BGR arrays (any sizes), at most max_batch."""
         frames = [np.ascontiguousarray(f, np.uint8) for f in frames]

@@ -265,6 +265,56 @@ int hp_resize_rois_yuv_hdr(const hp_yuv_image* src, const hp_tonemap* t, const h
 /* the whole-frame conversion in plain C++, no device: a P010 / I010 frame in HOST memory (any address, any stride that covers a row) -> 8-bit BGR HWC */
 int hp_tonemap_convert_host(const hp_yuv_image* host_frame, const hp_hdr_desc* d, uint8_t* bgr, int stride);
 
+/* ---- upright input: frames that are STORED turned and / or mirrored (the container's display matrix, EXIF orientation 1 .. 8, a ceiling camera) read
+ * upright inside the fused resize - no rotation pass over the full-resolution surface (hyperpose_amd/csrc/resize_oriented.hip, orientation.cpp;
+ * DESIGN.md 1.1 "Orientation").  The ONE definition:
+ *
+ * Orientation code HP_ORIENT_*, 0 .. 7:  code = q + 4 * m,  q = quarter turns CLOCKWISE that bring the stored picture upright (0, 1, 2, 3 = 0, 90,
+ * 180, 270 degrees),  m = 1 when the stored picture is mirrored left-right FIRST, before the turn.  With the stored frame S of sw x sh, the
+ * upright frame U is uw x uh = sw x sh for even q and sh x sw for odd q, and with S'(x, y) = S(m ? sw-1-x : x, y):
+ *     q = 0:  U(ux, uy) = S'(ux, uy)                 q = 1:  U(ux, uy) = S'(uy, sh-1-ux)
+ *     q = 2:  U(ux, uy) = S'(sw-1-ux, sh-1-uy)       q = 3:  U(ux, uy) = S'(sw-1-uy, ux)
+ * (numpy: np.rot90(S[:, ::-1] if m else S, k=-q)).  EXIF orientations 1 .. 8 are the codes { 0, 4, 2, 6, 7, 1, 5, 3 } (hp_orientation_from_exif).
+ *
+ * Contract of every feed (8-bit BGR, every SDR hp_yuv_image layout, PQ / HLG 10-bit with a tone-map): an oriented call writes, byte for byte, what
+ * the existing pipeline gives in three steps - 1. convert the whole stored frame to 8-bit BGR by that feed's own rule, 2. orient it by the map above
+ * (hp_orient_u8c3_host), 3. hp_resize_u8c3 (keep_ratio == 0) / hp_letterbox_u8c3 with (b, g, r) (keep_ratio != 0) from uw x uh.  The definition is in
+ * the BGR domain on purpose: a turned 4:2:2 frame is not a 4:2:2 frame, and chroma stays replicated over the luma pixels it covers in the STORED
+ * frame.  Mode (linear / 2 x 2 area / copy) and the letterbox inner size come from (uw, uh).
+ *
+ * The device calls only enqueue.  tm == NULL: an SDR frame; otherwise a P010 / I010 PQ / HLG frame ("HDR video in" above).  The region calls take
+ * regions in UPRIGHT coordinates; slot i equals the per-frame oriented result on the upright cut-out, and every other rule is hp_resize_rois_*'s
+ * (1 .. 64 regions, ceil(n / 16) launches, bytes outside a slot's dw * 3 x dh untouched).  The YUV alignment (hp_yuv_roi_alignment) applies to the
+ * STORED rectangle of a region (hp_orient_roi): for odd q an upright x, w must be multiples of ay and y, h of ax.  Orientation 0 forwards to the
+ * existing call: the same kernels, bytes and refusals.  HP_ERR_INVALID, with a message that names the argument, and nothing launched: an
+ * orientation outside 0 .. 7; whatever the un-oriented twin refuses; an 8-bit layout passed with a tone-map. */
+enum { HP_ORIENT_NONE = 0, HP_ORIENT_CW90 = 1, HP_ORIENT_180 = 2, HP_ORIENT_CW270 = 3,
+       HP_ORIENT_HFLIP = 4, HP_ORIENT_HFLIP_CW90 = 5, HP_ORIENT_HFLIP_180 = 6 /* = a vertical flip */, HP_ORIENT_HFLIP_CW270 = 7 /* = a transpose */ };
+int hp_resize_oriented_u8c3(const uint8_t* dev_src, int sw, int sh, int src_stride, int orientation, int keep_ratio, int b, int g, int r,
+                            uint8_t* dev_dst, int dw, int dh, int dst_stride, void* stream);
+int hp_resize_oriented_yuv(const hp_yuv_image* src /* device planes */, const hp_tonemap* tm /* NULL = SDR */, int orientation, int keep_ratio,
+                           int b, int g, int r, uint8_t* dev_dst, int dw, int dh, int dst_stride, void* stream);
+int hp_resize_rois_oriented_u8c3(const uint8_t* dev_src, int sw, int sh, int src_stride, int orientation, const hp_roi* rois /* host, upright */, int n,
+                                 int keep_ratio, int b, int g, int r, uint8_t* dev_dst, int dw, int dh, int dst_stride, size_t slot_stride, void* stream);
+int hp_resize_rois_oriented_yuv(const hp_yuv_image* src, const hp_tonemap* tm, int orientation, const hp_roi* rois, int n, int keep_ratio,
+                                int b, int g, int r, uint8_t* dev_dst, int dw, int dh, int dst_stride, size_t slot_stride, void* stream);
+/* Host only, plain C++, no device.  All return HP_OK or HP_ERR_INVALID (an orientation outside 0 .. 7, an empty frame, a null pointer, a stride
+ * smaller than a row, a region that is empty or not inside the upright frame). */
+int hp_oriented_size(int orientation, int sw, int sh, int* uw, int* uh);
+int hp_orientation_from_exif(int exif); /* the code (>= 0) of EXIF orientation 1 .. 8, or HP_ERR_INVALID */
+/* the stored rectangle that an upright region covers (same pixel count, w and h swapped for odd q) */
+int hp_orient_roi(const hp_roi* upright, int orientation, int sw, int sh, hp_roi* stored);
+/* the materialised upright BGR frame (uw x uh, rows dst_stride bytes apart; padding bytes are not written): the definition above, the reference of
+ * the tests and the fallback of a caller without a device */
+int hp_orient_u8c3_host(const uint8_t* src, int sw, int sh, int src_stride, int orientation, uint8_t* dst, int dst_stride);
+/* Humans between the two frames, in place, on NORMALISED coordinates (hp_overlay_draw_* paints into the stored frame): only parts with has_value are
+ * touched, scores stay, fp32 exactly as written.  to_stored != 0, upright (u, v) -> stored (x, y):
+ *     q = 0: (x', y') = (u, v)   q = 1: (v, 1.0f-u)   q = 2: (1.0f-u, 1.0f-v)   q = 3: (1.0f-v, u);   then x = m ? 1.0f-x' : x',  y = y'
+ * to_stored == 0 is the inverse, stored (x, y) -> upright (u, v):  x' = m ? 1.0f-x : x,  y' = y,  then
+ *     q = 0: (u, v) = (x', y')   q = 1: (1.0f-y', x')   q = 2: (1.0f-x', 1.0f-y')   q = 3: (y', 1.0f-x')
+ * 1.0f - (1.0f - t) rounds, so a round trip need not return the same float (it does for every t that is a multiple of 2^-24 in [0, 1]). */
+int hp_humans_orient(hp_human* humans, int n, int orientation, int to_stored);
+
 /* ---- writing back: the skeletons of a frame's humans painted into a DEVICE-resident frame, 8-bit BGR or any hp_yuv_image layout in the frame's
  * own colour space and bit depth (hyperpose_amd/csrc/overlay.hip) - the last stage of the reference's stream, draw_human + writer
  * (src/stream.cpp:114-147), for frames that never leave the device.  The picture is defined by exact integer rules, stated once in
@@ -656,6 +706,13 @@ int hp_pipeline_set_tiling(hp_pipeline* p, const hp_tiling* t);
  * of hp_pipeline_submit_yuv_images - host or device planes, tiled or not - goes through hp_resize_yuv_hdr / hp_letterbox_yuv_hdr / hp_resize_rois_yuv_hdr
  * with the tables of d; 8-bit frames of the same batch take the SDR path unchanged.  The pipeline owns its hp_tonemap. */
 int hp_pipeline_set_tonemap(hp_pipeline* p, const hp_hdr_desc* d);
+/* Upright input ("upright input" above); orientation 0 turns it off (the default), HP_ERR_STATE while batches are in flight, HP_ERR_INVALID outside
+ * 0 .. 7.  While a non-zero orientation is set, every frame of hp_pipeline_submit and hp_pipeline_submit_yuv_images - host or device planes, tiled or
+ * not, tone-mapped or not - is a STORED frame and goes through hp_resize_oriented_* / hp_resize_rois_oriented_*; tiles are planned on (uw, uh) with the
+ * alignment pair swapped for odd q; hp_pipeline_collect returns humans normalised to the UPRIGHT frame (hp_resume_ratio and the tile merge use
+ * (uw, uh); hp_humans_orient(.., to_stored = 1) takes them to the stored frame for hp_overlay_draw_*).  hp_pipeline_submit_yuv returns HP_ERR_STATE
+ * while a non-zero orientation is set, as it does in tiled mode. */
+int hp_pipeline_set_orientation(hp_pipeline* p, int orientation);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,12 @@ namespace dnn {
             hp_tonemap_destroy(m_tonemap);
             m_tonemap = nullptr;
         }
+        /// Addition: upright input (utility/data.hpp, orientation; hp_resize_oriented_*).  While a non-upright orientation is set, the frames of
+        /// inference(std::vector<cv::Mat>), inference(std::vector<yuv_frame>), both inference(frame, regions) and their calibrate() twins are
+        /// STORED frames and are read upright inside the resize: the maps equal those of the same call on the frames oriented first
+        /// (hp_orient_u8c3_host), bit for bit; regions are in UPRIGHT coordinates (plan them on oriented_size()).  The yuv420_frame overloads
+        /// throw std::logic_error while an orientation is set: pass yuv_frames.
+        void set_orientation(const orientation& o) { m_orientation = o.code(); }
         inline cv::Size input_size() noexcept { return m_inp_size; }
 
         /// src/tensorrt.cpp:436-461: every image is brought to the network's size (cv::resize, or non_scaling_resize when keep_ratio)
@@ -188,7 +194,7 @@ namespace dnn {
                 fatal(hp_last_error());
             retire_last_batch(); // (the engine is idle here: the previous call was synchronised before it returned)
             std::vector<uint8_t> scratch;
-            bool all_net_sized = true;
+            bool all_net_sized = m_orientation == HP_ORIENT_NONE;
             for (const cv::Mat& f : inputs) {
                 if (f.empty())
                     fatal("hyperpose::dnn::tensorrt::inference: empty image");
@@ -282,9 +288,9 @@ namespace dnn {
             if (hp_memcpy_h2d(m_dev_raw, src, bytes) != HP_OK)
                 fatal(hp_last_error());
             const std::vector<hp_roi> rois = to_rois(regions);
-            if (hp_resize_rois_u8c3(m_dev_raw, frame.cols, frame.rows, frame.cols * 3, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net,
-                    m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
-                != HP_OK)
+            if (hp_resize_rois_oriented_u8c3(m_dev_raw, frame.cols, frame.rows, frame.cols * 3, m_orientation, rois.data(), (int)rois.size(),
+                    m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
+                != HP_OK) // (orientation 0 forwards to hp_resize_rois_u8c3)
                 throw std::logic_error(hp_last_error());
             if (hp_engine_infer_u8(m_engine, m_dev_net, (int)rois.size(), 1, nullptr) != HP_OK)
                 fatal(hp_last_error());
@@ -308,10 +314,13 @@ namespace dnn {
             const hp_yuv_image im = yuv_image_on_device(frame, scratch);
             const std::vector<hp_roi> rois = to_rois(regions);
             const hp_tonemap* tm = tonemap_for(frame);
-            const int rc = tm ? hp_resize_rois_yuv_hdr(&im, tm, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width,
-                                    m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
-                              : hp_resize_rois_yuv(&im, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width,
-                                    m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine));
+            const int rc = m_orientation != HP_ORIENT_NONE
+                ? hp_resize_rois_oriented_yuv(&im, tm, m_orientation, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width,
+                      m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
+                : tm ? hp_resize_rois_yuv_hdr(&im, tm, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width,
+                           m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
+                     : hp_resize_rois_yuv(&im, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width,
+                           m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine));
             if (rc != HP_OK)
                 throw std::logic_error(hp_last_error());
             if (hp_engine_infer_u8(m_engine, m_dev_net, (int)rois.size(), 1, nullptr) != HP_OK)
@@ -444,7 +453,7 @@ namespace dnn {
         {
             const uint8_t* src = detail::mat_bytes(f, scratch);
             const size_t bytes = (size_t)f.cols * f.rows * 3;
-            if (f.cols == m_inp_size.width && f.rows == m_inp_size.height) { // resize to the same size is a copy
+            if (f.cols == m_inp_size.width && f.rows == m_inp_size.height && m_orientation == HP_ORIENT_NONE) { // resize to the same size is a copy
                 if (hp_memcpy_h2d(dst, src, bytes) != HP_OK)
                     fatal(hp_last_error());
                 return;
@@ -459,7 +468,10 @@ namespace dnn {
             }
             if (hp_memcpy_h2d(m_dev_raw, src, bytes) != HP_OK)
                 fatal(hp_last_error());
-            const int rc = m_keep_ratio
+            const int rc = m_orientation != HP_ORIENT_NONE
+                ? hp_resize_oriented_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, m_orientation, m_keep_ratio ? 1 : 0, 0, 0, 0, dst, m_inp_size.width,
+                      m_inp_size.height, m_inp_size.width * 3, hp_engine_stream(m_engine))
+                : m_keep_ratio
                 ? hp_letterbox_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, 0, 0, 0,
                       hp_engine_stream(m_engine))
                 : hp_resize_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3,
@@ -475,6 +487,8 @@ namespace dnn {
                 fatal("hyperpose::dnn::tensorrt: empty YUV frame");
             if (f.format != HP_YUV_NV12 && f.format != HP_YUV_I420)
                 throw std::logic_error("hyperpose: yuv420_frame::format must be HP_YUV_NV12 or HP_YUV_I420");
+            if (m_orientation != HP_ORIENT_NONE)
+                throw std::logic_error("hyperpose: yuv420_frames are not available while an orientation is set, pass yuv_frames");
             if (f.width % 2 || f.height % 2)
                 throw std::logic_error("hyperpose: YUV 4:2:0 frames need even width and height");
             const bool nv12 = f.format == HP_YUV_NV12;
@@ -517,7 +531,9 @@ namespace dnn {
             const int w = m_inp_size.width, h = m_inp_size.height;
             void* s = hp_engine_stream(m_engine);
             int rc;
-            if (const hp_tonemap* tm = tonemap_for(f))
+            if (m_orientation != HP_ORIENT_NONE)
+                rc = hp_resize_oriented_yuv(&im, tonemap_for(f), m_orientation, m_keep_ratio ? 1 : 0, 0, 0, 0, dst, w, h, w * 3, s);
+            else if (const hp_tonemap* tm = tonemap_for(f))
                 rc = m_keep_ratio ? hp_letterbox_yuv_hdr(&im, tm, dst, w, h, w * 3, 0, 0, 0, s) : hp_resize_yuv_hdr(&im, tm, dst, w, h, w * 3, s);
             else
                 rc = m_keep_ratio ? hp_letterbox_yuv(&im, dst, w, h, w * 3, 0, 0, 0, s) : hp_resize_yuv(&im, dst, w, h, w * 3, s);
@@ -648,6 +664,7 @@ namespace dnn {
         size_t m_raw_bytes = 0;
         uint8_t* m_dev_net = nullptr; // the batch at network size
         uint8_t* m_host_net = nullptr; // ... and its pinned staging copy on the host
+        int m_orientation = HP_ORIENT_NONE; // set_orientation: the HP_ORIENT_* code of the stored frames
         hp_tonemap* m_tonemap = nullptr; // set_tonemap: the tables of the HDR description in device memory
         std::shared_ptr<std::atomic<uint64_t>> m_calls; // bumped whenever the engine's output buffers are about to be overwritten
         std::weak_ptr<detail::device_batch> m_last;

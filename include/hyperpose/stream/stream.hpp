@@ -95,6 +95,10 @@ public:
         detail::hp_check(hp_pipeline_set_tonemap(m_pl, h ? &c : nullptr));
     }
 
+    // hp_pipeline_set_orientation: frames pushed from now on are STORED frames (utility/data.hpp, orientation) and pop() returns humans normalised to
+    // the upright frame.  Not while batches are in flight (std::runtime_error)
+    void set_orientation(const orientation& o) { detail::hp_check(hp_pipeline_set_orientation(m_pl, o.code())); }
+
     // one batch (<= max_batch_size frames, any sizes); throws when every pipe is busy
     void push(const std::vector<cv::Mat>& frames)
     {
@@ -268,6 +272,15 @@ public:
     /// are tone-mapped to SDR sRGB inside the fused resize; 8-bit frames are converted as before.  Like the tiling, not while batches are in flight.
     void set_tonemap(const hdr& h) { m_gpu.set_tonemap(&h); }
     void clear_tonemap() { m_gpu.set_tonemap(nullptr); }
+
+    /// Addition: upright input (utility/data.hpp, orientation; hp_pipeline_set_orientation): the frames the inputs deliver are STORED turned and / or
+    /// mirrored and are read upright inside the fused resize.  The sinks receive humans normalised to the UPRIGHT frame (to_stored takes them to the
+    /// frame as delivered); the drawing sinks paint them into the stored frame.  Like the tiling, not while batches are in flight.
+    void set_orientation(const orientation& o)
+    {
+        m_gpu.set_orientation(o);
+        m_orientation = o;
+    }
 
 private:
     struct item {
@@ -505,6 +518,8 @@ private:
     cv::Mat rendered(item& it)
     {
         cv::Mat img = it.frame;
+        if (!m_orientation.upright())
+            to_stored(it.poses, m_orientation); // the picture is the frame as it was delivered
         if (!m_use_original_resolution) {
             cv::Mat r;
             if (m_keep_ratio)
@@ -534,6 +549,7 @@ private:
     const bool m_use_original_resolution, m_keep_ratio;
     const size_t m_queue_max;
     hip_stream m_gpu;
+    orientation m_orientation; // set_orientation: how the delivered frames are stored
 
     std::mutex m_mu, m_mu_sinks; // (m_mu_sinks: the list of sink threads alone, never held together with a wait)
     std::condition_variable m_cv_in, m_cv_out, m_cv_space, m_cv_out_space, m_cv_jobs;

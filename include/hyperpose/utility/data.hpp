@@ -43,13 +43,45 @@ struct hdr {
     hp_hdr_desc c_form() const { return hp_hdr_desc{ transfer, to_bt709 ? 1 : 0, peak_nits, white_nits }; }
 };
 
+/// Addition: upright input (include/hp_hip.h, "upright input").  How a frame is STORED relative to the upright picture: `quarter_turns` clockwise
+/// quarter turns bring it upright (0 .. 3 = 0, 90, 180, 270 degrees - a container's `rotate` tag), after `mirrored` (left-right, first) is undone.
+/// What dnn::tensorrt::set_orientation, the stream's set_orientation, to_stored / to_upright and draw_humans take.
+struct orientation {
+    int quarter_turns = 0;
+    bool mirrored = false;
+    int code() const { return (quarter_turns & 3) + (mirrored ? 4 : 0); } // HP_ORIENT_*
+    static orientation from_code(int code) { return orientation{ code & 3, (code & 4) != 0 }; }
+    /// EXIF orientation 1 .. 8; std::invalid_argument otherwise
+    static orientation from_exif(int exif)
+    {
+        const int c = hp_orientation_from_exif(exif);
+        if (c < 0)
+            throw std::invalid_argument(hp_last_error());
+        return from_code(c);
+    }
+    bool upright() const { return code() == HP_ORIENT_NONE; }
+};
+
+/// hp_oriented_size: the upright size of a frame stored as `stored`
+inline cv::Size oriented_size(cv::Size stored, const orientation& o)
+{
+    int w = 0, h = 0;
+    if (hp_oriented_size(o.code(), stored.width, stored.height, &w, &h) != HP_OK)
+        throw std::invalid_argument(hp_last_error());
+    return cv::Size(w, h);
+}
+
 /// hp_tile_plan: the regions of a `size` frame, the whole frame first when t.with_full, then the tiles row-major.  `yuv_format`: the
 /// HP_YUV_* layout whose chroma alignment the tiles keep (-1: none, a BGR frame).  Throws std::invalid_argument on a plan the rules refuse.
-inline std::vector<cv::Rect> plan_tiles(cv::Size size, const tiling& t, int yuv_format = -1)
+/// With an orientation, `size` is the UPRIGHT size (oriented_size) and the tiles keep the alignment of their STORED rectangles: behind a quarter
+/// turn the pair is swapped.
+inline std::vector<cv::Rect> plan_tiles(cv::Size size, const tiling& t, int yuv_format = -1, const orientation& o = orientation{})
 {
     int ax = 1, ay = 1;
     if (yuv_format >= 0 && hp_yuv_roi_alignment(yuv_format, &ax, &ay) != HP_OK)
         throw std::invalid_argument(hp_last_error());
+    if (o.quarter_turns & 1)
+        std::swap(ax, ay);
     const hp_tiling c = t.c_form();
     hp_roi out[64];
     const int n = hp_tile_plan(&c, size.width, size.height, ax, ay, out, 64);

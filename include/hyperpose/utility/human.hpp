@@ -88,6 +88,28 @@ inline std::vector<human_t> merge_humans(const std::vector<human_t>& humans, con
     return r;
 }
 
+// ---- Addition: upright input (include/hp_hip.h, "upright input"; utility/data.hpp, orientation) ---------------------------------------------
+// to_stored / to_upright (hp_humans_orient): humans normalised to the upright frame <-> normalised to the frame as it is stored, `code` an
+// HP_ORIENT_* code.  draw_humans(.., orientation) paints into a stored frame through to_stored.  A round trip need not return the same float.
+namespace detail {
+    inline void humans_orient(std::vector<human_t>& humans, int code, bool to_stored)
+    {
+        std::vector<hp_human> c(humans.size());
+        for (size_t i = 0; i < humans.size(); ++i) {
+            c[i].score = humans[i].score;
+            for (int k = 0; k < COCO_N_PARTS; ++k)
+                c[i].parts[k] = hp_body_part{ humans[i].parts[k].has_value ? 1 : 0, humans[i].parts[k].x, humans[i].parts[k].y, humans[i].parts[k].score };
+        }
+        if (hp_humans_orient(c.data(), (int)c.size(), code, to_stored ? 1 : 0) != HP_OK)
+            throw std::invalid_argument(hp_last_error());
+        for (size_t i = 0; i < humans.size(); ++i)
+            for (int k = 0; k < COCO_N_PARTS; ++k)
+                humans[i].parts[k].x = c[i].parts[k].x, humans[i].parts[k].y = c[i].parts[k].y;
+    }
+} // namespace detail
+template <class Orientation> inline void to_stored(std::vector<human_t>& humans, const Orientation& o) { detail::humans_orient(humans, o.code(), true); }
+template <class Orientation> inline void to_upright(std::vector<human_t>& humans, const Orientation& o) { detail::humans_orient(humans, o.code(), false); }
+
 // ---- draw_human (reference include/hyperpose/utility/human.hpp:36-42, src/human.cpp:7-39, colours src/color.hpp:16-36, limb table
 // src/coco.hpp:32-51): limbs as lines, parts as filled circles, thickness = max(1, int(sqrt(bbox area in pixels)) / 32).
 // With OpenCV the drawing calls are the reference's (cv::line / cv::circle); without it (cv_min.hpp) a plain rasteriser draws the same

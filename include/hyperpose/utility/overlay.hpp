@@ -97,4 +97,24 @@ inline void draw_humans(const device_bgr& picture, const std::vector<human_t>& h
         picture.stride ? picture.stride : picture.width * 3, list.data(), (int)list.size(), opacity, thickness, stream));
 }
 
+/// Addition: upright input (utility/data.hpp, orientation).  `humans` are in the UPRIGHT frame's normalised coordinates - what an engine or a stream
+/// with set_orientation(o) returns - and the picture is the frame as it is STORED: the records go through to_stored, then the overload above.
+inline void draw_humans(yuv_frame& frame, std::vector<human_t> humans, const orientation& o, float opacity = 1, int thickness = 0, void* stream = nullptr)
+{
+    to_stored(humans, o);
+    draw_humans(frame, humans, opacity, thickness, stream);
+}
+inline void draw_humans(yuv_frame& frame, std::vector<human_t> humans, const orientation& o, const hdr& h, float opacity = 1, int thickness = 0,
+    void* stream = nullptr)
+{
+    to_stored(humans, o);
+    draw_humans(frame, humans, h, opacity, thickness, stream);
+}
+inline void draw_humans(const device_bgr& picture, std::vector<human_t> humans, const orientation& o, float opacity = 1, int thickness = 0,
+    void* stream = nullptr)
+{
+    to_stored(humans, o);
+    draw_humans(picture, humans, opacity, thickness, stream);
+}
+
 } // namespace hyperpose
