@@ -1,17 +1,27 @@
 // libstdcxx_sort.hpp — libstdc++'s std::sort (bits/stl_algo.h: __introsort_loop with median-of-three
 // __unguarded_partition_pivot down to 16 elements, heap sort (__partial_sort) when the depth limit 2 floor(log2 n) runs out, then
-// __final_insertion_sort) restated step by step on an INDEX array, for device code that has to reproduce the order in which the
-// reference's std::sort leaves EQUAL keys (the standard leaves it open; the reference's results are whatever this implementation
-// does: src/pose_proposal.cpp:224 sorts limb candidates by confidence and pops them from the back).  The sequence of
-// comparisons and moves is a pure function of the comparator's answers.  `comp(a, b)` compares the ELEMENTS with indices a and b
-// (the reference's comparator on the elements themselves).  Meant for one lane; v lives in LDS or registers.
+// __final_insertion_sort) restated step by step, for code that has to reproduce the order in which the reference's std::sort
+// leaves EQUAL keys (the standard leaves it open; the reference's results are whatever this implementation does:
+// src/pose_proposal.cpp:113 sorts a class's boxes and :224 the limb candidates by confidence and pops them from the back,
+// src/paf.cpp:249 sorts connection candidates).  The sequence of comparisons and moves is a pure function of the comparator's
+// answers.  This is the ONLY restatement: the PAF, PifPaf and PoseProposal parsers all call it, and tests/cpp/libstdcxx_sort.cpp
+// holds it to the real std::sort on the host (it is __host__ __device__ for that).
+//
+// `v` holds n elements of type T, sorted in place; `comp(a, b)` is the reference's comparator on two ELEMENTS.  Where the
+// reference sorts large structs the callers sort an array of indices instead (T = int, comp looks the keys up): the permutation is
+// the same.  Meant for one lane; v lives in LDS or registers.
+//
+// The explicit stack: libstdc++ recurses into the right part and loops on the left; here every partition pushes ONE continuation
+// (the left part) and lowers the depth by one, and a partition only happens at depth > 0.  Below a continuation of depth d at most
+// d more are pushed before the heap sort ends the descent, so with the initial entry at most 2 floor(log2 n) + 1 entries are live:
+// 61 for any int n.  The 64-entry stack cannot overflow; the `ok = false` branch is an unreachable guard.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace hp {
 
-template <class Comp>
-__device__ inline void libstdcxx_adjust_heap(int* v, int first, int hole, int len, int value, Comp comp)
+template <class T, class Comp>
+__host__ __device__ inline void libstdcxx_adjust_heap(T* v, int first, int hole, int len, T value, Comp comp)
 {
     // bits/stl_heap.h __adjust_heap(first, holeIndex, len, value, comp) followed by __push_heap
     const int top = hole;
@@ -37,9 +47,9 @@ __device__ inline void libstdcxx_adjust_heap(int* v, int first, int hole, int le
     v[first + hole] = value;
 }
 
-// returns false only if the explicit stack overflowed (cannot happen: its depth is bounded by the depth limit)
-template <class Comp>
-__device__ inline bool libstdcxx_sort(int* v, int n, Comp comp, bool* used_heap = nullptr)
+// returns false only if the explicit stack overflowed (cannot happen, see above); *used_heap is set when the heap sort ran
+template <class T, class Comp>
+__host__ __device__ inline bool libstdcxx_sort(T* v, int n, Comp comp, bool* used_heap = nullptr)
 {
     if (n <= 1)
         return true;
@@ -48,7 +58,7 @@ __device__ inline bool libstdcxx_sort(int* v, int n, Comp comp, bool* used_heap 
     while ((2 << lg) <= n)
         ++lg;
     auto swp = [&](int i, int j) {
-        const int t = v[i];
+        const T t = v[i];
         v[i] = v[j];
         v[j] = t;
     };
@@ -70,7 +80,7 @@ __device__ inline bool libstdcxx_sort(int* v, int n, Comp comp, bool* used_heap 
                 }
                 for (int l = last; l - first > 1;) {
                     --l;
-                    const int value = v[l]; // __pop_heap(first, l, l)
+                    const T value = v[l]; // __pop_heap(first, l, l)
                     v[l] = v[first];
                     libstdcxx_adjust_heap(v, first, 0, l - first, value, comp);
                 }
@@ -119,7 +129,7 @@ __device__ inline bool libstdcxx_sort(int* v, int n, Comp comp, bool* used_heap 
     // __final_insertion_sort: guarded insertion sort of the first 16, unguarded linear inserts for the rest
     const int head = n > 16 ? 16 : n;
     for (int i = 1; i < head; ++i) {
-        const int val = v[i];
+        const T val = v[i];
         if (comp(val, v[0])) {
             for (int k = i; k > 0; --k)
                 v[k] = v[k - 1];
@@ -134,7 +144,7 @@ __device__ inline bool libstdcxx_sort(int* v, int n, Comp comp, bool* used_heap 
         }
     }
     for (int i = head; i < n; ++i) {
-        const int val = v[i];
+        const T val = v[i];
         int k = i;
         while (k > 0 && comp(val, v[k - 1])) { // (k > 0 never decides after a completed introsort loop; kept as a guard)
             v[k] = v[k - 1];

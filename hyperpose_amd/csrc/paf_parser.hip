@@ -27,6 +27,7 @@
 // Every floating-point expression keeps the operand order and the (non-fused) rounding of the CPU
 // code it replaces; this translation unit is compiled with -ffp-contract=off.  See DESIGN.md.
 #include "hp_common.hpp"
+#include "libstdcxx_sort.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -354,158 +355,9 @@ struct cand_t {
     int seq; // a * n2 + b: generation order (tie-break for equal scores)
 };
 
-// libstdc++'s std::sort (bits/stl_algo.h: __introsort_loop with median-of-three __unguarded_partition_pivot down to 16 elements, then
-// __final_insertion_sort) restated on an index array, comparator std::greater<connection_candidate> = by score (src/paf.cpp:47-50).  The
-// standard leaves the order of equal elements open; the reference's results depend on this implementation's choice, so it is
-// reproduced step by step (the sequence of comparisons and swaps is a pure function of the scores).  When the depth limit
-// (2 * floor(log2 n)) is exhausted libstdc++ heap-sorts the range it is looking at (`std::__partial_sort(first, last, last)` =
-// __heap_select + __sort_heap: __make_heap, then __pop_heap down to one element, both through __adjust_heap / __push_heap); that is
-// restated too (`used_heap` reports that it ran).  Returns false only if the explicit stack overflowed (impossible: depth <= 2 log2 n).
-__device__ void libstdcxx_adjust_heap(int* v, const float* c, int first, int hole, int len, int value)
-{
-    // bits/stl_heap.h __adjust_heap(first, holeIndex, len, value, comp) followed by __push_heap; comp(a, b) = a.score > b.score
-    const int top = hole;
-    int child = hole;
-    while (child < (len - 1) / 2) {
-        child = 2 * (child + 1);
-        if (c[v[first + child]] > c[v[first + child - 1]])
-            --child;
-        v[first + hole] = v[first + child];
-        hole = child;
-    }
-    if ((len & 1) == 0 && child == (len - 2) / 2) {
-        child = 2 * (child + 1);
-        v[first + hole] = v[first + child - 1];
-        hole = child - 1;
-    }
-    int parent = (hole - 1) / 2;
-    while (hole > top && c[v[first + parent]] > c[value]) {
-        v[first + hole] = v[first + parent];
-        hole = parent;
-        parent = (hole - 1) / 2;
-    }
-    v[first + hole] = value;
-}
-
-__device__ void libstdcxx_heap_sort_greater(int* v, const float* c, int first, int last)
-{
-    const int len = last - first;
-    if (len >= 2) // __make_heap
-        for (int parent = (len - 2) / 2;; --parent) {
-            libstdcxx_adjust_heap(v, c, first, parent, len, v[first + parent]);
-            if (parent == 0)
-                break;
-        }
-    // __heap_select's scan over [middle, last) is empty (middle == last); __sort_heap:
-    for (int l = last; l - first > 1;) {
-        --l;
-        const int value = v[l]; // __pop_heap(first, l, l)
-        v[l] = v[first];
-        libstdcxx_adjust_heap(v, c, first, 0, l - first, value);
-    }
-}
-
-__device__ bool libstdcxx_sort_greater(int* v, int n, const float* c, bool* used_heap = nullptr)
-{
-#define HP_GT(i, j) (c[v[i]] > c[v[j]])
-#define HP_SWAP(i, j)                                                                                             \
-    {                                                                                                             \
-        const int t_ = v[i];                                                                                      \
-        v[i] = v[j];                                                                                              \
-        v[j] = t_;                                                                                                \
-    }
-    if (n <= 1)
-        return true;
-    bool ok = true;
-    int lg = 0;
-    while ((2 << lg) <= n)
-        ++lg;
-    // __introsort_loop(first, last, depth): `while (last - first > 16) { ...; __introsort_loop(cut, last, depth); last = cut; }` with
-    // the recursion on the RIGHT part first: an explicit stack of (first, last, depth) reproduces the same sequence of partitions
-    int stk_f[64], stk_l[64], stk_d[64], sp = 0;
-    stk_f[0] = 0, stk_l[0] = n, stk_d[0] = 2 * lg, sp = 1;
-    while (sp > 0) {
-        --sp;
-        int first = stk_f[sp], last = stk_l[sp], depth = stk_d[sp];
-        // iterative form of the loop: every partition pushes the LEFT remainder to be continued after the right recursion returns
-        while (last - first > 16) {
-            if (depth == 0) {
-                libstdcxx_heap_sort_greater(v, c, first, last);
-                if (used_heap)
-                    *used_heap = true;
-                break;
-            }
-            --depth;
-            const int mid = first + (last - first) / 2;
-            { // __move_median_to_first(result = first, a = first + 1, b = mid, c = last - 1)
-                const int a = first + 1, b = mid, cc = last - 1;
-                if (HP_GT(a, b)) {
-                    if (HP_GT(b, cc))
-                        HP_SWAP(first, b)
-                    else if (HP_GT(a, cc))
-                        HP_SWAP(first, cc)
-                    else
-                        HP_SWAP(first, a)
-                } else if (HP_GT(a, cc))
-                    HP_SWAP(first, a)
-                else if (HP_GT(b, cc))
-                    HP_SWAP(first, cc)
-                else
-                    HP_SWAP(first, b)
-            }
-            int lo = first + 1, hi = last; // __unguarded_partition(first + 1, last, pivot = first)
-            for (;;) {
-                while (HP_GT(lo, first))
-                    ++lo;
-                --hi;
-                while (HP_GT(first, hi))
-                    --hi;
-                if (!(lo < hi))
-                    break;
-                HP_SWAP(lo, hi)
-                ++lo;
-            }
-            const int cut = lo;
-            // recursion on [cut, last) happens NOW in libstdc++, the loop then continues with [first, cut): push the continuation
-            // first (it is popped after the right part and everything below it is done), then descend into the right part
-            if (sp < 63) {
-                stk_f[sp] = first, stk_l[sp] = cut, stk_d[sp] = depth, ++sp;
-            } else
-                ok = false;
-            first = cut;
-        }
-    }
-    // __final_insertion_sort: guarded insertion sort of the first 16, unguarded linear inserts for the rest
-    const int head = n > 16 ? 16 : n;
-    for (int i = 1; i < head; ++i) {
-        const int val = v[i];
-        if (c[val] > c[v[0]]) {
-            for (int k = i; k > 0; --k)
-                v[k] = v[k - 1];
-            v[0] = val;
-        } else {
-            int k = i;
-            while (c[val] > c[v[k - 1]]) {
-                v[k] = v[k - 1];
-                --k;
-            }
-            v[k] = val;
-        }
-    }
-    for (int i = head; i < n; ++i) {
-        const int val = v[i];
-        int k = i;
-        while (k > 0 && c[val] > c[v[k - 1]]) { // (k > 0 never decides after a completed introsort loop; kept as a guard)
-            v[k] = v[k - 1];
-            --k;
-        }
-        v[k] = val;
-    }
-#undef HP_GT
-#undef HP_SWAP
-    return ok;
-}
-
+// std::sort(..., std::greater<connection_candidate>) = by score (src/paf.cpp:47-50, :249) leaves equal scores in the order of
+// libstdc++'s algorithm; hp::libstdcxx_sort (libstdcxx_sort.hpp) restates it on the index array.
+//
 // hp_paf_debug_sort: the restated std::sort alone, on an arbitrary score sequence in generation order (tests: median-of-three
 // killers that drive libstdc++ into its heap-sort fallback, mass ties) - compared with the host's real std::sort.
 __global__ void paf_debug_sort_kernel(const float* __restrict__ scores, int n, cand_t* __restrict__ cand, int* __restrict__ order,
@@ -520,7 +372,7 @@ __global__ void paf_debug_sort_kernel(const float* __restrict__ scores, int n, c
     __syncthreads();
     if (threadIdx.x == 0) {
         bool heap = false;
-        const bool ok = libstdcxx_sort_greater(order, n, scores, &heap);
+        const bool ok = hp::libstdcxx_sort(order, n, [scores](int a, int b) { return scores[a] > scores[b]; }, &heap);
         *flag = (heap ? 1 : 0) | (ok ? 0 : 2);
     }
 }
@@ -841,7 +693,8 @@ __global__ __launch_bounds__(LIMB_THREADS) void paf_connect_kernel(const cand_t*
             s_order[rank] = i;
         }
         __syncthreads();
-        if (tid == 0 && !libstdcxx_sort_greater(s_order, n, s_score))
+        const float* const sc = s_score;
+        if (tid == 0 && !hp::libstdcxx_sort(s_order, n, [sc](int a, int b) { return sc[a] > sc[b]; }))
             atomicOr(flags + f, 8); // (unreachable: the explicit stack of the restated introsort cannot overflow)
         __syncthreads();
     }

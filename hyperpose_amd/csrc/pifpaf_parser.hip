@@ -26,6 +26,7 @@
 //
 // Compiled with -ffp-contract=off; every float/double expression keeps the reference's types and operand order.
 #include "hp_common.hpp"
+#include "libstdcxx_sort.hpp"
 
 #include <algorithm>
 #include <array>
@@ -849,7 +850,7 @@ __device__ __forceinline__ void pd_heap_push(pd_heap& h, int lane, float vk, int
 __device__ __forceinline__ void pd_heap_pop(pd_heap& h, int lane) // pop_heap + pop_back
 {
     if (h.n > 1) {
-        const float vk = rl_f(h.k, h.n - 1); // __pop_heap: value = *result; *result = *first; __adjust_heap(first, 0, len, value)
+        const float vk = rl_f(h.k, h.n - 1); // __pop_heap: value = *result; *result = *first; then the hole sifts down from the root (bits/stl_heap.h)
         const int vid = rl_i(h.id, h.n - 1);
         const int len = h.n - 1;
         int hole = 0, second = 0;
@@ -874,97 +875,6 @@ __device__ __forceinline__ void pd_heap_pop(pd_heap& h, int lane) // pop_heap + 
         pd_push_heap(h, lane, hole, vk, vid);
     }
     --h.n;
-}
-
-// ---- std::sort on an index array, keys DESCENDING (comp(a, b) = key[a] > key[b]): libstdc++'s introsort + final insertion sort, as in
-// paf_parser.hip::libstdcxx_sort_greater.  Returns false when the depth limit ran out (heap-sort fall-back not restated).
-__device__ bool pd_sort_desc(int* v, int n, const float* key)
-{
-#define PD_GT(i, j) (key[v[i]] > key[v[j]])
-#define PD_SWAP(i, j)                                                                                             \
-    {                                                                                                             \
-        const int t_ = v[i];                                                                                      \
-        v[i] = v[j];                                                                                              \
-        v[j] = t_;                                                                                                \
-    }
-    if (n <= 1)
-        return true;
-    bool ok = true;
-    int lg = 0;
-    while ((2 << lg) <= n)
-        ++lg;
-    int stk_f[48], stk_l[48], stk_d[48], sp = 0;
-    stk_f[0] = 0, stk_l[0] = n, stk_d[0] = 2 * lg, sp = 1;
-    while (sp > 0) {
-        --sp;
-        int first = stk_f[sp], last = stk_l[sp], depth = stk_d[sp];
-        while (last - first > 16) {
-            if (depth == 0) {
-                ok = false;
-                break;
-            }
-            --depth;
-            const int mid = first + (last - first) / 2, a = first + 1, b = mid, c = last - 1;
-            if (PD_GT(a, b)) {
-                if (PD_GT(b, c))
-                    PD_SWAP(first, b)
-                else if (PD_GT(a, c))
-                    PD_SWAP(first, c)
-                else
-                    PD_SWAP(first, a)
-            } else if (PD_GT(a, c))
-                PD_SWAP(first, a)
-            else if (PD_GT(b, c))
-                PD_SWAP(first, c)
-            else
-                PD_SWAP(first, b)
-            int lo = first + 1, hi = last;
-            for (;;) {
-                while (PD_GT(lo, first))
-                    ++lo;
-                --hi;
-                while (PD_GT(first, hi))
-                    --hi;
-                if (!(lo < hi))
-                    break;
-                PD_SWAP(lo, hi)
-                ++lo;
-            }
-            if (sp < 47)
-                stk_f[sp] = first, stk_l[sp] = lo, stk_d[sp] = depth, ++sp;
-            else
-                ok = false;
-            first = lo;
-        }
-    }
-    const int head = n > 16 ? 16 : n;
-    for (int i = 1; i < head; ++i) {
-        const int val = v[i];
-        if (key[val] > key[v[0]]) {
-            for (int k = i; k > 0; --k)
-                v[k] = v[k - 1];
-            v[0] = val;
-        } else {
-            int k = i;
-            while (key[val] > key[v[k - 1]]) {
-                v[k] = v[k - 1];
-                --k;
-            }
-            v[k] = val;
-        }
-    }
-    for (int i = head; i < n; ++i) {
-        const int val = v[i];
-        int k = i;
-        while (k > 0 && key[val] > key[v[k - 1]]) {
-            v[k] = v[k - 1];
-            --k;
-        }
-        v[k] = val;
-    }
-#undef PD_GT
-#undef PD_SWAP
-    return ok;
 }
 
 struct pd_xysv {
@@ -1407,8 +1317,11 @@ __global__ __launch_bounds__(64) void pp_decode_kernel(pd_params P, const int* _
             s_idx[a] = a;
         }
         __syncthreads();
-        if (lane == 0 && !pd_sort_desc(s_idx, na, s_key))
-            dflags[fr] = 4; // (merged with `flags` below)
+        // std::sort by score descending (the host tail's std::sort calls): libstdc++'s order of equal scores, heap fall-back included
+        const float* const key = s_key;
+        auto by_score_desc = [key](int a, int b) { return key[a] > key[b]; };
+        if (lane == 0 && !hp::libstdcxx_sort(s_idx, na, by_score_desc))
+            dflags[fr] = 4; // (unreachable: the restated introsort's stack cannot overflow; merged with `flags` below)
         __syncthreads();
         for (int oi = 0; oi < na; ++oi) {
             pd_ann& ann = A[s_idx[oi]];
@@ -1451,7 +1364,7 @@ __global__ __launch_bounds__(64) void pp_decode_kernel(pd_params P, const int* _
             }
         }
         __syncthreads();
-        if (lane == 0 && !pd_sort_desc(s_idx, nkept, s_key))
+        if (lane == 0 && !hp::libstdcxx_sort(s_idx, nkept, by_score_desc))
             dflags[fr] = 4;
         __syncthreads();
     }

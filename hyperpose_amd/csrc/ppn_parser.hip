@@ -131,16 +131,8 @@ __global__ __launch_bounds__(256) void ppn_extract_kernel(const float* __restric
         const int i = tid >> 3;
         ppn_box* arr = s_box(i);
         int m = s_cnt[i];
-        // std::sort ascending by conf (stable insertion sort: equal confidences keep cell order)
-        for (int a = 1; a < m; ++a) {
-            const ppn_box key = arr[a];
-            int q = a - 1;
-            while (q >= 0 && key.conf < arr[q].conf) {
-                arr[q + 1] = arr[q];
-                --q;
-            }
-            arr[q + 1] = key;
-        }
+        // std::sort ascending by conf (:113-115), in place: beyond 16 boxes equal confidences come out in libstdc++'s order, not cell order
+        hp::libstdcxx_sort(arr, m, [](const ppn_box& l, const ppn_box& r) { return l.conf < r.conf; });
         int ns = 0;
         while (m > 0) {
             const ppn_box cur = arr[m - 1];

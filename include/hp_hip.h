@@ -400,9 +400,10 @@ int hp_paf_debug_conns(hp_paf* p, int frame, hp_conn* out, int cap, int* n);
 /* The up-sampled (resize_area) and the smoothed (GaussianBlur) confidence maps [J,res_h,res_w] of ONE frame,
  * host pointers, either output may be NULL (tests only; the production kernels never materialise them). */
 int hp_paf_debug_maps(hp_paf* p, const float* host_conf, const int conf_shape[3], float* host_up, float* host_smoothed);
-/* The device's restatement of libstdc++'s std::sort(first, last, std::greater<connection_candidate>) (src/paf.cpp:249: the order of
- * equal scores is whatever that algorithm leaves) on n scores given in generation order; host_order[i] = index of the element
- * that ends at position i; *used_heap = 1 when the introsort depth limit was hit and the heap-sort fall-back ran (tests only). */
+/* The restatement of libstdc++'s std::sort that all three parsers share (csrc/libstdcxx_sort.hpp), run on the device as
+ * std::sort(first, last, std::greater<connection_candidate>) (src/paf.cpp:249: the order of equal scores is whatever that algorithm
+ * leaves) on n scores given in generation order; host_order[i] = index of the element that ends at position i; *used_heap = 1
+ * when the introsort depth limit was hit and the heap-sort fall-back ran (tests only). */
 int hp_paf_debug_sort(const float* host_scores, int n, int* host_order, int* used_heap);
 
 /* ---- hyperpose::parser::pose_proposal (include/hyperpose/operator/parser/proposal_network.hpp:17-81,
@@ -448,8 +449,10 @@ void* hp_pifpaf_stream(hp_pifpaf* p);
 int hp_pifpaf_enqueue(hp_pifpaf* p, int n, const float* dev_paf, const float* dev_pif, int fh, int fw, void* stream);
 int hp_pifpaf_collect(hp_pifpaf* p, hp_human* out, int cap_per_frame, int* n_out);
 /* Per frame of the last collected batch: 0 = decoded on the device, -1 = host tail by configuration, > 0 = why the device decoder
- * handed the frame to the host tail (1 annotations > 256, 2 soft-NMS extent, 4 sort depth, 8 seeds, 16 frontier / more than 256 list
- * entries inside one search box, 32 rounding, 64 declined by the HP_PIFPAF_DECLINE_ODD test hook). */
+ * handed the frame to the host tail (1 annotations > 256, 2 soft-NMS extent, 8 seeds, 16 frontier / more than 256 list entries inside
+ * one search box, 32 rounding, 64 declined by the HP_PIFPAF_DECLINE_ODD test hook; 4 is no longer produced: it meant that the sort of
+ * the annotation scores ran out of introsort depth, which the device now heap-sorts as libstdc++ does, and remains only as the guard
+ * for a stack overflow that cannot happen). */
 int hp_pifpaf_decode_flags(const hp_pifpaf* p, int* flags, int n);
 
 /* ---- hyperpose::dnn engine: replaces dnn::tensorrt (include/hyperpose/operator/dnn/tensorrt.hpp:33-141,

@@ -143,3 +143,50 @@ def test_gpu_async_enqueue_collect(hp):
             assert _same(got[b], loader.ref_ppn_process([a[b] for a in t])), (salt, b)
     with pytest.raises(Exception):
         p.collect()  # nothing in flight
+
+
+def _nms_tie_batches():
+    """Six batches of 4 frames (12 x 12 grid) whose key-point confidences are rounded to eighths: 33 - 81 boxes per class on 8 levels."""
+    for salt in (901, 902, 903):
+        for spurious in (0.1, 0.25):
+            t = [np.ascontiguousarray(a) for a in synth.ppn_maps(synth.rng_for(3, salt=salt), 4, people=(14, 6, 3, 9), spurious=spurious)]
+            t[0] = (np.round(t[0] * 8) / 8).astype(np.float32)
+            yield (salt, spurious), t
+
+
+@pytest.mark.gpu
+def test_gpu_nms_ties_beyond_sixteen_boxes(hp, monkeypatch):
+    """Equal box confidences among MORE THAN 16 boxes of a class: the reference's NMS sorts them with std::sort (src/pose_proposal.cpp:113),
+    which beyond its 16-element insertion-sort regime does not leave equals in cell order, and which boxes survive - hence the humans -
+    depends on that order.  The extract kernel sorts the boxes with the shared restatement (csrc/libstdcxx_sort.hpp); it used to sort them
+    stably.  24 frames: each equals the reference's own code byte for byte, assembled on the device, and the host statements
+    (HP_PPN_HOST_TAIL=1) give the same bytes.  So that the test cannot go blind it also shows, with the reference alone, that the frames ARE
+    order-sensitive: confidences multiplied by (1 + 2e-7 * cell) in float32 turn every tie into cell order - what a stable sort leaves - and
+    at least 8 of the 24 frames must then return other skeletons (has_value, x or y of some part, or the number of humans)."""
+    from hyperpose_amd.parser import PoseProposal
+    if not loader.have_ref():
+        pytest.skip("oracle/_ref not built")
+    B, args = 4, (384, 384, 0.10, 0.05, 0.3)
+    p = PoseProposal((384, 384), *args[2:], max_batch=B, cap_per_frame=256)
+    monkeypatch.setenv("HP_PPN_HOST_TAIL", "1")
+    q = PoseProposal((384, 384), *args[2:], max_batch=B, cap_per_frame=256)
+    monkeypatch.delenv("HP_PPN_HOST_TAIL")
+    sensitive = frames = 0
+    for case, t in _nms_tie_batches():
+        per_class = (t[0] > args[2]).reshape(B, t[0].shape[1], -1).sum(-1)
+        assert per_class.max() > 16, (case, per_class.max())
+        cell = np.arange(t[0].shape[2] * t[0].shape[3], dtype=np.float32).reshape(t[0].shape[2:])
+        stable = (t[0] * (np.float32(1) + np.float32(2e-7) * cell)).astype(np.float32)
+        got = p.process_batch(t)
+        assert (p.decode_flags(B) == 0).all(), (case, p.decode_flags(B))
+        host = q.process_batch(t)
+        assert (q.decode_flags(B) == -1).all()
+        for b in range(B):
+            ref = loader.ref_ppn_process([a[b] for a in t], *args, cap=256)
+            assert _same(got[b], ref), f"{case} frame {b}: {len(got[b])} vs {len(ref)} humans"
+            assert _same(host[b], ref), (case, b)
+            other = loader.ref_ppn_process([stable[b]] + [a[b] for a in t[1:]], *args, cap=256)
+            sensitive += len(other) != len(ref) or any(
+                not np.array_equal(other["parts"][k], ref["parts"][k]) for k in ("has_value", "x", "y"))
+            frames += 1
+    assert frames == 24 and sensitive >= 8, sensitive
