@@ -20,6 +20,9 @@
 //   * tiled inference (addition): `--tiles=<columns>x<rows> [--tile_overlap=<px>] [--tile_full]`: every frame - BGR or --yuv / .yuv, with or
 //     without --saving_yuv - is inferred on overlapping tiles (one engine call per frame, engine.inference(frame, regions)) and the humans
 //     are merged in the frame's coordinates (hp::plan_tiles / to_frame / merge_humans; stream runtime: stream.set_tiling);
+//   * flip ensemble (addition): `--flip_ensemble`: every frame - every tile of it with --tiles - runs through the network with its left-right
+//     flip and the parser reads the merged maps (engine.set_flip_ensemble / stream.set_flip_ensemble; include/hp_hip.h "flip ensemble"); a batch
+//     then holds --max_batch_size / 2 frames.  --post=paf only; works in both runtimes and with --tiles, --rotate, --hflip and --yuv_*;
 //   * upright input (addition): `--rotate=0|90|180|270` (the clockwise turn that brings the stored picture upright: a container's rotate tag) and
 //     `--hflip` (the stored picture is mirrored left-right): the frames of every source, in both runtimes, are read upright inside the resize
 //     (engine.set_orientation / stream.set_orientation; hp::orientation).  Pictures and --saving_yuv frames stay in stored orientation, the
@@ -82,6 +85,7 @@ static bool g_tiled = false;
 static hp::tiling g_tiling;
 static int FLAGS_rotate = 0;       // addition: --rotate=0|90|180|270: clockwise degrees that bring the stored frames upright (hp::orientation)
 static bool FLAGS_hflip = false;   // ... the stored frames are mirrored left-right
+static bool FLAGS_flip_ensemble = false; // addition: --flip_ensemble: frame + flipped frame through the network, maps merged on the device (PAF only)
 static hp::orientation g_orient;
 static std::string FLAGS_saving_yuv; // addition: append the frames, annotated on the device in their own format, to this file
 static int FLAGS_synthetic_humans = 0; // addition: stand-in humans added to every frame's poses (see the head of the file)
@@ -100,7 +104,7 @@ static bool parse_flags(int argc, char** argv)
     std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size }, { "tile_overlap", &FLAGS_tile_overlap },
         { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h }, { "synthetic_humans", &FLAGS_synthetic_humans }, { "rotate", &FLAGS_rotate } };
     std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 }, { "yuv", &FLAGS_yuv }, { "tile_full", &FLAGS_tile_full },
-        { "hdr_keep_primaries", &FLAGS_hdr_keep_primaries }, { "hflip", &FLAGS_hflip } };
+        { "hdr_keep_primaries", &FLAGS_hdr_keep_primaries }, { "hflip", &FLAGS_hflip }, { "flip_ensemble", &FLAGS_flip_ensemble } };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a.rfind("--", 0) != 0 && a.rfind("-", 0) == 0)
@@ -502,6 +506,16 @@ int main(int argc, char** argv)
         cli_log() << "ERROR: --saving_yuv writes video frames: it needs a .yuv source or --yuv\n";
         return 1;
     }
+    // --flip_ensemble is settled from the flags alone too: the PAF maps are the ones with a left / right channel table
+    if (FLAGS_flip_ensemble && FLAGS_post != kPAF) {
+        cli_log() << "ERROR: --flip_ensemble merges the maps of a PAF network (--post=" kPAF "), got --post=" << FLAGS_post << "\n";
+        return 1;
+    }
+    if (FLAGS_flip_ensemble && (g_tiled ? 2 * g_tiling.regions() : 2) > FLAGS_max_batch_size) {
+        cli_log() << "ERROR: --flip_ensemble runs every " << (g_tiled ? "region" : "frame") << " with its flip: " << (g_tiled ? 2 * g_tiling.regions() : 2)
+                  << " network images per frame, more than --max_batch_size=" << FLAGS_max_batch_size << "\n";
+        return 1;
+    }
     if (g_tiled && g_tiling.regions() > FLAGS_max_batch_size) {
         cli_log() << "ERROR: --tiles=" << FLAGS_tiles << (FLAGS_tile_full ? " --tile_full" : "") << " makes " << g_tiling.regions()
                   << " regions per frame, more than --max_batch_size=" << FLAGS_max_batch_size << "\n";
@@ -566,6 +580,10 @@ int main(int argc, char** argv)
         std::cerr << "--int8: calibrated the kINT8 engine on the first " << n << " frame(s) of the source (MinMax)" << std::endl;
     }
     any_parser parser = build_parser(engine);
+    if (FLAGS_flip_ensemble && FLAGS_runtime != kSTREAM) { // (after the calibration, which runs the plain schedule; the stream sets its own engines)
+        engine.set_flip_ensemble(true);
+        cli_log() << "--flip_ensemble: every frame runs with its left-right flip, batches of up to " << engine.batch_room() << "\n";
+    }
     if (FLAGS_runtime != kOPERATOR && FLAGS_runtime != kSTREAM) {
         cli_log() << "WARNING: --runtime=" << FLAGS_runtime << " is neither " kOPERATOR " nor " kSTREAM "; using " kOPERATOR "\n";
         FLAGS_runtime = kOPERATOR;
@@ -612,7 +630,7 @@ int main(int argc, char** argv)
     auto beg = clk_t::now();
     if (FLAGS_runtime == kOPERATOR) {
         // operator API: one batch at a time - engine.inference(batch) -> one internal_t per frame -> parser.process(internal_t)
-        const size_t step = (size_t)std::max(1, FLAGS_max_batch_size);
+        const size_t step = std::max<size_t>(1, engine.batch_room());
         for (size_t first = 0; first < images.size(); first += step) {
             std::vector<cv::Mat> batch(images.begin() + first, images.begin() + std::min(images.size(), first + step));
             std::vector<hp::yuv_frame> yuv_batch;
@@ -667,6 +685,8 @@ int main(int argc, char** argv)
                 if (g_tiled)
                     stream.set_tiling(g_tiling);
                 stream.set_orientation(g_orient);
+                if (FLAGS_flip_ensemble)
+                    stream.set_flip_ensemble(true);
                 stream.async() << images;
                 auto sink = [&](size_t, const cv::Mat& frame, const std::vector<hp::human_t>& poses) {
                     cv::Mat img = clone(frame);

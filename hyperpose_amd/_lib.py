@@ -67,6 +67,11 @@ class Roi(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
 
 
+class FlipOutput(C.Structure):
+    """hp_flip_output"""
+    _fields_ = [("output", C.c_int32), ("perm", C.POINTER(C.c_int32)), ("sign", C.POINTER(C.c_int8))]
+
+
 class HdrDesc(C.Structure):
     """hp_hdr_desc"""
     _fields_ = [("transfer", C.c_int32), ("to_bt709", C.c_int32), ("peak_nits", C.c_float), ("white_nits", C.c_float)]
@@ -119,6 +124,8 @@ SYMBOLS = [
     "hp_resize_rois_u8c3", "hp_resize_rois_yuv", "hp_yuv_roi_alignment", "hp_tile_plan", "hp_humans_to_frame", "hp_humans_merge", "hp_pipeline_set_tiling",
     "hp_resize_oriented_u8c3", "hp_resize_oriented_yuv", "hp_resize_rois_oriented_u8c3", "hp_resize_rois_oriented_yuv", "hp_oriented_size",
     "hp_orientation_from_exif", "hp_orient_roi", "hp_orient_u8c3_host", "hp_humans_orient", "hp_pipeline_set_orientation",
+    "hp_hflip_u8c3", "hp_hflip_u8c3_host", "hp_flip_merge", "hp_flip_merge_host", "hp_flip_tables_coco", "hp_engine_set_flip_ensemble",
+    "hp_engine_set_flip_ensemble_coco", "hp_engine_flip_ensemble", "hp_pipeline_set_flip_ensemble",
 ]
 
 

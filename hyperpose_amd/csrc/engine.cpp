@@ -257,6 +257,19 @@ struct hp_engine {
     std::map<graph_key, hipGraphExec_t> graphs;
     bool use_graph = true;
 
+    // Flip ensemble (hp_engine_set_flip_ensemble; csrc/flip_ensemble.hpp): one table pair per output while on, empty while off.  A u8 batch of n
+    // frames then runs as the 2n frames of flip_in - the caller's frames, their left-right flips behind them - and every output is merged in place.
+    struct flip_table {
+        std::vector<int32_t> perm;
+        std::vector<int8_t> sign;
+    };
+    std::vector<flip_table> flip;
+    hp::dev_buf flip_in; // [max_batch][in_h][in_w][3] u8
+    bool flip_on() const { return !flip.empty(); }
+    // dev_src != nullptr: the n frames are copied into flip_in first (device to device); then their flips are written behind them
+    int flip_stage(const uint8_t* dev_src, int n, hipStream_t s) const;
+    int flip_merge(int n, hipStream_t s) const; // hp_flip_merge on every output: frames [0, n) become the ensemble
+
     ~hp_engine()
     {
         for (auto& g : graphs)
@@ -1606,6 +1619,23 @@ int hp_engine::apply_int8_scales()
     return HP_OK;
 }
 
+int hp_engine::flip_stage(const uint8_t* dev_src, int n, hipStream_t s) const
+{
+    const size_t bytes = (size_t)n * in_h * in_w * 3;
+    if (dev_src)
+        HP_HIP_TRY(hipMemcpyAsync(flip_in.p, dev_src, bytes, hipMemcpyDeviceToDevice, s));
+    return hp_hflip_u8c3(flip_in.as<uint8_t>(), flip_in.as<uint8_t>() + bytes, in_w, in_h, n, s);
+}
+
+int hp_engine::flip_merge(int n, hipStream_t s) const
+{
+    for (size_t i = 0; i < outputs.size(); ++i) {
+        const out_info& o = outputs[i];
+        HP_TRY(hp_flip_merge(o.buf->as<float>(), n, o.out_c(), o.x.out_h, o.x.out_w, flip[i].perm.data(), flip[i].sign.data(), s));
+    }
+    return HP_OK;
+}
+
 int hp_engine::drop_graphs()
 {
     HP_HIP_TRY(hipStreamSynchronize(stream));
@@ -2149,6 +2179,28 @@ static int infer_common(hp_engine* e, const void* input, size_t frame_bytes, int
     HP_REQUIRE(n <= e->max_batch, HP_ERR_CAPACITY, "Input batch size overflow: Yours@%d Max@%d", n, e->max_batch);
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
     const void* dev_in = input;
+    // Flip ensemble: the schedule below runs on the 2n frames of flip_in as a device batch; `staged` brackets it with the flip and the merge.
+    // A host batch goes up into flip_in here (never part of a captured graph, as below); a device batch is copied there by flip_stage.
+    const bool fl = e->flip_on();
+    const uint8_t* fl_src = nullptr;
+    if (fl) {
+        HP_REQUIRE(kind == 0, HP_ERR_STATE, "hp_engine_infer_f32: not available while the flip ensemble is on (it is defined on u8 frames: hp_engine_infer_u8)");
+        HP_REQUIRE(2 * n <= e->max_batch, HP_ERR_CAPACITY, "Input batch size overflow: Yours@%d, with the flip ensemble on %d network images, Max@%d", n, 2 * n,
+            e->max_batch);
+        if (on_device)
+            fl_src = (const uint8_t*)input;
+        else
+            HP_HIP_TRY(hipMemcpyAsync(e->flip_in.p, input, frame_bytes * n, hipMemcpyHostToDevice, s));
+        dev_in = e->flip_in.p, on_device = 1, n *= 2;
+    }
+    const bool halves = e->parts == 2 && e->halves_ok() && n >= 2;
+    // the schedule of frames [b0, b0 + cnt) of the batch; with the ensemble on and one stream, flip and merge around it (captured with it)
+    auto staged = [&](const uint8_t* u8, const float* f32, int b0, int cnt, hipStream_t cs) -> int {
+        if (fl && !halves)
+            HP_TRY(e->flip_stage(fl_src, cnt / 2, cs));
+        HP_TRY(e->enqueue_range(u8, f32, b0, cnt, cs));
+        return fl && !halves ? e->flip_merge(cnt / 2, cs) : HP_OK;
+    };
     if (!on_device) {
         const size_t need = (size_t)e->max_batch * e->in_h * e->in_w * 3 * sizeof(float);
         if (e->in_stage.bytes < need)
@@ -2160,17 +2212,23 @@ static int infer_common(hp_engine* e, const void* input, size_t frame_bytes, int
     }
     const uint8_t* u8 = kind == 0 ? (const uint8_t*)dev_in : nullptr;
     const float* f32 = kind == 1 ? (const float*)dev_in : nullptr;
-    if (!e->use_graph)
-        return e->enqueue(u8, f32, n, s, on_device ? nullptr : input, frame_bytes);
+    if (!e->use_graph) {
+        if (fl)
+            HP_TRY(e->flip_stage(fl_src, n / 2, s));
+        HP_TRY(e->enqueue(u8, f32, n, s, on_device ? nullptr : input, frame_bytes));
+        return fl ? e->flip_merge(n / 2, s) : HP_OK; // (two half-batches: behind the join)
+    }
 
     // capture a range's schedule once per (frames, input buffer, first frame); replays cost one launch
     auto graph_for = [&](int b0, int cnt, hipStream_t cs, hipGraphExec_t* out) -> int {
-        const hp_engine::graph_key key{ cnt, dev_in, kind, b0 };
+        // (a one-stream ensemble graph holds the copy from the caller's device buffer: keyed by that pointer; the half-batch graphs read flip_in
+        // alone - flip and merge are launched around them - and are keyed by it; both apart from the plain graphs by kind)
+        const hp_engine::graph_key key{ cnt, fl_src && !halves ? (const void*)fl_src : dev_in, fl ? 2 : kind, b0 };
         auto it = e->graphs.find(key);
         if (it == e->graphs.end()) {
             hipGraph_t graph = nullptr;
             HP_HIP_TRY(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-            const int rc = e->enqueue_range(u8, f32, b0, cnt, cs);
+            const int rc = staged(u8, f32, b0, cnt, cs);
             const hipError_t ee = hipStreamEndCapture(cs, &graph);
             if (rc != HP_OK) {
                 if (graph)
@@ -2196,13 +2254,15 @@ static int infer_common(hp_engine* e, const void* input, size_t frame_bytes, int
         *out = it->second;
         return HP_OK;
     };
-    if (e->parts == 2 && e->halves_ok() && n >= 2) {
+    if (halves) {
         // two half-batches side by side (hp_engine::enqueue has the reasoning): ONE graph with two branches is replayed branch after branch by
         // the runtime (measured: 2.27 -> 2.22 ms per call), two graphs on two streams run side by side (the probe's 2.49 -> 1.96 ms)
         const int n0 = (n + 1) / 2;
         hipGraphExec_t ga = nullptr, gb = nullptr;
         HP_TRY(graph_for(0, n0, s, &ga));
         HP_TRY(graph_for(n0, n - n0, e->stream2, &gb));
+        if (fl) // the frames are the first half-batch, their flips the second: written before the fork, merged behind the join
+            HP_TRY(e->flip_stage(fl_src, n0, s));
         HP_HIP_TRY(hipEventRecord(e->ev_fork, s));
         HP_HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
         if (!on_device) { // the second half's frames cross PCIe under the first half's first layers
@@ -2214,7 +2274,7 @@ static int infer_common(hp_engine* e, const void* input, size_t frame_bytes, int
         HP_HIP_TRY(hipGraphLaunch(gb, e->stream2));
         HP_HIP_TRY(hipEventRecord(e->ev_join, e->stream2));
         HP_HIP_TRY(hipStreamWaitEvent(s, e->ev_join, 0));
-        return HP_OK;
+        return fl ? e->flip_merge(n0, s) : HP_OK;
     }
     hipGraphExec_t g = nullptr;
     HP_TRY(graph_for(0, n, s, &g));
@@ -2392,6 +2452,60 @@ int hp_engine_set_graph(hp_engine* e, int enable)
     e->use_graph = enable != 0;
     return HP_OK;
 }
+
+int hp_engine_set_flip_ensemble(hp_engine* e, const hp_flip_output* outs, int n_outs)
+{
+    HP_REQUIRE(e && n_outs >= 0 && (outs || n_outs == 0), HP_ERR_INVALID, "hp_engine_set_flip_ensemble: null argument");
+    const int NO = (int)e->outputs.size();
+    std::vector<hp_engine::flip_table> next(n_outs ? NO : 0);
+    if (n_outs) {
+        HP_REQUIRE(n_outs == NO, HP_ERR_INVALID, "hp_engine_set_flip_ensemble: %d outputs listed, the engine has %d: every output is listed exactly once", n_outs, NO);
+        for (int k = 0; k < n_outs; ++k) {
+            const int i = outs[k].output;
+            HP_REQUIRE(i >= 0 && i < NO, HP_ERR_INVALID, "hp_engine_set_flip_ensemble: entry %d names output %d, the engine has outputs 0 .. %d", k, i, NO - 1);
+            HP_REQUIRE(next[i].perm.empty(), HP_ERR_INVALID, "hp_engine_set_flip_ensemble: output %d (%s) is listed twice", i, e->outputs[i].name.c_str());
+            HP_REQUIRE(outs[k].perm && outs[k].sign, HP_ERR_INVALID, "hp_engine_set_flip_ensemble: entry %d (output %d) has a null table", k, i);
+            const int Cn = e->outputs[i].out_c();
+            HP_REQUIRE(Cn >= 1 && Cn <= 256, HP_ERR_INVALID, "hp_engine_set_flip_ensemble: output %d (%s) has %d channels, hp_flip_merge takes 1 .. 256", i,
+                e->outputs[i].name.c_str(), Cn);
+            for (int c = 0; c < Cn; ++c) {
+                HP_REQUIRE(outs[k].perm[c] >= 0 && outs[k].perm[c] < Cn, HP_ERR_INVALID, "hp_engine_set_flip_ensemble: output %d: perm[%d] = %d is outside [0, %d)", i, c,
+                    outs[k].perm[c], Cn);
+                HP_REQUIRE(outs[k].sign[c] == 1 || outs[k].sign[c] == -1, HP_ERR_INVALID, "hp_engine_set_flip_ensemble: output %d: sign[%d] = %d is neither -1 nor +1", i, c,
+                    (int)outs[k].sign[c]);
+            }
+            next[i].perm.assign(outs[k].perm, outs[k].perm + Cn), next[i].sign.assign(outs[k].sign, outs[k].sign + Cn);
+        }
+    }
+    HP_TRY(e->drop_graphs()); // (the captured schedules are of the other form)
+    const size_t need = (size_t)e->max_batch * e->in_h * e->in_w * 3;
+    if (n_outs && e->flip_in.bytes < need)
+        HP_TRY(e->flip_in.alloc(need));
+    e->flip.swap(next);
+    return HP_OK;
+}
+
+int hp_engine_set_flip_ensemble_coco(hp_engine* e, int enable)
+{
+    HP_REQUIRE(e, HP_ERR_INVALID, "hp_engine_set_flip_ensemble_coco: null engine");
+    if (!enable)
+        return hp_engine_set_flip_ensemble(e, nullptr, 0);
+    const int NO = (int)e->outputs.size();
+    HP_REQUIRE(NO == 2, HP_ERR_INVALID, "hp_engine_set_flip_ensemble_coco: a COCO PAF network has two outputs (conf, paf), this engine has %d", NO);
+    const out_info &c = e->outputs[0], &p = e->outputs[1];
+    HP_REQUIRE((c.out_c() == HP_COCO_N_PARTS || c.out_c() == HP_COCO_N_PARTS + 1) && p.out_c() == 2 * HP_COCO_N_PAIRS, HP_ERR_INVALID,
+        "hp_engine_set_flip_ensemble_coco: outputs %s with %d and %s with %d channels, expected 18 or 19 and 38", c.name.c_str(), c.out_c(), p.name.c_str(), p.out_c());
+    HP_REQUIRE(c.x.out_h == p.x.out_h && c.x.out_w == p.x.out_w, HP_ERR_INVALID, "hp_engine_set_flip_ensemble_coco: outputs %s %d x %d and %s %d x %d differ in size",
+        c.name.c_str(), c.x.out_h, c.x.out_w, p.name.c_str(), p.x.out_h, p.x.out_w);
+    int32_t conf_perm[HP_COCO_N_PARTS + 1], paf_perm[2 * HP_COCO_N_PAIRS];
+    int8_t conf_sign[HP_COCO_N_PARTS + 1], paf_sign[2 * HP_COCO_N_PAIRS];
+    HP_TRY(hp_flip_tables_coco(c.out_c(), conf_perm, paf_perm, paf_sign));
+    std::fill(conf_sign, conf_sign + HP_COCO_N_PARTS + 1, (int8_t)1);
+    const hp_flip_output outs[2] = { { 0, conf_perm, conf_sign }, { 1, paf_perm, paf_sign } };
+    return hp_engine_set_flip_ensemble(e, outs, 2);
+}
+
+int hp_engine_flip_ensemble(const hp_engine* e) { return e ? (int)e->flip_on() : HP_ERR_INVALID; }
 
 int hp_engine_num_outputs(const hp_engine* e) { return e ? (int)e->outputs.size() : HP_ERR_INVALID; }
 

@@ -15,6 +15,8 @@
 // (resize_yuv_hdr.hip); nothing else changes, and 8-bit frames of the same batch go the SDR way.
 // Upright input (hp_pipeline_set_orientation): while a non-zero code is set the submitted frames are STORED frames; every resize call above is replaced by
 // its oriented twin (resize_oriented.hip), and everything after it - letterbox, tiles, resume_ratio, the merge - sees the upright uw x uh frame.
+// Flip ensemble (hp_pipeline_set_flip_ensemble): every pipe's engine runs each network-sized slot and its left-right flip and merges the maps
+// (flip_ensemble.hip) before the parser reads them; here only the capacity changes: a batch holds pl->capacity() = max_batch / 2 slots.
 #include "hp_common.hpp"
 #include "yuv_formats.hpp"
 
@@ -62,6 +64,9 @@ struct hp_pipeline {
     std::vector<int32_t> cand_region;
     int orientation = HP_ORIENT_NONE; // non-zero: submitted frames are stored turned / mirrored, p.w / p.h and the regions are the upright frame's
     hp_tonemap* tonemap = nullptr; // set: 10-bit hp_yuv_image frames are PQ / HLG and are tone-mapped while they are resized
+    bool flip_ensemble = false;    // set: every engine runs slot + flipped slot, so a batch holds half as many slots
+    int capacity() const { return flip_ensemble ? max_batch / 2 : max_batch; } // network-sized slots per submit
+    const char* flip_note() const { return flip_ensemble ? " / 2: the flip ensemble is on, every frame runs with its flip" : ""; }
 
     // the tone-map of a frame, or null for the SDR path
     const hp_tonemap* tonemap_for(const hp_yuv_image& f) const { return tonemap && hp_yuv::layout_of(f.format)->sample_bytes == 2 ? tonemap : nullptr; }
@@ -169,6 +174,7 @@ int hp_pipeline_set_tiling(hp_pipeline* pl, const hp_tiling* t)
     if (R < 0)
         return R;
     HP_REQUIRE(R <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_set_tiling: %d regions per frame > max_batch %d", R, pl->max_batch);
+    HP_REQUIRE(R <= pl->capacity(), HP_ERR_CAPACITY, "hp_pipeline_set_tiling: %d regions per frame and their flips (the flip ensemble is on) > max_batch %d", R, pl->max_batch);
     HP_REQUIRE(t->min_common >= 1 && t->tol >= 0., HP_ERR_INVALID, "hp_pipeline_set_tiling: min_common %d (>= 1), tol %g (>= 0)", t->min_common, t->tol);
     pl->tiling = *t, pl->tiled = true;
     return HP_OK;
@@ -195,12 +201,37 @@ int hp_pipeline_set_orientation(hp_pipeline* pl, int orientation)
     return HP_OK;
 }
 
+int hp_pipeline_set_flip_ensemble(hp_pipeline* pl, int enable)
+{
+    static const char* const kinds[] = { "HP_PARSER_PAF", "HP_PARSER_PPN", "HP_PARSER_PIFPAF" };
+    HP_REQUIRE(pl, HP_ERR_INVALID, "hp_pipeline_set_flip_ensemble: null pipeline");
+    HP_REQUIRE(pl->inflight == 0, HP_ERR_STATE, "hp_pipeline_set_flip_ensemble: %d batches are in flight, collect first", pl->inflight);
+    HP_REQUIRE(pl->kind == HP_PARSER_PAF, HP_ERR_INVALID, "hp_pipeline_set_flip_ensemble: the flip ensemble is defined for HP_PARSER_PAF pipelines, this one ends in %s",
+        kinds[pl->kind]);
+    if (enable) {
+        HP_REQUIRE(pl->max_batch >= 2, HP_ERR_CAPACITY, "hp_pipeline_set_flip_ensemble: max_batch %d has no room for a frame and its flip", pl->max_batch);
+        const int R = pl->tiling.cols * pl->tiling.rows + pl->tiling.with_full;
+        HP_REQUIRE(!pl->tiled || 2 * R <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_set_flip_ensemble: %d regions per frame (tiling is on) and their flips > max_batch %d", R,
+            pl->max_batch);
+    }
+    for (size_t i = 0; i < pl->pipes.size(); ++i) {
+        const int rc = hp_engine_set_flip_ensemble_coco(pl->pipes[i].eng, enable != 0);
+        if (rc != HP_OK) { // (every pipe holds the same network: a refusal is the first pipe's, and nothing has changed)
+            for (size_t j = 0; j < i; ++j)
+                (void)hp_engine_set_flip_ensemble_coco(pl->pipes[j].eng, pl->flip_ensemble);
+            return rc;
+        }
+    }
+    pl->flip_ensemble = enable != 0;
+    return HP_OK;
+}
+
 int hp_pipeline_submit(hp_pipeline* pl, const uint8_t* const* frames, const int* widths, const int* heights, int n)
 {
     HP_REQUIRE(pl && frames && widths && heights, HP_ERR_INVALID, "hp_pipeline_submit: null argument");
     if (pl->tiled)
         return submit_tiled(pl, frames, widths, heights, n);
-    HP_REQUIRE(n >= 1 && n <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_submit: batch %d > max_batch %d", n, pl->max_batch);
+    HP_REQUIRE(n >= 1 && n <= pl->capacity(), HP_ERR_CAPACITY, "hp_pipeline_submit: batch %d > max_batch %d%s", n, pl->max_batch, pl->flip_note());
     HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "hp_pipeline_submit: all %d pipes are busy, collect first", pl->n_pipes);
     pipe_t& p = pl->pipes[pl->head];
     const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
@@ -263,7 +294,7 @@ int hp_pipeline_submit_yuv(hp_pipeline* pl, int format, const uint8_t* const* fr
     HP_REQUIRE(pl->orientation == HP_ORIENT_NONE, HP_ERR_STATE,
         "hp_pipeline_submit_yuv: not available while an orientation is set, submit hp_yuv_image frames with hp_pipeline_submit_yuv_images");
     HP_REQUIRE(format == HP_YUV_NV12 || format == HP_YUV_I420, HP_ERR_INVALID, "hp_pipeline_submit_yuv: unknown format %d", format);
-    HP_REQUIRE(n >= 1 && n <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_submit_yuv: batch %d > max_batch %d", n, pl->max_batch);
+    HP_REQUIRE(n >= 1 && n <= pl->capacity(), HP_ERR_CAPACITY, "hp_pipeline_submit_yuv: batch %d > max_batch %d%s", n, pl->max_batch, pl->flip_note());
     HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "hp_pipeline_submit_yuv: all %d pipes are busy, collect first", pl->n_pipes);
     pipe_t& p = pl->pipes[pl->head];
     const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
@@ -310,7 +341,7 @@ int hp_pipeline_submit_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, i
     HP_REQUIRE(pl && frames, HP_ERR_INVALID, "hp_pipeline_submit_yuv_images: null argument");
     if (pl->tiled)
         return submit_tiled_yuv_images(pl, frames, n, on_device);
-    HP_REQUIRE(n >= 1 && n <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_submit_yuv_images: batch %d > max_batch %d", n, pl->max_batch);
+    HP_REQUIRE(n >= 1 && n <= pl->capacity(), HP_ERR_CAPACITY, "hp_pipeline_submit_yuv_images: batch %d > max_batch %d%s", n, pl->max_batch, pl->flip_note());
     HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "hp_pipeline_submit_yuv_images: all %d pipes are busy, collect first", pl->n_pipes);
     pipe_t& p = pl->pipes[pl->head];
     const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
@@ -427,8 +458,8 @@ int tiled_regions(const hp_pipeline* pl) { return pl->tiling.cols * pl->tiling.r
 int tiled_admit(hp_pipeline* pl, const char* who, int n)
 {
     const int R = tiled_regions(pl);
-    HP_REQUIRE(n >= 1 && n <= pl->max_batch / R, HP_ERR_CAPACITY, "%s: %d frames of %d regions each > max_batch %d (at most %d frames per submit)", who, n, R,
-        pl->max_batch, pl->max_batch / R);
+    HP_REQUIRE(n >= 1 && n <= pl->capacity() / R, HP_ERR_CAPACITY, "%s: %d frames of %d regions each > max_batch %d%s (at most %d frames per submit)", who, n, R,
+        pl->max_batch, pl->flip_note(), pl->capacity() / R);
     HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "%s: all %d pipes are busy, collect first", who, pl->n_pipes);
     return HP_OK;
 }

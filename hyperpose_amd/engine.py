@@ -255,6 +255,29 @@ class Engine:
     def set_graph(self, enable: bool):
         check(lib().hp_engine_set_graph(self._h, int(enable)))
 
+    def set_flip_ensemble(self, on: bool = True, tables=None) -> None:
+        """``hp_engine_set_flip_ensemble``: from now on a u8 batch of n frames (2n <= max_batch) runs as the frames and their left-right flips
+        and the first n frames of every output are the merged maps (include/hp_hip.h, "flip ensemble").  ``tables`` None: the COCO tables
+        (``hp_engine_set_flip_ensemble_coco``, a (conf, paf) network); otherwise a list of (output index, perm, sign), every output once - the
+        way a network with another skeleton is described.  ``on=False`` restores the plain engine."""
+        if not on:
+            check(lib().hp_engine_set_flip_ensemble(self._h, None, 0))
+            return
+        if tables is None:
+            check(lib().hp_engine_set_flip_ensemble_coco(self._h, 1))
+            return
+        keep = [(int(i), np.ascontiguousarray(p, np.int32).ravel(), np.ascontiguousarray(s, np.int8).ravel()) for i, p, s in tables]
+        for i, p, s in keep:
+            if 0 <= i < len(self.outputs) and (p.size != self.outputs[i][1][0] or s.size != p.size):
+                raise ValueError(f"set_flip_ensemble: output {i} has {self.outputs[i][1][0]} channels, got {p.size} perm and {s.size} sign entries")
+        arr = (_lib.FlipOutput * max(1, len(keep)))(*[_lib.FlipOutput(i, p.ctypes.data_as(C.POINTER(C.c_int32)), s.ctypes.data_as(C.POINTER(C.c_int8)))
+                                                      for i, p, s in keep])
+        check(lib().hp_engine_set_flip_ensemble(self._h, arr, len(keep)))
+
+    @property
+    def flip_ensemble(self) -> bool:
+        return bool(check(lib().hp_engine_flip_ensemble(self._h)))
+
     # ---- asynchronous device-resident path (bench, pipelines)
     def set_concurrency(self, parts: int):
         """2: a batch runs as two half-batches side by side on two internal streams (hp_engine_set_concurrency; fp32 engines) - for a

@@ -302,6 +302,54 @@ def resize_oriented(src, dst_dev, dw: int, dh: int, orientation: int, keep_ratio
                                             bg[2], as_ptr(dst_dev), int(dw), int(dh), int(dst_stride or dw * 3), s))
 
 
+# ---- flip ensemble: the frame flip, the map merge and the COCO tables (include/hp_hip.h; the definition: csrc/flip_ensemble.hpp) ---------------
+
+def flip_tables_coco(conf_channels: int = 19):
+    """``hp_flip_tables_coco``: (conf_perm int32 [conf_channels], paf_perm int32 [38], paf_sign int8 [38]) of a COCO PAF network."""
+    conf = np.zeros(max(1, int(conf_channels)), np.int32)
+    perm, sign = np.zeros(38, np.int32), np.zeros(38, np.int8)
+    check(lib().hp_flip_tables_coco(int(conf_channels), conf.ctypes.data_as(C.POINTER(C.c_int32)), perm.ctypes.data_as(C.POINTER(C.c_int32)),
+                                    sign.ctypes.data_as(C.POINTER(C.c_int8))))
+    return conf[:conf_channels], perm, sign
+
+
+def hflip_u8c3(src_dev, dst_dev, w: int, h: int, n: int = 1, stream=None) -> None:
+    """``hp_hflip_u8c3``: ``n`` packed u8 HWC device frames flipped left-right into ``dst_dev`` (no overlap); only enqueues."""
+    check(lib().hp_hflip_u8c3(as_ptr(src_dev), as_ptr(dst_dev), int(w), int(h), int(n), C.c_void_p(stream) if stream else None))
+
+
+def hflip_u8c3_host(frames: np.ndarray) -> np.ndarray:
+    """``hp_hflip_u8c3_host``: [n, h, w, 3] (or [h, w, 3]) uint8 -> the flipped frames, no device needed."""
+    src = np.ascontiguousarray(frames, np.uint8)
+    assert src.ndim in (3, 4) and src.shape[-1] == 3
+    h, w = src.shape[-3], src.shape[-2]
+    out = np.empty_like(src)
+    check(lib().hp_hflip_u8c3_host(C.c_void_p(src.ctypes.data), C.c_void_p(out.ctypes.data), w, h, src.shape[0] if src.ndim == 4 else 1))
+    return out
+
+
+def _flip_tables(perm, sign):
+    p, s = np.ascontiguousarray(perm, np.int32).ravel(), np.ascontiguousarray(sign, np.int8).ravel()
+    return p, s, p.ctypes.data_as(C.POINTER(C.c_int32)), s.ctypes.data_as(C.POINTER(C.c_int8))
+
+
+def flip_merge(maps_dev, n: int, C_: int, H: int, W: int, perm, sign, stream=None) -> None:
+    """``hp_flip_merge``: device maps [>= 2n, C, H, W] fp32; maps [0, n) become 0.5 * (a +- b), in place; only enqueues.  ``perm`` and
+    ``sign`` are passed as they are (C entries expected), so that the refusals can be tested."""
+    p, s, pp, sp = _flip_tables(perm, sign)
+    check(lib().hp_flip_merge(as_ptr(maps_dev), int(n), int(C_), int(H), int(W), pp, sp, C.c_void_p(stream) if stream else None))
+
+
+def flip_merge_host(maps: np.ndarray, n: int, perm, sign, shape=None) -> np.ndarray:
+    """``hp_flip_merge_host`` on a copy of ``maps`` [>= 2n, C, H, W] float32: the whole array back, maps [0, n) merged.  ``shape`` = (C, H, W)
+    overrides the array's (tests of the refusals)."""
+    out = np.array(maps, np.float32, order="C", copy=True)
+    Cc, H, W = shape if shape is not None else out.shape[1:]
+    p, s, pp, sp = _flip_tables(perm, sign)
+    check(lib().hp_flip_merge_host(out.ctypes.data_as(C.POINTER(C.c_float)), int(n), int(Cc), int(H), int(W), pp, sp))
+    return out
+
+
 # ---- regions and tiles: many regions of one frame per launch, the tile planner, the way back and the merge (include/hp_hip.h) -----------
 
 def _rois(rois):

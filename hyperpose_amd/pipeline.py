@@ -95,6 +95,12 @@ class Pipeline:
         off.  Not while batches are in flight; ``submit_yuv`` is refused while an orientation is set."""
         check(lib().hp_pipeline_set_orientation(self._h, int(orientation)))
 
+    def set_flip_ensemble(self, on: bool = True) -> None:
+        """``hp_pipeline_set_flip_ensemble``: from now on every network-sized slot runs with its left-right flip and the parser reads the
+        merged maps (COCO tables; "paf" pipelines only).  A submit then carries at most ``max_batch // 2`` frames (tiled:
+        ``max_batch // (2 * regions)``).  Not while batches are in flight."""
+        check(lib().hp_pipeline_set_flip_ensemble(self._h, int(bool(on))))
+
     def submit(self, frames) -> None:
         """frames: list of [h, w, 3] uint8 BGR arrays (any sizes), at most max_batch."""
         frames = [np.ascontiguousarray(f, np.uint8) for f in frames]

@@ -655,6 +655,51 @@ int hp_engine_arena_info(const hp_engine* e, uint64_t info[3]);
  * compares them with global memory; out = { patch words that differed, weight words that differed, blocks checked, 0 } since the last reset. */
 int hp_debug_first_conv_verify(unsigned out[4], int reset);
 
+/* ---- flip ensemble: the network runs on every frame and on its left-right flip; the flipped maps are flipped back - left and right channels
+ * swapped, the x component of the part-affinity fields negated - and the two sets of maps are averaged on the device, before parsing
+ * (hyperpose_amd/csrc/flip_ensemble.hip; the definition is stated once in csrc/flip_ensemble.hpp and DESIGN.md 1.1 "Flip ensemble").  Off by
+ * default; while off, nothing here is launched.
+ *
+ * hp_hflip_u8c3: n packed u8 HWC frames (rows of w * 3 bytes, frames w * h * 3 bytes apart), dst[i][y][x][c] = src[i][y][w-1-x][c]; src and dst
+ * must not overlap (dst == src + n * w * h * 3 is the expected use); any w >= 1.  The device call only enqueues.
+ *
+ * hp_flip_merge: dev_maps holds at least 2n maps [C][H][W], contiguous, fp32: n frames, then the maps of their flips.  For f < n, in place,
+ *     a = maps[f][c][y][x]   b = maps[n+f][perm[c]][y][W-1-x]   maps[f][c][y][x] = sign[c] > 0 ? 0.5f * (a + b) : 0.5f * (a - b)
+ * Maps n .. 2n-1 and everything behind them are not written.  perm and sign are HOST tables of C entries, read before the call returns (they go
+ * to the kernel by value).  HP_ERR_INVALID, with a message that names the argument, and nothing launched: C outside 1 .. 256, a perm[c] outside
+ * [0, C), a sign[c] other than -1 / +1, n, H or W below 1.  Because a + b == b + a and 0.5f * (a - b) == -(0.5f * (b - a)) bit for bit, the
+ * ensemble E of a frame-invariant network is exactly equivariant when perm is an involution and sign[perm[c]] == sign[c]:
+ *     E(flip(x))[perm[c]](W-1-p) * sign[c] == E(x)[c](p)
+ * in every bit but the sign of a zero: where a == b a negated channel holds +0 on one side and -0 on the other.
+ * The *_host twins are the same statements in plain C++ (no device), same evaluation order.
+ *
+ * hp_flip_tables_coco (host only): the tables of a COCO PAF network, derived from the part pairs and PAF channel pairs the PAF parser reads:
+ * parts swap 2-5, 3-6, 4-7, 8-11, 9-12, 10-13, 14-15, 16-17 (0, 1 and a background channel 18 stay: conf_channels is 18 or 19, conf_perm has
+ * that many entries, the confidence signs are all +1); the mirror of limb k is the limb of the mirrored parts, paf_perm maps its x / y channel to
+ * the mirror's x / y channel and paf_sign is -1 on the x channels (the even ones). */
+int hp_hflip_u8c3(const uint8_t* dev_src, uint8_t* dev_dst, int w, int h, int n, void* stream);
+int hp_hflip_u8c3_host(const uint8_t* src, uint8_t* dst, int w, int h, int n);
+int hp_flip_merge(float* dev_maps, int n, int C, int H, int W, const int32_t* perm, const int8_t* sign /* host tables */, void* stream);
+int hp_flip_merge_host(float* maps, int n, int C, int H, int W, const int32_t* perm, const int8_t* sign);
+int hp_flip_tables_coco(int conf_channels /* 18 or 19 */, int32_t* conf_perm, int32_t paf_perm[38], int8_t paf_sign[38]);
+/* The engine's side.  While the ensemble is on, hp_engine_infer_u8(e, frames, n, ..) takes 1 <= n with 2n <= max_batch (HP_ERR_CAPACITY beyond,
+ * the message gives both numbers; hp_engine_max_batch is unchanged): the engine copies the n frames into a buffer of its own, writes their flips
+ * behind them (hp_hflip_u8c3), runs its unchanged schedule on the 2n frames and hp_flip_merge on every output - on the call's stream, inside the
+ * captured graph when graphs are on (hp_engine_set_concurrency(2): flip and merge are launched around the two half-batch graphs, the merge behind
+ * the join).  Afterwards the first n frames of every output are the ensemble (hp_engine_output_to_host(.., n, ..)).  hp_engine_infer_f32 returns
+ * HP_ERR_STATE; hp_engine_calibrate_u8 and hp_engine_profile* run the plain schedule.  The setters copy the tables, synchronise and drop the
+ * captured graphs; every engine output must be listed exactly once (HP_ERR_INVALID otherwise); n_outs == 0 turns the ensemble off, which restores
+ * the engine exactly.  The COCO form needs exactly two outputs (sorted by name: conf with 18 or 19 channels, paf with 38) of equal H x W
+ * (HP_ERR_INVALID, the message says what it found).  Another skeleton: pass its own tables. */
+typedef struct hp_flip_output {
+    int32_t output;           /* index as in hp_engine_output */
+    const int32_t* perm;
+    const int8_t* sign;       /* that output's C entries each */
+} hp_flip_output;
+int hp_engine_set_flip_ensemble(hp_engine* e, const hp_flip_output* outs, int n_outs); /* n_outs == 0: off */
+int hp_engine_set_flip_ensemble_coco(hp_engine* e, int enable);
+int hp_engine_flip_ensemble(const hp_engine* e); /* 0 / 1 */
+
 /* ---- hyperpose::stream on the GPU (reference include/hyperpose/stream/stream.hpp:119-390, src/stream.cpp:60-147): host frames of
  * any size in, humans out, in submission order.  Each submit copies one batch (<= max_batch frames, 8-bit BGR HWC, packed rows) to
  * the device and enqueues resize (keep_ratio = 0: cv::resize; 1: non_scaling_resize + resume_ratio on the way out) -> conv stack ->
@@ -716,6 +761,13 @@ int hp_pipeline_set_tonemap(hp_pipeline* p, const hp_hdr_desc* d);
  * (uw, uh); hp_humans_orient(.., to_stored = 1) takes them to the stored frame for hp_overlay_draw_*).  hp_pipeline_submit_yuv returns HP_ERR_STATE
  * while a non-zero orientation is set, as it does in tiled mode. */
 int hp_pipeline_set_orientation(hp_pipeline* p, int orientation);
+/* Flip ensemble ("flip ensemble" above): enable != 0 turns hp_engine_set_flip_ensemble_coco on for every pipe's engine, 0 turns it off (the default).
+ * HP_ERR_STATE while batches are in flight; HP_ERR_INVALID for a pipeline whose parser is not HP_PARSER_PAF (the message names the kind).  While on,
+ * a submit carries at most max_batch / 2 frames - tiled, max_batch / (2R) frames, and 2R <= max_batch is required by whichever of this call and
+ * hp_pipeline_set_tiling comes second (HP_ERR_CAPACITY).  The flip is taken of the NETWORK-SIZED slot - after resize, letterbox, colour conversion,
+ * tone-map, orientation and tile cut - so the letterbox padding stays where the maps expect it; every submit call works unchanged, the parser runs on
+ * the merged maps and hp_pipeline_collect is unchanged. */
+int hp_pipeline_set_flip_ensemble(hp_pipeline* p, int enable);
 
 #ifdef __cplusplus
 }

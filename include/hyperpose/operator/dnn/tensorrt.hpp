@@ -176,6 +176,17 @@ namespace dnn {
         /// (hp_orient_u8c3_host), bit for bit; regions are in UPRIGHT coordinates (plan them on oriented_size()).  The yuv420_frame overloads
         /// throw std::logic_error while an orientation is set: pass yuv_frames.
         void set_orientation(const orientation& o) { m_orientation = o.code(); }
+        /// Addition: flip ensemble (include/hp_hip.h, "flip ensemble"; hp_engine_set_flip_ensemble_coco).  While on, every inference() call on frames
+        /// or regions runs each network-sized picture and its left-right flip and returns the merged maps: left and right channels swapped back, the
+        /// x component of the part-affinity fields negated, the two sets averaged, on the device.  The batch then holds max_batch_size() / 2 frames or
+        /// regions (the over-size-batch std::logic_error beyond) and the float-buffer overload throws std::logic_error.  COCO PAF networks only: an
+        /// engine with other outputs is a std::logic_error with the C ABI's message (other skeletons: hp_engine_set_flip_ensemble on handle()).
+        void set_flip_ensemble(bool on)
+        {
+            if (hp_engine_set_flip_ensemble_coco(m_engine, on ? 1 : 0) != HP_OK)
+                throw std::logic_error(hp_last_error());
+        }
+        bool flip_ensemble() const { return hp_engine_flip_ensemble(m_engine) == 1; }
         inline cv::Size input_size() noexcept { return m_inp_size; }
 
         /// src/tensorrt.cpp:436-461: every image is brought to the network's size (cv::resize, or non_scaling_resize when keep_ratio)
@@ -183,8 +194,8 @@ namespace dnn {
         std::vector<internal_t> inference(std::vector<cv::Mat> inputs)
         {
             require_calibrated();
-            if (inputs.size() > (size_t)m_max_batch_size)
-                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(inputs.size()) + " Max@" + std::to_string(m_max_batch_size));
+            if (inputs.size() > batch_room())
+                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(inputs.size()) + " Max@" + std::to_string(batch_room()) + overflow_note());
             if (inputs.empty())
                 return {};
             const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
@@ -224,8 +235,8 @@ namespace dnn {
         std::vector<internal_t> inference(const std::vector<yuv420_frame>& inputs)
         {
             require_calibrated();
-            if (inputs.size() > (size_t)m_max_batch_size)
-                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(inputs.size()) + " Max@" + std::to_string(m_max_batch_size));
+            if (inputs.size() > batch_room())
+                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(inputs.size()) + " Max@" + std::to_string(batch_room()) + overflow_note());
             if (inputs.empty())
                 return {};
             const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
@@ -248,8 +259,8 @@ namespace dnn {
         std::vector<internal_t> inference(const std::vector<yuv_frame>& inputs)
         {
             require_calibrated();
-            if (inputs.size() > (size_t)m_max_batch_size)
-                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(inputs.size()) + " Max@" + std::to_string(m_max_batch_size));
+            if (inputs.size() > batch_room())
+                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(inputs.size()) + " Max@" + std::to_string(batch_room()) + overflow_note());
             if (inputs.empty())
                 return {};
             const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
@@ -271,8 +282,8 @@ namespace dnn {
         std::vector<internal_t> inference(const cv::Mat& frame, const std::vector<cv::Rect>& regions)
         {
             require_calibrated();
-            if (regions.size() > (size_t)m_max_batch_size)
-                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(regions.size()) + " Max@" + std::to_string(m_max_batch_size));
+            if (regions.size() > batch_room())
+                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(regions.size()) + " Max@" + std::to_string(batch_room()) + overflow_note());
             if (regions.empty())
                 return {};
             if (frame.empty())
@@ -302,8 +313,8 @@ namespace dnn {
         std::vector<internal_t> inference(const yuv_frame& frame, const std::vector<cv::Rect>& regions)
         {
             require_calibrated();
-            if (regions.size() > (size_t)m_max_batch_size)
-                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(regions.size()) + " Max@" + std::to_string(m_max_batch_size));
+            if (regions.size() > batch_room())
+                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(regions.size()) + " Max@" + std::to_string(batch_room()) + overflow_note());
             if (regions.empty())
                 return {};
             const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
@@ -414,6 +425,8 @@ namespace dnn {
                 throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(batch_size) + " Max@" + std::to_string(m_max_batch_size));
             if (float_buffer.size() < batch_size * 3 * (size_t)m_inp_size.area())
                 throw std::logic_error("Input float buffer is smaller than batch_size x 3 x H x W");
+            if (flip_ensemble())
+                throw std::logic_error("hyperpose::dnn::tensorrt: float buffers are not available while the flip ensemble is on, pass frames");
             require_calibrated();
             retire_last_batch();
             if (hp_engine_infer_f32(m_engine, float_buffer.data(), (int)batch_size, 0, nullptr) != HP_OK)
@@ -438,6 +451,13 @@ namespace dnn {
         }
         hp_engine* handle() { return m_engine; }
         bool keep_ratio() const { return m_keep_ratio; }
+
+        /// frames or regions one inference() call takes: max_batch_size(), half of it while the flip ensemble is on
+        size_t batch_room() const { return (size_t)m_max_batch_size / (flip_ensemble() ? 2 : 1); }
+        std::string overflow_note() const
+        {
+            return flip_ensemble() ? " (max_batch_size " + std::to_string(m_max_batch_size) + " halved: the flip ensemble runs every picture with its flip)" : "";
+        }
 
         void require_calibrated() const
         {

@@ -84,7 +84,8 @@ public:
     {
         const hp_tiling c = t ? t->c_form() : hp_tiling{};
         detail::hp_check(hp_pipeline_set_tiling(m_pl, t ? &c : nullptr));
-        m_max_batch = t ? m_engine_batch / t->regions() : m_engine_batch;
+        m_regions = t ? t->regions() : 1;
+        m_max_batch = m_engine_batch / (m_flip ? 2 : 1) / m_regions;
     }
 
     // hp_pipeline_set_tonemap: 10-bit yuv_frames pushed from now on are PQ / HLG frames (utility/data.hpp, hdr); nullptr turns it off.  Not while
@@ -98,6 +99,16 @@ public:
     // hp_pipeline_set_orientation: frames pushed from now on are STORED frames (utility/data.hpp, orientation) and pop() returns humans normalised to
     // the upright frame.  Not while batches are in flight (std::runtime_error)
     void set_orientation(const orientation& o) { detail::hp_check(hp_pipeline_set_orientation(m_pl, o.code())); }
+
+    // hp_pipeline_set_flip_ensemble: every network-sized slot runs with its left-right flip and the parser reads the merged maps (PAF parsers only);
+    // a push then carries half as many frames.  Not while batches are in flight (std::runtime_error)
+    void set_flip_ensemble(bool on)
+    {
+        detail::hp_check(hp_pipeline_set_flip_ensemble(m_pl, on ? 1 : 0));
+        m_flip = on;
+        m_max_batch = m_engine_batch / (m_flip ? 2 : 1) / m_regions;
+    }
+    bool flip_ensemble() const { return m_flip; }
 
     // one batch (<= max_batch_size frames, any sizes); throws when every pipe is busy
     void push(const std::vector<cv::Mat>& frames)
@@ -152,7 +163,8 @@ private:
     }
     hp_pipeline* m_pl = nullptr;
     std::atomic<int> m_max_batch;
-    int m_engine_batch, m_pipes = 0;
+    int m_engine_batch, m_pipes = 0, m_regions = 1;
+    bool m_flip = false;
     std::atomic<size_t> m_truncated{ 0 };
     std::vector<hp_human> m_out;
     std::vector<int> m_n;
@@ -281,6 +293,11 @@ public:
         m_gpu.set_orientation(o);
         m_orientation = o;
     }
+
+    /// Addition: flip ensemble (include/hp_hip.h, "flip ensemble"; hp_pipeline_set_flip_ensemble): every frame - every tile of it - runs through the
+    /// network with its left-right flip and the PAF parser reads the merged maps; a batch then holds half as many frames.  PAF parsers only
+    /// (std::runtime_error otherwise).  Like the tiling, not while batches are in flight.
+    void set_flip_ensemble(bool on) { m_gpu.set_flip_ensemble(on); }
 
 private:
     struct item {
