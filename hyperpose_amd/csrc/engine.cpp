@@ -14,6 +14,7 @@
 #include "conv_i8.hpp"
 #include "conv_kernels.hpp"
 #include "engine_timeline.hpp"
+#include "graph_cache.hpp"
 #include "hp_common.hpp"
 #include "weight_pack.hpp"
 
@@ -205,7 +206,7 @@ struct hp_engine {
     bool i8_eligible(int layer) const { return !i8_sw[layer].empty(); }
     int check_int8_scales(const float* s, int n, bool allow_uncalibrated) const;
     int apply_int8_scales(); // dq / inv_a of every int8 step from i8_scale; the caller has synchronised and dropped the graphs
-    int drop_graphs();       // synchronise, then forget every captured graph (they hold the launches and arguments of the old schedule)
+    int drop_graphs();       // synchronise the device, then forget every captured graph (they hold the launches and arguments of the old schedule)
     // which engines may run a batch as two half-batches (hp_engine_set_concurrency): the fp32 engines (their steps take a frame offset)
     bool halves_ok() const { return is_f32(); }
     // HP_DTYPE_F32S: a pinned host word the split kernels OR into when an activation exceeds fp16's range (|x| > 65504); once seen
@@ -246,15 +247,12 @@ struct hp_engine {
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 
-    // captured graphs keyed by (n, input pointer, kind)
-    struct graph_key {
-        int n;
-        const void* ptr;
-        int kind;
-        int b0; // first frame of the range the graph covers (hp_engine_set_concurrency(2): one graph per half-batch, launched on its own stream)
-        bool operator<(const graph_key& o) const { return std::tie(n, ptr, kind, b0) < std::tie(o.n, o.ptr, o.kind, o.b0); }
+    // captured graphs keyed by (n, input pointer, kind, first frame): csrc/graph_cache.hpp has the rules of their lifetime
+    using graph_key = hp::graph_key;
+    struct graph_destroy {
+        void operator()(hipGraphExec_t g) const { (void)hipGraphExecDestroy(g); }
     };
-    std::map<graph_key, hipGraphExec_t> graphs;
+    hp::graph_cache<hipGraphExec_t, graph_destroy> graphs;
     bool use_graph = true;
 
     // Flip ensemble (hp_engine_set_flip_ensemble; csrc/flip_ensemble.hpp): one table pair per output while on, empty while off.  A u8 batch of n
@@ -270,10 +268,8 @@ struct hp_engine {
     int flip_stage(const uint8_t* dev_src, int n, hipStream_t s) const;
     int flip_merge(int n, hipStream_t s) const; // hp_flip_merge on every output: frames [0, n) become the ensemble
 
-    ~hp_engine()
+    ~hp_engine() // (hp_engine_destroy has synchronised; `graphs` destroys what it still holds)
     {
-        for (auto& g : graphs)
-            (void)hipGraphExecDestroy(g.second);
         if (ev0)
             (void)hipEventDestroy(ev0);
         if (ev1)
@@ -1636,18 +1632,17 @@ int hp_engine::flip_merge(int n, hipStream_t s) const
     return HP_OK;
 }
 
-int hp_engine::drop_graphs()
+namespace {
+// What the graph cache waits for before it destroys an executable: every stream of the device.  An earlier call may have launched on a
+// caller's stream, and the caller may have destroyed that stream since, so no remembered list of streams can be waited on.
+int sync_device()
 {
-    HP_HIP_TRY(hipStreamSynchronize(stream));
-    if (last.stream)
-        HP_HIP_TRY(hipStreamSynchronize((hipStream_t)last.stream));
-    if (stream2)
-        HP_HIP_TRY(hipStreamSynchronize(stream2));
-    for (auto& g : graphs)
-        (void)hipGraphExecDestroy(g.second);
-    graphs.clear();
+    HP_HIP_TRY(hipDeviceSynchronize());
     return HP_OK;
 }
+} // namespace
+
+int hp_engine::drop_graphs() { return graphs.drop(sync_device); }
 
 namespace {
 // ---- bind(P, n, b0): a copy of a launch's parameters for frames [b0, b0 + n) of the batch: B (and npix, where the struct has it) for n frames,
@@ -2126,8 +2121,7 @@ void hp_engine_destroy(hp_engine* e)
 {
     if (!e)
         return;
-    if (e->stream)
-        (void)hipStreamSynchronize(e->stream);
+    (void)hipDeviceSynchronize(); // (not the engine's stream alone: a captured graph may still be running on a caller's stream)
     delete e;
 }
 
@@ -2219,48 +2213,45 @@ static int infer_common(hp_engine* e, const void* input, size_t frame_bytes, int
         return fl ? e->flip_merge(n / 2, s) : HP_OK; // (two half-batches: behind the join)
     }
 
-    // capture a range's schedule once per (frames, input buffer, first frame); replays cost one launch
-    auto graph_for = [&](int b0, int cnt, hipStream_t cs, hipGraphExec_t* out) -> int {
+    // capture a range's schedule once per (frames, input buffer, first frame); replays cost one launch.  A call names ALL its ranges at once:
+    // the cache decides about eviction before the first capture, so no executable of this call can be destroyed before it is launched
+    // (csrc/graph_cache.hpp), and a call whose keys are cached costs its look-ups.
+    struct range {
+        int b0, cnt;
+        hipStream_t cs;
+    };
+    auto graphs_for = [&](const range* r, int nr, hipGraphExec_t* out) -> int {
         // (a one-stream ensemble graph holds the copy from the caller's device buffer: keyed by that pointer; the half-batch graphs read flip_in
         // alone - flip and merge are launched around them - and are keyed by it; both apart from the plain graphs by kind)
-        const hp_engine::graph_key key{ cnt, fl_src && !halves ? (const void*)fl_src : dev_in, fl ? 2 : kind, b0 };
-        auto it = e->graphs.find(key);
-        if (it == e->graphs.end()) {
+        hp_engine::graph_key keys[2];
+        for (int i = 0; i < nr; ++i)
+            keys[i] = hp_engine::graph_key{ r[i].cnt, fl_src && !halves ? (const void*)fl_src : dev_in, fl ? 2 : kind, r[i].b0 };
+        auto capture = [&](int i, hipGraphExec_t* exec) -> int {
             hipGraph_t graph = nullptr;
-            HP_HIP_TRY(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-            const int rc = staged(u8, f32, b0, cnt, cs);
-            const hipError_t ee = hipStreamEndCapture(cs, &graph);
+            HP_HIP_TRY(hipStreamBeginCapture(r[i].cs, hipStreamCaptureModeThreadLocal));
+            const int rc = staged(u8, f32, r[i].b0, r[i].cnt, r[i].cs);
+            const hipError_t ee = hipStreamEndCapture(r[i].cs, &graph);
             if (rc != HP_OK) {
                 if (graph)
                     (void)hipGraphDestroy(graph);
                 return rc;
             }
             HP_HIP_TRY(ee);
-            hipGraphExec_t exec = nullptr;
-            const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+            const hipError_t ie = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
             (void)hipGraphDestroy(graph);
             HP_HIP_TRY(ie);
-            if (e->graphs.size() > 64) { // bound the cache for callers that pass a fresh pointer every time
-                (void)hipStreamSynchronize(s); // earlier launches of these executables may still be running on this stream ...
-                (void)hipStreamSynchronize(e->stream); // ... or on the engine's own
-                if (e->stream2)
-                    (void)hipStreamSynchronize(e->stream2);
-                for (auto& g : e->graphs)
-                    (void)hipGraphExecDestroy(g.second);
-                e->graphs.clear();
-            }
-            it = e->graphs.emplace(key, exec).first;
-        }
-        *out = it->second;
-        return HP_OK;
+            return HP_OK;
+        };
+        return e->graphs.acquire(keys, nr, out, capture, sync_device);
     };
     if (halves) {
         // two half-batches side by side (hp_engine::enqueue has the reasoning): ONE graph with two branches is replayed branch after branch by
         // the runtime (measured: 2.27 -> 2.22 ms per call), two graphs on two streams run side by side (the probe's 2.49 -> 1.96 ms)
         const int n0 = (n + 1) / 2;
-        hipGraphExec_t ga = nullptr, gb = nullptr;
-        HP_TRY(graph_for(0, n0, s, &ga));
-        HP_TRY(graph_for(n0, n - n0, e->stream2, &gb));
+        const range both[2] = { { 0, n0, s }, { n0, n - n0, e->stream2 } };
+        hipGraphExec_t g2[2] = { nullptr, nullptr };
+        HP_TRY(graphs_for(both, 2, g2));
+        const hipGraphExec_t ga = g2[0], gb = g2[1];
         if (fl) // the frames are the first half-batch, their flips the second: written before the fork, merged behind the join
             HP_TRY(e->flip_stage(fl_src, n0, s));
         HP_HIP_TRY(hipEventRecord(e->ev_fork, s));
@@ -2276,8 +2267,9 @@ static int infer_common(hp_engine* e, const void* input, size_t frame_bytes, int
         HP_HIP_TRY(hipStreamWaitEvent(s, e->ev_join, 0));
         return fl ? e->flip_merge(n0, s) : HP_OK;
     }
+    const range whole{ 0, n, s };
     hipGraphExec_t g = nullptr;
-    HP_TRY(graph_for(0, n, s, &g));
+    HP_TRY(graphs_for(&whole, 1, &g));
     HP_HIP_TRY(hipGraphLaunch(g, s));
     return HP_OK;
 }
@@ -2445,6 +2437,8 @@ int hp_engine_set_concurrency(hp_engine* e, int parts)
 }
 
 int hp_engine_concurrency(const hp_engine* e) { return e ? e->parts : HP_ERR_INVALID; }
+
+int hp_engine_cached_graphs(const hp_engine* e) { return e ? (int)e->graphs.size() : HP_ERR_INVALID; }
 
 int hp_engine_set_graph(hp_engine* e, int enable)
 {

@@ -288,6 +288,11 @@ class Engine:
     def concurrency(self) -> int:
         return int(lib().hp_engine_concurrency(self._h))
 
+    @property
+    def cached_graphs(self) -> int:
+        """Captured graphs the engine holds now (hp_engine_cached_graphs): at most 64, one per (frames, input pointer, entry, first frame)."""
+        return int(check(lib().hp_engine_cached_graphs(self._h)))
+
     def enqueue_u8(self, dev_frames, n: int, stream=None):
         check(lib().hp_engine_infer_u8(self._h, as_ptr(dev_frames), n, 1, C.c_void_p(stream) if stream else None))
 

@@ -558,6 +558,16 @@ int hp_engine_infer_f32(hp_engine* e, const float* nchw, int n, int on_device, v
 int hp_engine_synchronize(hp_engine* e);
 void* hp_engine_stream(hp_engine* e); /* hipStream_t of the engine */
 int hp_engine_set_graph(hp_engine* e, int enable); /* replay the schedule from a captured hipGraph (default on) */
+/* The captured graphs are cached per (frames of the call, input pointer, u8 / f32 entry, first frame): a host batch is keyed by the engine's
+ * staging buffer, a device batch by the caller's pointer; with hp_engine_set_concurrency(2) a batch holds two entries, one per half.  The cache
+ * holds at most HP_ENGINE_GRAPH_CACHE_BOUND entries.  A call whose graphs are cached costs its look-ups and the launches.  A call that needs a
+ * capture that no longer fits empties the cache first: ONE hipDeviceSynchronize() (every stream of the device, the caller's included), then the
+ * call's captures, and afterwards one capture for every other (frames, pointer) the caller comes back to.  A caller that cycles more device
+ * buffers than the bound / 2 (two halves) or the bound pays that on every round; one that stays below never does.  Changing a setting that
+ * changes the schedule (concurrency, flip ensemble, int8 scales, calibration) empties the cache in the same way; hp_engine_set_graph keeps it.
+ * hp_engine_cached_graphs: the number of entries now. */
+#define HP_ENGINE_GRAPH_CACHE_BOUND 64
+int hp_engine_cached_graphs(const hp_engine* e);
 /* parts = 2: every batch of >= 2 frames runs as two half-batches side by side, the second on an internal stream that forks from and joins the
  * call's stream (HP_DTYPE_F32 / F32S engines; an fp16 engine keeps one stream and hp_engine_concurrency() says so) - for a caller that keeps ONE batch in flight, as the reference's synchronous
  * tensorrt::inference does (src/tensorrt.cpp:364-434): the two halves fill each other's idle phases.  Outputs are bit-identical to parts = 1.
