@@ -16,12 +16,15 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace hp {
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) float gfloat; // global memory, said to the compiler
+typedef __attribute__((address_space(1))) f32x4 gf32x4;
 
 __device__ __forceinline__ float act32(float v, int act, float param, float alpha)
 {
@@ -94,6 +97,11 @@ __global__ __launch_bounds__(256) void conv32_kernel(const conv32_params p)
     const int lrow = tid >> 2, lchunk = (tid & 3) * 4;
     const int OHW = p.OH * p.OW, kc = p.Cin / BK, steps = p.KH * p.KW * kc;
 
+    int dbg_i = 0;
+#define HP_STAMP()                                       \
+    if (p.dbg && blockIdx.x == 9 && tid == 0)            \
+        p.dbg[dbg_i++] = __builtin_amdgcn_s_memtime();
+    HP_STAMP();
     long bbase[NB];
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
@@ -136,11 +144,6 @@ __global__ __launch_bounds__(256) void conv32_kernel(const conv32_params p)
                 acc[i][j][r] = 0.f;
 
     const int frow = lane & 31, fh = (lane >> 5) * 4;
-    int dbg_i = 0;
-#define HP_STAMP()                                       \
-    if (p.dbg && blockIdx.x == 9 && tid == 0)            \
-        p.dbg[dbg_i++] = __builtin_amdgcn_s_memtime();
-    HP_STAMP();
     // block residency trace: [128 + 3 b] = start, [.. + 1] = end (100 MHz clock), [.. + 2] = XCC_ID << 32 | HW_ID of block b < 4096
     if (p.dbg && tid == 0 && blockIdx.x < 4096) {
         p.dbg[128 + 3 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
@@ -183,6 +186,9 @@ __global__ __launch_bounds__(256) void conv32_kernel(const conv32_params p)
         // NHWC output only (every layer but the network's heads): row-major through a private LDS slab (conv32_epilogue.hpp)
         lds_barrier(); // every wavefront is done with the last K-step's tiles the slabs lie over
         float* const slab = reinterpret_cast<float*>(lds_raw) + wave * (rows_geom<TM>::SLAB_BYTES / 4);
+        // pixel -> (image, row, column): ONE division pair for the lane's first slab row, carried from one pixel() call to the next (ascending pixels)
+        int pn = min(n0 + wn * TN * 32 + lane / rows_geom<TM>::LPR, p.npix - 1), pb = pn / OHW;
+        int poy = (pn - pb * OHW) / p.OW, pox = pn - pb * OHW - poy * p.OW;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             floatx16 fin[TM];
@@ -191,14 +197,17 @@ __global__ __launch_bounds__(256) void conv32_kernel(const conv32_params p)
                 fin[i] = acc[i][j];
             const int nb = n0 + (wn * TN + j) * 32;
             conv32_store_rows<TM>(p, fin, slab, lane, m0 + wm * TM * 32, [&](int r, bool& ok, long& ooff, long& roff) {
-                const int n = nb + r;
+                const int n = nb + r, nc = min(n, p.npix - 1);
                 ok = n < p.npix;
-                const int nc = min(n, p.npix - 1);
-                const int b = nc / OHW, rem = nc - b * OHW;
-                const int oy = rem / p.OW, ox = rem - oy * p.OW;
-                ooff = tv32_off(p.out, b, oy, ox);
-                roff = p.res.p ? tv32_off(p.res, b, oy, ox) : 0;
-            });
+                pox += nc - pn, pn = nc;
+                while (pox >= p.OW) {
+                    pox -= p.OW;
+                    if (++poy == p.OH)
+                        poy = 0, ++pb;
+                }
+                ooff = tv32_off(p.out, pb, poy, pox);
+                roff = p.res.p ? tv32_off(p.res, pb, poy, pox) : 0;
+            }, [&]() { HP_STAMP(); });
         }
     } else {
     // the network's heads (fp32 NCHW for the parsers, runs along x): lane (n, h) of a 32 x 32 tile holds rows (r & 3) + 8 (r >> 2) + 4 h of
@@ -294,7 +303,7 @@ __global__ __launch_bounds__(256) void conv32_kernel(const conv32_params p)
 // any multiple of 16 pixels per block, e.g. 176: OpenPose-VGG19's 7 x 7 layers at 16 x 54 x 96 are 1 296 tiles of 64 x 128, 1 038 of 64 x 160 - 14 more
 // than the chip's 1 024 slots - and 944 of 64 x 176: one round).
 template <int BN, int WN = 2>
-__global__ __launch_bounds__(256) void conv32_t16_kernel(const conv32_params p)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv32_t16_kernel(const conv32_params p)
 {
     constexpr int BM = 64, BK = 16, WM = 4 / WN, TMW = BM / 16 / WM, TNW = BN / WN / 16; // a wavefront: TMW x TNW tiles of 16 x 16
     constexpr int NB = (BN + 63) / 64, BR = NB * 64;             // staging passes of the B tile (64 rows each); rows allocated
@@ -314,6 +323,11 @@ __global__ __launch_bounds__(256) void conv32_t16_kernel(const conv32_params p)
     const int OHW = p.OH * p.OW, kc = p.Cin / BK, steps = p.KH * p.KW * kc;
     auto swz = [](int row, int quad) { return row * BK + ((quad ^ (((row >> 3) & 1) << 1)) << 2); };
 
+    int dbg_i = 0;
+#define HP_STAMP()                                       \
+    if (p.dbg && blockIdx.x == 9 && tid == 0)            \
+        p.dbg[dbg_i++] = __builtin_amdgcn_s_memtime();
+    HP_STAMP();
     long bbase[NB];
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
@@ -348,11 +362,6 @@ __global__ __launch_bounds__(256) void conv32_t16_kernel(const conv32_params p)
             acc[i][j] = f32x4{ 0.f, 0.f, 0.f, 0.f };
 
     const int fr = lane & 15, kq = lane >> 4;
-    int dbg_i = 0;
-#define HP_STAMP()                                       \
-    if (p.dbg && blockIdx.x == 9 && tid == 0)            \
-        p.dbg[dbg_i++] = __builtin_amdgcn_s_memtime();
-    HP_STAMP();
     // block residency trace: [128 + 3 b] = start, [.. + 1] = end (100 MHz clock), [.. + 2] = XCC_ID << 32 | HW_ID of block b < 4096
     if (p.dbg && tid == 0 && blockIdx.x < 4096) {
         p.dbg[128 + 3 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
@@ -385,73 +394,136 @@ __global__ __launch_bounds__(256) void conv32_t16_kernel(const conv32_params p)
             HP_STAMP();
     }
 
-    // epilogue: lane (n, q) of tile (i, j) holds channels m0 + wm * 16 TMW + i * 16 + 4 q + {0..3} of pixel n0 + wn * BN / WN + j * 16 + n
+    // epilogue: lane (n, q) of tile (i, j) holds channels m0 + wm * 16 TMW + i * 16 + 4 q + {0..3} of pixel n0 + wn * BN / WN + j * 16 + n.
+    // In the form of conv32_winograd_kernel's drain: the staging registers and the fragments are dead here, their registers
+    // hold the epilogue's inputs.  Pixel -> offsets once per lane: ONE division pair for the lane's first pixel, carries for the tiles behind it
+    // (16 pixels apart).  A pixel past npix keeps the offsets of the tile before it (the first: of pixel npix - 1), a channel quad past Cout reads
+    // channel 0: addresses that valid lanes of the launch read, so every lane loads and no branch that depends on the lane lies between the
+    // first request and the last (a divergent branch is a join at which hipcc waits for every load in flight).
     const int q = lane >> 4;
-    const bool out_vec = p.out.p && ((p.out.coff | p.out.cs) & 3) == 0;
-    const bool res_vec = p.res.p && ((p.res.coff | p.res.cs) & 3) == 0;
+    const bool quads = (p.Cout & 3) == 0; // then a lane's quad is all or nothing
+    const bool out_vec = quads && ((p.out.coff | p.out.cs) & 3) == 0, res_vec = quads && ((p.res.coff | p.res.cs) & 3) == 0;
     const bool res_pre = p.res.p && p.res_before_act, res_post = p.res.p && !p.res_before_act;
-    f32x4 bs[TMW], sl[TMW];
+    const gfloat* const gres = (const gfloat*)p.res.p;
+    gfloat* const gout = (gfloat*)p.out.p;
+    int opix[TNW], rpix[TNW]; // the pixel's index in p.out / p.res (images of t.img pixels, rows of t.wp)
+    bool pok[TNW];
+    {
+        const int n = n0 + wn * (BN / WN) + fr, nc = min(n, p.npix - 1);
+        int b = nc / OHW;
+        const int rem = nc - b * OHW;
+        int oy = rem / p.OW, ox = rem - oy * p.OW;
+        pok[0] = n < p.npix;
+        opix[0] = b * p.out.img + oy * p.out.wp + ox;
+        rpix[0] = b * p.res.img + oy * p.res.wp + ox;
 #pragma unroll
-    for (int i = 0; i < TMW; ++i) {
-        const int m = m0 + wm * (16 * TMW) + i * 16 + 4 * q; // (m + 3 < Cout_pad)
-        bs[i] = *reinterpret_cast<const f32x4*>(p.bias + m);
-        sl[i] = f32x4{ p.act_slope, p.act_slope, p.act_slope, p.act_slope };
-        if (p.alpha)
-            sl[i] = *reinterpret_cast<const f32x4*>(p.alpha + m);
+        for (int j = 1; j < TNW; ++j) {
+            pok[j] = n + 16 * j < p.npix;
+            ox += 16;
+            while (ox >= p.OW) { // (once where the map is 16 pixels wide or more)
+                ox -= p.OW;
+                if (++oy == p.OH)
+                    oy = 0, ++b;
+            }
+            opix[j] = pok[j] ? b * p.out.img + oy * p.out.wp + ox : opix[j - 1];
+            rpix[j] = pok[j] ? b * p.res.img + oy * p.res.wp + ox : rpix[j - 1];
+        }
     }
+    int mch[TMW];
+    bool many[TMW];
 #pragma unroll
-    for (int j = 0; j < TNW; ++j) {
-        const int n = n0 + wn * (BN / WN) + j * 16 + fr;
-        const bool pix_ok = n < p.npix;
-        const int nc = min(n, p.npix - 1);
-        const int b = nc / OHW, rem = nc - b * OHW;
-        const int oy = rem / p.OW, ox = rem - oy * p.OW;
-        const long ooff = p.out.p ? tv32_off(p.out, b, oy, ox) : 0;
-        const long roff = p.res.p ? tv32_off(p.res, b, oy, ox) : 0;
+    for (int i = 0; i < TMW; ++i)
+        mch[i] = m0 + wm * (16 * TMW) + i * 16 + 4 * q, many[i] = mch[i] < p.Cout; // (mch + 3 < Cout_pad)
+    f32x4 bs[TMW], sl[TMW];
+    // Tiles [J0, J1) of the wavefront: the residual quads of all of them requested at once, then the arithmetic of all (per element as before:
+    // bias, residual before or after the activation, clamp or slope), then the stores back to back.  <160, 2>: all 2 x 5 tiles in one go;
+    // <176, 1> (1 x 11 tiles; forced selections only): two groups, for the registers that four blocks per CU leave.
+    constexpr int GJ = TMW * TNW <= 10 ? TNW : (TNW + 1) / 2;
+    auto drain = [&](auto J0c, auto J1c) {
+        constexpr int J0 = decltype(J0c)::value, J1 = decltype(J1c)::value;
+        HP_STAMP();
+        f32x4 rr[TMW][GJ];
 #pragma unroll
-        for (int i = 0; i < TMW; ++i) {
-            const int m = m0 + wm * (16 * TMW) + i * 16 + 4 * q;
-            if (!pix_ok || m >= p.Cout)
-                continue;
-            const bool full = m + 3 < p.Cout;
-            float v[4], rr[4] = { 0.f, 0.f, 0.f, 0.f };
-            if (p.res.p) {
-                if (full && res_vec) {
-                    const f32x4 t = *reinterpret_cast<const f32x4*>(p.res.p + roff + m);
-                    rr[0] = t[0], rr[1] = t[1], rr[2] = t[2], rr[3] = t[3];
-                } else {
+        for (int i = 0; i < TMW; ++i)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (m + e < p.Cout)
-                            rr[e] = p.res.p[roff + m + e];
+            for (int j = J0; j < J1; ++j)
+                rr[i][j - J0] = f32x4{ 0.f, 0.f, 0.f, 0.f };
+        if (gres) {
+            if (res_vec) {
+#pragma unroll
+                for (int j = J0; j < J1; ++j)
+#pragma unroll
+                    for (int i = 0; i < TMW; ++i)
+                        rr[i][j - J0] = *reinterpret_cast<const gf32x4*>(gres + ((long)rpix[j] * p.res.cs + p.res.coff + (many[i] ? mch[i] : 0)));
+            } else {
+#pragma unroll
+                for (int j = J0; j < J1; ++j)
+#pragma unroll
+                    for (int i = 0; i < TMW; ++i)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) // (channels past Cout: a re-read of the last one, never stored)
+                            rr[i][j - J0][e] = gres[(long)rpix[j] * p.res.cs + p.res.coff + min(mch[i] + e, p.Cout - 1)];
+            }
+        }
+        if constexpr (J0 == 0) {
+#pragma unroll
+            for (int i = 0; i < TMW; ++i) {
+                bs[i] = *(const gf32x4*)(p.bias + mch[i]);
+                sl[i] = f32x4{ p.act_slope, p.act_slope, p.act_slope, p.act_slope };
+                if (p.alpha)
+                    sl[i] = *(const gf32x4*)(p.alpha + mch[i]);
+            }
+        }
+        HP_STAMP();
+#pragma unroll
+        for (int i = 0; i < TMW; ++i)
+#pragma unroll
+            for (int j = J0; j < J1; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float x = acc[i][j][e] + bs[i][e];
+                    if (res_pre)
+                        x += rr[i][j - J0][e];
+                    x = x > 0.f ? fminf(x, p.act_hi) : x * sl[i][e];
+                    if (res_post)
+                        x += rr[i][j - J0][e];
+                    acc[i][j][e] = x;
                 }
-            }
+        HP_STAMP();
+        if (gout) {
+            if (out_vec) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float x = acc[i][j][e] + bs[i][e];
-                if (res_pre)
-                    x += rr[e];
-                x = x > 0.f ? fminf(x, p.act_hi) : x * sl[i][e];
-                if (res_post)
-                    x += rr[e];
-                v[e] = x;
-            }
-            if (p.out.p) {
-                if (full && out_vec)
-                    *reinterpret_cast<f32x4*>(p.out.p + ooff + m) = f32x4{ v[0], v[1], v[2], v[3] };
-                else {
+                for (int j = J0; j < J1; ++j)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (m + e < p.Cout)
-                            p.out.p[ooff + m + e] = v[e];
-                }
+                    for (int i = 0; i < TMW; ++i)
+                        if (pok[j] && many[i])
+                            *reinterpret_cast<gf32x4*>(gout + ((long)opix[j] * p.out.cs + p.out.coff + mch[i])) = acc[i][j];
+            } else {
+#pragma unroll
+                for (int j = J0; j < J1; ++j)
+#pragma unroll
+                    for (int i = 0; i < TMW; ++i)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (pok[j] && mch[i] + e < p.Cout)
+                                gout[(long)opix[j] * p.out.cs + p.out.coff + mch[i] + e] = acc[i][j][e];
             }
-            if (p.out_f32) {
+        }
+    };
+    drain(std::integral_constant<int, 0>{}, std::integral_constant<int, GJ>{});
+    if constexpr (GJ < TNW)
+        drain(std::integral_constant<int, GJ>{}, std::integral_constant<int, TNW>{});
+    if (p.out_f32) { // the network's fp32 NCHW output (a head on this tile: forced selections only): the pixel's image and index once more
+#pragma unroll
+        for (int j = 0; j < TNW; ++j) {
+            const int n = n0 + wn * (BN / WN) + j * 16 + fr, nc = min(n, p.npix - 1);
+            const int b = nc / OHW, rem = nc - b * OHW;
+#pragma unroll
+            for (int i = 0; i < TMW; ++i)
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (m + e < p.Cout)
-                        p.out_f32[((long)b * p.Cout + m + e) * OHW + rem] = v[e];
-            }
+                    if (pok[j] && mch[i] + e < p.Cout)
+                        p.out_f32[((long)b * p.Cout + mch[i] + e) * OHW + rem] = acc[i][j][e];
         }
     }
     HP_STAMP();
