@@ -5,18 +5,32 @@
 // (paf_parser.hip) are enqueued back to back on ONE HIP stream of one of `n_pipes` engine+parser pairs, and only the
 // humans come back.  Several batches are in flight (one per pipe); results are returned in submission order, like the
 // reference's queues.  resume_ratio is applied on the way out when the aspect ratio was kept.
-// Frames arrive as 8-bit BGR (hp_pipeline_submit) or as YUV 4:2:0 video frames (hp_pipeline_submit_yuv: half the bytes over PCIe, colour
-// conversion fused into the resize, resize_yuv.hip) or as hp_yuv_image descriptions of any layout, in host or in device memory
-// (hp_pipeline_submit_yuv_images, resize_yuv_formats.hip); all end in infer_and_parse().
-// Tiled mode (hp_pipeline_set_tiling): a frame becomes its R regions in R consecutive slots of the batch - one hp_resize_rois_* call per
-// frame (resize_rois.hip) instead of the per-frame resize - and hp_pipeline_collect maps every region's humans back to the frame and
-// merges them (tiles.cpp).  The BGR and the hp_yuv_image submit have a tiled twin below; with tiling off nothing of this runs.
-// HDR input (hp_pipeline_set_tonemap): while set, the P010 / I010 frames of hp_pipeline_submit_yuv_images take the *_hdr twin of their resize call
-// (resize_yuv_hdr.hip); nothing else changes, and 8-bit frames of the same batch go the SDR way.
-// Upright input (hp_pipeline_set_orientation): while a non-zero code is set the submitted frames are STORED frames; every resize call above is replaced by
-// its oriented twin (resize_oriented.hip), and everything after it - letterbox, tiles, resume_ratio, the merge - sees the upright uw x uh frame.
+//
+// One road from a submitted frame to its network slot.  Frames arrive as 8-bit BGR (hp_pipeline_submit), as YUV 4:2:0 buffers (hp_pipeline_submit_yuv)
+// or as hp_yuv_image descriptions of any layout, in host or in device memory (hp_pipeline_submit_yuv_images); every submit is
+//     admit()            n frames of R slots each fit a batch and a pipe is free (R = 1, or the regions of a frame in tiled mode)
+//     check and plan     EVERY frame is checked, and plan_frame() has its upright size and its R regions, before the first copy is enqueued:
+//                        a refused batch leaves nothing in the stream
+//     upload             upload_blob() (a contiguous host blob -> p.raw at 256-byte offsets, through p.stage unless pinned) or upload_yuv_images()
+//                        (planes packed tightly); all copies first, then all kernels: the stream changes between the copy engine and the
+//                        compute queue once per batch, not once per frame
+//     one resize call    per frame, and always the general one: hp_resize_oriented_u8c3 / hp_resize_oriented_yuv, in tiled mode
+//                        hp_resize_rois_oriented_u8c3 / hp_resize_rois_oriented_yuv, with the pipeline's orientation, the frame's tone-map (or null)
+//                        and keep_ratio.  Which kernel runs is decided inside those four calls (resize_oriented.hip) and nowhere here: orientation 0
+//                        forwards to the un-oriented call, a null tone-map is the SDR call
+//     infer_and_parse()  conv stack, parser, and the pipe joins the ring
+// The settings only feed that road.  Tiled mode (hp_pipeline_set_tiling): a frame becomes its R regions in R consecutive slots, and hp_pipeline_collect
+// maps every region's humans back to the frame and merges them (tiles.cpp).  HDR input (hp_pipeline_set_tonemap): the P010 / I010 frames of
+// hp_pipeline_submit_yuv_images get the tone-map, 8-bit frames of the same batch get null.  Upright input (hp_pipeline_set_orientation): the submitted
+// frames are STORED frames, and everything behind the resize - letterbox, tiles, resume_ratio, the merge - sees the upright uw x uh frame of plan_frame().
 // Flip ensemble (hp_pipeline_set_flip_ensemble): every pipe's engine runs each network-sized slot and its left-right flip and merges the maps
 // (flip_ensemble.hip) before the parser reads them; here only the capacity changes: a batch holds pl->capacity() = max_batch / 2 slots.
+// Three things leave the road on purpose:
+//     (a) an untiled, un-oriented BGR frame of the network's size needs no kernel: it is copied straight into its slot of p.net, and a run of such
+//         frames that is contiguous in pinned host memory goes in ONE copy (the benchmark's path)
+//     (b) hp_pipeline_submit_yuv keeps the 4:2:0 kernel of its own (hp_resize_yuv420 / hp_letterbox_yuv420, resize_yuv.hip) and is refused in tiled and
+//         in oriented mode
+//     (c) all copies first, then all kernels, within a batch - also where (a) mixes direct and resized frames
 #include "hp_common.hpp"
 #include "yuv_formats.hpp"
 
@@ -90,12 +104,55 @@ struct hp_pipeline {
 };
 
 namespace {
+
 int infer_and_parse(hp_pipeline* pl, pipe_t& p, int n);
-int submit_tiled(hp_pipeline* pl, const uint8_t* const* frames, const int* widths, const int* heights, int n);
-int submit_tiled_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, int n, int on_device);
 int collect_tiled(hp_pipeline* pl, pipe_t& p, hp_human* out, int cap_per_frame, int* n_out, int* n_frames);
-int upload_yuv_images(hp_pipeline* pl, pipe_t& p, const hp_yuv_image* frames, int n, std::vector<hp_yuv_image>& dev);
+int upload_yuv_images(pipe_t& p, const hp_yuv_image* frames, int n, std::vector<hp_yuv_image>& dev);
+
+// network-sized slots a frame takes: its regions in tiled mode, one otherwise
+int tiled_regions(const hp_pipeline* pl) { return pl->tiled ? pl->tiling.cols * pl->tiling.rows + pl->tiling.with_full : 1; }
+
+// what every submit checks first: n frames of R slots each fit a batch, and a pipe is free
+int admit(const hp_pipeline* pl, const char* who, int n)
+{
+    const int R = tiled_regions(pl);
+    if (pl->tiled)
+        HP_REQUIRE(n >= 1 && n <= pl->capacity() / R, HP_ERR_CAPACITY, "%s: %d frames of %d regions each > max_batch %d%s (at most %d frames per submit)", who, n,
+            R, pl->max_batch, pl->flip_note(), pl->capacity() / R);
+    else
+        HP_REQUIRE(n >= 1 && n <= pl->capacity(), HP_ERR_CAPACITY, "%s: batch %d > max_batch %d%s", who, n, pl->max_batch, pl->flip_note());
+    HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "%s: all %d pipes are busy, collect first", who, pl->n_pipes);
+    return HP_OK;
 }
+
+// Frame i of a batch as everything behind its resize sees it: the upright size in p.w / p.h and, in tiled mode, its R regions in p.roi, planned on
+// the upright frame.  (ax, ay) is the stored layout's region alignment; behind a quarter turn the upright x axis is the stored y axis.
+int plan_frame(const hp_pipeline* pl, pipe_t& p, int i, int sw, int sh, int ax, int ay)
+{
+    HP_TRY(hp_oriented_size(pl->orientation, sw, sh, &p.w[i], &p.h[i]));
+    if (!pl->tiled)
+        return HP_OK;
+    if (pl->orientation & 1)
+        std::swap(ax, ay);
+    const int R = tiled_regions(pl), rc = hp_tile_plan(&pl->tiling, p.w[i], p.h[i], ax, ay, &p.roi[(size_t)i * R], R);
+    return rc < 0 ? rc : HP_OK;
+}
+
+// One contiguous host blob -> the device, enqueued on p.s: from where it lies when it is pinned, through p.stage otherwise; to `dst`, or (null) to
+// p.raw.  `off` is the batch's running offset into p.stage and p.raw, a multiple of 256: it moves on when either slot is in use until the copy has run.
+int upload_blob(pipe_t& p, const uint8_t* src, size_t bytes, bool pinned, uint8_t* dst, size_t& off)
+{
+    if (!pinned) {
+        memcpy(p.stage.as<uint8_t>() + off, src, bytes);
+        src = p.stage.as<uint8_t>() + off;
+    }
+    HP_HIP_TRY(hipMemcpyAsync(dst ? dst : p.raw.as<uint8_t>() + off, src, bytes, hipMemcpyHostToDevice, p.s));
+    if (!dst || !pinned)
+        off += (bytes + 255) & ~(size_t)255;
+    return HP_OK;
+}
+
+} // namespace
 
 extern "C" {
 
@@ -210,7 +267,7 @@ int hp_pipeline_set_flip_ensemble(hp_pipeline* pl, int enable)
         kinds[pl->kind]);
     if (enable) {
         HP_REQUIRE(pl->max_batch >= 2, HP_ERR_CAPACITY, "hp_pipeline_set_flip_ensemble: max_batch %d has no room for a frame and its flip", pl->max_batch);
-        const int R = pl->tiling.cols * pl->tiling.rows + pl->tiling.with_full;
+        const int R = tiled_regions(pl);
         HP_REQUIRE(!pl->tiled || 2 * R <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_set_flip_ensemble: %d regions per frame (tiling is on) and their flips > max_batch %d", R,
             pl->max_batch);
     }
@@ -229,62 +286,48 @@ int hp_pipeline_set_flip_ensemble(hp_pipeline* pl, int enable)
 int hp_pipeline_submit(hp_pipeline* pl, const uint8_t* const* frames, const int* widths, const int* heights, int n)
 {
     HP_REQUIRE(pl && frames && widths && heights, HP_ERR_INVALID, "hp_pipeline_submit: null argument");
-    if (pl->tiled)
-        return submit_tiled(pl, frames, widths, heights, n);
-    HP_REQUIRE(n >= 1 && n <= pl->capacity(), HP_ERR_CAPACITY, "hp_pipeline_submit: batch %d > max_batch %d%s", n, pl->max_batch, pl->flip_note());
-    HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "hp_pipeline_submit: all %d pipes are busy, collect first", pl->n_pipes);
+    HP_TRY(admit(pl, "hp_pipeline_submit", n));
     pipe_t& p = pl->pipes[pl->head];
+    const int R = tiled_regions(pl);
     const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
+    std::vector<char> direct(n, 0);
+    for (int i = 0; i < n; ++i) { // everything is checked before the first copy is enqueued
+        HP_REQUIRE(frames[i] && widths[i] > 0 && heights[i] > 0, HP_ERR_INVALID, "hp_pipeline_submit: frame %d is empty", i);
+        HP_REQUIRE((size_t)widths[i] * heights[i] * 3 <= pl->max_frame_bytes, HP_ERR_CAPACITY, "hp_pipeline_submit: frame %d (%dx%d) exceeds max_frame_bytes %zu", i,
+            widths[i], heights[i], pl->max_frame_bytes);
+        HP_TRY(plan_frame(pl, p, i, widths[i], heights[i], 1, 1));
+        // (a) a frame that already has the network's size needs no geometry: cv::resize to the same size is a copy (src/tensorrt.cpp:446-451)
+        // and non_scaling_resize at ratio 1 fills the whole target (src/data.cpp:53-69) -> H2D straight into the network's input slot
+        // (a stored frame that is turned or mirrored always goes through the oriented kernel, a tiled frame through the regions kernel)
+        direct[i] = !pl->tiled && widths[i] == pl->in_w && heights[i] == pl->in_h && pl->orientation == HP_ORIENT_NONE;
+    }
     size_t off = 0;
     std::vector<size_t> offs(n);
-    std::vector<char> direct(n, 0);
     for (int i = 0; i < n; ++i) {
-        HP_REQUIRE(frames[i] && widths[i] > 0 && heights[i] > 0, HP_ERR_INVALID, "hp_pipeline_submit: frame %d is empty", i);
-        const size_t bytes = (size_t)widths[i] * heights[i] * 3;
-        HP_REQUIRE(bytes <= pl->max_frame_bytes, HP_ERR_CAPACITY, "hp_pipeline_submit: frame %d (%dx%d) exceeds max_frame_bytes %zu", i,
-            widths[i], heights[i], pl->max_frame_bytes);
-        offs[i] = off;
         const bool pinned = is_pinned(frames[i]);
-        const uint8_t* src = frames[i];
-        if (!pinned) {
-            memcpy(p.stage.as<uint8_t>() + off, frames[i], bytes);
-            src = p.stage.as<uint8_t>() + off;
-        }
-        // a frame that already has the network's size needs no geometry: cv::resize to the same size is a copy (src/tensorrt.cpp:446-451)
-        // and non_scaling_resize at ratio 1 fills the whole target (src/data.cpp:53-69) -> H2D straight into the network's input slot
-        // (a stored frame that is turned or mirrored always goes through the oriented kernel)
-        direct[i] = widths[i] == pl->in_w && heights[i] == pl->in_h && pl->orientation == HP_ORIENT_NONE;
-        uint8_t* dst = direct[i] ? p.net.as<uint8_t>() + (size_t)i * net_frame : p.raw.as<uint8_t>() + off;
-        // consecutive network-sized frames that are also consecutive in (pinned) host memory go in ONE copy
-        int run = 1;
-        if (direct[i] && pinned)
-            while (i + run < n && widths[i + run] == pl->in_w && heights[i + run] == pl->in_h && frames[i + run] == frames[i] + (size_t)run * net_frame)
+        uint8_t* slot = p.net.as<uint8_t>() + (size_t)i * net_frame;
+        if (direct[i] && pinned) { // consecutive network-sized frames that are also consecutive in (pinned) host memory go in ONE copy
+            int run = 1;
+            while (i + run < n && direct[i + run] && frames[i + run] == frames[i] + (size_t)run * net_frame)
                 ++run;
-        HP_HIP_TRY(hipMemcpyAsync(dst, src, bytes * run, hipMemcpyHostToDevice, p.s));
-        for (int r = 0; r < run; ++r) {
-            direct[i + r] = direct[i];
-            offs[i + r] = off;
-            p.w[i + r] = widths[i + r], p.h[i + r] = heights[i + r];
+            HP_HIP_TRY(hipMemcpyAsync(slot, frames[i], net_frame * run, hipMemcpyHostToDevice, p.s));
+            i += run - 1;
+            continue;
         }
-        i += run - 1;
-        if (!direct[i] || !pinned) // the slot of the staging / raw buffer is in use until the copy has run
-            off += (bytes + 255) & ~(size_t)255;
+        offs[i] = off;
+        HP_TRY(upload_blob(p, frames[i], (size_t)widths[i] * heights[i] * 3, pinned, direct[i] ? slot : nullptr, off));
     }
     for (int i = 0; i < n; ++i) {
         if (direct[i])
             continue;
-        uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * net_frame;
         const uint8_t* src = p.raw.as<uint8_t>() + offs[i];
-        if (pl->orientation != HP_ORIENT_NONE) { // p.w / p.h hold the stored size until here, the upright size from here on
-            const int sw = p.w[i], sh = p.h[i];
-            HP_TRY(hp_oriented_size(pl->orientation, sw, sh, &p.w[i], &p.h[i]));
-            HP_TRY(hp_resize_oriented_u8c3(src, sw, sh, sw * 3, pl->orientation, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
-        } else if (pl->keep_ratio)
-            HP_TRY(hp_letterbox_u8c3(src, p.w[i], p.h[i], p.w[i] * 3, dst, pl->in_w, pl->in_h, pl->in_w * 3, 0, 0, 0, p.s));
-        else
-            HP_TRY(hp_resize_u8c3(src, p.w[i], p.h[i], p.w[i] * 3, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
+        uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * R * net_frame;
+        HP_TRY(pl->tiled ? hp_resize_rois_oriented_u8c3(src, widths[i], heights[i], widths[i] * 3, pl->orientation, &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0,
+                               dst, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s)
+                         : hp_resize_oriented_u8c3(src, widths[i], heights[i], widths[i] * 3, pl->orientation, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h,
+                               pl->in_w * 3, p.s));
     }
-    return infer_and_parse(pl, p, n);
+    return infer_and_parse(pl, p, n * R);
 }
 
 int hp_pipeline_submit_yuv(hp_pipeline* pl, int format, const uint8_t* const* frames, const int* widths, const int* heights, int n)
@@ -294,8 +337,7 @@ int hp_pipeline_submit_yuv(hp_pipeline* pl, int format, const uint8_t* const* fr
     HP_REQUIRE(pl->orientation == HP_ORIENT_NONE, HP_ERR_STATE,
         "hp_pipeline_submit_yuv: not available while an orientation is set, submit hp_yuv_image frames with hp_pipeline_submit_yuv_images");
     HP_REQUIRE(format == HP_YUV_NV12 || format == HP_YUV_I420, HP_ERR_INVALID, "hp_pipeline_submit_yuv: unknown format %d", format);
-    HP_REQUIRE(n >= 1 && n <= pl->capacity(), HP_ERR_CAPACITY, "hp_pipeline_submit_yuv: batch %d > max_batch %d%s", n, pl->max_batch, pl->flip_note());
-    HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "hp_pipeline_submit_yuv: all %d pipes are busy, collect first", pl->n_pipes);
+    HP_TRY(admit(pl, "hp_pipeline_submit_yuv", n));
     pipe_t& p = pl->pipes[pl->head];
     const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
     for (int i = 0; i < n; ++i) { // everything is checked before the first copy is enqueued
@@ -305,21 +347,13 @@ int hp_pipeline_submit_yuv(hp_pipeline* pl, int format, const uint8_t* const* fr
         HP_REQUIRE((size_t)widths[i] * heights[i] * 3 / 2 <= pl->max_frame_bytes, HP_ERR_CAPACITY, "hp_pipeline_submit_yuv: frame %d (%dx%d) exceeds max_frame_bytes %zu", i,
             widths[i], heights[i], pl->max_frame_bytes);
     }
-    // all copies first, then all kernels, as the BGR submit does: the stream changes between the copy engine and the compute queue once
-    // per batch, not once per frame.  One copy of the 1.5-byte form per frame; the fused conversion + resize then writes the network's
+    // One copy of the 1.5-byte form per frame (half the bytes of BGR over PCIe); the fused conversion + resize then writes the network's
     // slot - a network-sized frame takes the same road (the kernel converts and nothing else): there is no BGR form of it anywhere to copy
     size_t off = 0;
     std::vector<size_t> offs(n);
     for (int i = 0; i < n; ++i) {
-        const size_t bytes = (size_t)widths[i] * heights[i] * 3 / 2;
-        const uint8_t* src = frames[i];
-        if (!is_pinned(frames[i])) {
-            memcpy(p.stage.as<uint8_t>() + off, frames[i], bytes);
-            src = p.stage.as<uint8_t>() + off;
-        }
-        HP_HIP_TRY(hipMemcpyAsync(p.raw.as<uint8_t>() + off, src, bytes, hipMemcpyHostToDevice, p.s));
         offs[i] = off, p.w[i] = widths[i], p.h[i] = heights[i];
-        off += (bytes + 255) & ~(size_t)255;
+        HP_TRY(upload_blob(p, frames[i], (size_t)widths[i] * heights[i] * 3 / 2, is_pinned(frames[i]), nullptr, off));
     }
     for (int i = 0; i < n; ++i) {
         const int w = p.w[i], h = p.h[i];
@@ -339,46 +373,40 @@ int hp_pipeline_submit_yuv(hp_pipeline* pl, int format, const uint8_t* const* fr
 int hp_pipeline_submit_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, int n, int on_device)
 {
     HP_REQUIRE(pl && frames, HP_ERR_INVALID, "hp_pipeline_submit_yuv_images: null argument");
-    if (pl->tiled)
-        return submit_tiled_yuv_images(pl, frames, n, on_device);
-    HP_REQUIRE(n >= 1 && n <= pl->capacity(), HP_ERR_CAPACITY, "hp_pipeline_submit_yuv_images: batch %d > max_batch %d%s", n, pl->max_batch, pl->flip_note());
-    HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "hp_pipeline_submit_yuv_images: all %d pipes are busy, collect first", pl->n_pipes);
+    HP_TRY(admit(pl, "hp_pipeline_submit_yuv_images", n));
     pipe_t& p = pl->pipes[pl->head];
+    const int R = tiled_regions(pl);
     const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
     for (int i = 0; i < n; ++i) { // everything is checked before the first copy is enqueued
         HP_TRY(hp_yuv::validate(&frames[i], "hp_pipeline_submit_yuv_images", on_device != 0));
         HP_REQUIRE(on_device || hp_yuv_packed_bytes(frames[i].format, frames[i].width, frames[i].height) <= pl->max_frame_bytes, HP_ERR_CAPACITY,
             "hp_pipeline_submit_yuv_images: frame %d (%s, %dx%d, %zu bytes) exceeds max_frame_bytes %zu", i, hp_yuv::layout_of(frames[i].format)->name,
             frames[i].width, frames[i].height, hp_yuv_packed_bytes(frames[i].format, frames[i].width, frames[i].height), pl->max_frame_bytes);
+        int ax = 1, ay = 1;
+        HP_TRY(hp_yuv_roi_alignment(frames[i].format, &ax, &ay));
+        HP_TRY(plan_frame(pl, p, i, frames[i].width, frames[i].height, ax, ay));
     }
-    std::vector<hp_yuv_image> dev;
+    std::vector<hp_yuv_image> dev; // each frame as a kernel will read it: the caller's surface, or the tightly packed copy in p.raw
     if (on_device)
         dev.assign(frames, frames + n);
     else
-        HP_TRY(upload_yuv_images(pl, p, frames, n, dev));
+        HP_TRY(upload_yuv_images(p, frames, n, dev));
     for (int i = 0; i < n; ++i) {
-        uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * net_frame;
-        p.w[i] = frames[i].width, p.h[i] = frames[i].height;
+        uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * R * net_frame;
         const hp_tonemap* tm = pl->tonemap_for(dev[i]);
-        if (pl->orientation != HP_ORIENT_NONE) {
-            HP_TRY(hp_oriented_size(pl->orientation, frames[i].width, frames[i].height, &p.w[i], &p.h[i]));
-            HP_TRY(hp_resize_oriented_yuv(&dev[i], tm, pl->orientation, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
-        } else if (pl->keep_ratio)
-            HP_TRY(tm ? hp_letterbox_yuv_hdr(&dev[i], tm, dst, pl->in_w, pl->in_h, pl->in_w * 3, 0, 0, 0, p.s)
-                      : hp_letterbox_yuv(&dev[i], dst, pl->in_w, pl->in_h, pl->in_w * 3, 0, 0, 0, p.s));
-        else
-            HP_TRY(tm ? hp_resize_yuv_hdr(&dev[i], tm, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s)
-                      : hp_resize_yuv(&dev[i], dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
+        HP_TRY(pl->tiled ? hp_resize_rois_oriented_yuv(&dev[i], tm, pl->orientation, &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h,
+                               pl->in_w * 3, net_frame, p.s)
+                         : hp_resize_oriented_yuv(&dev[i], tm, pl->orientation, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
     }
-    return infer_and_parse(pl, p, n);
+    return infer_and_parse(pl, p, n * R);
 }
 
 } // extern "C"
 
 namespace {
 
-// the part of a submit that does not depend on how the frames arrived: p.net holds n network-sized BGR frames (in stream order on p.s)
-// -> conv stack -> the pipeline's parser, and the pipe joins the ring of batches in flight
+// the part of a submit that does not depend on how the frames arrived: p.net holds n network-sized BGR slots (in stream order on p.s)
+// -> conv stack -> the pipeline's parser, and the pipe joins the ring of batches in flight (a tiled batch: as n / R frames of R regions)
 int infer_and_parse(hp_pipeline* pl, pipe_t& p, int n)
 {
     HP_TRY(hp_engine_infer_u8(p.eng, p.net.as<uint8_t>(), n, 1, p.s));
@@ -409,7 +437,7 @@ int infer_and_parse(hp_pipeline* pl, pipe_t& p, int n)
         HP_TRY(hp_engine_output(p.eng, 1, &name, b, &dpif));
         HP_TRY(hp_pifpaf_enqueue(p.pifpaf, n, dpaf, dpif, b[1], b[2], p.s));
     }
-    p.n = n, p.regions = 0; // (a tiled submit sets p.regions after this returns)
+    p.n = n, p.regions = pl->tiled ? tiled_regions(pl) : 0;
     pl->head = (pl->head + 1) % pl->n_pipes;
     ++pl->inflight;
     return HP_OK;
@@ -417,10 +445,8 @@ int infer_and_parse(hp_pipeline* pl, pipe_t& p, int n)
 
 // host frames of hp_pipeline_submit_yuv_images: every frame's planes tightly packed into p.raw (one copy per frame, enqueued on p.s);
 // `dev` describes each frame as a kernel will read it there
-int upload_yuv_images(hp_pipeline* pl, pipe_t& p, const hp_yuv_image* frames, int n, std::vector<hp_yuv_image>& dev)
+int upload_yuv_images(pipe_t& p, const hp_yuv_image* frames, int n, std::vector<hp_yuv_image>& dev)
 {
-    // host frames: all copies first, then all kernels (see hp_pipeline_submit_yuv).  `dev` describes each frame as the kernel will read it:
-    // the caller's surface for a device frame, the tightly packed copy in p.raw for a host frame
     dev.assign(frames, frames + n);
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
@@ -452,96 +478,17 @@ int upload_yuv_images(hp_pipeline* pl, pipe_t& p, const hp_yuv_image* frames, in
     return HP_OK;
 }
 
-int tiled_regions(const hp_pipeline* pl) { return pl->tiling.cols * pl->tiling.rows + pl->tiling.with_full; }
-
-// what every tiled submit checks first: n frames of R regions fit a batch, and a pipe is free
-int tiled_admit(hp_pipeline* pl, const char* who, int n)
+// the first half of every collect: the parser's list of every slot of the batch in pipe p (room for `cap` humans per slot, n_out their counts),
+// and the pipe leaves the ring whatever the parser answered
+int collect_slots(hp_pipeline* pl, pipe_t& p, hp_human* out, int cap, int* n_out)
 {
-    const int R = tiled_regions(pl);
-    HP_REQUIRE(n >= 1 && n <= pl->capacity() / R, HP_ERR_CAPACITY, "%s: %d frames of %d regions each > max_batch %d%s (at most %d frames per submit)", who, n, R,
-        pl->max_batch, pl->flip_note(), pl->capacity() / R);
-    HP_REQUIRE(pl->inflight < pl->n_pipes, HP_ERR_STATE, "%s: all %d pipes are busy, collect first", who, pl->n_pipes);
-    return HP_OK;
-}
-
-int submit_tiled(hp_pipeline* pl, const uint8_t* const* frames, const int* widths, const int* heights, int n)
-{
-    HP_TRY(tiled_admit(pl, "hp_pipeline_submit", n));
-    pipe_t& p = pl->pipes[pl->head];
-    const int R = tiled_regions(pl);
-    const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
-    for (int i = 0; i < n; ++i) { // everything is checked before the first copy is enqueued
-        HP_REQUIRE(frames[i] && widths[i] > 0 && heights[i] > 0, HP_ERR_INVALID, "hp_pipeline_submit: frame %d is empty", i);
-        HP_REQUIRE((size_t)widths[i] * heights[i] * 3 <= pl->max_frame_bytes, HP_ERR_CAPACITY, "hp_pipeline_submit: frame %d (%dx%d) exceeds max_frame_bytes %zu", i,
-            widths[i], heights[i], pl->max_frame_bytes);
-        int uw = 0, uh = 0; // the tiles are planned on the upright frame
-        HP_TRY(hp_oriented_size(pl->orientation, widths[i], heights[i], &uw, &uh));
-        const int rc = hp_tile_plan(&pl->tiling, uw, uh, 1, 1, &p.roi[(size_t)i * R], R);
-        if (rc < 0)
-            return rc;
-    }
-    size_t off = 0;
-    std::vector<size_t> offs(n);
-    for (int i = 0; i < n; ++i) {
-        const size_t bytes = (size_t)widths[i] * heights[i] * 3;
-        const uint8_t* src = frames[i];
-        if (!is_pinned(frames[i])) {
-            memcpy(p.stage.as<uint8_t>() + off, frames[i], bytes);
-            src = p.stage.as<uint8_t>() + off;
-        }
-        HP_HIP_TRY(hipMemcpyAsync(p.raw.as<uint8_t>() + off, src, bytes, hipMemcpyHostToDevice, p.s));
-        offs[i] = off;
-        HP_TRY(hp_oriented_size(pl->orientation, widths[i], heights[i], &p.w[i], &p.h[i]));
-        off += (bytes + 255) & ~(size_t)255;
-    }
-    for (int i = 0; i < n; ++i) // (orientation 0 forwards to hp_resize_rois_u8c3)
-        HP_TRY(hp_resize_rois_oriented_u8c3(p.raw.as<uint8_t>() + offs[i], widths[i], heights[i], widths[i] * 3, pl->orientation, &p.roi[(size_t)i * R], R,
-            pl->keep_ratio, 0, 0, 0, p.net.as<uint8_t>() + (size_t)i * R * net_frame, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s));
-    HP_TRY(infer_and_parse(pl, p, n * R));
-    p.regions = R;
-    return HP_OK;
-}
-
-int submit_tiled_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, int n, int on_device)
-{
-    HP_TRY(tiled_admit(pl, "hp_pipeline_submit_yuv_images", n));
-    pipe_t& p = pl->pipes[pl->head];
-    const int R = tiled_regions(pl);
-    const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
-    for (int i = 0; i < n; ++i) { // everything is checked before the first copy is enqueued
-        HP_TRY(hp_yuv::validate(&frames[i], "hp_pipeline_submit_yuv_images", on_device != 0));
-        HP_REQUIRE(on_device || hp_yuv_packed_bytes(frames[i].format, frames[i].width, frames[i].height) <= pl->max_frame_bytes, HP_ERR_CAPACITY,
-            "hp_pipeline_submit_yuv_images: frame %d (%s, %dx%d, %zu bytes) exceeds max_frame_bytes %zu", i, hp_yuv::layout_of(frames[i].format)->name,
-            frames[i].width, frames[i].height, hp_yuv_packed_bytes(frames[i].format, frames[i].width, frames[i].height), pl->max_frame_bytes);
-        int ax = 1, ay = 1;
-        HP_TRY(hp_yuv_roi_alignment(frames[i].format, &ax, &ay));
-        int uw = 0, uh = 0; // the tiles are planned on the upright frame; behind a quarter turn its x axis is the stored y axis
-        HP_TRY(hp_oriented_size(pl->orientation, frames[i].width, frames[i].height, &uw, &uh));
-        if (pl->orientation & 1)
-            std::swap(ax, ay);
-        const int rc = hp_tile_plan(&pl->tiling, uw, uh, ax, ay, &p.roi[(size_t)i * R], R);
-        if (rc < 0)
-            return rc;
-    }
-    std::vector<hp_yuv_image> dev;
-    if (on_device)
-        dev.assign(frames, frames + n);
-    else
-        HP_TRY(upload_yuv_images(pl, p, frames, n, dev));
-    for (int i = 0; i < n; ++i) {
-        HP_TRY(hp_oriented_size(pl->orientation, frames[i].width, frames[i].height, &p.w[i], &p.h[i]));
-        uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * R * net_frame;
-        const hp_tonemap* tm = pl->tonemap_for(dev[i]);
-        if (pl->orientation != HP_ORIENT_NONE)
-            HP_TRY(hp_resize_rois_oriented_yuv(&dev[i], tm, pl->orientation, &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h,
-                pl->in_w * 3, net_frame, p.s));
-        else
-            HP_TRY(tm ? hp_resize_rois_yuv_hdr(&dev[i], tm, &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s)
-                      : hp_resize_rois_yuv(&dev[i], &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, net_frame, p.s));
-    }
-    HP_TRY(infer_and_parse(pl, p, n * R));
-    p.regions = R;
-    return HP_OK;
+    const int rc = pl->kind == HP_PARSER_PAF ? hp_paf_collect(p.paf, out, cap, n_out)
+        : pl->kind == HP_PARSER_PPN        ? hp_ppn_collect(p.ppn, out, cap, n_out)
+                                           : hp_pifpaf_collect(p.pifpaf, out, cap, n_out);
+    p.n = 0, p.regions = 0;
+    pl->tail = (pl->tail + 1) % pl->n_pipes;
+    --pl->inflight;
+    return rc;
 }
 
 // hp_pipeline_collect of a tiled batch: the parser's lists of all slots, then per frame resume_ratio per region (keep_ratio), the way back
@@ -553,12 +500,7 @@ int collect_tiled(hp_pipeline* pl, pipe_t& p, hp_human* out, int cap_per_frame, 
     pl->slot_humans.resize((size_t)slots * cap);
     pl->slot_n.resize(slots);
     hp_human* sh = pl->slot_humans.data();
-    int rc = pl->kind == HP_PARSER_PAF ? hp_paf_collect(p.paf, sh, cap, pl->slot_n.data())
-        : pl->kind == HP_PARSER_PPN    ? hp_ppn_collect(p.ppn, sh, cap, pl->slot_n.data())
-                                       : hp_pifpaf_collect(p.pifpaf, sh, cap, pl->slot_n.data());
-    p.n = 0, p.regions = 0;
-    pl->tail = (pl->tail + 1) % pl->n_pipes;
-    --pl->inflight;
+    int rc = collect_slots(pl, p, sh, cap, pl->slot_n.data());
     *n_frames = frames;
     if (rc != HP_OK && rc != HP_ERR_CAPACITY)
         return rc;
@@ -605,12 +547,7 @@ int hp_pipeline_collect(hp_pipeline* pl, hp_human* out, int cap_per_frame, int* 
     if (p.regions)
         return collect_tiled(pl, p, out, cap_per_frame, n_out, n_frames);
     const int n = p.n;
-    const int rc = pl->kind == HP_PARSER_PAF ? hp_paf_collect(p.paf, out, cap_per_frame, n_out)
-        : pl->kind == HP_PARSER_PPN        ? hp_ppn_collect(p.ppn, out, cap_per_frame, n_out)
-                                           : hp_pifpaf_collect(p.pifpaf, out, cap_per_frame, n_out);
-    p.n = 0;
-    pl->tail = (pl->tail + 1) % pl->n_pipes;
-    --pl->inflight;
+    const int rc = collect_slots(pl, p, out, cap_per_frame, n_out);
     *n_frames = n;
     if ((rc == HP_OK || rc == HP_ERR_CAPACITY) && out && pl->keep_ratio) // (capacity: that frame's list is cut, everything returned is valid)
         for (int i = 0; i < n; ++i) // src/stream.cpp:120-124

@@ -90,15 +90,24 @@ template <class Taps> oriented_taps<Taps> orient(const Taps& in, int code, int s
     return t;
 }
 
-#define HP_LAUNCH_ORIENTED(kernel, g, t, code, s)                                                           \
-    do {                                                                                                    \
-        const bool cols_ = oriented_cols(code);                                                             \
-        if (cols_)                                                                                          \
-            hipLaunchKernelGGL(kernel<true>, oriented_grid(g, true), dim3(256), 0, s, g, t);                \
-        else                                                                                                \
-            hipLaunchKernelGGL(kernel<false>, oriented_grid(g, false), dim3(256), 0, s, g, t);              \
-        HP_HIP_TRY(hipGetLastError());                                                                      \
-    } while (0)
+// this unit's kernels for each Taps type: the per-frame one under either thread map, and the regions one (BGR regions: named at their one call)
+auto frame_kernel(const oriented_taps<bgr_taps>&, bool cols) { return cols ? resize_oriented_u8c3_kernel<true> : resize_oriented_u8c3_kernel<false>; }
+auto frame_kernel(const oriented_taps<yuv_hdr_taps>&, bool cols) { return cols ? resize_oriented_hdr_kernel<true> : resize_oriented_hdr_kernel<false>; }
+auto frame_kernel(const oriented_taps<yuv_taps<2, 1>>&, bool cols) { return cols ? resize_oriented_word16_kernel<true> : resize_oriented_word16_kernel<false>; }
+auto frame_kernel(const oriented_taps<yuv_taps<1, 2>>&, bool cols) { return cols ? resize_oriented_packed8_kernel<true> : resize_oriented_packed8_kernel<false>; }
+auto frame_kernel(const oriented_taps<yuv_taps<1, 1>>&, bool cols) { return cols ? resize_oriented_planar8_kernel<true> : resize_oriented_planar8_kernel<false>; }
+auto rois_kernel(const oriented_taps<yuv_hdr_taps>&) { return resize_rois_oriented_hdr_kernel; }
+auto rois_kernel(const oriented_taps<yuv_taps<2, 1>>&) { return resize_rois_oriented_word16_kernel; }
+auto rois_kernel(const oriented_taps<yuv_taps<1, 2>>&) { return resize_rois_oriented_packed8_kernel; }
+auto rois_kernel(const oriented_taps<yuv_taps<1, 1>>&) { return resize_rois_oriented_planar8_kernel; }
+
+template <class Taps> int launch_frame(const rz_geom& g, const oriented_taps<Taps>& t, hipStream_t s)
+{
+    const bool cols = oriented_cols(t.code);
+    hipLaunchKernelGGL(frame_kernel(t, cols), oriented_grid(g, cols), dim3(256), 0, s, g, t);
+    HP_HIP_TRY(hipGetLastError());
+    return HP_OK;
+}
 
 // the geometry of a per-frame call: the resize runs from the upright size
 int prepare_frame(int code, int sw, int sh, int keep_ratio, const int bg[3], uint8_t* dst, int dw, int dh, int dst_stride, rz_geom& g)
@@ -148,9 +157,7 @@ int hp_resize_oriented_u8c3(const uint8_t* dev_src, int sw, int sh, int src_stri
     const int bg[3] = { b, g, r };
     rz_geom geom;
     HP_TRY(prepare_frame(orientation, sw, sh, keep_ratio, bg, dev_dst, dw, dh, dst_stride, geom));
-    const auto t = orient(bgr_taps{ dev_src, src_stride }, orientation, sw, sh);
-    HP_LAUNCH_ORIENTED(resize_oriented_u8c3_kernel, geom, t, orientation, (hipStream_t)stream);
-    return HP_OK;
+    return launch_frame(geom, orient(bgr_taps{ dev_src, src_stride }, orientation, sw, sh), (hipStream_t)stream);
 }
 
 int hp_resize_oriented_yuv(const hp_yuv_image* src, const hp_tonemap* tm, int orientation, int keep_ratio, int b, int g, int r, uint8_t* dev_dst,
@@ -164,39 +171,12 @@ int hp_resize_oriented_yuv(const hp_yuv_image* src, const hp_tonemap* tm, int or
                               : hp_resize_yuv_hdr(src, tm, dev_dst, dw, dh, dst_stride, stream);
         return keep_ratio ? hp_letterbox_yuv(src, dev_dst, dw, dh, dst_stride, b, g, r, stream) : hp_resize_yuv(src, dev_dst, dw, dh, dst_stride, stream);
     }
-    const int bg[3] = { b, g, r };
-    const hipStream_t s = (hipStream_t)stream;
-    rz_geom geom;
-    if (tm) {
-        yuv_hdr_taps in;
-        HP_TRY(prepare_hdr(who, src, tm, in)); // refuses an 8-bit layout by name
+    return with_yuv_taps(who, src, tm, [&](const auto& in) -> int {
+        const int bg[3] = { b, g, r };
+        rz_geom geom;
         HP_TRY(prepare_frame(orientation, src->width, src->height, keep_ratio, bg, dev_dst, dw, dh, dst_stride, geom));
-        const auto t = orient(in, orientation, src->width, src->height);
-        HP_LAUNCH_ORIENTED(resize_oriented_hdr_kernel, geom, t, orientation, s);
-        return HP_OK;
-    }
-    HP_TRY(hp_yuv::validate(src, who));
-    const hp_yuv::layout& l = *hp_yuv::layout_of(src->format);
-    int32_t k[7];
-    HP_TRY(hp_yuv_coefficients(src->matrix, src->range, l.sample_bytes == 2 ? 10 : 8, k));
-    HP_TRY(prepare_frame(orientation, src->width, src->height, keep_ratio, bg, dev_dst, dw, dh, dst_stride, geom));
-    if (l.sample_bytes == 2) {
-        yuv_taps<2, 1> in;
-        fill_taps(in, *src, l, k);
-        const auto t = orient(in, orientation, src->width, src->height);
-        HP_LAUNCH_ORIENTED(resize_oriented_word16_kernel, geom, t, orientation, s);
-    } else if (l.planes == 1) {
-        yuv_taps<1, 2> in;
-        fill_taps(in, *src, l, k);
-        const auto t = orient(in, orientation, src->width, src->height);
-        HP_LAUNCH_ORIENTED(resize_oriented_packed8_kernel, geom, t, orientation, s);
-    } else {
-        yuv_taps<1, 1> in;
-        fill_taps(in, *src, l, k);
-        const auto t = orient(in, orientation, src->width, src->height);
-        HP_LAUNCH_ORIENTED(resize_oriented_planar8_kernel, geom, t, orientation, s);
-    }
-    return HP_OK;
+        return launch_frame(geom, orient(in, orientation, src->width, src->height), (hipStream_t)stream);
+    });
 }
 
 int hp_resize_rois_oriented_u8c3(const uint8_t* dev_src, int sw, int sh, int src_stride, int orientation, const hp_roi* rois, int n, int keep_ratio,
@@ -223,36 +203,15 @@ int hp_resize_rois_oriented_yuv(const hp_yuv_image* src, const hp_tonemap* tm, i
     if (orientation == HP_ORIENT_NONE)
         return tm ? hp_resize_rois_yuv_hdr(src, tm, rois, n, keep_ratio, b, g, r, dev_dst, dw, dh, dst_stride, slot_stride, stream)
                   : hp_resize_rois_yuv(src, rois, n, keep_ratio, b, g, r, dev_dst, dw, dh, dst_stride, slot_stride, stream);
-    const int bg[3] = { b, g, r };
-    const hipStream_t s = (hipStream_t)stream;
-    roi_geom geom[ROIS_MAX];
-    yuv_hdr_taps hdr;
-    if (tm)
-        HP_TRY(prepare_hdr(who, src, tm, hdr));
-    else
-        HP_TRY(hp_yuv::validate(src, who));
-    const hp_yuv::layout& l = *hp_yuv::layout_of(src->format);
-    HP_TRY(prepare_oriented_rois(who, l.name, orientation, src->width, src->height, 1 << l.sx, 1 << l.sy, rois, n, keep_ratio, dev_dst, dw, dh, dst_stride,
-        slot_stride, bg, geom));
-    if (tm) {
-        const oriented_taps<yuv_hdr_taps> t{ hdr, 0, 0, orientation };
-        return launch_rois(resize_rois_oriented_hdr_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, s);
-    }
-    int32_t k[7];
-    HP_TRY(hp_yuv_coefficients(src->matrix, src->range, l.sample_bytes == 2 ? 10 : 8, k));
-    if (l.sample_bytes == 2) {
-        oriented_taps<yuv_taps<2, 1>> t{ {}, 0, 0, orientation };
-        fill_taps(t.in, *src, l, k);
-        return launch_rois(resize_rois_oriented_word16_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, s);
-    }
-    if (l.planes == 1) {
-        oriented_taps<yuv_taps<1, 2>> t{ {}, 0, 0, orientation };
-        fill_taps(t.in, *src, l, k);
-        return launch_rois(resize_rois_oriented_packed8_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, s);
-    }
-    oriented_taps<yuv_taps<1, 1>> t{ {}, 0, 0, orientation };
-    fill_taps(t.in, *src, l, k);
-    return launch_rois(resize_rois_oriented_planar8_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, s);
+    return with_yuv_taps(who, src, tm, [&](const auto& in) -> int {
+        const hp_yuv::layout& l = *hp_yuv::layout_of(src->format);
+        const int bg[3] = { b, g, r };
+        roi_geom geom[ROIS_MAX];
+        HP_TRY(prepare_oriented_rois(who, l.name, orientation, src->width, src->height, 1 << l.sx, 1 << l.sy, rois, n, keep_ratio, dev_dst, dw, dh,
+            dst_stride, slot_stride, bg, geom));
+        const oriented_taps<std::decay_t<decltype(in)>> t{ in, 0, 0, orientation }; // (the origin is each region's, from geom)
+        return launch_rois(rois_kernel(t), t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, (hipStream_t)stream);
+    });
 }
 
 } // extern "C"

@@ -26,6 +26,11 @@ __global__ __launch_bounds__(256) void resize_rois_yuv_planar8_kernel(const roi_
 __global__ __launch_bounds__(256) void resize_rois_yuv_packed8_kernel(const roi_batch b, const yuv_taps<1, 2> t) { resize_rois_body(b, t); }
 __global__ __launch_bounds__(256) void resize_rois_yuv_word16_kernel(const roi_batch b, const yuv_taps<2, 1> t) { resize_rois_body(b, t); }
 
+// this unit's kernel for each Taps type that with_yuv_taps() hands out
+auto kernel_of(const yuv_taps<2, 1>&) { return resize_rois_yuv_word16_kernel; }
+auto kernel_of(const yuv_taps<1, 2>&) { return resize_rois_yuv_packed8_kernel; }
+auto kernel_of(const yuv_taps<1, 1>&) { return resize_rois_yuv_planar8_kernel; }
+
 } // namespace
 
 extern "C" {
@@ -56,28 +61,14 @@ int hp_resize_rois_u8c3(const uint8_t* dev_src, int sw, int sh, int src_stride, 
 int hp_resize_rois_yuv(const hp_yuv_image* src, const hp_roi* rois, int n, int keep_ratio, int b, int g, int r, uint8_t* dev_dst, int dw, int dh,
     int dst_stride, size_t slot_stride, void* stream)
 {
-    HP_TRY(hp_yuv::validate(src, "hp_resize_rois_yuv"));
-    const hp_yuv::layout& l = *hp_yuv::layout_of(src->format);
-    int32_t k[7];
-    HP_TRY(hp_yuv_coefficients(src->matrix, src->range, l.sample_bytes == 2 ? 10 : 8, k));
-    const int bg[3] = { b, g, r };
-    roi_geom geom[ROIS_MAX];
-    HP_TRY(prepare_rois("hp_resize_rois_yuv", l.name, src->width, src->height, 1 << l.sx, 1 << l.sy, rois, n, keep_ratio, dev_dst, dw, dh, dst_stride,
-        slot_stride, bg, geom));
-    const hipStream_t s = (hipStream_t)stream;
-    if (l.sample_bytes == 2) {
-        yuv_taps<2, 1> t;
-        fill_taps(t, *src, l, k);
-        return launch_rois(resize_rois_yuv_word16_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, s);
-    }
-    if (l.planes == 1) {
-        yuv_taps<1, 2> t;
-        fill_taps(t, *src, l, k);
-        return launch_rois(resize_rois_yuv_packed8_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, s);
-    }
-    yuv_taps<1, 1> t;
-    fill_taps(t, *src, l, k);
-    return launch_rois(resize_rois_yuv_planar8_kernel, t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, s);
+    return with_yuv_taps("hp_resize_rois_yuv", src, [&](const auto& t) -> int {
+        const hp_yuv::layout& l = *hp_yuv::layout_of(src->format);
+        const int bg[3] = { b, g, r };
+        roi_geom geom[ROIS_MAX];
+        HP_TRY(prepare_rois("hp_resize_rois_yuv", l.name, src->width, src->height, 1 << l.sx, 1 << l.sy, rois, n, keep_ratio, dev_dst, dw, dh, dst_stride,
+            slot_stride, bg, geom));
+        return launch_rois(kernel_of(t), t, geom, n, dev_dst, dw, dh, dst_stride, slot_stride, bg, (hipStream_t)stream);
+    });
 }
 
 } // extern "C"

@@ -68,4 +68,21 @@ template <class Taps> void fill_taps(Taps& t, const hp_yuv_image& im, const hp_y
     t.y_off = k[0], t.c_off = k[1], t.cy = k[2], t.cub = k[3], t.cug = k[4], t.cvg = k[5], t.cvr = k[6];
 }
 
+// The one statement of "image description -> Taps" for an SDR frame: every check of the description (hp_yuv::validate, then the matrix integers),
+// then `f` is called with the frame's filled Taps - yuv_taps<2, 1> for the 16-bit layouts, <1, 2> for the packed ones, <1, 1> for the rest - and
+// its result is returned.  An entry point is "this, and inside f: geometry, then the launch of the unit's kernel for that Taps type".
+// (with a tone-map: resize_yuv_hdr_device.hpp's overload, which adds yuv_hdr_taps)
+template <class F> int with_yuv_taps(const char* who, const hp_yuv_image* im, F&& f)
+{
+    HP_TRY(hp_yuv::validate(im, who));
+    const hp_yuv::layout& l = *hp_yuv::layout_of(im->format);
+    int32_t k[7];
+    HP_TRY(hp_yuv_coefficients(im->matrix, im->range, l.sample_bytes == 2 ? 10 : 8, k));
+    const auto filled = [&](auto t) {
+        fill_taps(t, *im, l, k);
+        return f(t);
+    };
+    return l.sample_bytes == 2 ? filled(yuv_taps<2, 1>{}) : l.planes == 1 ? filled(yuv_taps<1, 2>{}) : filled(yuv_taps<1, 1>{});
+}
+
 } // namespace hp_resize

@@ -28,7 +28,7 @@ namespace {
 
 using namespace hp_resize;
 
-// yuv_taps<> and fill_taps(): resize_yuv_device.hpp, shared with the multi-region kernels of resize_rois.hip
+// yuv_taps<>, fill_taps() and with_yuv_taps(): resize_yuv_device.hpp, shared with the multi-region kernels of resize_rois.hip
 
 template <class Taps> __device__ __forceinline__ void resize_yuv_body(const rz_geom& g, const Taps& t)
 {
@@ -42,33 +42,24 @@ __global__ __launch_bounds__(256) void resize_yuv_planar8_kernel(const rz_geom g
 __global__ __launch_bounds__(256) void resize_yuv_packed8_kernel(const rz_geom g, const yuv_taps<1, 2> t) { resize_yuv_body(g, t); }
 __global__ __launch_bounds__(256) void resize_yuv_word16_kernel(const rz_geom g, const yuv_taps<2, 1> t) { resize_yuv_body(g, t); }
 
+// this unit's kernel for each Taps type that with_yuv_taps() hands out
+auto kernel_of(const yuv_taps<2, 1>&) { return resize_yuv_word16_kernel; }
+auto kernel_of(const yuv_taps<1, 2>&) { return resize_yuv_packed8_kernel; }
+auto kernel_of(const yuv_taps<1, 1>&) { return resize_yuv_planar8_kernel; }
+
 int launch_resize_yuv_image(const hp_yuv_image* im, const char* who, uint8_t* dst, int dw, int dh, int dst_stride, bool letterbox, const int bg[3],
     hipStream_t s)
 {
-    HP_TRY(hp_yuv::validate(im, who));
-    const hp_yuv::layout& l = *hp_yuv::layout_of(im->format);
-    int32_t k[7];
-    HP_TRY(hp_yuv_coefficients(im->matrix, im->range, l.sample_bytes == 2 ? 10 : 8, k));
-    int iw = dw, ih = dh;
-    if (letterbox)
-        hp_letterbox_inner(im->width, im->height, dw, dh, &iw, &ih);
-    rz_geom g;
-    HP_TRY(rz_prepare(g, im->width, im->height, dst, dw, dh, dst_stride, iw, ih, bg));
-    if (l.sample_bytes == 2) {
-        yuv_taps<2, 1> t;
-        fill_taps(t, *im, l, k);
-        hipLaunchKernelGGL(resize_yuv_word16_kernel, rz_grid(g), dim3(256), 0, s, g, t);
-    } else if (l.planes == 1) {
-        yuv_taps<1, 2> t;
-        fill_taps(t, *im, l, k);
-        hipLaunchKernelGGL(resize_yuv_packed8_kernel, rz_grid(g), dim3(256), 0, s, g, t);
-    } else {
-        yuv_taps<1, 1> t;
-        fill_taps(t, *im, l, k);
-        hipLaunchKernelGGL(resize_yuv_planar8_kernel, rz_grid(g), dim3(256), 0, s, g, t);
-    }
-    HP_HIP_TRY(hipGetLastError());
-    return HP_OK;
+    return with_yuv_taps(who, im, [&](const auto& t) -> int {
+        int iw = dw, ih = dh;
+        if (letterbox)
+            hp_letterbox_inner(im->width, im->height, dw, dh, &iw, &ih);
+        rz_geom g;
+        HP_TRY(rz_prepare(g, im->width, im->height, dst, dw, dh, dst_stride, iw, ih, bg));
+        hipLaunchKernelGGL(kernel_of(t), rz_grid(g), dim3(256), 0, s, g, t);
+        HP_HIP_TRY(hipGetLastError());
+        return HP_OK;
+    });
 }
 
 } // namespace

@@ -59,4 +59,15 @@ inline int prepare_hdr(const char* who, const hp_yuv_image* im, const hp_tonemap
     return HP_OK;
 }
 
+// "image description (+ optional tone-map) -> Taps" for the calls that take both kinds of frame: with a tone-map prepare_hdr()'s checks and
+// yuv_hdr_taps, without one resize_yuv_device.hpp's SDR statement; `f` gets the filled Taps either way
+template <class F> int with_yuv_taps(const char* who, const hp_yuv_image* im, const hp_tonemap* tm, F&& f)
+{
+    if (!tm)
+        return with_yuv_taps(who, im, f);
+    yuv_hdr_taps t;
+    HP_TRY(prepare_hdr(who, im, tm, t)); // refuses an 8-bit layout by name
+    return f(t);
+}
+
 } // namespace hp_resize

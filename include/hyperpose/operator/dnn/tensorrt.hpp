@@ -193,17 +193,11 @@ namespace dnn {
         /// and the batch is inferred; throws std::logic_error on an over-size batch (:439-443).
         std::vector<internal_t> inference(std::vector<cv::Mat> inputs)
         {
-            require_calibrated();
-            if (inputs.size() > batch_room())
-                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(inputs.size()) + " Max@" + std::to_string(batch_room()) + overflow_note());
-            if (inputs.empty())
+            if (!begin_batch(inputs.size()))
                 return {};
-            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
-            if (!m_dev_net && hp_malloc((void**)&m_dev_net, net_frame * m_max_batch_size) != HP_OK)
-                fatal(hp_last_error());
+            const size_t net_frame = net_frame_bytes();
             if (!m_host_net && hp_malloc_host((void**)&m_host_net, net_frame * m_max_batch_size) != HP_OK)
                 fatal(hp_last_error());
-            retire_last_batch(); // (the engine is idle here: the previous call was synchronised before it returned)
             std::vector<uint8_t> scratch;
             bool all_net_sized = m_orientation == HP_ORIENT_NONE;
             for (const cv::Mat& f : inputs) {
@@ -223,9 +217,7 @@ namespace dnn {
             }
             for (size_t i = 0; i < inputs.size(); ++i)
                 frame_to_device(inputs[i], m_dev_net + i * net_frame, scratch);
-            if (hp_engine_infer_u8(m_engine, m_dev_net, (int)inputs.size(), 1, nullptr) != HP_OK)
-                fatal(hp_last_error());
-            return collect(inputs.size());
+            return run_batch(inputs.size());
         }
 
         /// Addition: the same call for video frames in the decoder's own form (utility/data.hpp, yuv420_frame: NV12 or I420 in host memory).
@@ -234,21 +226,12 @@ namespace dnn {
         /// converted with cv::cvtColor(COLOR_YUV2BGR_NV12 / _I420), bit for bit.  Same over-size-batch exception, same calibration rule.
         std::vector<internal_t> inference(const std::vector<yuv420_frame>& inputs)
         {
-            require_calibrated();
-            if (inputs.size() > batch_room())
-                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(inputs.size()) + " Max@" + std::to_string(batch_room()) + overflow_note());
-            if (inputs.empty())
+            if (!begin_batch(inputs.size()))
                 return {};
-            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
-            if (!m_dev_net && hp_malloc((void**)&m_dev_net, net_frame * m_max_batch_size) != HP_OK)
-                fatal(hp_last_error());
-            retire_last_batch();
             std::vector<uint8_t> scratch;
             for (size_t i = 0; i < inputs.size(); ++i)
-                yuv_frame_to_device(inputs[i], m_dev_net + i * net_frame, scratch);
-            if (hp_engine_infer_u8(m_engine, m_dev_net, (int)inputs.size(), 1, nullptr) != HP_OK)
-                fatal(hp_last_error());
-            return collect(inputs.size());
+                yuv_frame_to_device(inputs[i], m_dev_net + i * net_frame_bytes(), scratch);
+            return run_batch(inputs.size());
         }
 
         /// Addition: the same call for frames of any layout, colour matrix and range (utility/data.hpp, yuv_frame), in host memory or -
@@ -258,21 +241,12 @@ namespace dnn {
         /// calibration rule.  A std::vector<yuv420_frame> keeps its own overload above.
         std::vector<internal_t> inference(const std::vector<yuv_frame>& inputs)
         {
-            require_calibrated();
-            if (inputs.size() > batch_room())
-                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(inputs.size()) + " Max@" + std::to_string(batch_room()) + overflow_note());
-            if (inputs.empty())
+            if (!begin_batch(inputs.size()))
                 return {};
-            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
-            if (!m_dev_net && hp_malloc((void**)&m_dev_net, net_frame * m_max_batch_size) != HP_OK)
-                fatal(hp_last_error());
-            retire_last_batch();
             std::vector<uint8_t> scratch;
             for (size_t i = 0; i < inputs.size(); ++i)
-                yuv_image_to_device(inputs[i], m_dev_net + i * net_frame, scratch);
-            if (hp_engine_infer_u8(m_engine, m_dev_net, (int)inputs.size(), 1, nullptr) != HP_OK)
-                fatal(hp_last_error());
-            return collect(inputs.size());
+                yuv_image_to_device(inputs[i], m_dev_net + i * net_frame_bytes(), scratch);
+            return run_batch(inputs.size());
         }
 
         /// Addition: many regions of ONE frame in one call (tiled inference: hyperpose::plan_tiles, to_frame, merge_humans).  One packet per
@@ -281,17 +255,10 @@ namespace dnn {
         /// (std::logic_error beyond); a region that is empty or not inside the frame is a std::logic_error too.
         std::vector<internal_t> inference(const cv::Mat& frame, const std::vector<cv::Rect>& regions)
         {
-            require_calibrated();
-            if (regions.size() > batch_room())
-                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(regions.size()) + " Max@" + std::to_string(batch_room()) + overflow_note());
-            if (regions.empty())
+            if (!begin_batch(regions.size()))
                 return {};
             if (frame.empty())
                 fatal("hyperpose::dnn::tensorrt::inference: empty image");
-            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
-            if (!m_dev_net && hp_malloc((void**)&m_dev_net, net_frame * m_max_batch_size) != HP_OK)
-                fatal(hp_last_error());
-            retire_last_batch();
             std::vector<uint8_t> scratch;
             const uint8_t* src = detail::mat_bytes(frame, scratch);
             const size_t bytes = (size_t)frame.cols * frame.rows * 3;
@@ -300,43 +267,28 @@ namespace dnn {
                 fatal(hp_last_error());
             const std::vector<hp_roi> rois = to_rois(regions);
             if (hp_resize_rois_oriented_u8c3(m_dev_raw, frame.cols, frame.rows, frame.cols * 3, m_orientation, rois.data(), (int)rois.size(),
-                    m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
+                    m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, net_frame_bytes(),
+                    hp_engine_stream(m_engine))
                 != HP_OK) // (orientation 0 forwards to hp_resize_rois_u8c3)
                 throw std::logic_error(hp_last_error());
-            if (hp_engine_infer_u8(m_engine, m_dev_net, (int)rois.size(), 1, nullptr) != HP_OK)
-                fatal(hp_last_error());
-            return collect(rois.size());
+            return run_batch(rois.size());
         }
 
         /// The same for a yuv_frame (host planes are uploaded once, a device-resident surface is read where it lies; hp_resize_rois_yuv):
         /// the regions keep the layout's alignment (hyperpose::plan_tiles(size, tiling, frame.format) plans them so).
         std::vector<internal_t> inference(const yuv_frame& frame, const std::vector<cv::Rect>& regions)
         {
-            require_calibrated();
-            if (regions.size() > batch_room())
-                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(regions.size()) + " Max@" + std::to_string(batch_room()) + overflow_note());
-            if (regions.empty())
+            if (!begin_batch(regions.size()))
                 return {};
-            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
-            if (!m_dev_net && hp_malloc((void**)&m_dev_net, net_frame * m_max_batch_size) != HP_OK)
-                fatal(hp_last_error());
-            retire_last_batch();
             std::vector<uint8_t> scratch;
             const hp_yuv_image im = yuv_image_on_device(frame, scratch);
             const std::vector<hp_roi> rois = to_rois(regions);
-            const hp_tonemap* tm = tonemap_for(frame);
-            const int rc = m_orientation != HP_ORIENT_NONE
-                ? hp_resize_rois_oriented_yuv(&im, tm, m_orientation, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width,
-                      m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
-                : tm ? hp_resize_rois_yuv_hdr(&im, tm, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width,
-                           m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine))
-                     : hp_resize_rois_yuv(&im, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width,
-                           m_inp_size.height, m_inp_size.width * 3, net_frame, hp_engine_stream(m_engine));
-            if (rc != HP_OK)
+            // (orientation 0 forwards to hp_resize_rois_yuv, or with a tone-map to hp_resize_rois_yuv_hdr)
+            if (hp_resize_rois_oriented_yuv(&im, tonemap_for(frame), m_orientation, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net,
+                    m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, net_frame_bytes(), hp_engine_stream(m_engine))
+                != HP_OK)
                 throw std::logic_error(hp_last_error());
-            if (hp_engine_infer_u8(m_engine, m_dev_net, (int)rois.size(), 1, nullptr) != HP_OK)
-                fatal(hp_last_error());
-            return collect(rois.size());
+            return run_batch(rois.size());
         }
 
         /// data_type::kINT8: TensorRT's MinMax calibration (an IInt8MinMaxCalibrator fed with these frames).  Frames of any size are brought to
@@ -344,65 +296,21 @@ namespace dnn {
         /// every per-layer activation scale; calibration is never implicit.
         void calibrate(const std::vector<cv::Mat>& frames)
         {
-            if (hp_engine_dtype(m_engine) != HP_DTYPE_I8)
-                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: only data_type::kINT8 engines are calibrated");
-            if (frames.empty())
-                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: no frames");
-            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
-            retire_last_batch();
-            uint8_t* all = nullptr; // every frame at the network's size, on the device: the calibration is one call over all of them
-            if (hp_malloc((void**)&all, net_frame * frames.size()) != HP_OK)
-                fatal(hp_last_error());
-            std::vector<uint8_t> scratch;
-            for (size_t i = 0; i < frames.size(); ++i) {
-                if (frames[i].empty())
+            calibrate_with(frames, [this](const cv::Mat& f, uint8_t* dst, std::vector<uint8_t>& scratch) {
+                if (f.empty())
                     fatal("hyperpose::dnn::tensorrt::calibrate: empty image");
-                frame_to_device(frames[i], all + i * net_frame, scratch);
-            }
-            const int rc = hp_device_synchronize() == HP_OK ? hp_engine_calibrate_u8(m_engine, all, (int)frames.size(), 1) : HP_ERR_HIP;
-            hp_free(all);
-            if (rc != HP_OK)
-                fatal(hp_last_error());
+                frame_to_device(f, dst, scratch);
+            });
         }
         /// Addition: calibration from YUV 4:2:0 frames, brought to the network's size exactly as inference(std::vector<yuv420_frame>) does
         void calibrate(const std::vector<yuv420_frame>& frames)
         {
-            if (hp_engine_dtype(m_engine) != HP_DTYPE_I8)
-                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: only data_type::kINT8 engines are calibrated");
-            if (frames.empty())
-                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: no frames");
-            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
-            retire_last_batch();
-            uint8_t* all = nullptr;
-            if (hp_malloc((void**)&all, net_frame * frames.size()) != HP_OK)
-                fatal(hp_last_error());
-            std::vector<uint8_t> scratch;
-            for (size_t i = 0; i < frames.size(); ++i)
-                yuv_frame_to_device(frames[i], all + i * net_frame, scratch);
-            const int rc = hp_device_synchronize() == HP_OK ? hp_engine_calibrate_u8(m_engine, all, (int)frames.size(), 1) : HP_ERR_HIP;
-            hp_free(all);
-            if (rc != HP_OK)
-                fatal(hp_last_error());
+            calibrate_with(frames, [this](const yuv420_frame& f, uint8_t* dst, std::vector<uint8_t>& scratch) { yuv_frame_to_device(f, dst, scratch); });
         }
         /// Addition: calibration from frames of any layout, brought to the network's size exactly as inference(std::vector<yuv_frame>) does
         void calibrate(const std::vector<yuv_frame>& frames)
         {
-            if (hp_engine_dtype(m_engine) != HP_DTYPE_I8)
-                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: only data_type::kINT8 engines are calibrated");
-            if (frames.empty())
-                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: no frames");
-            const size_t net_frame = (size_t)m_inp_size.width * m_inp_size.height * 3;
-            retire_last_batch();
-            uint8_t* all = nullptr;
-            if (hp_malloc((void**)&all, net_frame * frames.size()) != HP_OK)
-                fatal(hp_last_error());
-            std::vector<uint8_t> scratch;
-            for (size_t i = 0; i < frames.size(); ++i)
-                yuv_image_to_device(frames[i], all + i * net_frame, scratch);
-            const int rc = hp_device_synchronize() == HP_OK ? hp_engine_calibrate_u8(m_engine, all, (int)frames.size(), 1) : HP_ERR_HIP;
-            hp_free(all);
-            if (rc != HP_OK)
-                fatal(hp_last_error());
+            calibrate_with(frames, [this](const yuv_frame& f, uint8_t* dst, std::vector<uint8_t>& scratch) { yuv_image_to_device(f, dst, scratch); });
         }
         /// false for a data_type::kINT8 engine that was neither calibrated nor loaded calibrated
         bool calibrated() const
@@ -467,8 +375,50 @@ namespace dnn {
         }
 
     private:
+        size_t net_frame_bytes() const { return (size_t)m_inp_size.width * m_inp_size.height * 3; }
+        // what every frame-taking inference() does first: the calibration rule, the over-size-batch exception, the batch buffer, and the
+        // previous call's maps get their host copy (the engine is idle here: the previous call was synchronised before it returned).
+        // False for an empty batch, which returns no packets.
+        bool begin_batch(size_t n)
+        {
+            require_calibrated();
+            if (n > batch_room())
+                throw std::logic_error("Input batch size overflow: Yours@" + std::to_string(n) + " Max@" + std::to_string(batch_room()) + overflow_note());
+            if (n == 0)
+                return false;
+            if (!m_dev_net && hp_malloc((void**)&m_dev_net, net_frame_bytes() * m_max_batch_size) != HP_OK)
+                fatal(hp_last_error());
+            retire_last_batch();
+            return true;
+        }
+        // ... and last: the n network-sized slots in m_dev_net are inferred
+        std::vector<internal_t> run_batch(size_t n)
+        {
+            if (hp_engine_infer_u8(m_engine, m_dev_net, (int)n, 1, nullptr) != HP_OK)
+                fatal(hp_last_error());
+            return collect(n);
+        }
+        // the body of every calibrate(): `to_device(frame, dst, scratch)` brings one frame to the network's size at device address dst
+        template <class Frame, class ToDevice> void calibrate_with(const std::vector<Frame>& frames, ToDevice to_device)
+        {
+            if (hp_engine_dtype(m_engine) != HP_DTYPE_I8)
+                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: only data_type::kINT8 engines are calibrated");
+            if (frames.empty())
+                throw std::logic_error("hyperpose::dnn::tensorrt::calibrate: no frames");
+            retire_last_batch();
+            uint8_t* all = nullptr; // every frame at the network's size, on the device: the calibration is one call over all of them
+            if (hp_malloc((void**)&all, net_frame_bytes() * frames.size()) != HP_OK)
+                fatal(hp_last_error());
+            std::vector<uint8_t> scratch;
+            for (size_t i = 0; i < frames.size(); ++i)
+                to_device(frames[i], all + i * net_frame_bytes(), scratch);
+            const int rc = hp_device_synchronize() == HP_OK ? hp_engine_calibrate_u8(m_engine, all, (int)frames.size(), 1) : HP_ERR_HIP;
+            hp_free(all);
+            if (rc != HP_OK)
+                fatal(hp_last_error());
+        }
         // one frame brought to the network's size at device address dst (src/tensorrt.cpp:446-451): cv::resize (INTER_LINEAR) or, with
-        // keep_ratio, non_scaling_resize on the device; a network-sized frame is a copy
+        // keep_ratio, non_scaling_resize on the device, read upright under set_orientation; a network-sized upright frame is a copy
         void frame_to_device(const cv::Mat& f, uint8_t* dst, std::vector<uint8_t>& scratch)
         {
             const uint8_t* src = detail::mat_bytes(f, scratch);
@@ -478,24 +428,12 @@ namespace dnn {
                     fatal(hp_last_error());
                 return;
             }
-            if (bytes > m_raw_bytes) {
-                if (m_dev_raw)
-                    hp_free(m_dev_raw);
-                m_dev_raw = nullptr, m_raw_bytes = 0;
-                if (hp_malloc((void**)&m_dev_raw, bytes) != HP_OK)
-                    fatal(hp_last_error());
-                m_raw_bytes = bytes;
-            }
+            reserve_raw(bytes);
             if (hp_memcpy_h2d(m_dev_raw, src, bytes) != HP_OK)
                 fatal(hp_last_error());
-            const int rc = m_orientation != HP_ORIENT_NONE
-                ? hp_resize_oriented_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, m_orientation, m_keep_ratio ? 1 : 0, 0, 0, 0, dst, m_inp_size.width,
-                      m_inp_size.height, m_inp_size.width * 3, hp_engine_stream(m_engine))
-                : m_keep_ratio
-                ? hp_letterbox_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3, 0, 0, 0,
-                      hp_engine_stream(m_engine))
-                : hp_resize_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, dst, m_inp_size.width, m_inp_size.height, m_inp_size.width * 3,
-                      hp_engine_stream(m_engine));
+            // (orientation 0 forwards to hp_letterbox_u8c3 / hp_resize_u8c3)
+            const int rc = hp_resize_oriented_u8c3(m_dev_raw, f.cols, f.rows, f.cols * 3, m_orientation, m_keep_ratio ? 1 : 0, 0, 0, 0, dst, m_inp_size.width,
+                m_inp_size.height, m_inp_size.width * 3, hp_engine_stream(m_engine));
             if (rc != HP_OK || hp_engine_synchronize(m_engine) != HP_OK) // m_dev_raw is re-used by the next frame
                 fatal(hp_last_error());
         }
@@ -523,14 +461,7 @@ namespace dnn {
                 if (!nv12)
                     std::memcpy(scratch.data() + luma + luma / 4 + r * crow, f.v + r * (size_t)f.uv_stride, crow);
             }
-            if (bytes > m_raw_bytes) {
-                if (m_dev_raw)
-                    hp_free(m_dev_raw);
-                m_dev_raw = nullptr, m_raw_bytes = 0;
-                if (hp_malloc((void**)&m_dev_raw, bytes) != HP_OK)
-                    fatal(hp_last_error());
-                m_raw_bytes = bytes;
-            }
+            reserve_raw(bytes);
             if (hp_memcpy_h2d(m_dev_raw, scratch.data(), bytes) != HP_OK)
                 fatal(hp_last_error());
             const uint8_t *du = m_dev_raw + luma, *dv = nv12 ? nullptr : du + luma / 4;
@@ -543,20 +474,13 @@ namespace dnn {
                 fatal(hp_last_error());
         }
         // the same for a yuv_frame of any layout: a host frame's planes are packed without row padding into ONE upload of
-        // hp_yuv_packed_bytes, a device frame is read where it lies; then hp_resize_yuv / hp_letterbox_yuv - for a 10-bit frame under
-        // set_tonemap their *_hdr twins - writes dst
+        // hp_yuv_packed_bytes, a device frame is read where it lies; then hp_resize_oriented_yuv writes dst: with orientation 0 that is
+        // hp_resize_yuv / hp_letterbox_yuv, for a 10-bit frame under set_tonemap their *_hdr twins
         void yuv_image_to_device(const yuv_frame& f, uint8_t* dst, std::vector<uint8_t>& scratch)
         {
             const hp_yuv_image im = yuv_image_on_device(f, scratch);
             const int w = m_inp_size.width, h = m_inp_size.height;
-            void* s = hp_engine_stream(m_engine);
-            int rc;
-            if (m_orientation != HP_ORIENT_NONE)
-                rc = hp_resize_oriented_yuv(&im, tonemap_for(f), m_orientation, m_keep_ratio ? 1 : 0, 0, 0, 0, dst, w, h, w * 3, s);
-            else if (const hp_tonemap* tm = tonemap_for(f))
-                rc = m_keep_ratio ? hp_letterbox_yuv_hdr(&im, tm, dst, w, h, w * 3, 0, 0, 0, s) : hp_resize_yuv_hdr(&im, tm, dst, w, h, w * 3, s);
-            else
-                rc = m_keep_ratio ? hp_letterbox_yuv(&im, dst, w, h, w * 3, 0, 0, 0, s) : hp_resize_yuv(&im, dst, w, h, w * 3, s);
+            const int rc = hp_resize_oriented_yuv(&im, tonemap_for(f), m_orientation, m_keep_ratio ? 1 : 0, 0, 0, 0, dst, w, h, w * 3, hp_engine_stream(m_engine));
             if (rc != HP_OK || hp_engine_synchronize(m_engine) != HP_OK) // m_dev_raw is re-used by the next frame
                 fatal(hp_last_error());
         }
@@ -581,14 +505,7 @@ namespace dnn {
             hp_yuv_image im = f.image();
             if (!f.on_device) {
                 scratch.resize(bytes);
-                if (bytes > m_raw_bytes) {
-                    if (m_dev_raw)
-                        hp_free(m_dev_raw);
-                    m_dev_raw = nullptr, m_raw_bytes = 0;
-                    if (hp_malloc((void**)&m_dev_raw, bytes) != HP_OK)
-                        fatal(hp_last_error());
-                    m_raw_bytes = bytes;
-                }
+                reserve_raw(bytes);
                 size_t at = 0;
                 for (int k = 0; k < planes; ++k) {
                     const size_t row = yuv_frame::row_bytes(f.format, k, f.width, f.height);

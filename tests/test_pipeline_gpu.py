@@ -68,6 +68,37 @@ def test_pipeline_equals_stages_by_hand(hp, keep_ratio, dtype):
     assert total > 0  # the loose thresholds make the random-weight maps produce humans: the comparison is not vacuous
 
 
+def test_refused_frame_is_found_before_the_first_copy(hp):
+    """hp_pipeline_submit checks every frame before it enqueues anything: a batch whose SECOND frame exceeds max_frame_bytes is refused
+    (HP_ERR_CAPACITY, naming frame 1) with nothing in flight, and the pipeline then gives the humans of a fresh one.  (48 x 64 network:
+    a 64 x 48 frame has exactly max_frame_bytes and still goes through the resize kernel.)"""
+    from hyperpose_amd import _lib
+    in_w, in_h = 48, 64
+    m = E.Model("lw_openpose_mobilenet", in_w, in_h)
+    w = m.init_weights(11)
+    for L in m.layers:  # O(1) maps from random weights, as above
+        if L.op == E.OP_CONV and L.cout in (19, 38) and L.out in [o.tensor for o in m.outputs]:
+            w[L.w_off:L.w_off + L.cout * L.cin] *= 400.0
+    make = lambda: Pipeline(m, w, max_batch=2, n_pipes=2, keep_ratio=True, conf_thresh=0.05, paf_thresh=-1e9, max_frame_wh=(64, 48))
+    rng = np.random.default_rng(17)
+    good = [rng.integers(0, 256, (48, 64, 3), dtype=np.uint8) for _ in range(2)]
+    too_big = rng.integers(0, 256, (48, 80, 3), dtype=np.uint8)
+    pl = make()
+    with pytest.raises(_lib.HpError) as e:
+        pl.submit([good[0], too_big])
+    assert e.value.code == _lib.HP_ERR_CAPACITY and "frame 1 " in str(e.value)
+    assert pl.in_flight == 0
+    pl.submit(good)
+    got = pl.collect()
+    fresh = make()
+    fresh.submit(good)
+    ref = fresh.collect()
+    assert len(got) == len(ref) == 2
+    for hg, hr in zip(got, ref):
+        assert hg.tobytes() == hr.tobytes()
+    print("humans per frame:", [len(h) for h in got])
+
+
 @pytest.mark.parametrize("kind", ["ppn", "pifpaf"])
 def test_pipeline_other_parsers_equal_stages_by_hand(hp, kind):
     """hp_pipeline_create_ex with the PoseProposal / PifPaf parser == resize on the host -> engine -> the blocking parser call."""
