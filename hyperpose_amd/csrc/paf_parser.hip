@@ -27,6 +27,7 @@
 // Every floating-point expression keeps the operand order and the (non-fused) rounding of the CPU
 // code it replaces; this translation unit is compiled with -ffp-contract=off.  See DESIGN.md.
 #include "hp_common.hpp"
+#include "parser_host.hpp"
 #include "libstdcxx_sort.hpp"
 
 #include <algorithm>
@@ -1346,10 +1347,9 @@ gauss_t make_gauss(double sigma)
 } // namespace
 
 // =====================================================================================================
-struct hp_paf {
+struct hp_paf final : hp::parser_session {
     float conf_thresh, paf_thresh;
     int res_w, res_h;
-    int max_batch;
     int peak_cap = 512;   // peaks per part per frame
     int cand_cap = 2048;  // candidates per limb per frame that survive the two criteria
     int human_cap = 128;  // humans per frame copied back
@@ -1360,18 +1360,39 @@ struct hp_paf {
     int BH = 0, CW = 0, strips = 0, bands = 0, src_rows_cap = 0; // peaks kernel tiling
     size_t peaks_lds = 0, score_lds = 0, connect_lds = 0;
 
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    hp::dev_buf tables, plist, sorted, pcount, pcount_last, cands, cand_count, conns, conn_count, flags, in_conf, in_paf;
+    hp::dev_buf tables, plist, sorted, pcount, pcount_last, cands, cand_count, conns, conn_count, flags;
+    hp::staged_input in_conf, in_paf;
     hp::host_buf h_humans, h_counts; // h_counts: [n_humans(max_batch) | flags(max_batch)], written by the assemble kernel
-    int pending = 0; // frames of the enqueued, not yet collected batch
     int last_n = 0;  // frames of the last completed batch (debug taps)
     const float *last_conf = nullptr, *last_paf = nullptr; // inputs of the batch in flight (re-parsed with larger lists on overflow)
 
+    ~hp_paf() override { drain(); }
     int shape(const int conf_shape[3], const int paf_shape[3]);
     int alloc_lists();
     int launch(int n, const float* dev_conf, const float* dev_paf, hipStream_t s);
+    // shape, launch, and the inputs are kept for a second parse: they must stay valid until collect
+    int start(int n, const float* dev_conf, const int conf_shape[3], const float* dev_paf, const int paf_shape[3], hipStream_t s)
+    {
+        HP_TRY(shape(conf_shape, paf_shape));
+        HP_TRY(launch(n, dev_conf, dev_paf, s));
+        last_conf = dev_conf, last_paf = dev_paf;
+        return HP_OK;
+    }
+    // the engine's outputs, sorted by name, are the reference's argument order (conf, paf), src/paf.cpp:300
+    int engine_outputs() const override { return 2; }
+    int enqueue_outputs(hp_engine* e, int n, hipStream_t s) override
+    {
+        const char* name = nullptr;
+        int cs[3], ps[3];
+        const float *dconf = nullptr, *dpaf = nullptr;
+        HP_TRY(hp_engine_output(e, 0, &name, cs, &dconf));
+        HP_TRY(hp_engine_output(e, 1, &name, ps, &dpaf));
+        return hp_paf_enqueue(this, n, dconf, cs, dpaf, ps, s);
+    }
+    int collect(hp_human* out, int cap_per_frame, int* n_out) override { return hp_paf_collect(this, out, cap_per_frame, n_out); }
 };
+
+hp::parser_session* hp::session_of(hp_paf* p) { return p; }
 
 // The reference's lists are std::vectors (src/post_process.hpp:171-193, src/paf.cpp:108-141): they grow.  Here they start at sizes
 // that fit every realistic frame (512 peaks per part, 2048 candidates per limb, 128 humans) and hp_paf_collect re-parses a batch
@@ -1484,32 +1505,14 @@ int hp_paf_create(hp_paf** out, float conf_thresh, float paf_thresh, int res_w, 
 {
     HP_REQUIRE(out, HP_ERR_INVALID, "hp_paf_create: null out");
     HP_REQUIRE(max_batch >= 1 && max_batch <= 65535, HP_ERR_INVALID, "hp_paf_create: max_batch %d", max_batch);
-    hp_paf* p = new hp_paf();
-    p->conf_thresh = conf_thresh, p->paf_thresh = paf_thresh, p->res_w = res_w, p->res_h = res_h, p->max_batch = max_batch;
-    hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-    if (e == hipSuccess)
-        e = hipEventCreateWithFlags(&p->done, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        hp::set_error("hp_paf_create: %s", hipGetErrorString(e));
-        delete p;
-        return HP_ERR_HIP;
-    }
-    *out = p;
+    std::unique_ptr<hp_paf> p(new hp_paf());
+    p->conf_thresh = conf_thresh, p->paf_thresh = paf_thresh, p->res_w = res_w, p->res_h = res_h;
+    HP_TRY(p->open(max_batch));
+    *out = p.release();
     return HP_OK;
 }
 
-void hp_paf_destroy(hp_paf* p)
-{
-    if (!p)
-        return;
-    if (p->stream)
-        (void)hipStreamSynchronize(p->stream);
-    if (p->done)
-        (void)hipEventDestroy(p->done);
-    if (p->stream)
-        (void)hipStreamDestroy(p->stream);
-    delete p;
-}
+void hp_paf_destroy(hp_paf* p) { delete p; }
 
 void* hp_paf_stream(hp_paf* p) { return p ? (void*)p->stream : nullptr; }
 
@@ -1557,8 +1560,7 @@ int hp_paf::launch(int n, const float* dev_conf, const float* dev_paf, hipStream
         p->conns.as<dconn>(), p->conn_count.as<int>(), p->res_w, p->res_h, p->h_humans.as<hp_human>(), p->h_counts.as<int>(),
         p->human_cap, p->flags.as<int>(), p->h_counts.as<int>() + p->max_batch, p->pcount_last.as<int>());
     HP_HIP_TRY(hipGetLastError());
-    HP_HIP_TRY(hipEventRecord(p->done, s));
-    return HP_OK;
+    return launched(n, s);
 }
 
 extern "C" {
@@ -1567,98 +1569,66 @@ int hp_paf_enqueue(hp_paf* p, int n, const float* dev_conf, const int conf_shape
     const int paf_shape[3], void* stream)
 {
     HP_REQUIRE(p && dev_conf && dev_paf, HP_ERR_INVALID, "hp_paf_enqueue: null argument");
-    HP_REQUIRE(n >= 1 && n <= p->max_batch, HP_ERR_CAPACITY, "hp_paf_enqueue: batch %d > max_batch %d", n, p->max_batch);
-    HP_REQUIRE(p->pending == 0, HP_ERR_STATE, "hp_paf_enqueue: previous batch not collected");
-    HP_TRY(p->shape(conf_shape, paf_shape));
-    HP_TRY(p->launch(n, dev_conf, dev_paf, stream ? (hipStream_t)stream : p->stream));
-    p->last_conf = dev_conf, p->last_paf = dev_paf; // must stay valid until hp_paf_collect (a frame that overflows a list is re-parsed)
-    p->pending = n;
+    HP_TRY(p->begin("hp_paf_enqueue", n));
+    return p->start(n, dev_conf, conf_shape, dev_paf, paf_shape, p->stream_or_own(stream));
+}
+
+// a list overflowed somewhere in the batch: grow what can grow (the reference's vectors just grow)
+static int paf_grow(hp_paf* p, int n, bool* grown)
+{
+    int fl = 0, max_h = 0;
+    for (int f = 0; f < n; ++f) {
+        fl |= p->h_counts.as<int>()[p->max_batch + f];
+        max_h = std::max(max_h, p->h_counts.as<int>()[f]);
+    }
+    const int old_peak = p->peak_cap, old_cand = p->cand_cap, old_human = p->human_cap;
+    if ((fl & 1) && p->peak_cap < PEAK_CAP_MAX)
+        p->peak_cap = std::min(p->peak_cap * 2, PEAK_CAP_MAX), *grown = true;
+    if ((fl & 2) && p->cand_cap < CAND_CAP_MAX)
+        p->cand_cap = std::min(p->cand_cap * 2, CAND_CAP_MAX), *grown = true;
+    while (p->human_cap < max_h && p->human_cap < HUMAN_CAP_MAX)
+        p->human_cap *= 2, *grown = true;
+    if (!*grown)
+        return HP_OK;
+    // the capacities never stay larger than plist / sorted / conns / h_humans: a failed allocation puts the old ones back
+    if (const int rc_alloc = p->alloc_lists(); rc_alloc != HP_OK) {
+        p->peak_cap = old_peak, p->cand_cap = old_cand, p->human_cap = old_human; // (buffers already re-allocated are only larger)
+        (void)p->alloc_lists();
+        return rc_alloc;
+    }
     return HP_OK;
 }
 
 int hp_paf_collect(hp_paf* p, hp_human* out, int cap_per_frame, int* n_out)
 {
     HP_REQUIRE(p && n_out, HP_ERR_INVALID, "hp_paf_collect: null argument");
-    HP_REQUIRE(p->pending > 0, HP_ERR_STATE, "hp_paf_collect: nothing enqueued");
-    HP_HIP_TRY(hipEventSynchronize(p->done));
-    const int n = p->pending;
-    p->pending = 0;
+    int n = 0;
+    HP_TRY(p->wait("hp_paf_collect", &n));
     p->last_n = n;
-    int fl = 0, max_h = 0;
-    for (int round = 0;; ++round) {
-        fl = 0, max_h = 0;
-        for (int f = 0; f < n; ++f) {
-            fl |= p->h_counts.as<int>()[p->max_batch + f];
-            max_h = std::max(max_h, p->h_counts.as<int>()[f]);
-        }
-        // a list overflowed somewhere in the batch: grow what can grow and parse the batch again (the reference's vectors just grow)
-        const int cand_max = CAND_CAP_MAX;
-        // the new capacities are computed into locals and committed only together with the buffers that match them: leaving the loop
-        // (round limit) or failing to allocate must not leave caps larger than plist / sorted / conns / h_humans
-        if (round >= 6)
-            break;
-        int peak_cap = p->peak_cap, cand_cap = p->cand_cap, human_cap = p->human_cap;
-        bool grown = false;
-        if ((fl & 1) && peak_cap < PEAK_CAP_MAX)
-            peak_cap = std::min(peak_cap * 2, PEAK_CAP_MAX), grown = true;
-        if ((fl & 2) && cand_cap < cand_max)
-            cand_cap = std::min(cand_cap * 2, cand_max), grown = true;
-        if (max_h > human_cap && human_cap < HUMAN_CAP_MAX) {
-            while (human_cap < max_h && human_cap < HUMAN_CAP_MAX)
-                human_cap *= 2;
-            grown = true;
-        }
-        if (!grown)
-            break;
-        const int old_peak = p->peak_cap, old_cand = p->cand_cap, old_human = p->human_cap;
-        p->peak_cap = peak_cap, p->cand_cap = cand_cap, p->human_cap = human_cap;
-        if (const int rc_alloc = p->alloc_lists(); rc_alloc != HP_OK) {
-            p->peak_cap = old_peak, p->cand_cap = old_cand, p->human_cap = old_human; // (buffers already re-allocated are only larger)
-            (void)p->alloc_lists();
-            return rc_alloc;
-        }
-        HP_TRY(p->launch(n, p->last_conf, p->last_paf, p->stream));
-        HP_HIP_TRY(hipEventSynchronize(p->done));
-    }
-    int rc = HP_OK;
+    HP_TRY(hp::reparse(
+        *p, "hp_paf_collect", 6, [&](bool* grown) { return paf_grow(p, n, grown); }, [&] { return p->launch(n, p->last_conf, p->last_paf, p->stream); }));
+    hp::frame_results res{ "paf", out, cap_per_frame, n_out, std::vector<std::string>(n) };
     for (int f = 0; f < n; ++f) {
         const int nh = p->h_counts.as<int>()[f];
         const int ff = p->h_counts.as<int>()[p->max_batch + f] & 7;
-        n_out[f] = nh;
-        if (ff) { // per-frame status: the other frames of the batch are complete, this one is truncated at a hard limit
-            hp::set_error("paf: frame %d exceeds a hard list limit (flags=%d: 1=peaks/part>%d, 2=candidates/limb>%d, 4=skeleton fragments>%d); its result is truncated",
+        if (ff) // per-frame status: the other frames of the batch are complete, this one is truncated at a hard limit
+            res.fail(f, "paf: frame %d exceeds a hard list limit (flags=%d: 1=peaks/part>%d, 2=candidates/limb>%d, 4=skeleton fragments>%d); its result is truncated",
                 f, ff, p->peak_cap, p->cand_cap, MAXH);
-            rc = HP_ERR_CAPACITY;
-        }
-        if (nh > cap_per_frame || nh > p->human_cap) {
-            hp::set_error("paf: frame %d has %d humans, capacity %d", f, nh, std::min(cap_per_frame, p->human_cap));
-            rc = HP_ERR_CAPACITY;
-        }
-        if (out)
-            memcpy(out + (size_t)f * cap_per_frame, p->h_humans.as<hp_human>() + (size_t)f * p->human_cap,
-                sizeof(hp_human) * std::min(std::min(nh, cap_per_frame), p->human_cap));
+        res.deliver(f, p->h_humans.as<hp_human>() + (size_t)f * p->human_cap, nh, std::min(nh, p->human_cap));
     }
-    return rc;
+    return res.code();
 }
 
 int hp_paf_process_batch(hp_paf* p, int n, const float* conf, const int conf_shape[3], const float* paf,
     const int paf_shape[3], int on_device, hp_human* out, int cap_per_frame, int* n_out)
 {
     HP_REQUIRE(p && conf && paf && conf_shape && paf_shape, HP_ERR_INVALID, "hp_paf_process_batch: null argument");
-    HP_REQUIRE(n >= 1 && n <= p->max_batch, HP_ERR_CAPACITY, "hp_paf_process_batch: batch %d > max_batch %d", n, p->max_batch);
-    const float *dc = conf, *dp = paf;
+    HP_TRY(p->begin("hp_paf_process_batch", n));
     if (!on_device) {
-        const size_t cb = (size_t)n * conf_shape[0] * conf_shape[1] * conf_shape[2] * sizeof(float);
-        const size_t pb = (size_t)n * paf_shape[0] * paf_shape[1] * paf_shape[2] * sizeof(float);
-        if (p->in_conf.bytes < cb)
-            HP_TRY(p->in_conf.alloc((size_t)p->max_batch * conf_shape[0] * conf_shape[1] * conf_shape[2] * sizeof(float)));
-        if (p->in_paf.bytes < pb)
-            HP_TRY(p->in_paf.alloc((size_t)p->max_batch * paf_shape[0] * paf_shape[1] * paf_shape[2] * sizeof(float)));
-        HP_HIP_TRY(hipMemcpyAsync(p->in_conf.p, conf, cb, hipMemcpyHostToDevice, p->stream));
-        HP_HIP_TRY(hipMemcpyAsync(p->in_paf.p, paf, pb, hipMemcpyHostToDevice, p->stream));
-        dc = p->in_conf.as<float>(), dp = p->in_paf.as<float>();
+        HP_TRY(p->in_conf.stage(conf, (size_t)conf_shape[0] * conf_shape[1] * conf_shape[2] * sizeof(float), n, p->max_batch, p->stream, &conf));
+        HP_TRY(p->in_paf.stage(paf, (size_t)paf_shape[0] * paf_shape[1] * paf_shape[2] * sizeof(float), n, p->max_batch, p->stream, &paf));
     }
-    HP_TRY(hp_paf_enqueue(p, n, dc, conf_shape, dp, paf_shape, nullptr));
+    HP_TRY(p->start(n, conf, conf_shape, paf, paf_shape, p->stream));
     return hp_paf_collect(p, out, cap_per_frame, n_out);
 }
 

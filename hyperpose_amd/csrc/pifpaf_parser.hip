@@ -26,6 +26,7 @@
 //
 // Compiled with -ffp-contract=off; every float/double expression keeps the reference's types and operand order.
 #include "hp_common.hpp"
+#include "parser_host.hpp"
 #include "libstdcxx_sort.hpp"
 
 #include <algorithm>
@@ -1404,28 +1405,42 @@ __global__ __launch_bounds__(64) void pp_decode_kernel(pd_params P, const int* _
 
 } // namespace
 
-struct hp_pifpaf {
-    int net_h, net_w, max_batch;
+struct hp_pifpaf final : hp::parser_session {
+    int net_h, net_w;
     float thresh;
     int seed_cap = 0; // NK x H x W once the field size is known
     bool shaped = false;
     pp_geom g{};
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    hp::dev_buf cells, ncells, seeds, lists, hdr, total, in_paf, in_pif;
+    hp::dev_buf cells, ncells, seeds, lists, hdr, total;
+    hp::staged_input in_paf, in_pif;
     hp::host_buf h_hdr, h_arena; // the pack kernel writes the dense arena straight into pinned host memory
     size_t arena_cap = 0;        // floats
     int arena_growths = 0;       // times hp_pifpaf_collect enlarged the arena and parsed a batch again (the reference's vectors just grow)
     struct { int n = 0, fh = 0, fw = 0; const float *paf = nullptr, *pif = nullptr; hipStream_t s = nullptr; } last; // the batch in flight, on the device
     std::vector<occupancy> occ;  // one per pool worker
-    int pending = 0;
     // device decoder (pp_decode_kernel); HP_PIFPAF_HOST_TAIL=1 keeps every frame on the host tail
     bool device_decode = true;
     pd_params dp{};
     hp::dev_buf seed_order, anns, occ_dev, n_humans, dflags;
     hp::host_buf h_humans, h_counts; // humans written by the kernel; h_counts = [n_humans x B][dflags x B]
     std::vector<int> last_flags;
+
+    ~hp_pifpaf() override { drain(); }
+    // the engine's outputs, sorted by name, are the reference's argument order (paf, pif), src/pifpaf.cpp:7
+    int engine_outputs() const override { return 2; }
+    int enqueue_outputs(hp_engine* e, int n, hipStream_t s) override
+    {
+        const char* name = nullptr;
+        int a[3], b[3];
+        const float *dpaf = nullptr, *dpif = nullptr;
+        HP_TRY(hp_engine_output(e, 0, &name, a, &dpaf));
+        HP_TRY(hp_engine_output(e, 1, &name, b, &dpif));
+        return hp_pifpaf_enqueue(this, n, dpaf, dpif, b[1], b[2], s);
+    }
+    int collect(hp_human* out, int cap_per_frame, int* n_out) override { return hp_pifpaf_collect(this, out, cap_per_frame, n_out); }
 };
+
+hp::parser_session* hp::session_of(hp_pifpaf* p) { return p; }
 
 extern "C" {
 
@@ -1433,9 +1448,8 @@ int hp_pifpaf_create(hp_pifpaf** out, int net_h, int net_w, float thresh, int ma
 {
     HP_REQUIRE(out && net_h > 0 && net_w > 0 && max_batch >= 1, HP_ERR_INVALID, "hp_pifpaf_create: bad argument");
     std::unique_ptr<hp_pifpaf> p(new hp_pifpaf());
-    p->net_h = net_h, p->net_w = net_w, p->thresh = thresh, p->max_batch = max_batch;
-    HP_HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    HP_HIP_TRY(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
+    p->net_h = net_h, p->net_w = net_w, p->thresh = thresh;
+    HP_TRY(p->open(max_batch));
     p->occ.resize(hp::frame_pool::instance().workers());
     if (const char* e = std::getenv("HP_PIFPAF_HOST_TAIL"))
         p->device_decode = !(e[0] && e[0] != '0');
@@ -1449,29 +1463,15 @@ int hp_pifpaf_create(hp_pifpaf** out, int net_h, int net_w, float thresh, int ma
     return HP_OK;
 }
 
-void hp_pifpaf_destroy(hp_pifpaf* p)
-{
-    if (!p)
-        return;
-    if (p->stream) {
-        (void)hipStreamSynchronize(p->stream);
-        (void)hipStreamDestroy(p->stream);
-    }
-    if (p->done) {
-        (void)hipEventSynchronize(p->done);
-        (void)hipEventDestroy(p->done);
-    }
-    delete p;
-}
+void hp_pifpaf_destroy(hp_pifpaf* p) { delete p; }
 
 void* hp_pifpaf_stream(hp_pifpaf* p) { return p ? (void*)p->stream : nullptr; }
 
 static int pifpaf_launch(hp_pifpaf* p, int n, const float* paf, const float* pif, int fh, int fw, int on_device, hipStream_t s)
 {
     HP_REQUIRE(p && paf && pif, HP_ERR_INVALID, "hp_pifpaf: null argument");
-    HP_REQUIRE(n >= 1 && n <= p->max_batch, HP_ERR_CAPACITY, "hp_pifpaf: batch %d > max_batch %d", n, p->max_batch);
+    HP_TRY(p->begin("hp_pifpaf", n));
     HP_REQUIRE(fh >= 2 && fw >= 2, HP_ERR_INVALID, "pifpaf: bad field size %dx%d", fh, fw);
-    HP_REQUIRE(p->pending == 0, HP_ERR_STATE, "hp_pifpaf: a batch is already in flight, collect it first");
     if (p->shaped)
         HP_REQUIRE(p->g.H == fh && p->g.W == fw, HP_ERR_STATE, "pifpaf: field size changed after the first call");
     const size_t HW = (size_t)fh * fw, B = p->max_batch;
@@ -1509,14 +1509,8 @@ static int pifpaf_launch(hp_pifpaf* p, int n, const float* paf, const float* pif
     }
     const float *dpaf = paf, *dpif = pif;
     if (!on_device) {
-        const size_t pb = (size_t)NB * 9 * HW * sizeof(float), ib = (size_t)NK * 5 * HW * sizeof(float);
-        if (p->in_paf.bytes < pb * B)
-            HP_TRY(p->in_paf.alloc(pb * B));
-        if (p->in_pif.bytes < ib * B)
-            HP_TRY(p->in_pif.alloc(ib * B));
-        HP_HIP_TRY(hipMemcpyAsync(p->in_paf.p, paf, pb * n, hipMemcpyHostToDevice, s));
-        HP_HIP_TRY(hipMemcpyAsync(p->in_pif.p, pif, ib * n, hipMemcpyHostToDevice, s));
-        dpaf = p->in_paf.as<float>(), dpif = p->in_pif.as<float>();
+        HP_TRY(p->in_paf.stage(paf, (size_t)NB * 9 * HW * sizeof(float), n, p->max_batch, s, &dpaf));
+        HP_TRY(p->in_pif.stage(pif, (size_t)NK * 5 * HW * sizeof(float), n, p->max_batch, s, &dpif));
     }
     p->last.n = n, p->last.fh = fh, p->last.fw = fw, p->last.paf = dpaf, p->last.pif = dpif, p->last.s = s;
     HP_HIP_TRY(hipMemsetAsync(p->hdr.p, 0, (size_t)n * HDR * sizeof(int), s));
@@ -1542,98 +1536,65 @@ static int pifpaf_launch(hp_pifpaf* p, int n, const float* paf, const float* pif
         p->lists.as<float>(), p->h_arena.as<float>());
     HP_HIP_TRY(hipGetLastError());
     HP_HIP_TRY(hipMemcpyAsync(p->h_hdr.p, p->hdr.p, (size_t)n * HDR * sizeof(int), hipMemcpyDeviceToHost, s));
-    HP_HIP_TRY(hipEventRecord(p->done, s));
-    p->pending = n;
+    return p->launched(n, s);
+}
+
+// The reference's lists are std::vectors (openpifpaf_postprocessor.cpp:764-851).  The pinned arena that carries the frames the host tail
+// decodes starts at a size that fits ordinary frames; when a frame's lists did not fit (h[40] & 2) it grows to what the batch needs
+// (h[42] per frame, + 25 %) - at most the size at which no list can overflow - and hp_pifpaf_collect parses the batch again from the
+// inputs, which the API keeps valid until collect returns (device inputs) or which were copied to the parser's own buffers (host inputs).
+static int pifpaf_grow_arena(hp_pifpaf* p, int n, bool* grown)
+{
+    size_t need = 0;
+    bool over = false;
+    for (int f = 0; f < n; ++f) {
+        const int* h = p->h_hdr.as<int>() + (size_t)f * HDR;
+        over |= (h[40] & 2) != 0;
+        if (!h[41])
+            need += (size_t)h[42];
+    }
+    const size_t HW = (size_t)p->g.H * p->g.W, cap_max = (size_t)p->max_batch * HW * (NK * 5 + NB * 2 * 9);
+    if (!over || p->arena_cap >= cap_max)
+        return HP_OK;
+    const size_t cap = std::min(cap_max, std::max(p->arena_cap * 2, need + need / 4));
+    HP_TRY(p->h_arena.alloc(cap * sizeof(float)));
+    p->arena_cap = cap, ++p->arena_growths, *grown = true;
     return HP_OK;
 }
 
 int hp_pifpaf_enqueue(hp_pifpaf* p, int n, const float* dev_paf, const float* dev_pif, int fh, int fw, void* stream)
 {
-    return pifpaf_launch(p, n, dev_paf, dev_pif, fh, fw, 1, stream ? (hipStream_t)stream : (p ? p->stream : nullptr));
+    return pifpaf_launch(p, n, dev_paf, dev_pif, fh, fw, 1, p ? p->stream_or_own(stream) : nullptr);
 }
-
-namespace {
-struct pifpaf_job {
-    hp_pifpaf* p;
-    hp_human* out;
-    int cap;
-    int* n_out;
-    std::vector<int> rc;
-};
-void pifpaf_frame(int f, int worker, void* ctx)
-{
-    pifpaf_job& j = *static_cast<pifpaf_job*>(ctx);
-    hp_pifpaf* p = j.p;
-    const int* hdr = p->h_hdr.as<int>() + (size_t)f * HDR;
-    if (p->device_decode && p->last_flags[f] == 0) { // decoded on the device: the kernel wrote the humans into pinned memory
-        const int nh = p->h_counts.as<int>()[f];
-        j.n_out[f] = nh;
-        if (nh > j.cap)
-            j.rc[f] = 2;
-        if (j.out)
-            std::copy_n(p->h_humans.as<hp_human>() + (size_t)f * PD_MAXA, std::min(nh, j.cap), j.out + (size_t)f * j.cap);
-        return;
-    }
-    if (hdr[40] != 0)
-        j.rc[f] = hdr[40] & 2 ? 3 : 1;
-    std::vector<hp_human> humans;
-    decode_frame(p->g, hdr, p->h_arena.as<float>(), p->thresh, p->net_w, p->net_h, p->occ[worker], humans);
-    j.n_out[f] = (int)humans.size();
-    if ((int)humans.size() > j.cap && !j.rc[f])
-        j.rc[f] = 2;
-    if (j.out)
-        std::copy(humans.begin(), humans.begin() + std::min<size_t>(humans.size(), j.cap), j.out + (size_t)f * j.cap);
-}
-} // namespace
 
 int hp_pifpaf_collect(hp_pifpaf* p, hp_human* out, int cap_per_frame, int* n_out)
 {
     HP_REQUIRE(p && n_out, HP_ERR_INVALID, "hp_pifpaf_collect: null argument");
-    HP_REQUIRE(p->pending > 0, HP_ERR_STATE, "hp_pifpaf_collect: nothing was enqueued");
-    const int n = p->pending;
-    p->pending = 0;
-    HP_HIP_TRY(hipEventSynchronize(p->done));
-    // The reference's lists are std::vectors (openpifpaf_postprocessor.cpp:764-851).  The pinned arena that carries the frames the host tail
-    // decodes starts at a size that fits ordinary frames; when a frame's lists did not fit (h[40] & 2) it grows to what the batch needs
-    // (h[42] per frame, + 25 %) - at most the size at which no list can overflow - and the batch is parsed again from the inputs, which
-    // the API keeps valid until collect returns (device inputs) or which were copied to the parser's own buffers (host inputs).
-    for (int round = 0; round < 4; ++round) {
-        size_t need = 0;
-        bool over = false;
-        for (int f = 0; f < n; ++f) {
-            const int* h = p->h_hdr.as<int>() + (size_t)f * HDR;
-            over |= (h[40] & 2) != 0;
-            if (!h[41])
-                need += (size_t)h[42];
-        }
-        const size_t HW = (size_t)p->g.H * p->g.W, cap_max = (size_t)p->max_batch * HW * (NK * 5 + NB * 2 * 9);
-        if (!over || p->arena_cap >= cap_max)
-            break;
-        const size_t cap = std::min(cap_max, std::max(p->arena_cap * 2, need + need / 4));
-        HP_TRY(p->h_arena.alloc(cap * sizeof(float)));
-        p->arena_cap = cap, ++p->arena_growths;
-        HP_TRY(pifpaf_launch(p, p->last.n, p->last.paf, p->last.pif, p->last.fh, p->last.fw, 1, p->last.s));
-        p->pending = 0;
-        HP_HIP_TRY(hipEventSynchronize(p->done));
-    }
+    int n = 0;
+    HP_TRY(p->wait("hp_pifpaf_collect", &n));
+    HP_TRY(hp::reparse(
+        *p, "hp_pifpaf_collect", 4, [&](bool* grown) { return pifpaf_grow_arena(p, n, grown); },
+        [&] { return pifpaf_launch(p, p->last.n, p->last.paf, p->last.pif, p->last.fh, p->last.fw, 1, p->last.s); }));
     p->last_flags.assign(n, -1);
     if (p->device_decode)
         std::copy_n(p->h_counts.as<int>() + p->max_batch, n, p->last_flags.begin());
-    pifpaf_job job{ p, out, cap_per_frame, n_out, std::vector<int>(n, 0) };
-    hp::frame_pool::instance().run(n, pifpaf_frame, &job);
-    int rc = HP_OK;
-    for (int f = 0; f < n; ++f)
-        if (job.rc[f] == 1) {
-            hp::set_error("pifpaf: frame %d has more than %d seeds", f, p->seed_cap);
-            rc = HP_ERR_CAPACITY;
-        } else if (job.rc[f] == 3) {
-            hp::set_error("pifpaf: the compacted lists of frame %d exceed the arena (%zu floats for the batch)", f, p->arena_cap);
-            rc = HP_ERR_CAPACITY;
-        } else if (job.rc[f] == 2) {
-            hp::set_error("pifpaf: frame %d has %d humans, capacity %d", f, n_out[f], cap_per_frame);
-            rc = HP_ERR_CAPACITY;
+    hp::frame_results res{ "pifpaf", out, cap_per_frame, n_out, std::vector<std::string>(n) };
+    hp::on_host_pool(n, [&](int f, int worker) {
+        if (p->device_decode && p->last_flags[f] == 0) { // decoded on the device: the kernel wrote the humans into pinned memory
+            const int nh = p->h_counts.as<int>()[f];
+            res.deliver(f, p->h_humans.as<hp_human>() + (size_t)f * PD_MAXA, nh, nh);
+            return;
         }
-    return rc;
+        const int* hdr = p->h_hdr.as<int>() + (size_t)f * HDR;
+        std::vector<hp_human> humans;
+        decode_frame(p->g, hdr, p->h_arena.as<float>(), p->thresh, p->net_w, p->net_h, p->occ[worker], humans);
+        res.deliver(f, humans.data(), (int)humans.size(), (int)humans.size());
+        if (hdr[40] & 2) // (these two take precedence over the count's message)
+            res.fail(f, "pifpaf: the compacted lists of frame %d exceed the arena (%zu floats for the batch)", f, p->arena_cap);
+        else if (hdr[40] != 0)
+            res.fail(f, "pifpaf: frame %d has more than %d seeds", f, p->seed_cap);
+    });
+    return res.code();
 }
 
 int hp_pifpaf_decode_flags(const hp_pifpaf* p, int* flags, int n)

@@ -32,6 +32,7 @@
 //         in oriented mode
 //     (c) all copies first, then all kernels, within a batch - also where (a) mixes direct and resized frames
 #include "hp_common.hpp"
+#include "parser_host.hpp"
 #include "yuv_formats.hpp"
 
 #include <cstring>
@@ -42,9 +43,7 @@ namespace {
 
 struct pipe_t {
     hp_engine* eng = nullptr;
-    hp_paf* paf = nullptr;
-    hp_ppn* ppn = nullptr;
-    hp_pifpaf* pifpaf = nullptr;
+    std::unique_ptr<hp::parser_session> parser; // the hyperpose::parser the pipeline ends in (make_parser)
     hipStream_t s = nullptr;
     hp::host_buf stage;     // pinned staging for frames that arrive in pageable memory
     hp::dev_buf raw, net;   // frames as submitted; frames at network size [max_batch][in_h][in_w][3]
@@ -90,12 +89,7 @@ struct hp_pipeline {
         for (auto& p : pipes) {
             if (p.s)
                 (void)hipStreamSynchronize(p.s);
-            if (p.paf)
-                hp_paf_destroy(p.paf);
-            if (p.ppn)
-                hp_ppn_destroy(p.ppn);
-            if (p.pifpaf)
-                hp_pifpaf_destroy(p.pifpaf);
+            p.parser.reset();
             if (p.eng)
                 hp_engine_destroy(p.eng);
         }
@@ -152,6 +146,28 @@ int upload_blob(pipe_t& p, const uint8_t* src, size_t bytes, bool pinned, uint8_
     return HP_OK;
 }
 
+// The one place where the parser's kind is looked at: the hyperpose::parser of `pd` with its constructor arguments (hp_parser_desc, include/hp_hip.h)
+// for the network of `ed`.  It reads the engine's outputs by the reference's convention - sorted by name (src/tensorrt.cpp:405) = its argument order.
+int make_parser(const hp_parser_desc& pd, const hp_engine_desc& ed, std::unique_ptr<hp::parser_session>& out)
+{
+    if (pd.kind == HP_PARSER_PAF) {
+        hp_paf* h = nullptr;
+        HP_TRY(hp_paf_create(&h, pd.thresh[0], pd.thresh[1], pd.res_w, pd.res_h, ed.max_batch));
+        out.reset(hp::session_of(h));
+    } else if (pd.kind == HP_PARSER_PPN) { // pose_proposal(net_resolution, point_thresh, limb_thresh, mns_thresh)
+        hp_ppn* h = nullptr;
+        HP_TRY(hp_ppn_create(&h, ed.in_w, ed.in_h, pd.thresh[0], pd.thresh[1], pd.thresh[2], ed.max_batch));
+        out.reset(hp::session_of(h));
+    } else { // pifpaf(h, w, thresh)
+        hp_pifpaf* h = nullptr;
+        HP_TRY(hp_pifpaf_create(&h, ed.in_h, ed.in_w, pd.thresh[0], ed.max_batch));
+        out.reset(hp::session_of(h));
+    }
+    HP_REQUIRE(ed.n_outputs == out->engine_outputs(), HP_ERR_INVALID, "hp_pipeline_create: this parser needs a network with exactly %d outputs, the engine has %d",
+        out->engine_outputs(), ed.n_outputs);
+    return HP_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -172,8 +188,7 @@ int hp_pipeline_create_ex(hp_pipeline** out, const hp_engine_desc* desc, const h
 {
     HP_REQUIRE(out && desc && parser, HP_ERR_INVALID, "hp_pipeline_create: null argument");
     HP_REQUIRE(n_pipes >= 1 && n_pipes <= 16, HP_ERR_INVALID, "hp_pipeline_create: n_pipes %d", n_pipes);
-    HP_REQUIRE(parser->kind == HP_PARSER_PAF || parser->kind == HP_PARSER_PPN || parser->kind == HP_PARSER_PIFPAF, HP_ERR_INVALID,
-        "hp_pipeline_create: unknown parser kind %d", parser->kind);
+    HP_REQUIRE(parser->kind >= HP_PARSER_PAF && parser->kind <= HP_PARSER_PIFPAF, HP_ERR_INVALID, "hp_pipeline_create: unknown parser kind %d", parser->kind);
     // HP_DTYPE_F32S is refused here: its guard against values outside fp16's range (|x| > 65504) runs in hp_engine_synchronize /
     // hp_engine_output_to_host, which a pipeline never calls - a batch that overflowed would be parsed and returned as humans with no error
     HP_REQUIRE(desc->dtype != HP_DTYPE_F32S, HP_ERR_INVALID,
@@ -192,12 +207,7 @@ int hp_pipeline_create_ex(hp_pipeline** out, const hp_engine_desc* desc, const h
     for (auto& p : pl->pipes) {
         // engine first, parser second: their streams then alternate over the runtime's hardware queues
         HP_TRY(hp_engine_create(&p.eng, desc));
-        if (parser->kind == HP_PARSER_PAF)
-            HP_TRY(hp_paf_create(&p.paf, parser->thresh[0], parser->thresh[1], parser->res_w, parser->res_h, desc->max_batch));
-        else if (parser->kind == HP_PARSER_PPN) // pose_proposal(net_resolution, point_thresh, limb_thresh, mns_thresh)
-            HP_TRY(hp_ppn_create(&p.ppn, desc->in_w, desc->in_h, parser->thresh[0], parser->thresh[1], parser->thresh[2], desc->max_batch));
-        else // pifpaf(h, w, thresh)
-            HP_TRY(hp_pifpaf_create(&p.pifpaf, desc->in_h, desc->in_w, parser->thresh[0], desc->max_batch));
+        HP_TRY(make_parser(*parser, *desc, p.parser));
         p.s = (hipStream_t)hp_engine_stream(p.eng);
         HP_TRY(p.stage.alloc((pl->max_frame_bytes + 256) * desc->max_batch)); // frames are packed at 256-byte offsets
         HP_TRY(p.raw.alloc((pl->max_frame_bytes + 256) * desc->max_batch));
@@ -205,11 +215,6 @@ int hp_pipeline_create_ex(hp_pipeline** out, const hp_engine_desc* desc, const h
         p.w.assign(desc->max_batch, 0), p.h.assign(desc->max_batch, 0);
         p.roi.assign(desc->max_batch, hp_roi{ 0, 0, 0, 0 });
     }
-    // the feature maps the parsers read, by the reference's convention: outputs sorted by name (src/tensorrt.cpp:405) = the parsers'
-    // argument order: PAF (conf, paf), src/paf.cpp:300; PifPaf (paf, pif), src/pifpaf.cpp:7; PoseProposal 7 tensors, src/pose_proposal.cpp:12-20
-    const int want = parser->kind == HP_PARSER_PPN ? 7 : 2;
-    HP_REQUIRE(hp_engine_num_outputs(pl->pipes[0].eng) == want, HP_ERR_INVALID, "hp_pipeline_create: this parser needs a network with exactly %d outputs, the engine has %d",
-        want, hp_engine_num_outputs(pl->pipes[0].eng));
     *out = pl.release();
     return HP_OK;
 }
@@ -410,33 +415,7 @@ namespace {
 int infer_and_parse(hp_pipeline* pl, pipe_t& p, int n)
 {
     HP_TRY(hp_engine_infer_u8(p.eng, p.net.as<uint8_t>(), n, 1, p.s));
-    const char* name = nullptr;
-    if (pl->kind == HP_PARSER_PAF) {
-        int cs[3], ps[3];
-        const float *dconf = nullptr, *dpaf = nullptr;
-        HP_TRY(hp_engine_output(p.eng, 0, &name, cs, &dconf));
-        HP_TRY(hp_engine_output(p.eng, 1, &name, ps, &dpaf));
-        HP_TRY(hp_paf_enqueue(p.paf, n, dconf, cs, dpaf, ps, p.s));
-    } else if (pl->kind == HP_PARSER_PPN) {
-        const float* d[7];
-        int sh[7][3];
-        for (int t = 0; t < 7; ++t)
-            HP_TRY(hp_engine_output(p.eng, t, &name, sh[t], &d[t]));
-        // the edge tensor leaves the network as [E*nh*nw, gh, gw] (pose_proposal/model.py:104-109): nh = nw = sqrt(C / E) with E = 17 limbs
-        const int E = 17, nn = sh[6][0] / E;
-        int nh = 1;
-        while (nh * nh < nn)
-            ++nh;
-        HP_REQUIRE(nh * nh * E == sh[6][0], HP_ERR_INVALID, "hp_pipeline: edge output has %d channels, expected 17 * k * k", sh[6][0]);
-        const int es[5] = { E, nh, nh, sh[6][1], sh[6][2] };
-        HP_TRY(hp_ppn_enqueue(p.ppn, n, d, sh[0], es, p.s));
-    } else {
-        int a[3], b[3];
-        const float *dpaf = nullptr, *dpif = nullptr;
-        HP_TRY(hp_engine_output(p.eng, 0, &name, a, &dpaf));
-        HP_TRY(hp_engine_output(p.eng, 1, &name, b, &dpif));
-        HP_TRY(hp_pifpaf_enqueue(p.pifpaf, n, dpaf, dpif, b[1], b[2], p.s));
-    }
+    HP_TRY(p.parser->enqueue_outputs(p.eng, n, p.s));
     p.n = n, p.regions = pl->tiled ? tiled_regions(pl) : 0;
     pl->head = (pl->head + 1) % pl->n_pipes;
     ++pl->inflight;
@@ -482,9 +461,7 @@ int upload_yuv_images(pipe_t& p, const hp_yuv_image* frames, int n, std::vector<
 // and the pipe leaves the ring whatever the parser answered
 int collect_slots(hp_pipeline* pl, pipe_t& p, hp_human* out, int cap, int* n_out)
 {
-    const int rc = pl->kind == HP_PARSER_PAF ? hp_paf_collect(p.paf, out, cap, n_out)
-        : pl->kind == HP_PARSER_PPN        ? hp_ppn_collect(p.ppn, out, cap, n_out)
-                                           : hp_pifpaf_collect(p.pifpaf, out, cap, n_out);
+    const int rc = p.parser->collect(out, cap, n_out);
     p.n = 0, p.regions = 0;
     pl->tail = (pl->tail + 1) % pl->n_pipes;
     --pl->inflight;

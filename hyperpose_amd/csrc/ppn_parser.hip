@@ -17,6 +17,7 @@
 //
 // Compiled with -ffp-contract=off; the float expressions keep the reference's operand order.
 #include "hp_common.hpp"
+#include "parser_host.hpp"
 #include "libstdcxx_sort.hpp"
 
 #include <algorithm>
@@ -524,12 +525,10 @@ int assemble_frame(const int* hdr, const ppn_box* boxes, const ppn_cand* cands, 
 
 } // namespace
 
-struct hp_ppn {
-    int net_w, net_h, max_batch;
+struct hp_ppn final : hp::parser_session {
+    int net_w, net_h;
     float point_thresh, limb_thresh, nms_thresh;
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
-    hp::dev_buf in[7];
+    hp::staged_input in[7];
     // compacted lists: device memory (read by ppn_assemble_kernel); the host copies are filled on demand only (a declined frame,
     // HP_PPN_HOST_TAIL=1)
     hp::dev_buf d_hdr, d_boxes, d_cands;
@@ -540,9 +539,31 @@ struct hp_ppn {
     hp::dev_buf d_spill;             // [B][PPN_MAXH - PPN_MAXP] fragments beyond the LDS list
     std::vector<int> last_flags;
     bool host_tail = false; // HP_PPN_HOST_TAIL=1: the device tail is not launched, every frame takes the host statements
-    int pending = 0;        // frames enqueued and not yet collected
     int K = 0;
+
+    ~hp_ppn() override { drain(); }
+    // the engine's seven outputs, sorted by name, are the reference's argument order (src/pose_proposal.cpp:12-20)
+    int engine_outputs() const override { return 7; }
+    int enqueue_outputs(hp_engine* e, int n, hipStream_t s) override
+    {
+        const char* name = nullptr;
+        const float* d[7];
+        int sh[7][3];
+        for (int t = 0; t < 7; ++t)
+            HP_TRY(hp_engine_output(e, t, &name, sh[t], &d[t]));
+        // the edge tensor leaves the network as [E*nh*nw, gh, gw] (pose_proposal/model.py:104-109): nh = nw = sqrt(C / E) with E = 17 limbs
+        const int E = 17, nn = sh[6][0] / E;
+        int nh = 1;
+        while (nh * nh < nn)
+            ++nh;
+        HP_REQUIRE(nh * nh * E == sh[6][0], HP_ERR_INVALID, "hp_pipeline: edge output has %d channels, expected 17 * k * k", sh[6][0]);
+        const int es[5] = { E, nh, nh, sh[6][1], sh[6][2] };
+        return hp_ppn_enqueue(this, n, d, sh[0], es, s);
+    }
+    int collect(hp_human* out, int cap_per_frame, int* n_out) override { return hp_ppn_collect(this, out, cap_per_frame, n_out); }
 };
+
+hp::parser_session* hp::session_of(hp_ppn* p) { return p; }
 
 extern "C" {
 
@@ -550,10 +571,9 @@ int hp_ppn_create(hp_ppn** out, int net_w, int net_h, float point_thresh, float 
 {
     HP_REQUIRE(out && net_w > 0 && net_h > 0 && max_batch >= 1, HP_ERR_INVALID, "hp_ppn_create: bad argument");
     std::unique_ptr<hp_ppn> p(new hp_ppn());
-    p->net_w = net_w, p->net_h = net_h, p->max_batch = max_batch;
+    p->net_w = net_w, p->net_h = net_h;
     p->point_thresh = point_thresh, p->limb_thresh = limb_thresh, p->nms_thresh = nms_thresh;
-    HP_HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    HP_HIP_TRY(hipEventCreateWithFlags(&p->done, hipEventDisableTiming));
+    HP_TRY(p->open(max_batch));
     const size_t B = max_batch;
     HP_TRY(p->d_hdr.alloc(B * HDR * sizeof(int)));
     HP_TRY(p->d_boxes.alloc(B * PPN_K * PPN_MAXB * sizeof(ppn_box)));
@@ -568,20 +588,7 @@ int hp_ppn_create(hp_ppn** out, int net_w, int net_h, float point_thresh, float 
     return HP_OK;
 }
 
-void hp_ppn_destroy(hp_ppn* p)
-{
-    if (!p)
-        return;
-    if (p->stream) {
-        (void)hipStreamSynchronize(p->stream);
-        (void)hipStreamDestroy(p->stream);
-    }
-    if (p->done) {
-        (void)hipEventSynchronize(p->done);
-        (void)hipEventDestroy(p->done);
-    }
-    delete p;
-}
+void hp_ppn_destroy(hp_ppn* p) { delete p; }
 
 void* hp_ppn_stream(hp_ppn* p) { return p ? (void*)p->stream : nullptr; }
 
@@ -596,8 +603,7 @@ static int ppn_launch(hp_ppn* p, int n, const float* const tensors[7], const int
     hipStream_t s)
 {
     HP_REQUIRE(p && tensors && conf_shape && edge_shape, HP_ERR_INVALID, "hp_ppn: null argument");
-    HP_REQUIRE(n >= 1 && n <= p->max_batch, HP_ERR_CAPACITY, "hp_ppn: batch %d > max_batch %d", n, p->max_batch);
-    HP_REQUIRE(p->pending == 0, HP_ERR_STATE, "hp_ppn: a batch is already in flight, collect it first");
+    HP_TRY(p->begin("hp_ppn", n));
     ppn_geom g;
     g.K = conf_shape[0], g.gh = conf_shape[1], g.gw = conf_shape[2];
     g.E = edge_shape[0], g.nh = edge_shape[1], g.nw = edge_shape[2];
@@ -613,13 +619,8 @@ static int ppn_launch(hp_ppn* p, int n, const float* const tensors[7], const int
     }
     if (!on_device) {
         const size_t map_b = (size_t)g.K * g.gh * g.gw * sizeof(float), edge_b = (size_t)g.E * g.nh * g.nw * g.gh * g.gw * sizeof(float);
-        for (int t = 0; t < 7; ++t) {
-            const size_t per = t == 6 ? edge_b : map_b;
-            if (p->in[t].bytes < per * p->max_batch)
-                HP_TRY(p->in[t].alloc(per * p->max_batch));
-            HP_HIP_TRY(hipMemcpyAsync(p->in[t].p, tensors[t], per * n, hipMemcpyHostToDevice, s));
-            d[t] = p->in[t].as<float>();
-        }
+        for (int t = 0; t < 7; ++t)
+            HP_TRY(p->in[t].stage(tensors[t], t == 6 ? edge_b : map_b, n, p->max_batch, s, &d[t]));
     }
     // tensor order: 0 conf_point, 1 conf_iou (ignored, pose_proposal.cpp:74), 2 x, 3 y, 4 w, 5 h, 6 edge
     const size_t lds = ((size_t)PPN_K * g.gh * g.gw + (size_t)PPN_K * PPN_MAXB) * sizeof(ppn_box);
@@ -633,73 +634,39 @@ static int ppn_launch(hp_ppn* p, int n, const float* const tensors[7], const int
             p->net_w, p->net_h, g.K, p->h_humans.as<hp_human>(), PPN_MAXH, p->h_counts.as<int>(), p->h_counts.as<int>() + p->max_batch, p->d_spill.as<hp_human>());
         HP_HIP_TRY(hipGetLastError());
     }
-    HP_HIP_TRY(hipEventRecord(p->done, s));
-    p->pending = n;
     p->K = g.K;
-    return HP_OK;
+    return p->launched(n, s);
 }
 
 int hp_ppn_enqueue(hp_ppn* p, int n, const float* const dev_tensors[7], const int conf_shape[3], const int edge_shape[5], void* stream)
 {
-    return ppn_launch(p, n, dev_tensors, conf_shape, edge_shape, 1, stream ? (hipStream_t)stream : (p ? p->stream : nullptr));
+    return ppn_launch(p, n, dev_tensors, conf_shape, edge_shape, 1, p ? p->stream_or_own(stream) : nullptr);
 }
-
-namespace {
-struct ppn_job {
-    hp_ppn* p;
-    hp_human* out;
-    int cap;
-    int* n_out;
-    std::vector<int> frames; // the frames that take the host statements
-    std::vector<int> rc;
-};
-void ppn_frame(int k, int, void* ctx)
-{
-    ppn_job& j = *static_cast<ppn_job*>(ctx);
-    hp_ppn* p = j.p;
-    const int f = j.frames[k];
-    const int* hdr = p->h_hdr.data() + (size_t)f * HDR;
-    std::vector<hp_human> poses;
-    assemble_frame(hdr, p->h_boxes.data() + (size_t)f * PPN_K * PPN_MAXB, p->h_cands.data() + (size_t)f * PPN_LIMBS * PPN_MAXC, p->net_w, p->net_h,
-        p->K, poses);
-    j.n_out[f] = (int)poses.size();
-    if ((int)poses.size() > j.cap)
-        j.rc[f] = 2;
-    if (j.out)
-        std::copy(poses.begin(), poses.begin() + std::min<size_t>(poses.size(), j.cap), j.out + (size_t)f * j.cap);
-}
-} // namespace
 
 int hp_ppn_collect(hp_ppn* p, hp_human* out, int cap_per_frame, int* n_out)
 {
     HP_REQUIRE(p && n_out, HP_ERR_INVALID, "hp_ppn_collect: null argument");
-    HP_REQUIRE(p->pending > 0, HP_ERR_STATE, "hp_ppn_collect: nothing was enqueued");
-    const int n = p->pending;
-    p->pending = 0;
-    HP_HIP_TRY(hipEventSynchronize(p->done));
-    ppn_job job{ p, out, cap_per_frame, n_out, {}, std::vector<int>(n, 0) };
+    int n = 0;
+    HP_TRY(p->wait("hp_ppn_collect", &n));
+    hp::frame_results res{ "ppn", out, cap_per_frame, n_out, std::vector<std::string>(n) };
+    auto overflowed = [&](int f) { // an extract-kernel list overflowed
+        n_out[f] = 0;
+        res.fail(f, "ppn: frame %d overflowed a device list (1=survivors/class>%d, 2=candidates/limb>%d)", f, PPN_MAXB, PPN_MAXC);
+    };
+    std::vector<int> host_frames; // the frames that take the host statements
     const int* counts = p->h_counts.as<int>();
     const int* flags = counts + p->max_batch;
     for (int f = 0; f < n; ++f) {
         const int fl = p->host_tail ? 0 : flags[f];
         p->last_flags[f] = p->host_tail ? -1 : fl;
-        if (p->host_tail || (fl & (PPN_FLAG_POSES | PPN_FLAG_HASH | PPN_FLAG_OUT))) {
-            job.frames.push_back(f); // declined by the device tail (or HP_PPN_HOST_TAIL=1): the host statements take the frame
-            continue;
-        }
-        if (fl) { // an extract-kernel list overflowed
-            job.rc[f] = 1;
-            n_out[f] = 0;
-            continue;
-        }
-        const int nh = counts[f];
-        n_out[f] = nh;
-        if (nh > cap_per_frame)
-            job.rc[f] = 2;
-        if (out)
-            memcpy(out + (size_t)f * cap_per_frame, p->h_humans.as<hp_human>() + (size_t)f * PPN_MAXH, sizeof(hp_human) * std::min(nh, cap_per_frame));
+        if (p->host_tail || (fl & (PPN_FLAG_POSES | PPN_FLAG_HASH | PPN_FLAG_OUT)))
+            host_frames.push_back(f); // declined by the device tail (or HP_PPN_HOST_TAIL=1): the host statements take the frame
+        else if (fl)
+            overflowed(f);
+        else
+            res.deliver(f, p->h_humans.as<hp_human>() + (size_t)f * PPN_MAXH, counts[f], counts[f]);
     }
-    if (!job.frames.empty()) {
+    if (!host_frames.empty()) {
         // rare path: fetch the compacted lists of the batch and run the reference's statements on the host
         if (p->h_boxes.empty())
             p->h_boxes.resize((size_t)p->max_batch * PPN_K * PPN_MAXB), p->h_cands.resize((size_t)p->max_batch * PPN_LIMBS * PPN_MAXC);
@@ -710,26 +677,21 @@ int hp_ppn_collect(hp_ppn* p, hp_human* out, int cap_per_frame, int* n_out)
         HP_HIP_TRY(hipMemcpyAsync(p->h_cands.data(), p->d_cands.p, (size_t)n * PPN_LIMBS * PPN_MAXC * sizeof(ppn_cand), hipMemcpyDeviceToHost, p->stream));
         HP_HIP_TRY(hipStreamSynchronize(p->stream));
         std::vector<int> todo;
-        for (int f : job.frames) {
-            if (p->h_hdr[(size_t)f * HDR + PPN_K + PPN_LIMBS] != 0) { // (host-tail mode: the extract kernel's own overflow flags)
-                job.rc[f] = 1;
-                n_out[f] = 0;
-            } else
+        for (int f : host_frames) {
+            if (p->h_hdr[(size_t)f * HDR + PPN_K + PPN_LIMBS] != 0) // (host-tail mode: the extract kernel's own overflow flags)
+                overflowed(f);
+            else
                 todo.push_back(f);
         }
-        job.frames = todo;
-        hp::frame_pool::instance().run((int)job.frames.size(), ppn_frame, &job);
+        hp::on_host_pool((int)todo.size(), [&](int k, int) {
+            const int f = todo[k];
+            std::vector<hp_human> poses;
+            assemble_frame(p->h_hdr.data() + (size_t)f * HDR, p->h_boxes.data() + (size_t)f * PPN_K * PPN_MAXB,
+                p->h_cands.data() + (size_t)f * PPN_LIMBS * PPN_MAXC, p->net_w, p->net_h, p->K, poses);
+            res.deliver(f, poses.data(), (int)poses.size(), (int)poses.size());
+        });
     }
-    int rc = HP_OK;
-    for (int f = 0; f < n; ++f)
-        if (job.rc[f] == 1) {
-            hp::set_error("ppn: frame %d overflowed a device list (1=survivors/class>%d, 2=candidates/limb>%d)", f, PPN_MAXB, PPN_MAXC);
-            rc = HP_ERR_CAPACITY;
-        } else if (job.rc[f] == 2) {
-            hp::set_error("ppn: frame %d has %d humans, capacity %d", f, n_out[f], cap_per_frame);
-            rc = HP_ERR_CAPACITY;
-        }
-    return rc;
+    return res.code();
 }
 
 int hp_ppn_decode_flags(hp_ppn* p, int* flags, int n)

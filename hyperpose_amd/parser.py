@@ -16,22 +16,24 @@ from ._lib import CONN_DTYPE, HUMAN_DTYPE, PEAK_DTYPE, Conn, Human, Peak, as_ptr
 _FP = C.POINTER(C.c_float)
 
 
-class Paf:
-    """``hyperpose::parser::paf`` (conf_thresh=0.05, paf_thresh=0.05, resolution_size=(-1,-1))."""
+class _Parser:
+    """What the three parsers share: the handle of kind ``_KIND`` (``hp_<kind>_create`` ... ``hp_<kind>_destroy``), the buffers a
+    batch's humans come back in, the parser's own stream, and the asynchronous half's ``collect``."""
 
-    def __init__(self, conf_thresh: float = 0.05, paf_thresh: float = 0.05, resolution_size=(-1, -1),
-                 max_batch: int = 8, cap_per_frame: int = 128):
+    _KIND = ""
+
+    def __init__(self, max_batch: int, cap_per_frame: int, *create_args):
         self._h = C.c_void_p()
-        self.max_batch = int(max_batch)
-        self.cap = int(cap_per_frame)
-        w, h = resolution_size  # cv::Size(width, height)
-        check(lib().hp_paf_create(C.byref(self._h), C.c_float(conf_thresh), C.c_float(paf_thresh), int(w), int(h),
-                                  self.max_batch))
+        self.max_batch, self.cap = int(max_batch), int(cap_per_frame)
+        check(self._fn("create")(C.byref(self._h), *create_args, self.max_batch))
         self._out = (Human * (self.max_batch * self.cap))()
         self._n = (C.c_int * self.max_batch)()
         self._pending = 0
-        lib().hp_paf_stream.restype = C.c_void_p
-        self.stream = lib().hp_paf_stream(self._h)
+        self._fn("stream").restype = C.c_void_p
+        self.stream = self._fn("stream")(self._h)
+
+    def _fn(self, name: str):
+        return getattr(lib(), f"hp_{self._KIND}_{name}")
 
     def after(self, stream) -> None:
         """Work enqueued on the parser's own stream from now on waits for everything already enqueued on ``stream``."""
@@ -39,7 +41,7 @@ class Paf:
 
     def close(self):
         if self._h:
-            lib().hp_paf_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -48,15 +50,33 @@ class Paf:
         except Exception:
             pass
 
+    def _humans(self, n: int):
+        arr = np.frombuffer(self._out, dtype=HUMAN_DTYPE)
+        return [arr[f * self.cap: f * self.cap + self._n[f]].copy() for f in range(n)]
+
+    def collect(self):
+        """The humans of the enqueued batch, one structured array per frame (HP_ERR_STATE when nothing was enqueued)."""
+        n = self._pending
+        check(self._fn("collect")(self._h, self._out, self.cap, self._n))
+        self._pending = 0
+        return self._humans(n)
+
+
+class Paf(_Parser):
+    """``hyperpose::parser::paf`` (conf_thresh=0.05, paf_thresh=0.05, resolution_size=(-1,-1))."""
+
+    _KIND = "paf"
+
+    def __init__(self, conf_thresh: float = 0.05, paf_thresh: float = 0.05, resolution_size=(-1, -1),
+                 max_batch: int = 8, cap_per_frame: int = 128):
+        w, h = resolution_size  # cv::Size(width, height)
+        super().__init__(max_batch, cap_per_frame, C.c_float(conf_thresh), C.c_float(paf_thresh), int(w), int(h))
+
     def set_paf_thresh(self, thresh: float):
         check(lib().hp_paf_set_paf_thresh(self._h, C.c_float(thresh)))
 
     def set_conf_thresh(self, thresh: float):
         check(lib().hp_paf_set_conf_thresh(self._h, C.c_float(thresh)))
-
-    def _humans(self, n: int):
-        arr = np.frombuffer(self._out, dtype=HUMAN_DTYPE)
-        return [arr[f * self.cap: f * self.cap + self._n[f]].copy() for f in range(n)]
 
     def process(self, conf: np.ndarray, paf: np.ndarray):
         """One frame, host arrays conf [J,rows,cols], paf [2L,rows,cols] -> structured array of humans."""
@@ -86,12 +106,6 @@ class Paf:
         check(lib().hp_paf_enqueue(self._h, n, as_ptr(conf_dev), cs, as_ptr(paf_dev), ps,
                                    C.c_void_p(stream) if stream else None))
         self._pending = n
-
-    def collect(self):
-        n = self._pending
-        check(lib().hp_paf_collect(self._h, self._out, self.cap, self._n))
-        self._pending = 0
-        return self._humans(n)
 
     # ---- stage-wise parity taps -------------------------------------------------------------------
     def debug_peaks(self, frame: int = 0, cap: int = 16384) -> np.ndarray:
@@ -136,30 +150,16 @@ def preproc_u8hwc_to_f32nchw(images: np.ndarray, factor: float = 1.0 / 255, flip
     return dout.to_numpy(np.float32, (n, 3, h, w))
 
 
-class PoseProposal:
+class PoseProposal(_Parser):
     """``hyperpose::parser::pose_proposal`` (net_resolution, point_thresh=0.10, limb_thresh=0.05, mns_thresh=0.3),
     reference include/hyperpose/operator/parser/proposal_network.hpp:17-81."""
 
+    _KIND = "ppn"
+
     def __init__(self, net_resolution, point_thresh: float = 0.10, limb_thresh: float = 0.05, mns_thresh: float = 0.3,
                  max_batch: int = 32, cap_per_frame: int = 128):
-        self._h = C.c_void_p()
-        self.max_batch, self.cap = int(max_batch), int(cap_per_frame)
         w, h = net_resolution  # cv::Size(width, height)
-        check(lib().hp_ppn_create(C.byref(self._h), int(w), int(h), C.c_float(point_thresh), C.c_float(limb_thresh),
-                                  C.c_float(mns_thresh), self.max_batch))
-        self._out = (Human * (self.max_batch * self.cap))()
-        self._n = (C.c_int * self.max_batch)()
-
-    def close(self):
-        if self._h:
-            lib().hp_ppn_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(max_batch, cap_per_frame, int(w), int(h), C.c_float(point_thresh), C.c_float(limb_thresh), C.c_float(mns_thresh))
 
     def set_thresholds(self, point_thresh, limb_thresh, nms_thresh):
         check(lib().hp_ppn_set_thresholds(self._h, C.c_float(point_thresh), C.c_float(limb_thresh), C.c_float(nms_thresh)))
@@ -176,8 +176,7 @@ class PoseProposal:
             ptrs = (C.c_void_p * 7)(*[as_ptr(t).value for t in tensors])
         cs, es = (C.c_int * 3)(*conf_shape), (C.c_int * 5)(*edge_shape)
         check(lib().hp_ppn_process_batch(self._h, n, ptrs, cs, es, int(on_device), self._out, self.cap, self._n))
-        arr = np.frombuffer(self._out, dtype=HUMAN_DTYPE)
-        return [arr[f * self.cap: f * self.cap + self._n[f]].copy() for f in range(n)]
+        return self._humans(n)
 
     def process(self, tensors):
         return self.process_batch([np.asarray(t)[None] for t in tensors])[0]
@@ -195,35 +194,15 @@ class PoseProposal:
         check(lib().hp_ppn_decode_flags(self._h, fl, n))
         return np.array(fl[:n])
 
-    def collect(self):
-        n = self._pending
-        check(lib().hp_ppn_collect(self._h, self._out, self.cap, self._n))
-        self._pending = 0
-        arr = np.frombuffer(self._out, dtype=HUMAN_DTYPE)
-        return [arr[f * self.cap: f * self.cap + self._n[f]].copy() for f in range(n)]
 
-
-class PifPaf:
+class PifPaf(_Parser):
     """``hyperpose::parser::pifpaf(h, w, thresh=0.1)`` (reference include/hyperpose/operator/parser/pifpaf.hpp:8-26).
     ``process(paf, pif)`` takes the tensors in the order of the reference's .cpp (src/pifpaf.cpp:7)."""
 
+    _KIND = "pifpaf"
+
     def __init__(self, h: int, w: int, thresh: float = 0.1, max_batch: int = 8, cap_per_frame: int = 128):
-        self._h = C.c_void_p()
-        self.max_batch, self.cap = int(max_batch), int(cap_per_frame)
-        check(lib().hp_pifpaf_create(C.byref(self._h), int(h), int(w), C.c_float(thresh), self.max_batch))
-        self._out = (Human * (self.max_batch * self.cap))()
-        self._n = (C.c_int * self.max_batch)()
-
-    def close(self):
-        if self._h:
-            lib().hp_pifpaf_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(max_batch, cap_per_frame, int(h), int(w), C.c_float(thresh))
 
     def process_batch(self, paf, pif, on_device: bool = False, n: int = None, fh: int = None, fw: int = None):
         if not on_device:
@@ -234,8 +213,7 @@ class PifPaf:
         else:
             a, b = as_ptr(paf), as_ptr(pif)
         check(lib().hp_pifpaf_process_batch(self._h, n, a, b, fh, fw, int(on_device), self._out, self.cap, self._n))
-        arr = np.frombuffer(self._out, dtype=HUMAN_DTYPE)
-        return [arr[f * self.cap: f * self.cap + self._n[f]].copy() for f in range(n)]
+        return self._humans(n)
 
     def process(self, paf, pif):
         return self.process_batch(np.asarray(paf)[None], np.asarray(pif)[None])[0]
@@ -250,10 +228,3 @@ class PifPaf:
     def enqueue(self, dev_paf, dev_pif, n: int, fh: int, fw: int, stream=None):
         check(lib().hp_pifpaf_enqueue(self._h, n, as_ptr(dev_paf), as_ptr(dev_pif), fh, fw, C.c_void_p(stream) if stream else None))
         self._pending = n
-
-    def collect(self):
-        n = self._pending
-        check(lib().hp_pifpaf_collect(self._h, self._out, self.cap, self._n))
-        self._pending = 0
-        arr = np.frombuffer(self._out, dtype=HUMAN_DTYPE)
-        return [arr[f * self.cap: f * self.cap + self._n[f]].copy() for f in range(n)]

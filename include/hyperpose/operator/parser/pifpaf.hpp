@@ -3,13 +3,8 @@
 // src/pifpaf.cpp:7; its header names them the other way round).  The engine also emits them as [171,h,w] / [85,h,w].
 #pragma once
 #include <cassert>
-#include <cstdlib>
-#include <iostream>
-#include <memory>
-#include <vector>
 
-#include "../../../hp_hip.h"
-#include "../../utility/data.hpp"
+#include "detail.hpp"
 
 namespace hyperpose::parser {
 
@@ -32,29 +27,13 @@ public:
     std::vector<human_t> process(const feature_map_t& paf, const feature_map_t& pif)
     {
         const int fh = pif.shape()[pif.shape().size() - 2], fw = pif.shape().back(); // src/pifpaf.cpp:23-24
-        // maps that still lie in their engine's device buffers: the whole batch is decoded in one launch when its first frame is asked for
-        // (operator/parser/paf.hpp has the reasoning; utility/data.hpp the record)
-        const detail::device_batch* b = paf.device_batch();
-        if (b && b == pif.device_batch() && paf.batch_frame() == pif.batch_frame() && !std::getenv("HP_MIRROR_HOST_MAPS")) {
-            if (m_cached.lock().get() != b || m_cached_gen != b->gen) {
-                ensure(b->n);
-                std::vector<hp_human> out((size_t)b->n * CAP);
-                std::vector<int> cnt(b->n);
-                if (hp_pifpaf_process_batch(m_h, b->n, b->outs[paf.batch_output()].dev, b->outs[pif.batch_output()].dev, fh, fw, 1, out.data(), CAP, cnt.data()) != HP_OK)
-                    fatal(hp_last_error());
-                m_cache.assign(b->n, {});
-                for (int f = 0; f < b->n; ++f)
-                    m_cache[f] = convert(out.data() + (size_t)f * CAP, cnt[f]);
-                m_cached = paf.batch_handle(), m_cached_gen = b->gen;
-            }
-            return m_cache[paf.batch_frame()];
-        }
-        ensure(1);
-        std::vector<hp_human> out(CAP);
-        int n = 0;
-        if (hp_pifpaf_process_batch(m_h, 1, paf.view<float>(), pif.view<float>(), fh, fw, 0, out.data(), CAP, &n) != HP_OK)
-            fatal(hp_last_error());
-        return convert(out.data(), n);
+        // maps that still lie in their engine's device buffers: the whole batch in one launch (detail.hpp, batch_cache)
+        const bool same = paf.device_batch() == pif.device_batch() && paf.batch_frame() == pif.batch_frame();
+        if (const std::vector<human_t>* hit = m_cache.frame(paf, same, [&](const detail::device_batch& b) {
+                return run(b.n, b.outs[paf.batch_output()].dev, b.outs[pif.batch_output()].dev, fh, fw, 1);
+            }))
+            return *hit;
+        return std::move(run(1, paf.view<float>(), pif.view<float>(), fh, fw, 0)[0]);
     }
     template <typename C>
     std::vector<human_t> process(C&& feature_map_containers)
@@ -64,21 +43,11 @@ public:
     }
 
 private:
-    static constexpr int CAP = 128;
-    [[noreturn]] static void fatal(const char* msg)
+    [[noreturn]] static void fatal(const char* msg) { detail::fatal(msg, true); }
+    std::vector<std::vector<human_t>> run(int n, const float* paf, const float* pif, int fh, int fw, int on_device)
     {
-        std::cerr << "[HyperPose::ERROR  ] " << msg << "\n";
-        std::exit(-1);
-    }
-    static std::vector<human_t> convert(const hp_human* out, int n)
-    {
-        std::vector<human_t> ret(n);
-        for (int i = 0; i < n; ++i) {
-            ret[i].score = out[i].score;
-            for (int k = 0; k < COCO_N_PARTS; ++k)
-                ret[i].parts[k] = body_part_t{ out[i].parts[k].has_value != 0, out[i].parts[k].x, out[i].parts[k].y, out[i].parts[k].score };
-        }
-        return ret;
+        ensure(n);
+        return detail::parse_batch(n, true, [&](hp_human* out, int cap, int* cnt) { return hp_pifpaf_process_batch(m_h, n, paf, pif, fh, fw, on_device, out, cap, cnt); });
     }
     void ensure(int batch) // a decoder handle that takes `batch` frames per call (rebuilt when a larger batch arrives)
     {
@@ -94,9 +63,7 @@ private:
     float m_keypoint_thresh;
     hp_pifpaf* m_h = nullptr;
     int m_handle_batch = 0;
-    std::weak_ptr<detail::device_batch> m_cached;
-    uint64_t m_cached_gen = 0;
-    std::vector<std::vector<human_t>> m_cache;
+    detail::batch_cache m_cache;
 };
 
 } // namespace hyperpose::parser

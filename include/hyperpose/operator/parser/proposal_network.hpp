@@ -2,11 +2,8 @@
 // reference class (include/hyperpose/operator/parser/proposal_network.hpp:17-81, src/pose_proposal.cpp).
 #pragma once
 #include <cassert>
-#include <cstdlib>
-#include <iostream>
 
-#include "../../../hp_hip.h"
-#include "../../utility/data.hpp"
+#include "detail.hpp"
 
 namespace hyperpose {
 namespace parser {
@@ -34,38 +31,21 @@ namespace parser {
                     es[i] = edge.shape()[i];
             else if (edge.shape().size() == 3) // [L*9*9, h, w], the layout the engine emits
                 es[0] = edge.shape()[0] / 81;
-            // maps that still lie in their engine's device buffers: the whole batch in one launch when its first frame is asked for
-            // (operator/parser/paf.hpp has the reasoning; utility/data.hpp the record)
+            // maps that still lie in their engine's device buffers: the whole batch in one launch (detail.hpp, batch_cache)
             const feature_map_t* maps[7] = { &conf_point, &conf_iou, &x, &y, &w, &h, &edge };
-            const detail::device_batch* b = conf_point.device_batch();
-            bool on_dev = b && !std::getenv("HP_MIRROR_HOST_MAPS");
-            for (int k = 1; k < 7 && on_dev; ++k)
-                on_dev = maps[k]->device_batch() == b && maps[k]->batch_frame() == conf_point.batch_frame();
-            if (on_dev) {
-                if (m_cached.lock().get() != b || m_cached_gen != b->gen) {
-                    ensure(b->n);
+            bool same = true;
+            for (int k = 1; k < 7 && same; ++k)
+                same = maps[k]->device_batch() == conf_point.device_batch() && maps[k]->batch_frame() == conf_point.batch_frame();
+            if (const std::vector<human_t>* hit = m_cache.frame(conf_point, same, [&](const detail::device_batch& b) {
                     const float* t[7];
                     for (int k = 0; k < 7; ++k)
-                        t[k] = b->outs[maps[k]->batch_output()].dev;
-                    std::vector<hp_human> out((size_t)b->n * CAP);
-                    std::vector<int> cnt(b->n);
-                    if (hp_ppn_process_batch(m_h, b->n, t, cs, es, 1, out.data(), CAP, cnt.data()) != HP_OK)
-                        fatal(hp_last_error());
-                    m_cache.assign(b->n, {});
-                    for (int f = 0; f < b->n; ++f)
-                        m_cache[f] = convert(out.data() + (size_t)f * CAP, cnt[f]);
-                    m_cached = conf_point.batch_handle(), m_cached_gen = b->gen;
-                }
-                return m_cache[conf_point.batch_frame()];
-            }
-            ensure(1);
+                        t[k] = b.outs[maps[k]->batch_output()].dev;
+                    return run(b.n, t, cs, es, 1);
+                }))
+                return *hit;
             const float* t[7] = { conf_point.view<float>(), conf_iou.view<float>(), x.view<float>(), y.view<float>(), w.view<float>(),
                 h.view<float>(), edge.view<float>() };
-            std::vector<hp_human> out(CAP);
-            int n = 0;
-            if (hp_ppn_process_batch(m_h, 1, t, cs, es, 0, out.data(), CAP, &n) != HP_OK)
-                fatal(hp_last_error());
-            return convert(out.data(), n);
+            return std::move(run(1, t, cs, es, 0)[0]);
         }
         inline std::vector<human_t> process(const std::vector<feature_map_t>& l)
         {
@@ -85,27 +65,17 @@ namespace parser {
         void set_nms_thresh(float thresh) { m_nms_thresh = thresh, push(); }
 
     private:
-        static constexpr int CAP = 128;
-        [[noreturn]] static void fatal(const char* msg)
-        {
-            std::cerr << "[HyperPose::ERROR  ] " << msg << "\n";
-            std::exit(-1);
-        }
+        [[noreturn]] static void fatal(const char* msg) { detail::fatal(msg, true); }
         void push()
         {
-            m_cached.reset();
+            m_cache.reset();
             if (m_h)
                 hp_ppn_set_thresholds(m_h, m_point_thresh, m_limb_thresh, m_nms_thresh);
         }
-        static std::vector<human_t> convert(const hp_human* out, int n)
+        std::vector<std::vector<human_t>> run(int n, const float* const t[7], const int cs[3], const int es[5], int on_device)
         {
-            std::vector<human_t> ret(n);
-            for (int i = 0; i < n; ++i) {
-                ret[i].score = out[i].score;
-                for (int k = 0; k < COCO_N_PARTS; ++k)
-                    ret[i].parts[k] = body_part_t{ out[i].parts[k].has_value != 0, out[i].parts[k].x, out[i].parts[k].y, out[i].parts[k].score };
-            }
-            return ret;
+            ensure(n);
+            return detail::parse_batch(n, true, [&](hp_human* out, int cap, int* cnt) { return hp_ppn_process_batch(m_h, n, t, cs, es, on_device, out, cap, cnt); });
         }
         void ensure(int batch) // a parser handle that takes `batch` frames per call (rebuilt when a larger batch arrives)
         {
@@ -121,9 +91,7 @@ namespace parser {
         float m_point_thresh, m_limb_thresh, m_nms_thresh;
         hp_ppn* m_h = nullptr;
         int m_handle_batch = 0;
-        std::weak_ptr<detail::device_batch> m_cached;
-        uint64_t m_cached_gen = 0;
-        std::vector<std::vector<human_t>> m_cache;
+        detail::batch_cache m_cache;
     };
 
 } // namespace parser
