@@ -14,7 +14,7 @@
 #include "conv_i8.hpp"
 #include "conv_kernels.hpp"
 #include "engine_timeline.hpp"
-#include "graph_cache.hpp"
+#include "call_plan.hpp"
 #include "hp_common.hpp"
 #include "weight_pack.hpp"
 
@@ -214,7 +214,7 @@ struct hp_engine {
     hp::host_buf ovf_flag;
     bool split_off = false;
     int split_fallbacks = 0;
-    struct { const void* input = nullptr; size_t frame_bytes = 0; int n = 0, on_device = 0, kind = 0; void* stream = nullptr; } last; // the newest hp_engine_infer_* call
+    hp::call_args last; // the newest hp_engine_infer_* call
     bool split_overflowed() const { return dtype == HP_DTYPE_F32S && !split_off && ovf_flag.p && *static_cast<volatile unsigned*>(ovf_flag.p) != 0; }
     int leave_split(); // stop using conv32_direct_kernel: drop the captured graphs (they hold its launches), count the event
     hp::engine_switches switches; // read_engine_switches() at hp_engine_create / hp_engine_load
@@ -238,7 +238,12 @@ struct hp_engine {
     };
     std::vector<arena_buf> arena;
     size_t arena_private_bytes = 0; // what the same tensors took with one allocation each
-    hp::dev_buf in_stage; // staging for host inputs
+    hp::dev_buf in_stage; // staging for host inputs, and the hp_engine_profile* calls' synthetic batch: max_batch fp32 frames
+    int ensure_in_stage()
+    {
+        const size_t need = (size_t)max_batch * in_h * in_w * 3 * sizeof(float);
+        return in_stage.bytes < need ? in_stage.alloc(need) : HP_OK;
+    }
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // hp_engine_set_concurrency(2): a batch runs as two half-batches, the second on `stream2` (fork / join by events; inside a captured graph:
@@ -247,8 +252,7 @@ struct hp_engine {
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 
-    // captured graphs keyed by (n, input pointer, kind, first frame): csrc/graph_cache.hpp has the rules of their lifetime
-    using graph_key = hp::graph_key;
+    // captured graphs keyed by (n, input pointer, kind, first frame): csrc/graph_cache.hpp has the rules of their lifetime, call_plan.hpp the keys
     struct graph_destroy {
         void operator()(hipGraphExec_t g) const { (void)hipGraphExecDestroy(g); }
     };
@@ -348,9 +352,9 @@ struct hp_engine {
     template <typename V>
     float* fused_output(size_t layer, bool whole_tensor_only, V& out);
     int pointwise_params(size_t layer, int H, int W, int cout_pad, hp::conv_params& q); // the 1 x 1 second half of a fused fp16 pair
-    // host_src != nullptr (eager launches of a host batch): every range copies ITS frames to the device on ITS stream first (frame_bytes each)
+    hp::call_settings call_settings(bool ensemble, bool graph) const { return { max_batch, parts, halves_ok(), ensemble, graph }; }
+    int run_call(const hp::call_settings& cfg, const hp::call_args& a); // one call, from its arguments to its launches: csrc/call_plan.hpp decides
     // ---- running the schedule: const, `steps` is written by build(), apply_int8_scales() and nobody else
-    int enqueue(const uint8_t* u8, const float* f32, int n, hipStream_t s, const void* host_src = nullptr, size_t frame_bytes = 0) const;
     int enqueue_range(const uint8_t* u8, const float* f32, int b0, int n, hipStream_t s) const;
     // the step's parameters for frames [b0, b0 + n) of the batch at u8 / f32, as its launch gets them (and whether it is the int8 launch)
     launch_payload bound(const step& st, const uint8_t* u8, const float* f32, int n, int b0) const;
@@ -362,7 +366,6 @@ struct hp_engine {
     int tile_of(launch_kind kind, const launch_payload& bound) const;
     int step_tile(const step& st, int n) const; // hp_layer_time::tile: which kernel form the step launches on n frames (0: ops with one form)
     void fill_row(hp_layer_time* out, int k, int cap, const step& st, int n, float ms) const; // a profile row
-    int stage_profile_input();                  // in_stage as the hp_engine_profile* calls' synthetic max_batch input
 };
 
 bool hp_engine::tensor_is_read(int t) const
@@ -1951,43 +1954,75 @@ void hp_engine::fill_row(hp_layer_time* out, int k, int cap, const step& st, int
     out[k].flops = st.flops * n, out[k].bytes = st.bytes * n;
 }
 
-int hp_engine::stage_profile_input()
+// One call as csrc/call_plan.hpp plans it (refusals are the caller's); eager and captured calls differ only in how a range is run (`run`)
+int hp_engine::run_call(const hp::call_settings& cfg, const hp::call_args& a)
 {
-    const size_t need = (size_t)max_batch * in_h * in_w * 3 * sizeof(float); // (only timing matters)
-    if (in_stage.bytes < need)
-        HP_TRY(in_stage.alloc(need));
-    return HP_OK;
-}
-
-int hp_engine::enqueue(const uint8_t* u8, const float* f32, int n, hipStream_t s, const void* host_src, size_t frame_bytes) const
-{
-    unsigned char* const dev_in = u8 ? (unsigned char*)u8 : (unsigned char*)f32;
-    auto h2d = [&](int b0, int cnt, hipStream_t st) -> int {
-        if (host_src)
-            HP_HIP_TRY(hipMemcpyAsync(dev_in + (size_t)b0 * frame_bytes, (const unsigned char*)host_src + (size_t)b0 * frame_bytes, (size_t)cnt * frame_bytes, hipMemcpyHostToDevice, st));
+    if (hp::reads_in_stage(cfg, a))
+        HP_TRY(ensure_in_stage());
+    const hp::call_plan p = hp::plan_call(cfg, { in_stage.p, flip_in.p }, a);
+    const hipStream_t s = a.stream ? (hipStream_t)a.stream : stream;
+    const size_t frame_bytes = (size_t)in_h * in_w * 3 * (p.kind == 1 ? sizeof(float) : 1);
+    auto stream_of = [&](int i) { return p.ranges[i].second ? stream2 : s; };
+    auto upload = [&](int b0, int cnt, hipStream_t st) -> int { // host frames [b0, b0 + cnt) to the buffer the network reads
+        HP_HIP_TRY(hipMemcpyAsync((unsigned char*)p.read + b0 * frame_bytes, (const unsigned char*)p.host_src + b0 * frame_bytes, cnt * frame_bytes, hipMemcpyHostToDevice, st));
         return HP_OK;
     };
-    if (parts < 2 || !halves_ok() || n < 2) {
-        HP_TRY(h2d(0, n, s));
-        return enqueue_range(u8, f32, 0, n, s);
-    }
-    // two half-batches side by side: frames [0, n0) on `s`, frames [n0, n) on stream2, which joins `s` again.  The kernels of one half are
-    // half as many blocks - what fills the chip is that the two halves are never in the same phase (a store-bound launch of one runs under an
-    // MFMA-bound launch of the other): measured 2490 -> 1962 us per synchronous batch of 8 (profiles/r06_half_batch_probe.txt).  Frames are
-    // independent and every kernel is batch-invariant bit for bit (tests), so the outputs are those of the one-stream schedule.
-    // (A host batch goes up in two copies, each on the stream that reads it: an event recorded behind ONE hipMemcpyAsync from pageable memory
-    // does not cover all of that copy's staged chunks - measured: stream2's first layer now and then read a few stale input rows of frames 4 / 5
-    // of 8, tools/r6_halves_debug.py - while a kernel behind the copy on the same stream always saw it complete.)
-    const int n0 = (n + 1) / 2;
-    HP_HIP_TRY(hipEventRecord(ev_fork, s));
-    HP_HIP_TRY(hipStreamWaitEvent(stream2, ev_fork, 0));
-    HP_TRY(h2d(0, n0, s));
-    HP_TRY(h2d(n0, n - n0, stream2));
-    HP_TRY(enqueue_range(u8, f32, 0, n0, s));
-    HP_TRY(enqueue_range(u8, f32, n0, n - n0, stream2));
-    HP_HIP_TRY(hipEventRecord(ev_join, stream2));
-    HP_HIP_TRY(hipStreamWaitEvent(s, ev_join, 0));
-    return HP_OK;
+    auto range = [&](int i) -> int {
+        return enqueue_range(p.kind == 0 ? (const uint8_t*)p.read : nullptr, p.kind == 1 ? (const float*)p.read : nullptr, p.ranges[i].b0, p.ranges[i].cnt, stream_of(i));
+    };
+    auto bracketed = [&](auto&& inner) -> int { // the ensemble's flip and merge around `inner`, on the call's stream (images / 2: the caller's frames)
+        if (p.ensemble)
+            HP_TRY(flip_stage((const uint8_t*)p.fl_src, p.images / 2, s));
+        HP_TRY(inner());
+        return p.ensemble ? flip_merge(p.images / 2, s) : HP_OK;
+    };
+    // capture a range's schedule once per key; replays cost one launch.  A call names ALL its ranges at once: the cache decides about eviction
+    // before the first capture, so no executable of this call can be destroyed before it is launched (csrc/graph_cache.hpp), and a call whose
+    // keys are cached costs its look-ups.
+    hipGraphExec_t exec[2] = { nullptr, nullptr };
+    auto capture = [&](int i, hipGraphExec_t* made) -> int {
+        hipGraph_t graph = nullptr;
+        HP_HIP_TRY(hipStreamBeginCapture(stream_of(i), hipStreamCaptureModeThreadLocal));
+        const int rc = p.stage_inside ? bracketed([&] { return range(i); }) : range(i);
+        const hipError_t ee = hipStreamEndCapture(stream_of(i), &graph);
+        if (rc != HP_OK) {
+            if (graph)
+                (void)hipGraphDestroy(graph);
+            return rc;
+        }
+        HP_HIP_TRY(ee);
+        const hipError_t ie = hipGraphInstantiate(made, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        HP_HIP_TRY(ie);
+        return HP_OK;
+    };
+    if (p.captured)
+        HP_TRY(graphs.acquire(p.keys, p.nr, exec, capture, sync_device));
+    if (p.host_src && p.ensemble)
+        HP_TRY(upload(0, p.images / 2, s));
+    // Two half-batches side by side: frames [0, n0) on `s`, [n0, n) on stream2, which joins `s` again.  The kernels of one half are half as many
+    // blocks - what fills the chip is that the halves are never in the same phase (a store-bound launch of one runs under an MFMA-bound launch of
+    // the other): 2490 -> 1962 us per synchronous batch of 8 (profiles/r06_half_batch_probe.txt).  Frames are independent and every kernel is
+    // batch-invariant bit for bit (tests).  Captured: two graphs on two streams - ONE graph with two branches is replayed branch after branch.
+    auto run = [&]() -> int {
+        if (p.nr == 2) {
+            HP_HIP_TRY(hipEventRecord(ev_fork, s));
+            HP_HIP_TRY(hipStreamWaitEvent(stream2, ev_fork, 0));
+        }
+        for (int i = 0; i < p.nr && p.host_src && !p.ensemble; ++i) // (the second half's frames cross PCIe under the first half's first layers)
+            HP_TRY(upload(p.ranges[i].b0, p.ranges[i].cnt, stream_of(i)));
+        for (int i = 0; i < p.nr; ++i)
+            if (p.captured)
+                HP_HIP_TRY(hipGraphLaunch(exec[i], stream_of(i)));
+            else
+                HP_TRY(range(i));
+        if (p.nr == 2) {
+            HP_HIP_TRY(hipEventRecord(ev_join, stream2));
+            HP_HIP_TRY(hipStreamWaitEvent(s, ev_join, 0));
+        }
+        return HP_OK;
+    };
+    return p.captured && p.stage_inside ? run() : bracketed(run); // (one captured range holds flip and merge itself)
 }
 
 hp::engine_switches hp::read_engine_switches()
@@ -2158,132 +2193,37 @@ int hp_engine::leave_split()
     return HP_OK;
 }
 
-static int infer_common(hp_engine* e, const void* input, size_t frame_bytes, int n, int on_device, void* stream, int kind)
+static int infer_common(hp_engine* e, const hp::call_args& a)
 {
-    HP_REQUIRE(e && input, HP_ERR_INVALID, "hp_engine_infer: null argument");
+    HP_REQUIRE(e && a.input, HP_ERR_INVALID, "hp_engine_infer: null argument");
     if (e->split_overflowed()) // an earlier batch held a value outside fp16's range: from here on the fp32 matrix pipe
         HP_TRY(e->leave_split());
-    e->last.input = input, e->last.frame_bytes = frame_bytes, e->last.n = n, e->last.on_device = on_device, e->last.kind = kind, e->last.stream = stream;
-    HP_REQUIRE(n >= 1, HP_ERR_INVALID, "hp_engine_infer: empty batch");
+    e->last = a;
+    const hp::call_settings cfg = e->call_settings(e->flip_on(), e->use_graph);
+    const hp::call_refusal why = hp::refusal_of(cfg, a);
+    HP_REQUIRE(why != hp::CALL_EMPTY, HP_ERR_INVALID, "hp_engine_infer: empty batch");
     // TensorRT builds no kINT8 engine without a calibrator or per-tensor dynamic ranges; here the engine exists and refuses to run
     for (float v : e->i8_scale)
         HP_REQUIRE(v >= 0.f, HP_ERR_STATE,
             "hp_engine_infer: the HP_DTYPE_I8 engine is not calibrated: call hp_engine_calibrate_u8 (calibrate()) or hp_engine_set_int8_scales first");
     // src/tensorrt.cpp:439-443 throws std::logic_error here
-    HP_REQUIRE(n <= e->max_batch, HP_ERR_CAPACITY, "Input batch size overflow: Yours@%d Max@%d", n, e->max_batch);
-    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    const void* dev_in = input;
-    // Flip ensemble: the schedule below runs on the 2n frames of flip_in as a device batch; `staged` brackets it with the flip and the merge.
-    // A host batch goes up into flip_in here (never part of a captured graph, as below); a device batch is copied there by flip_stage.
-    const bool fl = e->flip_on();
-    const uint8_t* fl_src = nullptr;
-    if (fl) {
-        HP_REQUIRE(kind == 0, HP_ERR_STATE, "hp_engine_infer_f32: not available while the flip ensemble is on (it is defined on u8 frames: hp_engine_infer_u8)");
-        HP_REQUIRE(2 * n <= e->max_batch, HP_ERR_CAPACITY, "Input batch size overflow: Yours@%d, with the flip ensemble on %d network images, Max@%d", n, 2 * n,
-            e->max_batch);
-        if (on_device)
-            fl_src = (const uint8_t*)input;
-        else
-            HP_HIP_TRY(hipMemcpyAsync(e->flip_in.p, input, frame_bytes * n, hipMemcpyHostToDevice, s));
-        dev_in = e->flip_in.p, on_device = 1, n *= 2;
-    }
-    const bool halves = e->parts == 2 && e->halves_ok() && n >= 2;
-    // the schedule of frames [b0, b0 + cnt) of the batch; with the ensemble on and one stream, flip and merge around it (captured with it)
-    auto staged = [&](const uint8_t* u8, const float* f32, int b0, int cnt, hipStream_t cs) -> int {
-        if (fl && !halves)
-            HP_TRY(e->flip_stage(fl_src, cnt / 2, cs));
-        HP_TRY(e->enqueue_range(u8, f32, b0, cnt, cs));
-        return fl && !halves ? e->flip_merge(cnt / 2, cs) : HP_OK;
-    };
-    if (!on_device) {
-        const size_t need = (size_t)e->max_batch * e->in_h * e->in_w * 3 * sizeof(float);
-        if (e->in_stage.bytes < need)
-            HP_TRY(e->in_stage.alloc(need));
-        // (the copy is not part of the captured schedule; two half-batches: each half goes up on the stream that reads it, below)
-        if (e->use_graph && !(e->parts == 2 && e->halves_ok() && n >= 2))
-            HP_HIP_TRY(hipMemcpyAsync(e->in_stage.p, input, frame_bytes * n, hipMemcpyHostToDevice, s));
-        dev_in = e->in_stage.p;
-    }
-    const uint8_t* u8 = kind == 0 ? (const uint8_t*)dev_in : nullptr;
-    const float* f32 = kind == 1 ? (const float*)dev_in : nullptr;
-    if (!e->use_graph) {
-        if (fl)
-            HP_TRY(e->flip_stage(fl_src, n / 2, s));
-        HP_TRY(e->enqueue(u8, f32, n, s, on_device ? nullptr : input, frame_bytes));
-        return fl ? e->flip_merge(n / 2, s) : HP_OK; // (two half-batches: behind the join)
-    }
-
-    // capture a range's schedule once per (frames, input buffer, first frame); replays cost one launch.  A call names ALL its ranges at once:
-    // the cache decides about eviction before the first capture, so no executable of this call can be destroyed before it is launched
-    // (csrc/graph_cache.hpp), and a call whose keys are cached costs its look-ups.
-    struct range {
-        int b0, cnt;
-        hipStream_t cs;
-    };
-    auto graphs_for = [&](const range* r, int nr, hipGraphExec_t* out) -> int {
-        // (a one-stream ensemble graph holds the copy from the caller's device buffer: keyed by that pointer; the half-batch graphs read flip_in
-        // alone - flip and merge are launched around them - and are keyed by it; both apart from the plain graphs by kind)
-        hp_engine::graph_key keys[2];
-        for (int i = 0; i < nr; ++i)
-            keys[i] = hp_engine::graph_key{ r[i].cnt, fl_src && !halves ? (const void*)fl_src : dev_in, fl ? 2 : kind, r[i].b0 };
-        auto capture = [&](int i, hipGraphExec_t* exec) -> int {
-            hipGraph_t graph = nullptr;
-            HP_HIP_TRY(hipStreamBeginCapture(r[i].cs, hipStreamCaptureModeThreadLocal));
-            const int rc = staged(u8, f32, r[i].b0, r[i].cnt, r[i].cs);
-            const hipError_t ee = hipStreamEndCapture(r[i].cs, &graph);
-            if (rc != HP_OK) {
-                if (graph)
-                    (void)hipGraphDestroy(graph);
-                return rc;
-            }
-            HP_HIP_TRY(ee);
-            const hipError_t ie = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            HP_HIP_TRY(ie);
-            return HP_OK;
-        };
-        return e->graphs.acquire(keys, nr, out, capture, sync_device);
-    };
-    if (halves) {
-        // two half-batches side by side (hp_engine::enqueue has the reasoning): ONE graph with two branches is replayed branch after branch by
-        // the runtime (measured: 2.27 -> 2.22 ms per call), two graphs on two streams run side by side (the probe's 2.49 -> 1.96 ms)
-        const int n0 = (n + 1) / 2;
-        const range both[2] = { { 0, n0, s }, { n0, n - n0, e->stream2 } };
-        hipGraphExec_t g2[2] = { nullptr, nullptr };
-        HP_TRY(graphs_for(both, 2, g2));
-        const hipGraphExec_t ga = g2[0], gb = g2[1];
-        if (fl) // the frames are the first half-batch, their flips the second: written before the fork, merged behind the join
-            HP_TRY(e->flip_stage(fl_src, n0, s));
-        HP_HIP_TRY(hipEventRecord(e->ev_fork, s));
-        HP_HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_fork, 0));
-        if (!on_device) { // the second half's frames cross PCIe under the first half's first layers
-            HP_HIP_TRY(hipMemcpyAsync(e->in_stage.p, input, frame_bytes * n0, hipMemcpyHostToDevice, s));
-            HP_HIP_TRY(hipMemcpyAsync(e->in_stage.as<unsigned char>() + frame_bytes * n0, (const unsigned char*)input + frame_bytes * n0, frame_bytes * (n - n0),
-                hipMemcpyHostToDevice, e->stream2));
-        }
-        HP_HIP_TRY(hipGraphLaunch(ga, s));
-        HP_HIP_TRY(hipGraphLaunch(gb, e->stream2));
-        HP_HIP_TRY(hipEventRecord(e->ev_join, e->stream2));
-        HP_HIP_TRY(hipStreamWaitEvent(s, e->ev_join, 0));
-        return fl ? e->flip_merge(n0, s) : HP_OK;
-    }
-    const range whole{ 0, n, s };
-    hipGraphExec_t g = nullptr;
-    HP_TRY(graphs_for(&whole, 1, &g));
-    HP_HIP_TRY(hipGraphLaunch(g, s));
-    return HP_OK;
+    HP_REQUIRE(why != hp::CALL_OVERFLOW, HP_ERR_CAPACITY, "Input batch size overflow: Yours@%d Max@%d", a.n, e->max_batch);
+    HP_REQUIRE(why != hp::CALL_F32_ENSEMBLE, HP_ERR_STATE, "hp_engine_infer_f32: not available while the flip ensemble is on (it is defined on u8 frames: hp_engine_infer_u8)");
+    HP_REQUIRE(why != hp::CALL_ENSEMBLE_OVERFLOW, HP_ERR_CAPACITY, "Input batch size overflow: Yours@%d, with the flip ensemble on %d network images, Max@%d", a.n,
+        2 * a.n, e->max_batch);
+    return e->run_call(cfg, a);
 }
 
 int hp_engine_infer_u8(hp_engine* e, const uint8_t* hwc_bgr, int n, int on_device, void* stream)
 {
     HP_REQUIRE(e, HP_ERR_INVALID, "hp_engine_infer_u8: null engine");
-    return infer_common(e, hwc_bgr, (size_t)e->in_h * e->in_w * 3, n, on_device, stream, 0);
+    return infer_common(e, { hwc_bgr, n, on_device, 0, stream });
 }
 
 int hp_engine_infer_f32(hp_engine* e, const float* nchw, int n, int on_device, void* stream)
 {
     HP_REQUIRE(e, HP_ERR_INVALID, "hp_engine_infer_f32: null engine");
-    return infer_common(e, nchw, (size_t)e->in_h * e->in_w * 3 * sizeof(float), n, on_device, stream, 1);
+    return infer_common(e, { nchw, n, on_device, 1, stream });
 }
 
 int hp_engine_synchronize(hp_engine* e)
@@ -2297,7 +2237,7 @@ int hp_engine_synchronize(hp_engine* e)
         // pipe before the caller reads them (a host input is copied again from the caller's buffer, which the API keeps valid until the
         // outputs are read)
         HP_TRY(e->leave_split());
-        HP_TRY(infer_common(e, e->last.input, e->last.frame_bytes, e->last.n, e->last.on_device, e->last.stream, e->last.kind));
+        HP_TRY(infer_common(e, e->last));
         HP_HIP_TRY(hipStreamSynchronize(e->last.stream ? (hipStream_t)e->last.stream : e->stream));
     }
     return HP_OK;
@@ -2346,20 +2286,10 @@ int hp_engine_calibrate_u8(hp_engine* e, const uint8_t* hwc_bgr, int n, int on_d
     hp::dev_buf amax;
     HP_TRY(amax.alloc((size_t)NL * sizeof(unsigned)));
     HP_HIP_TRY(hipMemsetAsync(amax.p, 0, (size_t)NL * sizeof(unsigned), e->stream));
-    const size_t frame_bytes = (size_t)e->in_h * e->in_w * 3;
-    if (!on_device) {
-        const size_t need = (size_t)e->max_batch * frame_bytes * sizeof(float); // (the size infer_common keeps)
-        if (e->in_stage.bytes < need)
-            HP_TRY(e->in_stage.alloc(need));
-    }
+    const hp::call_settings eager = e->call_settings(false, false); // (calibration ignores the ensemble setting)
     for (int b0 = 0; b0 < n; b0 += e->max_batch) {
         const int cnt = std::min(e->max_batch, n - b0);
-        const uint8_t* src = hwc_bgr + (size_t)b0 * frame_bytes;
-        if (!on_device) {
-            HP_HIP_TRY(hipMemcpyAsync(e->in_stage.p, src, (size_t)cnt * frame_bytes, hipMemcpyHostToDevice, e->stream));
-            src = e->in_stage.as<uint8_t>();
-        }
-        HP_TRY(e->enqueue(src, nullptr, cnt, e->stream));
+        HP_TRY(e->run_call(eager, { hwc_bgr + (size_t)b0 * e->in_h * e->in_w * 3, cnt, on_device, 0, e->stream }));
         for (const auto& st : e->steps) {
             if (!st.int8())
                 continue;
@@ -2575,7 +2505,7 @@ int hp_engine_debug_raw_tensor(hp_engine* e, int tensor, void* host, size_t cap_
 int hp_engine_profile(hp_engine* e, int n, int iters, hp_layer_time* out, int cap, int* n_out)
 {
     HP_REQUIRE(e && n >= 1 && n <= e->max_batch && iters >= 1 && n_out, HP_ERR_INVALID, "hp_engine_profile: bad argument");
-    HP_TRY(e->stage_profile_input());
+    HP_TRY(e->ensure_in_stage());
     const uint8_t* u8 = e->in_stage.as<uint8_t>();
     int k = 0;
     for (const step& st : e->steps) {
@@ -2604,8 +2534,8 @@ int hp_engine_profile_pair(hp_engine* e, hp_engine* f, int n, int iters, hp_laye
         HP_REQUIRE(e->steps[i].op == f->steps[i].op && e->steps[i].layer == f->steps[i].layer && e->steps[i].flops == f->steps[i].flops
                 && e->steps[i].bytes == f->steps[i].bytes,
             HP_ERR_INVALID, "hp_engine_profile_pair: the engines' schedules differ at step %zu", i);
-    HP_TRY(e->stage_profile_input());
-    HP_TRY(f->stage_profile_input());
+    HP_TRY(e->ensure_in_stage());
+    HP_TRY(f->ensure_in_stage());
     int k = 0;
     for (size_t i = 0; i < e->steps.size(); ++i) {
         const step &sa = e->steps[i], &sb = f->steps[i];
@@ -2635,7 +2565,7 @@ int hp_engine_profile_pair(hp_engine* e, hp_engine* f, int n, int iters, hp_laye
 int hp_engine_profile_sequence(hp_engine* e, int n, int iters, hp_layer_time* out, int cap, int* n_out)
 {
     HP_REQUIRE(e && n >= 1 && n <= e->max_batch && iters >= 1 && n_out, HP_ERR_INVALID, "hp_engine_profile_sequence: bad argument");
-    HP_TRY(e->stage_profile_input());
+    HP_TRY(e->ensure_in_stage());
     const uint8_t* u8 = e->in_stage.as<uint8_t>();
     const size_t ns = e->steps.size();
     // one (start, stop) event pair per step; the launch itself records them (hipExtLaunchKernelGGL), so they bracket the

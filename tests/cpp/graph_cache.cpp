@@ -1,15 +1,16 @@
-// Host-only check of csrc/graph_cache.hpp, the cache of captured-graph executables that hp_engine's infer_common, drop_graphs and destructor
+// Host-only check of csrc/graph_cache.hpp, the cache of captured-graph executables that hp_engine's run_call, drop_graphs and destructor
 // use.  The executables are integers; a ledger records for each: created, in flight on stream k, destroyed.  `engine_sim` replays the
 // engine's call: one acquire() for all keys of the call (the whole batch, or its two halves with concurrency 2), then one launch per
 // executable on its stream; now and then a stream or the device is synchronised, or a setting changes (drop).  The ledger reports
 //   a launch of a destroyed handle, a destroy of a handle in flight, a double destroy, a leak at the end, a size above the bound,
 //   and any eviction, synchronisation or capture on a call whose keys all hit.
+// The keys of a call are the engine's own: csrc/call_plan.hpp plans every simulated call, device or host batch, flip ensemble on or off.
 // Seeded key streams: one or two keys per call, pointer pools of 1, 8, 33, 64, 65 and 200, n = 1 .. 8, both entries, three streams, drops,
-// and sequences that sit exactly at the bound.  So that the checker cannot go blind, `parent_sim` restates the order the engine had before
+// once with plain device batches alone and once mixed with host batches and the ensemble, and sequences that sit exactly at the bound.  So that the checker cannot go blind, `parent_sim` restates the order the engine had before
 // this header (look up the first half; look up the second and, on a miss above the bound, synchronise three streams and destroy everything;
 // launch the first half) and runs through the same ledger: it MUST report a launch of a destroyed handle, and a destroy of a handle in
 // flight on a caller's stream.  Prints "OK <checks>".
-#include "../../hyperpose_amd/csrc/graph_cache.hpp"
+#include "../../hyperpose_amd/csrc/call_plan.hpp"
 
 #include <cstdint>
 #include <cstdio>
@@ -117,35 +118,36 @@ static_assert(cache_t::bound == BOUND, "the issue keeps the bound at 64");
 
 static const void* ptr_of(int i) { return (const void*)(uintptr_t)(0x7f0000001000ull + 4608ull * (unsigned)i); }
 
-// the keys of one call, as infer_common forms them
-static int keys_of(const void* p, int n, int kind, int parts, hp::graph_key keys[2], int streams[2], int s)
+// the keys of one call and the streams of their launches, as the engine forms them: csrc/call_plan.hpp, for an fp32 engine (half-batches
+// allowed) of max_batch 16 with captured graphs on, its staging buffer and its flip buffer at two addresses no pool pointer has
+static const void* const IN_STAGE = (const void*)(uintptr_t)0x7e0000001000ull;
+static const void* const FLIP_IN = (const void*)(uintptr_t)0x7e0000002000ull;
+static int keys_of(const void* p, int n, int kind, int parts, hp::graph_key keys[2], int streams[2], int s, bool ensemble = false, bool on_device = true)
 {
-    if (parts == 2 && n >= 2) {
-        const int n0 = (n + 1) / 2;
-        keys[0] = hp::graph_key{ n0, p, kind, 0 }, streams[0] = s;
-        keys[1] = hp::graph_key{ n - n0, p, kind, n0 }, streams[1] = S_SECOND;
-        return 2;
-    }
-    keys[0] = hp::graph_key{ n, p, kind, 0 }, streams[0] = s;
-    return 1;
+    const hp::call_plan plan = hp::plan_call({ 16, parts, true, ensemble, true }, { IN_STAGE, FLIP_IN }, { p, n, on_device, kind, nullptr });
+    CHECK(plan.refusal == hp::CALL_OK, "a simulated call of %d frames, kind %d, was refused (%d)", n, kind, (int)plan.refusal);
+    for (int i = 0; i < plan.nr; ++i)
+        keys[i] = plan.keys[i], streams[i] = plan.ranges[i].second ? S_SECOND : s;
+    return plan.nr;
 }
 
-// ---- the engine's order: graph_cache.hpp as infer_common, drop_graphs and the destructor use it
+// ---- the engine's order: graph_cache.hpp as run_call, drop_graphs and the destructor use it
 struct engine_sim {
     ledger& L;
     cache_t cache;
     int parts = 1;
+    bool ensemble = false; // hp_engine_set_flip_ensemble
     int fail_make_at = -1; // make(i) fails for this i (a capture that fails)
     explicit engine_sim(ledger& l)
         : L(l)
         , cache(fake_destroy{ &l })
     {
     }
-    int call(const void* p, int n, int kind, int s)
+    int call(const void* p, int n, int kind, int s, bool on_device = true)
     {
         hp::graph_key keys[2];
         int streams[2], out[2] = { 0, 0 };
-        const int nk = keys_of(p, n, kind, parts, keys, streams, s);
+        const int nk = keys_of(p, n, kind, parts, keys, streams, s, ensemble, on_device);
         int want[2];
         bool all_hit = true;
         for (int i = 0; i < nk; ++i)
@@ -239,10 +241,10 @@ static void expect_clean(const ledger& L, const char* what)
 }
 
 // a seeded stream of calls over a pool of pointers
-static void random_run(int pool, int parts0, unsigned seed, int calls)
+static void random_run(int pool, int parts0, unsigned seed, int calls, bool mixed)
 {
     char what[96];
-    std::snprintf(what, sizeof what, "pool %d parts %d seed %u", pool, parts0, seed);
+    std::snprintf(what, sizeof what, "pool %d parts %d seed %u%s", pool, parts0, seed, mixed ? " mixed" : "");
     ledger L;
     int evictions = 0;
     {
@@ -253,7 +255,12 @@ static void random_run(int pool, int parts0, unsigned seed, int calls)
         static const int call_streams[3] = { S_OWN, S_A, S_B };
         for (int c = 0; c < calls; ++c) {
             const int destroys = L.destroys;
-            e.call(ptr_of(pick(pool)), 1 + pick(8), pick(4) == 0 ? 1 : 0, call_streams[pick(3)]);
+            if (!mixed)
+                e.call(ptr_of(pick(pool)), 1 + pick(8), pick(4) == 0 ? 1 : 0, call_streams[pick(3)]);
+            else { // a fifth of the calls bring a host batch (the pointer is then the caller's host buffer); the ensemble takes u8 frames only
+                const bool on_device = pick(5) != 0;
+                e.call(ptr_of(pick(pool)), 1 + pick(8), !e.ensemble && pick(4) == 0 ? 1 : 0, call_streams[pick(3)], on_device);
+            }
             evictions += L.destroys > destroys;
             const int r = pick(100);
             if (r < 10)
@@ -264,15 +271,19 @@ static void random_run(int pool, int parts0, unsigned seed, int calls)
                 e.drop();
                 if (pick(2))
                     e.parts = 3 - e.parts;
+                else if (mixed)
+                    e.ensemble = !e.ensemble;
             }
         }
         L.sync_device(); // hp_engine_destroy; then the cache's destructor
     }
     expect_clean(L, what);
     // n in 1 .. 8 and two entries: a pointer has 16 keys with one stream and 30 with two halves (n = 1: one key, n >= 2: two); a pool whose keys
-    // all fit may never evict
-    if (pool * 30 <= (int)BOUND)
-        CHECK(evictions == 0, "%s: %d evictions with at most %d keys", what, evictions, pool * 30);
+    // all fit may never evict.  (Mixed: the staging buffer is one pointer more; under the ensemble a pointer has 8 keys with one stream, and with
+    // two halves all calls share flip_in's 16; a change of concurrency or ensemble drops, so only one setting's keys live at a time.)
+    const int most_keys = (pool + (mixed ? 1 : 0)) * 30;
+    if (most_keys <= (int)BOUND)
+        CHECK(evictions == 0, "%s: %d evictions with at most %d keys", what, evictions, most_keys);
     if (pool >= 33)
         CHECK(evictions > 0, "%s: the run never reached eviction", what);
 }
@@ -341,6 +352,30 @@ static void at_the_bound()
             L.sync_device();
         }
         expect_clean(L, "hit + miss on a full cache");
+    }
+    { // the ensemble and host batches: which pointer a call is keyed by
+        ledger L;
+        {
+            engine_sim e(L);
+            e.ensemble = true; // one stream, device batches: the caller's pointer, so 64 pointers fill the cache and the 65th empties it
+            for (int i = 0; i < 65; ++i)
+                e.call(ptr_of(i), 2, 0, S_OWN);
+            CHECK(L.created == 65 && L.destroys == 64 && e.cache.size() == 1, "ensemble, 65 pointers: %d captures, %d destroys", L.created, L.destroys);
+            e.drop();
+            e.parts = 2; // two halves read flip_in alone: every pointer, and a host batch, has the same two keys
+            for (int i = 0; i < 70; ++i)
+                e.call(ptr_of(i), 2, 0, i & 1 ? S_A : S_OWN, i % 7 != 0);
+            CHECK(L.created == 67 && e.cache.size() == 2, "ensemble with two halves, 70 pointers: %d captures, %zu entries", L.created - 65, e.cache.size());
+            e.drop();
+            e.ensemble = false; // host batches are keyed by the staging buffer: 70 host buffers, 2 halves, one capture each
+            for (int i = 0; i < 70; ++i)
+                e.call(ptr_of(i), 3, 0, S_B, false);
+            CHECK(L.created == 69 && e.cache.size() == 2, "70 host batches: %d captures, %zu entries", L.created - 67, e.cache.size());
+            e.call(ptr_of(0), 3, 0, S_B); // the same frames as a device batch: keys of their own
+            CHECK(L.created == 71 && e.cache.size() == 4, "a device batch after host batches: %zu entries", e.cache.size());
+            L.sync_device();
+        }
+        expect_clean(L, "ensemble and host batches");
     }
     { // a capture that fails: what was made before it stays cached and is destroyed once
         ledger L;
@@ -437,7 +472,8 @@ int main()
     for (int pool : { 1, 8, 33, 64, 65, 200 })
         for (int parts : { 1, 2 })
             for (unsigned seed = 0; seed < 4; ++seed)
-                random_run(pool, parts, seed, 600);
+                for (bool mixed : { false, true })
+                    random_run(pool, parts, seed, 600, mixed);
     if (g_fail) {
         std::printf("FAILED %d of %d\n", g_fail, g_checks);
         return 1;

@@ -4,6 +4,7 @@ summation order: |err| <= 1e-4 * max|ref| (+ 1e-6), two orders of magnitude tigh
 VERDICT r3 item 3 asks for.  Small graphs cover every operator / option of the kernel family on the CPU oracle; the four BASELINE
 configurations run at their FULL size against the same definition evaluated by PyTorch's own fp32 GPU kernels.
 """
+import functools
 import os
 import tempfile
 
@@ -13,6 +14,7 @@ import pytest
 import footprint
 from hyperpose_amd import engine as E
 from hyperpose_amd import synth
+from hyperpose_amd._lib import DevBuf
 from oracle import ref_net
 from test_engine_gpu import Net, Out, _frames
 
@@ -523,6 +525,52 @@ def test_split_engine_leaves_the_fp16_pipe_when_a_value_does_not_fit(hp):
         _close32(got[b][0][1], ref["y"][b], "after the fall-back")
     got2 = big.inference(frames)
     assert big.split_fallbacks == 1 and np.array_equal(got2[0][0][1], got[0][0][1])
+
+
+@functools.lru_cache(maxsize=None)
+def _overflowing_net():
+    """The three-layer net of the test above with first-layer outputs ~ 1e6, and what its fall-back gives in the form that test runs
+    (concurrency 1, host batch, captured graphs): the reference of every other form, computed once."""
+    net = Net(21)
+    t0 = net.conv(0, 3, 32, 3, 1, act=E.ACT_NONE)
+    t1 = net.conv(t0, 32, 64, 3, 1, act=E.ACT_NONE)
+    t2 = net.conv(t1, 64, 64, 1, 1, act=E.ACT_NONE)
+    frames = _frames(2, 24, 32, seed=21)
+    make = lambda: E.Engine(net.layers, [Out("y", t2, 0, 64).c()], net.blob(), 32, 24, 2, dtype="f32s", factor=4000.0)  # noqa: E731
+    eng = make()
+    want = np.stack([img[0][1] for img in eng.inference(frames)])
+    assert eng.split_fallbacks == 1
+    return make, frames, want
+
+
+@pytest.mark.parametrize("on_device", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("graph", [True, False], ids=["graph", "eager"])
+@pytest.mark.parametrize("parts", [1, 2])
+def test_split_engine_fall_back_in_every_call_form(hp, parts, graph, on_device):
+    """hp_engine_synchronize's re-run replays the newest call as it was made: one stream or two half-batches, captured or eager, a host or a
+    device batch.  Each form gives the bytes of the form above (half-batches are batch-invariant), counts one fall-back, and stays there."""
+    make, frames, want = _overflowing_net()
+    eng = make()
+    eng.set_graph(graph)
+    eng.set_concurrency(parts)
+    assert eng.concurrency == parts
+    dev = DevBuf.from_numpy(frames) if on_device else None
+
+    def call():
+        if not on_device:
+            return np.stack([img[0][1] for img in eng.inference(frames)])
+        eng.enqueue_u8(dev, 2)
+        return eng.output_to_host(0, 2)
+
+    try:
+        got = call()
+        assert eng.split_fallbacks == 1
+        assert got.tobytes() == want.tobytes(), "after the fall-back: not the bytes of the one-stream, host, captured form"
+        assert call().tobytes() == want.tobytes() and eng.split_fallbacks == 1
+    finally:
+        eng.close()
+        if dev is not None:
+            dev.free()
 
 
 # ---- the BASELINE configurations at FULL size, one probed frame each, against PyTorch's own fp32 GPU kernels
