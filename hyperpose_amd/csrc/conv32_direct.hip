@@ -30,7 +30,7 @@
 //            is 16 channels, fragments hi | lo of 8 halves; fp32: a step is 8 channels, lane (row, h) holds channels 4h .. 4h + 3 and
 //            feeds element e to MFMA e, exactly like the B side - conv32_kernel's permutation): coalesced 1 KB loads straight from L2
 //            into registers, two steps ahead, never through LDS.
-#include "conv_fp32.hpp"
+#include "conv32_pick.hpp"
 
 #include "conv32_epilogue.hpp"
 #include "conv_device.hpp"
@@ -51,34 +51,7 @@ __device__ __forceinline__ long tvd_off(const tview32& t, int b, int y, int x)
     return ((long)b * t.img + (long)y * t.wp + x) * t.cs + t.coff;
 }
 
-template <bool SPLIT, int KS, int CK, int MW, int DWD = 0>
-struct direct32_geom {
-    static constexpr int HP = 8 + KS - 1;                          // halo tile is HP x HP pixels
-    static constexpr int PBU = CK / 4 + 1;                         // 16-byte units per halo pixel: CK elements of 4 bytes + one unit of padding (odd)
-    static constexpr int PB = PBU * 16;
-    static constexpr int RP = ((HP * PBU + 7) / 16 * 16 + 8) * 16; // pixel-row pitch in bytes: >= HP pixels, = 8 mod 16 units
-    static constexpr int LDS_BYTES = HP * RP;
-    static constexpr int QPP = CK / 4;                             // float4 quads per pixel
-    // DWD > 0 (a depthwise 3 x 3 of dilation DWD fused in front of the 1 x 1, KS = 1): the chunk's DEPTHWISE input - (8 + 2 DWD)^2 pixels x CK
-    // fp32 channels in pixel rows of PB bytes - is what arrives from HBM, into a second LDS tile behind the first; the depthwise outputs are
-    // computed from it into the first tile, which the MFMAs read as before.  The depthwise weights and biases of ALL chunks ([9][C] + [C]
-    // floats) sit behind that, loaded once per block.
-    static constexpr int XP = DWD ? 8 + 2 * DWD : HP;              // staged tile is XP x XP pixels
-    static constexpr int XT_BYTES = DWD ? XP * XP * PB : 0;
-    static constexpr int QUADS = XP * XP * QPP;                    // float4 quads staged per chunk
-    static constexpr int TM = SPLIT ? 2 : 1, TN = SPLIT ? 2 : 1, NWN = 2 / TN; // MFMA tiles per wavefront; wavefronts side by side over the pixels
-    static constexpr int SLABS = MW * NWN * (32 * (TM * 32 + 4) * 4); // the epilogue's transposition slabs (rows_geom<TM>::SLAB_BYTES per wavefront) lie over the dead tiles
-    static constexpr int TILES_BYTES = LDS_BYTES + XT_BYTES;
-    static constexpr int DWW_OFF = TILES_BYTES > SLABS ? TILES_BYTES : SLABS; // dynamic LDS: this + 40 bytes per depthwise channel (DWD)
-    static constexpr int KQ = SPLIT ? CK / 16 : CK / 8;            // steps per tap: 32 bytes of a pixel row each
-    static constexpr int SPC = KS * KS * KQ;                       // steps per chunk
-    static constexpr int RING = SPC % 3 == 0 ? 3 : (SPLIT ? 2 : 4); // A-fragment ring: the step in use + one or two in flight
-    static constexpr int AHEAD = RING - 1;                         // steps between an A fragment's request and its use
-    // chunks in flight between HBM and LDS (registers): a 1 x 1 layer's chunk is only KQ steps of MFMAs - far shorter than an HBM round trip
-    // under load - and Little's law asks for ~40 KB in flight per CU to stream at the rate the layer needs; a 3 x 3 chunk covers its successor
-    static constexpr int DEPTH = KS != 1 ? 1 : DWD ? (SPLIT && MW == 8 ? 1 : 2) : (SPLIT && (MW < 4 || MW == 8) ? 2 : 3); // (fewer threads share a tile's staging when MW < 4: 16 quads per thread and chunk at MW = 1)
-    static_assert(SPC % RING == 0 && SPC % 2 == 0, "ring / double buffer periods");
-};
+// (direct32_geom - a block's LDS layout and pipeline depths per instance - is conv32_pick.hpp's: the picker sizes the launch by it)
 
 } // namespace
 
@@ -434,42 +407,12 @@ __global__ __launch_bounds__(SPLIT ? 64 * MW : 128 * MW, (SPLIT && (MW < 4 || (D
 #undef HP_STAMP
 }
 
-// Which layers the direct kernels take: square 1 x 1 / 3 x 3, stride 1, dilation 1, SAME padding, channel slice readable in whole chunks
-// (32 channels at 3 x 3, 64 at 1 x 1).
-bool conv32_direct_ok(const conv32_params& p)
-{
-    return p.KH == p.KW && ((p.KH == 1 && p.Cin % 64 == 0) || (p.KH == 3 && p.Cin % 32 == 0)) && p.stride == 1 && p.dil == 1 && p.Cout_pad % 64 == 0
-        && p.OH == p.H && p.OW == p.W && p.pad_t == (p.KH - 1) / 2 && p.pad_l == (p.KW - 1) / 2;
-}
-
-// Wavefront groups per block.  All wavefronts of a block share one 8 x 8 pixel tile, so more of them amortise the tile's staging over more
-// output channels - but a layer needs enough blocks for 256 CUs.  SPLIT: MW wavefronts of 64 channels; fp32: MW x 2 wavefronts, 32 MW channels.
-// dwd = dilation of a depthwise 3 x 3 fused in front (0: none).  The fused forms exist for 2 / 4 (and, split at dilation 1, 8) groups only: a
-// fused layer takes the largest of those that still leaves enough blocks, 2 at least; 0 = no fused form fits (odd group count).
-static int direct_mw(const conv32_params& p, bool split, int dwd)
-{
-    const int groups = p.Cout_pad / (split ? 64 : 32);
-    const long tiles = (long)p.B * ((p.OH + 7) / 8) * ((p.OW + 7) / 8);
-    for (int mw : { 8, 4, 2, 1 }) {
-        if (mw == 8 && (!split || p.KH != 1 || dwd == 2))
-            continue; // (8 wavefronts of 64 channels: the split 1 x 1 layers with 512 outputs read their input tile once; behind a depthwise layer of dilation 2: 68 spilled registers - not compiled)
-        if (dwd && mw == 1)
-            break;
-        if (groups % mw == 0 && (mw == 1 || (dwd && mw == 2) || tiles * (groups / mw) >= (split ? 256 : 640)))
-            return mw;
-    }
-    return dwd ? 0 : 1;
-}
-static int direct_mw(const conv32_params& p, bool split) { return direct_mw(p, split, p.dw_w ? p.dw_dil : 0); }
-
-int conv32_direct_tile(const conv32_params& p, bool split) { return (split ? 33000000 : 34000000) + (p.dw_w ? 100000 * p.dw_dil : 0) + p.KH * 1000 + direct_mw(p, split); }
-
 // Host side: the packed fp32 matrix [tap][Cout_pad][Cin] (conv32_params::w's layout) in the kernels' fragment order.
 //   split: [chunk][tap][k16][32-row tile][hi | lo][lane][8 halves]      (2 * taps * cout_pad * cin halves)
 //   fp32:  [chunk][tap][k8][32-row tile][lane][4 floats], lane (row, h) = channels 8 k8 + 4 h + {0..3}   (taps * cout_pad * cin floats)
 void conv32_split_pack(const float* packed, int taps, int cout_pad, int cin, _Float16* out)
 {
-    const int ck = taps == 1 ? 64 : 32, kq = ck / 16, nch = cin / ck, MT = cout_pad / 32;
+    const int ck = pick32::direct_chunk(taps), kq = ck / 16, nch = cin / ck, MT = cout_pad / 32;
     for (int c = 0; c < nch; ++c)
         for (int t = 0; t < taps; ++t)
             for (int ks = 0; ks < kq; ++ks)
@@ -488,7 +431,7 @@ void conv32_split_pack(const float* packed, int taps, int cout_pad, int cin, _Fl
 
 void conv32_frag_pack(const float* packed, int taps, int cout_pad, int cin, float* out)
 {
-    const int ck = taps == 1 ? 64 : 32, kq = ck / 8, nch = cin / ck, MT = cout_pad / 32;
+    const int ck = pick32::direct_chunk(taps), kq = ck / 8, nch = cin / ck, MT = cout_pad / 32;
     for (int c = 0; c < nch; ++c)
         for (int t = 0; t < taps; ++t)
             for (int ks = 0; ks < kq; ++ks)
@@ -502,62 +445,32 @@ void conv32_frag_pack(const float* packed, int taps, int cout_pad, int cin, floa
                 }
 }
 
-// The depthwise-fused forms that are compiled: dilation 1 | 2; split: 2 / 4 / 8 wavefronts of 64 channels, fp32: 2 / 4 wavefront pairs of 32.
-bool conv32_dw_fusable(const conv32_params& p, bool split, int dil)
-{
-    return conv32_direct_ok(p) && p.KH == 1 && (dil == 1 || dil == 2) && direct_mw(p, split, dil) != 0;
-}
-
 template <bool SPLIT, int KS, int CK, int MW, int DWD>
-static hipError_t launch_direct_case(const conv32_params& p, dim3 grid, int tiles_x, int tiles_y, hipStream_t s)
+static hipError_t launch_direct_case(const conv32_params& p, const conv32_choice& c, hipStream_t s)
 {
-    using G = direct32_geom<SPLIT, KS, CK, MW, DWD>;
-    const size_t lds = (size_t)G::DWW_OFF + (DWD ? (size_t)40 * p.Cin : 0);
-    if (lds > 160 * 1024)
-        return hipErrorInvalidValue;
     static size_t granted = 0; // (per instantiation: the largest dynamic LDS size the runtime has been told about)
-    if (lds > 64 * 1024 && lds > granted) {
-        const hipError_t e = hipFuncSetAttribute((const void*)conv32_direct_kernel<SPLIT, KS, CK, MW, DWD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (c.lds > 64 * 1024 && c.lds > granted) {
+        const hipError_t e = hipFuncSetAttribute((const void*)conv32_direct_kernel<SPLIT, KS, CK, MW, DWD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds);
         if (e != hipSuccess)
             return e;
-        granted = lds;
+        granted = c.lds;
     }
-    HP_LAUNCH((conv32_direct_kernel<SPLIT, KS, CK, MW, DWD>), grid, dim3((SPLIT ? 64 : 128) * MW), lds, s, p, tiles_x, tiles_y);
+    HP_LAUNCH((conv32_direct_kernel<SPLIT, KS, CK, MW, DWD>), dim3(c.grid_x, c.grid_y), dim3(c.threads), c.lds, s, p, c.tiles_x, c.tiles_y);
     return hipGetLastError();
 }
 
+// Which instance and grid: pick_conv32 (conv32_pick.hpp; no engine switch bears on this form); not ok = no compiled instance takes the layer
 hipError_t launch_conv32_direct(const conv32_params& p, bool split, hipStream_t s)
 {
-    if (!conv32_direct_ok(p) || !(split ? (const void*)p.w_split : (const void*)p.w_frag) || p.npix <= 0)
+    if (!(split ? (const void*)p.w_split : (const void*)p.w_frag) || p.npix <= 0)
         return hipErrorInvalidValue;
-    const int tiles_x = (p.OW + 7) / 8, tiles_y = (p.OH + 7) / 8, mw = direct_mw(p, split);
-    const dim3 grid(tiles_x * tiles_y * p.B, p.Cout_pad / ((split ? 64 : 32) * mw));
-    const int dwd = p.dw_w ? p.dw_dil : 0;
-#define HP_DIRECT_CASE(SPLIT_, KS_, CK_, MW_, DWD_)                                                               \
-    if (split == SPLIT_ && p.KH == KS_ && mw == MW_ && dwd == DWD_)                                               \
-        return launch_direct_case<SPLIT_, KS_, CK_, MW_, DWD_>(p, grid, tiles_x, tiles_y, s);
-    HP_DIRECT_CASE(true, 1, 64, 1, 0)
-    HP_DIRECT_CASE(true, 1, 64, 2, 0)
-    HP_DIRECT_CASE(true, 1, 64, 4, 0)
-    HP_DIRECT_CASE(true, 1, 64, 8, 0)
-    HP_DIRECT_CASE(true, 3, 32, 1, 0)
-    HP_DIRECT_CASE(true, 3, 32, 2, 0)
-    HP_DIRECT_CASE(true, 3, 32, 4, 0)
-    HP_DIRECT_CASE(false, 1, 64, 1, 0)
-    HP_DIRECT_CASE(false, 1, 64, 2, 0)
-    HP_DIRECT_CASE(false, 1, 64, 4, 0)
-    HP_DIRECT_CASE(false, 3, 32, 1, 0)
-    HP_DIRECT_CASE(false, 3, 32, 2, 0)
-    HP_DIRECT_CASE(false, 3, 32, 4, 0)
-    HP_DIRECT_CASE(true, 1, 64, 2, 1)
-    HP_DIRECT_CASE(true, 1, 64, 4, 1)
-    HP_DIRECT_CASE(true, 1, 64, 8, 1)
-    HP_DIRECT_CASE(true, 1, 64, 2, 2)
-    HP_DIRECT_CASE(true, 1, 64, 4, 2)
-    HP_DIRECT_CASE(false, 1, 64, 2, 1)
-    HP_DIRECT_CASE(false, 1, 64, 4, 1)
-    HP_DIRECT_CASE(false, 1, 64, 2, 2)
-    HP_DIRECT_CASE(false, 1, 64, 4, 2)
+    const conv32_choice c = pick_conv32(p, engine_switches{}, C32_DIRECT, split);
+    if (!c.ok)
+        return hipErrorInvalidValue;
+#define HP_DIRECT_CASE(SPLIT_, KS_, CK_, MW_, DWD_)                                           \
+    if (c.targ[0] == SPLIT_ && c.targ[1] == KS_ && c.targ[3] == MW_ && c.targ[4] == DWD_)     \
+        return launch_direct_case<SPLIT_, KS_, CK_, MW_, DWD_>(p, c, s);
+    HP_CONV32_DIRECT_INSTANCES(HP_DIRECT_CASE)
 #undef HP_DIRECT_CASE
     return hipErrorInvalidValue;
 }

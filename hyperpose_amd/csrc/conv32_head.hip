@@ -13,7 +13,7 @@
 //             {h_r, h_r + 4} directly, with W2 packed to match (conv32_head_pack): 16 MFMAs per 32 outputs, no LDS round trip;
 //   output  = the four wavefronts' partial sums meet in LDS (summed in wavefront order: deterministic), then the lane = pixel epilogue
 //             (NHWC slice of any alignment + the fp32 NCHW network output the parsers read).
-#include "conv_fp32.hpp"
+#include "conv32_pick.hpp"
 
 #include "conv_device.hpp"
 
@@ -25,7 +25,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int HK1 = 128;            // input channels
+// (HK1 = 128 input channels: conv32_pick.hpp)
 constexpr int HXP = (HK1 + 4) * 4;  // LDS row (one pixel) pitch in bytes
 constexpr int HX_BYTES = 32 * HXP;  // 16896
 
@@ -210,12 +210,6 @@ __global__ __launch_bounds__(256, 2) void conv32_head_pair_kernel(const conv32_p
         conv32_head_body<TMA>(qa, ha, xs, red, blk);
 }
 
-// The pairs this kernel takes: 1 x 1 / stride 1 / no padding on both layers, 128 input channels (a 4-aligned slice), a hidden width that is a
-// multiple of 128 (32 rows x four wavefronts), at most 64 outputs, no residual on either layer
-bool conv32_head_ok(int k1, int hid, int c2) { return k1 == HK1 && hid >= 128 && hid % 128 == 0 && c2 >= 1 && c2 <= 64; }
-
-int conv32_head_tile(int hid, int c2) { return 37000000 + hid * 100 + c2; }
-
 // W2 = [c2_pad = 32 tm2][hid] row-major (zero rows in the padding) -> [hidden tile][output tile][register quad][lane][4]: lane (m, fk), register
 // r = 4 quad + e  <->  W2[32 output tile + m][32 hidden tile + (r & 3) + 8 (r >> 2) + 4 fk]  (hid * 32 * tm2 floats)
 void conv32_head_pack(const float* w2, int tm2, int hid, float* out)
@@ -229,46 +223,32 @@ void conv32_head_pack(const float* w2, int tm2, int hid, float* out)
                             w2[(size_t)(m2 * 32 + (lane & 31)) * hid + ht * 32 + e + 8 * qd + 4 * (lane >> 5)];
 }
 
-static bool head_args_ok(const conv32_params& q, const head32_hidden& h)
-{
-    return conv32_head_ok(HK1, h.HID, q.Cout) && h.w1_frag && h.w2_frag && h.bias1 && q.npix > 0 && (q.out.p || q.out_f32);
-}
-
-// whether two head launches may share one grid: the same input view and map
-static bool same_input(const conv32_params& a, const conv32_params& b)
-{
-    return a.in.p == b.in.p && a.in.cs == b.in.cs && a.in.coff == b.in.coff && a.in.wp == b.in.wp && a.in.img == b.in.img && a.OH == b.OH && a.OW == b.OW
-        && a.npix == b.npix;
-}
-
-bool conv32_head_pair_ok(const conv32_params& a, const conv32_params& b, const engine_switches& sw) { return sw.head_pair32 && same_input(a, b); }
+// what the picker (pick_head32, conv32_pick.hpp) does not see: the weights and an output to write
+static bool head_args_ok(const conv32_params& q, const head32_hidden& h) { return h.w1_frag && h.w2_frag && h.bias1 && (q.out.p || q.out_f32); }
 
 hipError_t launch_conv32_head_pair(const conv32_params& qa, const head32_hidden& ha, const conv32_params& qb, const head32_hidden& hb, hipStream_t s)
 {
-    if (!head_args_ok(qa, ha) || !head_args_ok(qb, hb) || !same_input(qa, qb))
+    const conv32_choice c = pick_head32(qa, ha.HID, &qb, hb.HID);
+    if (!c.ok || !head_args_ok(qa, ha) || !head_args_ok(qb, hb))
         return hipErrorInvalidValue;
-    const dim3 grid(((qa.npix + 31) / 32 + 7) / 8 * 8 * 2);
-    const bool a1 = qa.Cout <= 32, b1 = qb.Cout <= 32;
-    if (a1 && b1)
-        HP_LAUNCH((conv32_head_pair_kernel<1, 1>), grid, dim3(256), 0, s, qa, ha, qb, hb);
-    else if (a1)
-        HP_LAUNCH((conv32_head_pair_kernel<1, 2>), grid, dim3(256), 0, s, qa, ha, qb, hb);
-    else if (b1)
-        HP_LAUNCH((conv32_head_pair_kernel<2, 1>), grid, dim3(256), 0, s, qa, ha, qb, hb);
-    else
-        HP_LAUNCH((conv32_head_pair_kernel<2, 2>), grid, dim3(256), 0, s, qa, ha, qb, hb);
+#define HP_HEAD_CASE(TMA_, TMB_)                                                                                           \
+    if (c.targ[0] == TMA_ && c.targ[1] == TMB_)                                                                            \
+        HP_LAUNCH((conv32_head_pair_kernel<TMA_, TMB_>), dim3(c.grid_x), dim3(c.threads), c.lds, s, qa, ha, qb, hb);
+    HP_CONV32_HEAD_PAIR_INSTANCES(HP_HEAD_CASE)
+#undef HP_HEAD_CASE
     return hipGetLastError();
 }
 
 hipError_t launch_conv32_head(const conv32_params& q, const head32_hidden& h, hipStream_t s)
 {
-    if (!conv32_head_ok(HK1, h.HID, q.Cout) || !h.w1_frag || !h.w2_frag || !h.bias1 || q.npix <= 0 || (!q.out.p && !q.out_f32))
+    const conv32_choice c = pick_head32(q, h.HID);
+    if (!c.ok || !head_args_ok(q, h))
         return hipErrorInvalidValue;
-    const dim3 grid((q.npix + 31) / 32);
-    if (q.Cout <= 32)
-        HP_LAUNCH((conv32_head_kernel<1>), grid, dim3(256), 0, s, q, h);
-    else
-        HP_LAUNCH((conv32_head_kernel<2>), grid, dim3(256), 0, s, q, h);
+#define HP_HEAD_CASE(TM2_)  \
+    if (c.targ[0] == TM2_)  \
+        HP_LAUNCH((conv32_head_kernel<TM2_>), dim3(c.grid_x), dim3(c.threads), c.lds, s, q, h);
+    HP_CONV32_HEAD_INSTANCES(HP_HEAD_CASE)
+#undef HP_HEAD_CASE
     return hipGetLastError();
 }
 

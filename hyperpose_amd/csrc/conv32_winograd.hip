@@ -38,7 +38,7 @@
 // 8.7 k (chunk 0: 6.4 k; 8.2 k = the pipe's time for the two blocks' 2 x 128 MFMAs per SIMD: the loop is at the pipe's rate), next patch stored
 // 0.4 - 1.0 k | epilogue requests 2.1 k (3.1 k with a residual) | output transform 1.5 k | stores 5.4 k.  81 - 82 k cycles per block, with or
 // without a residual (before: 85 k without, 89 k with one), of which 2 x 32.8 k are MFMA issue.
-#include "conv_fp32.hpp"
+#include "conv32_pick.hpp"
 
 #include "conv32_epilogue.hpp"
 #include "conv_device.hpp"
@@ -54,7 +54,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(1))) float gfloat; // global memory, said to the compiler
 typedef __attribute__((address_space(1))) f32x4 gf32x4;
 
-constexpr int WCK = 16;                        // input channels per chunk
+// (WCK = 16, the input channels per chunk: conv32_pick.hpp)
 constexpr int HALO_W = 10;                     // halo patch of the 16 NC x 8 pixel tile: (8 NC + 2) x 10 pixels
 constexpr int RAW_PB = WCK * 4;
 constexpr int VP = 24 * 4;                     // V row (one tile, 16 channels) pitch in bytes: 24 floats - the transform's ds_write_b128 and the MFMA's ds_read_b128 are conflict-free
@@ -449,17 +449,6 @@ __global__ __launch_bounds__(64 * MW, MW == 8 ? 1 : NC == 1 ? 3 : 2) void conv32
         p.dbg[121] = __builtin_readcyclecounter(), p.dbg[122] = __builtin_amdgcn_s_memrealtime();
 }
 
-// 3 x 3, stride 1, dilation 1, SAME padding, input slice readable in whole 16-channel chunks, NHWC output only (a network head keeps the
-// direct kernel's lane = pixel epilogue for its NCHW copy)
-bool conv32_winograd_ok(const conv32_params& p)
-{
-    return p.KH == 3 && p.KW == 3 && p.stride == 1 && p.dil == 1 && p.Cin % WCK == 0 && p.Cout_pad % 64 == 0 && p.OH == p.H && p.OW == p.W && p.pad_t == 1
-        && p.pad_l == 1 && !p.out_f32 && p.out.p;
-}
-
-// four wavefronts (16-channel MFMA tiles) per block, the pipelined form: see "Kernel shape"
-int conv32_winograd_tile(const conv32_params& p) { return p.w_wino3 ? conv32_winograd3_tile(p) : 35000000 + 3000 + 4; }
-
 // MFMA work of one launch (what the roofline fraction of this kernel is computed from): 16 products per tile and channel pair
 double conv32_winograd_flops(const conv32_params& p)
 {
@@ -498,9 +487,10 @@ void conv32_winograd_pack(const float* packed, int cout_pad, int cin, float* out
 }
 
 template <int MW, bool PIPE, int NC = 2>
-static hipError_t launch_wino_case(const conv32_params& q, dim3 grid, int tiles_x, int tiles_y, int vh, int rows, hipStream_t s)
+static hipError_t launch_wino_case(const conv32_params& q, const conv32_choice& c, hipStream_t s)
 {
     constexpr int lds = PIPE ? wino_geom<MW, NC>::PLDS_BYTES : wino_geom<MW, NC>::LDS_BYTES;
+    static_assert(MW == WINO_MW && PIPE && lds == WINO_LDS[NC], "conv32_pick.hpp sizes the launch");
     static bool granted = false;
     if (lds > 64 * 1024 && !granted) {
         const hipError_t e = hipFuncSetAttribute((const void*)conv32_winograd_kernel<MW, PIPE, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -508,60 +498,22 @@ static hipError_t launch_wino_case(const conv32_params& q, dim3 grid, int tiles_
             return e;
         granted = true;
     }
-    HP_LAUNCH((conv32_winograd_kernel<MW, PIPE, NC>), grid, dim3(64 * MW), lds, s, q, tiles_x, tiles_y, vh, rows);
+    HP_LAUNCH((conv32_winograd_kernel<MW, PIPE, NC>), dim3(c.grid_x), dim3(c.threads), lds, s, q, c.tiles_x, c.tiles_y, c.vh, c.rows);
     return hipGetLastError();
 }
 
-// Column tiles per block: 2 (16 x 8 pixels) or 1 (8 x 8 pixels: twice the blocks, half the accumulators, three blocks per CU - and twice the U
-// bytes per MFMA).  A 128 -> 128 layer at 8 x 46 x 54 is 336 blocks of the first form for 256 CUs x 2: 176 CUs run one block, 80 run two and
-// set the launch's time (45.0 us); as 672 blocks of the second it takes 35.9 us alone and the same 27 us next to a second stream's launch -
-// but four pipes lose 1.4 % (5 113 -> 5 042 frames/s, three runs each: the U stream).  So: the small form for a caller with ONE batch in flight
-// (conv32_params::latency, i.e. hp_engine_set_concurrency(e, 2)) when the large form would not fill the chip's 512 slots twice; the same
-// tiles, the same arithmetic: the same bits (tests/test_engine_fp32_gpu.py).  HP_WINO_NC=1 | 2 forces one.
-static int winograd_nc(const conv32_params& p, const engine_switches& sw, int blocks_nc2)
-{
-    const int force = sw.wino_nc;
-    if (force == 1 || force == 2)
-        return force;
-    return p.latency && blocks_nc2 <= 512 ? 1 : 2;
-}
-
-// Rows per image of the tall form, or 0 where it does not apply: the input's images must lie vh = even rows apart with at least one (zero) halo
-// row above and below each.  HP_WINO_TALL=0: the A/B switch.
-static int winograd_tall(const conv32_params& p, const engine_switches& sw)
-{
-    if (!sw.wino_tall)
-        return 0;
-    if (p.B < 2 || p.in.wp <= 0 || p.in.img % p.in.wp)
-        return 0;
-    const int vh = p.in.img / p.in.wp;
-    return (vh & 1) == 0 && vh >= p.H + 2 ? vh : 0;
-}
-
+// Column tiles per block, the per-image / tall / rows form and the grid: pick_conv32 (conv32_pick.hpp)
 hipError_t launch_conv32_winograd(const conv32_params& p, const engine_switches& sw, hipStream_t s)
 {
-    if (!conv32_winograd_ok(p) || !p.w_wino || p.npix <= 0)
+    const conv32_choice c = pick_conv32(p, sw, C32_WINO2, false);
+    if (!c.ok || !p.w_wino || p.npix <= 0)
         return hipErrorInvalidValue;
-    constexpr int mw = 4;
-    const int tiles_x = (p.OW + 7) / 8;
-    const int nc = winograd_nc(p, sw, tiles_x * ((p.OH + 15) / 16) * p.B * (p.Cout_pad / 64)), bh = 8 * nc;
-    int tiles_y = (p.OH + bh - 1) / bh, vh = winograd_tall(p, sw), images = p.B, rows = 0;
-    // the rows form (tile rows numbered per image: see the kernel) where an image has at least a block's tile rows and the batch's tile rows
-    // are fewer blocks than the images' own; it reads what the per-image form reads, whatever lies between two images
-    const int T = (p.OH + 1) / 2, rows_y = (p.B * T + 4 * nc - 1) / (4 * nc);
-    if (sw.wino_tall && p.B > 1 && T >= 4 * nc && rows_y < tiles_y * p.B)
-        tiles_y = rows_y, images = 1, rows = T, vh = 0;
-    else if (vh) { // fewer tile rows per image: the tall form
-        const int tall_y = ((p.B - 1) * vh + p.H + bh - 1) / bh;
-        if (tall_y < tiles_y * p.B)
-            tiles_y = tall_y, images = 1;
-        else
-            vh = 0; // (a map that is whole 16-row blocks already: 48 rows + 2 halo rows would only add separator rows)
-    }
-    const dim3 grid((tiles_x * tiles_y * images + 7) / 8 * 8 * (p.Cout_pad / (16 * mw))); // XCD-aware 1-D order: see the kernel
-    if (nc == 1)
-        return launch_wino_case<4, true, 1>(p, grid, tiles_x, tiles_y, vh, rows, s);
-    return launch_wino_case<4, true>(p, grid, tiles_x, tiles_y, vh, rows, s);
+#define HP_WINO_CASE(MW_, PIPE_, NC_) \
+    if (c.targ[2] == NC_)             \
+        return launch_wino_case<MW_, PIPE_, NC_>(p, c, s);
+    HP_CONV32_WINO_INSTANCES(HP_WINO_CASE)
+#undef HP_WINO_CASE
+    return hipErrorInvalidValue;
 }
 
 hipError_t conv32_winograd_occupancy(const conv32_params&, int* blocks_per_cu)

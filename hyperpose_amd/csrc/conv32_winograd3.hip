@@ -20,7 +20,7 @@
 //             from V; four v_mfma_f32_16x16x4_f32 per step, 25 steps per chunk
 //   output  = At M A per lane from its own registers, into a slab the block shares ([144 pixels][64 channels]), then conv32_epilogue.hpp's whole pixel rows
 // A frame's tiles start at its own first row and column: the same bits in every batch and at every frame offset.
-#include "conv_fp32.hpp"
+#include "conv32_pick.hpp"
 
 #include "conv32_epilogue.hpp"
 #include "conv_device.hpp"
@@ -34,9 +34,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int W3_CK = 16;                         // input channels per chunk
-constexpr int W3_TY = 8, W3_TX = 2;               // tiles of a block
-constexpr int W3_BH = 3 * W3_TY, W3_BW = 3 * W3_TX; // 24 x 6 output pixels
+// (W3_CK = 16 input channels per chunk, W3_TY x W3_TX = 8 x 2 tiles = W3_BH x W3_BW = 24 x 6 output pixels per block: conv32_pick.hpp)
 constexpr int W3_HH = W3_BH + 2, W3_HW = W3_BW + 2; // 26 x 8 halo patch
 constexpr int W3_RP = W3_HW * 64 + 16;            // patch row pitch in bytes (+ 16: the eight tile rows of a 16-lane group spread over the banks)
 constexpr int W3_QUADS = W3_HH * W3_HW * 4;       // 832 float4 quads per chunk
@@ -263,15 +261,6 @@ __global__ __launch_bounds__(256, 2) void conv32_winograd3_kernel(const conv32_p
 #undef HP_STAMP
 }
 
-// 3 x 3, stride 1, dilation 1, SAME padding, input slice readable in whole 16-channel chunks, NHWC output only
-bool conv32_winograd3_ok(const conv32_params& p)
-{
-    return p.KH == 3 && p.KW == 3 && p.stride == 1 && p.dil == 1 && p.Cin % W3_CK == 0 && p.Cout_pad % 64 == 0 && p.OH == p.H && p.OW == p.W && p.pad_t == 1
-        && p.pad_l == 1 && !p.out_f32 && p.out.p;
-}
-
-int conv32_winograd3_tile(const conv32_params&) { return 35005004; }
-
 // packed = [9 taps][cout_pad][cin] fp32 (conv32_params::w's layout) -> U = G g Gt (5 x 5) in fragment order [chunk][pos][16-row tile][lane][4 floats]
 // (25 * cout_pad * cin floats); lane (row, kq) = channels chunk * 16 + 4 kq + {0..3}.  U is formed in double and rounded to fp32 once.
 void conv32_winograd3_pack(const float* packed, int cout_pad, int cin, float* out)
@@ -305,7 +294,9 @@ void conv32_winograd3_pack(const float* packed, int cout_pad, int cin, float* ou
 
 hipError_t launch_conv32_winograd3(const conv32_params& p, hipStream_t s)
 {
-    if (!conv32_winograd3_ok(p) || !p.w_wino3 || p.npix <= 0)
+    static_assert(W3_LDS == W3_LDS_BYTES, "conv32_pick.hpp sizes the launch");
+    const conv32_choice c = pick_conv32(p, engine_switches{}, C32_WINO3, false);
+    if (!c.ok || !p.w_wino3 || p.npix <= 0)
         return hipErrorInvalidValue;
     static bool granted = false;
     if (!granted) {
@@ -314,9 +305,7 @@ hipError_t launch_conv32_winograd3(const conv32_params& p, hipStream_t s)
             return e;
         granted = true;
     }
-    const int tiles_x = (p.OW + W3_BW - 1) / W3_BW, tiles_y = (p.OH + W3_BH - 1) / W3_BH;
-    const dim3 grid((tiles_x * tiles_y * p.B + 7) / 8 * 8 * (p.Cout_pad / 64)); // XCD-aware 1-D order: see the kernel
-    HP_LAUNCH(conv32_winograd3_kernel, grid, dim3(256), W3_LDS, s, p, tiles_x, tiles_y);
+    HP_LAUNCH(conv32_winograd3_kernel, dim3(c.grid_x), dim3(c.threads), c.lds, s, p, c.tiles_x, c.tiles_y);
     return hipGetLastError();
 }
 

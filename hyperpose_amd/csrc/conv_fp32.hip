@@ -9,7 +9,7 @@
 //   first_conv32_kernel    the 3-channel input layer with the u8 -> f32 pre-processing of src/data.cpp:21-51 folded into its load;
 //   dwconv32_kernel        depthwise 3 x 3;   maxpool32_kernel / upsample32_kernel;   output_transform32_kernel (NHWC fp32 -> NCHW fp32).
 // Activations keep the zero-halo NHWC layout of the fp16 path with 4-byte elements.
-#include "conv_fp32.hpp"
+#include "conv32_pick.hpp"
 
 #include "conv32_epilogue.hpp"
 #include "conv_device.hpp"
@@ -710,9 +710,9 @@ __global__ __launch_bounds__(256) void conv32_wk_kernel(const conv32_params p)
 }
 
 template <int KT, int BN>
-static hipError_t launch_wk(const conv32_params& p, dim3 grid, hipStream_t s)
+static hipError_t launch_wk(const conv32_params& p, const conv32_choice& c, hipStream_t s)
 {
-    constexpr int lds = KT / 16 * ((64 * 16 + 16) + (BN * 16 + 16)) * 4 + 4 * 16 * 36 * 4 + 3 * BN * 8;
+    constexpr int lds = pick32::wk_lds(KT, BN);
     static bool granted = false;
     if (lds > 64 * 1024 && !granted) {
         const hipError_t e = hipFuncSetAttribute((const void*)conv32_wk_kernel<KT, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -720,80 +720,8 @@ static hipError_t launch_wk(const conv32_params& p, dim3 grid, hipStream_t s)
             return e;
         granted = true;
     }
-    HP_LAUNCH((conv32_wk_kernel<KT, BN>), grid, dim3(256), lds, s, p);
+    HP_LAUNCH((conv32_wk_kernel<KT, BN>), dim3(c.grid_x), dim3(c.threads), lds, s, p);
     return hipGetLastError();
-}
-
-// Which layers take conv32_wk_kernel: 1 x 1 (any stride), exactly 32 / 64 / 128 input channels, an NHWC output only, and enough pixel tiles that
-// two blocks per CU stay busy (HP_C32_WK=0: none, the A/B switch; =1: every layer of that shape).  Looks at pick_npix like conv32_pick.
-static int conv32_wk_bn(const conv32_params& p, const engine_switches& sw)
-{
-    const int wk = sw.c32_wk;
-    if (wk == 0 || p.KH != 1 || p.KW != 1 || p.dil != 1 || p.out_f32 || !p.out.p || (p.Cin != 32 && p.Cin != 64 && p.Cin != 128))
-        return 0;
-    // K = 128 (two blocks per CU) wins nothing: ResNet's 128 -> 512 at 32 x 48 x 48 140 -> 135 us, MobileNet's 128 -> 128 at 8 x 92 x 108 38.6 -> 41.6
-    // (profiles/r06_ab_layers_f32_whole_k.txt): forced only (the tests)
-    if (p.Cin == 128 && wk != 1)
-        return 0;
-    const int bn = 64; // (LDS: 27 / 44 / 77 KB per block at K = 32 / 64 / 128: five / three / two blocks per CU)
-    const long np = p.pick_npix > 0 ? p.pick_npix : p.npix, blocks = (np + bn - 1) / bn * (p.Cout_pad / 64);
-    return wk == 1 || blocks >= 768 ? bn : 0;
-}
-
-// Block tile (BM output channels x BN pixels) of a layer.  The fp32 matrix pipe is slow enough (64 cycles per MFMA) that small tiles cost
-// little per MFMA, and a layer that is one wave of 128 x 128 tiles leaves CUs idle: LW-OpenPose's 3 x 3 128 -> 128 layers at 8 x 46 x 54 pixels
-// are 156 such tiles on 256 CUs (0.38 of the fp32 MFMA peak) - as 64 x 64 tiles they are 622 blocks, several per CU.
-static void conv32_pick(const conv32_params& p, const engine_switches& sw, int& BM, int& BN)
-{
-    BM = p.Cout_pad % 128 == 0 ? 128 : 64, BN = 128;
-    const long blocks = (long)(((p.pick_npix > 0 ? p.pick_npix : p.npix) + 127) / 128) * (p.Cout_pad / BM);
-    if (blocks < 448) // fewer than ~1.75 blocks per CU: quarter the tile
-        BM = 64, BN = 64;
-    else if (blocks < 1024 && BM == 128) // up to four blocks per CU: halve the tile (512 -> 512 at 8 x 46 x 54: 115 -> 100 us alone, same machine time)
-        BM = 64;
-    // Round quantisation: 64 x 128 tiles have 1024 slots (four blocks per CU); a layer that is "one round and a bit" of them but ONE round of
-    // 64 x 160 tiles takes conv32_t16_kernel<160> (see there).  HP_C32_BN160=0: the A/B switch back; =1: every layer (tests).
-    const int bn160 = sw.c32_bn160;
-    if (bn160 == 1 || bn160 == 176) { // (tests: every layer on the 64 x 160 | 64 x 176 tile)
-        BM = 64, BN = bn160 == 1 ? 160 : 176;
-        return;
-    }
-    if (BM == 64 && BN == 128 && bn160 != 0) {
-        const long np = p.pick_npix > 0 ? p.pick_npix : p.npix; // (the engine's max_batch geometry: see conv32_params::pick_npix)
-        const long g = p.Cout_pad / 64, b128 = (long)((np + 127) / 128) * g, b160 = (long)((np + 159) / 160) * g;
-        if (b128 > 1024 && b160 <= 1024)
-            BN = 160;
-        // (b160 a few blocks over the 1 024 slots - OpenPose-VGG19's 7 x 7 layers at 16 x 54 x 96: 1 296 tiles of 64 x 128, 1 038 of 64 x 160, 944 of
-        // 64 x 176 = conv32_t16_kernel<176, 1>, one round: 1 272 -> 1 172 us alone, but 1 039 -> 1 053 with a second stream, whose blocks fill the
-        // second round's empty slots anyway: not taken; HP_C32_BN160=176 forces it, tests/test_engine_fp32_gpu.py::test_one_round_tile_64x160)
-    }
-    // ResNet's 1 x 1 expansions with few input channels (64 -> 256 at 96 x 96, 128 -> 512 at 48 x 48, batch 32): four to eight K-steps, then 300 MB
-    // of output + residual - the layer is its epilogue.  conv32_t16_kernel's stores cover 16 pixels x 64 contiguous bytes per instruction where
-    // the 32 x 32 accumulator layout covers 64 pixels x 16 bytes: 259 -> 205 us alone, 218 -> 188 with a second stream for 64 -> 256, 146 -> 142 | 130 -> 126
-    // for 128 -> 512; every wider-K layer is slower on it (profiles/r06_ab_layers_f32_config3_t16.txt)
-    if (bn160 != 0 && p.KH == 1 && p.KW == 1 && p.stride == 1 && p.Cin <= 128 && p.Cout_pad >= 256 && !p.out_f32 && (BN == 128))
-        BM = 64, BN = 160;
-}
-
-static bool conv32_rows(const conv32_params& p, int BN)
-{
-    if (BN == 160 || BN == 176)
-        return false; // conv32_t16_kernel has the one epilogue (16 pixels x 64 contiguous bytes per store instruction)
-    // The row-major epilogue pays on the 64-pixel tile only.  Measured per layer of LW-OpenPose @ 8 x 46 x 54 (us alone | with a second
-    // stream; rows -> lane = pixel): <64, 64> 256 -> 256 33.2 | 26.9 -> 33.8 | 29.2, 128 -> 256 21.3 | 15.8 -> 21.7 | 19.0;  <64, 128> (two
-    // channel tiles per wavefront: eight pixel rows of 256 B in flight per lane group) 128 -> 512 61.5 | 40.3 -> 35.1 | 27.4, 32 -> 64 at
-    // 184 x 216 59.2 | 46.6 -> 36.0 | 29.6, 512 -> 512 129 | 93 -> 106 | 94 (profiles/r05_ab_layers_f32_*_epilogue.txt).
-    // HP_LANE_EPILOGUE=1: lane form everywhere, HP_LANE_EPILOGUE=-1: row form everywhere.
-    return !p.out_f32 && (p.lane_epilogue < 0 || (p.lane_epilogue == 0 && BN == 64));
-}
-
-int conv32_tile(const conv32_params& p, const engine_switches& sw)
-{
-    if (const int bn = conv32_wk_bn(p, sw))
-        return 39000000 + p.Cin * 1000 + bn;
-    int BM, BN;
-    conv32_pick(p, sw, BM, BN);
-    return 32000000 + (conv32_rows(p, BN) ? 400000 : 0) + BM * 1000 + BN;
 }
 
 bool set_act32(conv32_params& p)
@@ -820,38 +748,39 @@ bool set_act32(conv32_params& p)
     }
 }
 
+// Which kernel, tile and grid: pick_conv32 (conv32_pick.hpp)
 hipError_t launch_conv32(const conv32_params& p, const engine_switches& sw, hipStream_t s)
 {
     if (p.Cin % 16 || p.Cout_pad % 64 || p.npix <= 0)
         return hipErrorInvalidValue;
-    if (const int bn = conv32_wk_bn(p, sw)) {
-        const dim3 g(((p.npix + bn - 1) / bn + 7) / 8 * 8 * (p.Cout_pad / 64));
-        return p.Cin == 32 ? launch_wk<32, 64>(p, g, s) : p.Cin == 64 ? launch_wk<64, 64>(p, g, s) : launch_wk<128, 64>(p, g, s);
+    const conv32_choice c = pick_conv32(p, sw, C32_GEMM, false);
+    const int* const t = c.targ;
+    const dim3 grid(c.grid_x), block(c.threads);
+#define HP_WK_CASE(KT_, BN_) \
+    if (c.kernel == K32_WK && t[0] == KT_ && t[1] == BN_) \
+        return launch_wk<KT_, BN_>(p, c, s);
+    HP_CONV32_WK_INSTANCES(HP_WK_CASE)
+#undef HP_WK_CASE
+    // (conv32_t16_kernel<160>: three blocks per CU instead of four - 12 KB of unused dynamic LDS, to leave registers and LDS to the other pipes' depthwise
+    // kernels - cost four pipes 1.3 %: 1.466 -> 1.485 ms of conv stack per batch, two runs each)
+#define HP_T16_CASE(BN_, WN_)                                                 \
+    if (c.kernel == K32_T16 && t[0] == BN_) {                                 \
+        HP_LAUNCH((conv32_t16_kernel<BN_, WN_>), grid, block, c.lds, s, p);   \
+        return hipGetLastError();                                             \
     }
-    int BM, BN;
-    conv32_pick(p, sw, BM, BN);
-    const dim3 grid(((p.npix + BN - 1) / BN + 7) / 8 * 8 * (p.Cout_pad / BM)); // XCD-aware 1-D order: see conv32_kernel
-    const bool rows = conv32_rows(p, BN);
-#define HP_C32_CASE(BM_, BN_, WM_, WN_)                                                    \
-    if (rows)                                                                              \
-        HP_LAUNCH((conv32_kernel<BM_, BN_, WM_, WN_, true>), grid, dim3(256), 0, s, p);    \
-    else                                                                                   \
-        HP_LAUNCH((conv32_kernel<BM_, BN_, WM_, WN_, false>), grid, dim3(256), 0, s, p);
-    if (BN == 176) {
-        HP_LAUNCH((conv32_t16_kernel<176, 1>), grid, dim3(256), 0, s, p);
-    } else if (BN == 160) {
-        // (three blocks per CU instead of four - 12 KB of unused dynamic LDS, to leave registers and LDS to the other pipes' depthwise kernels - cost four
-        // pipes 1.3 %: 1.466 -> 1.485 ms of conv stack per batch, two runs each)
-        HP_LAUNCH((conv32_t16_kernel<160>), grid, dim3(256), 0, s, p);
-    } else if (BM == 128) {
-        HP_C32_CASE(128, 128, 2, 2)
-    } else if (BN == 128) {
-        HP_C32_CASE(64, 128, 1, 4)
-    } else {
-        HP_C32_CASE(64, 64, 2, 2)
+    HP_CONV32_T16_INSTANCES(HP_T16_CASE)
+#undef HP_T16_CASE
+#define HP_C32_CASE(BM_, BN_, WM_, WN_)                                                       \
+    if (c.kernel == K32_CONV && t[0] == BM_ && t[1] == BN_) {                                 \
+        if (t[4])                                                                             \
+            HP_LAUNCH((conv32_kernel<BM_, BN_, WM_, WN_, true>), grid, block, c.lds, s, p);   \
+        else                                                                                  \
+            HP_LAUNCH((conv32_kernel<BM_, BN_, WM_, WN_, false>), grid, block, c.lds, s, p);  \
+        return hipGetLastError();                                                             \
     }
+    HP_CONV32_INSTANCES(HP_C32_CASE)
 #undef HP_C32_CASE
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 // ---------------------------------------------------------------------------------------------------

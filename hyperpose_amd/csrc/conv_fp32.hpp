@@ -62,33 +62,25 @@ struct conv32_params {
 // fills act_slope / act_hi from act / act_param; false for activations the epilogue does not evaluate (sigmoid / softplus are output post-ops)
 bool set_act32(conv32_params& p);
 // Dense KH x KW convolution (any stride / dilation) as an implicit GEMM on v_mfma_f32_32x32x2_f32.
+// Which kernel, template instance and grid a launch below gets, the eligibility predicates and the profile rows' tile codes: conv32_pick.hpp.
 hipError_t launch_conv32(const conv32_params& p, const engine_switches& sw, hipStream_t s);
-int conv32_tile(const conv32_params& p, const engine_switches& sw); // profile rows: 32000000 + 400000 (row-major epilogue) + BM * 1000 + BN; conv32_wk_kernel (1 x 1, 32 / 64 input channels, large maps): 39000000 + Cin * 1000 + pixels per block
 // The barrier-free direct form for square 1 x 1 / 3 x 3, stride 1, dilation 1, SAME padding (conv32_direct.hip): a chunk's halo tile staged in LDS once
 // for all taps, weights in fragment order straight from L2.  split = false: exact fp32 products on v_mfma_f32_32x32x2_f32 (needs w_frag);
 // split = true: every fp32 product formed as three exact fp16 x fp16 products on the fp16 matrix pipe, x = hi + 2^-11 lo,
 // hi-hi + 2^-11 (hi-lo + lo-hi), fp32 accumulation (needs w_split).  Cin must be whole chunks (64 channels at 1 x 1, 32 at 3 x 3).
-bool conv32_direct_ok(const conv32_params& p);
 hipError_t launch_conv32_direct(const conv32_params& p, bool split, hipStream_t s);
-int conv32_direct_tile(const conv32_params& p, bool split); // profile rows: 33000000 (split) / 34000000 (fp32) + 100000 * fused depthwise dilation + KS * 1000 + wavefront groups per block
-// whether the 1 x 1 layer p can take a depthwise 3 x 3 of dilation `dil` in front of it in the same launch (p.dw_w etc. not yet set)
-bool conv32_dw_fusable(const conv32_params& p, bool split, int dil);
 // packed = [taps][cout_pad][cin] fp32 (conv32_params::w's layout) -> the kernels' fragment order: 2 * taps * cout_pad * cin halves / taps * cout_pad * cin floats
 void conv32_split_pack(const float* packed, int taps, int cout_pad, int cin, _Float16* out);
 void conv32_frag_pack(const float* packed, int taps, int cout_pad, int cin, float* out);
 
 // Winograd F(2 x 2, 3 x 3) on the fp32 matrix pipe for 3 x 3, stride 1, dilation 1, SAME-padded layers with an NHWC output (conv32_winograd.hip):
 // 16 instead of 36 MFMA products per output tile and channel pair.  Needs w_wino (conv32_winograd_pack of the packed matrix).
-bool conv32_winograd_ok(const conv32_params& p);
 hipError_t launch_conv32_winograd(const conv32_params& p, const engine_switches& sw, hipStream_t s);
 hipError_t conv32_winograd_occupancy(const conv32_params& p, int* blocks_per_cu);
 // Winograd F(3 x 3, 3 x 3) for the same layers (conv32_winograd3.hip): 25 products per 3 x 3 output tile and channel pair - 2.78 per pixel against 4.
 // Needs w_wino3 (conv32_winograd3_pack of the packed matrix: 25 * cout_pad * cin floats).
-bool conv32_winograd3_ok(const conv32_params& p);
 hipError_t launch_conv32_winograd3(const conv32_params& p, hipStream_t s);
-int conv32_winograd3_tile(const conv32_params& p);
-void conv32_winograd3_pack(const float* packed, int cout_pad, int cin, float* out); // what the runtime grants this launch's kernel
-int conv32_winograd_tile(const conv32_params& p);     // profile rows: 35003004 (F(3 x 3, 3 x 3): conv32_winograd3_tile)
+void conv32_winograd3_pack(const float* packed, int cout_pad, int cin, float* out);
 double conv32_winograd_flops(const conv32_params& p); // the MFMA work of one launch: 2 * 16 * tiles * Cout * Cin
 void conv32_winograd_pack(const float* packed, int cout_pad, int cin, float* out); // [9][cout_pad][cin] -> 16 * cout_pad * cin floats
 
@@ -98,16 +90,13 @@ void conv32_winograd_pack(const float* packed, int cout_pad, int cin, float* out
 struct head32_hidden {
     const float* w1_frag; // conv32_frag_pack of the first layer's [1][HID][128] matrix
     const float* bias1;   // [HID]
-    const float* w2_frag; // conv32_head_pack of the second layer's [32 tm2][HID] matrix (zero rows in the padding), tm2 = C2 <= 32 ? 1 : 2
+    const float* w2_frag; // conv32_head_pack of the second layer's [32 tm2][HID] matrix (zero rows in the padding), tm2 = pick32::head_tm2(C2)
     float slope1, hi1;    // hidden activation: y = v > 0 ? min(v, hi1) : v * slope1
     int HID;
 };
-bool conv32_head_ok(int k1, int hid, int c2);
 hipError_t launch_conv32_head(const conv32_params& q, const head32_hidden& h, hipStream_t s);
 // two heads that read the same tensor in one grid (LW-OpenPose's heat-map and PAF heads of a stage): same results, the blocks of both side by side
-bool conv32_head_pair_ok(const conv32_params& a, const conv32_params& b, const engine_switches& sw);
 hipError_t launch_conv32_head_pair(const conv32_params& qa, const head32_hidden& ha, const conv32_params& qb, const head32_hidden& hb, hipStream_t s);
-int conv32_head_tile(int hid, int c2); // profile rows: 37000000 + 100 * HID + C2
 void conv32_head_pack(const float* w2, int tm2, int hid, float* out);
 
 struct first_conv32_params {

@@ -10,7 +10,7 @@
 //   * activations are NHWC fp16 with fp32 MFMA accumulation, concat is a channel offset into a shared buffer;
 //   * heads write fp32 NCHW straight from the conv epilogue into the buffers the parser kernels read —
 //     feature maps never cross PCIe.
-#include "conv_fp32.hpp"
+#include "conv32_pick.hpp"
 #include "conv_i8.hpp"
 #include "conv_kernels.hpp"
 #include "engine_timeline.hpp"
@@ -79,7 +79,7 @@ struct out_info {
 // What the engine can launch: one value per kernel family and form.  Set by the lowering or fusion pass that decides it (lower_layers, fuse_*,
 // pair_heads) and never changed afterwards.  Two decisions are left to every launch, because they depend on what it is bound to:
 // an int8-capable dense conv runs conv_i8 only while its scale is positive (hp_engine::bound), and two adjacent fp32 heads share a grid when
-// conv32_head_pair_ok says so for the batch (hp_engine::launch_head_pair32).
+// pick32::head_pair_ok (conv32_pick.hpp) says so for the batch (hp_engine::launch_head_pair32).
 enum class launch_kind : char {
     // fp16 (and int8) engines
     first16,
@@ -215,7 +215,8 @@ struct hp_engine {
     bool split_off = false;
     int split_fallbacks = 0;
     hp::call_args last; // the newest hp_engine_infer_* call
-    bool split_overflowed() const { return dtype == HP_DTYPE_F32S && !split_off && ovf_flag.p && *static_cast<volatile unsigned*>(ovf_flag.p) != 0; }
+    bool on_split_pipe() const { return dtype == HP_DTYPE_F32S && !split_off; } // the direct kernel: on the fp16 pipe until a value left fp16's range, then on the fp32 pipe
+    bool split_overflowed() const { return on_split_pipe() && ovf_flag.p && *static_cast<volatile unsigned*>(ovf_flag.p) != 0; }
     int leave_split(); // stop using conv32_direct_kernel: drop the captured graphs (they hold its launches), count the event
     hp::engine_switches switches; // read_engine_switches() at hp_engine_create / hp_engine_load
     double factor = 1.0 / 255;
@@ -299,8 +300,8 @@ struct hp_engine {
     // ... fp32 engines: one step per layer, or per fused pair (described at its second layer)
     int lower32_conv(size_t i, step& st);
     int lower32_dw_in_front(size_t i, step& st);
-    int lower32_winograd_forms(size_t i, step& st, const std::vector<float>& packed);
-    int lower32_direct_forms(size_t i, step& st, const std::vector<float>& packed, int room);
+    int lower32_winograd_forms(size_t i, step& st, const std::vector<float>& packed, const hp::conv32_forms& f);
+    int lower32_direct_forms(size_t i, step& st, const std::vector<float>& packed, const hp::conv32_forms& f);
     int lower32_head_in_front(size_t i, step& st, const float* w); // (turns the step's conv32_launch into a head32_launch)
     int lower32_dw(size_t i, step& st);
     // ... fp16 and int8 engines: one layer, a two-layer head, a separable block
@@ -609,7 +610,7 @@ int hp_engine::mark_pair_fusions(const hp_engine_desc* d)
             q.B = max_batch, q.H = q.OH = geos[i].OH, q.W = q.OW = geos[i].OW, q.Cin = Bn.cin, q.Cout = Bn.cout, q.Cout_pad = round_up(Bn.cout, 64);
             q.KH = q.KW = 1, q.stride = 1, q.dil = 1, q.pad_t = q.pad_l = 0, q.npix = max_batch * q.OH * q.OW;
             // (an HP_DTYPE_F32S engine must also be able to run the block on the fp32 pipe: where it goes when a value leaves fp16's range)
-            if (!hp::conv32_dw_fusable(q, false, A.dil) || (dtype == HP_DTYPE_F32S && !hp::conv32_dw_fusable(q, true, A.dil)))
+            if (!hp::pick32::dw_fusable(q, false, A.dil) || (dtype == HP_DTYPE_F32S && !hp::pick32::dw_fusable(q, true, A.dil)))
                 continue;
             fuse(i, fuse_kind::sep32);
         }
@@ -639,7 +640,7 @@ int hp_engine::mark_pair_fusions(const hp_engine_desc* d)
                 continue;
             if (!pointwise_behind(A, Bn) || Bn.res >= 0 || post_op_act(Bn) || !keeps_map(i) || !keeps_map(i + 1))
                 continue;
-            if (!hp::conv32_head_ok(A.cin, A.cout, Bn.cout) || A.in_coff + A.cin > round_up(tensors[A.in]->C, 32))
+            if (!hp::pick32::head_ok(A.cin, A.cout, Bn.cout) || A.in_coff + A.cin > round_up(tensors[A.in]->C, 32))
                 continue;
             if ((i > 0 && (fuse_next[i - 1] == fuse_kind::sep32)) || (fuse_next[i] == fuse_kind::sep32))
                 continue;
@@ -968,9 +969,13 @@ int hp_engine::lower32_conv(size_t i, step& st)
     p.B = max_batch, p.npix = p.pick_npix = max_batch * g.OH * g.OW;
     p.w_split = nullptr, p.w_frag = nullptr, p.w_wino = nullptr, p.w_wino3 = nullptr, p.ovf = ovf_dev, p.dbg = nullptr;
     p.lane_epilogue = switches.lane_epilogue;
-    // the weight forms of the kernels beside conv32_kernel; each looks at the filled p and says whether it applies
-    HP_TRY(lower32_winograd_forms(i, st, packed));
-    HP_TRY(lower32_direct_forms(i, st, packed, tsrc.cs - S.in_coff));
+    // the weight forms of the kernels beside conv32_kernel: conv32_layer_forms looks at the filled p and decides, the two lowerings pack and upload
+    const hp::conv32_forms f = hp::conv32_layer_forms(p, dtype, switches, dw_in_front, tsrc.cs - S.in_coff, L.cin);
+    HP_REQUIRE(!dw_in_front || f.kind == hp::C32_DIRECT, HP_ERR_STATE, "layer %zu: fused behind a depthwise layer but not a direct-kernel layer (engine bug)", i);
+    HP_TRY(lower32_winograd_forms(i, st, packed, f));
+    HP_TRY(lower32_direct_forms(i, st, packed, f));
+    // (the launch kind is the picker's: the lowerings above only packed what it asked for)
+    st.kind = f.kind == hp::C32_WINO2 ? launch_kind::wino2 : f.kind == hp::C32_WINO3 ? launch_kind::wino3 : f.kind == hp::C32_DIRECT ? launch_kind::direct : launch_kind::conv32;
     if (head_in_front) // (last: it replaces the payload `p` refers to)
         HP_TRY(lower32_head_in_front(i, st, w));
     return HP_OK;
@@ -1000,16 +1005,15 @@ int hp_engine::lower32_dw_in_front(size_t i, step& st)
 // instead of 36 (conv32_winograd.hip; HP_NO_WINOGRAD32=1 is the A/B switch back to the direct kernel).  The step's `flops` stay the
 // layer's ALGORITHMIC count (the direct form's 2 * 9 * Cin * Cout per pixel); the MFMA work issued is 16 / 36 of it (bench.py reports both).
 // (Never a layer with a depthwise or hidden layer fused in front: those are 1 x 1.)
-int hp_engine::lower32_winograd_forms(size_t i, step& st, const std::vector<float>& packed)
+int hp_engine::lower32_winograd_forms(size_t i, step& st, const std::vector<float>& packed, const hp::conv32_forms& f)
 {
     auto& p = st.cp32();
-    if (dtype != HP_DTYPE_F32 || switches.no_winograd32 || !hp::conv32_winograd_ok(p))
+    if (!f.w_wino)
         return HP_OK;
     const double wbytes = (double)layers[i].cout * 9 * layers[i].cin * 4; // the layer's own weights
     std::vector<float> wu((size_t)16 * p.Cout_pad * p.Cin);
     hp::conv32_winograd_pack(packed.data(), p.Cout_pad, p.Cin, wu.data());
     HP_TRY(upload(wu, p.w_wino));
-    st.kind = launch_kind::wino2;
     st.bytes += wbytes * (16.0 / 9 - 1);
     // ... or, opt-in (HP_WINO_F33=1), F(3 x 3, 3 x 3): 25 products per 3 x 3 tile - 1.44 x fewer MFMA cycles, same accuracy
     // (conv32_winograd3.hip).  Measured: it wins where its 24 x 6-pixel blocks tile the map exactly and the layer is mid-sized (256 -> 256
@@ -1017,11 +1021,10 @@ int hp_engine::lower32_winograd_forms(size_t i, step& st, const std::vector<floa
     // 45.0 (35.9 in 8 x 8 blocks) | 27.0, every layer of PifPaf's 97 / 49 / 25-row maps - because one 16-tile column per wavefront streams
     // 3.1 x the U bytes per output pixel.  Not the default: taken by itself only on PoseProposal's exactly tiled 48 x 48 / 24 x 24
     // stages it made configs[3] 0.6 % faster (4 353 -> 4 380 frames/s resident, two runs each) - not worth a second numeric path.
-    if (switches.wino_f33 && hp::conv32_winograd3_ok(p)) {
+    if (f.w_wino3) {
         std::vector<float> wu3((size_t)25 * p.Cout_pad * p.Cin);
         hp::conv32_winograd3_pack(packed.data(), p.Cout_pad, p.Cin, wu3.data());
         HP_TRY(upload(wu3, p.w_wino3));
-        st.kind = launch_kind::wino3;
         st.bytes += wbytes * (25.0 / 9 - 16.0 / 9);
     }
     return HP_OK;
@@ -1035,22 +1038,14 @@ int hp_engine::lower32_winograd_forms(size_t i, step& st, const std::vector<floa
 // layer within +-3 % or worse (64 -> 128 22.9 -> 29.0 paired, 512 -> 512 100 -> 100 alone): 1 x 1 layers wider than 64 padded outputs
 // stay on conv32_kernel
 // (a 3 x 3 layer the Winograd kernel has taken needs no direct-form fragments: they doubled its weight bytes in HBM)
-int hp_engine::lower32_direct_forms(size_t i, step& st, const std::vector<float>& packed, int room)
+int hp_engine::lower32_direct_forms(size_t, step& st, const std::vector<float>& packed, const hp::conv32_forms& f)
 {
     auto& p = st.cp32();
-    const int taps = p.KH * p.KW, cout_pad = p.Cout_pad;
-    const bool dw_in_front = p.dw_w != nullptr;
-    if (dtype != HP_DTYPE_F32S && !dw_in_front && (p.w_wino || (taps == 1 && cout_pad > 64)))
+    if (!f.w_frag)
         return HP_OK;
-    const int ck = taps == 1 ? 64 : 32, cin_s = round_up(layers[i].cin, ck);
-    hp::conv32_params q = p;
-    q.Cin = cin_s;
-    const bool direct = cin_s <= room && hp::conv32_direct_ok(q);
-    HP_REQUIRE(!dw_in_front || direct, HP_ERR_STATE, "layer %zu: fused behind a depthwise layer but not a direct-kernel layer (engine bug)", i);
-    if (!direct)
-        return HP_OK;
+    const int taps = p.KH * p.KW, cout_pad = p.Cout_pad, cin_s = f.cin_split;
     const std::vector<float> wide = hp::wpack::restride32(packed, taps, cout_pad, p.Cin, cin_s);
-    if (dtype == HP_DTYPE_F32S) {
+    if (f.w_split) {
         // (a BN-folded weight beyond fp16's range has no (hi, lo) split - hi would be inf - and the run-time flag only watches
         // activations: such an engine starts on the fp32 pipe.  ADVICE r5)
         for (float v : wide)
@@ -1064,7 +1059,7 @@ int hp_engine::lower32_direct_forms(size_t i, step& st, const std::vector<float>
     std::vector<float> wf(wide.size());
     hp::conv32_frag_pack(wide.data(), taps, cout_pad, cin_s, wf.data());
     HP_TRY(upload(wf, p.w_frag));
-    st.kind = launch_kind::direct, st.as<conv32_launch>().cin_split = cin_s;
+    st.as<conv32_launch>().cin_split = cin_s;
     return HP_OK;
 }
 
@@ -1084,7 +1079,7 @@ int hp_engine::lower32_head_in_front(size_t i, step& st, const float* w)
     HP_TRY(upload_padded(A.b_off, A.cout, A.cout, "bias", i - 1, hd.hh.bias1));
     std::vector<float> w1f(nwa);
     hp::conv32_frag_pack(wa, 1, A.cout, A.cin, w1f.data()); // ([1][HID][128] is the blob's own layout: HID rows of 128)
-    const int tm2 = L.cout <= 32 ? 1 : 2;
+    const int tm2 = hp::pick32::head_tm2(L.cout);
     const std::vector<float> w2p = hp::wpack::padded(w, nw, (size_t)p.Cout_pad * L.cin); // [cout][HID] rows, zero rows up to 32 tm2
     std::vector<float> w2f((size_t)32 * tm2 * L.cin);
     hp::conv32_head_pack(w2p.data(), tm2, L.cin, w2f.data());
@@ -1763,7 +1758,6 @@ launch_payload hp_engine::bound(const step& st, const uint8_t* u8, const float* 
 // The one place that knows which launcher a kind has.  dbg != nullptr: the HP_*_DBG relaunch, the family's debug field set on the bound copy.
 int hp_engine::launch(launch_kind kind, launch_payload& b, hipStream_t s, unsigned long long* dbg) const
 {
-    const bool split = dtype == HP_DTYPE_F32S && !split_off; // the direct kernel: on the fp16 pipe until a value left fp16's range, then on the fp32 pipe
     switch (kind) {
     case launch_kind::first16: HP_HIP_TRY(hp::launch_first_conv(std::get<hp::first_conv_params>(b), s)); break;
     case launch_kind::conv16: {
@@ -1800,7 +1794,7 @@ int hp_engine::launch(launch_kind kind, launch_payload& b, hipStream_t s, unsign
         HP_HIP_TRY(kind == launch_kind::conv32 ? hp::launch_conv32(cp, switches, s)
                 : kind == launch_kind::wino2   ? hp::launch_conv32_winograd(cp, switches, s)
                 : kind == launch_kind::wino3   ? hp::launch_conv32_winograd3(cp, s)
-                                               : hp::launch_conv32_direct(cp, split, s));
+                                               : hp::launch_conv32_direct(cp, on_split_pipe(), s));
         break;
     }
     case launch_kind::head32: HP_HIP_TRY(hp::launch_conv32_head(std::get<head32_launch>(b).cp, std::get<head32_launch>(b).hh, s)); break;
@@ -1825,11 +1819,11 @@ int hp_engine::tile_of(launch_kind kind, const launch_payload& b) const
     case launch_kind::head_pair: return 6000000 + std::get<head_pair_launch>(b).a.K1;
     case launch_kind::chain: return 7000000 + hp::conv_chain_variant(std::get<hp::chain_params>(b));
     case launch_kind::bneck: return 9000000 + hp::bottleneck_variant(std::get<hp::bneck_params>(b));
-    case launch_kind::conv32: return hp::conv32_tile(std::get<conv32_launch>(b).cp, switches);
-    case launch_kind::wino2:
-    case launch_kind::wino3: return hp::conv32_winograd_tile(std::get<conv32_launch>(b).cp);
-    case launch_kind::direct: return hp::conv32_direct_tile(std::get<conv32_launch>(b).cp, dtype == HP_DTYPE_F32S && !split_off);
-    case launch_kind::head32: return hp::conv32_head_tile(std::get<head32_launch>(b).hh.HID, std::get<head32_launch>(b).cp.Cout);
+    case launch_kind::conv32: return hp::pick_conv32(std::get<conv32_launch>(b).cp, switches, hp::C32_GEMM, false).tile;
+    case launch_kind::wino2: return hp::pick_conv32(std::get<conv32_launch>(b).cp, switches, hp::C32_WINO2, false).tile;
+    case launch_kind::wino3: return hp::pick_conv32(std::get<conv32_launch>(b).cp, switches, hp::C32_WINO3, false).tile;
+    case launch_kind::direct: return hp::pick_conv32(std::get<conv32_launch>(b).cp, switches, hp::C32_DIRECT, on_split_pipe()).tile;
+    case launch_kind::head32: return hp::pick32::head_tile(std::get<head32_launch>(b).hh.HID, std::get<head32_launch>(b).cp.Cout);
     default: return 0; // first convolutions, depthwise, pooling, up-sampling: one form each
     }
 }
@@ -1915,7 +1909,7 @@ int hp_engine::launch_head_pair32(size_t i, int n, int b0, hipStream_t s, bool* 
         return HP_OK;
     const auto &ha = steps[i].as<head32_launch>(), &hb = steps[i + 1].as<head32_launch>();
     const hp::conv32_params a = bind(ha.cp, n, b0), b = bind(hb.cp, n, b0);
-    if (!hp::conv32_head_pair_ok(a, b, switches))
+    if (!hp::pick32::head_pair_ok(a, b, switches))
         return HP_OK;
     HP_HIP_TRY(hp::launch_conv32_head_pair(a, ha.hh, b, hb.hh, s));
     *done = true;

@@ -568,7 +568,7 @@ def _bneck_proj_rows():
 def _sep32_rows(full=True):
     """mark_pair_fusions, fuse_kind::sep32: depthwise 3x3 stride 1, dilation 1 | 2, whole 64-channel chunks, none / relu / relu6 / leaky, TF-SAME
     geometry, one reader (the next layer, an unpadded 1x1 reading all of it) / one writer / no output; the 1x1 half may carry a residual
-    (not the elided tensor), write a slice and be an output; conv32_dw_fusable has a form."""
+    (not the elided tensor), write a slice and be an output; pick32::dw_fusable has a form."""
     v = [1]
     rows = [(None, v, "canonical"), (("batch",), v, "n < max_batch"), (("size", 9, 7), v, "")] + [(s, v, "") for s in SIZES]
     rows += [(("reader", 0), [], ""), (("as_res", 0), [], ""), (("mid_out", 0, 0.0), [], ""), (("mid_out", 0, 2.0), [], ""), (("mid_concat", 0), [], ""), (("sub", 0), [], "")]
@@ -585,7 +585,7 @@ def _sep32_rows(full=True):
 
 
 def _stage32_rows():
-    """Two head32 launches on one input (paired at run time, conv32_head_pair_ok: not visible in the profile), writing the stage's concat
+    """Two head32 launches on one input (paired at run time, pick32::head_pair_ok: not visible in the profile), writing the stage's concat
     slices at 128 and 147 which are outputs as well."""
     v = [1, 1]
     rows = [(None, v, "canonical"), (("batch",), v, "n < max_batch")] + [(s, v, "") for s in SIZES]
