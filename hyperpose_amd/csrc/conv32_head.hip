@@ -52,8 +52,9 @@ __device__ __forceinline__ void conv32_head_body(const conv32_params& q, const h
     {
         const int px = tid >> 3, q0 = tid & 7;
         const int n = min(n0 + px, q.npix - 1);
-        const int b = n / OHW, rem = n - b * OHW;
-        const int oy = rem / q.OW, ox = rem - oy * q.OW;
+        int b, oy, rem;
+        fd_pixel(n, q.fd_ohw, q.fd_ow, b, oy, rem);
+        const int ox = rem - oy * q.OW;
         const float* const src = q.in.p + tvh_off(q.in, b, oy, ox);
         f32x4 v[4];
 #pragma unroll
@@ -141,8 +142,9 @@ __device__ __forceinline__ void conv32_head_body(const conv32_params& q, const h
     const int np = n0 + n;
     const bool pix_ok = np < q.npix;
     const int nc = min(np, q.npix - 1);
-    const int b = nc / OHW, rem = nc - b * OHW;
-    const int oy = rem / q.OW, ox = rem - oy * q.OW;
+    int b, oy, rem;
+    fd_pixel(nc, q.fd_ohw, q.fd_ow, b, oy, rem);
+    const int ox = rem - oy * q.OW;
     const long ooff = q.out.p ? tvh_off(q.out, b, oy, ox) : 0;
     const bool out_vec = q.out.p && ((q.out.coff | q.out.cs) & 3) == 0;
 #pragma unroll
@@ -224,7 +226,8 @@ void conv32_head_pack(const float* w2, int tm2, int hid, float* out)
 }
 
 // what the picker (pick_head32, conv32_pick.hpp) does not see: the weights and an output to write
-static bool head_args_ok(const conv32_params& q, const head32_hidden& h) { return h.w1_frag && h.w2_frag && h.bias1 && (q.out.p || q.out_f32); }
+// (and the division constants the body turns a pixel into offsets with)
+static bool head_args_ok(const conv32_params& q, const head32_hidden& h) { return h.w1_frag && h.w2_frag && h.bias1 && (q.out.p || q.out_f32) && geom32_ok(q); }
 
 hipError_t launch_conv32_head_pair(const conv32_params& qa, const head32_hidden& ha, const conv32_params& qb, const head32_hidden& hb, hipStream_t s)
 {

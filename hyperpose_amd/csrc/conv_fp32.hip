@@ -106,8 +106,9 @@ __global__ __launch_bounds__(256) void conv32_kernel(const conv32_params p)
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
         const int n = min(n0 + lrow + 64 * j, p.npix - 1);
-        const int b = n / OHW, rem = n - b * OHW;
-        const int oy = rem / p.OW, ox = rem - oy * p.OW;
+        int b, oy, rem;
+        fd_pixel(n, p.fd_ohw, p.fd_ow, b, oy, rem);
+        const int ox = rem - oy * p.OW;
         bbase[j] = tv32_off(p.in, b, oy * p.stride - p.pad_t, ox * p.stride - p.pad_l) + lchunk;
     }
     const float* const wrow = p.w + (long)(m0 + lrow) * p.Cin + lchunk;
@@ -186,9 +187,8 @@ __global__ __launch_bounds__(256) void conv32_kernel(const conv32_params p)
         // NHWC output only (every layer but the network's heads): row-major through a private LDS slab (conv32_epilogue.hpp)
         lds_barrier(); // every wavefront is done with the last K-step's tiles the slabs lie over
         float* const slab = reinterpret_cast<float*>(lds_raw) + wave * (rows_geom<TM>::SLAB_BYTES / 4);
-        // pixel -> (image, row, column): ONE division pair for the lane's first slab row, carried from one pixel() call to the next (ascending pixels)
-        int pn = min(n0 + wn * TN * 32 + lane / rows_geom<TM>::LPR, p.npix - 1), pb = pn / OHW;
-        int poy = (pn - pb * OHW) / p.OW, pox = pn - pb * OHW - poy * p.OW;
+        // pixel -> (image, row) with the layer's division constants, per slab row: no carry loop whose trip count depends on the lane and the width
+        const fastdiv fohw = p.fd_ohw, fow = p.fd_ow;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             floatx16 fin[TM];
@@ -196,17 +196,13 @@ __global__ __launch_bounds__(256) void conv32_kernel(const conv32_params p)
             for (int i = 0; i < TM; ++i)
                 fin[i] = acc[i][j];
             const int nb = n0 + (wn * TN + j) * 32;
-            conv32_store_rows<TM>(p, fin, slab, lane, m0 + wm * TM * 32, [&](int r, bool& ok, long& ooff, long& roff) {
+            conv32_store_rows<TM>(p, fin, slab, lane, m0 + wm * TM * 32, [&](int r, bool& ok, long& ooff, long& roff) __attribute__((always_inline)) {
                 const int n = nb + r, nc = min(n, p.npix - 1);
                 ok = n < p.npix;
-                pox += nc - pn, pn = nc;
-                while (pox >= p.OW) {
-                    pox -= p.OW;
-                    if (++poy == p.OH)
-                        poy = 0, ++pb;
-                }
-                ooff = tv32_off(p.out, pb, poy, pox);
-                roff = p.res.p ? tv32_off(p.res, pb, poy, pox) : 0;
+                int b, oy, rem;
+                fd_pixel(nc, fohw, fow, b, oy, rem);
+                ooff = fd_view_pixel(nc, b, oy, fohw, fow, p.out.img, p.out.wp) * p.out.cs + p.out.coff;
+                roff = p.res.p ? fd_view_pixel(nc, b, oy, fohw, fow, p.res.img, p.res.wp) * p.res.cs + p.res.coff : 0;
             }, [&]() { HP_STAMP(); });
         }
     } else {
@@ -220,8 +216,9 @@ __global__ __launch_bounds__(256) void conv32_kernel(const conv32_params p)
         const int n = n0 + (wn * TN + j) * 32 + frow;
         const bool pix_ok = n < p.npix;
         const int nc = min(n, p.npix - 1);
-        const int b = nc / OHW, rem = nc - b * OHW;
-        const int oy = rem / p.OW, ox = rem - oy * p.OW;
+        int b, oy, rem;
+        fd_pixel(nc, p.fd_ohw, p.fd_ow, b, oy, rem);
+        const int ox = rem - oy * p.OW;
         const long ooff = p.out.p ? tv32_off(p.out, b, oy, ox) : 0;
         const long roff = p.res.p ? tv32_off(p.res, b, oy, ox) : 0;
 #pragma unroll
@@ -332,8 +329,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
         const int n = min(n0 + min(lrow + 64 * j, BN - 1), p.npix - 1); // (rows past the tile / the tensor: a clamped pixel nobody reads)
-        const int b = n / OHW, rem = n - b * OHW;
-        const int oy = rem / p.OW, ox = rem - oy * p.OW;
+        int b, oy, rem;
+        fd_pixel(n, p.fd_ohw, p.fd_ow, b, oy, rem);
+        const int ox = rem - oy * p.OW;
         bbase[j] = tv32_off(p.in, b, oy * p.stride - p.pad_t, ox * p.stride - p.pad_l) + lq * 4;
     }
     const float* const wrow = p.w + (long)(m0 + lrow) * p.Cin + lq * 4;
@@ -396,8 +394,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
     // epilogue: lane (n, q) of tile (i, j) holds channels m0 + wm * 16 TMW + i * 16 + 4 q + {0..3} of pixel n0 + wn * BN / WN + j * 16 + n.
     // In the form of conv32_winograd_kernel's drain: the staging registers and the fragments are dead here, their registers
-    // hold the epilogue's inputs.  Pixel -> offsets once per lane: ONE division pair for the lane's first pixel, carries for the tiles behind it
-    // (16 pixels apart).  A pixel past npix keeps the offsets of the tile before it (the first: of pixel npix - 1), a channel quad past Cout reads
+    // hold the epilogue's inputs.  Pixel -> offsets per tile (16 pixels apart) with the layer's division constants: eight instructions and two
+    // multiply-adds per view, no carry loop (its trip count was the lane's and the width's).  A pixel past npix keeps the offsets of the tile
+    // before it (the first: of pixel npix - 1), a channel quad past Cout reads
     // channel 0: addresses that valid lanes of the launch read, so every lane loads and no branch that depends on the lane lies between the
     // first request and the last (a divergent branch is a join at which hipcc waits for every load in flight).
     const int q = lane >> 4;
@@ -409,24 +408,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     int opix[TNW], rpix[TNW]; // the pixel's index in p.out / p.res (images of t.img pixels, rows of t.wp)
     bool pok[TNW];
     {
-        const int n = n0 + wn * (BN / WN) + fr, nc = min(n, p.npix - 1);
-        int b = nc / OHW;
-        const int rem = nc - b * OHW;
-        int oy = rem / p.OW, ox = rem - oy * p.OW;
-        pok[0] = n < p.npix;
-        opix[0] = b * p.out.img + oy * p.out.wp + ox;
-        rpix[0] = b * p.res.img + oy * p.res.wp + ox;
+        const int n = n0 + wn * (BN / WN) + fr;
 #pragma unroll
-        for (int j = 1; j < TNW; ++j) {
+        for (int j = 0; j < TNW; ++j) {
             pok[j] = n + 16 * j < p.npix;
-            ox += 16;
-            while (ox >= p.OW) { // (once where the map is 16 pixels wide or more)
-                ox -= p.OW;
-                if (++oy == p.OH)
-                    oy = 0, ++b;
-            }
-            opix[j] = pok[j] ? b * p.out.img + oy * p.out.wp + ox : opix[j - 1];
-            rpix[j] = pok[j] ? b * p.res.img + oy * p.res.wp + ox : rpix[j - 1];
+            const int nc = j == 0 ? min(n, p.npix - 1) : n + 16 * j; // (j > 0 past npix: not used)
+            int b, oy, rem;
+            fd_pixel(nc, p.fd_ohw, p.fd_ow, b, oy, rem);
+            const int op = (int)fd_view_pixel(nc, b, oy, p.fd_ohw, p.fd_ow, p.out.img, p.out.wp);
+            const int rp = (int)fd_view_pixel(nc, b, oy, p.fd_ohw, p.fd_ow, p.res.img, p.res.wp);
+            opix[j] = j == 0 || pok[j] ? op : opix[j - 1];
+            rpix[j] = j == 0 || pok[j] ? rp : rpix[j - 1];
         }
     }
     int mch[TMW];
@@ -517,7 +509,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
         for (int j = 0; j < TNW; ++j) {
             const int n = n0 + wn * (BN / WN) + j * 16 + fr, nc = min(n, p.npix - 1);
-            const int b = nc / OHW, rem = nc - b * OHW;
+            int b, oy, rem;
+            fd_pixel(nc, p.fd_ohw, p.fd_ow, b, oy, rem);
 #pragma unroll
             for (int i = 0; i < TMW; ++i)
 #pragma unroll
@@ -576,13 +569,13 @@ __global__ __launch_bounds__(256) void conv32_wk_kernel(const conv32_params p)
     if (ptile >= nx)
         return;
     const int n0 = ptile * BN, m0 = (bj % G) * BM;
-    const int OHW = p.OH * p.OW;
     auto swz = [](int row, int quad) { return row * 16 + ((quad ^ (((row >> 3) & 1) << 1)) << 2); };
 
     if (tid < BN) { // (pixels past the tensor: the last pixel again - read, multiplied, never stored)
         const int n = min(n0 + tid, p.npix - 1);
-        const int b = n / OHW, rem = n - b * OHW;
-        const int oy = rem / p.OW, ox = rem - oy * p.OW;
+        int b, oy, rem;
+        fd_pixel(n, p.fd_ohw, p.fd_ow, b, oy, rem);
+        const int ox = rem - oy * p.OW;
         s_in[tid] = tv32_off(p.in, b, oy * p.stride - p.pad_t, ox * p.stride - p.pad_l);
         s_out[tid] = tv32_off(p.out, b, oy, ox);
         s_res[tid] = p.res.p ? tv32_off(p.res, b, oy, ox) : 0;
@@ -751,7 +744,7 @@ bool set_act32(conv32_params& p)
 // Which kernel, tile and grid: pick_conv32 (conv32_pick.hpp)
 hipError_t launch_conv32(const conv32_params& p, const engine_switches& sw, hipStream_t s)
 {
-    if (p.Cin % 16 || p.Cout_pad % 64 || p.npix <= 0)
+    if (p.Cin % 16 || p.Cout_pad % 64 || !geom32_ok(p)) // (the kernels divide by OW / OH * OW with the struct's constants only)
         return hipErrorInvalidValue;
     const conv32_choice c = pick_conv32(p, sw, C32_GEMM, false);
     const int* const t = c.targ;
@@ -984,23 +977,25 @@ hipError_t launch_first_conv32(const first_conv32_params& p, const engine_switch
 // four loads for two outputs instead of six (1.5 + 1 requests of the vector memory path per output instead of 3 + 1: that path, not HBM,
 // bounds the kernel - 512 channels at 8 x 46 x 54 ran at 3.3 TB/s of its compulsory bytes).  Each output is the same chain of fmaf as before.
 template <int S, int D, int PX>
-__global__ __launch_bounds__(256) void dwconv32_kernel(const dw32_params p, int run)
+__global__ __launch_bounds__(256) void dwconv32_kernel(const dw32_params p)
 {
     static_assert(PX == 1 || (PX == 2 && S == 1), "column pairs share taps at stride 1 only");
     constexpr int NR = 2 * D + 1; // input rows one output needs, from its first to its last tap row
     constexpr int NC = 2 + PX;    // tap columns of a window row: offsets 0, D, 2 D (, 3 D)
-    const int CG = p.C / 4, segs = (p.OH + run - 1) / run;
-    const int ncol = PX == 1 ? p.OW : (p.OW + 2 * D - 1) / (2 * D) * D; // column slots: PX = 2 pairs columns (j, j + D) inside groups of 2 D
-    const long total = (long)p.B * segs * ncol * CG;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int cg = (int)(i % CG);
-        long n = i / CG;
-        const int q = (int)(n % ncol);
-        n /= ncol;
+    // thread index -> (channel group, column slot, row segment, image) in 32 bits with the layer's division constants (fastdiv.hpp; the launcher
+    // keeps the total below 2^31): three 64-bit `%` / `/` pairs per thread were a third of the instructions of a thread with 600 FMAs of work
+    const int run = p.run;
+    const fastdiv& fcol = p.fd_ncol[PX - 1]; // column slots: PX = 2 pairs columns (j, j + D) inside groups of 2 D
+    const uint32_t total = (uint32_t)p.B * p.fd_segs.d * fcol.d * p.fd_cg.d;
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        uint32_t n, ucg, uq, useg, ub;
+        fd_divmod(i, p.fd_cg, n, ucg);
+        fd_divmod(n, fcol, n, uq);
+        fd_divmod(n, p.fd_segs, ub, useg);
+        const int cg = (int)ucg, q = (int)uq, seg = (int)useg, b = (int)ub;
         const int ox = PX == 1 ? q : (q / D) * 2 * D + q % D;
         if (ox >= p.OW)
             continue; // (a ragged last group of 2 D columns)
-        const int seg = (int)(n % segs), b = (int)(n / segs);
         const int oy0 = seg * run, oy1 = min(oy0 + run, p.OH);
         f32x4 w[9];
 #pragma unroll
@@ -1010,10 +1005,10 @@ __global__ __launch_bounds__(256) void dwconv32_kernel(const dw32_params p, int 
         // input row r of the window = tensor row oy * S - pad_t + r; tap columns at ox * S - pad_l + {0, D, 2 D (, 3 D)}.  A column past the
         // tensor's halo (the second output of a pair beyond the map) is clamped to it: it only feeds an output that is not stored
         const int cx0 = ox * S - p.pad_l, cmax = p.W - 1 + (2 * D - p.pad_l);
-        long coff[NC];
+        int coff[NC]; // (at most 3 D pixels of cs elements: 32 bits)
 #pragma unroll
         for (int c = 0; c < NC; ++c)
-            coff[c] = (long)(min(cx0 + c * D, cmax) - cx0) * p.in.cs;
+            coff[c] = (min(cx0 + c * D, cmax) - cx0) * p.in.cs;
         const float* const col0 = p.in.p + tv32_off(p.in, b, oy0 * S - p.pad_t, cx0) + cg * 4;
         const long rstride = (long)p.in.wp * p.in.cs;
         f32x4 x[NR][NC];
@@ -1094,12 +1089,28 @@ __global__ __launch_bounds__(256) void dwconv32_any_kernel(const dw32_params p)
     }
 }
 
+// rows per thread: long runs re-use more, short runs give more threads; 8 keeps > 100 k threads on the 46 x 54 maps of LW-OpenPose
+static int dw32_run(int OH) { return OH >= 32 ? 8 : 4; }
+static int dw32_pair_cols(int OW, int dil) { return dil >= 1 ? (OW + 2 * dil - 1) / (2 * dil) * dil : OW; }
+
+void set_geom32(dw32_params& p)
+{
+    p.run = dw32_run(p.OH);
+    p.fd_cg = make_fastdiv(p.C / 4), p.fd_segs = make_fastdiv((p.OH + p.run - 1) / p.run);
+    p.fd_ncol[0] = make_fastdiv(p.OW), p.fd_ncol[1] = make_fastdiv(dw32_pair_cols(p.OW, p.dil));
+}
+
+static bool dw_geom32_ok(const dw32_params& p)
+{
+    return p.run == dw32_run(p.OH) && fastdiv_is(p.fd_cg, p.C / 4) && fastdiv_is(p.fd_segs, (p.OH + p.run - 1) / p.run) && fastdiv_is(p.fd_ncol[0], p.OW)
+        && fastdiv_is(p.fd_ncol[1], dw32_pair_cols(p.OW, p.dil));
+}
+
 hipError_t launch_dwconv32(const dw32_params& p, const engine_switches& sw, hipStream_t s)
 {
     if (p.C % 4)
         return hipErrorInvalidValue;
-    // rows per thread: long runs re-use more, short runs give more threads; 8 keeps > 100 k threads on the 46 x 54 maps of LW-OpenPose
-    const int run = p.OH >= 32 ? 8 : 4;
+    const int run = p.run;
     const int px_env = sw.dw32_px; // A/B switch and test hook: 1 = one column per thread always, 2 = pairs always
     const bool pairs = px_env != 1;
     // column pairs where they still leave > 120 k threads.  LW-OpenPose @ 8 x 46 x 54, us alone | with a second stream, one column -> pairs: 512 channels
@@ -1110,18 +1121,21 @@ hipError_t launch_dwconv32(const dw32_params& p, const engine_switches& sw, hipS
     const int ncol = two ? (p.OW + 2 * p.dil - 1) / (2 * p.dil) * p.dil : p.OW;
     const long total = (long)p.B * ((p.OH + run - 1) / run) * ncol * (p.C / 4);
     const int blocks = (int)std::min<long>((total + 255) / 256, 256 * 32);
+    const bool tiled = p.stride * p.dil == 1 || p.stride * p.dil == 2; // dwconv32_kernel's forms: 32-bit thread indices, the struct's division constants
+    if (tiled && (total >= (1L << 31) || !dw_geom32_ok(p)))
+        return hipErrorInvalidValue;
     if (p.stride == 1 && p.dil == 1) {
         if (two)
-            HP_LAUNCH((dwconv32_kernel<1, 1, 2>), dim3(blocks), dim3(256), 0, s, p, run);
+            HP_LAUNCH((dwconv32_kernel<1, 1, 2>), dim3(blocks), dim3(256), 0, s, p);
         else
-            HP_LAUNCH((dwconv32_kernel<1, 1, 1>), dim3(blocks), dim3(256), 0, s, p, run);
+            HP_LAUNCH((dwconv32_kernel<1, 1, 1>), dim3(blocks), dim3(256), 0, s, p);
     } else if (p.stride == 2 && p.dil == 1)
-        HP_LAUNCH((dwconv32_kernel<2, 1, 1>), dim3(blocks), dim3(256), 0, s, p, run);
+        HP_LAUNCH((dwconv32_kernel<2, 1, 1>), dim3(blocks), dim3(256), 0, s, p);
     else if (p.stride == 1 && p.dil == 2) {
         if (two)
-            HP_LAUNCH((dwconv32_kernel<1, 2, 2>), dim3(blocks), dim3(256), 0, s, p, run);
+            HP_LAUNCH((dwconv32_kernel<1, 2, 2>), dim3(blocks), dim3(256), 0, s, p);
         else
-            HP_LAUNCH((dwconv32_kernel<1, 2, 1>), dim3(blocks), dim3(256), 0, s, p, run);
+            HP_LAUNCH((dwconv32_kernel<1, 2, 1>), dim3(blocks), dim3(256), 0, s, p);
     }
     else {
         const long px = (long)p.B * p.OH * p.OW * (p.C / 4);

@@ -8,6 +8,7 @@
 // products; HP_DTYPE_F32S is the same engine with the dense products formed on the fp16 pipe (conv32_direct.hip, SPLIT).
 #pragma once
 #include "conv_kernels.hpp"
+#include "fastdiv.hpp"
 #include "hp_common.hpp"
 
 namespace hp {
@@ -21,6 +22,7 @@ struct tview32 {
 struct conv32_params {
     tview32 in;
     int B, H, W, OH, OW;
+    fastdiv fd_ow, fd_ohw; // division by OW and by OH * OW (fastdiv.hpp): set_geom32(), wherever OH / OW are filled - the kernels divide with these only
     int Cin;      // channels read per tap, multiple of 16 (the slice [coff, coff + Cin) must lie inside the buffer's channel stride)
     int Cout;     // real output channels
     int Cout_pad; // rows of the packed weight matrix, multiple of 64
@@ -61,6 +63,9 @@ struct conv32_params {
 };
 // fills act_slope / act_hi from act / act_param; false for activations the epilogue does not evaluate (sigmoid / softplus are output post-ops)
 bool set_act32(conv32_params& p);
+// fills fd_ow / fd_ohw from OH / OW (they do not depend on the batch); the launchers refuse a struct whose constants are not its geometry's
+inline void set_geom32(conv32_params& p) { p.fd_ow = make_fastdiv(p.OW), p.fd_ohw = make_fastdiv((long)p.OH * p.OW); }
+inline bool geom32_ok(const conv32_params& p) { return fastdiv_is(p.fd_ow, p.OW) && fastdiv_is(p.fd_ohw, (long)p.OH * p.OW) && p.npix > 0; }
 // Dense KH x KW convolution (any stride / dilation) as an implicit GEMM on v_mfma_f32_32x32x2_f32.
 // Which kernel, template instance and grid a launch below gets, the eligibility predicates and the profile rows' tile codes: conv32_pick.hpp.
 hipError_t launch_conv32(const conv32_params& p, const engine_switches& sw, hipStream_t s);
@@ -126,7 +131,12 @@ struct dw32_params {
     int act;
     float act_param;
     tview32 out;
+    // dwconv32_kernel's thread index -> (channel group, column slot, row segment, image) without a division (fastdiv.hpp): set_geom32()
+    int run;                           // output rows a thread marches down
+    fastdiv fd_cg, fd_segs;            // C / 4; segments of `run` rows in OH
+    fastdiv fd_ncol[2];                // column slots: [0] one column per thread (OW), [1] column pairs (groups of 2 dil)
 };
+void set_geom32(dw32_params& p);
 hipError_t launch_dwconv32(const dw32_params& p, const engine_switches& sw, hipStream_t s);
 
 struct pool32_params {

@@ -956,6 +956,7 @@ int hp_engine::lower32_conv(size_t i, step& st)
     p.in = ti.view32(L.in_coff);
     p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.Cin = cin_pad, p.Cout = L.cout, p.Cout_pad = cout_pad;
     p.KH = L.kh, p.KW = L.kw, p.stride = L.stride, p.dil = L.dil, p.pad_t = g.pt, p.pad_l = g.pl;
+    hp::set_geom32(p); // (the kernels' division constants: OW and OH * OW do not change with the call's batch)
     p.dw_w = nullptr, p.dw_dil = 0, p.dw_slope = 1.f, p.dw_hi = __builtin_huge_valf();
     st.flops = 2.0 * opix * L.cout * taps * L.cin;
     st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cout * 4 + (double)nw * 4;
@@ -1115,6 +1116,7 @@ int hp_engine::lower32_dw(size_t i, step& st)
     p.in = ti.view32(L.in_coff);
     p.H = ti.H, p.W = ti.W, p.OH = g.OH, p.OW = g.OW, p.C = L.cin, p.stride = L.stride, p.dil = L.dil;
     p.pad_t = g.pt, p.pad_l = g.pl, p.act = L.act, p.act_param = L.act_param;
+    hp::set_geom32(p); // (rows per thread and the division constants of the thread index)
     p.out = tensors[L.out]->view32(L.out_coff);
     st.flops = 2.0 * opix * L.cin * 9;
     st.bytes = (double)ti.H * ti.W * L.cin * 4 + opix * L.cin * 4;
