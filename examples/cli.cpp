@@ -23,6 +23,10 @@
 //   * flip ensemble (addition): `--flip_ensemble`: every frame - every tile of it with --tiles - runs through the network with its left-right
 //     flip and the parser reads the merged maps (engine.set_flip_ensemble / stream.set_flip_ensemble; include/hp_hip.h "flip ensemble"); a batch
 //     then holds --max_batch_size / 2 frames.  --post=paf only; works in both runtimes and with --tiles, --rotate, --hflip and --yuv_*;
+//   * scale ensemble (addition): `--scale_ensemble=<s>[,<s>...]` (1 .. 3 scales in (0, 1], e.g. 0.5,0.75): every frame - every tile of it - also runs
+//     shrunk by each scale and the parser reads the maps averaged over the K = count + 1 passes (engine.set_scale_ensemble /
+//     stream.set_scale_ensemble; include/hp_hip.h "scale ensemble"); a batch then holds --max_batch_size / K frames (/ 2K with --flip_ensemble).
+//     --post=paf only; both runtimes;
 //   * upright input (addition): `--rotate=0|90|180|270` (the clockwise turn that brings the stored picture upright: a container's rotate tag) and
 //     `--hflip` (the stored picture is mirrored left-right): the frames of every source, in both runtimes, are read upright inside the resize
 //     (engine.set_orientation / stream.set_orientation; hp::orientation).  Pictures and --saving_yuv frames stay in stored orientation, the
@@ -86,6 +90,8 @@ static hp::tiling g_tiling;
 static int FLAGS_rotate = 0;       // addition: --rotate=0|90|180|270: clockwise degrees that bring the stored frames upright (hp::orientation)
 static bool FLAGS_hflip = false;   // ... the stored frames are mirrored left-right
 static bool FLAGS_flip_ensemble = false; // addition: --flip_ensemble: frame + flipped frame through the network, maps merged on the device (PAF only)
+static std::string FLAGS_scale_ensemble; // addition: --scale_ensemble=0.5,0.75: frame + shrunken frames through the network, maps merged (PAF only)
+static std::vector<float> g_scales;      // ... parsed
 static hp::orientation g_orient;
 static std::string FLAGS_saving_yuv; // addition: append the frames, annotated on the device in their own format, to this file
 static int FLAGS_synthetic_humans = 0; // addition: stand-in humans added to every frame's poses (see the head of the file)
@@ -99,7 +105,8 @@ static bool parse_flags(int argc, char** argv)
 {
     std::map<std::string, std::string*> sflags = { { "model", &FLAGS_model }, { "post", &FLAGS_post }, { "source", &FLAGS_source },
         { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix }, { "saving_yuv", &FLAGS_saving_yuv }, { "tiles", &FLAGS_tiles }, { "yuv_format", &FLAGS_yuv_format },
-        { "yuv_matrix", &FLAGS_yuv_matrix }, { "yuv_range", &FLAGS_yuv_range }, { "yuv_transfer", &FLAGS_yuv_transfer } };
+        { "yuv_matrix", &FLAGS_yuv_matrix }, { "yuv_range", &FLAGS_yuv_range }, { "yuv_transfer", &FLAGS_yuv_transfer },
+        { "scale_ensemble", &FLAGS_scale_ensemble } };
     std::map<std::string, double*> dflags = { { "alpha", &FLAGS_alpha }, { "hdr_peak", &FLAGS_hdr_peak }, { "hdr_white", &FLAGS_hdr_white } };
     std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size }, { "tile_overlap", &FLAGS_tile_overlap },
         { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h }, { "synthetic_humans", &FLAGS_synthetic_humans }, { "rotate", &FLAGS_rotate } };
@@ -516,6 +523,33 @@ int main(int argc, char** argv)
                   << " network images per frame, more than --max_batch_size=" << FLAGS_max_batch_size << "\n";
         return 1;
     }
+    // --scale_ensemble likewise: 1 .. 3 scales in (0, 1], a PAF network, and room for every pass of a frame
+    if (!FLAGS_scale_ensemble.empty()) {
+        const std::string list = FLAGS_scale_ensemble + ",";
+        bool ok = true;
+        for (size_t at = 0, comma; ok && (comma = list.find(',', at)) != std::string::npos; at = comma + 1) {
+            const std::string item = list.substr(at, comma - at);
+            char* end = nullptr;
+            const float v = std::strtof(item.c_str(), &end);
+            ok = !item.empty() && *end == 0 && v > 0.f && v <= 1.f && g_scales.size() < 3; // (nan fails both comparisons)
+            g_scales.push_back(v);
+        }
+        if (!ok) {
+            cli_log() << "ERROR: --scale_ensemble=" << FLAGS_scale_ensemble << ": expected 1 .. 3 comma-separated scales in (0, 1], e.g. 0.5,0.75\n";
+            return 1;
+        }
+        if (FLAGS_post != kPAF) {
+            cli_log() << "ERROR: --scale_ensemble merges the maps of a PAF network (--post=" kPAF "), got --post=" << FLAGS_post << "\n";
+            return 1;
+        }
+        const int passes = (int)(g_scales.size() + 1) * (FLAGS_flip_ensemble ? 2 : 1) * (g_tiled ? g_tiling.regions() : 1);
+        if (passes > FLAGS_max_batch_size) {
+            cli_log() << "ERROR: --scale_ensemble runs every " << (g_tiled ? "region" : "frame") << " at " << g_scales.size() + 1 << " scales"
+                      << (FLAGS_flip_ensemble ? " with their flips" : "") << ": " << passes << " network images per frame, more than --max_batch_size="
+                      << FLAGS_max_batch_size << "\n";
+            return 1;
+        }
+    }
     if (g_tiled && g_tiling.regions() > FLAGS_max_batch_size) {
         cli_log() << "ERROR: --tiles=" << FLAGS_tiles << (FLAGS_tile_full ? " --tile_full" : "") << " makes " << g_tiling.regions()
                   << " regions per frame, more than --max_batch_size=" << FLAGS_max_batch_size << "\n";
@@ -583,6 +617,10 @@ int main(int argc, char** argv)
     if (FLAGS_flip_ensemble && FLAGS_runtime != kSTREAM) { // (after the calibration, which runs the plain schedule; the stream sets its own engines)
         engine.set_flip_ensemble(true);
         cli_log() << "--flip_ensemble: every frame runs with its left-right flip, batches of up to " << engine.batch_room() << "\n";
+    }
+    if (!g_scales.empty() && FLAGS_runtime != kSTREAM) { // (after the calibration, as the flip ensemble)
+        engine.set_scale_ensemble(g_scales);
+        cli_log() << "--scale_ensemble: every frame runs at " << g_scales.size() + 1 << " scales, batches of up to " << engine.batch_room() << "\n";
     }
     if (FLAGS_runtime != kOPERATOR && FLAGS_runtime != kSTREAM) {
         cli_log() << "WARNING: --runtime=" << FLAGS_runtime << " is neither " kOPERATOR " nor " kSTREAM "; using " kOPERATOR "\n";
@@ -687,6 +725,8 @@ int main(int argc, char** argv)
                 stream.set_orientation(g_orient);
                 if (FLAGS_flip_ensemble)
                     stream.set_flip_ensemble(true);
+                if (!g_scales.empty())
+                    stream.set_scale_ensemble(g_scales);
                 stream.async() << images;
                 auto sink = [&](size_t, const cv::Mat& frame, const std::vector<hp::human_t>& poses) {
                     cv::Mat img = clone(frame);

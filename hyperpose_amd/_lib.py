@@ -126,6 +126,8 @@ SYMBOLS = [
     "hp_orientation_from_exif", "hp_orient_roi", "hp_orient_u8c3_host", "hp_humans_orient", "hp_pipeline_set_orientation",
     "hp_hflip_u8c3", "hp_hflip_u8c3_host", "hp_flip_merge", "hp_flip_merge_host", "hp_flip_tables_coco", "hp_engine_set_flip_ensemble",
     "hp_engine_set_flip_ensemble_coco", "hp_engine_flip_ensemble", "hp_pipeline_set_flip_ensemble",
+    "hp_scale_stage_u8c3", "hp_scale_stage_u8c3_host", "hp_scale_tables", "hp_scale_merge", "hp_scale_merge_host", "hp_engine_set_scale_ensemble",
+    "hp_engine_set_scale_ensemble_coco", "hp_engine_scale_ensemble", "hp_pipeline_set_scale_ensemble",
 ]
 
 

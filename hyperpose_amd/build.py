@@ -45,6 +45,8 @@ UNITS = [
     ("overlay.hip", ["-ffp-contract=off"]),
     # the flip ensemble's merge is fp32 vector code in the engines' streams, beside fp16 MFMA kernels, and bit-equal to its host twin
     ("flip_ensemble.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # the scale ensemble's merge and its fp32 bicubic tables: the flip unit's reasons; its stage is resize_device.hpp's arithmetic once more
+    ("scale_ensemble.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("paf_parser.hip", ["-ffp-contract=off"]),
     ("ppn_parser.hip", ["-ffp-contract=off"]),
     ("pifpaf_parser.hip", ["-ffp-contract=off"]),

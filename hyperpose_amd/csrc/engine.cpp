@@ -16,6 +16,7 @@
 #include "engine_timeline.hpp"
 #include "call_plan.hpp"
 #include "hp_common.hpp"
+#include "scale_ensemble.hpp"
 #include "weight_pack.hpp"
 
 #include <algorithm>
@@ -267,11 +268,21 @@ struct hp_engine {
         std::vector<int8_t> sign;
     };
     std::vector<flip_table> flip;
-    hp::dev_buf flip_in; // [max_batch][in_h][in_w][3] u8
+    hp::dev_buf flip_in; // [max_batch][in_h][in_w][3] u8: the staging buffer of both ensembles
     bool flip_on() const { return !flip.empty(); }
-    // dev_src != nullptr: the n frames are copied into flip_in first (device to device); then their flips are written behind them
-    int flip_stage(const uint8_t* dev_src, int n, hipStream_t s) const;
-    int flip_merge(int n, hipStream_t s) const; // hp_flip_merge on every output: frames [0, n) become the ensemble
+    // Scale ensemble (hp_engine_set_scale_ensemble; csrc/scale_ensemble.hpp): the K - 1 extra scales while on, empty while off.  A u8 batch of n
+    // frames then runs as the K n slots of flip_in - the caller's frames, their shrunken copies behind them, scale-major - (and their flips behind
+    // those when the flip ensemble is on too), and every output's frames [0, n) become the average of the K passes.
+    std::vector<float> scale_ens;
+    int scale_bgr[3] = { 0, 0, 0 };
+    int scale_map_w = 0, scale_map_h = 0; // every output's W x H
+    hp::dev_buf scale_tables;             // hp_scale::tap4 [K-1][W], then [K-1][H]
+    int scale_k() const { return 1 + (int)scale_ens.size(); }
+    // dev_src != nullptr: the n frames are copied into flip_in first (device to device); then, as the plan says, their shrunken copies are written
+    // behind them (scales = K > 1) and the flips of all K n slots behind those (flip)
+    int ensemble_stage(const uint8_t* dev_src, int n, int scales, bool with_flip, hipStream_t s) const;
+    // hp_flip_merge on every output over the K n slots (flip), then the scale merge over the n frames (scales = K > 1): frames [0, n) become the ensemble
+    int ensemble_merge(int n, int scales, bool with_flip, hipStream_t s) const;
 
     ~hp_engine() // (hp_engine_destroy has synchronised; `graphs` destroys what it still holds)
     {
@@ -353,7 +364,7 @@ struct hp_engine {
     template <typename V>
     float* fused_output(size_t layer, bool whole_tensor_only, V& out);
     int pointwise_params(size_t layer, int H, int W, int cout_pad, hp::conv_params& q); // the 1 x 1 second half of a fused fp16 pair
-    hp::call_settings call_settings(bool ensemble, bool graph) const { return { max_batch, parts, halves_ok(), ensemble, graph }; }
+    hp::call_settings call_settings(bool ensemble, bool graph, int scales = 1) const { return { max_batch, parts, halves_ok(), ensemble, graph, scales }; }
     int run_call(const hp::call_settings& cfg, const hp::call_args& a); // one call, from its arguments to its launches: csrc/call_plan.hpp decides
     // ---- running the schedule: const, `steps` is written by build(), apply_int8_scales() and nobody else
     int enqueue_range(const uint8_t* u8, const float* f32, int b0, int n, hipStream_t s) const;
@@ -1615,19 +1626,26 @@ int hp_engine::apply_int8_scales()
     return HP_OK;
 }
 
-int hp_engine::flip_stage(const uint8_t* dev_src, int n, hipStream_t s) const
+int hp_engine::ensemble_stage(const uint8_t* dev_src, int n, int scales, bool with_flip, hipStream_t s) const
 {
     const size_t bytes = (size_t)n * in_h * in_w * 3;
     if (dev_src)
         HP_HIP_TRY(hipMemcpyAsync(flip_in.p, dev_src, bytes, hipMemcpyDeviceToDevice, s));
-    return hp_hflip_u8c3(flip_in.as<uint8_t>(), flip_in.as<uint8_t>() + bytes, in_w, in_h, n, s);
+    if (scales > 1)
+        HP_TRY(hp_scale::launch_stage(flip_in.as<uint8_t>(), flip_in.as<uint8_t>() + bytes, in_w, in_h, n, scale_map_w, scale_map_h, scale_ens.data(),
+            scales - 1, scale_bgr, s));
+    return with_flip ? hp_hflip_u8c3(flip_in.as<uint8_t>(), flip_in.as<uint8_t>() + scales * bytes, in_w, in_h, scales * n, s) : HP_OK;
 }
 
-int hp_engine::flip_merge(int n, hipStream_t s) const
+int hp_engine::ensemble_merge(int n, int scales, bool with_flip, hipStream_t s) const
 {
-    for (size_t i = 0; i < outputs.size(); ++i) {
+    for (size_t i = 0; i < outputs.size() && with_flip; ++i) {
         const out_info& o = outputs[i];
-        HP_TRY(hp_flip_merge(o.buf->as<float>(), n, o.out_c(), o.x.out_h, o.x.out_w, flip[i].perm.data(), flip[i].sign.data(), s));
+        HP_TRY(hp_flip_merge(o.buf->as<float>(), scales * n, o.out_c(), o.x.out_h, o.x.out_w, flip[i].perm.data(), flip[i].sign.data(), s));
+    }
+    for (size_t i = 0; i < outputs.size() && scales > 1; ++i) {
+        const out_info& o = outputs[i];
+        HP_TRY(hp_scale::launch_merge(o.buf->as<float>(), n, scales, o.out_c(), o.x.out_h, o.x.out_w, scale_tables.as<hp_scale::tap4>(), s));
     }
     return HP_OK;
 }
@@ -1966,11 +1984,11 @@ int hp_engine::run_call(const hp::call_settings& cfg, const hp::call_args& a)
     auto range = [&](int i) -> int {
         return enqueue_range(p.kind == 0 ? (const uint8_t*)p.read : nullptr, p.kind == 1 ? (const float*)p.read : nullptr, p.ranges[i].b0, p.ranges[i].cnt, stream_of(i));
     };
-    auto bracketed = [&](auto&& inner) -> int { // the ensemble's flip and merge around `inner`, on the call's stream (images / 2: the caller's frames)
-        if (p.ensemble)
-            HP_TRY(flip_stage((const uint8_t*)p.fl_src, p.images / 2, s));
+    auto bracketed = [&](auto&& inner) -> int { // the ensembles' stage and merge around `inner`, on the call's stream (a.n: the caller's frames)
+        if (p.staged)
+            HP_TRY(ensemble_stage((const uint8_t*)p.fl_src, a.n, p.scales, p.ensemble, s));
         HP_TRY(inner());
-        return p.ensemble ? flip_merge(p.images / 2, s) : HP_OK;
+        return p.staged ? ensemble_merge(a.n, p.scales, p.ensemble, s) : HP_OK;
     };
     // capture a range's schedule once per key; replays cost one launch.  A call names ALL its ranges at once: the cache decides about eviction
     // before the first capture, so no executable of this call can be destroyed before it is launched (csrc/graph_cache.hpp), and a call whose
@@ -1994,8 +2012,8 @@ int hp_engine::run_call(const hp::call_settings& cfg, const hp::call_args& a)
     };
     if (p.captured)
         HP_TRY(graphs.acquire(p.keys, p.nr, exec, capture, sync_device));
-    if (p.host_src && p.ensemble)
-        HP_TRY(upload(0, p.images / 2, s));
+    if (p.host_src && p.staged)
+        HP_TRY(upload(0, a.n, s));
     // Two half-batches side by side: frames [0, n0) on `s`, [n0, n) on stream2, which joins `s` again.  The kernels of one half are half as many
     // blocks - what fills the chip is that the halves are never in the same phase (a store-bound launch of one runs under an MFMA-bound launch of
     // the other): 2490 -> 1962 us per synchronous batch of 8 (profiles/r06_half_batch_probe.txt).  Frames are independent and every kernel is
@@ -2005,7 +2023,7 @@ int hp_engine::run_call(const hp::call_settings& cfg, const hp::call_args& a)
             HP_HIP_TRY(hipEventRecord(ev_fork, s));
             HP_HIP_TRY(hipStreamWaitEvent(stream2, ev_fork, 0));
         }
-        for (int i = 0; i < p.nr && p.host_src && !p.ensemble; ++i) // (the second half's frames cross PCIe under the first half's first layers)
+        for (int i = 0; i < p.nr && p.host_src && !p.staged; ++i) // (the second half's frames cross PCIe under the first half's first layers)
             HP_TRY(upload(p.ranges[i].b0, p.ranges[i].cnt, stream_of(i)));
         for (int i = 0; i < p.nr; ++i)
             if (p.captured)
@@ -2195,7 +2213,7 @@ static int infer_common(hp_engine* e, const hp::call_args& a)
     if (e->split_overflowed()) // an earlier batch held a value outside fp16's range: from here on the fp32 matrix pipe
         HP_TRY(e->leave_split());
     e->last = a;
-    const hp::call_settings cfg = e->call_settings(e->flip_on(), e->use_graph);
+    const hp::call_settings cfg = e->call_settings(e->flip_on(), e->use_graph, e->scale_k());
     const hp::call_refusal why = hp::refusal_of(cfg, a);
     HP_REQUIRE(why != hp::CALL_EMPTY, HP_ERR_INVALID, "hp_engine_infer: empty batch");
     // TensorRT builds no kINT8 engine without a calibrator or per-tensor dynamic ranges; here the engine exists and refuses to run
@@ -2204,6 +2222,12 @@ static int infer_common(hp_engine* e, const hp::call_args& a)
             "hp_engine_infer: the HP_DTYPE_I8 engine is not calibrated: call hp_engine_calibrate_u8 (calibrate()) or hp_engine_set_int8_scales first");
     // src/tensorrt.cpp:439-443 throws std::logic_error here
     HP_REQUIRE(why != hp::CALL_OVERFLOW, HP_ERR_CAPACITY, "Input batch size overflow: Yours@%d Max@%d", a.n, e->max_batch);
+    if (cfg.scales > 1) { // (the flip ensemble's messages below keep their wording while the scale ensemble is off)
+        HP_REQUIRE(why != hp::CALL_F32_ENSEMBLE, HP_ERR_STATE, "hp_engine_infer_f32: not available while the scale ensemble%s is on (it is defined on u8 frames: hp_engine_infer_u8)",
+            cfg.ensemble ? " (and the flip ensemble)" : "");
+        HP_REQUIRE(why != hp::CALL_ENSEMBLE_OVERFLOW, HP_ERR_CAPACITY, "Input batch size overflow: Yours@%d, with the scale ensemble on (K = %d)%s %d network images, Max@%d",
+            a.n, cfg.scales, cfg.ensemble ? " and the flip ensemble on" : "", hp::images_of(cfg, a.n), e->max_batch);
+    }
     HP_REQUIRE(why != hp::CALL_F32_ENSEMBLE, HP_ERR_STATE, "hp_engine_infer_f32: not available while the flip ensemble is on (it is defined on u8 frames: hp_engine_infer_u8)");
     HP_REQUIRE(why != hp::CALL_ENSEMBLE_OVERFLOW, HP_ERR_CAPACITY, "Input batch size overflow: Yours@%d, with the flip ensemble on %d network images, Max@%d", a.n,
         2 * a.n, e->max_batch);
@@ -2426,6 +2450,59 @@ int hp_engine_set_flip_ensemble_coco(hp_engine* e, int enable)
 }
 
 int hp_engine_flip_ensemble(const hp_engine* e) { return e ? (int)e->flip_on() : HP_ERR_INVALID; }
+
+int hp_engine_set_scale_ensemble(hp_engine* e, const float* scales, int n_scales, int b, int g, int r)
+{
+    const char* who = "hp_engine_set_scale_ensemble";
+    HP_REQUIRE(e, HP_ERR_INVALID, "%s: null engine", who);
+    if (n_scales == 0) {
+        HP_TRY(e->drop_graphs()); // (the captured schedules are of the other form)
+        e->scale_ens.clear(), e->scale_tables.release();
+        return HP_OK;
+    }
+    HP_TRY(hp_scale::check_scales(who, scales, n_scales));
+    HP_REQUIRE(b >= 0 && b <= 255 && g >= 0 && g <= 255 && r >= 0 && r <= 255, HP_ERR_INVALID, "%s: fill (%d, %d, %d) is outside 0 .. 255", who, b, g, r);
+    const int NO = (int)e->outputs.size();
+    HP_REQUIRE(NO >= 1, HP_ERR_INVALID, "%s: the engine has no outputs", who);
+    const int H = e->outputs[0].x.out_h, W = e->outputs[0].x.out_w;
+    for (int i = 0; i < NO; ++i) {
+        const out_info& o = e->outputs[i];
+        HP_REQUIRE(o.x.out_h == H && o.x.out_w == W, HP_ERR_INVALID, "%s: outputs %s %d x %d and %s %d x %d differ in size: the scale ensemble needs one map grid", who,
+            e->outputs[0].name.c_str(), W, H, o.name.c_str(), o.x.out_w, o.x.out_h);
+        HP_REQUIRE(o.out_c() >= 1 && o.out_c() <= hp_scale::MAX_C, HP_ERR_INVALID, "%s: output %d (%s) has %d channels, the scale merge takes 1 .. %d", who, i,
+            o.name.c_str(), o.out_c(), hp_scale::MAX_C);
+    }
+    HP_REQUIRE(e->in_w % W == 0 && e->in_h % H == 0, HP_ERR_INVALID, "%s: the input %d x %d is not a whole number of map cells of the outputs' %d x %d", who, e->in_w,
+        e->in_h, W, H);
+    std::vector<hp_scale::tap4> tables(hp_scale::tables_entries(n_scales, H, W));
+    HP_TRY(hp_scale::fill_tables(tables.data(), scales, n_scales, H, W));
+    HP_TRY(e->drop_graphs()); // (the captured schedules are of the other form; and nothing in flight reads the old tables from here on)
+    const size_t need = (size_t)e->max_batch * e->in_h * e->in_w * 3;
+    if (e->flip_in.bytes < need)
+        HP_TRY(e->flip_in.alloc(need));
+    HP_TRY(e->scale_tables.alloc(tables.size() * sizeof(hp_scale::tap4)));
+    HP_HIP_TRY(hipMemcpy(e->scale_tables.p, tables.data(), tables.size() * sizeof(hp_scale::tap4), hipMemcpyHostToDevice));
+    e->scale_ens.assign(scales, scales + n_scales);
+    e->scale_bgr[0] = b, e->scale_bgr[1] = g, e->scale_bgr[2] = r, e->scale_map_w = W, e->scale_map_h = H;
+    return HP_OK;
+}
+
+int hp_engine_set_scale_ensemble_coco(hp_engine* e, const float* scales, int n_scales)
+{
+    HP_REQUIRE(e, HP_ERR_INVALID, "hp_engine_set_scale_ensemble_coco: null engine");
+    if (n_scales == 0)
+        return hp_engine_set_scale_ensemble(e, nullptr, 0, 0, 0, 0);
+    const int NO = (int)e->outputs.size();
+    HP_REQUIRE(NO == 2, HP_ERR_INVALID, "hp_engine_set_scale_ensemble_coco: a COCO PAF network has two outputs (conf, paf), this engine has %d", NO);
+    const out_info &c = e->outputs[0], &p = e->outputs[1];
+    HP_REQUIRE((c.out_c() == HP_COCO_N_PARTS || c.out_c() == HP_COCO_N_PARTS + 1) && p.out_c() == 2 * HP_COCO_N_PAIRS, HP_ERR_INVALID,
+        "hp_engine_set_scale_ensemble_coco: outputs %s with %d and %s with %d channels, expected 18 or 19 and 38", c.name.c_str(), c.out_c(), p.name.c_str(), p.out_c());
+    HP_REQUIRE(c.x.out_h == p.x.out_h && c.x.out_w == p.x.out_w, HP_ERR_INVALID, "hp_engine_set_scale_ensemble_coco: outputs %s %d x %d and %s %d x %d differ in size",
+        c.name.c_str(), c.x.out_h, c.x.out_w, p.name.c_str(), p.x.out_h, p.x.out_w);
+    return hp_engine_set_scale_ensemble(e, scales, n_scales, 0, 0, 0);
+}
+
+int hp_engine_scale_ensemble(const hp_engine* e) { return e ? e->scale_k() : HP_ERR_INVALID; }
 
 int hp_engine_num_outputs(const hp_engine* e) { return e ? (int)e->outputs.size() : HP_ERR_INVALID; }
 

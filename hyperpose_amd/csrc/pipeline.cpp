@@ -24,7 +24,8 @@
 // hp_pipeline_submit_yuv_images get the tone-map, 8-bit frames of the same batch get null.  Upright input (hp_pipeline_set_orientation): the submitted
 // frames are STORED frames, and everything behind the resize - letterbox, tiles, resume_ratio, the merge - sees the upright uw x uh frame of plan_frame().
 // Flip ensemble (hp_pipeline_set_flip_ensemble): every pipe's engine runs each network-sized slot and its left-right flip and merges the maps
-// (flip_ensemble.hip) before the parser reads them; here only the capacity changes: a batch holds pl->capacity() = max_batch / 2 slots.
+// (flip_ensemble.hip) before the parser reads them; here only the capacity changes: a batch holds pl->capacity() = max_batch / 2 slots.  Scale
+// ensemble (hp_pipeline_set_scale_ensemble): the same with K - 1 shrunken copies of every slot (scale_ensemble.hip), max_batch / (K (flip ? 2 : 1)).
 // Three things leave the road on purpose:
 //     (a) an untiled, un-oriented BGR frame of the network's size needs no kernel: it is copied straight into its slot of p.net, and a run of such
 //         frames that is contiguous in pinned host memory goes in ONE copy (the benchmark's path)
@@ -33,6 +34,7 @@
 //     (c) all copies first, then all kernels, within a batch - also where (a) mixes direct and resized frames
 #include "hp_common.hpp"
 #include "parser_host.hpp"
+#include "scale_ensemble.hpp"
 #include "yuv_formats.hpp"
 
 #include <cstring>
@@ -78,8 +80,18 @@ struct hp_pipeline {
     int orientation = HP_ORIENT_NONE; // non-zero: submitted frames are stored turned / mirrored, p.w / p.h and the regions are the upright frame's
     hp_tonemap* tonemap = nullptr; // set: 10-bit hp_yuv_image frames are PQ / HLG and are tone-mapped while they are resized
     bool flip_ensemble = false;    // set: every engine runs slot + flipped slot, so a batch holds half as many slots
-    int capacity() const { return flip_ensemble ? max_batch / 2 : max_batch; } // network-sized slots per submit
-    const char* flip_note() const { return flip_ensemble ? " / 2: the flip ensemble is on, every frame runs with its flip" : ""; }
+    std::vector<float> scale_ens;  // set: every engine runs slot + its K - 1 shrunken copies, so a batch holds 1 / K as many slots
+    int passes() const { return (int)(1 + scale_ens.size()) * (flip_ensemble ? 2 : 1); } // network images per slot
+    int capacity() const { return max_batch / passes(); } // network-sized slots per submit
+    std::string note;              // what flip_note() says under the scale ensemble (set_note)
+    const char* flip_note() const { return !scale_ens.empty() ? note.c_str() : flip_ensemble ? " / 2: the flip ensemble is on, every frame runs with its flip" : ""; }
+    void set_note()
+    {
+        char b[160];
+        std::snprintf(b, sizeof b, " / %d: the scale ensemble (K = %d)%s is on, every frame runs %d times", passes(), (int)(1 + scale_ens.size()),
+            flip_ensemble ? " and the flip ensemble" : "", passes());
+        note = b;
+    }
 
     // the tone-map of a frame, or null for the SDR path
     const hp_tonemap* tonemap_for(const hp_yuv_image& f) const { return tonemap && hp_yuv::layout_of(f.format)->sample_bytes == 2 ? tonemap : nullptr; }
@@ -236,6 +248,9 @@ int hp_pipeline_set_tiling(hp_pipeline* pl, const hp_tiling* t)
     if (R < 0)
         return R;
     HP_REQUIRE(R <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_set_tiling: %d regions per frame > max_batch %d", R, pl->max_batch);
+    if (!pl->scale_ens.empty()) // (the flip ensemble's message below keeps its wording while the scale ensemble is off)
+        HP_REQUIRE(R * pl->passes() <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_set_tiling: %d regions per frame x %d passes (the scale ensemble%s is on) > max_batch %d",
+            R, pl->passes(), pl->flip_ensemble ? " and the flip ensemble" : "", pl->max_batch);
     HP_REQUIRE(R <= pl->capacity(), HP_ERR_CAPACITY, "hp_pipeline_set_tiling: %d regions per frame and their flips (the flip ensemble is on) > max_batch %d", R, pl->max_batch);
     HP_REQUIRE(t->min_common >= 1 && t->tol >= 0., HP_ERR_INVALID, "hp_pipeline_set_tiling: min_common %d (>= 1), tol %g (>= 0)", t->min_common, t->tol);
     pl->tiling = *t, pl->tiled = true;
@@ -271,8 +286,11 @@ int hp_pipeline_set_flip_ensemble(hp_pipeline* pl, int enable)
     HP_REQUIRE(pl->kind == HP_PARSER_PAF, HP_ERR_INVALID, "hp_pipeline_set_flip_ensemble: the flip ensemble is defined for HP_PARSER_PAF pipelines, this one ends in %s",
         kinds[pl->kind]);
     if (enable) {
+        const int R = tiled_regions(pl), K = 1 + (int)pl->scale_ens.size();
+        if (K > 1) // (the messages below keep their wording while the scale ensemble is off)
+            HP_REQUIRE(2 * K * R <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_set_flip_ensemble: %d regions per frame x %d scales (the scale ensemble is on) and their flips > max_batch %d",
+                R, K, pl->max_batch);
         HP_REQUIRE(pl->max_batch >= 2, HP_ERR_CAPACITY, "hp_pipeline_set_flip_ensemble: max_batch %d has no room for a frame and its flip", pl->max_batch);
-        const int R = tiled_regions(pl);
         HP_REQUIRE(!pl->tiled || 2 * R <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_set_flip_ensemble: %d regions per frame (tiling is on) and their flips > max_batch %d", R,
             pl->max_batch);
     }
@@ -285,6 +303,34 @@ int hp_pipeline_set_flip_ensemble(hp_pipeline* pl, int enable)
         }
     }
     pl->flip_ensemble = enable != 0;
+    pl->set_note();
+    return HP_OK;
+}
+
+int hp_pipeline_set_scale_ensemble(hp_pipeline* pl, const float* scales, int n_scales)
+{
+    static const char* const kinds[] = { "HP_PARSER_PAF", "HP_PARSER_PPN", "HP_PARSER_PIFPAF" };
+    HP_REQUIRE(pl, HP_ERR_INVALID, "hp_pipeline_set_scale_ensemble: null pipeline");
+    HP_REQUIRE(pl->inflight == 0, HP_ERR_STATE, "hp_pipeline_set_scale_ensemble: %d batches are in flight, collect first", pl->inflight);
+    HP_REQUIRE(pl->kind == HP_PARSER_PAF, HP_ERR_INVALID, "hp_pipeline_set_scale_ensemble: the scale ensemble is defined for HP_PARSER_PAF pipelines, this one ends in %s",
+        kinds[pl->kind]);
+    HP_REQUIRE(n_scales >= 0, HP_ERR_INVALID, "hp_pipeline_set_scale_ensemble: n_scales %d (0 turns the ensemble off, 1 .. 3 extra scales)", n_scales);
+    if (n_scales) {
+        HP_TRY(hp_scale::check_scales("hp_pipeline_set_scale_ensemble", scales, n_scales));
+        const int R = tiled_regions(pl), K = 1 + n_scales, F = pl->flip_ensemble ? 2 : 1;
+        HP_REQUIRE(R * K * F <= pl->max_batch, HP_ERR_CAPACITY, "hp_pipeline_set_scale_ensemble: %d region%s per frame x %d scales%s > max_batch %d", R,
+            R == 1 ? "" : "s (tiling is on)", K, F == 2 ? " x 2 (the flip ensemble is on)" : "", pl->max_batch);
+    }
+    for (size_t i = 0; i < pl->pipes.size(); ++i) {
+        const int rc = hp_engine_set_scale_ensemble_coco(pl->pipes[i].eng, scales, n_scales);
+        if (rc != HP_OK) { // (every pipe holds the same network: a refusal is the first pipe's, and nothing has changed)
+            for (size_t j = 0; j < i; ++j)
+                (void)hp_engine_set_scale_ensemble_coco(pl->pipes[j].eng, pl->scale_ens.data(), (int)pl->scale_ens.size());
+            return rc;
+        }
+    }
+    pl->scale_ens.assign(scales, scales + n_scales);
+    pl->set_note();
     return HP_OK;
 }
 

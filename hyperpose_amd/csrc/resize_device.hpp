@@ -27,7 +27,7 @@ struct rz_geom {
 struct bgr_taps {
     const uint8_t* src;
     int stride;
-    __device__ __forceinline__ void load(int x, int y, int (&c)[3]) const
+    __host__ __device__ __forceinline__ void load(int x, int y, int (&c)[3]) const
     {
         const uint8_t* s = src + (size_t)y * stride + x * 3;
         c[0] = s[0], c[1] = s[1], c[2] = s[2];
@@ -36,14 +36,19 @@ struct bgr_taps {
     __device__ __forceinline__ bgr_taps at(int rx, int ry) const { return bgr_taps{ src + (size_t)ry * stride + rx * 3, stride }; }
 };
 
-__device__ __forceinline__ short sat_short_rn(float v)
+// (host and device: the scale ensemble's host twin, hp_scale_stage_u8c3_host, runs resize_pixel on the CPU; the device code is unchanged)
+__host__ __device__ __forceinline__ short sat_short_rn(float v)
 {
+#if defined(__HIP_DEVICE_COMPILE__)
     const int r = __float2int_rn(v);
+#else
+    const int r = (int)std::nearbyint(v); // round half to even, as __float2int_rn, in the default rounding mode
+#endif
     return (short)min(max(r, -32768), 32767);
 }
 
 // one output pixel (x, y) of the destination frame; the caller has checked x < dw, y < dh
-template <class Taps> __device__ __forceinline__ void resize_pixel(const rz_geom& p, const Taps& t, int x, int y)
+template <class Taps> __host__ __device__ __forceinline__ void resize_pixel(const rz_geom& p, const Taps& t, int x, int y)
 {
     uint8_t* d = p.dst + (size_t)y * p.dst_stride + x * 3;
     if (x >= p.iw || y >= p.ih) {

@@ -278,6 +278,24 @@ class Engine:
     def flip_ensemble(self) -> bool:
         return bool(check(lib().hp_engine_flip_ensemble(self._h)))
 
+    def set_scale_ensemble(self, scales=(0.5,), bgcolor=None) -> None:
+        """``hp_engine_set_scale_ensemble``: from now on a u8 batch of n frames (K n <= max_batch, K = len(scales) + 1; twice that with the flip
+        ensemble) runs as the frames and their copies shrunk by each scale in (0, 1], and the first n frames of every output are the average of
+        the K passes resampled to the map grid (include/hp_hip.h, "scale ensemble").  ``bgcolor`` None: the COCO form
+        (``hp_engine_set_scale_ensemble_coco``, a (conf, paf) network, fill 0); otherwise the (b, g, r) fill, any network whose outputs share one
+        grid.  Empty ``scales`` (or None) restores the plain engine."""
+        s = np.ascontiguousarray(list(scales or []), np.float32)
+        sp = s.ctypes.data_as(C.POINTER(C.c_float)) if s.size else None
+        if bgcolor is None:
+            check(lib().hp_engine_set_scale_ensemble_coco(self._h, sp, int(s.size)))
+        else:
+            check(lib().hp_engine_set_scale_ensemble(self._h, sp, int(s.size), int(bgcolor[0]), int(bgcolor[1]), int(bgcolor[2])))
+
+    @property
+    def scale_ensemble(self) -> int:
+        """K: the passes every frame runs, 1 while the scale ensemble is off."""
+        return int(check(lib().hp_engine_scale_ensemble(self._h)))
+
     # ---- asynchronous device-resident path (bench, pipelines)
     def set_concurrency(self, parts: int):
         """2: a batch runs as two half-batches side by side on two internal streams (hp_engine_set_concurrency; fp32 engines) - for a

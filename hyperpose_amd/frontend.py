@@ -350,6 +350,57 @@ def flip_merge_host(maps: np.ndarray, n: int, perm, sign, shape=None) -> np.ndar
     return out
 
 
+# ---- scale ensemble: the shrunken slots, the bicubic tables and the map merge (include/hp_hip.h; the definition: csrc/scale_ensemble.hpp) ------
+
+def _scales(scales):
+    s = np.ascontiguousarray(scales, np.float32).ravel()
+    return s, len(s), s.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def scale_tables(W: int, mw: int):
+    """``hp_scale_tables``: (idx int32 [W, 4], wgt float32 [W, 4]), the bicubic taps from ``mw`` valid columns to ``W``."""
+    idx, wgt = np.zeros((max(1, int(W)), 4), np.int32), np.zeros((max(1, int(W)), 4), np.float32)
+    check(lib().hp_scale_tables(int(W), int(mw), idx.ctypes.data_as(C.c_void_p), wgt.ctypes.data_as(C.c_void_p)))
+    return idx[:W], wgt[:W]
+
+
+def scale_stage(src_dev, dst_dev, w: int, h: int, n: int, map_w: int, map_h: int, scales, bgcolor=(0, 0, 0), stream=None) -> None:
+    """``hp_scale_stage_u8c3``: ``n`` packed network-sized u8 HWC device slots -> the ``len(scales) * n`` shrunken slots of ``dst_dev``, scale-major;
+    only enqueues."""
+    s, k, sp = _scales(scales)
+    check(lib().hp_scale_stage_u8c3(as_ptr(src_dev), as_ptr(dst_dev), int(w), int(h), int(n), int(map_w), int(map_h), sp, k, int(bgcolor[0]),
+                                    int(bgcolor[1]), int(bgcolor[2]), C.c_void_p(stream) if stream else None))
+
+
+def scale_stage_host(slots: np.ndarray, map_w: int, map_h: int, scales, bgcolor=(0, 0, 0)) -> np.ndarray:
+    """``hp_scale_stage_u8c3_host``: [n, h, w, 3] uint8 network-sized slots -> [len(scales) * n, h, w, 3], no device needed."""
+    src = np.ascontiguousarray(slots, np.uint8)
+    assert src.ndim == 4 and src.shape[-1] == 3
+    n, h, w = src.shape[:3]
+    s, k, sp = _scales(scales)
+    out = np.zeros((max(1, k) * n, h, w, 3), np.uint8)
+    check(lib().hp_scale_stage_u8c3_host(C.c_void_p(src.ctypes.data), C.c_void_p(out.ctypes.data), w, h, n, int(map_w), int(map_h), sp, k,
+                                         int(bgcolor[0]), int(bgcolor[1]), int(bgcolor[2])))
+    return out
+
+
+def scale_merge(maps_dev, n: int, K: int, C_: int, H: int, W: int, scales, stream=None) -> None:
+    """``hp_scale_merge``: device maps [>= K * n, C, H, W] fp32, scale-major; maps [0, n) become the ensemble, in place; only enqueues (after the
+    first call of a geometry, which uploads its tables).  ``scales`` is passed as it is (K - 1 entries expected), so that the refusals can be tested."""
+    s, _, sp = _scales(scales)
+    check(lib().hp_scale_merge(as_ptr(maps_dev), int(n), int(K), int(C_), int(H), int(W), sp, C.c_void_p(stream) if stream else None))
+
+
+def scale_merge_host(maps: np.ndarray, n: int, scales, K=None, shape=None) -> np.ndarray:
+    """``hp_scale_merge_host`` on a copy of ``maps`` [>= K * n, C, H, W] float32: the whole array back, maps [0, n) merged.  ``K`` defaults to
+    ``len(scales) + 1``; ``shape`` = (C, H, W) overrides the array's (tests of the refusals)."""
+    out = np.array(maps, np.float32, order="C", copy=True)
+    Cc, H, W = shape if shape is not None else out.shape[1:]
+    s, k, sp = _scales(scales)
+    check(lib().hp_scale_merge_host(out.ctypes.data_as(C.POINTER(C.c_float)), int(n), int(k + 1 if K is None else K), int(Cc), int(H), int(W), sp))
+    return out
+
+
 # ---- regions and tiles: many regions of one frame per launch, the tile planner, the way back and the merge (include/hp_hip.h) -----------
 
 def _rois(rois):

@@ -101,6 +101,14 @@ class Pipeline:
         ``max_batch // (2 * regions)``).  Not while batches are in flight."""
         check(lib().hp_pipeline_set_flip_ensemble(self._h, int(bool(on))))
 
+    def set_scale_ensemble(self, scales=(0.5,)) -> None:
+        """``hp_pipeline_set_scale_ensemble``: from now on every network-sized slot also runs shrunk by each of ``scales`` (1 .. 3 values in
+        (0, 1]) and the parser reads the maps averaged over the K = len(scales) + 1 passes ("paf" pipelines only).  A submit then carries at most
+        ``max_batch // (K * (2 if flip else 1))`` frames (tiled: that over the regions).  Empty ``scales`` (or None) turns it off.  Not while
+        batches are in flight."""
+        s = np.ascontiguousarray(list(scales or []), np.float32)
+        check(lib().hp_pipeline_set_scale_ensemble(self._h, s.ctypes.data_as(C.POINTER(C.c_float)) if s.size else None, int(s.size)))
+
     def submit(self, frames) -> None:
         """frames: list of [h, w, 3] uint8 BGR arrays (any sizes), at most max_batch."""
         frames = [np.ascontiguousarray(f, np.uint8) for f in frames]

@@ -710,6 +710,62 @@ int hp_engine_set_flip_ensemble(hp_engine* e, const hp_flip_output* outs, int n_
 int hp_engine_set_flip_ensemble_coco(hp_engine* e, int enable);
 int hp_engine_flip_ensemble(const hp_engine* e); /* 0 / 1 */
 
+/* ---- scale ensemble: the network runs on every frame and on K - 1 shrunken copies of it; the maps of every copy are resampled back to the map
+ * grid and the K sets of maps are averaged on the device, before parsing (hyperpose_amd/csrc/scale_ensemble.hip; the definition is stated once in
+ * csrc/scale_ensemble.hpp and DESIGN.md 1.1 "Scale ensemble").  Scales above 1 are tiles' job ("regions and tiles" above).
+ *
+ * The caller gives K - 1 extra scales (1 <= K - 1 <= 3), each a float in (0, 1]; scale 0 is the frame as it is.  For a network with input
+ * in_w x in_h and maps of W x H cells (in_w % W == 0, in_h % H == 0), scale s keeps the map region mw = max(1, (int)floor((double)s * W + 0.5)),
+ * mh likewise, and shrinks the slot's content to iw = mw * (in_w / W), ih = mh * (in_h / H): the scale is rounded to whole map cells.
+ *
+ * hp_scale_stage_u8c3: n packed network-sized u8 HWC slots (w x h) -> the n_scales * n slots of the extra scales, scale-major: slot (k, i) at index
+ * (k - 1) * n + i of dst is slot i resized into its top-left iw_k x ih_k - byte for byte what hp_resize_u8c3 of the slot into a tight iw_k x ih_k
+ * image gives - and the rest filled with (b, g, r), each 0 .. 255.  src and dst must not overlap.  One launch; the device call only enqueues.
+ * HP_ERR_INVALID (the message names the sizes or the argument): w or h not a multiple of map_w / map_h, n_scales outside 1 .. 3, a scale outside
+ * (0, 1] or not finite, n * n_scales above 65535.
+ *
+ * hp_scale_tables (host only): for each of the W destination columns the four source columns idx[x][0..3] and weights wgt[x][0..3] of OpenCV's
+ * bicubic (A = -0.75) from a valid region of mw columns (1 <= mw <= W), fp32:
+ *     fx = (float)((x + 0.5) * ((double)mw / W) - 0.5); sx = (int)floorf(fx); fx -= sx
+ *     c0 = ((A*(fx+1) - 5*A)*(fx+1) + 8*A)*(fx+1) - 4*A;  c1 = ((A+2)*fx - (A+3))*fx*fx + 1
+ *     c2 = ((A+2)*(1-fx) - (A+3))*(1-fx)*(1-fx) + 1;      c3 = 1.f - c0 - c1 - c2
+ * columns sx-1 .. sx+2, each clamped to [0, mw-1].  At mw == W the weights are exactly (0, 1, 0, 0) on column x.  The same function serves rows.
+ * Parity with OpenCV itself is unpinned (no OpenCV to compare with; tests/scale_ref.py restates the coefficients), as for the front-end resize.
+ *
+ * hp_scale_merge: dev_maps holds K * n maps [C][H][W], contiguous, fp32, scale-major (the n frames, then the n frames at scales[0], ...); scales has
+ * K - 1 HOST entries.  For f < n, in place, with no fused operation:
+ *     acc = maps[f][c][y][x]
+ *     for k = 1 .. K-1:  row_r = ((wx0*p[r][0] + wx1*p[r][1]) + wx2*p[r][2]) + wx3*p[r][3]  (r = 0 .. 3; p = maps[k*n + f][c] at the tables' rows
+ *                        and columns: only the valid mh_k x mw_k region is read);  acc = acc + (((wy0*row_0 + wy1*row_1) + wy2*row_2) + wy3*row_3)
+ *     maps[f][c][y][x] = acc * (1.0f / (float)K)
+ * Maps n .. K*n-1 and everything behind them are not written.  The tables are too large for kernel arguments: the stand-alone call uploads them
+ * the first time it sees a (device, H, W, scales) and keeps that copy for the life of the process, never writing it again (so that first call
+ * synchronises the device and cannot be captured in a graph; later ones only enqueue).  HP_ERR_INVALID, with a message that names the argument,
+ * and nothing launched: K outside 2 .. 4, a scale outside (0, 1] or not finite, C outside 1 .. 256, H or W below 1, H * W over 2^31 - 1, n outside
+ * 1 .. 65535.  The *_host twins are the same statements in plain C++ (no device), same evaluation order and the same resize_pixel. */
+int hp_scale_stage_u8c3(const uint8_t* dev_src, uint8_t* dev_dst, int w, int h, int n, int map_w, int map_h, const float* scales, int n_scales, int b,
+                        int g, int r, void* stream);
+int hp_scale_stage_u8c3_host(const uint8_t* src, uint8_t* dst, int w, int h, int n, int map_w, int map_h, const float* scales, int n_scales, int b,
+                             int g, int r);
+int hp_scale_tables(int W, int mw, int32_t idx[][4], float wgt[][4]);
+int hp_scale_merge(float* dev_maps, int n, int K, int C, int H, int W, const float* scales /* K - 1, host */, void* stream);
+int hp_scale_merge_host(float* maps, int n, int K, int C, int H, int W, const float* scales);
+/* The engine's side.  While the ensemble is on, hp_engine_infer_u8(e, frames, n, ..) takes 1 <= n with K * n <= max_batch - 2 * K * n with the flip
+ * ensemble on as well - (HP_ERR_CAPACITY beyond, the message gives all the numbers; hp_engine_max_batch is unchanged): the engine copies the n
+ * frames into its staging buffer (the flip ensemble's), writes their shrunken copies behind them (hp_scale_stage_u8c3), with the flip ensemble the
+ * flips of all K n slots behind those (hp_hflip_u8c3), runs its unchanged schedule, hp_flip_merge over the K n slots if the flip ensemble is on, and
+ * the scale merge of the n frames on every output - on the call's stream, inside the captured graph when graphs are on (with two half-batch graphs:
+ * around the fork and the join).  Afterwards the first n frames of every output are the ensemble.  hp_engine_infer_f32 returns HP_ERR_STATE;
+ * hp_engine_calibrate_u8 and hp_engine_profile* run the plain schedule.  The setter checks, computes and uploads the tables, synchronises and drops
+ * the captured graphs; every output must have the same W x H with in_w % W == 0 and in_h % H == 0 and 1 .. 256 channels (HP_ERR_INVALID, the
+ * message names the sizes); (b, g, r) fills the shrunken slots (each 0 .. 255; the reference pads with 0).  n_scales == 0 turns the ensemble off,
+ * which restores the engine exactly.  The COCO form checks two outputs of 18 or 19 and of 38 channels of equal size, as its flip twin does, and
+ * fills with 0.  hp_engine_scale_ensemble returns K, 1 while off.  No perm and no sign: confidences and unit-vector fields do not change under
+ * scaling (PifPaf's and PoseProposal's outputs do: PAF networks only). */
+int hp_engine_set_scale_ensemble(hp_engine* e, const float* scales, int n_scales, int b, int g, int r); /* n_scales == 0: off */
+int hp_engine_set_scale_ensemble_coco(hp_engine* e, const float* scales, int n_scales);
+int hp_engine_scale_ensemble(const hp_engine* e); /* K, 1 while off */
+
 /* ---- hyperpose::stream on the GPU (reference include/hyperpose/stream/stream.hpp:119-390, src/stream.cpp:60-147): host frames of
  * any size in, humans out, in submission order.  Each submit copies one batch (<= max_batch frames, 8-bit BGR HWC, packed rows) to
  * the device and enqueues resize (keep_ratio = 0: cv::resize; 1: non_scaling_resize + resume_ratio on the way out) -> conv stack ->
@@ -778,6 +834,12 @@ int hp_pipeline_set_orientation(hp_pipeline* p, int orientation);
  * tone-map, orientation and tile cut - so the letterbox padding stays where the maps expect it; every submit call works unchanged, the parser runs on
  * the merged maps and hp_pipeline_collect is unchanged. */
 int hp_pipeline_set_flip_ensemble(hp_pipeline* p, int enable);
+/* Scale ensemble ("scale ensemble" above): n_scales extra scales turn hp_engine_set_scale_ensemble_coco on for every pipe's engine, n_scales == 0 turns
+ * it off (the default).  HP_ERR_STATE while batches are in flight; HP_ERR_INVALID for a pipeline whose parser is not HP_PARSER_PAF (the message names
+ * the kind).  While on, a submit carries at most max_batch / (K * (flip ? 2 : 1)) frames - tiled, R times fewer, and R * K * (flip ? 2 : 1) <= max_batch
+ * is required by whichever of this call, hp_pipeline_set_flip_ensemble and hp_pipeline_set_tiling comes last (HP_ERR_CAPACITY).  A refused call
+ * leaves every pipe as it was.  The scale is taken of the NETWORK-SIZED slot, as the flip is; every submit call works unchanged. */
+int hp_pipeline_set_scale_ensemble(hp_pipeline* p, const float* scales, int n_scales);
 
 #ifdef __cplusplus
 }

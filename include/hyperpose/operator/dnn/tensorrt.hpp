@@ -187,6 +187,17 @@ namespace dnn {
                 throw std::logic_error(hp_last_error());
         }
         bool flip_ensemble() const { return hp_engine_flip_ensemble(m_engine) == 1; }
+        /// Addition: scale ensemble (include/hp_hip.h, "scale ensemble"; hp_engine_set_scale_ensemble_coco).  While on, every inference() call on
+        /// frames or regions also runs each network-sized picture shrunk by every one of `scales` (1 .. 3 values in (0, 1]) and returns the maps
+        /// of the K = scales.size() + 1 passes resampled to the map grid and averaged, on the device.  The batch then holds max_batch_size() / K
+        /// frames or regions (/ 2K with the flip ensemble) and the float-buffer overload throws std::logic_error.  COCO PAF networks only (a
+        /// std::logic_error with the C ABI's message otherwise).  An empty list turns it off.
+        void set_scale_ensemble(const std::vector<float>& scales)
+        {
+            if (hp_engine_set_scale_ensemble_coco(m_engine, scales.data(), (int)scales.size()) != HP_OK)
+                throw std::logic_error(hp_last_error());
+        }
+        int scale_ensemble() const { return hp_engine_scale_ensemble(m_engine); } // K, 1 while off
         inline cv::Size input_size() noexcept { return m_inp_size; }
 
         /// src/tensorrt.cpp:436-461: every image is brought to the network's size (cv::resize, or non_scaling_resize when keep_ratio)
@@ -335,6 +346,8 @@ namespace dnn {
                 throw std::logic_error("Input float buffer is smaller than batch_size x 3 x H x W");
             if (flip_ensemble())
                 throw std::logic_error("hyperpose::dnn::tensorrt: float buffers are not available while the flip ensemble is on, pass frames");
+            if (scale_ensemble() > 1)
+                throw std::logic_error("hyperpose::dnn::tensorrt: float buffers are not available while the scale ensemble is on, pass frames");
             require_calibrated();
             retire_last_batch();
             if (hp_engine_infer_f32(m_engine, float_buffer.data(), (int)batch_size, 0, nullptr) != HP_OK)
@@ -360,10 +373,14 @@ namespace dnn {
         hp_engine* handle() { return m_engine; }
         bool keep_ratio() const { return m_keep_ratio; }
 
-        /// frames or regions one inference() call takes: max_batch_size(), half of it while the flip ensemble is on
-        size_t batch_room() const { return (size_t)m_max_batch_size / (flip_ensemble() ? 2 : 1); }
+        /// frames or regions one inference() call takes: max_batch_size(), half of it while the flip ensemble is on, 1 / K of that under the scale ensemble
+        size_t batch_room() const { return (size_t)m_max_batch_size / (flip_ensemble() ? 2 : 1) / scale_ensemble(); }
         std::string overflow_note() const
         {
+            const int passes = scale_ensemble() * (flip_ensemble() ? 2 : 1);
+            if (scale_ensemble() > 1) // (the flip ensemble's note below keeps its wording while the scale ensemble is off)
+                return " (max_batch_size " + std::to_string(m_max_batch_size) + " / " + std::to_string(passes) + ": the scale ensemble"
+                    + (flip_ensemble() ? " and the flip ensemble run" : " runs") + " every picture " + std::to_string(passes) + " times)";
             return flip_ensemble() ? " (max_batch_size " + std::to_string(m_max_batch_size) + " halved: the flip ensemble runs every picture with its flip)" : "";
         }
 

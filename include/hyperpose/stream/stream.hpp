@@ -85,7 +85,7 @@ public:
         const hp_tiling c = t ? t->c_form() : hp_tiling{};
         detail::hp_check(hp_pipeline_set_tiling(m_pl, t ? &c : nullptr));
         m_regions = t ? t->regions() : 1;
-        m_max_batch = m_engine_batch / (m_flip ? 2 : 1) / m_regions;
+        m_max_batch = m_engine_batch / (m_flip ? 2 : 1) / m_scales / m_regions;
     }
 
     // hp_pipeline_set_tonemap: 10-bit yuv_frames pushed from now on are PQ / HLG frames (utility/data.hpp, hdr); nullptr turns it off.  Not while
@@ -106,9 +106,20 @@ public:
     {
         detail::hp_check(hp_pipeline_set_flip_ensemble(m_pl, on ? 1 : 0));
         m_flip = on;
-        m_max_batch = m_engine_batch / (m_flip ? 2 : 1) / m_regions;
+        m_max_batch = m_engine_batch / (m_flip ? 2 : 1) / m_scales / m_regions;
     }
     bool flip_ensemble() const { return m_flip; }
+
+    // hp_pipeline_set_scale_ensemble: every network-sized slot also runs shrunk by each of `scales` (1 .. 3 values in (0, 1]) and the parser reads
+    // the maps averaged over the K passes (PAF parsers only); a push then carries 1 / K as many frames.  An empty list turns it off.  Not while
+    // batches are in flight (std::runtime_error)
+    void set_scale_ensemble(const std::vector<float>& scales)
+    {
+        detail::hp_check(hp_pipeline_set_scale_ensemble(m_pl, scales.data(), (int)scales.size()));
+        m_scales = (int)scales.size() + 1;
+        m_max_batch = m_engine_batch / (m_flip ? 2 : 1) / m_scales / m_regions;
+    }
+    int scale_ensemble() const { return m_scales; }
 
     // one batch (<= max_batch_size frames, any sizes); throws when every pipe is busy
     void push(const std::vector<cv::Mat>& frames)
@@ -165,6 +176,7 @@ private:
     std::atomic<int> m_max_batch;
     int m_engine_batch, m_pipes = 0, m_regions = 1;
     bool m_flip = false;
+    int m_scales = 1; // K of the scale ensemble
     std::atomic<size_t> m_truncated{ 0 };
     std::vector<hp_human> m_out;
     std::vector<int> m_n;
@@ -298,6 +310,10 @@ public:
     /// network with its left-right flip and the PAF parser reads the merged maps; a batch then holds half as many frames.  PAF parsers only
     /// (std::runtime_error otherwise).  Like the tiling, not while batches are in flight.
     void set_flip_ensemble(bool on) { m_gpu.set_flip_ensemble(on); }
+    /// Addition: scale ensemble (include/hp_hip.h, "scale ensemble"; hp_pipeline_set_scale_ensemble): every frame - every tile of it - also runs
+    /// shrunk by each of `scales` (1 .. 3 values in (0, 1]) and the PAF parser reads the maps averaged over the K passes; a batch then holds 1 / K
+    /// as many frames.  PAF parsers only (std::runtime_error otherwise); an empty list turns it off.  Like the tiling, not while batches are in flight.
+    void set_scale_ensemble(const std::vector<float>& scales) { m_gpu.set_scale_ensemble(scales); }
 
 private:
     struct item {
