@@ -60,7 +60,6 @@ UNITS = [
     ("conv_fp32.hip", ["-fno-slp-vectorize"]),
     ("conv32_direct.hip", []),
     ("conv32_winograd.hip", []),
-    ("conv32_winograd3.hip", []),
     ("conv32_head.hip", []),
     # -fno-slp-vectorize, as for conv_fp32.hip: the int8 kernels run in the same stream as the fp16-MFMA kernels and their
     # epilogue / quantization must not turn into packed fp32 FMAs

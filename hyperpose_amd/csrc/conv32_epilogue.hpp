@@ -34,6 +34,7 @@ struct no_stamp {
 // A lane's calls come with ascending r (conv32_kernel's callback carries the coordinates from one call to the next instead of dividing).
 // Only the NHWC output (p.out) is written here; the NCHW network output keeps the lane = pixel form (its runs lie along x).
 // stamp(): the caller's HP_DIRECT_DBG time stamp, called behind a group's offsets, requests and arithmetic (default: none).
+// Its users, both through conv32_store_rows below: conv32_kernel's row form (conv_fp32.hip) and conv32_direct_kernel (conv32_direct.hip).
 template <int TM, int NROWS, class F, class S = no_stamp>
 __device__ __forceinline__ void conv32_drain_rows(const conv32_params& p, const float* slab, int lane, int m_base, F&& pixel, S&& stamp = S{})
 {

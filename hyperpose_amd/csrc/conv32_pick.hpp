@@ -1,7 +1,7 @@
 // conv32_pick.hpp — which kernel, which template instance and which grid a dense fp32 layer gets, decided ONCE, as pure host code: no device
 // code, no HIP runtime call, no allocation, so the decision runs in a plain host program (tests/cpp/conv32_pick.cpp).  The engine asks
 // conv32_layer_forms at build time (which weight forms a layer gets), the launchers of conv_fp32.hip / conv32_direct.hip / conv32_winograd.hip /
-// conv32_winograd3.hip / conv32_head.hip carry out the conv32_choice that pick_conv32 / pick_head32 return, and the profile rows print its `tile`.
+// conv32_head.hip carry out the conv32_choice that pick_conv32 / pick_head32 return, and the profile rows print its `tile`.
 // (The first layer and the depthwise kernels keep their arithmetic in their launchers, conv_fp32.hip: it is used once.)
 #pragma once
 #include "conv_fp32.hpp"
@@ -13,10 +13,6 @@ constexpr int WCK = 16;                             // conv32_winograd_kernel: i
 constexpr int WINO_BW = 8;                          // ... its block: 8 NC rows x 8 columns of pixels, NC = 2 | 1
 constexpr int WINO_MW = 4;                          // ... four wavefronts (16-channel MFMA tiles) per block, the pipelined form
 constexpr int WINO_LDS[3] = { 0, 40960, 77824 };    // ... dynamic LDS by NC (wino_geom<4, NC>::PLDS_BYTES: conv32_winograd.hip asserts it)
-constexpr int W3_CK = 16;                           // conv32_winograd3_kernel: input channels per chunk
-constexpr int W3_TY = 8, W3_TX = 2;                 // tiles of a block
-constexpr int W3_BH = 3 * W3_TY, W3_BW = 3 * W3_TX; // 24 x 6 output pixels
-constexpr int W3_LDS_BYTES = 65024;                 // (W3_LDS: conv32_winograd3.hip asserts it)
 constexpr int DIRECT_T = 8;                         // conv32_direct_kernel: a block's 8 x 8 pixel tile
 constexpr int HK1 = 128;                            // conv32_head_kernel: input channels
 constexpr int HEAD_PX = 32;                         // ... pixels per block
@@ -53,8 +49,8 @@ struct direct32_geom {
 // ---- the compiled instances, as data: the launchers expand these into their dispatch, the host test asks them "does this choice exist?"
 // conv32_kernel<BM, BN, WM, WN, ROWS> (both epilogues of each), conv32_t16_kernel<BN, WN>, conv32_wk_kernel<KT, BN>
 #define HP_CONV32_INSTANCES(X) X(128, 128, 2, 2) X(64, 128, 1, 4) X(64, 64, 2, 2)
-#define HP_CONV32_T16_INSTANCES(X) X(176, 1) X(160, 2)
-#define HP_CONV32_WK_INSTANCES(X) X(32, 64) X(64, 64) X(128, 64)
+#define HP_CONV32_T16_INSTANCES(X) X(160, 2)
+#define HP_CONV32_WK_INSTANCES(X) X(32, 64) X(64, 64)
 // conv32_winograd_kernel<MW, PIPE, NC>
 #define HP_CONV32_WINO_INSTANCES(X) X(4, true, 2) X(4, true, 1)
 // conv32_direct_kernel<SPLIT, KS, CK, MW, DWD>.  Eight wavefront groups: the split 1 x 1 layers only, and not behind a depthwise layer of
@@ -70,8 +66,8 @@ struct direct32_geom {
 #define HP_CONV32_HEAD_INSTANCES(X) X(1) X(2)
 #define HP_CONV32_HEAD_PAIR_INSTANCES(X) X(1, 1) X(1, 2) X(2, 1) X(2, 2)
 
-enum conv32_form : int { C32_GEMM, C32_WINO2, C32_WINO3, C32_DIRECT }; // what a dense layer can be launched as (engine.cpp: launch_kind)
-enum conv32_kern : int { K32_CONV, K32_T16, K32_WK, K32_WINO2, K32_WINO3, K32_DIRECT, K32_HEAD, K32_HEAD_PAIR };
+enum conv32_form : int { C32_GEMM, C32_WINO2, C32_DIRECT }; // what a dense layer can be launched as (engine.cpp: launch_kind)
+enum conv32_kern : int { K32_CONV, K32_T16, K32_WK, K32_WINO2, K32_DIRECT, K32_HEAD, K32_HEAD_PAIR };
 
 struct conv32_choice {
     bool ok; // false: the form does not take this layer, or no compiled instance does - the launcher returns hipErrorInvalidValue
@@ -85,17 +81,17 @@ struct conv32_choice {
     int tiles_x, tiles_y, vh, rows; // the kernel arguments behind the parameter struct (Winograd and direct kernels)
     // the profile rows' code: 32000000 + 400000 (row-major epilogue) + BM * 1000 + BN conv32_kernel / conv32_t16_kernel; 39000000 + Cin * 1000 +
     // pixels per block conv32_wk_kernel; 33000000 (split) / 34000000 (fp32) + 100000 * fused depthwise dilation + KS * 1000 + wavefront groups per
-    // block conv32_direct_kernel; 35003004 / 35005004 the Winograd F(2 x 2) / F(3 x 3) kernels; 37000000 + 100 * HID + C2 the two-layer heads
+    // block conv32_direct_kernel; 35003004 the Winograd F(2 x 2) kernel; 37000000 + 100 * HID + C2 the two-layer heads
     int tile;
 };
 
 namespace pick32 {
 
-// 3 x 3, stride 1, dilation 1, SAME padding, input slice readable in whole ck-channel chunks (WCK | W3_CK), NHWC output only (a network head
+// 3 x 3, stride 1, dilation 1, SAME padding, input slice readable in whole WCK-channel chunks, NHWC output only (a network head
 // keeps the direct kernel's lane = pixel epilogue for its NCHW copy)
-inline bool winograd_ok(const conv32_params& p, int ck)
+inline bool winograd_ok(const conv32_params& p)
 {
-    return p.KH == 3 && p.KW == 3 && p.stride == 1 && p.dil == 1 && p.Cin % ck == 0 && p.Cout_pad % 64 == 0 && p.OH == p.H && p.OW == p.W && p.pad_t == 1
+    return p.KH == 3 && p.KW == 3 && p.stride == 1 && p.dil == 1 && p.Cin % WCK == 0 && p.Cout_pad % 64 == 0 && p.OH == p.H && p.OW == p.W && p.pad_t == 1
         && p.pad_l == 1 && !p.out_f32 && p.out.p;
 }
 
@@ -163,18 +159,16 @@ inline bool head_pair_ok(const conv32_params& a, const conv32_params& b, const e
 
 constexpr int wk_lds(int kt, int bn) { return kt / 16 * ((64 * 16 + 16) + (bn * 16 + 16)) * 4 + 4 * 16 * 36 * 4 + 3 * bn * 8; }
 
-// Which layers take conv32_wk_kernel: 1 x 1 (any stride), exactly 32 / 64 / 128 input channels, an NHWC output only, and enough pixel tiles that
+// Which layers take conv32_wk_kernel: 1 x 1 (any stride), exactly 32 / 64 input channels, an NHWC output only, and enough pixel tiles that
 // two blocks per CU stay busy (HP_C32_WK=0: none, the A/B switch; =1: every layer of that shape).  Looks at pick_npix like gemm_tile.
 inline int wk_bn(const conv32_params& p, const engine_switches& sw)
 {
     const int wk = sw.c32_wk;
-    if (wk == 0 || p.KH != 1 || p.KW != 1 || p.dil != 1 || p.out_f32 || !p.out.p || (p.Cin != 32 && p.Cin != 64 && p.Cin != 128))
+    if (wk == 0 || p.KH != 1 || p.KW != 1 || p.dil != 1 || p.out_f32 || !p.out.p || (p.Cin != 32 && p.Cin != 64))
         return 0;
-    // K = 128 (two blocks per CU) wins nothing: ResNet's 128 -> 512 at 32 x 48 x 48 140 -> 135 us, MobileNet's 128 -> 128 at 8 x 92 x 108 38.6 -> 41.6
-    // (profiles/r06_ab_layers_f32_whole_k.txt): forced only (the tests)
-    if (p.Cin == 128 && wk != 1)
-        return 0;
-    const int bn = 64; // (LDS: 27 / 44 / 77 KB per block at K = 32 / 64 / 128: five / three / two blocks per CU)
+    // (K = 128, 77 KB and two blocks per CU, won nothing: ResNet's 128 -> 512 at 32 x 48 x 48 140 -> 135 us, MobileNet's 128 -> 128 at 8 x 92 x 108
+    // 38.6 -> 41.6, profiles/r06_ab_layers_f32_whole_k.txt: not built)
+    const int bn = 64; // (LDS: 27 / 44 KB per block at K = 32 / 64: five / three blocks per CU)
     const long np = p.pick_npix > 0 ? p.pick_npix : p.npix, blocks = (np + bn - 1) / bn * (p.Cout_pad / 64);
     return wk == 1 || blocks >= 768 ? bn : 0;
 }
@@ -193,8 +187,8 @@ inline void gemm_tile(const conv32_params& p, const engine_switches& sw, int& BM
     // Round quantisation: 64 x 128 tiles have 1024 slots (four blocks per CU); a layer that is "one round and a bit" of them but ONE round of
     // 64 x 160 tiles takes conv32_t16_kernel<160> (see there).  HP_C32_BN160=0: the A/B switch back; =1: every layer (tests).
     const int bn160 = sw.c32_bn160;
-    if (bn160 == 1 || bn160 == 176) { // (tests: every layer on the 64 x 160 | 64 x 176 tile)
-        BM = 64, BN = bn160 == 1 ? 160 : 176;
+    if (bn160 == 1) { // (tests: every layer on the 64 x 160 tile)
+        BM = 64, BN = 160;
         return;
     }
     if (BM == 64 && BN == 128 && bn160 != 0) {
@@ -202,9 +196,7 @@ inline void gemm_tile(const conv32_params& p, const engine_switches& sw, int& BM
         const long g = p.Cout_pad / 64, b128 = (long)((np + 127) / 128) * g, b160 = (long)((np + 159) / 160) * g;
         if (b128 > 1024 && b160 <= 1024)
             BN = 160;
-        // (b160 a few blocks over the 1 024 slots - OpenPose-VGG19's 7 x 7 layers at 16 x 54 x 96: 1 296 tiles of 64 x 128, 1 038 of 64 x 160, 944 of
-        // 64 x 176 = conv32_t16_kernel<176, 1>, one round: 1 272 -> 1 172 us alone, but 1 039 -> 1 053 with a second stream, whose blocks fill the
-        // second round's empty slots anyway: not taken; HP_C32_BN160=176 forces it, tests/test_engine_fp32_gpu.py::test_one_round_tile_64x160)
+        // (a 64 x 176 tile for b160 a few blocks over the 1 024 slots: 1 272 -> 1 172 us alone, 1 039 -> 1 053 with a second stream - not built)
     }
     // ResNet's 1 x 1 expansions with few input channels (64 -> 256 at 96 x 96, 128 -> 512 at 48 x 48, batch 32): four to eight K-steps, then 300 MB
     // of output + residual - the layer is its epilogue.  conv32_t16_kernel's stores cover 16 pixels x 64 contiguous bytes per instruction where
@@ -216,7 +208,7 @@ inline void gemm_tile(const conv32_params& p, const engine_switches& sw, int& BM
 
 inline bool gemm_rows(const conv32_params& p, int BN)
 {
-    if (BN == 160 || BN == 176)
+    if (BN == 160)
         return false; // conv32_t16_kernel has the one epilogue (16 pixels x 64 contiguous bytes per store instruction)
     // The row-major epilogue pays on the 64-pixel tile only.  Measured per layer of LW-OpenPose @ 8 x 46 x 54 (us alone | with a second
     // stream; rows -> lane = pixel): <64, 64> 256 -> 256 33.2 | 26.9 -> 33.8 | 29.2, 128 -> 256 21.3 | 15.8 -> 21.7 | 19.0;  <64, 128> (two
@@ -257,7 +249,7 @@ inline void set_targ(conv32_choice& c, int a0, int a1 = 0, int a2 = 0, int a3 = 
 } // namespace pick32
 
 // The launch of dense layer p as `form` (split: the direct kernel's products on the fp16 pipe).  Every field of p that the launch depends on is
-// read here and nowhere else; the pointers w_frag / w_split / w_wino / w_wino3 are the launcher's argument check.
+// read here and nowhere else; the pointers w_frag / w_split / w_wino are the launcher's argument check.
 inline conv32_choice pick_conv32(const conv32_params& p, const engine_switches& sw, conv32_form form, bool split)
 {
     using namespace pick32;
@@ -280,8 +272,8 @@ inline conv32_choice pick_conv32(const conv32_params& p, const engine_switches& 
         WM = WM_, WN = WN_;
             HP_CONV32_INSTANCES(HP_X)
 #undef HP_X
-            if (BN == 160 || BN == 176)
-                c.kernel = K32_T16, set_targ(c, BN, BN == 160 ? 2 : 1);
+            if (BN == 160)
+                c.kernel = K32_T16, set_targ(c, BN, 2);
             else
                 c.kernel = K32_CONV, set_targ(c, BM, BN, WM, WN, rows);
             c.grid_x = ((p.npix + BN - 1) / BN + 7) / 8 * 8 * (p.Cout_pad / BM); // XCD-aware 1-D order: see conv32_kernel
@@ -289,7 +281,7 @@ inline conv32_choice pick_conv32(const conv32_params& p, const engine_switches& 
         }
         break;
     case C32_WINO2: {
-        c.ok = winograd_ok(p, WCK);
+        c.ok = winograd_ok(p);
         c.tiles_x = (p.OW + WINO_BW - 1) / WINO_BW;
         const int nc = winograd_nc(p, sw, c.tiles_x * ((p.OH + 15) / 16) * p.B * (p.Cout_pad / 64)), bh = 8 * nc;
         int tiles_y = (p.OH + bh - 1) / bh, vh = winograd_tall(p, sw), images = p.B, rows = 0;
@@ -312,14 +304,6 @@ inline conv32_choice pick_conv32(const conv32_params& p, const engine_switches& 
         c.tile = 35000000 + 3000 + 4; // four wavefronts (16-channel MFMA tiles) per block, the pipelined form: see "Kernel shape"
         break;
     }
-    case C32_WINO3:
-        c.ok = winograd_ok(p, W3_CK);
-        c.kernel = K32_WINO3;
-        c.tiles_x = (p.OW + W3_BW - 1) / W3_BW, c.tiles_y = (p.OH + W3_BH - 1) / W3_BH;
-        c.grid_x = (c.tiles_x * c.tiles_y * p.B + 7) / 8 * 8 * (p.Cout_pad / 64); // XCD-aware 1-D order: see the kernel
-        c.lds = W3_LDS_BYTES;
-        c.tile = 35005004;
-        break;
     case C32_DIRECT: {
         const int dwd = p.dw_w ? p.dw_dil : 0, mw = direct_mw(p, split, dwd);
         const long lds = direct_lds(split, p.KH, mw, dwd);
@@ -355,7 +339,7 @@ inline conv32_choice pick_head32(const conv32_params& q, int hid, const conv32_p
 // launched as and, for the direct kernel, the channel count the launch reads (whole chunks).  dw_in_front: a depthwise layer is fused in front;
 // room: the channels the input buffer has from the slice's first one; layer_cin: the layer's own input channels.
 struct conv32_forms {
-    bool w_wino, w_wino3, w_frag, w_split;
+    bool w_wino, w_frag, w_split;
     conv32_form kind;
     int cin_split;
 };
@@ -364,13 +348,10 @@ inline conv32_forms conv32_layer_forms(const conv32_params& p, int dtype, const 
     using namespace pick32;
     conv32_forms f{};
     f.kind = C32_GEMM;
-    // HP_DTYPE_F32: 3 x 3 stride-1 layers in Winograd's F(2 x 2, 3 x 3) form (HP_NO_WINOGRAD32=1 is the A/B switch back to the direct kernel) or,
-    // opt-in (HP_WINO_F33=1), F(3 x 3, 3 x 3).  (Never a layer with a depthwise or hidden layer fused in front: those are 1 x 1.)
-    if (dtype == HP_DTYPE_F32 && !sw.no_winograd32 && winograd_ok(p, WCK)) {
+    // HP_DTYPE_F32: 3 x 3 stride-1 layers in Winograd's F(2 x 2, 3 x 3) form (HP_NO_WINOGRAD32=1 is the A/B switch back to the direct kernel).
+    // (Never a layer with a depthwise or hidden layer fused in front: those are 1 x 1.)
+    if (dtype == HP_DTYPE_F32 && !sw.no_winograd32 && winograd_ok(p))
         f.w_wino = true, f.kind = C32_WINO2;
-        if (sw.wino_f33 && winograd_ok(p, W3_CK))
-            f.w_wino3 = true, f.kind = C32_WINO3;
-    }
     // a 3 x 3 layer the Winograd kernel has taken needs no direct-form fragments (they doubled its weight bytes in HBM); 1 x 1 layers wider than
     // 64 padded outputs stay on conv32_kernel - unless HP_DTYPE_F32S (every direct layer) or a depthwise layer is fused in front
     const int taps = p.KH * p.KW;

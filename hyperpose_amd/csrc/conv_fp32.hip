@@ -296,21 +296,20 @@ __global__ __launch_bounds__(256) void conv32_kernel(const conv32_params p)
 // = 32 KB per block.  K order as in conv32_kernel: lane (row, kq) reads channels [4 kq, 4 kq + 4) with one ds_read_b128 and feeds element e to
 // MFMA e - A and B use the same permutation.  Epilogue: lane (pixel n, q) of a 16 x 16 tile holds channels 4 q .. 4 q + 3 of pixel n: one
 // global_store_dwordx4 of a wavefront covers 16 pixels x 64 contiguous bytes.
-// WN = wavefronts side by side over the pixels (2: 2 x 2 wavefronts of 32 channels x BN / 2 pixels; 1: four wavefronts of 16 channels x all BN pixels -
-// any multiple of 16 pixels per block, e.g. 176: OpenPose-VGG19's 7 x 7 layers at 16 x 54 x 96 are 1 296 tiles of 64 x 128, 1 038 of 64 x 160 - 14 more
-// than the chip's 1 024 slots - and 944 of 64 x 176: one round).
+// WN = wavefronts side by side over the pixels: 2 x 2 wavefronts of 32 channels x BN / 2 pixels.
 template <int BN, int WN = 2>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv32_t16_kernel(const conv32_params p)
 {
     constexpr int BM = 64, BK = 16, WM = 4 / WN, TMW = BM / 16 / WM, TNW = BN / WN / 16; // a wavefront: TMW x TNW tiles of 16 x 16
     constexpr int NB = (BN + 63) / 64, BR = NB * 64;             // staging passes of the B tile (64 rows each); rows allocated
-    static_assert(BN % (16 * WN) == 0 && (WN == 1 || WN == 2), "wavefront columns of whole 16-pixel tiles");
+    static_assert(WN == 2, "the one built form; the parameter stays because traces and profiles name conv32_t16_kernel<160,2>");
+    static_assert(BN % (16 * WN) == 0, "wavefront columns of whole 16-pixel tiles");
     __shared__ __attribute__((aligned(16))) float lds[2 * (BM + BR) * BK];
     float (*const sA)[BM * BK] = reinterpret_cast<float (*)[BM * BK]>(lds);
     float (*const sB)[BR * BK] = reinterpret_cast<float (*)[BR * BK]>(lds + 2 * BM * BK);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = WN == 2 ? wave >> 1 : wave, wn = WN == 2 ? wave & 1 : 0;
+    const int wm = wave >> 1, wn = wave & 1;
     const int G = p.Cout_pad / BM, nx = (p.npix + BN - 1) / BN; // XCD-aware 1-D block order: see conv32_kernel
     const int bj = blockIdx.x >> 3, ptile = (bj / G) * 8 + (blockIdx.x & 7);
     if (ptile >= nx)
@@ -427,72 +426,68 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int i = 0; i < TMW; ++i)
         mch[i] = m0 + wm * (16 * TMW) + i * 16 + 4 * q, many[i] = mch[i] < p.Cout; // (mch + 3 < Cout_pad)
     f32x4 bs[TMW], sl[TMW];
-    // Tiles [J0, J1) of the wavefront: the residual quads of all of them requested at once, then the arithmetic of all (per element as before:
-    // bias, residual before or after the activation, clamp or slope), then the stores back to back.  <160, 2>: all 2 x 5 tiles in one go;
-    // <176, 1> (1 x 11 tiles; forced selections only): two groups, for the registers that four blocks per CU leave.
-    constexpr int GJ = TMW * TNW <= 10 ? TNW : (TNW + 1) / 2;
-    auto drain = [&](auto J0c, auto J1c) {
-        constexpr int J0 = decltype(J0c)::value, J1 = decltype(J1c)::value;
+    // The residual quads of all 2 x 5 tiles of the wavefront requested at once, then the arithmetic of all (per element as before: bias, residual
+    // before or after the activation, clamp or slope), then the stores back to back.  (A lambda called once: written straight into the body,
+    // the same statements compile to other code - 71 scalar registers instead of 58)
+    auto drain = [&] {
         HP_STAMP();
-        f32x4 rr[TMW][GJ];
+        f32x4 rr[TMW][TNW];
 #pragma unroll
         for (int i = 0; i < TMW; ++i)
 #pragma unroll
-            for (int j = J0; j < J1; ++j)
-                rr[i][j - J0] = f32x4{ 0.f, 0.f, 0.f, 0.f };
+            for (int j = 0; j < TNW; ++j)
+                rr[i][j] = f32x4{ 0.f, 0.f, 0.f, 0.f };
         if (gres) {
             if (res_vec) {
 #pragma unroll
-                for (int j = J0; j < J1; ++j)
+                for (int j = 0; j < TNW; ++j)
 #pragma unroll
                     for (int i = 0; i < TMW; ++i)
-                        rr[i][j - J0] = *reinterpret_cast<const gf32x4*>(gres + ((long)rpix[j] * p.res.cs + p.res.coff + (many[i] ? mch[i] : 0)));
+                        rr[i][j] = *reinterpret_cast<const gf32x4*>(gres + ((long)rpix[j] * p.res.cs + p.res.coff + (many[i] ? mch[i] : 0)));
             } else {
 #pragma unroll
-                for (int j = J0; j < J1; ++j)
+                for (int j = 0; j < TNW; ++j)
 #pragma unroll
                     for (int i = 0; i < TMW; ++i)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) // (channels past Cout: a re-read of the last one, never stored)
-                            rr[i][j - J0][e] = gres[(long)rpix[j] * p.res.cs + p.res.coff + min(mch[i] + e, p.Cout - 1)];
+                            rr[i][j][e] = gres[(long)rpix[j] * p.res.cs + p.res.coff + min(mch[i] + e, p.Cout - 1)];
             }
         }
-        if constexpr (J0 == 0) {
 #pragma unroll
-            for (int i = 0; i < TMW; ++i) {
-                bs[i] = *(const gf32x4*)(p.bias + mch[i]);
-                sl[i] = f32x4{ p.act_slope, p.act_slope, p.act_slope, p.act_slope };
-                if (p.alpha)
-                    sl[i] = *(const gf32x4*)(p.alpha + mch[i]);
-            }
+        for (int i = 0; i < TMW; ++i) {
+            bs[i] = *(const gf32x4*)(p.bias + mch[i]);
+            sl[i] = f32x4{ p.act_slope, p.act_slope, p.act_slope, p.act_slope };
+            if (p.alpha)
+                sl[i] = *(const gf32x4*)(p.alpha + mch[i]);
         }
         HP_STAMP();
 #pragma unroll
         for (int i = 0; i < TMW; ++i)
 #pragma unroll
-            for (int j = J0; j < J1; ++j)
+            for (int j = 0; j < TNW; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float x = acc[i][j][e] + bs[i][e];
                     if (res_pre)
-                        x += rr[i][j - J0][e];
+                        x += rr[i][j][e];
                     x = x > 0.f ? fminf(x, p.act_hi) : x * sl[i][e];
                     if (res_post)
-                        x += rr[i][j - J0][e];
+                        x += rr[i][j][e];
                     acc[i][j][e] = x;
                 }
         HP_STAMP();
         if (gout) {
             if (out_vec) {
 #pragma unroll
-                for (int j = J0; j < J1; ++j)
+                for (int j = 0; j < TNW; ++j)
 #pragma unroll
                     for (int i = 0; i < TMW; ++i)
                         if (pok[j] && many[i])
                             *reinterpret_cast<gf32x4*>(gout + ((long)opix[j] * p.out.cs + p.out.coff + mch[i])) = acc[i][j];
             } else {
 #pragma unroll
-                for (int j = J0; j < J1; ++j)
+                for (int j = 0; j < TNW; ++j)
 #pragma unroll
                     for (int i = 0; i < TMW; ++i)
 #pragma unroll
@@ -502,9 +497,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             }
         }
     };
-    drain(std::integral_constant<int, 0>{}, std::integral_constant<int, GJ>{});
-    if constexpr (GJ < TNW)
-        drain(std::integral_constant<int, GJ>{}, std::integral_constant<int, TNW>{});
+    drain();
     if (p.out_f32) { // the network's fp32 NCHW output (a head on this tile: forced selections only): the pixel's image and index once more
 #pragma unroll
         for (int j = 0; j < TNW; ++j) {
@@ -702,21 +695,6 @@ __global__ __launch_bounds__(256) void conv32_wk_kernel(const conv32_params p)
     }
 }
 
-template <int KT, int BN>
-static hipError_t launch_wk(const conv32_params& p, const conv32_choice& c, hipStream_t s)
-{
-    constexpr int lds = pick32::wk_lds(KT, BN);
-    static bool granted = false;
-    if (lds > 64 * 1024 && !granted) {
-        const hipError_t e = hipFuncSetAttribute((const void*)conv32_wk_kernel<KT, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess)
-            return e;
-        granted = true;
-    }
-    HP_LAUNCH((conv32_wk_kernel<KT, BN>), dim3(c.grid_x), dim3(c.threads), lds, s, p);
-    return hipGetLastError();
-}
-
 bool set_act32(conv32_params& p)
 {
     const float inf = __builtin_huge_valf();
@@ -749,9 +727,12 @@ hipError_t launch_conv32(const conv32_params& p, const engine_switches& sw, hipS
     const conv32_choice c = pick_conv32(p, sw, C32_GEMM, false);
     const int* const t = c.targ;
     const dim3 grid(c.grid_x), block(c.threads);
-#define HP_WK_CASE(KT_, BN_) \
-    if (c.kernel == K32_WK && t[0] == KT_ && t[1] == BN_) \
-        return launch_wk<KT_, BN_>(p, c, s);
+#define HP_WK_CASE(KT_, BN_)                                                                              \
+    if (c.kernel == K32_WK && t[0] == KT_ && t[1] == BN_) {                                               \
+        static_assert(pick32::wk_lds(KT_, BN_) <= 64 * 1024, "dynamic LDS a launch gets without asking"); \
+        HP_LAUNCH((conv32_wk_kernel<KT_, BN_>), grid, block, c.lds, s, p);                                \
+        return hipGetLastError();                                                                         \
+    }
     HP_CONV32_WK_INSTANCES(HP_WK_CASE)
 #undef HP_WK_CASE
     // (conv32_t16_kernel<160>: three blocks per CU instead of four - 12 KB of unused dynamic LDS, to leave registers and LDS to the other pipes' depthwise

@@ -98,7 +98,6 @@ enum class launch_kind : char {
     first32,
     conv32,
     wino2,  // a 3 x 3 stride-1 layer on conv32_winograd_kernel (cp.w_wino)
-    wino3,  // ... on the opt-in F(3 x 3, 3 x 3) kernel (cp.w_wino3)
     direct, // conv32_direct_kernel, which reads `cin_split` input channels (whole chunks)
     head32, // 1 x 1 128 -> HID -> 1 x 1 HID -> C2 in one launch (conv32_head.hip): cp = the second layer's epilogue, hh = the first layer
     dw32,
@@ -120,7 +119,7 @@ struct sep_pair_launch {
 struct head_pair_launch {
     hp::head_params a, b;
 };
-struct conv32_launch { // conv32, wino2, wino3, direct
+struct conv32_launch { // conv32, wino2, direct
     hp::conv32_params cp;
     int cin_split; // direct: what the launch sets cp.Cin to
 };
@@ -979,7 +978,7 @@ int hp_engine::lower32_conv(size_t i, step& st)
     p.out_f32 = fused_output(i, true, p.out);
     HP_REQUIRE(hp::set_act32(p), HP_ERR_INVALID, "layer %zu: activation %d cannot be fused into a dense conv (use an output post-op)", i, L.act);
     p.B = max_batch, p.npix = p.pick_npix = max_batch * g.OH * g.OW;
-    p.w_split = nullptr, p.w_frag = nullptr, p.w_wino = nullptr, p.w_wino3 = nullptr, p.ovf = ovf_dev, p.dbg = nullptr;
+    p.w_split = nullptr, p.w_frag = nullptr, p.w_wino = nullptr, p.ovf = ovf_dev, p.dbg = nullptr;
     p.lane_epilogue = switches.lane_epilogue;
     // the weight forms of the kernels beside conv32_kernel: conv32_layer_forms looks at the filled p and decides, the two lowerings pack and upload
     const hp::conv32_forms f = hp::conv32_layer_forms(p, dtype, switches, dw_in_front, tsrc.cs - S.in_coff, L.cin);
@@ -987,7 +986,7 @@ int hp_engine::lower32_conv(size_t i, step& st)
     HP_TRY(lower32_winograd_forms(i, st, packed, f));
     HP_TRY(lower32_direct_forms(i, st, packed, f));
     // (the launch kind is the picker's: the lowerings above only packed what it asked for)
-    st.kind = f.kind == hp::C32_WINO2 ? launch_kind::wino2 : f.kind == hp::C32_WINO3 ? launch_kind::wino3 : f.kind == hp::C32_DIRECT ? launch_kind::direct : launch_kind::conv32;
+    st.kind = f.kind == hp::C32_WINO2 ? launch_kind::wino2 : f.kind == hp::C32_DIRECT ? launch_kind::direct : launch_kind::conv32;
     if (head_in_front) // (last: it replaces the payload `p` refers to)
         HP_TRY(lower32_head_in_front(i, st, w));
     return HP_OK;
@@ -1022,23 +1021,10 @@ int hp_engine::lower32_winograd_forms(size_t i, step& st, const std::vector<floa
     auto& p = st.cp32();
     if (!f.w_wino)
         return HP_OK;
-    const double wbytes = (double)layers[i].cout * 9 * layers[i].cin * 4; // the layer's own weights
     std::vector<float> wu((size_t)16 * p.Cout_pad * p.Cin);
     hp::conv32_winograd_pack(packed.data(), p.Cout_pad, p.Cin, wu.data());
     HP_TRY(upload(wu, p.w_wino));
-    st.bytes += wbytes * (16.0 / 9 - 1);
-    // ... or, opt-in (HP_WINO_F33=1), F(3 x 3, 3 x 3): 25 products per 3 x 3 tile - 1.44 x fewer MFMA cycles, same accuracy
-    // (conv32_winograd3.hip).  Measured: it wins where its 24 x 6-pixel blocks tile the map exactly and the layer is mid-sized (256 -> 256
-    // at 32 x 24 x 24: 121 -> 87 us) and loses everywhere else - LW-OpenPose's 128 -> 128 at 8 x 46 x 54 48.6 | 28.6 us alone | paired against
-    // 45.0 (35.9 in 8 x 8 blocks) | 27.0, every layer of PifPaf's 97 / 49 / 25-row maps - because one 16-tile column per wavefront streams
-    // 3.1 x the U bytes per output pixel.  Not the default: taken by itself only on PoseProposal's exactly tiled 48 x 48 / 24 x 24
-    // stages it made configs[3] 0.6 % faster (4 353 -> 4 380 frames/s resident, two runs each) - not worth a second numeric path.
-    if (f.w_wino3) {
-        std::vector<float> wu3((size_t)25 * p.Cout_pad * p.Cin);
-        hp::conv32_winograd3_pack(packed.data(), p.Cout_pad, p.Cin, wu3.data());
-        HP_TRY(upload(wu3, p.w_wino3));
-        st.bytes += wbytes * (25.0 / 9 - 16.0 / 9);
-    }
+    st.bytes += (double)layers[i].cout * 9 * layers[i].cin * 4 * (16.0 / 9 - 1); // (the layer's own weights are counted already)
     return HP_OK;
 }
 
@@ -1757,7 +1743,6 @@ launch_payload hp_engine::bound(const step& st, const uint8_t* u8, const float* 
     case launch_kind::first32: return bind(st.as<hp::first_conv32_params>(), u8, f32, frame, n, b0);
     case launch_kind::conv32:
     case launch_kind::wino2:
-    case launch_kind::wino3:
     case launch_kind::direct: {
         conv32_launch c = st.as<conv32_launch>();
         c.cp = bind(c.cp, n, b0);
@@ -1807,13 +1792,11 @@ int hp_engine::launch(launch_kind kind, launch_payload& b, hipStream_t s, unsign
     case launch_kind::first32: HP_HIP_TRY(hp::launch_first_conv32(std::get<hp::first_conv32_params>(b), switches, s)); break;
     case launch_kind::conv32:
     case launch_kind::wino2:
-    case launch_kind::wino3:
     case launch_kind::direct: {
         hp::conv32_params& cp = std::get<conv32_launch>(b).cp;
         cp.dbg = dbg;
         HP_HIP_TRY(kind == launch_kind::conv32 ? hp::launch_conv32(cp, switches, s)
                 : kind == launch_kind::wino2   ? hp::launch_conv32_winograd(cp, switches, s)
-                : kind == launch_kind::wino3   ? hp::launch_conv32_winograd3(cp, s)
                                                : hp::launch_conv32_direct(cp, on_split_pipe(), s));
         break;
     }
@@ -1841,7 +1824,6 @@ int hp_engine::tile_of(launch_kind kind, const launch_payload& b) const
     case launch_kind::bneck: return 9000000 + hp::bottleneck_variant(std::get<hp::bneck_params>(b));
     case launch_kind::conv32: return hp::pick_conv32(std::get<conv32_launch>(b).cp, switches, hp::C32_GEMM, false).tile;
     case launch_kind::wino2: return hp::pick_conv32(std::get<conv32_launch>(b).cp, switches, hp::C32_WINO2, false).tile;
-    case launch_kind::wino3: return hp::pick_conv32(std::get<conv32_launch>(b).cp, switches, hp::C32_WINO3, false).tile;
     case launch_kind::direct: return hp::pick_conv32(std::get<conv32_launch>(b).cp, switches, hp::C32_DIRECT, on_split_pipe()).tile;
     case launch_kind::head32: return hp::pick32::head_tile(std::get<head32_launch>(b).hh.HID, std::get<head32_launch>(b).cp.Cout);
     default: return 0; // first convolutions, depthwise, pooling, up-sampling: one form each
@@ -1875,14 +1857,12 @@ bool hp_engine::timeline_of(const step& st, const launch_payload& b, hp::timelin
         return switches.dbg_sep;
     case launch_kind::conv32:
     case launch_kind::wino2:
-    case launch_kind::wino3:
     case launch_kind::direct: {
         const hp::conv32_params& q = std::get<conv32_launch>(b).cp;
         if (!switches.dbg_direct || (st.kind == launch_kind::conv32 && q.Cin < switches.dbg_min_cin))
             return false;
         kind = st.kind == launch_kind::conv32 ? hp::timeline_kind::conv32
             : st.kind == launch_kind::wino2   ? hp::timeline_kind::wino
-            : st.kind == launch_kind::wino3   ? hp::timeline_kind::wino3
                                               : hp::timeline_kind::direct;
         hd.cin = q.Cin, hd.cout = q.Cout, hd.kh = q.KH, hd.kw = q.KW, hd.tile = tile_of(st.kind, b);
         if (st.kind == launch_kind::wino2)
@@ -2047,7 +2027,7 @@ hp::engine_switches hp::read_engine_switches()
     w.no_fuse = on("HP_NO_FUSE"), w.no_fuse_head = num("HP_NO_FUSE_HEAD", 0) != 0, w.no_splitk = on("HP_NO_SPLITK");
     w.no_chain = on("HP_NO_CHAIN"), w.no_bneck = on("HP_NO_BNECK"), w.no_seppair = on("HP_NO_SEPPAIR"), w.no_pair_heads = on("HP_NO_PAIR_HEADS");
     w.fuse32 = on("HP_FUSE32"), w.no_fuse32 = on("HP_NO_FUSE32"), w.no_head32 = on("HP_NO_HEAD32"), w.no_arena = on("HP_NO_ARENA");
-    w.no_winograd32 = on("HP_NO_WINOGRAD32"), w.wino_f33 = num("HP_WINO_F33", 0) == 1, w.wino_tall = num("HP_WINO_TALL", 1) != 0;
+    w.no_winograd32 = on("HP_NO_WINOGRAD32"), w.wino_tall = num("HP_WINO_TALL", 1) != 0;
     w.wino_nc = num("HP_WINO_NC", 0), w.head_pair32 = num("HP_HEAD_PAIR", 1) != 0;
     w.c32_wk = num("HP_C32_WK", -1), w.c32_bn160 = num("HP_C32_BN160", -1), w.dw32_px = num("HP_DW32_PX", 0);
     w.lane_epilogue = num("HP_LANE_EPILOGUE", 0), w.first_conv_verify = on("HP_FIRST_CONV_VERIFY");

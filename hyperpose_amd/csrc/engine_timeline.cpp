@@ -105,7 +105,7 @@ size_t hp::timeline_words(timeline_kind k)
     case timeline_kind::sep: return 64 + 2 * 1024 + 64; // [0, 64) block 0's stamps, then (start, end) of the first 1024 blocks, then wavefront 4 of block 1
     case timeline_kind::wino: return 128;
     case timeline_kind::conv32: return 128 + 3 * 4096;
-    default: return 64; // conv, wino3, direct
+    default: return 64; // conv, direct
     }
 }
 
@@ -155,11 +155,6 @@ void hp::print_timeline(FILE* f, timeline_kind k, const timeline_header& hd, con
             fprintf(f, "  %d blocks: first start -> last end %.2f us, starts spread over %.2f us, block duration %.2f .. %.2f us\n", b.nb,
                 (b.t1 - b.t0) * 0.01, (b.smax - b.t0) * 0.01, b.dmin * 0.01, b.dmax * 0.01);
         }
-        break;
-    case timeline_kind::wino3:
-        fprintf(f, "winograd3 layer %d %d->%d cycles [start | chunk 0 transformed | per chunk: patch stored, multiplied | output transformed | stored]:", hd.layer, hd.cin, hd.cout);
-        deltas(1, 60);
-        fprintf(f, "\n");
         break;
     case timeline_kind::wino:
         fprintf(f, "winograd layer %d %d->%d tile %d cycles [chunk 0 staged | transformed, chunk 1 stored | per chunk: multiplied, next patch stored | epilogue requests | output transform | slab complete | stored]:", hd.layer, hd.cin, hd.cout,

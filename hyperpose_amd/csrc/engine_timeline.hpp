@@ -15,7 +15,6 @@ enum class timeline_kind {
     bneck,  // conv_bottleneck.hip: block 0's phases, then (start, end) of the first 1024 blocks
     chain,  // conv_chain.hip: block 0's phases
     sep,    // sepconv_kernel: block 0, (start, end) of the first 1024 blocks, wavefront 4 of block 1
-    wino3,  // conv32_winograd3.hip: block 9, thread 0
     wino,   // conv32_winograd.hip: block (1, 0), thread 0
     direct, // conv32_direct.hip: block (1, 0), thread 0
     conv32, // conv32_kernel: block 9, thread 0, then every block's residency

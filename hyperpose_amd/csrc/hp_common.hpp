@@ -119,12 +119,11 @@ struct engine_switches {
     bool no_head32 = false;      // HP_NO_HEAD32: fp32 1 x 1 head pairs as two launches
     bool no_arena = false;       // HP_NO_ARENA: every fp32 activation tensor in its own allocation
     bool no_winograd32 = false;  // HP_NO_WINOGRAD32: no fp32 Winograd layers
-    bool wino_f33 = false;       // HP_WINO_F33=1: F(3 x 3, 3 x 3) where it applies (opt-in)
     bool wino_tall = true;       // HP_WINO_TALL=0: the per-image Winograd form instead of the tall one
     int wino_nc = 0;             // HP_WINO_NC=1 | 2: force the Winograd column tiles per block (0: by the engine's mode)
     bool head_pair32 = true;     // HP_HEAD_PAIR=0: fp32 sibling heads as two launches instead of one grid
     int c32_wk = -1;             // HP_C32_WK: 0 = no conv32_wk_kernel, 1 = every layer of its shape, -1 = by size
-    int c32_bn160 = -1;          // HP_C32_BN160: 0 = no 64 x 160 tiles, 1 | 176 = every layer on 64 x 160 | 64 x 176, -1 = by size
+    int c32_bn160 = -1;          // HP_C32_BN160: 0 = no 64 x 160 tiles, 1 = every layer on them, -1 = by size
     int dw32_px = 0;             // HP_DW32_PX: 1 = one depthwise column per thread, 2 = column pairs always, 0 = by size
     int lane_epilogue = 0;       // HP_LANE_EPILOGUE: conv32_params::lane_epilogue
     bool first_conv_verify = false; // HP_FIRST_CONV_VERIFY: first_conv32_kernel compares its LDS with global memory (first_conv32_verify_counts)

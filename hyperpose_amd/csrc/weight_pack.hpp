@@ -2,7 +2,7 @@
 // No HIP runtime call and nothing of hp_engine, so every layout runs in a plain host program (tests/cpp/weight_pack.cpp).  Sources are
 // pointers into the weight blob as the exported graph stores them: dense [cout][taps][cin], depthwise [C][9].  The layouts that belong to
 // one fp32 kernel family stay next to it and are only called from the engine: conv32_frag_pack, conv32_split_pack, conv32_winograd_pack,
-// conv32_winograd3_pack, conv32_head_pack (conv_fp32.hpp).
+// conv32_head_pack (conv_fp32.hpp).
 #pragma once
 #include "conv_i8.hpp" // conv_i8_direct_index; __half / __float2half through conv_kernels.hpp
 

@@ -43,7 +43,6 @@ static bool instance_exists(const conv32_choice& c)
 #define HP_X(MW, PIPE, NC) found |= t[0] == MW && t[1] == PIPE && t[2] == NC;
     case K32_WINO2: HP_CONV32_WINO_INSTANCES(HP_X) break;
 #undef HP_X
-    case K32_WINO3: found = true; break;
 #define HP_X(SPLIT, KS, CK, MW, DWD) found |= t[0] == SPLIT && t[1] == KS && t[2] == CK && t[3] == MW && t[4] == DWD;
     case K32_DIRECT: HP_CONV32_DIRECT_INSTANCES(HP_X) break;
 #undef HP_X
@@ -87,7 +86,7 @@ static void check_consistent(const conv_case& g, size_t line)
     case K32_WINO2: {
         const int nc = t[2], bh = 8 * nc, T = (p.OH + 1) / 2;
         const long groups = p.Cout_pad / (16 * t[0]), blocks = c.grid_x / groups;
-        CHECK(pick32::winograd_ok(p, WCK) && c.threads == 64 * t[0] && c.lds == (size_t)WINO_LDS[nc], "line %d: Winograd block", n);
+        CHECK(pick32::winograd_ok(p) && c.threads == 64 * t[0] && c.lds == (size_t)WINO_LDS[nc], "line %d: Winograd block", n);
         CHECK(c.grid_x % (xcd * groups) == 0 && c.tiles_x * WINO_BW >= p.OW, "line %d: Winograd grid %u", n, c.grid_x);
         if (c.rows) // tile rows numbered through the batch
             CHECK(c.rows == T && c.vh == 0 && c.tiles_y * 4 * nc >= p.B * T && blocks >= (long)c.tiles_x * c.tiles_y, "line %d: rows form", n);
@@ -99,13 +98,6 @@ static void check_consistent(const conv_case& g, size_t line)
         CHECK(c.tile == 35000000 + 3000 + t[0], "line %d: tile %d", n, c.tile);
         break;
     }
-    case K32_WINO3:
-        CHECK(pick32::winograd_ok(p, W3_CK) && c.threads == 256 && c.lds == (size_t)W3_LDS_BYTES, "line %d: F(3x3) block", n);
-        CHECK(c.grid_x % (xcd * (p.Cout_pad / 64)) == 0 && c.tiles_x * W3_BW >= p.OW && c.tiles_y * W3_BH >= p.OH
-                && (long)(c.grid_x / (p.Cout_pad / 64)) >= (long)c.tiles_x * c.tiles_y * p.B,
-            "line %d: F(3x3) grid %u", n, c.grid_x);
-        CHECK(c.tile == 35005004, "line %d: tile %d", n, c.tile);
-        break;
     case K32_DIRECT: {
         const int per_block = (t[0] ? 64 : 32) * t[3];
         CHECK(pick32::direct_ok(p) && t[0] == g.split && t[1] == p.KH && t[2] == pick32::direct_chunk(p.KH * p.KW) && p.Cin % t[2] == 0 && t[4] == g.dwd, "line %d: direct form", n);
@@ -140,7 +132,7 @@ static void check_consistent(const form_case& g, size_t line)
 {
     conv32_params p = make_layer(g);
     engine_switches sw;
-    sw.no_winograd32 = g.no_wino != 0, sw.wino_f33 = g.f33 != 0;
+    sw.no_winograd32 = g.no_wino != 0;
     const conv32_forms f = conv32_layer_forms(p, g.dtype, sw, g.dwf != 0, g.room, g.cin);
     const int n = (int)line;
     if (g.dwf) { // (the engine's sep32 pass fuses a depthwise layer in front only where dw_fusable said yes for every pipe the engine may run on)
@@ -150,8 +142,8 @@ static void check_consistent(const form_case& g, size_t line)
             return;
     }
     static float buf[1];
-    p.w_wino = p.w_wino3 = p.w_frag = buf, p.w_split = reinterpret_cast<const _Float16*>(buf);
-    CHECK(f.w_wino == (f.kind == C32_WINO2 || f.kind == C32_WINO3) && f.w_wino3 == (f.kind == C32_WINO3), "line %d: Winograd weights", n);
+    p.w_wino = p.w_frag = buf, p.w_split = reinterpret_cast<const _Float16*>(buf);
+    CHECK(f.w_wino == (f.kind == C32_WINO2), "line %d: Winograd weights", n);
     CHECK(f.w_frag == (f.kind == C32_DIRECT) && f.w_split == (f.w_frag && g.dtype == HP_DTYPE_F32S), "line %d: direct weights", n);
     CHECK(g.dtype == HP_DTYPE_F32 || !f.w_wino, "line %d: Winograd is the fp32 pipe's", n);
     if (f.kind == C32_DIRECT) {
@@ -197,7 +189,7 @@ int main(int argc, char** argv)
     }
     std::fclose(f);
     CHECK(n == lines.size(), "the table has %zu lines, the grid %zu cases", n, lines.size());
-    int kernels[8] = {};
+    int kernels[7] = {};
     size_t line = 0;
     for (auto& g : v.conv) {
         check_consistent(g, ++line);
@@ -213,7 +205,7 @@ int main(int argc, char** argv)
     }
     for (auto& g : v.form)
         check_consistent(g, ++line);
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < 7; ++i)
         CHECK(kernels[i] > 0, "kernel %d never chosen", i);
     // every compiled direct instance is reachable by the picker's own rule for some layer of the grid
 #define HP_X(SPLIT, KS, CK, MW, DWD)                                                                                                  \

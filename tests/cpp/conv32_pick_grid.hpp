@@ -2,7 +2,7 @@
 // included this file behind the launchers' own arithmetic instead).  Three kinds of line:
 //   C form split KH Cin Cout H W B stride dil out pickB lane bn160 wk latency nc tall view dwd : ok kernel targ[5] grid_x grid_y threads lds tiles_x tiles_y vh rows tile
 //   H hid c2 hidb c2b same pair_switch npix : ok kernel TMA TMB grid_x threads tile head_ok head_pair_ok        (hidb = 0: one head)
-//   F dtype no_winograd32 wino_f33 dw_in_front room KH cin cout stride : w_wino w_wino3 w_frag w_split kind cin_split dw_fusable(fp32, split; dilation 1)
+//   F dtype no_winograd32 dw_in_front room KH cin cout stride : w_wino w_frag w_split kind cin_split dw_fusable(fp32, split; dilation 1)
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -55,7 +55,7 @@ inline conv32_params make_case(const conv_case& g)
     p.out = p.in, p.out.cs = round_up(g.Cout, 32), p.out.p = g.out == 2 ? nullptr : buf;
     p.out_f32 = g.out ? buf : nullptr;
     p.lane_epilogue = g.lane, p.latency = g.latency;
-    p.w = p.w_frag = p.w_wino = p.w_wino3 = buf, p.w_split = reinterpret_cast<const _Float16*>(buf);
+    p.w = p.w_frag = p.w_wino = buf, p.w_split = reinterpret_cast<const _Float16*>(buf);
     if (g.dwd)
         p.dw_w = buf, p.dw_dil = g.dwd;
     return p;
@@ -111,7 +111,7 @@ inline std::string line_of(const head_case& g)
 }
 
 struct form_case {
-    int dtype, no_wino, f33, dwf, room, KH, cin, cout, stride;
+    int dtype, no_wino, dwf, room, KH, cin, cout, stride;
 };
 // what lower32_conv hands over: Cin padded to 16, the forms' pointers null; dwf: the depthwise layer's weights set (lower32_dw_in_front)
 inline conv32_params make_layer(const form_case& g)
@@ -119,7 +119,7 @@ inline conv32_params make_layer(const form_case& g)
     conv_case c = cc(0, 0, g.KH, round_up(g.cin, 16), g.cout, 46, 54, 8);
     c.stride = g.stride;
     conv32_params p = make_case(c);
-    p.w_frag = p.w_wino = p.w_wino3 = nullptr, p.w_split = nullptr;
+    p.w_frag = p.w_wino = nullptr, p.w_split = nullptr;
     if (g.dwf)
         p.dw_w = p.w, p.dw_dil = 1;
     return p;
@@ -128,13 +128,13 @@ inline std::string line_of(const form_case& g)
 {
     const conv32_params p = make_layer(g);
     engine_switches sw;
-    sw.no_winograd32 = g.no_wino != 0, sw.wino_f33 = g.f33 != 0;
+    sw.no_winograd32 = g.no_wino != 0;
     const conv32_forms f = conv32_layer_forms(p, g.dtype, sw, g.dwf != 0, g.room, g.cin);
     conv32_params q = p;
     q.Cin = round_up(g.cin, 64), q.dw_w = nullptr;
     char s[200];
-    std::snprintf(s, sizeof s, "F %d %d %d %d %d %d %d %d %d : %d %d %d %d %d %d %d %d", g.dtype, g.no_wino, g.f33, g.dwf, g.room, g.KH, g.cin, g.cout, g.stride, (int)f.w_wino,
-        (int)f.w_wino3, (int)f.w_frag, (int)f.w_split, (int)f.kind, f.cin_split, (int)pick32::dw_fusable(q, false, 1), (int)pick32::dw_fusable(q, true, 1));
+    std::snprintf(s, sizeof s, "F %d %d %d %d %d %d %d %d : %d %d %d %d %d %d %d", g.dtype, g.no_wino, g.dwf, g.room, g.KH, g.cin, g.cout, g.stride, (int)f.w_wino,
+        (int)f.w_frag, (int)f.w_split, (int)f.kind, f.cin_split, (int)pick32::dw_fusable(q, false, 1), (int)pick32::dw_fusable(q, true, 1));
     return s;
 }
 
@@ -173,7 +173,7 @@ inline cases grid()
         for (int w = 0; w < 2; ++w) {
             const conv_case base = cc(C32_GEMM, 0, 1, w ? 128 : 64, w ? 64 : 256, MAPS[mi][0], MAPS[mi][1], MAPS[mi][2]);
             for (int lane : { -1, 0, 1 })
-                for (int bn : { -1, 0, 1, 176 }) {
+                for (int bn : { -1, 0, 1 }) {
                     conv_case c = base;
                     c.lane = lane, c.bn160 = bn, C.push_back(c);
                 }
@@ -259,13 +259,9 @@ inline cases grid()
             conv_case c = cc(C32_WINO2, 0, 3, 32, 64, h, 16, 8);
             c.latency = lat, C.push_back(c);
         }
-    // Winograd 4: F(3 x 3, 3 x 3) at maps that 24 x 6 blocks tile exactly (24 x 24, 48 x 48) and at maps they do not
-    for (auto& m : WM)
-        for (int b : { 1, 8 })
-            C.push_back(cc(C32_WINO3, 0, 3, 128, 128, m[0], m[1], b));
-    // Winograd 5: what both forms refuse
-    for (int form : { C32_WINO2, C32_WINO3 }) {
-        conv_case c = cc(form, 0, 3, 64, 64, 46, 54, 8);
+    // Winograd 4: what the form refuses
+    {
+        conv_case c = cc(C32_WINO2, 0, 3, 64, 64, 46, 54, 8);
         c.stride = 2, C.push_back(c);
         c.stride = 1, c.dil = 2, C.push_back(c);
         c.dil = 1, c.out = 1, C.push_back(c);
@@ -286,19 +282,18 @@ inline cases grid()
                         v.head.push_back({ 128, c2, 256, c2b, same, sw, 8 * 46 * 54 });
     v.head.push_back({ 128, 19, 192, 19, 1, 1, 31 });
     v.head.push_back({ 128, 19, 128, 19, 1, 1, 33 });
-    // layer forms: both fp32 engine types x the Winograd switches x a depthwise layer in front x room below / at the padded slice
+    // layer forms: both fp32 engine types x the Winograd switch x a depthwise layer in front x room below / at the padded slice
     static const int FL[][4] = { { 3, 128, 128, 1 }, { 3, 48, 128, 1 }, { 3, 128, 128, 2 }, { 1, 128, 64, 1 }, { 1, 128, 512, 1 }, { 1, 100, 64, 1 } };
     for (int dt : { HP_DTYPE_F32, HP_DTYPE_F32S })
         for (auto& l : FL)
             for (int nw : { 0, 1 })
-                for (int f33 : { 0, 1 })
-                    for (int dwf : { 0, 1 })
-                        for (int short_room : { 0, 1 }) {
-                            if (l[0] == 3 ? dwf : (nw || f33))
-                                continue;
-                            const int cin_s = round_up(l[1], l[0] == 1 ? 64 : 32);
-                            v.form.push_back({ dt, nw, f33, dwf, cin_s - (short_room ? 16 : 0), l[0], l[1], l[2], l[3] });
-                        }
+                for (int dwf : { 0, 1 })
+                    for (int short_room : { 0, 1 }) {
+                        if (l[0] == 3 ? dwf : nw)
+                            continue;
+                        const int cin_s = round_up(l[1], l[0] == 1 ? 64 : 32);
+                        v.form.push_back({ dt, nw, dwf, cin_s - (short_room ? 16 : 0), l[0], l[1], l[2], l[3] });
+                    }
     return v;
 }
 

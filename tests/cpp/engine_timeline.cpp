@@ -14,9 +14,9 @@ using hp::timeline_kind;
 using stamps = std::vector<unsigned long long>;
 typedef void (*printer)(FILE*, timeline_kind, const hp::timeline_header&, const unsigned long long*);
 
-static const timeline_kind KINDS[] = { timeline_kind::conv, timeline_kind::bneck, timeline_kind::chain, timeline_kind::sep, timeline_kind::wino3,
-    timeline_kind::wino, timeline_kind::direct, timeline_kind::conv32 };
-static const char* const NAMES[] = { "conv", "bneck", "chain", "sep", "wino3", "wino", "direct", "conv32" };
+static const timeline_kind KINDS[] = { timeline_kind::conv, timeline_kind::bneck, timeline_kind::chain, timeline_kind::sep, timeline_kind::wino,
+    timeline_kind::direct, timeline_kind::conv32 };
+static const char* const NAMES[] = { "conv", "bneck", "chain", "sep", "wino", "direct", "conv32" };
 static const hp::timeline_header HD = { 7, 128, 256, 3, 3, 35003004, 2 };
 
 static unsigned long long g_seed;
@@ -60,7 +60,6 @@ static stamps typical(timeline_kind k)
     case timeline_kind::bneck: phases(h, 0, 50), spans(h, 300); break;
     case timeline_kind::chain: phases(h, 0, 32); break; // (no zero inside the buffer: the loop ends at `to`)
     case timeline_kind::sep: phases(h, 0, 44), spans(h, 700), phases(h, 2112, 2112 + 30); break;
-    case timeline_kind::wino3: phases(h, 0, 40); break;
     case timeline_kind::wino: phases(h, 0, 100), h[119] = 500, h[120] = 9000, h[121] = 210500, h[122] = 19000; break;
     case timeline_kind::direct: phases(h, 0, 64); break;
     case timeline_kind::conv32: phases(h, 0, 128), residency(h, 1000, 8, 0, 0, 0); break;
@@ -77,7 +76,10 @@ static void run_cases(FILE* f, printer print)
         std::fflush(f);
     };
     g_seed = 20240607;
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < 7; ++i) {
+        if (KINDS[i] == timeline_kind::wino) // (a kind that stood here, F(3 x 3) Winograd, drew 41 numbers: the recorded texts behind it keep theirs)
+            for (int d = 0; d < 41; ++d)
+                rnd(1);
         one(std::string(NAMES[i]) + " typical", KINDS[i], typical(KINDS[i]));
         one(std::string(NAMES[i]) + " all zero", KINDS[i], stamps(hp::timeline_words(KINDS[i]), 0));
     }

@@ -1,6 +1,6 @@
 """GPU: the epilogues ("drains") of the fp32 GEMM kernels, bit for bit against values that do not depend on the order of summation.
 
-conv32_t16_kernel's drain and conv32_drain_rows (conv32_kernel's row form, conv32_direct_kernel, conv32_winograd3_kernel) compute a lane's
+conv32_t16_kernel's drain and conv32_drain_rows (conv32_kernel's row form, conv32_direct_kernel) compute a lane's
 pixel offsets with one division pair and carries, request bias, slopes and residual from clamped addresses, and choose the quad or the
 scalar path per launch.  What can go wrong there is an offset, a guard or an operand - not a rounding - so the expected
 values are made exact: weights, biases and the network input are small integers, act_hi = 6, the leaky slope 0.25, PReLU slopes powers of
@@ -17,9 +17,7 @@ one 16-pixel MFMA tile - the carries).  Cin 16 (one K-step: the loop's clamped r
 Every tested tensor has a halo (a 3 x 3 dilation-2 consumer); halo, separator rows and channels past Cout must still read zero
 (raw-buffer tap), and frame 1 alone equals frame 1 of the batch.  The tile code of every tested layer is asserted from profile().
 
-The two kernels that only share the drain get one case each.  conv32_winograd3_kernel multiplies by G = [1/4; 1/6; 1/24 ..] first, so
-integer weights do not give it exact sums: its case has all-zero 3 x 3 weights - the sums are exactly zero and bias, residual, activation,
-offsets and stores, i.e. the drain, are all that is left.
+The kernel that only shares the drain, conv32_direct_kernel, gets one case.
 """
 import numpy as np
 import pytest
@@ -89,7 +87,7 @@ def _bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def _graph(cin, couts, k=1, zero_weights=False, sliced=(False, True), in_coff=0):
+def _graph(cin, couts, k=1, sliced=(False, True), in_coff=0):
     """stem (integers 0 .. 6; the tested layers read its channels in_coff ..) and two residual sources, then per (Cout, residual, layout) a
     tested layer and its halo consumer.
     Returns the net, the outputs and [(layer index, tensor, channel offset, residual tensor or -1)]."""
@@ -116,10 +114,6 @@ def _graph(cin, couts, k=1, zero_weights=False, sliced=(False, True), in_coff=0)
                     t = net.conv(t0, cin, cout, k, **kw)
                     width = cout
                 li = len(net.layers) - 1
-                if zero_weights:
-                    L = net.layers[li]
-                    blob_i = next(i for i, _ in enumerate(net.w) if sum(len(x) for x in net.w[:i]) == L.w_off)
-                    net.w[blob_i][:] = 0
                 tested.append((li, t, SLICE_AT if sl else 0, r))
                 y, c = halo(net, t, width)
                 outs.append(Out(f"y{len(outs)}", y, 0, c))
@@ -175,9 +169,3 @@ def test_gemm_drains_are_exact(hp, monkeypatch, kernel, size, cin):
 def test_direct_kernel_shares_the_drain(hp, monkeypatch):
     """conv32_direct_kernel (1 x 1 on whole 64-channel chunks, narrow outputs): 38 channels, whole and sliced, every residual form."""
     _run_case(monkeypatch, dict(HP_NO_ARENA="1"), 34001001, 3, 7, 11, 64, (38,))
-
-
-@guarded
-def test_winograd3_kernel_shares_the_drain(hp, monkeypatch):
-    """conv32_winograd3_kernel (HP_WINO_F33=1), zero 3 x 3 weights (see the module's text): 96 channels on 3 x 7 x 11, every residual form."""
-    _run_case(monkeypatch, dict(HP_WINO_F33="1", HP_NO_ARENA="1"), 35005004, 3, 7, 11, 48, (96,), k=3, zero_weights=True, sliced=(False,))

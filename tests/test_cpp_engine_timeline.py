@@ -18,4 +18,4 @@ def test_timeline_text_is_the_recorded_text():
     out = subprocess.run([BIN, GOLDEN], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, f"exit {out.returncode}\n" + out.stdout[-2000:] + out.stderr[-2000:]
     tag, cases, size = out.stdout.split()[-3:]
-    assert tag == "OK" and int(cases) == 25 and int(size) == os.path.getsize(GOLDEN)
+    assert tag == "OK" and int(cases) == 23 and int(size) == os.path.getsize(GOLDEN)

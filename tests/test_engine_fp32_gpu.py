@@ -194,36 +194,6 @@ def test_winograd_3x3_layers(hp, cin, cout, h, w, act, monkeypatch):
             assert np.abs(x - yv).max() <= 2e-5 * np.abs(yv).max() + 1e-6, nm
 
 
-@pytest.mark.parametrize("cin,cout,h,w,act", [(16, 64, 23, 17, E.ACT_RELU), (48, 200, 31, 41, E.ACT_LEAKY), (128, 128, 24, 24, E.ACT_NONE), (256, 64, 25, 25, E.ACT_RELU6)])
-def test_winograd_f33_opt_in(hp, cin, cout, h, w, act, monkeypatch):
-    """conv32_winograd3_kernel (round 6, opt-in HP_WINO_F33=1): the same layers in F(3 x 3, 3 x 3) - 25 products per 3 x 3 output tile.  Ragged 24 x 6
-    pixel blocks, odd maps, one-chunk layers, residuals before / after the activation: against the oracle at the engine's one tolerance, against the
-    F(2 x 2, 3 x 3) engine at 2e-5 of scale, batch invariance bit for bit."""
-    def build():
-        net = Net(40 + cin)
-        t0 = net.conv(0, 3, cin, 3, 1)
-        a = net.conv(t0, cin, cout, 3, 1, act=act, act_param=0.2)
-        b = net.conv(a, cout, cout, 3, 1, res=a, res_before_act=0, act=E.ACT_RELU)
-        c = net.conv(b, cout, cout, 3, 1, res=b, res_before_act=1, act=act, act_param=0.2)
-        y = net.conv(c, cout, 24, 1, 1, act=E.ACT_NONE)
-        return net, [Out("y", y, 0, 24)]
-    frames = _frames(3, h, w, seed=cin + h)
-    monkeypatch.setenv("HP_WINO_F33", "1")
-    net, outs = build()
-    eng, got, _ = _run32(net, outs, frames, h, w, dtype="f32")
-    assert sum(p["tile"] == 35005004 for p in eng.profile(3, iters=1)) == 3
-    alone = eng.inference(frames[2:3])[0]
-    for (_, a1), (_, a3) in zip(alone, got[2]):
-        assert np.array_equal(a1, a3)
-    monkeypatch.delenv("HP_WINO_F33")
-    net2, outs2 = build()
-    eng2, got2, _ = _run32(net2, outs2, frames, h, w, dtype="f32")
-    assert sum(p["tile"] // 1000 == 35003 for p in eng2.profile(3, iters=1)) == 3
-    for b in range(3):
-        for (nm, x), (_, yv) in zip(got[b], got2[b]):
-            assert np.abs(x - yv).max() <= 2e-5 * np.abs(yv).max() + 1e-6, nm
-
-
 @pytest.mark.parametrize("hid,h,w,act1", [(512, 23, 27, E.ACT_RELU), (256, 9, 13, E.ACT_RELU6), (128, 16, 32, E.ACT_LEAKY)])
 def test_fused_two_layer_heads(hp, hid, h, w, act1, monkeypatch):
     """HP_DTYPE_F32: 1 x 1 128 -> HID -> 1 x 1 HID -> 19 | 38 | 64 in ONE launch (conv32_head.hip), the hidden tile's accumulator registers
@@ -262,7 +232,7 @@ def test_fused_two_layer_heads(hp, hid, h, w, act1, monkeypatch):
             assert np.abs(x - yv).max() <= 2e-5 * np.abs(yv).max() + 1e-6, nm
 
 
-@pytest.mark.parametrize("force,tile", [("1", 32064160), ("176", 32064176)])
+@pytest.mark.parametrize("force,tile", [("1", 32064160)])
 @pytest.mark.parametrize("cin,cout,k,h,w", [(64, 128, 1, 40, 52), (128, 512, 1, 23, 27), (512, 512, 1, 23, 27), (96, 200, 3, 19, 33), (32, 64, 1, 61, 47), (128, 128, 7, 20, 23)])
 def test_one_round_tile_64x160(hp, cin, cout, k, h, w, force, tile, monkeypatch):
     """conv32_t16_kernel<160> (round 6: 64 output channels x 160 pixels per block on v_mfma_f32_16x16x4_f32, taken where 64 x 128 tiles are
@@ -278,7 +248,7 @@ def test_one_round_tile_64x160(hp, cin, cout, k, h, w, force, tile, monkeypatch)
         y = net.conv(c, 70, 38, 1, 1, act=E.ACT_NONE)
         return net, [Out("y", y, 0, 38), Out("c", c, 0, 70), Out("b", b, 0, cout)]
     frames = _frames(5, h, w, seed=cin + k)
-    monkeypatch.setenv("HP_C32_BN160", force)  # "1": conv32_t16_kernel<160, 2>; "176": conv32_t16_kernel<176, 1> (four wavefronts of 16 channels x 176 pixels)
+    monkeypatch.setenv("HP_C32_BN160", force)  # "1": conv32_t16_kernel<160, 2> on every layer
     monkeypatch.setenv("HP_C32_WK", "0")
     net, outs = build()
     eng, got, _ = _run32(net, outs, frames, h, w, dtype="f32")
@@ -289,41 +259,48 @@ def test_one_round_tile_64x160(hp, cin, cout, k, h, w, force, tile, monkeypatch)
     monkeypatch.setenv("HP_C32_BN160", "0")
     net2, outs2 = build()
     eng2, got2, _ = _run32(net2, outs2, frames, h, w, dtype="f32")
-    assert not [p for p in eng2.profile(5, iters=1) if p["tile"] in (32064160, 32064176)]
+    assert not [p for p in eng2.profile(5, iters=1) if p["tile"] == 32064160]
     for b in range(5):
         for (nm, x), (_, yv) in zip(got[b], got2[b]):
             assert np.abs(x - yv).max() <= 2e-5 * np.abs(yv).max() + 1e-6, nm
 
 
-@pytest.mark.parametrize("cin,h,w", [(32, 61, 47), (64, 40, 52), (128, 23, 27), (64, 12, 12)])
+@pytest.mark.parametrize("cin,h,w", [(32, 61, 47), (64, 40, 52), (64, 12, 12)])
 def test_whole_k_tile(hp, cin, h, w, monkeypatch):
-    """conv32_wk_kernel (round 6: 1 x 1 layers with 32 / 64 / 128 input channels; a block reads its 64 weight rows, its pixels for ALL K, the
+    """conv32_wk_kernel (round 6: 1 x 1 layers with 32 / 64 input channels; a block reads its 64 weight rows, its pixels for ALL K, the
     residual and the bias at once, then multiplies and stores 16-pixel tiles without another barrier): forced (HP_C32_WK=1) on maps whose
     pixel counts are not multiples of the tile, with a residual before the activation, every activation form, 70 real output channels of 128
-    (partial quads) and a stride-2 layer - against the oracle at the engine's tolerance, against the other kernels (HP_C32_WK=0) at 2e-5 of
+    (partial quads) and a stride-2 layer, each on 32 or 64 input channels - against the oracle at the engine's tolerance, against the other kernels (HP_C32_WK=0) at 2e-5 of
     scale, batch invariance bit for bit."""
     def build():
         net = Net(300 + cin)
+        wk = {}   # the layers that must run on the kernel: index -> tile code (39 | input channels | 64 pixels per block)
+        def conv_wk(in_, k_, *a_, **kw):
+            t = net.conv(in_, k_, *a_, **kw)
+            wk[len(net.layers) - 1] = 39000000 + 1000 * k_ + 64
+            return t
         t0 = net.conv(0, 3, cin, 3, 1)
-        a = net.conv(t0, cin, 128, 1, 1, act=E.ACT_PRELU)
-        r = net.conv(t0, cin, 128, 1, 1, act=E.ACT_RELU)
-        b = net.conv(a, 128, 128, 1, 1, res=r, res_before_act=1, act=E.ACT_RELU6)
-        c = net.conv(b, 128, 70, 1, 1, act=E.ACT_LEAKY, act_param=0.1)
-        d = net.conv(t0, cin, 64, 1, 2, act=E.ACT_NONE)
+        a = conv_wk(t0, cin, 128, 1, 1, act=E.ACT_PRELU)
+        r = conv_wk(t0, cin, 128, 1, 1, act=E.ACT_RELU)
+        m = net.conv(a, 128, 64, 1, 1)   # (128 input channels: another kernel's)
+        # (a 1 x 1 stride-1 layer of at most 64 padded outputs on a whole 64-channel chunk is conv32_direct_kernel's: b and c are wider, d has stride 2)
+        b = conv_wk(m, 64, 128, 1, 1, res=r, res_before_act=1, act=E.ACT_RELU6)
+        c = conv_wk(m, 64, 70, 1, 1, act=E.ACT_LEAKY, act_param=0.1)
+        d = conv_wk(t0, cin, 64, 1, 2, act=E.ACT_NONE)
         # (a layer that writes a network output is not this kernel's: every layer under test is read through a 3 x 3 layer behind it)
         yb, yc, yd = net.conv(b, 128, 32, 3, 1, act=E.ACT_NONE), net.conv(c, 70, 38, 3, 1, act=E.ACT_NONE), net.conv(d, 64, 24, 3, 1, act=E.ACT_NONE)
-        return net, [Out("yb", yb, 0, 32), Out("yc", yc, 0, 38), Out("yd", yd, 0, 24)]
+        return net, [Out("yb", yb, 0, 32), Out("yc", yc, 0, 38), Out("yd", yd, 0, 24)], wk
     frames = _frames(5, h, w, seed=cin)
     monkeypatch.setenv("HP_C32_WK", "1")
-    net, outs = build()
+    net, outs, wk = build()
     eng, got, _ = _run32(net, outs, frames, h, w, dtype="f32")
-    tiles = [p["tile"] for p in eng.profile(5, iters=1)]
-    assert sum(t // 1000000 == 39 for t in tiles) == 5, tiles
+    tiles = {p["layer"]: p["tile"] for p in eng.profile(5, iters=1)}
+    assert len(wk) == 5 and {i: t for i, t in tiles.items() if t // 1000000 == 39} == wk, tiles
     alone = eng.inference(frames[3:4])[0]
     for (_, a1), (_, a5) in zip(alone, got[3]):
         assert np.array_equal(a1, a5)
     monkeypatch.setenv("HP_C32_WK", "0")
-    net2, outs2 = build()
+    net2, outs2, _ = build()
     eng2, got2, _ = _run32(net2, outs2, frames, h, w, dtype="f32")
     assert not [p for p in eng2.profile(5, iters=1) if p["tile"] // 1000000 == 39]
     for b in range(5):

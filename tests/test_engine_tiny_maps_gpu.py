@@ -60,7 +60,6 @@ assert len(BY_NAME) == len(CASES) and set(ROUTED_AWAY) <= set(BY_NAME) and set(B
 #   HP_WINO_NC=1 (8-row blocks; "f32-winograd-small-blocks"): tall_y = ceil((2 vh + H) / 8) = 2, 2, 3, 2, 2, 2: TALL at every size but 5 x 1,
 #       where 3 is no fewer than the images' own 3 block rows: PER IMAGE;
 #   HP_WINO_TALL=0 ("f32-winograd-per-image"): PER IMAGE at every size.
-# F(3 x 3) ("f32-winograd-f33", tile 35005004) has the per-image form only.
 
 
 @pytest.fixture(scope="module")
