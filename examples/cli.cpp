@@ -35,6 +35,9 @@
 //     runs on it as a device-resident frame, the skeletons are drawn on the device surface (hp::draw_humans, opacity = alpha; alpha == 0 -> 1)
 //     and the annotated frames are appended to <file> as raw frames of the same format; <file>.humans receives, per frame, an int32 count and
 //     that many 292-byte hp_human records in the frame's coordinates (what was drawn).  The PPM output is unchanged.
+//   * redaction (addition): `--redact=head|body` pixelates (`--redact_effect=pixelate|black`) the heads or the whole persons on the --saving_yuv
+//     frames, on the device surface (hp::redact_humans: cells of `--redact_cell=16` pixels, regions grown by `--redact_margin=1.0`), BEFORE the
+//     skeletons are drawn on top; `--redact_only` leaves the skeletons out.  Refused from the flags alone without --saving_yuv or with a bad value.
 //   * `--synthetic_humans=<n>` (addition, default 0): n seeded stand-in humans are added to every frame's parser output before anything is drawn -
 //     the built-in models carry synthetic weights and find nobody, so this is what makes a demonstration (or a test) of the drawing paths show
 //     something; operator runtime only.  A warning says that the pictures and the count are not the model's result.
@@ -94,6 +97,12 @@ static std::string FLAGS_scale_ensemble; // addition: --scale_ensemble=0.5,0.75:
 static std::vector<float> g_scales;      // ... parsed
 static hp::orientation g_orient;
 static std::string FLAGS_saving_yuv; // addition: append the frames, annotated on the device in their own format, to this file
+static std::string FLAGS_redact, FLAGS_redact_effect = "pixelate"; // addition: --redact=head|body on the --saving_yuv frames (hp::redaction)
+static int FLAGS_redact_cell = 16;
+static double FLAGS_redact_margin = 1.0;
+static bool FLAGS_redact_only = false; // ... and no skeletons on top
+static bool g_redact = false;
+static hp::redaction g_redaction;
 static int FLAGS_synthetic_humans = 0; // addition: stand-in humans added to every frame's poses (see the head of the file)
 static bool g_yuv_from_file = false; // the frames came from a .yuv source (else --yuv made NV12 ones)
 static int g_yuv_format = HP_YUV_I420, g_yuv_matrix = HP_YUV_BT601, g_yuv_range = HP_YUV_LIMITED;      // the same, parsed
@@ -106,12 +115,15 @@ static bool parse_flags(int argc, char** argv)
     std::map<std::string, std::string*> sflags = { { "model", &FLAGS_model }, { "post", &FLAGS_post }, { "source", &FLAGS_source },
         { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix }, { "saving_yuv", &FLAGS_saving_yuv }, { "tiles", &FLAGS_tiles }, { "yuv_format", &FLAGS_yuv_format },
         { "yuv_matrix", &FLAGS_yuv_matrix }, { "yuv_range", &FLAGS_yuv_range }, { "yuv_transfer", &FLAGS_yuv_transfer },
-        { "scale_ensemble", &FLAGS_scale_ensemble } };
-    std::map<std::string, double*> dflags = { { "alpha", &FLAGS_alpha }, { "hdr_peak", &FLAGS_hdr_peak }, { "hdr_white", &FLAGS_hdr_white } };
+        { "scale_ensemble", &FLAGS_scale_ensemble }, { "redact", &FLAGS_redact }, { "redact_effect", &FLAGS_redact_effect } };
+    std::map<std::string, double*> dflags = { { "alpha", &FLAGS_alpha }, { "hdr_peak", &FLAGS_hdr_peak }, { "hdr_white", &FLAGS_hdr_white },
+        { "redact_margin", &FLAGS_redact_margin } };
     std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size }, { "tile_overlap", &FLAGS_tile_overlap },
-        { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h }, { "synthetic_humans", &FLAGS_synthetic_humans }, { "rotate", &FLAGS_rotate } };
+        { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h }, { "synthetic_humans", &FLAGS_synthetic_humans }, { "rotate", &FLAGS_rotate },
+        { "redact_cell", &FLAGS_redact_cell } };
     std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 }, { "yuv", &FLAGS_yuv }, { "tile_full", &FLAGS_tile_full },
-        { "hdr_keep_primaries", &FLAGS_hdr_keep_primaries }, { "hflip", &FLAGS_hflip }, { "flip_ensemble", &FLAGS_flip_ensemble } };
+        { "hdr_keep_primaries", &FLAGS_hdr_keep_primaries }, { "hflip", &FLAGS_hflip }, { "flip_ensemble", &FLAGS_flip_ensemble },
+        { "redact_only", &FLAGS_redact_only } };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         if (a.rfind("--", 0) != 0 && a.rfind("-", 0) == 0)
@@ -210,6 +222,25 @@ static bool parse_flags(int argc, char** argv)
         g_hdr_on = true;
     } else if (FLAGS_hdr_keep_primaries || FLAGS_hdr_peak != HP_HDR_DEFAULT_PEAK || FLAGS_hdr_white != HP_HDR_DEFAULT_WHITE) {
         cli_log() << "ERROR: --hdr_peak / --hdr_white / --hdr_keep_primaries describe the frames of --yuv_transfer=pq|hlg\n";
+        return false;
+    }
+    // --redact and its companions: enumerated names, an even cell in [2, 128], a margin in (0, 8]; the companions describe --redact
+    if (!FLAGS_redact.empty()) {
+        if (!pick("redact", FLAGS_redact, { { "head", hp::redaction::head }, { "body", hp::redaction::body } }, g_redaction.what)
+            || !pick("redact_effect", FLAGS_redact_effect, { { "pixelate", hp::redaction::pixelate }, { "black", hp::redaction::black } }, g_redaction.effect))
+            return false;
+        if (FLAGS_redact_cell < 2 || FLAGS_redact_cell > 128 || FLAGS_redact_cell % 2 != 0) {
+            cli_log() << "ERROR: --redact_cell=" << FLAGS_redact_cell << " is not an even number in [2, 128]\n";
+            return false;
+        }
+        if (!(FLAGS_redact_margin > 0 && FLAGS_redact_margin <= 8)) {
+            cli_log() << "ERROR: --redact_margin=" << FLAGS_redact_margin << " is outside (0, 8]\n";
+            return false;
+        }
+        g_redaction.cell = FLAGS_redact_cell, g_redaction.margin = (float)FLAGS_redact_margin;
+        g_redact = true;
+    } else if (FLAGS_redact_only || FLAGS_redact_effect != "pixelate" || FLAGS_redact_cell != 16 || FLAGS_redact_margin != 1.0) {
+        cli_log() << "ERROR: --redact_effect / --redact_cell / --redact_margin / --redact_only describe --redact=head|body\n";
         return false;
     }
     return pick("yuv_format", FLAGS_yuv_format, { { "i420", HP_YUV_I420 }, { "nv12", HP_YUV_NV12 }, { "p010", HP_YUV_P010 }, { "i010", HP_YUV_I010 },
@@ -513,6 +544,11 @@ int main(int argc, char** argv)
         cli_log() << "ERROR: --saving_yuv writes video frames: it needs a .yuv source or --yuv\n";
         return 1;
     }
+    // --redact rewrites the frames --saving_yuv writes: settled from the flags alone as well
+    if (g_redact && FLAGS_saving_yuv.empty()) {
+        cli_log() << "ERROR: --redact=" << FLAGS_redact << " redacts the frames of --saving_yuv=<file>; the PPM pictures are not redacted\n";
+        return 1;
+    }
     // --flip_ensemble is settled from the flags alone too: the PAF maps are the ones with a left / right channel table
     if (FLAGS_flip_ensemble && FLAGS_post != kPAF) {
         cli_log() << "ERROR: --flip_ensemble merges the maps of a PAF network (--post=" kPAF "), got --post=" << FLAGS_post << "\n";
@@ -697,10 +733,14 @@ int main(int argc, char** argv)
                         for (auto& pose : drawn)
                             hp::resume_ratio(pose, hp::oriented_size(batch[k].size(), g_orient), engine.input_size());
                     // `drawn` stays upright (it is what <file>.humans records); the surface is the stored frame
-                    if (g_hdr_on)
-                        hp::draw_humans(yuv_batch[k], drawn, g_orient, g_hdr, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
-                    else
-                        hp::draw_humans(yuv_batch[k], drawn, g_orient, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
+                    if (g_redact) // first the persons made unrecognisable, then the skeletons on top
+                        hp::redact_humans(yuv_batch[k], drawn, g_orient, g_redaction);
+                    if (!FLAGS_redact_only) {
+                        if (g_hdr_on)
+                            hp::draw_humans(yuv_batch[k], drawn, g_orient, g_hdr, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
+                        else
+                            hp::draw_humans(yuv_batch[k], drawn, g_orient, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
+                    }
                     std::vector<uint8_t> annotated(g_yuv[first + k].data.size());
                     if (hp_device_synchronize() != HP_OK || hp_memcpy_d2h(annotated.data(), surfaces[k]->p, annotated.size()) != HP_OK) {
                         cli_log() << "ERROR: " << hp_last_error() << "\n";

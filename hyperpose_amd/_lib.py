@@ -62,6 +62,18 @@ class OverlayPrim(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("kind", "x0", "y0", "x1", "y1", "t", "colour", "human")]
 
 
+class RedactRegion(C.Structure):
+    """hp_redact_region"""
+    _fields_ = [(k, C.c_int32) for k in ("kind", "x0", "y0", "x1", "y1", "human")]
+
+
+HP_REDACT_RECT, HP_REDACT_DISC = 0, 1
+HP_REDACT_HEAD, HP_REDACT_BODY = 0, 1
+HP_REDACT_PIXELATE, HP_REDACT_BLACK = 0, 1
+REDACT_WHAT = {"head": HP_REDACT_HEAD, "body": HP_REDACT_BODY}
+REDACT_EFFECTS = {"pixelate": HP_REDACT_PIXELATE, "black": HP_REDACT_BLACK}
+
+
 class Roi(C.Structure):
     """hp_roi: a region of a frame in source pixels"""
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
@@ -96,6 +108,7 @@ PART_DTYPE = np.dtype([("has_value", "<i4"), ("x", "<f4"), ("y", "<f4"), ("score
 HUMAN_DTYPE = np.dtype({"names": ["parts", "score"], "formats": [(PART_DTYPE, 18), "<f4"]})
 PEAK_DTYPE = np.dtype([("part_id", "<i4"), ("x", "<i4"), ("y", "<i4"), ("score", "<f4"), ("id", "<i4")])
 OVERLAY_PRIM_DTYPE = np.dtype([(k, "<i4") for k in ("kind", "x0", "y0", "x1", "y1", "t", "colour", "human")])
+REDACT_REGION_DTYPE = np.dtype([(k, "<i4") for k in ("kind", "x0", "y0", "x1", "y1", "human")])
 CONN_DTYPE = np.dtype([("pair_id", "<i4"), ("cid1", "<i4"), ("cid2", "<i4"), ("score", "<f4")])
 assert HUMAN_DTYPE.itemsize == C.sizeof(Human) == 292
 
@@ -109,6 +122,7 @@ SYMBOLS = [
     "hp_resize_yuv", "hp_letterbox_yuv", "hp_yuv_coefficients", "hp_yuv_packed_bytes", "hp_yuv_plane_layout", "hp_pipeline_submit_yuv_images",
     "hp_overlay_create", "hp_overlay_destroy", "hp_overlay_primitives", "hp_yuv_colours", "hp_overlay_draw_u8c3", "hp_overlay_draw_yuv",
     "hp_overlay_draw_u8c3_host", "hp_overlay_draw_yuv_host",
+    "hp_redact_create", "hp_redact_destroy", "hp_redact_regions", "hp_redact_u8c3", "hp_redact_yuv", "hp_redact_u8c3_host", "hp_redact_yuv_host",
     "hp_paf_create", "hp_paf_stream", "hp_paf_destroy", "hp_paf_set_conf_thresh", "hp_paf_set_paf_thresh", "hp_paf_process_batch",
     "hp_paf_enqueue", "hp_paf_collect", "hp_paf_debug_peaks", "hp_paf_debug_conns", "hp_paf_debug_maps", "hp_paf_debug_sort",
     "hp_pifpaf_create", "hp_pifpaf_destroy", "hp_pifpaf_process_batch", "hp_pifpaf_stream", "hp_pifpaf_enqueue", "hp_pifpaf_collect", "hp_pifpaf_decode_flags",

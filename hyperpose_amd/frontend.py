@@ -6,8 +6,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HDR_DEFAULT_PEAK, HDR_DEFAULT_WHITE, HDR_TRANSFERS, HUMAN_DTYPE, OVERLAY_PRIM_DTYPE, TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL,
-                   YUV_FORMATS, YUV_LAYOUTS, YUV_MATRICES, YUV_RANGES, DevBuf, HdrDesc, Human, OverlayPrim, Roi, Tiling, YuvImage, as_ptr, check, lib)
+from ._lib import (HDR_DEFAULT_PEAK, HDR_DEFAULT_WHITE, HDR_TRANSFERS, HUMAN_DTYPE, OVERLAY_PRIM_DTYPE, REDACT_EFFECTS, REDACT_REGION_DTYPE, REDACT_WHAT,
+                   TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL, YUV_FORMATS, YUV_LAYOUTS, YUV_MATRICES, YUV_RANGES, DevBuf, HdrDesc, Human, OverlayPrim,
+                   RedactRegion, Roi, Tiling, YuvImage, as_ptr, check, lib)
 
 
 def resize(src_dev, sw: int, sh: int, dst_dev, dw: int, dh: int, stream=None, src_stride=None, dst_stride=None) -> None:
@@ -572,3 +573,80 @@ def draw_humans_host(frame, humans, fmt=None, matrix: str = "bt601", range: str 
         check(lib().hp_overlay_draw_yuv_host_hdr(C.byref(im), C.byref(hdr), hp, len(hs), C.c_float(opacity), int(thickness)))
         return
     check(lib().hp_overlay_draw_yuv_host(C.byref(im), hp, len(hs), C.c_float(opacity), int(thickness)))
+
+
+# ---- writing back: heads or whole persons made unrecognisable (hp_redact_*; the rules are stated in csrc/redact.hpp and DESIGN.md 1.1) ----
+
+def _regions(regions) -> np.ndarray:
+    return np.ascontiguousarray(regions, REDACT_REGION_DTYPE).reshape(-1)
+
+
+def redact_regions(humans, w: int, h: int, what: str = "head", margin: float = 1.0) -> np.ndarray:
+    """``hp_redact_regions``: the regions (REDACT_REGION_DTYPE records, in order) that cover the heads (``what`` "head": one disc per human
+    with a face part) or the whole persons ("body": a rectangle, then the head disc) of a ``w`` x ``h`` frame's humans."""
+    hs = _humans(humans)
+    out = np.zeros(max(1, 2 * len(hs)), REDACT_REGION_DTYPE)
+    n = check(lib().hp_redact_regions(hs.ctypes.data_as(C.POINTER(Human)), len(hs), int(w), int(h), REDACT_WHAT[what], C.c_float(margin),
+                                      out.ctypes.data_as(C.POINTER(RedactRegion)), len(out)))
+    return out[:n]
+
+
+class Redactor:
+    """``hp_redact``: the handle the device entry points work through (pinned staging slots and device lists for ``max_regions`` per call)."""
+
+    def __init__(self, max_regions: int = 128):
+        self.h = C.c_void_p()
+        self.max_regions = int(max_regions)
+        check(lib().hp_redact_create(C.byref(self.h), self.max_regions))
+
+    def close(self):
+        if self.h:
+            lib().hp_redact_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_redactor = None
+
+
+def _default_redactor(n: int) -> Redactor:
+    global _redactor
+    if _redactor is None or _redactor.max_regions < n:
+        _redactor = Redactor(max(128, n))
+    return _redactor
+
+
+def redact(target, regions, effect: str = "pixelate", cell: int = 16, w=None, h=None, stride=None, stream=None, redactor=None) -> None:
+    """Pixelate or black out every ``cell`` x ``cell`` cell that ``regions`` (REDACT_REGION_DTYPE, in the frame's pixels: ``redact_regions`` or the
+    caller's own) reach, in a frame in DEVICE memory, in place and stream-ordered: ``target`` is a ``YuvImage`` whose planes are device pointers
+    (``hp_redact_yuv``) or a device buffer of 8-bit BGR with ``w``, ``h`` and optionally ``stride`` in bytes (``hp_redact_u8c3``)."""
+    rs = _regions(regions)
+    rd = redactor or _default_redactor(len(rs))
+    rp, s = rs.ctypes.data_as(C.POINTER(RedactRegion)), C.c_void_p(stream) if stream else None
+    if isinstance(target, YuvImage):
+        check(lib().hp_redact_yuv(rd.h, C.byref(target), rp, len(rs), REDACT_EFFECTS[effect], int(cell), s))
+    else:
+        check(lib().hp_redact_u8c3(rd.h, as_ptr(target), int(w), int(h), int(stride or w * 3), rp, len(rs), REDACT_EFFECTS[effect], int(cell), s))
+
+
+def redact_host(frame, regions, fmt=None, matrix: str = "bt601", range: str = "limited", effect: str = "pixelate", cell: int = 16) -> None:
+    """The same picture on a frame in HOST memory, in place, no device needed: ``frame`` is a uint8 array [h, w, 3] (BGR, ``fmt`` None) or the
+    list of 2-D plane arrays ``yuv_planes`` returns (``fmt`` names the layout).  Rows may be padded (views of wider arrays); samples must be
+    contiguous within a row."""
+    rs = _regions(regions)
+    rp = rs.ctypes.data_as(C.POINTER(RedactRegion))
+    if fmt is None:
+        assert frame.dtype == np.uint8 and frame.ndim == 3 and frame.shape[2] == 3 and frame.strides[1:] == (3, 1) and frame.flags.writeable
+        check(lib().hp_redact_u8c3_host(C.c_void_p(frame.ctypes.data), frame.shape[1], frame.shape[0], frame.strides[0], rp, len(rs),
+                                        REDACT_EFFECTS[effect], int(cell)))
+        return
+    for p in frame:
+        assert p.ndim == 2 and p.strides[1] == p.itemsize and p.flags.writeable
+    w, h = yuv_size_of_planes(fmt, frame)
+    im = yuv_image(fmt, [p.ctypes.data for p in frame], [p.strides[0] for p in frame], w, h, matrix, range)
+    check(lib().hp_redact_yuv_host(C.byref(im), rp, len(rs), REDACT_EFFECTS[effect], int(cell)))

@@ -366,6 +366,45 @@ int hp_yuv_colours_hdr(int matrix, int range, const hp_hdr_desc* d, int32_t out[
 int hp_overlay_set_transfer(hp_overlay* o, const hp_hdr_desc* d);
 int hp_overlay_draw_yuv_host_hdr(const hp_yuv_image* frame, const hp_hdr_desc* d, const hp_human* humans, int n, float opacity, int thickness);
 
+/* ---- redaction: the heads or the whole persons of a frame made unrecognisable in a DEVICE-resident frame before it is encoded, stored or shown,
+ * 8-bit BGR or any hp_yuv_image layout (hyperpose_amd/csrc/redact.hip) - the write-back counterpart of the overlay.  The picture is defined by
+ * exact integer rules, stated once in hyperpose_amd/csrc/redact.hpp and DESIGN.md 1.1 "Redaction":
+ *   regions      RECT covers the pixels of [x0, x1] x [y0, y1], inclusive (x0 <= x1, y0 <= y1); DISC has centre (x0, y0) and radius x1 >= 0, y1 == 0;
+ *                coordinates in [-8192, 16383], radii in [0, 16384]; `human` is informational (-1 for a caller's own region - a licence plate, a screen)
+ *   from humans  hp_redact_regions: points are int(x * w), int(y * h) in fp32, a part is present when has_value, x and y are finite and the point lies
+ *                in [-8192, 16383]^2; m = nearbyint(margin * 256), margin in (0, 8].  Head disc per human: over the present parts among nose, eyes, ears
+ *                (0, 14 .. 17; none: no disc) the bounding box lo, hi gives the centre floor((lo + hi) / 2) and e = its longer side; nk = isqrt(|neck -
+ *                nose|^2), sh = isqrt(|shoulder - shoulder|^2) >> 1 where present, else 0; r = min(16384, max(1, (max(e, nk, sh, 1) * m + 128) >> 8)).
+ *                HP_REDACT_HEAD: that disc.  HP_REDACT_BODY: first a RECT, the bounding box of ALL present parts grown by p = max(1, (its longer side *
+ *                m + 1024) >> 11) and clamped into the coordinate range, then the head disc.
+ *   cells        `cell` even, 2 .. 128, grid anchored at pixel (0, 0), edge cells partial.  A cell is hit when any region reaches it: a RECT that
+ *                intersects it; a DISC with dx * dx + dy * dy <= r * r (int64) for d = centre - the centre clamped into the cell.  A union: order and
+ *                overlap do not matter.  A hit cell is rewritten whole, every sample of every plane in it; nothing else is written (row padding included).
+ *   effect       HP_REDACT_PIXELATE: each of B, G, R / Y, U, V becomes (sum + cnt / 2) / cnt over that channel's samples in the cell, on code values
+ *                (P010: word >> 6, stored << 6; I010: word & 1023).  HP_REDACT_BLACK: BGR 0; Y = 16 << (d - 8) limited, 0 full; U = V = 1 << (d - 1).
+ * The handle owns pinned staging slots and device lists for up to max_regions regions per call; a call only ENQUEUES one launch on `stream` (NULL =
+ * the default stream) and does not wait for the previous call.  Frames follow hp_resize_yuv's rules, width and height at most 8192.  HP_ERR_INVALID,
+ * with a message that names the format or the offending value, nothing launched and the frame untouched: cell odd or outside 2 .. 128, an unknown
+ * effect or kind, a region outside the ranges above, n > max_regions, margin outside (0, 8].  n == 0 is HP_OK and launches nothing. */
+enum { HP_REDACT_RECT = 0, HP_REDACT_DISC = 1 };
+enum { HP_REDACT_HEAD = 0, HP_REDACT_BODY = 1 };
+enum { HP_REDACT_PIXELATE = 0, HP_REDACT_BLACK = 1 };
+typedef struct hp_redact_region {
+    int32_t kind, x0, y0, x1, y1, human;
+} hp_redact_region;
+typedef struct hp_redact hp_redact;
+int hp_redact_create(hp_redact** out, int max_regions);
+void hp_redact_destroy(hp_redact* r);
+/* host only: the regions of a frame's humans, in order; returns the count (or a negative HP_ERR_*), writes at most cap entries (at most 2 per human) */
+int hp_redact_regions(const hp_human* humans, int n, int w, int h, int what, float margin, hp_redact_region* out, int cap);
+/* device frames, rewritten in place; regions in host memory, in the frame's pixels */
+int hp_redact_u8c3(hp_redact* r, uint8_t* dev_bgr, int w, int h, int stride, const hp_redact_region* regions, int n, int effect, int cell, void* stream);
+int hp_redact_yuv(hp_redact* r, const hp_yuv_image* frame /* planes in DEVICE memory, WRITTEN */, const hp_redact_region* regions, int n, int effect,
+                  int cell, void* stream);
+/* the same picture on frames in HOST memory (plain C++, the integer rules above; no device needed) */
+int hp_redact_u8c3_host(uint8_t* bgr, int w, int h, int stride, const hp_redact_region* regions, int n, int effect, int cell);
+int hp_redact_yuv_host(const hp_yuv_image* frame, const hp_redact_region* regions, int n, int effect, int cell);
+
 /* ---- hyperpose::parser::paf (include/hyperpose/operator/parser/paf.hpp:17-93, src/paf.cpp) -------- */
 typedef struct hp_paf hp_paf;
 

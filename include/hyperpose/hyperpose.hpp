@@ -8,3 +8,4 @@
 #include "utility/data.hpp"
 #include "utility/human.hpp"
 #include "utility/overlay.hpp"
+#include "utility/redact.hpp"
