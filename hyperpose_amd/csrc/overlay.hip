@@ -29,47 +29,38 @@
 //     overlay_packed8_kernel       33     88        0       8208             8
 //     overlay_word16_kernel        38     94        0       8208             8
 //
-// The list reaches the device through the handle (hp_overlay): SLOTS pinned staging buffers and as many device lists, used in turn.  A call
-// builds the list in the next pinned slot, enqueues one hipMemcpyAsync and the kernel on the caller's stream and records the slot's event;
-// it waits (on the host) only if that slot's use SLOTS calls ago has not finished.
+// The list reaches the device through the handle (hp_overlay): an hp::staged_ring (annotate.hpp), SLOTS pinned staging buffers and as many
+// device lists, used in turn.  A call takes the next slot, builds the list in its pinned buffer, enqueues one hipMemcpyAsync and the kernel on
+// the caller's stream and commits the slot; it waits (on the host) only if that slot's use SLOTS calls ago has not finished.  Where a part lies
+// (part_points.hpp), the frame checks (annotate.hpp) and the bytewise host sample access (yuv_formats.hpp) are shared with redact.hip.
+#include "annotate.hpp"
 #include "overlay.hpp"
 #include "tonemap.hpp"
 #include "yuv_formats.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 namespace {
 
 using namespace hp_ovl;
 
-constexpr int TILE_W = 32, TILE_H = 8, THREADS = TILE_W * TILE_H, LIST_CAP = 256, SLOTS = 4;
+constexpr int TILE_W = 32, TILE_H = 8, THREADS = TILE_W * TILE_H, LIST_CAP = 256;
 
 // ---- host: primitive list and colour tables -------------------------------------------------------------------------------------------
-
-bool present(const hp_body_part& p) { return p.has_value != 0 && std::isfinite(p.x) && std::isfinite(p.y); }
-
-// int(v) for v = coordinate * size, when it lies inside [COORD_MIN, COORD_MAX]
-bool to_pixel(float v, int32_t& out)
-{
-    if (!(v > (float)(COORD_MIN - 1) && v < (float)(COORD_MAX + 1)))
-        return false;
-    out = (int32_t)v;
-    return true;
-}
 
 int build_primitives(const hp_human* humans, int n, int w, int h, int thickness, hp_overlay_prim* out, int cap)
 {
     int count = 0;
-    const float fw = (float)w, fh = (float)h;
     for (int i = 0; i < n; ++i) {
         const hp_human& hm = humans[i];
         int t = thickness;
-        if (t <= 0) {
+        if (t <= 0) { // over the PRESENT parts, whether or not their pixel is in range
             float nn = 1, s = 0, ww = 1, e = 0;
             for (const auto& p : hm.parts)
-                if (present(p))
+                if (hp_pts::present(p))
                     nn = std::min(nn, p.y), s = std::max(s, p.y), ww = std::min(ww, p.x), e = std::max(e, p.x);
             const float area = (e - ww) * (s - nn);
             float root = std::sqrt(area * (float)(w * h));
@@ -79,15 +70,7 @@ int build_primitives(const hp_human* humans, int n, int w, int h, int thickness,
         }
         int32_t px[HP_COCO_N_PARTS], py[HP_COCO_N_PARTS];
         bool ok[HP_COCO_N_PARTS];
-        for (int k = 0; k < HP_COCO_N_PARTS; ++k) {
-            const hp_body_part& p = hm.parts[k];
-            ok[k] = present(p);
-            if (ok[k]) {
-                const float fx = p.x * fw, fy = p.y * fh;
-                const bool in_x = to_pixel(fx, px[k]), in_y = to_pixel(fy, py[k]);
-                ok[k] = in_x && in_y;
-            }
-        }
+        hp_pts::part_points(hm, w, h, px, py, ok);
         auto emit = [&](int kind, int a, int b, int colour) {
             if (count < cap)
                 out[count] = hp_overlay_prim{ kind, px[a], py[a], px[b], py[b], t, colour, i };
@@ -286,19 +269,9 @@ __global__ __launch_bounds__(THREADS) void overlay_word16_kernel(const ovl_geom 
 
 struct hp_overlay {
     int max_humans = 0, cap = 0; // cap = max_humans * PRIMS_PER_HUMAN primitives per list
-    hp::host_buf stage[SLOTS];
-    hp::dev_buf list[SLOTS];
-    hipEvent_t done[SLOTS] = {};
-    bool used[SLOTS] = {};
-    int next = 0;
+    hp::staged_ring ring;        // cap hp_overlay_prim per slot
     bool hdr = false;       // hp_overlay_set_transfer: 10-bit frames are PQ / HLG and take hp_yuv_colours_hdr's table
     hp_hdr_desc transfer {};
-    ~hp_overlay()
-    {
-        for (auto& e : done)
-            if (e)
-                (void)hipEventDestroy(e);
-    }
 };
 
 namespace {
@@ -318,8 +291,7 @@ struct frame_desc {
 
 int check_common(const char* who, const char* name, int w, int h, const hp_human* humans, int n, float opacity, int thickness)
 {
-    HP_REQUIRE(w <= MAX_DIM && h <= MAX_DIM, HP_ERR_INVALID, "%s: %s: a frame of %d x %d is beyond the %d x %d the coverage arithmetic is stated for", who, name, w,
-        h, MAX_DIM, MAX_DIM);
+    HP_TRY(hp::check_max_dim(who, name, w, h));
     HP_REQUIRE(opacity > 0.f && opacity <= 1.f, HP_ERR_INVALID, "%s: %s: opacity %g is outside (0, 1]", who, name, (double)opacity);
     HP_REQUIRE(n >= 0 && (n == 0 || humans), HP_ERR_INVALID, "%s: %s: %d humans at a null pointer or a negative count", who, name, n);
     HP_REQUIRE(thickness <= MAX_T, HP_ERR_INVALID, "%s: %s: thickness %d is beyond %d", who, name, thickness, MAX_T);
@@ -328,9 +300,7 @@ int check_common(const char* who, const char* name, int w, int h, const hp_human
 
 int describe_bgr(frame_desc& f, const char* who, uint8_t* bgr, int w, int h, int stride, const hp_human* humans, int n, float opacity, int thickness)
 {
-    HP_REQUIRE(bgr, HP_ERR_INVALID, "%s: BGR: null frame", who);
-    HP_REQUIRE(w > 0 && h > 0, HP_ERR_INVALID, "%s: BGR: empty frame (%d x %d)", who, w, h);
-    HP_REQUIRE(stride > 0 && (int64_t)stride >= (int64_t)w * 3, HP_ERR_INVALID, "%s: BGR: stride %d is smaller than a row (%lld bytes)", who, stride, (long long)w * 3);
+    HP_TRY(hp::check_bgr_frame(who, bgr, w, h, stride));
     HP_TRY(check_common(who, "BGR", w, h, humans, n, opacity, thickness));
     f.bgr = true, f.w = w, f.h = h, f.base = bgr, f.stride = stride;
     bgr_colours(f.colours);
@@ -367,19 +337,17 @@ int draw_device(hp_overlay* o, const char* who, const frame_desc& f, const hp_hu
     HP_REQUIRE(n <= o->max_humans, HP_ERR_INVALID, "%s: %s: %d humans, the handle was created for %d", who, f.name, n, o->max_humans);
     if (n == 0)
         return HP_OK;
-    const int slot = o->next;
-    if (o->used[slot])
-        HP_HIP_TRY(hipEventSynchronize(o->done[slot])); // the use SLOTS calls ago
-    hp_overlay_prim* prims = o->stage[slot].as<hp_overlay_prim>();
+    hp_overlay_prim* prims; // built in the slot's pinned buffer: the slot is taken before there is a list
+    HP_TRY(o->ring.take(prims));
     const int count = build_primitives(humans, n, f.w, f.h, thickness, prims, o->cap);
     int x0, y0, x1, y1;
     if (count == 0 || !list_rect(prims, count, f.w, f.h, x0, y0, x1, y1))
         return HP_OK;
     for (int i = 0; i < count; ++i)
         prims[i].colour = pack_colour(f.colours[prims[i].colour]);
-    HP_HIP_TRY(hipMemcpyAsync(o->list[slot].p, prims, (size_t)count * sizeof(hp_overlay_prim), hipMemcpyHostToDevice, s));
+    HP_TRY(o->ring.upload((size_t)count * sizeof(hp_overlay_prim), s));
     ovl_geom g;
-    g.prims = o->list[slot].as<hp_overlay_prim>(), g.n_prims = count, g.w = f.w, g.h = f.h, g.sx = f.sx, g.sy = f.sy;
+    g.prims = o->ring.device<hp_overlay_prim>(), g.n_prims = count, g.w = f.w, g.h = f.h, g.sx = f.sx, g.sy = f.sy;
     g.bx0 = x0 >> f.sx, g.by0 = y0 >> f.sy, g.bx1 = x1 >> f.sx, g.by1 = y1 >> f.sy;
     g.weight = weight_of(opacity);
     const dim3 grid(hp::ceil_div(g.bx1 - g.bx0 + 1, TILE_W), hp::ceil_div(g.by1 - g.by0 + 1, TILE_H));
@@ -399,23 +367,14 @@ int draw_device(hp_overlay* o, const char* who, const frame_desc& f, const hp_hu
         fill_target(t, f);
         hipLaunchKernelGGL(overlay_planar8_kernel, grid, dim3(THREADS), 0, s, g, t);
     }
-    HP_HIP_TRY(hipGetLastError());
-    HP_HIP_TRY(hipEventRecord(o->done[slot], s));
-    o->used[slot] = true;
-    o->next = (slot + 1) % SLOTS;
-    return HP_OK;
+    return o->ring.commit(s);
 }
 
 // ---- host twin: the rules of overlay.hpp on a frame in host memory -------------------------------------------------------------------------
 
 void host_put(const frame_desc& f, uint8_t* q, int c, int w)
 {
-    if (f.sample_bytes == 2) { // bytewise: a host plane need not be aligned
-        const int word = q[0] | (q[1] << 8);
-        const int out = (w == 256 ? c : blend(c, (word >> f.shift) & 1023, w)) << f.shift;
-        q[0] = (uint8_t)(out & 255), q[1] = (uint8_t)(out >> 8);
-    } else
-        *q = (uint8_t)(w == 256 ? c : blend(c, *q, w));
+    hp_yuv::host_put(q, f.sample_bytes, f.shift, w == 256 ? c : blend(c, hp_yuv::host_get(q, f.sample_bytes, f.shift), w));
 }
 
 int draw_host(const frame_desc& f, const hp_human* humans, int n, float opacity, int thickness)
@@ -479,35 +438,14 @@ int hp_overlay_create(hp_overlay** out, int max_humans)
     HP_REQUIRE(out, HP_ERR_INVALID, "hp_overlay_create: null output");
     *out = nullptr;
     HP_REQUIRE(max_humans > 0 && max_humans <= (1 << 16), HP_ERR_INVALID, "hp_overlay_create: max_humans %d (1 .. 65536)", max_humans);
-    hp_overlay* o = new hp_overlay;
+    std::unique_ptr<hp_overlay> o(new hp_overlay); // a failed create frees what it allocated
     o->max_humans = max_humans, o->cap = max_humans * PRIMS_PER_HUMAN;
-    int rc = HP_OK;
-    for (int k = 0; k < SLOTS && rc == HP_OK; ++k) {
-        rc = o->stage[k].alloc((size_t)o->cap * sizeof(hp_overlay_prim));
-        if (rc == HP_OK)
-            rc = o->list[k].alloc((size_t)o->cap * sizeof(hp_overlay_prim));
-        if (rc == HP_OK && hipEventCreateWithFlags(&o->done[k], hipEventDisableTiming) != hipSuccess) {
-            hp::set_error("hp_overlay_create: hipEventCreateWithFlags failed");
-            rc = HP_ERR_HIP;
-        }
-    }
-    if (rc != HP_OK) {
-        delete o;
-        return rc;
-    }
-    *out = o;
+    HP_TRY(o->ring.alloc((size_t)o->cap * sizeof(hp_overlay_prim), "hp_overlay_create"));
+    *out = o.release();
     return HP_OK;
 }
 
-void hp_overlay_destroy(hp_overlay* o)
-{
-    if (!o)
-        return;
-    for (int k = 0; k < SLOTS; ++k)
-        if (o->used[k])
-            (void)hipEventSynchronize(o->done[k]);
-    delete o;
-}
+void hp_overlay_destroy(hp_overlay* o) { delete o; } // the ring drains first
 
 int hp_overlay_primitives(const hp_human* humans, int n, int w, int h, int thickness, hp_overlay_prim* out, int cap)
 {

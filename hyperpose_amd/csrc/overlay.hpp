@@ -7,11 +7,11 @@
 // Primitive list (build_primitives, host only, fp32 without fused operations).  For a W x H frame and humans h = 0..n-1 in order, each human
 // contributes its limbs pair_id = 0..18 (COCO_PAIRS, colour pair_id), each where both parts are present, as a CAPSULE, then its parts 0..17
 // (colour = part index), each present one, as a DISC.  A part is present when has_value != 0 and x and y are finite.  End points and centres
-// are int(p.x * W), int(p.y * H) in fp32 - what draw_human computes.  Thickness T = the caller's `thickness` when > 0, else the reference's rule
+// are int(p.x * W), int(p.y * H) in fp32 - what draw_human computes (hp_pts::part_points, part_points.hpp, states both).  Thickness T = the caller's `thickness` when > 0, else the reference's rule
 // (src/human.cpp:7-39) per human: T = max(1, int(sqrtf((e - w) * (s - n) * (W * H))) / 32) over the present parts, n = min(1, y..), s = max(0, y..),
 // w = min(1, x..), e = max(0, x..); the square root is capped at 32 * MAX_T before the cast, so T <= MAX_T.
 //
-// Range limit.  W, H <= MAX_DIM = 8192.  A primitive with an end point outside [COORD_MIN, COORD_MAX] = [-8192, 16383] is dropped: such a point
+// Range limit (the constants: part_points.hpp).  W, H <= MAX_DIM = 8192.  A primitive with an end point outside [COORD_MIN, COORD_MAX] = [-8192, 16383] is dropped: such a point
 // is more than a frame away from the picture.  With pixels in [0, 8191] every difference below is at most 24575 < 2^14.6 in magnitude, so
 // |cross| < 2^30.2, 4 * cross^2 < 2^62.4 < 2^63, and T^2 * L <= 2^28 * 2^30.2 < 2^63: everything fits signed 64 bits.
 //
@@ -30,7 +30,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "../../include/hp_hip.h"
+#include "part_points.hpp"
 
 #if defined(__HIPCC__)
 #define HP_OVL_HD __host__ __device__ inline __attribute__((always_inline))
@@ -40,8 +40,9 @@
 
 namespace hp_ovl {
 
-constexpr int MAX_DIM = 8192;
-constexpr int COORD_MIN = -8192, COORD_MAX = 16383;
+using hp_pts::COORD_MAX;
+using hp_pts::COORD_MIN;
+using hp_pts::MAX_DIM;
 constexpr int MAX_T = 16384;
 constexpr int PRIMS_PER_HUMAN = HP_COCO_N_PAIRS + HP_COCO_N_PARTS; // 37
 constexpr int KIND_CAPSULE = 0, KIND_DISC = 1;

@@ -20,19 +20,20 @@
 //     redact_kernel<1>         16     41        0          0             8
 //     redact_kernel<2>         16     43        0          0             8
 //
-// The list reaches the device through the handle (hp_redact), as for hp_overlay: SLOTS pinned staging buffers and as many device lists, used in
-// turn.  A call copies the regions into the next pinned slot, enqueues one hipMemcpyAsync and the kernel on the caller's stream and records the
-// slot's event; it waits (on the host) only if that slot's use SLOTS calls ago has not finished.
+// The list reaches the device through the handle (hp_redact), as for hp_overlay: an hp::staged_ring (annotate.hpp).  A call that has work takes
+// the next slot, copies the regions into its pinned buffer, enqueues one hipMemcpyAsync and the kernel on the caller's stream and commits the
+// slot; it waits (on the host) only if that slot's use SLOTS calls ago has not finished.  The frame checks both annotators make are there too.
+#include "annotate.hpp"
 #include "redact.hpp"
-#include "yuv_formats.hpp"
 
 #include <algorithm>
+#include <memory>
 
 namespace {
 
 using namespace hp_red;
 
-constexpr int WAVES = 4, THREADS = WAVES * 64, SLOTS = 4;
+constexpr int WAVES = 4, THREADS = WAVES * 64;
 
 struct red_geom {
     const hp_redact_region* regs;
@@ -143,17 +144,7 @@ template <int SAMPLE_BYTES> __global__ __launch_bounds__(THREADS) void redact_ke
 
 struct hp_redact {
     int max_regions = 0;
-    hp::host_buf stage[SLOTS];
-    hp::dev_buf list[SLOTS];
-    hipEvent_t done[SLOTS] = {};
-    bool used[SLOTS] = {};
-    int next = 0;
-    ~hp_redact()
-    {
-        for (auto& e : done)
-            if (e)
-                (void)hipEventDestroy(e);
-    }
+    hp::staged_ring ring; // max_regions hp_redact_region per slot
 };
 
 namespace {
@@ -162,8 +153,7 @@ namespace {
 
 int check_call(const char* who, const char* name, int w, int h, const hp_redact_region* regs, int n, int effect, int cell)
 {
-    HP_REQUIRE(w <= MAX_DIM && h <= MAX_DIM, HP_ERR_INVALID, "%s: %s: a frame of %d x %d is beyond the %d x %d the coverage arithmetic is stated for", who, name, w,
-        h, MAX_DIM, MAX_DIM);
+    HP_TRY(hp::check_max_dim(who, name, w, h));
     HP_REQUIRE(cell_ok(cell), HP_ERR_INVALID, "%s: %s: cell %d is not an even number in [%d, %d]", who, name, cell, MIN_CELL, MAX_CELL);
     HP_REQUIRE(effect == HP_REDACT_PIXELATE || effect == HP_REDACT_BLACK, HP_ERR_INVALID, "%s: %s: unknown effect %d", who, name, effect);
     HP_REQUIRE(n >= 0 && (n == 0 || regs), HP_ERR_INVALID, "%s: %s: %d regions at a null pointer or a negative count", who, name, n);
@@ -177,9 +167,7 @@ int check_call(const char* who, const char* name, int w, int h, const hp_redact_
 
 int frame_bgr(frame& f, const char* who, uint8_t* bgr, int w, int h, int stride, const hp_redact_region* regs, int n, int effect, int cell)
 {
-    HP_REQUIRE(bgr, HP_ERR_INVALID, "%s: BGR: null frame", who);
-    HP_REQUIRE(w > 0 && h > 0, HP_ERR_INVALID, "%s: BGR: empty frame (%d x %d)", who, w, h);
-    HP_REQUIRE(stride > 0 && (int64_t)stride >= (int64_t)w * 3, HP_ERR_INVALID, "%s: BGR: stride %d is smaller than a row (%lld bytes)", who, stride, (long long)w * 3);
+    HP_TRY(hp::check_bgr_frame(who, bgr, w, h, stride));
     HP_TRY(check_call(who, "BGR", w, h, regs, n, effect, cell));
     describe_bgr(f, bgr, w, h, stride);
     return HP_OK;
@@ -191,7 +179,7 @@ int frame_yuv(frame& f, const char*& name, const char* who, const hp_yuv_image* 
     const hp_yuv::layout& l = *hp_yuv::layout_of(im->format);
     name = l.name;
     HP_TRY(check_call(who, l.name, im->width, im->height, regs, n, effect, cell));
-    describe_yuv(f, *im, l.planes, l.sample_bytes, l.sx, l.sy, l.shift);
+    describe_yuv(f, *im);
     return HP_OK;
 }
 
@@ -202,13 +190,11 @@ int redact_device(hp_redact* r, const char* who, const char* name, const frame& 
     int cy1;
     if (n == 0 || !cell_rect(regs, n, f.w, f.h, cell, g.cx0, g.cy0, g.cx1, cy1))
         return HP_OK;
-    const int slot = r->next;
-    if (r->used[slot])
-        HP_HIP_TRY(hipEventSynchronize(r->done[slot])); // the use SLOTS calls ago
-    hp_redact_region* staged = r->stage[slot].as<hp_redact_region>();
+    hp_redact_region* staged;
+    HP_TRY(r->ring.take(staged));
     std::copy(regs, regs + n, staged);
-    HP_HIP_TRY(hipMemcpyAsync(r->list[slot].p, staged, (size_t)n * sizeof(hp_redact_region), hipMemcpyHostToDevice, s));
-    g.regs = r->list[slot].as<hp_redact_region>(), g.n_regs = n, g.w = f.w, g.h = f.h, g.cell = cell, g.effect = effect;
+    HP_TRY(r->ring.upload((size_t)n * sizeof(hp_redact_region), s));
+    g.regs = r->ring.device<hp_redact_region>(), g.n_regs = n, g.w = f.w, g.h = f.h, g.cell = cell, g.effect = effect;
     g.n_spans = f.n_spans, g.shift = f.shift;
     for (int k = 0; k < 3; ++k)
         g.s[k] = k < f.n_spans ? f.s[k] : span{}, g.black[k] = f.black[k];
@@ -217,11 +203,7 @@ int redact_device(hp_redact* r, const char* who, const char* name, const frame& 
         hipLaunchKernelGGL(redact_kernel<2>, grid, dim3(THREADS), 0, s, g);
     else
         hipLaunchKernelGGL(redact_kernel<1>, grid, dim3(THREADS), 0, s, g);
-    HP_HIP_TRY(hipGetLastError());
-    HP_HIP_TRY(hipEventRecord(r->done[slot], s));
-    r->used[slot] = true;
-    r->next = (slot + 1) % SLOTS;
-    return HP_OK;
+    return r->ring.commit(s);
 }
 
 } // namespace
@@ -235,35 +217,14 @@ int hp_redact_create(hp_redact** out, int max_regions)
     HP_REQUIRE(out, HP_ERR_INVALID, "hp_redact_create: null output");
     *out = nullptr;
     HP_REQUIRE(max_regions > 0 && max_regions <= (1 << 20), HP_ERR_INVALID, "hp_redact_create: max_regions %d (1 .. 1048576)", max_regions);
-    hp_redact* r = new hp_redact;
+    std::unique_ptr<hp_redact> r(new hp_redact); // a failed create frees what it allocated
     r->max_regions = max_regions;
-    int rc = HP_OK;
-    for (int k = 0; k < SLOTS && rc == HP_OK; ++k) {
-        rc = r->stage[k].alloc((size_t)max_regions * sizeof(hp_redact_region));
-        if (rc == HP_OK)
-            rc = r->list[k].alloc((size_t)max_regions * sizeof(hp_redact_region));
-        if (rc == HP_OK && hipEventCreateWithFlags(&r->done[k], hipEventDisableTiming) != hipSuccess) {
-            hp::set_error("hp_redact_create: hipEventCreateWithFlags failed");
-            rc = HP_ERR_HIP;
-        }
-    }
-    if (rc != HP_OK) {
-        delete r;
-        return rc;
-    }
-    *out = r;
+    HP_TRY(r->ring.alloc((size_t)max_regions * sizeof(hp_redact_region), "hp_redact_create"));
+    *out = r.release();
     return HP_OK;
 }
 
-void hp_redact_destroy(hp_redact* r)
-{
-    if (!r)
-        return;
-    for (int k = 0; k < SLOTS; ++k)
-        if (r->used[k])
-            (void)hipEventSynchronize(r->done[k]);
-    delete r;
-}
+void hp_redact_destroy(hp_redact* r) { delete r; } // the ring drains first
 
 int hp_redact_regions(const hp_human* humans, int n, int w, int h, int what, float margin, hp_redact_region* out, int cap)
 {

@@ -2,14 +2,15 @@
 // of the frame a region reaches and what a reached cell becomes.  Shared by the kernels and the host twins (redact.hip) and quoted by DESIGN.md
 // 1.1 "Redaction"; the tests restate it in numpy with Python integers (tests/redact_ref.py).  Everything past the part points is exact integer
 // arithmetic, so the GPU, the host twin and the tests agree byte for byte.  The host side (everything but the kernels) needs nothing but
-// hp_hip.h and compiles with a plain C++ compiler: tests/cpp/redact_rules.cpp runs it under sanitizers on planes allocated with no slack.
+// hp_hip.h and the two pure headers beside it - part_points.hpp (the part-point rule and the coordinate limits) and yuv_formats.hpp (the layouts) -
+// and compiles with a plain C++ compiler: tests/cpp/redact_rules.cpp runs it under sanitizers on planes allocated with no slack.
 //
 // Regions.  RECT covers the pixels of [x0, x1] x [y0, y1], inclusive (x0 <= x1, y0 <= y1); DISC has centre (x0, y0) and radius x1 >= 0, y1 == 0.
-// Coordinates lie in [COORD_MIN, COORD_MAX] = [-8192, 16383] and radii in [0, MAX_R = 16384] - the overlay's ranges (overlay.hpp) - so with
+// Coordinates lie in [COORD_MIN, COORD_MAX] = [-8192, 16383] (part_points.hpp) and radii in [0, MAX_R = 16384] - the overlay's ranges - so with
 // pixels in [0, 8191] every difference is below 2^15 in magnitude and every sum of two squares below 2^31: int64 holds all of it.
 //
-// Region list (build_regions, host only, fp32 without fused operations).  A part's point is (int)(x * (float)W), (int)(y * (float)H), as in
-// overlay.hip's build_primitives; it is present when has_value != 0, x and y are finite and both coordinates lie in [COORD_MIN, COORD_MAX].
+// Region list (build_regions, host only, fp32 without fused operations).  A part's point, and whether it counts ("present" below), is
+// hp_pts::part_points' px, py and ok (part_points.hpp): has_value != 0, x and y finite, both coordinates in [COORD_MIN, COORD_MAX].
 // m = nearbyint(margin * 256) for margin in (0, 8].  Per human, in order:
 //   head disc   F = the present parts among {0, 14, 15, 16, 17} (nose, eyes, ears); none: no disc.  lo, hi = the bounding box of F; centre
 //               (floor((lo_x + hi_x) / 2), floor((lo_y + hi_y) / 2)); e = max(hi_x - lo_x, hi_y - lo_y); nk = isqrt(|p1 - p0|^2) when neck and
@@ -37,7 +38,8 @@
 #include <cmath>
 #include <stdint.h>
 
-#include "../../include/hp_hip.h"
+#include "part_points.hpp"
+#include "yuv_formats.hpp"
 
 #if defined(__HIPCC__)
 #define HP_RED_HD __host__ __device__ inline __attribute__((always_inline))
@@ -47,8 +49,9 @@
 
 namespace hp_red {
 
-constexpr int MAX_DIM = 8192;
-constexpr int COORD_MIN = -8192, COORD_MAX = 16383;
+using hp_pts::COORD_MAX;
+using hp_pts::COORD_MIN;
+using hp_pts::MAX_DIM;
 constexpr int MAX_R = 16384;
 constexpr int MIN_CELL = 2, MAX_CELL = 128;
 constexpr int FACE_PARTS[5] = { 0, 14, 15, 16, 17 };
@@ -145,7 +148,6 @@ inline int clamp_coord(int64_t v) { return (int)(v < COORD_MIN ? COORD_MIN : v >
 inline int build_regions(const hp_human* humans, int n, int w, int h, int what, float margin, hp_redact_region* out, int cap)
 {
     const int64_t m = (int64_t)std::nearbyint((double)margin * 256.);
-    const float fw = (float)w, fh = (float)h;
     int count = 0;
     auto emit = [&](const hp_redact_region& g) {
         if (count < cap)
@@ -155,16 +157,7 @@ inline int build_regions(const hp_human* humans, int n, int w, int h, int what, 
     for (int i = 0; i < n; ++i) {
         int32_t px[HP_COCO_N_PARTS], py[HP_COCO_N_PARTS];
         bool ok[HP_COCO_N_PARTS];
-        for (int k = 0; k < HP_COCO_N_PARTS; ++k) {
-            const hp_body_part& p = humans[i].parts[k];
-            ok[k] = p.has_value != 0 && std::isfinite(p.x) && std::isfinite(p.y);
-            if (!ok[k])
-                continue;
-            const float fx = p.x * fw, fy = p.y * fh;
-            ok[k] = fx > (float)(COORD_MIN - 1) && fx < (float)(COORD_MAX + 1) && fy > (float)(COORD_MIN - 1) && fy < (float)(COORD_MAX + 1);
-            if (ok[k])
-                px[k] = (int32_t)fx, py[k] = (int32_t)fy;
-        }
+        hp_pts::part_points(humans[i], w, h, px, py, ok);
         if (what == HP_REDACT_BODY) {
             box all;
             for (int k = 0; k < HP_COCO_N_PARTS; ++k)
@@ -220,22 +213,28 @@ inline void describe_bgr(frame& f, uint8_t* bgr, int w, int h, int stride)
     f.s[0] = span{ bgr, stride, 0, 0, 3, 0 | (1 << 2) | (2 << 4) };
 }
 
-// `planes`, `sample_bytes`, `sx`, `sy`, `shift`: the layout's entry of hp_yuv::layout_of (yuv_formats.hpp); the image has been validated
-inline void describe_yuv(frame& f, const hp_yuv_image& im, int planes, int sample_bytes, int sx, int sy, int shift)
+// The image has been validated.  One span per memory plane, from the layout's entry and its sample map (yuv_formats.hpp): a block of a plane
+// is what lies between two chroma samples of it (a luma plane: between two luma samples), and a sample's channel is read off where the map
+// puts the first Y (and every y_step bytes after it), U and V sample - no format is named here.
+inline void describe_yuv(frame& f, const hp_yuv_image& im)
 {
+    const hp_yuv::layout& l = *hp_yuv::layout_of(im.format);
+    const hp_yuv::sample_map m = hp_yuv::map_samples(im, l);
+    const int sb = l.sample_bytes;
+    const bool packed = l.planes == 1;
     f = frame();
-    f.w = im.width, f.h = im.height, f.sample_bytes = sample_bytes, f.shift = shift, f.n_spans = planes;
-    uint8_t *p0 = (uint8_t*)im.plane[0], *p1 = (uint8_t*)im.plane[1], *p2 = (uint8_t*)im.plane[2];
-    if (planes == 1) // YUY2: Y0 U Y1 V; UYVY: U Y0 V Y1
-        f.s[0] = span{ p0, im.stride[0], sx, sy, 4, im.format == HP_YUV_YUY2 ? (0 | (1 << 2) | (0 << 4) | (2 << 6)) : (1 | (0 << 2) | (2 << 4) | (0 << 6)) };
-    else {
-        f.s[0] = span{ p0, im.stride[0], 0, 0, 1, 0 };
-        if (planes == 2)
-            f.s[1] = span{ p1, im.stride[1], sx, sy, 2, 1 | (2 << 2) };
-        else
-            f.s[1] = span{ p1, im.stride[1], sx, sy, 1, 1 }, f.s[2] = span{ p2, im.stride[2], sx, sy, 1, 2 };
-    }
-    const int d = sample_bytes == 2 ? 10 : 8;
+    f.w = im.width, f.h = im.height, f.sample_bytes = sb, f.shift = l.shift, f.n_spans = l.planes;
+    f.s[0] = span{ (uint8_t*)im.plane[0], im.stride[0], packed ? l.sx : 0, packed ? l.sy : 0, (packed ? m.c_step : m.y_step) / sb, 0 };
+    for (int k = 1; k < l.planes; ++k)
+        f.s[k] = span{ (uint8_t*)im.plane[k], im.stride[k], l.sx, l.sy, m.c_step / sb, 0 };
+    auto mark = [&](span& s, const uint8_t* at, int channel) {
+        const int q = (int)(at - s.base) / sb;
+        s.pat = (s.pat & ~(3 << (2 * q))) | (channel << (2 * q));
+    };
+    for (int at = 0; at < f.s[0].k * sb; at += m.y_step)
+        mark(f.s[0], m.y + at, 0);
+    mark(f.s[l.planes > 1], m.u, 1), mark(f.s[l.planes - 1], m.v, 2);
+    const int d = sb == 2 ? 10 : 8;
     f.black[0] = im.range == HP_YUV_LIMITED ? 16 << (d - 8) : 0, f.black[1] = f.black[2] = 1 << (d - 1);
 }
 
@@ -255,20 +254,7 @@ HP_RED_HD int channel_of(const span& s, int j)
 
 // ---- host twin ----------------------------------------------------------------------------------------------------------------------------------
 
-inline int host_get(const frame& f, const uint8_t* q)
-{
-    return f.sample_bytes == 2 ? ((q[0] | (q[1] << 8)) >> f.shift) & 1023 : q[0]; // bytewise: a host plane need not be aligned
-}
-inline void host_put(const frame& f, uint8_t* q, int v)
-{
-    if (f.sample_bytes == 2) {
-        const int word = v << f.shift;
-        q[0] = (uint8_t)(word & 255), q[1] = (uint8_t)(word >> 8);
-    } else
-        q[0] = (uint8_t)v;
-}
-
-// the arguments have been checked (regions, effect, cell)
+// the arguments have been checked (regions, effect, cell); samples are read and written bytewise (hp_yuv::host_get / host_put)
 inline void paint_host(const frame& f, const hp_redact_region* regs, int n, int effect, int cell)
 {
     int cx0, cy0, cx1, cy1;
@@ -291,7 +277,7 @@ inline void paint_host(const frame& f, const hp_redact_region* regs, int n, int 
                     for (int r = r0; r <= r1; ++r)
                         for (int j = j0; j < j1; ++j) {
                             const int c = channel_of(f.s[k], j);
-                            sum[c] += host_get(f, f.s[k].base + (size_t)r * f.s[k].stride + (size_t)j * f.sample_bytes), ++cnt[c];
+                            sum[c] += hp_yuv::host_get(f.s[k].base + (size_t)r * f.s[k].stride + (size_t)j * f.sample_bytes, f.sample_bytes, f.shift), ++cnt[c];
                         }
                 }
                 for (int c = 0; c < 3; ++c)
@@ -302,7 +288,7 @@ inline void paint_host(const frame& f, const hp_redact_region* regs, int n, int 
                 cell_of_span(f.s[k], X0, Y0, X1, Y1, r0, r1, j0, j1);
                 for (int r = r0; r <= r1; ++r)
                     for (int j = j0; j < j1; ++j)
-                        host_put(f, f.s[k].base + (size_t)r * f.s[k].stride + (size_t)j * f.sample_bytes, value[channel_of(f.s[k], j)]);
+                        hp_yuv::host_put(f.s[k].base + (size_t)r * f.s[k].stride + (size_t)j * f.sample_bytes, f.sample_bytes, f.shift, value[channel_of(f.s[k], j)]);
             }
         }
 }

@@ -100,9 +100,6 @@ void tables(const hp_hdr_desc& d, uint16_t lin[LIN_N], int32_t m[9], uint8_t out
         out[j] = (uint8_t)std::rint(255. * srgb_oetf((16 * j + 7.5) / 65535.));
 }
 
-// a 16-bit little-endian word at any address (host frames are not held to the kernels' alignment rule)
-inline int word_at(const uint8_t* p) { return p[0] | (p[1] << 8); }
-
 } // namespace
 
 int hp_hdr::check_desc(const hp_hdr_desc* d, const char* who)
@@ -151,8 +148,8 @@ int hp_tonemap_convert_host(const hp_yuv_image* f, const hp_hdr_desc* d, uint8_t
     for (int y = 0; y < f->height; ++y)
         for (int x = 0; x < f->width; ++x) {
             const size_t at = (size_t)(y >> l.sy) * s.c_stride + (size_t)(x >> l.sx) * s.c_step;
-            const int Y = (word_at(s.y + (size_t)y * s.y_stride + (size_t)x * s.y_step) >> l.shift) & 1023;
-            const int U = (word_at(s.u + at) >> l.shift) & 1023, V = (word_at(s.v + at + (ptrdiff_t)(y >> l.sy) * s.v_extra) >> l.shift) & 1023;
+            const int Y = hp_yuv::host_get(s.y + (size_t)y * s.y_stride + (size_t)x * s.y_step, 2, l.shift); // bytewise: any address
+            const int U = hp_yuv::host_get(s.u + at, 2, l.shift), V = hp_yuv::host_get(s.v + at + (ptrdiff_t)(y >> l.sy) * s.v_extra, 2, l.shift);
             int c[3];
             convert(Y, U - k[1], V - k[1], k[0], k[2], k[3], k[4], k[5], k[6], lin.data(), m, d->to_bt709 != 0, out.data(), c);
             uint8_t* px = bgr + (size_t)y * stride + (size_t)x * 3;

@@ -1,8 +1,13 @@
 // yuv_formats.hpp — the ONE host-side description of the video layouts hp_yuv_image names (include/hp_hip.h): how many planes a format
 // has, how wide a sample is, how its chroma is sub-sampled and how many bytes a row of each plane holds.  Shared by the front-end
-// (resize_yuv_formats.hip: argument checks and the kernel's addressing) and the pipeline (pipeline.cpp: packing a frame's planes for upload).
+// (resize_yuv_formats.hip: argument checks and the kernel's addressing), the pipeline (pipeline.cpp: packing a frame's planes for upload), the
+// units that write into frames (overlay.hip, redact.hpp) and the HDR host twin (tonemap.cpp).  Pure: it needs nothing but hp_hip.h and the
+// standard headers and compiles with a plain C++ compiler (tests/cpp/redact_rules.cpp uses it so); `validate` is only declared here.
 #pragma once
-#include "hp_common.hpp"
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/hp_hip.h"
 
 namespace hp_yuv {
 
@@ -42,7 +47,7 @@ inline int rows(const layout& l, int k, int h) { return k == 0 ? h : h >> l.sy; 
 // plane), the row strides, and the steps between horizontally neighbouring samples.  Luma pixel (x, y) is at y + y * y_stride + x * y_step,
 // its chroma at u | v + (y >> sy) * c_stride + (x >> sx) * c_step (the V plane of a planar frame: + (y >> sy) * v_extra, its own pitch).
 // The one statement of "YUY2 is Y0 U Y1 V, UYVY is U Y0 V Y1, semi-planar pairs are (U, V)": the resize kernels read through it
-// (resize_yuv_formats.hip) and the overlay kernels write through it (overlay.hip).
+// (resize_yuv_formats.hip), the overlay kernels write through it (overlay.hip) and the redaction derives its channel patterns from it (redact.hpp).
 struct sample_map {
     const uint8_t *y, *u, *v;
     int y_stride, c_stride, v_extra;
@@ -65,6 +70,18 @@ inline sample_map map_samples(const hp_yuv_image& im, const layout& l)
         m.c_stride = im.stride[1], m.y_step = l.sample_bytes, m.c_step = l.sample_bytes, m.v_extra = im.stride[2] - im.stride[1];
     }
     return m;
+}
+
+// One sample of a frame in HOST memory, read and written bytewise: a host plane is not held to the kernels' alignment rule.  16-bit samples are
+// little-endian words holding value << shift (the value is (word >> shift) & 1023; the bits outside it are stored as zero).
+inline int host_get(const uint8_t* q, int sample_bytes, int shift) { return sample_bytes == 2 ? ((q[0] | (q[1] << 8)) >> shift) & 1023 : q[0]; }
+inline void host_put(uint8_t* q, int sample_bytes, int shift, int v)
+{
+    if (sample_bytes == 2) {
+        const int word = v << shift;
+        q[0] = (uint8_t)(word & 255), q[1] = (uint8_t)(word >> 8);
+    } else
+        q[0] = (uint8_t)v;
 }
 
 // format, matrix, range, size, planes and strides of one image; `who` starts the message.  HP_OK or HP_ERR_INVALID (message set).

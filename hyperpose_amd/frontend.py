@@ -151,6 +151,54 @@ def yuv_size_of_planes(fmt: str, planes):
     return (cols // 2 if YUV_LAYOUTS[fmt][1] == 1 else cols), rows
 
 
+def _host_image(frame_planes, fmt: str, matrix: str, range: str, written: bool = False) -> YuvImage:
+    """The ``hp_yuv_image`` of a frame in HOST memory given as its list of 2-D plane arrays: rows may be padded (views of wider arrays),
+    samples must be contiguous within a row; ``written``: the call paints into the planes."""
+    for p in frame_planes:
+        assert p.ndim == 2 and p.strides[1] == p.itemsize and (p.flags.writeable or not written)
+    w, h = yuv_size_of_planes(fmt, frame_planes)
+    return yuv_image(fmt, [p.ctypes.data for p in frame_planes], [p.strides[0] for p in frame_planes], w, h, matrix, range)
+
+
+def _host_bgr(frame):
+    """(address, w, h, stride in bytes) of a writeable uint8 [h, w, 3] frame in HOST memory whose rows may be padded"""
+    assert frame.dtype == np.uint8 and frame.ndim == 3 and frame.shape[2] == 3 and frame.strides[1:] == (3, 1) and frame.flags.writeable
+    return C.c_void_p(frame.ctypes.data), frame.shape[1], frame.shape[0], frame.strides[0]
+
+
+class _Handle:
+    """One handle of the C ABI: ``self.h`` is made by ``hp_<NAME>_create(&h, *args)`` and given back to ``hp_<NAME>_destroy`` by ``close``
+    or when the object is collected."""
+    NAME = ""
+
+    def __init__(self, *args):
+        self.h = C.c_void_p()
+        check(getattr(lib(), f"hp_{self.NAME}_create")(C.byref(self.h), *args))
+
+    def close(self):
+        if self.h:
+            getattr(lib(), f"hp_{self.NAME}_destroy")(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_default_handles = {}
+
+
+def _default_handle(cls, floor: int, n: int):
+    """This module's own handle of class ``cls`` (an ``Overlay``, a ``Redactor``), made anew when a call brings more than it holds"""
+    held = _default_handles.get(cls)
+    if held is None or held[1] < n:
+        cap = max(floor, n)
+        held = _default_handles[cls] = (cls(cap), cap)
+    return held[0]
+
+
 def yuv_upload(planes, fmt: str, pitch=0, fill: int = 0xA5):
     """Device copy of a frame's planes, each in a ``DevBuf`` of its own with rows ``pitch`` bytes longer than the picture's (the padding
     holds ``fill``), as a decoder surface has them; ``pitch`` is one number or one per plane (the U and the V plane of a planar frame may
@@ -206,37 +254,23 @@ def tonemap_tables(transfer: str = "pq", to_bt709: bool = True, peak_nits: float
     return lin, m, out
 
 
-class Tonemap:
+class Tonemap(_Handle):
     """``hp_tonemap``: the tables of one description in device memory, what ``resize_yuv(..., tonemap=)`` and ``resize_rois(..., tonemap=)`` take."""
+    NAME = "tonemap"
 
     def __init__(self, transfer: str = "pq", to_bt709: bool = True, peak_nits: float = HDR_DEFAULT_PEAK, white_nits: float = HDR_DEFAULT_WHITE):
-        self.h = C.c_void_p()
         self.desc = hdr_desc(transfer, to_bt709, peak_nits, white_nits)
-        check(lib().hp_tonemap_create(C.byref(self.h), C.byref(self.desc)))
-
-    def close(self):
-        if self.h:
-            lib().hp_tonemap_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(C.byref(self.desc))
 
 
 def tonemap_host(frame_planes, fmt: str, matrix: str = "bt2020", range: str = "limited", transfer: str = "pq", to_bt709: bool = True,
                  peak_nits: float = HDR_DEFAULT_PEAK, white_nits: float = HDR_DEFAULT_WHITE) -> np.ndarray:
     """``hp_tonemap_convert_host``: a P010 / I010 frame in host memory (its list of 2-D plane arrays; rows may be padded) -> [h, w, 3] uint8 BGR,
     no device needed."""
-    for p in frame_planes:
-        assert p.ndim == 2 and p.strides[1] == p.itemsize
-    w, h = yuv_size_of_planes(fmt, frame_planes)
-    im = yuv_image(fmt, [p.ctypes.data for p in frame_planes], [p.strides[0] for p in frame_planes], w, h, matrix, range)
+    im = _host_image(frame_planes, fmt, matrix, range)
     d = hdr_desc(transfer, to_bt709, peak_nits, white_nits)
-    out = np.empty((h, w, 3), np.uint8)
-    check(lib().hp_tonemap_convert_host(C.byref(im), C.byref(d), out.ctypes.data_as(C.c_void_p), w * 3))
+    out = np.empty((im.height, im.width, 3), np.uint8)
+    check(lib().hp_tonemap_convert_host(C.byref(im), C.byref(d), out.ctypes.data_as(C.c_void_p), im.width * 3))
     return out
 
 
@@ -504,13 +538,13 @@ def yuv_colours(matrix: str = "bt601", range: str = "limited", depth: int = 8) -
     return out
 
 
-class Overlay:
+class Overlay(_Handle):
     """``hp_overlay``: the handle the device entry points draw through (pinned staging slots and device lists for ``max_humans`` per call)."""
+    NAME = "overlay"
 
     def __init__(self, max_humans: int = 64):
-        self.h = C.c_void_p()
         self.max_humans = int(max_humans)
-        check(lib().hp_overlay_create(C.byref(self.h), self.max_humans))
+        super().__init__(self.max_humans)
 
     def set_transfer(self, transfer=None, to_bt709: bool = True, peak_nits: float = HDR_DEFAULT_PEAK, white_nits: float = HDR_DEFAULT_WHITE) -> None:
         """``hp_overlay_set_transfer``: 10-bit frames drawn through this handle are "pq" / "hlg" frames and get ``yuv_colours_hdr``'s colours;
@@ -518,34 +552,13 @@ class Overlay:
         d = None if transfer is None else hdr_desc(transfer, to_bt709, peak_nits, white_nits)
         check(lib().hp_overlay_set_transfer(self.h, C.byref(d) if d is not None else None))
 
-    def close(self):
-        if self.h:
-            lib().hp_overlay_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-_overlay = None
-
-
-def _default_overlay(n: int) -> Overlay:
-    global _overlay
-    if _overlay is None or _overlay.max_humans < n:
-        _overlay = Overlay(max(64, n))
-    return _overlay
-
 
 def draw_humans(target, humans, opacity: float = 1.0, thickness: int = 0, w=None, h=None, stride=None, stream=None, overlay=None) -> None:
     """Paint the skeletons of ``humans`` (HUMAN_DTYPE, in the frame's normalised coordinates) into a frame in DEVICE memory, in place and
     stream-ordered: ``target`` is a ``YuvImage`` whose planes are device pointers (``hp_overlay_draw_yuv``) or a device buffer of 8-bit BGR
     with ``w``, ``h`` and optionally ``stride`` in bytes (``hp_overlay_draw_u8c3``)."""
     hs = _humans(humans)
-    ov = overlay or _default_overlay(len(hs))
+    ov = overlay or _default_handle(Overlay, 64, len(hs))
     hp, s = hs.ctypes.data_as(C.POINTER(Human)), C.c_void_p(stream) if stream else None
     if isinstance(target, YuvImage):
         check(lib().hp_overlay_draw_yuv(ov.h, C.byref(target), hp, len(hs), C.c_float(opacity), int(thickness), s))
@@ -561,14 +574,9 @@ def draw_humans_host(frame, humans, fmt=None, matrix: str = "bt601", range: str 
     hs = _humans(humans)
     hp = hs.ctypes.data_as(C.POINTER(Human))
     if fmt is None:
-        assert frame.dtype == np.uint8 and frame.ndim == 3 and frame.shape[2] == 3 and frame.strides[1:] == (3, 1) and frame.flags.writeable
-        check(lib().hp_overlay_draw_u8c3_host(C.c_void_p(frame.ctypes.data), frame.shape[1], frame.shape[0], frame.strides[0], hp, len(hs),
-                                              C.c_float(opacity), int(thickness)))
+        check(lib().hp_overlay_draw_u8c3_host(*_host_bgr(frame), hp, len(hs), C.c_float(opacity), int(thickness)))
         return
-    for p in frame:
-        assert p.ndim == 2 and p.strides[1] == p.itemsize and p.flags.writeable
-    w, h = yuv_size_of_planes(fmt, frame)
-    im = yuv_image(fmt, [p.ctypes.data for p in frame], [p.strides[0] for p in frame], w, h, matrix, range)
+    im = _host_image(frame, fmt, matrix, range, written=True)
     if hdr is not None:  # an ``hdr_desc``: the frame is PQ / HLG (``hp_overlay_draw_yuv_host_hdr``)
         check(lib().hp_overlay_draw_yuv_host_hdr(C.byref(im), C.byref(hdr), hp, len(hs), C.c_float(opacity), int(thickness)))
         return
@@ -591,34 +599,13 @@ def redact_regions(humans, w: int, h: int, what: str = "head", margin: float = 1
     return out[:n]
 
 
-class Redactor:
+class Redactor(_Handle):
     """``hp_redact``: the handle the device entry points work through (pinned staging slots and device lists for ``max_regions`` per call)."""
+    NAME = "redact"
 
     def __init__(self, max_regions: int = 128):
-        self.h = C.c_void_p()
         self.max_regions = int(max_regions)
-        check(lib().hp_redact_create(C.byref(self.h), self.max_regions))
-
-    def close(self):
-        if self.h:
-            lib().hp_redact_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-_redactor = None
-
-
-def _default_redactor(n: int) -> Redactor:
-    global _redactor
-    if _redactor is None or _redactor.max_regions < n:
-        _redactor = Redactor(max(128, n))
-    return _redactor
+        super().__init__(self.max_regions)
 
 
 def redact(target, regions, effect: str = "pixelate", cell: int = 16, w=None, h=None, stride=None, stream=None, redactor=None) -> None:
@@ -626,7 +613,7 @@ def redact(target, regions, effect: str = "pixelate", cell: int = 16, w=None, h=
     caller's own) reach, in a frame in DEVICE memory, in place and stream-ordered: ``target`` is a ``YuvImage`` whose planes are device pointers
     (``hp_redact_yuv``) or a device buffer of 8-bit BGR with ``w``, ``h`` and optionally ``stride`` in bytes (``hp_redact_u8c3``)."""
     rs = _regions(regions)
-    rd = redactor or _default_redactor(len(rs))
+    rd = redactor or _default_handle(Redactor, 128, len(rs))
     rp, s = rs.ctypes.data_as(C.POINTER(RedactRegion)), C.c_void_p(stream) if stream else None
     if isinstance(target, YuvImage):
         check(lib().hp_redact_yuv(rd.h, C.byref(target), rp, len(rs), REDACT_EFFECTS[effect], int(cell), s))
@@ -641,12 +628,7 @@ def redact_host(frame, regions, fmt=None, matrix: str = "bt601", range: str = "l
     rs = _regions(regions)
     rp = rs.ctypes.data_as(C.POINTER(RedactRegion))
     if fmt is None:
-        assert frame.dtype == np.uint8 and frame.ndim == 3 and frame.shape[2] == 3 and frame.strides[1:] == (3, 1) and frame.flags.writeable
-        check(lib().hp_redact_u8c3_host(C.c_void_p(frame.ctypes.data), frame.shape[1], frame.shape[0], frame.strides[0], rp, len(rs),
-                                        REDACT_EFFECTS[effect], int(cell)))
+        check(lib().hp_redact_u8c3_host(*_host_bgr(frame), rp, len(rs), REDACT_EFFECTS[effect], int(cell)))
         return
-    for p in frame:
-        assert p.ndim == 2 and p.strides[1] == p.itemsize and p.flags.writeable
-    w, h = yuv_size_of_planes(fmt, frame)
-    im = yuv_image(fmt, [p.ctypes.data for p in frame], [p.strides[0] for p in frame], w, h, matrix, range)
+    im = _host_image(frame, fmt, matrix, range, written=True)
     check(lib().hp_redact_yuv_host(C.byref(im), rp, len(rs), REDACT_EFFECTS[effect], int(cell)))

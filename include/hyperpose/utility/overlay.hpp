@@ -36,24 +36,29 @@ namespace detail {
         }
         return out;
     }
-    // the calling thread's hp_overlay handle, grown when a frame has more humans than it was made for (one handle = one thread, hp_hip.h).
-    // It is released when the thread ends; for the main thread that is before objects of static storage duration are destroyed
-    // ([basic.start.term]), hence before the HIP runtime's own teardown, and hp_overlay_destroy ignores what a late call returns
-    inline hp_overlay* overlay_handle(size_t n_humans)
+    // the calling thread's handle of one kind (hp_overlay, hp_redact), made for at least `floor` items and grown when a frame brings more than
+    // it was made for (one handle = one thread, hp_hip.h).  It is released when the thread ends; for the main thread that is before objects
+    // of static storage duration are destroyed ([basic.start.term]), hence before the HIP runtime's own teardown, and the destroy functions
+    // ignore what a late call returns
+    template <class H, int (*Create)(H**, int), void (*Destroy)(H*)> H* thread_handle(size_t n, size_t floor, const char* who)
     {
         struct holder {
-            hp_overlay* h = nullptr;
+            H* h = nullptr;
             size_t cap = 0;
-            ~holder() { hp_overlay_destroy(h); }
+            ~holder() { Destroy(h); }
         };
         thread_local holder t;
-        if (!t.h || t.cap < n_humans) {
-            hp_overlay_destroy(t.h);
-            t.h = nullptr, t.cap = std::max<size_t>(64, n_humans);
-            if (hp_overlay_create(&t.h, (int)t.cap) != HP_OK)
-                throw std::runtime_error(std::string("hyperpose::draw_humans: ") + hp_last_error());
+        if (!t.h || t.cap < n) {
+            Destroy(t.h);
+            t.h = nullptr, t.cap = std::max(floor, n);
+            if (Create(&t.h, (int)t.cap) != HP_OK)
+                throw std::runtime_error(std::string(who) + ": " + hp_last_error());
         }
         return t.h;
+    }
+    inline hp_overlay* overlay_handle(size_t n_humans)
+    {
+        return thread_handle<hp_overlay, hp_overlay_create, hp_overlay_destroy>(n_humans, 64, "hyperpose::draw_humans");
     }
     inline void overlay_check(int rc)
     {

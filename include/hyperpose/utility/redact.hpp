@@ -33,23 +33,10 @@ namespace detail {
         if (rc < HP_OK)
             throw std::logic_error(std::string("hyperpose::redact_humans: ") + hp_last_error());
     }
-    // the calling thread's hp_redact handle, grown when a frame has more regions than it was made for (one handle = one thread, hp_hip.h);
-    // released when the thread ends, as overlay_handle is
+    // the calling thread's hp_redact handle (thread_handle, overlay.hpp)
     inline hp_redact* redact_handle(size_t n_regions)
     {
-        struct holder {
-            hp_redact* h = nullptr;
-            size_t cap = 0;
-            ~holder() { hp_redact_destroy(h); }
-        };
-        thread_local holder t;
-        if (!t.h || t.cap < n_regions) {
-            hp_redact_destroy(t.h);
-            t.h = nullptr, t.cap = std::max<size_t>(128, n_regions);
-            if (hp_redact_create(&t.h, (int)t.cap) != HP_OK)
-                throw std::runtime_error(std::string("hyperpose::redact_humans: ") + hp_last_error());
-        }
-        return t.h;
+        return thread_handle<hp_redact, hp_redact_create, hp_redact_destroy>(n_regions, 128, "hyperpose::redact_humans");
     }
     inline std::vector<hp_redact_region> redact_regions(const std::vector<human_t>& humans, int w, int h, const redaction& r)
     {

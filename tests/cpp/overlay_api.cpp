@@ -1,41 +1,12 @@
 // hyperpose::draw_humans (include/hyperpose/utility/overlay.hpp): a P010 BT.709 frame with padded pitch painted in DEVICE memory and the same
 // frame painted in HOST memory give the same bytes, padding included, plain and blended; the device_bgr form equals the C ABI's host BGR twin;
 // an opacity outside (0, 1] throws.  Prints "OK <comparisons> <threw>"; run by tests/test_cpp_overlay.py on the GPU box.
-#include <hyperpose/hyperpose.hpp>
+#include "frame_fixture.hpp"
 
 #include <cstdio>
 #include <cstring>
-#include <vector>
 
 namespace hp = hyperpose;
-
-static std::vector<uint8_t> noise(size_t n, unsigned seed, bool p010)
-{
-    std::vector<uint8_t> v(n);
-    unsigned s = seed * 2654435761u + 12345u;
-    for (size_t i = 0; i < n; ++i)
-        s = s * 1664525u + 1013904223u, v[i] = (uint8_t)(s >> 24);
-    if (p010)
-        for (size_t i = 0; i + 1 < n; i += 2)
-            v[i] &= 0xC0; // a P010 word holds its sample in the high ten bits
-    return v;
-}
-
-static std::vector<hp::human_t> some_humans()
-{
-    std::vector<hp::human_t> out(3);
-    unsigned s = 77;
-    auto next = [&] { return (s = s * 1664525u + 1013904223u, (float)(s >> 8) / (float)(1 << 24)); };
-    for (size_t i = 0; i < out.size(); ++i) {
-        out[i].score = 1;
-        const float cx = 0.2f + 0.3f * i, cy = 0.3f + 0.2f * i;
-        for (int k = 0; k < hp::COCO_N_PARTS; ++k)
-            if (k % 5 != (int)i) // some parts missing
-                out[i].parts[k] = hp::body_part_t{ true, cx + 0.3f * (next() - 0.5f), cy + 0.4f * (next() - 0.5f), 1.f };
-    }
-    out[2].parts[3].x = 1.2f, out[2].parts[4].y = -0.1f; // beyond the frame
-    return out;
-}
 
 int main()
 {
@@ -43,7 +14,7 @@ int main()
         std::printf("NO_DEVICE %s\n", hp_last_error());
         return 2;
     }
-    const auto humans = some_humans();
+    const auto humans = some_humans(0.3f, 0.4f);
     int compared = 0, threw = 0;
     const int w = 200, h = 120, pitch = 26;
     for (float opacity : { 1.f, 0.4f }) {

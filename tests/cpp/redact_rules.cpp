@@ -1,30 +1,15 @@
 // The host side of hyperpose_amd/csrc/redact.hpp - the region list and the host painter - on frames allocated with NO slack: one malloc per plane
 // of exactly the plane's size, so that under -fsanitize=address,undefined any read or write outside a plane, and any overflow of the integer
 // rules, aborts.  Every layout (BGR and the nine hp_yuv_image formats), both effects, cells 2 and 128, heads and bodies of humans that lie partly
-// outside the frame, plus regions at the limits of the coordinate range.  The layouts' geometry is restated here (the library's table lives behind
-// the HIP headers).  Prints "OK <frames painted>"; run by tests/test_cpp_redact_rules.py.
+// outside the frame, plus regions at the limits of the coordinate range.  The layouts' geometry is the library's own (yuv_formats.hpp): that this
+// file compiles with plain g++ and no ROCm include path is the proof that it, part_points.hpp and redact.hpp are host-pure.
+// Prints "OK <frames painted>"; run by tests/test_cpp_redact_rules.py.
 #include "../../hyperpose_amd/csrc/redact.hpp"
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-
-struct layout {
-    int format, planes, sample_bytes, sx, sy, shift;
-};
-static const layout LAYOUTS[] = { { HP_YUV_NV12, 2, 1, 1, 1, 0 }, { HP_YUV_I420, 3, 1, 1, 1, 0 }, { HP_YUV_P010, 2, 2, 1, 1, 6 }, { HP_YUV_I010, 3, 2, 1, 1, 0 },
-    { HP_YUV_NV16, 2, 1, 1, 0, 0 }, { HP_YUV_I422, 3, 1, 1, 0, 0 }, { HP_YUV_YUY2, 1, 1, 1, 0, 0 }, { HP_YUV_UYVY, 1, 1, 1, 0, 0 }, { HP_YUV_I444, 3, 1, 0, 0, 0 } };
-
-static size_t row_bytes(const layout& l, int k, int w)
-{
-    if (l.planes == 1)
-        return (size_t)w * 2;
-    if (k == 0)
-        return (size_t)w * l.sample_bytes;
-    const size_t cw = (size_t)(w >> l.sx) * l.sample_bytes;
-    return l.planes == 2 ? cw * 2 : cw;
-}
 
 static std::vector<hp_human> humans()
 {
@@ -92,19 +77,20 @@ int main()
             run(f, all);
             std::free(p);
         }
-        for (const layout& l : LAYOUTS) {
+        for (int format = 0; hp_yuv::layout_of(format); ++format) {
+            const hp_yuv::layout& l = *hp_yuv::layout_of(format);
             const int w = (size ? 258 : 98) - (l.sx ? 0 : 1), h = (size ? 130 : 66) - (l.sy ? 0 : 1);
             hp_yuv_image im {};
-            im.format = l.format, im.matrix = HP_YUV_BT709, im.range = HP_YUV_LIMITED, im.width = w, im.height = h;
+            im.format = format, im.matrix = HP_YUV_BT709, im.range = HP_YUV_LIMITED, im.width = w, im.height = h;
             void* planes[3] = { nullptr, nullptr, nullptr };
             for (int k = 0; k < l.planes; ++k) {
-                const size_t bytes = row_bytes(l, k, w) * (size_t)(k == 0 ? h : h >> l.sy);
+                const size_t bytes = hp_yuv::row_bytes(l, k, w) * (size_t)hp_yuv::rows(l, k, h);
                 planes[k] = std::malloc(bytes);
                 std::memset(planes[k], 0xFF, bytes);
-                im.plane[k] = planes[k], im.stride[k] = (int)row_bytes(l, k, w);
+                im.plane[k] = planes[k], im.stride[k] = (int)hp_yuv::row_bytes(l, k, w);
             }
             hp_red::frame f;
-            hp_red::describe_yuv(f, im, l.planes, l.sample_bytes, l.sx, l.sy, l.shift);
+            hp_red::describe_yuv(f, im);
             const auto all = regions(w, h);
             for (const auto& g : all)
                 run(f, { g });
