@@ -12,6 +12,11 @@
 //     `--yuv_matrix=bt601|bt709|bt2020` and `--yuv_range=limited|full` (defaults bt601, limited); `--yuv` converts any other source to
 //     NV12 first.  Either way the operator runtime hands the engine hyperpose::yuv_frame batches (colour conversion fused into the resize
 //     on the GPU); the BGR pictures, converted on the host with the same table (hp_yuv_coefficients), are only drawn on.
+//   * packed RGB / grey frames (addition): `--rgb=<rgb24|bgr24|bgra|rgba|argb|abgr|gray>` feeds every frame of any source to the engine as an
+//     hyperpose::rgb_frame of that layout (hp_rgb_image: read by the fused resize, nothing is repacked for the engine).  The frame is made on the host
+//     from the BGR picture: alpha 255, grey = (B + 2 G + R + 2) >> 2.  `--source=<file>.rgb` reads raw frames of `--yuv_w` x `--yuv_h` in that layout,
+//     back to back.  Operator runtime (as --yuv); refused from the flags alone: an unknown name, --rgb with --yuv or a .yuv source, --saving_yuv or
+//     --redact with --rgb (drawing and redaction have no RGB targets), a .rgb source without --rgb.
 //   * HDR video (addition): `--yuv_transfer=sdr|pq|hlg` (default sdr) `[--hdr_peak=<cd/m2> --hdr_white=<cd/m2> --hdr_keep_primaries]`, only with
 //     a .yuv source in a 10-bit layout (`--yuv_format=p010|i010`): the frames are HDR10 (pq) or HLG and are tone-mapped to SDR sRGB inside the
 //     fused resize (engine.set_tonemap; hp::hdr, defaults 1000 / 203, BT.2020 primaries converted to BT.709 unless --hdr_keep_primaries); the
@@ -102,6 +107,8 @@ static int FLAGS_redact_cell = 16;
 static double FLAGS_redact_margin = 1.0;
 static bool FLAGS_redact_only = false; // ... and no skeletons on top
 static bool g_redact = false;
+static std::string FLAGS_rgb; // addition: --rgb=<layout>: feed the engine packed RGB / grey frames (dnn::tensorrt::inference(std::vector<rgb_frame>))
+static int g_rgb_format = -1; // ... parsed: HP_RGB_*, -1 while off
 static hp::redaction g_redaction;
 static int FLAGS_synthetic_humans = 0; // addition: stand-in humans added to every frame's poses (see the head of the file)
 static bool g_yuv_from_file = false; // the frames came from a .yuv source (else --yuv made NV12 ones)
@@ -115,7 +122,7 @@ static bool parse_flags(int argc, char** argv)
     std::map<std::string, std::string*> sflags = { { "model", &FLAGS_model }, { "post", &FLAGS_post }, { "source", &FLAGS_source },
         { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix }, { "saving_yuv", &FLAGS_saving_yuv }, { "tiles", &FLAGS_tiles }, { "yuv_format", &FLAGS_yuv_format },
         { "yuv_matrix", &FLAGS_yuv_matrix }, { "yuv_range", &FLAGS_yuv_range }, { "yuv_transfer", &FLAGS_yuv_transfer },
-        { "scale_ensemble", &FLAGS_scale_ensemble }, { "redact", &FLAGS_redact }, { "redact_effect", &FLAGS_redact_effect } };
+        { "scale_ensemble", &FLAGS_scale_ensemble }, { "redact", &FLAGS_redact }, { "redact_effect", &FLAGS_redact_effect }, { "rgb", &FLAGS_rgb } };
     std::map<std::string, double*> dflags = { { "alpha", &FLAGS_alpha }, { "hdr_peak", &FLAGS_hdr_peak }, { "hdr_white", &FLAGS_hdr_white },
         { "redact_margin", &FLAGS_redact_margin } };
     std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size }, { "tile_overlap", &FLAGS_tile_overlap },
@@ -224,6 +231,25 @@ static bool parse_flags(int argc, char** argv)
         cli_log() << "ERROR: --hdr_peak / --hdr_white / --hdr_keep_primaries describe the frames of --yuv_transfer=pq|hlg\n";
         return false;
     }
+    // --rgb: an enumerated layout; what it cannot go with is settled here, from the flags alone
+    const bool rgb_file = FLAGS_source.size() >= 4 && FLAGS_source.compare(FLAGS_source.size() - 4, 4, ".rgb") == 0;
+    if (!FLAGS_rgb.empty()) {
+        if (!pick("rgb", FLAGS_rgb, { { "rgb24", HP_RGB_RGB24 }, { "bgr24", HP_RGB_BGR24 }, { "bgra", HP_RGB_BGRA32 }, { "rgba", HP_RGB_RGBA32 }, { "argb", HP_RGB_ARGB32 },
+                                       { "abgr", HP_RGB_ABGR32 }, { "gray", HP_RGB_GRAY8 } }, g_rgb_format))
+            return false;
+        const bool yuv_file = FLAGS_source.size() >= 4 && FLAGS_source.compare(FLAGS_source.size() - 4, 4, ".yuv") == 0;
+        if (FLAGS_yuv || yuv_file) {
+            cli_log() << "ERROR: --rgb=" << FLAGS_rgb << " and --yuv (or a .yuv source) both say how the engine is fed: give one\n";
+            return false;
+        }
+        if (!FLAGS_saving_yuv.empty() || !FLAGS_redact.empty()) {
+            cli_log() << "ERROR: --saving_yuv and --redact write video frames; with --rgb=" << FLAGS_rgb << " there is none (drawing and redaction have no RGB targets)\n";
+            return false;
+        }
+    } else if (rgb_file) {
+        cli_log() << "ERROR: a .rgb source holds raw frames: say their layout with --rgb=<rgb24|bgr24|bgra|rgba|argb|abgr|gray> (and --yuv_w, --yuv_h)\n";
+        return false;
+    }
     // --redact and its companions: enumerated names, an even cell in [2, 128], a margin in (0, 8]; the companions describe --redact
     if (!FLAGS_redact.empty()) {
         if (!pick("redact", FLAGS_redact, { { "head", hp::redaction::head }, { "body", hp::redaction::body } }, g_redaction.what)
@@ -315,6 +341,38 @@ struct yuv_buffer {
     hp::yuv_frame frame() const { return hp::yuv_frame::packed(format, data.data(), w, h, matrix, range); }
 };
 static std::vector<yuv_buffer> g_yuv; // one per image, same order, when the engine is fed YUV
+
+// ---- packed RGB / grey frames (host side, as above: inputs for the engine, BGR pictures to draw on)
+struct rgb_buffer {
+    int format = HP_RGB_BGR24, w = 0, h = 0;
+    std::vector<uint8_t> data; // hp_rgb_packed_bytes(format, w, h) bytes, tightly packed
+    hp::rgb_frame frame() const { return hp::rgb_frame::packed(format, data.data(), w, h); }
+};
+static std::vector<rgb_buffer> g_rgb; // one per image, same order, when the engine is fed RGB
+
+// the BGR picture in layout `format`: memory order as the name reads, alpha 255, grey = (B + 2 G + R + 2) >> 2
+static rgb_buffer bgr_to_rgb_layout(const cv::Mat& m, int format)
+{
+    static const char* const order[7] = { "BGR", "RGB", "BGRA", "RGBA", "ARGB", "ABGR", "Y" };
+    const std::string o = order[format];
+    rgb_buffer b;
+    b.format = format, b.w = m.cols, b.h = m.rows;
+    b.data.resize((size_t)m.cols * m.rows * o.size());
+    const uint8_t* s = hp::detail::mat_data(m);
+    uint8_t* d = b.data.data();
+    for (size_t i = 0; i < (size_t)m.cols * m.rows; ++i, s += 3)
+        for (char c : o)
+            *d++ = c == 'B' ? s[0] : c == 'G' ? s[1] : c == 'R' ? s[2] : c == 'A' ? 255 : (uint8_t)((s[0] + 2 * s[1] + s[2] + 2) >> 2);
+    return b;
+}
+static cv::Mat rgb_to_bgr(const rgb_buffer& b)
+{
+    cv::Mat m(b.h, b.w, CV_8UC3);
+    const hp_rgb_image im = b.frame().image();
+    if (hp_rgb_to_bgr_host(&im, const_cast<uint8_t*>(hp::detail::mat_data(m)), b.w * 3) != HP_OK)
+        cli_log() << "ERROR: " << hp_last_error() << "\n";
+    return m;
+}
 
 // BT.601 limited range, chroma = mean of its 2 x 2 pixels (what an encoder's input conversion does)
 static yuv_buffer bgr_to_nv12(const cv::Mat& m)
@@ -442,6 +500,31 @@ static std::vector<cv::Mat> load_source()
             g_yuv.push_back(std::move(b));
         }
         FLAGS_yuv = g_yuv_from_file = true;
+        return images;
+    }
+    if (match_suffix(".rgb")) { // raw frames of --rgb=<layout>, --yuv_w x --yuv_h, back to back
+        const size_t bytes = hp_rgb_packed_bytes(g_rgb_format, FLAGS_yuv_w, FLAGS_yuv_h);
+        if (bytes == 0) {
+            cli_log() << "ERROR: a .rgb source needs --yuv_w and --yuv_h: raw frames carry no header\n";
+            return {};
+        }
+        std::ifstream f(FLAGS_source, std::ios::binary | std::ios::ate);
+        const std::streamoff size = f ? (std::streamoff)f.tellg() : 0;
+        if (size <= 0 || (size_t)size % bytes != 0) {
+            cli_log() << "ERROR: " << FLAGS_source << " holds " << size << " bytes, which is not a whole number of " << FLAGS_rgb << " frames of " << FLAGS_yuv_w
+                      << " x " << FLAGS_yuv_h << " (" << bytes << " bytes each)\n";
+            return {};
+        }
+        f.seekg(0);
+        for (;;) {
+            rgb_buffer b;
+            b.format = g_rgb_format, b.w = FLAGS_yuv_w, b.h = FLAGS_yuv_h;
+            b.data.resize(bytes);
+            if (!f.read((char*)b.data.data(), bytes))
+                break;
+            images.push_back(rgb_to_bgr(b));
+            g_rgb.push_back(std::move(b));
+        }
         return images;
     }
     if (match_suffix(".ppm")) {
@@ -616,6 +699,13 @@ int main(int argc, char** argv)
             g_yuv.push_back(bgr_to_nv12(m));
         }
     }
+    if (g_rgb_format >= 0 && g_rgb.empty()) // --rgb on a BGR source: the frames as a capture API or a grey camera would deliver them
+        for (const auto& m : images)
+            g_rgb.push_back(bgr_to_rgb_layout(m, g_rgb_format));
+    if (g_rgb_format >= 0 && FLAGS_runtime == kSTREAM) {
+        cli_log() << "WARNING: the stream runtime carries cv::Mat frames (stream.hpp); RGB frames go through --runtime=" kOPERATOR "\n";
+        FLAGS_runtime = kOPERATOR;
+    }
     if (FLAGS_yuv && FLAGS_runtime == kSTREAM) {
         cli_log() << "WARNING: the stream runtime carries cv::Mat frames (stream.hpp); YUV frames go through --runtime=" kOPERATOR "\n";
         FLAGS_runtime = kOPERATOR;
@@ -644,6 +734,11 @@ int main(int argc, char** argv)
             std::vector<hp::yuv_frame> frames;
             for (size_t i = 0; i < n; ++i)
                 frames.push_back(g_yuv[i].frame());
+            engine.calibrate(frames);
+        } else if (g_rgb_format >= 0) {
+            std::vector<hp::rgb_frame> frames;
+            for (size_t i = 0; i < n; ++i)
+                frames.push_back(g_rgb[i].frame());
             engine.calibrate(frames);
         } else
             engine.calibrate(std::vector<cv::Mat>(images.begin(), images.begin() + n));
@@ -685,10 +780,10 @@ int main(int argc, char** argv)
 
     // --tiles: one frame's regions in one engine call, every region parsed on its own, the poses brought back to the frame and merged
     // (with --rotate / --hflip the regions, and the poses returned, are in the upright frame's coordinates)
-    auto tiled_poses = [&](const cv::Mat& stored, const hp::yuv_frame* yuv) {
+    auto tiled_poses = [&](const cv::Mat& stored, const hp::yuv_frame* yuv, const hp::rgb_frame* rgb = nullptr) {
         const cv::Size frame = hp::oriented_size(stored.size(), g_orient);
         const std::vector<cv::Rect> regions = hp::plan_tiles(frame, g_tiling, yuv ? yuv->format : -1, g_orient);
-        const auto maps = yuv ? engine.inference(*yuv, regions) : engine.inference(stored, regions);
+        const auto maps = yuv ? engine.inference(*yuv, regions) : rgb ? engine.inference(*rgb, regions) : engine.inference(stored, regions);
         std::vector<hp::human_t> all;
         std::vector<int> region_of;
         for (size_t r = 0; r < regions.size(); ++r)
@@ -723,9 +818,16 @@ int main(int argc, char** argv)
                     }
                     yuv_batch.push_back(hp::yuv_frame::packed(b.format, surfaces.back()->p, b.w, b.h, b.matrix, b.range, true));
                 }
-            const auto maps = g_tiled ? std::vector<hp::internal_t>{} : FLAGS_yuv ? engine.inference(yuv_batch) : engine.inference(batch);
+            std::vector<hp::rgb_frame> rgb_batch;
+            if (g_rgb_format >= 0)
+                for (size_t k = 0; k < batch.size(); ++k)
+                    rgb_batch.push_back(g_rgb[first + k].frame());
+            const auto maps = g_tiled ? std::vector<hp::internal_t>{}
+                : FLAGS_yuv       ? engine.inference(yuv_batch)
+                : g_rgb_format >= 0 ? engine.inference(rgb_batch)
+                                    : engine.inference(batch);
             for (size_t k = 0; k < batch.size(); ++k) {
-                auto poses = g_tiled ? tiled_poses(batch[k], FLAGS_yuv ? &yuv_batch[k] : nullptr) : std::visit([&](auto& op) { return op.process(maps[k]); }, parser);
+                auto poses = g_tiled ? tiled_poses(batch[k], FLAGS_yuv ? &yuv_batch[k] : nullptr, g_rgb_format >= 0 ? &rgb_batch[k] : nullptr) : std::visit([&](auto& op) { return op.process(maps[k]); }, parser);
                 add_synthetic_humans(poses, first + k, FLAGS_synthetic_humans);
                 if (yuv_out.is_open()) { // annotate the surface where it lies, in its own format, and append it to the file
                     std::vector<hp::human_t> drawn = poses;

@@ -25,6 +25,11 @@ HP_YUV_LIMITED, HP_YUV_FULL = 0, 1
 # (frontend.yuv_plane_shapes), and tests/test_yuv_formats_convert.py ties this table to it
 YUV_LAYOUTS = {"nv12": (0, 2, 1, 1, 1), "i420": (1, 3, 1, 1, 1), "p010": (2, 2, 2, 1, 1), "i010": (3, 3, 2, 1, 1), "nv16": (4, 2, 1, 1, 0),
                "i422": (5, 3, 1, 1, 0), "yuy2": (6, 1, 1, 1, 0), "uyvy": (7, 1, 1, 1, 0), "i444": (8, 3, 1, 0, 0)}
+# every layout hp_rgb_image names (a type of its own, not hp_yuv_image formats): (code, bytes per pixel, byte offsets of B, G, R inside a pixel);
+# hyperpose_amd/csrc/rgb_formats.hpp holds the same table, tests/test_rgb_host.py ties the two together
+HP_RGB_BGR24, HP_RGB_RGB24, HP_RGB_BGRA32, HP_RGB_RGBA32, HP_RGB_ARGB32, HP_RGB_ABGR32, HP_RGB_GRAY8 = 0, 1, 2, 3, 4, 5, 6
+RGB_LAYOUTS = {"bgr24": (0, 3, 0, 1, 2), "rgb24": (1, 3, 2, 1, 0), "bgra": (2, 4, 0, 1, 2), "rgba": (3, 4, 2, 1, 0), "argb": (4, 4, 3, 2, 1),
+               "abgr": (5, 4, 1, 2, 3), "gray": (6, 1, 0, 0, 0)}
 YUV_MATRICES = {"bt601": HP_YUV_BT601, "bt709": HP_YUV_BT709, "bt2020": HP_YUV_BT2020}
 YUV_RANGES = {"limited": HP_YUV_LIMITED, "full": HP_YUV_FULL}
 
@@ -55,6 +60,11 @@ class YuvImage(C.Structure):
     """hp_yuv_image"""
     _fields_ = [("format", C.c_int32), ("matrix", C.c_int32), ("range", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("plane", C.c_void_p * 3), ("stride", C.c_int32 * 3)]
+
+
+class RgbImage(C.Structure):
+    """hp_rgb_image"""
+    _fields_ = [("format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("data", C.c_void_p), ("stride", C.c_int32)]
 
 
 class OverlayPrim(C.Structure):
@@ -142,6 +152,7 @@ SYMBOLS = [
     "hp_engine_set_flip_ensemble_coco", "hp_engine_flip_ensemble", "hp_pipeline_set_flip_ensemble",
     "hp_scale_stage_u8c3", "hp_scale_stage_u8c3_host", "hp_scale_tables", "hp_scale_merge", "hp_scale_merge_host", "hp_engine_set_scale_ensemble",
     "hp_engine_set_scale_ensemble_coco", "hp_engine_scale_ensemble", "hp_pipeline_set_scale_ensemble",
+    "hp_resize_rgb", "hp_resize_rois_rgb", "hp_rgb_pixel_bytes", "hp_rgb_packed_bytes", "hp_rgb_to_bgr_host", "hp_pipeline_submit_rgb_images",
 ]
 
 
@@ -156,6 +167,7 @@ def lib() -> C.CDLL:
         L.hp_last_error.restype = C.c_char_p
         L.hp_version.restype = C.c_char_p
         L.hp_yuv_packed_bytes.restype = C.c_size_t
+        L.hp_rgb_packed_bytes.restype = C.c_size_t
         L.hp_humans_to_frame.restype = None
         L.hp_engine_debug_raw_tensor.restype = C.c_int
         L.hp_engine_debug_raw_tensor.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]

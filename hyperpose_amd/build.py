@@ -35,6 +35,8 @@ UNITS = [
     ("resize_yuv_hdr.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # stored-turned / mirrored frames read upright: every feed's Taps behind a coordinate map, the same arithmetic and flags once more
     ("resize_oriented.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # packed RGB / BGRA-family / grey frames (hp_rgb_image): their Taps behind the same coordinate map, the same arithmetic and flags once more
+    ("resize_rgb.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # the host side of HP_ORIENT_*: the humans' fp32 formulas must not fuse (tests/orient_ref.py restates them)
     ("orientation.cpp", ["-ffp-contract=off"]),
     # the tone-map tables, float64 without fused operations: tests/hdr_ref.py derives them a second time

@@ -7,15 +7,16 @@
 // reference's queues.  resume_ratio is applied on the way out when the aspect ratio was kept.
 //
 // One road from a submitted frame to its network slot.  Frames arrive as 8-bit BGR (hp_pipeline_submit), as YUV 4:2:0 buffers (hp_pipeline_submit_yuv)
-// or as hp_yuv_image descriptions of any layout, in host or in device memory (hp_pipeline_submit_yuv_images); every submit is
+// as hp_yuv_image descriptions of any layout, in host or in device memory (hp_pipeline_submit_yuv_images), or as hp_rgb_image descriptions of the packed
+// RGB / BGRA-family / grey layouts, again in host or in device memory (hp_pipeline_submit_rgb_images); every submit is
 //     admit()            n frames of R slots each fit a batch and a pipe is free (R = 1, or the regions of a frame in tiled mode)
 //     check and plan     EVERY frame is checked, and plan_frame() has its upright size and its R regions, before the first copy is enqueued:
 //                        a refused batch leaves nothing in the stream
 //     upload             upload_blob() (a contiguous host blob -> p.raw at 256-byte offsets, through p.stage unless pinned) or upload_yuv_images()
-//                        (planes packed tightly); all copies first, then all kernels: the stream changes between the copy engine and the
+//                        (planes packed tightly) or upload_rgb_images() (rows packed tightly, in the frame's own layout); all copies first, then all kernels: the stream changes between the copy engine and the
 //                        compute queue once per batch, not once per frame
-//     one resize call    per frame, and always the general one: hp_resize_oriented_u8c3 / hp_resize_oriented_yuv, in tiled mode
-//                        hp_resize_rois_oriented_u8c3 / hp_resize_rois_oriented_yuv, with the pipeline's orientation, the frame's tone-map (or null)
+//     one resize call    per frame, and always the general one: hp_resize_oriented_u8c3 / hp_resize_oriented_yuv / hp_resize_rgb, in tiled mode
+//                        hp_resize_rois_oriented_u8c3 / hp_resize_rois_oriented_yuv / hp_resize_rois_rgb, with the pipeline's orientation, the frame's tone-map (or null)
 //                        and keep_ratio.  Which kernel runs is decided inside those four calls (resize_oriented.hip) and nowhere here: orientation 0
 //                        forwards to the un-oriented call, a null tone-map is the SDR call
 //     infer_and_parse()  conv stack, parser, and the pipe joins the ring
@@ -34,6 +35,7 @@
 //     (c) all copies first, then all kernels, within a batch - also where (a) mixes direct and resized frames
 #include "hp_common.hpp"
 #include "parser_host.hpp"
+#include "rgb_formats.hpp"
 #include "scale_ensemble.hpp"
 #include "yuv_formats.hpp"
 
@@ -114,6 +116,7 @@ namespace {
 int infer_and_parse(hp_pipeline* pl, pipe_t& p, int n);
 int collect_tiled(hp_pipeline* pl, pipe_t& p, hp_human* out, int cap_per_frame, int* n_out, int* n_frames);
 int upload_yuv_images(pipe_t& p, const hp_yuv_image* frames, int n, std::vector<hp_yuv_image>& dev);
+int upload_rgb_images(pipe_t& p, const hp_rgb_image* frames, int n, std::vector<hp_rgb_image>& dev);
 
 // network-sized slots a frame takes: its regions in tiled mode, one otherwise
 int tiled_regions(const hp_pipeline* pl) { return pl->tiled ? pl->tiling.cols * pl->tiling.rows + pl->tiling.with_full : 1; }
@@ -452,6 +455,35 @@ int hp_pipeline_submit_yuv_images(hp_pipeline* pl, const hp_yuv_image* frames, i
     return infer_and_parse(pl, p, n * R);
 }
 
+int hp_pipeline_submit_rgb_images(hp_pipeline* pl, const hp_rgb_image* frames, int n, int on_device)
+{
+    const char* who = "hp_pipeline_submit_rgb_images";
+    HP_REQUIRE(pl && frames, HP_ERR_INVALID, "%s: null argument", who);
+    HP_TRY(admit(pl, who, n));
+    pipe_t& p = pl->pipes[pl->head];
+    const int R = tiled_regions(pl);
+    const size_t net_frame = (size_t)pl->in_w * pl->in_h * 3;
+    for (int i = 0; i < n; ++i) { // everything is checked before the first copy is enqueued
+        HP_TRY(hp_rgb::validate(&frames[i], who, on_device != 0));
+        const size_t bytes = hp_rgb_packed_bytes(frames[i].format, frames[i].width, frames[i].height);
+        HP_REQUIRE(on_device || bytes <= pl->max_frame_bytes, HP_ERR_CAPACITY, "%s: frame %d (%s, %dx%d, %zu bytes) exceeds max_frame_bytes %zu", who, i,
+            hp_rgb::layout_of(frames[i].format)->name, frames[i].width, frames[i].height, bytes, pl->max_frame_bytes);
+        HP_TRY(plan_frame(pl, p, i, frames[i].width, frames[i].height, 1, 1));
+    }
+    std::vector<hp_rgb_image> dev; // each frame as a kernel will read it: the caller's surface, or the tightly packed copy in p.raw
+    if (on_device)
+        dev.assign(frames, frames + n);
+    else
+        HP_TRY(upload_rgb_images(p, frames, n, dev));
+    for (int i = 0; i < n; ++i) { // (8-bit SDR frames: the pipeline's tone-map has nothing to act on)
+        uint8_t* dst = p.net.as<uint8_t>() + (size_t)i * R * net_frame;
+        HP_TRY(pl->tiled ? hp_resize_rois_rgb(&dev[i], pl->orientation, &p.roi[(size_t)i * R], R, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3,
+                               net_frame, p.s)
+                         : hp_resize_rgb(&dev[i], pl->orientation, pl->keep_ratio, 0, 0, 0, dst, pl->in_w, pl->in_h, pl->in_w * 3, p.s));
+    }
+    return infer_and_parse(pl, p, n * R);
+}
+
 } // extern "C"
 
 namespace {
@@ -497,6 +529,29 @@ int upload_yuv_images(pipe_t& p, const hp_yuv_image* frames, int n, std::vector<
                     memcpy(to, (const uint8_t*)f.plane[k] + (size_t)r * f.stride[k], row);
             }
         }
+        HP_HIP_TRY(hipMemcpyAsync(p.raw.as<uint8_t>() + off, src, bytes, hipMemcpyHostToDevice, p.s));
+        off += (bytes + 255) & ~(size_t)255;
+    }
+    return HP_OK;
+}
+
+// host frames of hp_pipeline_submit_rgb_images: every frame's rows tightly packed into p.raw in the frame's own layout (one copy per frame, enqueued
+// on p.s; the 256-byte offsets keep the 4-byte layouts aligned); `dev` describes each frame as a kernel will read it there
+int upload_rgb_images(pipe_t& p, const hp_rgb_image* frames, int n, std::vector<hp_rgb_image>& dev)
+{
+    dev.assign(frames, frames + n);
+    size_t off = 0;
+    for (int i = 0; i < n; ++i) {
+        const hp_rgb_image& f = frames[i];
+        const size_t row = (size_t)f.width * hp_rgb::layout_of(f.format)->pixel_bytes, bytes = row * f.height;
+        const uint8_t* src = (const uint8_t*)f.data;
+        if ((size_t)f.stride != row || !is_pinned(src)) {
+            uint8_t* to = p.stage.as<uint8_t>() + off;
+            for (int r = 0; r < f.height; ++r)
+                memcpy(to + (size_t)r * row, src + (size_t)r * f.stride, row);
+            src = to;
+        }
+        dev[i].data = p.raw.as<uint8_t>() + off, dev[i].stride = (int32_t)row;
         HP_HIP_TRY(hipMemcpyAsync(p.raw.as<uint8_t>() + off, src, bytes, hipMemcpyHostToDevice, p.s));
         off += (bytes + 255) & ~(size_t)255;
     }

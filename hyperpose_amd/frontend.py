@@ -8,7 +8,7 @@ import numpy as np
 
 from ._lib import (HDR_DEFAULT_PEAK, HDR_DEFAULT_WHITE, HDR_TRANSFERS, HUMAN_DTYPE, OVERLAY_PRIM_DTYPE, REDACT_EFFECTS, REDACT_REGION_DTYPE, REDACT_WHAT,
                    TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL, YUV_FORMATS, YUV_LAYOUTS, YUV_MATRICES, YUV_RANGES, DevBuf, HdrDesc, Human, OverlayPrim,
-                   RedactRegion, Roi, Tiling, YuvImage, as_ptr, check, lib)
+                   RedactRegion, RGB_LAYOUTS, RgbImage, Roi, Tiling, YuvImage, as_ptr, check, lib)
 
 
 def resize(src_dev, sw: int, sh: int, dst_dev, dw: int, dh: int, stream=None, src_stride=None, dst_stride=None) -> None:
@@ -335,6 +335,76 @@ def resize_oriented(src, dst_dev, dw: int, dh: int, orientation: int, keep_ratio
     else:
         check(lib().hp_resize_oriented_u8c3(as_ptr(src), int(sw), int(sh), int(src_stride or sw * 3), int(orientation), int(bool(keep_ratio)), bg[0], bg[1],
                                             bg[2], as_ptr(dst_dev), int(dw), int(dh), int(dst_stride or dw * 3), s))
+
+
+# ---- packed RGB and grey frames: hp_rgb_image, its host twin and the fused resize (include/hp_hip.h, "packed RGB and grey frames") -------------
+
+def rgb_image(fmt: str, data, w: int, h: int, stride=None) -> RgbImage:
+    """An ``hp_rgb_image``: ``data`` an address (host or device; a ``DevBuf`` or tensor works), ``stride`` the row pitch in bytes (default: tight)."""
+    return RgbImage(RGB_LAYOUTS[fmt][0], int(w), int(h), as_ptr(data), int(stride if stride is not None else w * RGB_LAYOUTS[fmt][1]))
+
+
+def rgb_host_image(frame, fmt: str):
+    """(``RgbImage``, the array it points into) of a host frame ``[h, w, 3]``, ``[h, w, 4]`` or ``[h, w]`` uint8; a view whose pixels are contiguous
+    keeps its row stride and is not copied."""
+    pb = RGB_LAYOUTS[fmt][1]
+    a = np.asarray(frame)
+    shape_ok = a.ndim == 2 if pb == 1 else a.ndim == 3 and a.shape[2] == pb
+    if not shape_ok:
+        raise ValueError(f"a {fmt} frame is a {'[h, w]' if pb == 1 else f'[h, w, {pb}]'} uint8 array, got shape {a.shape}")
+    if a.dtype != np.uint8 or a.strides[1] != pb or (pb > 1 and a.strides[2] != 1) or a.strides[0] < a.shape[1] * pb:
+        a = np.ascontiguousarray(a, np.uint8)
+    return RgbImage(RGB_LAYOUTS[fmt][0], a.shape[1], a.shape[0], a.ctypes.data, a.strides[0]), a
+
+
+def rgb_pixel_bytes(fmt: str) -> int:
+    return int(lib().hp_rgb_pixel_bytes(RGB_LAYOUTS[fmt][0]))
+
+
+def rgb_packed_bytes(fmt: str, w: int, h: int) -> int:
+    """``hp_rgb_packed_bytes``: bytes of one tightly packed frame; 0 for an invalid size."""
+    return int(lib().hp_rgb_packed_bytes(RGB_LAYOUTS[fmt][0], int(w), int(h)))
+
+
+def rgb_to_bgr_host(frame, fmt: str = "bgra", pitch: int = 0, fill: int = 0) -> np.ndarray:
+    """``hp_rgb_to_bgr_host``: a host frame (array or ``RgbImage``) as 8-bit BGR ``[h, w, 3]`` - the definition of what every RGB feed computes.
+    With ``pitch`` the result is a view into rows of ``pitch`` bytes pre-filled with ``fill`` (``.base`` shows that the padding was not written)."""
+    im, keep = (frame, None) if isinstance(frame, RgbImage) else rgb_host_image(frame, fmt)  # (keep: the array the description points into)
+    w, h = im.width, im.height
+    stride = int(pitch or w * 3)
+    buf = np.full((max(h, 0), max(stride, 0)), fill, np.uint8)
+    check(lib().hp_rgb_to_bgr_host(C.byref(im), buf.ctypes.data_as(C.c_void_p), stride))
+    return np.ndarray((h, w, 3), np.uint8, buffer=buf, strides=(stride, 3, 1))
+
+
+def resize_rgb(im: RgbImage, dst_dev, dw: int, dh: int, orientation: int = 0, keep_ratio: bool = False, bgcolor=(0, 0, 0), dst_stride=None,
+               stream=None) -> None:
+    """``hp_resize_rgb``: a STORED device frame of any ``hp_rgb_image`` layout read upright and resized (letterboxed with ``bgcolor`` when
+    ``keep_ratio``) to 8-bit BGR ``dw`` x ``dh``: the bytes of ``resize_oriented`` on ``rgb_to_bgr_host`` of the frame."""
+    bg = [int(c) for c in bgcolor]
+    check(lib().hp_resize_rgb(C.byref(im), int(orientation), int(bool(keep_ratio)), bg[0], bg[1], bg[2], as_ptr(dst_dev), int(dw), int(dh),
+                              int(dst_stride or dw * 3), C.c_void_p(stream) if stream else None))
+
+
+def resize_rois_rgb(im: RgbImage, rois, dst_dev, dw: int, dh: int, orientation: int = 0, keep_ratio: bool = False, bgcolor=(0, 0, 0), dst_stride=None,
+                    slot_stride=None, stream=None) -> None:
+    """``hp_resize_rois_rgb``: the UPRIGHT regions ``rois`` [(x, y, w, h)] of one stored device frame to ``len(rois)`` slots of ``dst_dev``."""
+    arr, n = _rois(rois)
+    ds = int(dst_stride or dw * 3)
+    ss = C.c_size_t(int(slot_stride if slot_stride is not None else ds * dh))
+    bg = [int(c) for c in bgcolor]
+    check(lib().hp_resize_rois_rgb(C.byref(im), int(orientation), arr, n, int(bool(keep_ratio)), bg[0], bg[1], bg[2], as_ptr(dst_dev), int(dw), int(dh),
+                                   ds, ss, C.c_void_p(stream) if stream else None))
+
+
+def resize_rgb_host(frame, dw: int, dh: int, fmt: str = "bgra", orientation: int = 0, keep_ratio: bool = False, bgcolor=(0, 0, 0)) -> np.ndarray:
+    """Convenience for tests, like ``resize_host``: host frame -> device (tightly packed) -> ``resize_rgb`` -> host ``[dh, dw, 3]``."""
+    a = np.ascontiguousarray(frame, np.uint8)
+    src = DevBuf.from_numpy(a)
+    dst = DevBuf(dw * dh * 3)
+    resize_rgb(rgb_image(fmt, src, a.shape[1], a.shape[0]), dst, dw, dh, orientation, keep_ratio, bgcolor)
+    check(lib().hp_device_synchronize())
+    return dst.to_numpy(np.uint8, (dh, dw, 3))
 
 
 # ---- flip ensemble: the frame flip, the map merge and the COCO tables (include/hp_hip.h; the definition: csrc/flip_ensemble.hpp) ---------------

@@ -6,8 +6,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HDR_DEFAULT_PEAK, HDR_DEFAULT_WHITE, HUMAN_DTYPE, TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL, YUV_FORMATS, YUV_LAYOUTS, Human, YuvImage,
-                   check, lib)
+from ._lib import (HDR_DEFAULT_PEAK, HDR_DEFAULT_WHITE, HUMAN_DTYPE, TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL, YUV_FORMATS, YUV_LAYOUTS, Human, RgbImage,
+                   YuvImage, check, lib)
 from .engine import _DTYPES, EngineDesc, Layer, OutputDesc
 
 
@@ -171,6 +171,33 @@ class Pipeline:
     def submit_yuv_images_raw(self, images, n: int, on_device: bool = False) -> None:
         """Pre-marshalled form for hot loops: ``images`` is a ctypes array of ``YuvImage``."""
         check(lib().hp_pipeline_submit_yuv_images(self._h, images, n, int(bool(on_device))))
+
+    def submit_rgb_images(self, frames, format="bgr24", on_device: bool = False) -> None:
+        """Packed RGB, BGRA-family and grey frames (``hp_pipeline_submit_rgb_images``).  A frame is a uint8 array ``[h, w, 3]`` (``format`` "bgr24" or
+        "rgb24"), ``[h, w, 4]`` ("bgra", "rgba", "argb", "abgr") or ``[h, w]`` ("gray"); a row-padded view keeps its stride and is not copied - or,
+        ready-made, an ``RgbImage`` (``frontend.rgb_image``), which is the only form of a device-resident frame.  ``format`` is one name for the batch
+        or one per frame.  The frames go up in their own form and are read by the fused resize: nothing is repacked to BGR.
+        ``on_device=True``: ``data`` is a device pointer and nothing is copied; the surfaces must be complete now and stay untouched until the
+        batch has been collected."""
+        from . import frontend
+        n = len(frames)
+        fmts = list(format) if isinstance(format, (list, tuple)) else [format] * n
+        arr = (RgbImage * n)()
+        keep = []
+        for i, (f, fm) in enumerate(zip(frames, fmts)):
+            if isinstance(f, RgbImage):
+                arr[i] = f
+                continue
+            if on_device:
+                raise ValueError("submit_rgb_images: a device-resident frame is given as an RgbImage (frontend.rgb_image)")
+            arr[i], a = frontend.rgb_host_image(f, fm)
+            keep.append(a)
+        check(lib().hp_pipeline_submit_rgb_images(self._h, arr, n, int(bool(on_device))))
+        self._keep = (keep, frames)
+
+    def submit_rgb_images_raw(self, images, n: int, on_device: bool = False) -> None:
+        """Pre-marshalled form for hot loops: ``images`` is a ctypes array of ``RgbImage``."""
+        check(lib().hp_pipeline_submit_rgb_images(self._h, images, n, int(bool(on_device))))
 
     def collect(self):
         """Humans of the oldest batch in flight: list (per frame) of Human structure arrays."""

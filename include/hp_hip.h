@@ -315,6 +315,40 @@ int hp_orient_u8c3_host(const uint8_t* src, int sw, int sh, int src_stride, int 
  * 1.0f - (1.0f - t) rounds, so a round trip need not return the same float (it does for every t that is a multiple of 2^-24 in [0, 1]). */
 int hp_humans_orient(hp_human* humans, int n, int orientation, int to_stored);
 
+/* ---- packed RGB and grey frames: what sources other than a video decoder deliver - screen and window capture, compositors, canvases and 4-channel
+ * pictures (4-byte pixels), PIL / imageio / PPM pictures (RGB order), IR and machine-vision cameras (grey) - read by the fused resize where they lie,
+ * with a stride, in host or device memory: no repack on the CPU (hyperpose_amd/csrc/resize_rgb.hip, rgb_formats.hpp; DESIGN.md 1.1 "Packed RGB and grey
+ * frames").  A type of its own: the codes are not hp_yuv_image formats.  The ONE rule:
+ *     memory order is as the name reads: HP_RGB_BGRA32 is bytes B, G, R, A; HP_RGB_ARGB32 is A, R, G, B; HP_RGB_RGB24 is R, G, B
+ *     the fourth byte of the 4-byte layouts (alpha or padding) is ignored: no premultiplication, no blend
+ *     HP_RGB_GRAY8 gives B = G = R = the sample
+ *     any width and height >= 1;  stride (bytes) >= width * pixel bytes
+ *     where a kernel reads the plane where it lies (the device calls, on_device submits), `data` and `stride` of the 4-byte layouts must be multiples
+ *     of 4: a pixel is fetched as one aligned word.  Host frames are re-packed bytewise and have no such rule
+ * A violation is HP_ERR_INVALID with a message that names the layout ("HP_RGB_BGRA32" ...) and the offending quantity, and nothing is launched.
+ * hp_rgb_to_bgr_host is the definition: the whole frame as 8-bit BGR.
+ *
+ * Contract of the device calls: for every layout, size, orientation code 0 .. 7, keep_ratio and (b, g, r) the bytes written equal what
+ * hp_resize_oriented_u8c3 (hp_resize_rgb) / hp_resize_rois_oriented_u8c3 (hp_resize_rois_rgb) give on hp_rgb_to_bgr_host(src); the other arguments and
+ * the refusals (orientation outside 0 .. 7, n outside 1 .. 64, a region outside the upright frame, a short slot_stride, ...) are theirs, bytes of
+ * dev_dst those calls leave alone are left alone, and the region alignment is 1 x 1 for every layout.  An HP_RGB_BGR24 image gives the bytes of the
+ * _u8c3 entry points on the same buffer.  No byte outside width * pixel bytes of a row is read.  The calls only enqueue. */
+enum { HP_RGB_BGR24 = 0, HP_RGB_RGB24 = 1, HP_RGB_BGRA32 = 2, HP_RGB_RGBA32 = 3, HP_RGB_ARGB32 = 4, HP_RGB_ABGR32 = 5, HP_RGB_GRAY8 = 6 };
+typedef struct hp_rgb_image {
+    int32_t format, width, height;
+    const void* data;
+    int32_t stride; /* bytes */
+} hp_rgb_image;
+int hp_resize_rgb(const hp_rgb_image* src /* data in DEVICE memory */, int orientation, int keep_ratio, int b, int g, int r, uint8_t* dev_dst, int dw,
+                  int dh, int dst_stride, void* stream);
+int hp_resize_rois_rgb(const hp_rgb_image* src, int orientation, const hp_roi* rois /* host, upright */, int n, int keep_ratio, int b, int g, int r,
+                       uint8_t* dev_dst, int dw, int dh, int dst_stride, size_t slot_stride, void* stream);
+/* Host only.  Bytes of one pixel (0 for an unknown format); bytes of one tightly packed frame (0 for an invalid format or size) */
+int hp_rgb_pixel_bytes(int format);
+size_t hp_rgb_packed_bytes(int format, int width, int height);
+/* the whole HOST frame as 8-bit BGR, rows bgr_stride bytes apart (>= width * 3; padding bytes are not written): the definition above */
+int hp_rgb_to_bgr_host(const hp_rgb_image* src, uint8_t* bgr, int bgr_stride);
+
 /* ---- writing back: the skeletons of a frame's humans painted into a DEVICE-resident frame, 8-bit BGR or any hp_yuv_image layout in the frame's
  * own colour space and bit depth (hyperpose_amd/csrc/overlay.hip) - the last stage of the reference's stream, draw_human + writer
  * (src/stream.cpp:114-147), for frames that never leave the device.  The picture is defined by exact integer rules, stated once in
@@ -843,6 +877,14 @@ int hp_pipeline_submit_yuv(hp_pipeline* p, int format, const uint8_t* const* fra
  * stream and wait for nobody) and must not be written until that batch has been collected; max_frame_bytes does not apply.  Host planes
  * are re-packed byte by byte, so the even-address / even-stride rule of the 16-bit formats holds for device planes only. */
 int hp_pipeline_submit_yuv_images(hp_pipeline* p, const hp_yuv_image* frames, int n, int on_device);
+/* The same for packed RGB and grey frames ("packed RGB and grey frames" above; the frames of one batch may differ in layout and size).
+ * on_device == 0: `data` is a HOST pointer; each frame goes up ONCE in its own form, hp_rgb_packed_bytes() bytes - from where it lies when it is
+ * tight and pinned, otherwise row by row through the pipe's staging - and max_frame_bytes bounds that number (HP_ERR_CAPACITY; the message names
+ * layout, size and bytes).  on_device != 0: `data` is a DEVICE pointer and nothing is copied; the rules of device planes above hold (complete at the
+ * call, not written until the batch is collected, max_frame_bytes does not apply) and so does the multiple-of-4 rule of the 4-byte layouts.  Then ONE
+ * hp_resize_rgb / hp_resize_rois_rgb per frame: tiling (alignment 1 x 1), orientation and both ensembles work as for every other feed.  These are
+ * 8-bit SDR frames: a tone-map set on the pipeline does not apply to them.  RGB, YUV and BGR submits may alternate with several batches in flight. */
+int hp_pipeline_submit_rgb_images(hp_pipeline* p, const hp_rgb_image* frames, int n, int on_device);
 /* waits for the OLDEST batch in flight; out[i * cap_per_frame + j], n_out[i] for i < *n_frames */
 int hp_pipeline_collect(hp_pipeline* p, hp_human* out, int cap_per_frame, int* n_out, int* n_frames);
 int hp_pipeline_in_flight(const hp_pipeline* p);

@@ -12,7 +12,8 @@
 // the DEVICE exactly as the reference does on the host: cv::resize (INTER_LINEAR) or, with keep_ratio, non_scaling_resize
 // (src/tensorrt.cpp:446-451, src/data.cpp:53-69) through hp_resize_u8c3 / hp_letterbox_u8c3.  Addition: inference / calibrate also take
 // std::vector<yuv420_frame> (NV12 / I420 video frames, utility/data.hpp), converted inside the resize kernel (hp_resize_yuv420), and
-// std::vector<yuv_frame> (every layout, matrix and range of hp_yuv_image, host or device-resident; hp_resize_yuv).
+// std::vector<yuv_frame> (every layout, matrix and range of hp_yuv_image, host or device-resident; hp_resize_yuv) and std::vector<rgb_frame> (packed
+// RGB, BGRA-family and grey frames with a stride, host or device-resident; hp_resize_rgb).
 #pragma once
 #include <atomic>
 #include <cstdint>
@@ -260,6 +261,21 @@ namespace dnn {
             return run_batch(inputs.size());
         }
 
+        /// Addition: the same call for packed RGB, BGRA-family and grey frames (utility/data.hpp, rgb_frame), in host memory or - rgb_frame::on_device -
+        /// device-resident.  A host frame is uploaded once in its own form (hp_rgb_packed_bytes: nothing is repacked to BGR on the host) and brought
+        /// to the network's size by hp_resize_rgb; the maps equal those of the cv::Mat overload on the frames converted with hp_rgb_to_bgr_host, bit
+        /// for bit.  set_orientation and both ensembles act as for every other frame type; a tone-map does not apply (8-bit SDR frames).  Same
+        /// over-size-batch exception, same calibration rule; a description the C ABI refuses is a std::logic_error.
+        std::vector<internal_t> inference(const std::vector<rgb_frame>& inputs)
+        {
+            if (!begin_batch(inputs.size()))
+                return {};
+            std::vector<uint8_t> scratch;
+            for (size_t i = 0; i < inputs.size(); ++i)
+                rgb_image_to_device(inputs[i], m_dev_net + i * net_frame_bytes(), scratch);
+            return run_batch(inputs.size());
+        }
+
         /// Addition: many regions of ONE frame in one call (tiled inference: hyperpose::plan_tiles, to_frame, merge_humans).  One packet per
         /// region, each equal, bit for bit, to inference() of that region cut out into a cv::Mat of its own: the frame goes up once and
         /// all regions are brought to the network's size by one hp_resize_rois_u8c3 call.  regions.size() <= max_batch_size
@@ -302,6 +318,21 @@ namespace dnn {
             return run_batch(rois.size());
         }
 
+        /// The same for an rgb_frame (hp_resize_rois_rgb): regions of any alignment, in upright coordinates under set_orientation.
+        std::vector<internal_t> inference(const rgb_frame& frame, const std::vector<cv::Rect>& regions)
+        {
+            if (!begin_batch(regions.size()))
+                return {};
+            std::vector<uint8_t> scratch;
+            const hp_rgb_image im = rgb_image_on_device(frame, scratch);
+            const std::vector<hp_roi> rois = to_rois(regions);
+            if (hp_resize_rois_rgb(&im, m_orientation, rois.data(), (int)rois.size(), m_keep_ratio ? 1 : 0, 0, 0, 0, m_dev_net, m_inp_size.width,
+                    m_inp_size.height, m_inp_size.width * 3, net_frame_bytes(), hp_engine_stream(m_engine))
+                != HP_OK)
+                throw std::logic_error(hp_last_error());
+            return run_batch(rois.size());
+        }
+
         /// data_type::kINT8: TensorRT's MinMax calibration (an IInt8MinMaxCalibrator fed with these frames).  Frames of any size are brought to
         /// the network's size exactly as inference() does; any number of frames (the engine runs them in max_batch_size chunks).  Replaces
         /// every per-layer activation scale; calibration is never implicit.
@@ -322,6 +353,11 @@ namespace dnn {
         void calibrate(const std::vector<yuv_frame>& frames)
         {
             calibrate_with(frames, [this](const yuv_frame& f, uint8_t* dst, std::vector<uint8_t>& scratch) { yuv_image_to_device(f, dst, scratch); });
+        }
+        /// Addition: calibration from packed RGB / grey frames, brought to the network's size exactly as inference(std::vector<rgb_frame>) does
+        void calibrate(const std::vector<rgb_frame>& frames)
+        {
+            calibrate_with(frames, [this](const rgb_frame& f, uint8_t* dst, std::vector<uint8_t>& scratch) { rgb_image_to_device(f, dst, scratch); });
         }
         /// false for a data_type::kINT8 engine that was neither calibrated nor loaded calibrated
         bool calibrated() const
@@ -532,6 +568,44 @@ namespace dnn {
                 }
                 if (hp_memcpy_h2d(m_dev_raw, scratch.data(), bytes) != HP_OK)
                     fatal(hp_last_error());
+            }
+            return im;
+        }
+        // the same for an rgb_frame: a host frame's rows are packed without padding into ONE upload of hp_rgb_packed_bytes, in its own layout; a
+        // device frame is read where it lies; then hp_resize_rgb writes dst
+        void rgb_image_to_device(const rgb_frame& f, uint8_t* dst, std::vector<uint8_t>& scratch)
+        {
+            const hp_rgb_image im = rgb_image_on_device(f, scratch);
+            const int w = m_inp_size.width, h = m_inp_size.height;
+            if (hp_resize_rgb(&im, m_orientation, m_keep_ratio ? 1 : 0, 0, 0, 0, dst, w, h, w * 3, hp_engine_stream(m_engine)) != HP_OK)
+                throw std::logic_error(hp_last_error());
+            if (hp_engine_synchronize(m_engine) != HP_OK) // m_dev_raw is re-used by the next frame
+                fatal(hp_last_error());
+        }
+        // the checks of an rgb_frame and its description as a kernel reads it: the caller's surface, or the packed copy in m_dev_raw
+        hp_rgb_image rgb_image_on_device(const rgb_frame& f, std::vector<uint8_t>& scratch)
+        {
+            hp_rgb_image im = f.image();
+            const size_t pixel = (size_t)hp_rgb_pixel_bytes(f.format);
+            if (pixel == 0)
+                throw std::logic_error("hyperpose: rgb_frame::format must be one of HP_RGB_BGR24 .. HP_RGB_GRAY8");
+            if (f.empty())
+                throw std::logic_error("hyperpose: empty rgb_frame");
+            const size_t row = (size_t)f.width * pixel, bytes = row * (size_t)f.height;
+            if (f.stride <= 0 || (size_t)f.stride < row)
+                throw std::logic_error("hyperpose: rgb_frame stride smaller than a row");
+            if (!f.on_device) {
+                const uint8_t* src = (const uint8_t*)f.data;
+                if ((size_t)f.stride != row) {
+                    scratch.resize(bytes);
+                    for (int r = 0; r < f.height; ++r)
+                        std::memcpy(scratch.data() + (size_t)r * row, src + (size_t)r * f.stride, row);
+                    src = scratch.data();
+                }
+                reserve_raw(bytes);
+                if (hp_memcpy_h2d(m_dev_raw, src, bytes) != HP_OK)
+                    fatal(hp_last_error());
+                im.data = m_dev_raw, im.stride = (int32_t)row;
             }
             return im;
         }

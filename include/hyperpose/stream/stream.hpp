@@ -134,6 +134,21 @@ public:
         detail::hp_check(hp_pipeline_submit(m_pl, ptrs.data(), ws.data(), hs.data(), (int)frames.size()));
     }
 
+    // Addition: one batch of packed RGB, BGRA-family or grey frames (utility/data.hpp, rgb_frame; hp_pipeline_submit_rgb_images), all in host memory
+    // or all device-resident (rgb_frame::on_device: read where they lie, untouched until the batch has been popped).  Host frames go up in their own
+    // form; nothing is repacked to BGR on the host.  The frames of one batch may differ in layout and size.
+    void push(const std::vector<rgb_frame>& frames)
+    {
+        std::vector<hp_rgb_image> images;
+        bool on_device = !frames.empty() && frames[0].on_device;
+        for (const rgb_frame& f : frames) {
+            if (f.on_device != on_device)
+                throw std::logic_error("hyperpose::hip_stream::push: the rgb_frames of one batch are all in host or all in device memory");
+            images.push_back(f.image());
+        }
+        detail::hp_check(hp_pipeline_submit_rgb_images(m_pl, images.data(), (int)images.size(), on_device ? 1 : 0));
+    }
+
     // the oldest batch's humans, one pose_set per frame
     std::vector<pose_set> pop()
     {

@@ -264,6 +264,39 @@ struct yuv_frame {
     bool empty() const { return !plane[0] || width <= 0 || height <= 0; }
 };
 
+/// Addition: one packed 8-bit frame of any layout the C ABI's hp_rgb_image names (include/hp_hip.h, "packed RGB and grey frames": HP_RGB_BGR24,
+/// _RGB24, _BGRA32, _RGBA32, _ARGB32, _ABGR32, _GRAY8) - what screen capture, compositors, canvases, PIL-style pictures and grey cameras deliver -
+/// with its row stride in bytes, in host memory or - `on_device` - in device memory on the engine's device (read where it lies, nothing is copied;
+/// complete when inference() is called; 4-byte layouts then need an address and a stride that are multiples of 4).  Memory order is as the name
+/// reads, the fourth byte is ignored, grey gives B = G = R.  dnn::tensorrt::inference / calibrate take a vector of these; nothing is repacked on the
+/// host: the layout is read inside the resize kernel.
+struct rgb_frame {
+    int format = HP_RGB_BGR24;
+    int width = 0, height = 0;
+    const void* data = nullptr;
+    int stride = 0; // bytes
+    bool on_device = false;
+
+    rgb_frame() = default;
+    /// a frame whose rows are `stride` bytes apart
+    rgb_frame(int format, const void* data, int width, int height, int stride, bool on_device = false)
+        : format(format), width(width), height(height), data(data), stride(stride), on_device(on_device)
+    {
+    }
+    /// a contiguous, tightly packed frame of hp_rgb_packed_bytes(format, width, height) bytes
+    static rgb_frame packed(int format, const void* data, int width, int height, bool on_device = false)
+    {
+        return rgb_frame(format, data, width, height, width * hp_rgb_pixel_bytes(format), on_device);
+    }
+    hp_rgb_image image() const
+    {
+        hp_rgb_image im;
+        im.format = format, im.width = width, im.height = height, im.data = data, im.stride = stride;
+        return im;
+    }
+    bool empty() const { return !data || width <= 0 || height <= 0; }
+};
+
 // ---- free functions of the reference's data.hpp (:58-67), evaluated by the same device code as the engine's own pre-processing
 namespace detail {
     struct dev_ptr { // scoped hp_malloc
