@@ -70,8 +70,9 @@ def _same(size, k, s, d):
     return total // 2, total - total // 2
 
 
-def _emulate(L, x, blob, s_a, res=None):
-    """The int8 layer L on fp32 NCHW input x (the stored fp16 values): returns v before the fp16 rounding (fp32)."""
+def _emulate(L, x, blob, s_a, res=None, return_acc=False):
+    """The int8 layer L on fp32 NCHW input x (the stored fp16 values): returns v before the fp16 rounding (fp32); `return_acc`: and the
+    exact integer sums (float64)."""
     k, cin, cout = L.kh, L.cin, L.cout
     w = blob[L.w_off:L.w_off + cout * k * k * cin].reshape(cout, k, k, cin).astype(np.float32)
     m = np.abs(w).reshape(cout, -1).max(axis=1)
@@ -99,7 +100,7 @@ def _emulate(L, x, blob, s_a, res=None):
         v = np.where(v > 0, v, v * slope)
     if not L.res_before_act:
         v = v + r
-    return v.astype(np.float32)
+    return (v.astype(np.float32), acc) if return_acc else v.astype(np.float32)
 
 
 def _fp16_gate(got, want16):
@@ -231,6 +232,111 @@ def test_int8_layer_on_signed_tying_saturating_inputs(hp, case):
     assert np.abs(y - v).max() <= 2e-6 * scale + 1e-6, "fused fp32 output copy vs the unrounded emulation"
     tiles = {q["layer"]: q["tile"] for q in eng.profile(n, 1)}
     assert tiles[li] == (8900000 + k if (k in (3, 7) and stride == 1 and cout > 64) else tiles[li]) and 8000000 <= tiles[li] < 9000000, tiles[li]
+
+
+# Sums beyond 2^24.  With random data |acc| stays far below 2^24, where every integer is a float32: a kernel that carried partial sums in fp32
+# would pass every case above.  Here the first layer's outputs are all positive (positive weights, bias 1.3), the scale is set by hand to 2^-6 so
+# that most inputs saturate at 127 and the rest land on 100 .. 126, and the first third of the output channels has the constant weight
+# 127 * 2^-11 in every tap (q_w = 127 everywhere, s_w = 2^-11) and no bias: their acc = 127 * sum q_x, odd as often as not - no float32 above 2^24.
+# dq = 2^-17 is a power of two, so for those channels the contract's v = (float)acc * dq is ONE rounding, the int -> float conversion of the exact
+# sum, and the fused fp32 copy must equal it bit for bit; an fp32 partial sum rounds somewhere else.  (The fp16 store keeps 11 bits and cannot
+# see this: the fp32 copy is the witness.  The other channels keep random weights and the gates above.)
+# (cin, cout, k).  127 * 127 * K must pass 2^24: K >= 1041.  A 1 x 1 layer on 512 channels tops out at 8 258 048 and the first layer cannot feed more than
+# ~600 channels, so the generic kernel's case is 3 x 3 with 64 outputs (K = 1152, conv_i8_kernel: the direct kernel wants more than 64); the direct
+# kernel runs 3 x 3 (18 580 608 at most, reached away from the border) and 7 x 7 on 128 -> 128.
+BIG_SUM_CASES = [(128, 128, 3), (128, 128, 7), (128, 64, 3)]
+BIG_H, BIG_W, BIG_N = 9, 11, 2
+
+
+@pytest.mark.parametrize("cin,cout,k", BIG_SUM_CASES, ids=[f"{a}-{b}-{k}x{k}" for a, b, k in BIG_SUM_CASES])
+def test_int8_sums_beyond_2_to_the_24_are_exact(hp, cin, cout, k):
+    net = Net(cin + k)
+    t0 = net.conv(0, 3, cin, 3, 1)
+    t = net.conv(t0, cin, cout, k, act=E.ACT_NONE)
+    z = net.conv(t, cout, 8, 1)
+    blob = net.blob()
+    L0, L = net.layers[0], net.layers[1]
+    blob[L0.w_off:L0.w_off + cin * 27] = net.rng.uniform(0, 0.12, cin * 27)
+    blob[L0.b_off:L0.b_off + cin] = 1.3
+    third = cout // 3
+    blob[L.w_off:L.w_off + third * k * k * cin] = 127 * 2.0 ** -11
+    blob[L.b_off:L.b_off + third] = 0
+    net.w = [blob]
+    eng = E.Engine(net.layers, [Out("y", t, 0, cout).c(), Out("z", z, 0, 8).c()], blob, BIG_W, BIG_H, BIG_N, dtype="i8")
+    eng.calibrate(_frames(4, BIG_H, BIG_W, seed=99))
+    s = eng.int8_scales
+    assert s[1] > 0
+    s[1] = np.float32(2.0 ** -6)
+    eng.int8_scales = s
+    got = eng.inference(_frames(BIG_N, BIG_H, BIG_W, seed=k))
+    x = eng.debug_tensor(t0, BIG_N)
+    v, acc = _emulate(L, x, blob, s[1], return_acc=True)
+    # conditions on the inputs: saturation with variety, sums beyond 2^24 that are no float32, magnitudes that survive fp16
+    q = x / 2.0 ** -6
+    assert (x > 0).all() and float((q >= 127.5).mean()) >= 0.4 and float((q < 126.5).mean()) >= 0.05, (float((q >= 127.5).mean()), float((q < 126.5).mean()))
+    a3 = acc[:, :third]
+    beyond = (np.abs(a3) > 2 ** 24) & (a3.astype(np.float32).astype(np.float64) != a3)
+    print(f"{cin}->{cout} {k}x{k}: max |acc| {np.abs(a3).max():.0f}, beyond 2^24 and no float32: {float(beyond.mean()):.3f} of the constant channels' elements")
+    assert float(beyond.mean()) >= 0.10
+    assert float(np.abs(v).max()) < 65504
+    _fp16_gate(eng.debug_tensor(t, BIG_N), v.astype(np.float16))
+    y = np.stack([dict(g)["y"] for g in got])
+    scale = float(np.abs(v).max()) + 1e-6
+    assert np.abs(y - v).max() <= 2e-6 * scale + 1e-6, "fused fp32 output copy vs the unrounded emulation"
+    exact = a3.astype(np.float32) * np.float32(2.0 ** -17)
+    assert np.array_equal(v[:, :third], exact)
+    wrong = y[:, :third] != exact
+    assert not wrong.any(), f"{int(wrong.sum())} of {wrong.size} sums are not the exact integer rounded once ({int((wrong & beyond).sum())} of them beyond 2^24)"
+    tiles = {r["layer"]: r["tile"] for r in eng.profile(BIG_N, 1)}
+    assert (tiles[1] == 8900000 + k) if cout > 64 else (8000000 <= tiles[1] < 8900000), tiles[1]
+
+
+@pytest.mark.parametrize("cin,cout,k", [(64, 128, 1), (128, 128, 3), (96, 38, 3)], ids=["1x1", "direct-3x3", "generic-3x3-38ch"])
+def test_int8_channel_of_zero_weights_is_its_bias(hp, cin, cout, k):
+    """max |w| == 0 -> s_w = 1 (no division by zero), q_w = 0, acc = 0: v = 0 * dq + bias, exactly."""
+    net = Net(cin + k)
+    t0 = net.conv(0, 3, cin, 3, 1)
+    t = net.conv(t0, cin, cout, k, act=E.ACT_NONE)
+    z = net.conv(t, cout, 8, 1)
+    blob = net.blob()
+    L = net.layers[1]
+    dead = [0, 5, cout - 1]
+    for c in dead:
+        blob[L.w_off + c * k * k * cin:L.w_off + (c + 1) * k * k * cin] = 0
+    net.w = [blob]
+    eng = E.Engine(net.layers, [Out("y", t, 0, cout).c(), Out("z", z, 0, 8).c()], blob, 29, 23, 2, dtype="i8")
+    eng.calibrate(_frames(4, 23, 29, seed=99))
+    s = eng.int8_scales
+    assert s[1] > 0
+    got = eng.inference(_frames(2, 23, 29, seed=3))
+    bias = blob[L.b_off:L.b_off + cout]
+    y = np.stack([dict(g)["y"] for g in got])
+    stored = eng.debug_tensor(t, 2)
+    for c in dead:
+        assert bias[c] != 0 and (y[:, c] == bias[c]).all() and (stored[:, c] == np.float32(np.float16(bias[c]))).all(), c
+    _fp16_gate(stored, _emulate(L, eng.debug_tensor(t0, 2), blob, s[1]).astype(np.float16))
+
+
+def test_int8_all_zero_calibration_gives_scale_one(hp):
+    """max |x| == 0 -> s_a = 1: all-zero frames through a first layer without bias; the layer's outputs are then exactly its biases."""
+    net = Net(9)
+    t0 = net.conv(0, 3, 64, 3, 1)
+    t = net.conv(t0, 64, 128, 1, act=E.ACT_NONE)
+    z = net.conv(t, 128, 8, 1)
+    blob = net.blob()
+    L0, L = net.layers[0], net.layers[1]
+    blob[L0.b_off:L0.b_off + 64] = 0
+    net.w = [blob]
+    eng = E.Engine(net.layers, [Out("y", t, 0, 128).c(), Out("z", z, 0, 8).c()], blob, 29, 23, 2, dtype="i8")
+    zeros = np.zeros((2, 23, 29, 3), np.uint8)
+    eng.calibrate(zeros)
+    assert eng.int8_scales[1] == 1.0
+    got = eng.inference(zeros)
+    assert not eng.debug_tensor(t0, 2).any()
+    bias = blob[L.b_off:L.b_off + 128]
+    y = np.stack([dict(g)["y"] for g in got])
+    assert np.array_equal(y, np.broadcast_to(bias[None, :, None, None], y.shape))
+    assert np.array_equal(eng.debug_tensor(t, 2), np.broadcast_to(bias.astype(np.float16).astype(np.float32)[None, :, None, None], y.shape))
 
 
 def test_uncovered_geometry_stays_fp16(hp):
