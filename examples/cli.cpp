@@ -40,6 +40,10 @@
 //     runs on it as a device-resident frame, the skeletons are drawn on the device surface (hp::draw_humans, opacity = alpha; alpha == 0 -> 1)
 //     and the annotated frames are appended to <file> as raw frames of the same format; <file>.humans receives, per frame, an int32 count and
 //     that many 292-byte hp_human records in the frame's coordinates (what was drawn).  The PPM output is unchanged.
+//   * map view (addition): `--show_maps=conf|paf` blends the network's own maps - the largest confidence channel, or the longest part-affinity
+//     vector - into the --saving_yuv frames on the device surface (hp::draw_maps: `--maps_palette=jet|heat|grey`, `--maps_alpha=constant|scaled`,
+//     `--maps_opacity=0.5`, `--maps_gain=1`), AFTER the redaction and BEFORE the skeletons.  Operator runtime, --post=paf, no --tiles; refused
+//     from the flags alone without --saving_yuv, with --runtime=stream or with a bad value.
 //   * redaction (addition): `--redact=head|body` pixelates (`--redact_effect=pixelate|black`) the heads or the whole persons on the --saving_yuv
 //     frames, on the device surface (hp::redact_humans: cells of `--redact_cell=16` pixels, regions grown by `--redact_margin=1.0`), BEFORE the
 //     skeletons are drawn on top; `--redact_only` leaves the skeletons out.  Refused from the flags alone without --saving_yuv or with a bad value.
@@ -110,6 +114,10 @@ static bool g_redact = false;
 static std::string FLAGS_rgb; // addition: --rgb=<layout>: feed the engine packed RGB / grey frames (dnn::tensorrt::inference(std::vector<rgb_frame>))
 static int g_rgb_format = -1; // ... parsed: HP_RGB_*, -1 while off
 static hp::redaction g_redaction;
+static std::string FLAGS_show_maps, FLAGS_maps_palette = "jet", FLAGS_maps_alpha = "constant"; // addition: --show_maps=conf|paf on the --saving_yuv frames (hp::map_view)
+static double FLAGS_maps_opacity = 0.5, FLAGS_maps_gain = 1.0;
+static bool g_show_maps = false;
+static hp::map_view g_map_view;
 static int FLAGS_synthetic_humans = 0; // addition: stand-in humans added to every frame's poses (see the head of the file)
 static bool g_yuv_from_file = false; // the frames came from a .yuv source (else --yuv made NV12 ones)
 static int g_yuv_format = HP_YUV_I420, g_yuv_matrix = HP_YUV_BT601, g_yuv_range = HP_YUV_LIMITED;      // the same, parsed
@@ -122,9 +130,10 @@ static bool parse_flags(int argc, char** argv)
     std::map<std::string, std::string*> sflags = { { "model", &FLAGS_model }, { "post", &FLAGS_post }, { "source", &FLAGS_source },
         { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix }, { "saving_yuv", &FLAGS_saving_yuv }, { "tiles", &FLAGS_tiles }, { "yuv_format", &FLAGS_yuv_format },
         { "yuv_matrix", &FLAGS_yuv_matrix }, { "yuv_range", &FLAGS_yuv_range }, { "yuv_transfer", &FLAGS_yuv_transfer },
-        { "scale_ensemble", &FLAGS_scale_ensemble }, { "redact", &FLAGS_redact }, { "redact_effect", &FLAGS_redact_effect }, { "rgb", &FLAGS_rgb } };
+        { "scale_ensemble", &FLAGS_scale_ensemble }, { "redact", &FLAGS_redact }, { "redact_effect", &FLAGS_redact_effect }, { "rgb", &FLAGS_rgb },
+        { "show_maps", &FLAGS_show_maps }, { "maps_palette", &FLAGS_maps_palette }, { "maps_alpha", &FLAGS_maps_alpha } };
     std::map<std::string, double*> dflags = { { "alpha", &FLAGS_alpha }, { "hdr_peak", &FLAGS_hdr_peak }, { "hdr_white", &FLAGS_hdr_white },
-        { "redact_margin", &FLAGS_redact_margin } };
+        { "redact_margin", &FLAGS_redact_margin }, { "maps_opacity", &FLAGS_maps_opacity }, { "maps_gain", &FLAGS_maps_gain } };
     std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size }, { "tile_overlap", &FLAGS_tile_overlap },
         { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h }, { "synthetic_humans", &FLAGS_synthetic_humans }, { "rotate", &FLAGS_rotate },
         { "redact_cell", &FLAGS_redact_cell } };
@@ -267,6 +276,26 @@ static bool parse_flags(int argc, char** argv)
         g_redact = true;
     } else if (FLAGS_redact_only || FLAGS_redact_effect != "pixelate" || FLAGS_redact_cell != 16 || FLAGS_redact_margin != 1.0) {
         cli_log() << "ERROR: --redact_effect / --redact_cell / --redact_margin / --redact_only describe --redact=head|body\n";
+        return false;
+    }
+    // --show_maps and its companions: enumerated names, an opacity in (0, 1], a gain above 0; the companions describe --show_maps
+    if (!FLAGS_show_maps.empty()) {
+        if (!pick("show_maps", FLAGS_show_maps, { { "conf", hp::map_view::max }, { "paf", hp::map_view::field } }, g_map_view.mode)
+            || !pick("maps_palette", FLAGS_maps_palette, { { "jet", hp::map_view::jet }, { "heat", hp::map_view::heat }, { "grey", hp::map_view::grey } }, g_map_view.palette)
+            || !pick("maps_alpha", FLAGS_maps_alpha, { { "constant", hp::map_view::constant }, { "scaled", hp::map_view::scaled } }, g_map_view.alpha))
+            return false;
+        if (!(FLAGS_maps_opacity > 0 && FLAGS_maps_opacity <= 1)) {
+            cli_log() << "ERROR: --maps_opacity=" << FLAGS_maps_opacity << " is outside (0, 1]\n";
+            return false;
+        }
+        if (!(FLAGS_maps_gain > 0 && FLAGS_maps_gain < 1e30)) {
+            cli_log() << "ERROR: --maps_gain=" << FLAGS_maps_gain << " is not a finite number above 0\n";
+            return false;
+        }
+        g_map_view.opacity = (float)FLAGS_maps_opacity, g_map_view.gain = (float)FLAGS_maps_gain;
+        g_show_maps = true;
+    } else if (FLAGS_maps_palette != "jet" || FLAGS_maps_alpha != "constant" || FLAGS_maps_opacity != 0.5 || FLAGS_maps_gain != 1.0) {
+        cli_log() << "ERROR: --maps_palette / --maps_alpha / --maps_opacity / --maps_gain describe --show_maps=conf|paf\n";
         return false;
     }
     return pick("yuv_format", FLAGS_yuv_format, { { "i420", HP_YUV_I420 }, { "nv12", HP_YUV_NV12 }, { "p010", HP_YUV_P010 }, { "i010", HP_YUV_I010 },
@@ -632,6 +661,20 @@ int main(int argc, char** argv)
         cli_log() << "ERROR: --redact=" << FLAGS_redact << " redacts the frames of --saving_yuv=<file>; the PPM pictures are not redacted\n";
         return 1;
     }
+    // --show_maps blends the network's maps into the frames --saving_yuv writes, in the operator runtime (the stream runtime recycles its engine
+    // outputs before the caller holds the humans), from the conf / paf pair of a PAF network, one engine call per frame batch (no tiles)
+    if (g_show_maps && FLAGS_saving_yuv.empty()) {
+        cli_log() << "ERROR: --show_maps=" << FLAGS_show_maps << " shows the maps on the frames of --saving_yuv=<file>; the PPM pictures do not get them\n";
+        return 1;
+    }
+    if (g_show_maps && FLAGS_runtime == kSTREAM) {
+        cli_log() << "ERROR: --show_maps=" << FLAGS_show_maps << " needs --runtime=" kOPERATOR ": with --runtime=" kSTREAM " the engine's outputs are recycled before the humans arrive\n";
+        return 1;
+    }
+    if (g_show_maps && (FLAGS_post != kPAF || !FLAGS_tiles.empty())) {
+        cli_log() << "ERROR: --show_maps=" << FLAGS_show_maps << " shows the conf / paf maps of one engine call per frame: --post=" kPAF " without --tiles\n";
+        return 1;
+    }
     // --flip_ensemble is settled from the flags alone too: the PAF maps are the ones with a left / right channel table
     if (FLAGS_flip_ensemble && FLAGS_post != kPAF) {
         cli_log() << "ERROR: --flip_ensemble merges the maps of a PAF network (--post=" kPAF "), got --post=" << FLAGS_post << "\n";
@@ -837,6 +880,9 @@ int main(int argc, char** argv)
                     // `drawn` stays upright (it is what <file>.humans records); the surface is the stored frame
                     if (g_redact) // first the persons made unrecognisable, then the skeletons on top
                         hp::redact_humans(yuv_batch[k], drawn, g_orient, g_redaction);
+                    if (g_show_maps) // then what the network saw, under the skeletons: maps[k] = (conf, paf) of this frame, still on the device
+                        hp::draw_maps(yuv_batch[k], maps[k][g_map_view.mode == hp::map_view::field ? 1 : 0],
+                            engine.map_cover(hp::oriented_size(batch[k].size(), g_orient)), g_orient, g_map_view);
                     if (!FLAGS_redact_only) {
                         if (g_hdr_on)
                             hp::draw_humans(yuv_batch[k], drawn, g_orient, g_hdr, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);

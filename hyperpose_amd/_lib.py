@@ -89,6 +89,19 @@ class Roi(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32)]
 
 
+class MapViewDesc(C.Structure):
+    """hp_mapview_desc"""
+    _fields_ = [("maps", C.c_void_p), ("C", C.c_int32), ("mh", C.c_int32), ("mw", C.c_int32), ("frame", C.c_int32), ("c0", C.c_int32), ("cn", C.c_int32),
+                ("c_step", C.c_int32), ("mode", C.c_int32), ("gain", C.c_float), ("cover_x", C.c_double), ("cover_y", C.c_double),
+                ("orientation", C.c_int32), ("roi", Roi), ("has_roi", C.c_int32)]
+
+
+HP_MAPVIEW_MAX, HP_MAPVIEW_FIELD = 0, 1
+MAPVIEW_MODES = {"max": HP_MAPVIEW_MAX, "field": HP_MAPVIEW_FIELD}
+MAPVIEW_PALETTES = {"jet": 0, "heat": 1, "grey": 2}
+MAPVIEW_ALPHAS = {"constant": 0, "scaled": 1}
+
+
 class FlipOutput(C.Structure):
     """hp_flip_output"""
     _fields_ = [("output", C.c_int32), ("perm", C.POINTER(C.c_int32)), ("sign", C.POINTER(C.c_int8))]
@@ -133,6 +146,8 @@ SYMBOLS = [
     "hp_overlay_create", "hp_overlay_destroy", "hp_overlay_primitives", "hp_yuv_colours", "hp_overlay_draw_u8c3", "hp_overlay_draw_yuv",
     "hp_overlay_draw_u8c3_host", "hp_overlay_draw_yuv_host",
     "hp_redact_create", "hp_redact_destroy", "hp_redact_regions", "hp_redact_u8c3", "hp_redact_yuv", "hp_redact_u8c3_host", "hp_redact_yuv_host",
+    "hp_mapview_create", "hp_mapview_destroy", "hp_mapview_cover", "hp_mapview_taps", "hp_mapview_palette", "hp_mapview_palette_yuv",
+    "hp_mapview_draw_u8c3", "hp_mapview_draw_yuv", "hp_mapview_draw_u8c3_host", "hp_mapview_draw_yuv_host", "hp_mapview_index_host", "hp_mapview_debug_plane",
     "hp_paf_create", "hp_paf_stream", "hp_paf_destroy", "hp_paf_set_conf_thresh", "hp_paf_set_paf_thresh", "hp_paf_process_batch",
     "hp_paf_enqueue", "hp_paf_collect", "hp_paf_debug_peaks", "hp_paf_debug_conns", "hp_paf_debug_maps", "hp_paf_debug_sort",
     "hp_pifpaf_create", "hp_pifpaf_destroy", "hp_pifpaf_process_batch", "hp_pifpaf_stream", "hp_pifpaf_enqueue", "hp_pifpaf_collect", "hp_pifpaf_decode_flags",

@@ -1,5 +1,5 @@
-// annotate.hpp — what the units that write into device-resident frames (overlay.hip, redact.hip; a further annotator is a kernel and its rules
-// on top of this) share on the host: the ring that takes a call's list to the device, and the argument checks of a frame.
+// annotate.hpp — what the units that write into device-resident frames (overlay.hip, redact.hip, mapview.hip; a further annotator is a kernel and
+// its rules on top of this) share on the host: the ring that takes a call's list or tables to the device, and the argument checks of a frame.
 #pragma once
 #include "hp_common.hpp"
 #include "part_points.hpp"

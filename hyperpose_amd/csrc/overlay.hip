@@ -36,6 +36,7 @@
 #include "annotate.hpp"
 #include "overlay.hpp"
 #include "tonemap.hpp"
+#include "yuv_colour.hpp"
 #include "yuv_formats.hpp"
 
 #include <algorithm>
@@ -88,18 +89,8 @@ int build_primitives(const hp_human* humans, int n, int w, int h, int thickness,
 
 int yuv_colours(int matrix, int range, int depth, int32_t out[19][3])
 {
-    static const double KR[3] = { 0.299, 0.2126, 0.2627 }, KB[3] = { 0.114, 0.0722, 0.0593 };
-    const double kr = KR[matrix], kb = KB[matrix], kg = 1. - kr - kb;
-    const double top = (double)((1 << depth) - 1), up = (double)(1 << (depth - 8)), half = (double)(1 << (depth - 1));
-    auto clip = [&](double v) { return (int32_t)std::min(top, std::max(0., std::nearbyint(v))); };
-    for (int i = 0; i < 19; ++i) {
-        const double r = COCO_COLOURS_RGB[i][0] / 255., g = COCO_COLOURS_RGB[i][1] / 255., b = COCO_COLOURS_RGB[i][2] / 255.;
-        const double y = kr * r + kg * g + kb * b, cb = (b - y) / (2. * (1. - kb)), cr = (r - y) / (2. * (1. - kr));
-        if (range == HP_YUV_LIMITED)
-            out[i][0] = clip((16. + 219. * y) * up), out[i][1] = clip((128. + 224. * cb) * up), out[i][2] = clip((128. + 224. * cr) * up);
-        else
-            out[i][0] = clip(y * top), out[i][1] = clip(half + cb * top), out[i][2] = clip(half + cr * top);
-    }
+    for (int i = 0; i < 19; ++i) // the formulas: yuv_colour.hpp
+        hp_yuv::colour_of(COCO_COLOURS_RGB[i][0], COCO_COLOURS_RGB[i][1], COCO_COLOURS_RGB[i][2], matrix, range, depth, out[i]);
     return HP_OK;
 }
 

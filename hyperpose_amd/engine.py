@@ -323,6 +323,12 @@ class Engine:
         check(lib().hp_engine_output_to_host(self._h, i, n, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    def output_device(self, i: int):
+        """(device address, (C, H, W)) of output ``i``: fp32 ``[max_batch][C][H][W]``, valid on the engine's stream after an enqueue (what
+        ``frontend.draw_maps`` reads where it lies)."""
+        _, shape, dev = self.outputs[i]
+        return dev, shape
+
     # ---- reference-shaped API
     def inference(self, frames: np.ndarray):
         """u8 HWC BGR frames [n,h,w,3] (network-sized) -> list (per image) of list of (name, fp32 array [C,H,W])."""

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (HDR_DEFAULT_PEAK, HDR_DEFAULT_WHITE, HDR_TRANSFERS, HUMAN_DTYPE, OVERLAY_PRIM_DTYPE, REDACT_EFFECTS, REDACT_REGION_DTYPE, REDACT_WHAT,
+from ._lib import (HDR_DEFAULT_PEAK, HDR_DEFAULT_WHITE, HDR_TRANSFERS, HUMAN_DTYPE, MAPVIEW_ALPHAS, MAPVIEW_MODES, MAPVIEW_PALETTES, MapViewDesc, OVERLAY_PRIM_DTYPE, REDACT_EFFECTS, REDACT_REGION_DTYPE, REDACT_WHAT,
                    TILING_DEFAULT_MIN_COMMON, TILING_DEFAULT_TOL, YUV_FORMATS, YUV_LAYOUTS, YUV_MATRICES, YUV_RANGES, DevBuf, HdrDesc, Human, OverlayPrim,
                    RedactRegion, RGB_LAYOUTS, RgbImage, Roi, Tiling, YuvImage, as_ptr, check, lib)
 
@@ -702,3 +702,111 @@ def redact_host(frame, regions, fmt=None, matrix: str = "bt601", range: str = "l
         return
     im = _host_image(frame, fmt, matrix, range, written=True)
     check(lib().hp_redact_yuv_host(C.byref(im), rp, len(rs), REDACT_EFFECTS[effect], int(cell)))
+
+
+# ---- writing back: the network's own maps shown on the frame (hp_mapview_*; the rules are stated in csrc/mapview.hpp and DESIGN.md 1.1) ----
+
+def map_cover(frame_w: int, frame_h: int, in_w: int, in_h: int, keep_ratio: bool = True):
+    """``hp_mapview_cover``: (cover_x, cover_y), the fractions of the network's ``in_w`` x ``in_h`` input - and so of the maps' cells - that an
+    upright ``frame_w`` x ``frame_h`` frame fills: the letterbox's inner size over the input size, or (1, 1) for a plain resize."""
+    out = (C.c_double * 2)()
+    check(lib().hp_mapview_cover(int(frame_w), int(frame_h), int(in_w), int(in_h), int(bool(keep_ratio)), out))
+    return out[0], out[1]
+
+
+def map_taps(U: int, m: int, cover: float = 1.0) -> np.ndarray:
+    """``hp_mapview_taps``: int32 [U, 3], per upright pixel of an axis the two map cells it samples and the weight (of 2048) of the second."""
+    out = np.zeros((max(1, int(U)), 3), np.int32)
+    check(lib().hp_mapview_taps(int(U), int(m), C.c_double(cover), out.ctypes.data_as(C.c_void_p)))
+    return out[:U]
+
+
+def map_palette(kind="jet", alpha: str = "constant", matrix=None, range: str = "limited", depth: int = 8) -> np.ndarray:
+    """``hp_mapview_palette``: int32 [256, 4], the built-in palette ``kind`` ("jet", "heat", "grey") as (R, G, B, A), A = 255 ("constant") or the
+    index ("scaled").  With ``matrix``: the ``depth``-bit (Y, U, V, A) a frame of that matrix and range is painted with
+    (``hp_mapview_palette_yuv``); ``kind`` may then also be a caller's own [256, 4] (R, G, B, A) table."""
+    if isinstance(kind, str):
+        rgba = np.zeros((256, 4), np.int32)
+        check(lib().hp_mapview_palette(MAPVIEW_PALETTES[kind], MAPVIEW_ALPHAS[alpha], rgba.ctypes.data_as(C.c_void_p)))
+    else:
+        rgba = _palette(kind)
+    if matrix is None:
+        return rgba
+    out = np.zeros((256, 4), np.int32)
+    check(lib().hp_mapview_palette_yuv(rgba.ctypes.data_as(C.c_void_p), YUV_MATRICES[matrix], YUV_RANGES[range], int(depth), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def _palette(palette) -> np.ndarray:
+    p = map_palette(palette) if isinstance(palette, str) else np.ascontiguousarray(palette, np.int32)
+    assert p.shape == (256, 4)
+    return p
+
+
+def _map_desc(maps_ptr, shape, frame, mode, channels, gain, cover, orientation, roi) -> MapViewDesc:
+    """``hp_mapview_desc``; ``channels`` is (c0, cn, c_step) or None = every channel (every pair, for "field")"""
+    C_, mh, mw = (int(v) for v in shape)
+    field = MAPVIEW_MODES[mode] == MAPVIEW_MODES["field"]
+    c0, cn, step = channels if channels is not None else (0, C_ // 2 if field else C_, 2 if field else 1)
+    d = MapViewDesc(maps_ptr, C_, mh, mw, int(frame), int(c0), int(cn), int(step), MAPVIEW_MODES[mode], float(gain), float(cover[0]), float(cover[1]),
+                    int(orientation))
+    if roi is not None:
+        d.roi, d.has_roi = Roi(*(int(v) for v in roi)), 1
+    return d
+
+
+def map_index_host(maps, frame: int = 0, mode: str = "max", channels=None, gain: float = 1.0) -> np.ndarray:
+    """``hp_mapview_index_host``: uint8 [mh, mw], the index plane of frame ``frame`` of ``maps`` (float32 [frames, C, mh, mw] in host memory)."""
+    maps = np.ascontiguousarray(maps, np.float32)
+    assert maps.ndim == 4
+    d = _map_desc(maps.ctypes.data, maps.shape[1:], frame, mode, channels, gain, (1.0, 1.0), 0, None)
+    out = np.zeros(maps.shape[2:], np.uint8)
+    check(lib().hp_mapview_index_host(C.byref(d), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+class MapView(_Handle):
+    """``hp_mapview``: the handle the device entry points draw through (staging slots for maps of up to ``max_map_cells`` cells)."""
+    NAME = "mapview"
+
+    def __init__(self, max_map_cells: int = 1 << 16):
+        self.max_map_cells = int(max_map_cells)
+        super().__init__(self.max_map_cells)
+
+    def debug_plane(self) -> np.ndarray:
+        """``hp_mapview_debug_plane``: the index plane of the last draw call, flat (synchronises the device)"""
+        out = np.zeros(self.max_map_cells, np.uint8)
+        n = check(lib().hp_mapview_debug_plane(self.h, out.ctypes.data_as(C.c_void_p), len(out)))
+        return out[:n]
+
+
+def draw_maps(target, maps_dev, shape, frame: int = 0, mode: str = "max", palette="jet", opacity: float = 0.5, gain: float = 1.0, channels=None,
+              cover=(1.0, 1.0), orientation: int = 0, roi=None, w=None, h=None, stride=None, stream=None, view=None) -> None:
+    """Blend the colour-mapped, up-sampled maps of one frame into that frame in DEVICE memory, in place and stream-ordered.  ``maps_dev``: device
+    address of fp32 [frames, C, mh, mw] (``Engine.output_device``), ``shape`` = (C, mh, mw); ``mode`` "max" (confidence maps) or "field" (channel
+    pairs are vectors: part-affinity fields); ``palette`` a built-in name or an int [256, 4] (R, G, B, A) table; ``channels`` (c0, cn, c_step) or
+    None for all; ``cover`` from ``map_cover``; ``roi`` (x, y, w, h) in stored pixels.  ``target`` is a ``YuvImage`` whose planes are device
+    pointers (``hp_mapview_draw_yuv``) or a device buffer of 8-bit BGR with ``w``, ``h`` and optionally ``stride`` (``hp_mapview_draw_u8c3``)."""
+    d = _map_desc(as_ptr(maps_dev).value, shape, frame, mode, channels, gain, cover, orientation, roi)
+    mv = view or _default_handle(MapView, 1 << 16, d.mh * d.mw)
+    pal, s = _palette(palette), C.c_void_p(stream) if stream else None
+    pp = pal.ctypes.data_as(C.c_void_p)
+    if isinstance(target, YuvImage):
+        check(lib().hp_mapview_draw_yuv(mv.h, C.byref(target), C.byref(d), pp, C.c_float(opacity), s))
+    else:
+        check(lib().hp_mapview_draw_u8c3(mv.h, as_ptr(target), int(w), int(h), int(stride or w * 3), C.byref(d), pp, C.c_float(opacity), s))
+
+
+def draw_maps_host(frame, maps, fmt=None, matrix: str = "bt601", range: str = "limited", index: int = 0, mode: str = "max", palette="jet",
+                   opacity: float = 0.5, gain: float = 1.0, channels=None, cover=(1.0, 1.0), orientation: int = 0, roi=None) -> None:
+    """The same picture with frame and maps in HOST memory, in place, no device needed: ``frame`` is a uint8 array [h, w, 3] (BGR, ``fmt`` None) or
+    the list of 2-D plane arrays ``yuv_planes`` returns; ``maps`` float32 [frames, C, mh, mw], of which frame ``index`` is shown."""
+    maps = np.ascontiguousarray(maps, np.float32)
+    assert maps.ndim == 4
+    d = _map_desc(maps.ctypes.data, maps.shape[1:], index, mode, channels, gain, cover, orientation, roi)
+    pp = _palette(palette).ctypes.data_as(C.c_void_p)
+    if fmt is None:
+        check(lib().hp_mapview_draw_u8c3_host(*_host_bgr(frame), C.byref(d), pp, C.c_float(opacity)))
+        return
+    im = _host_image(frame, fmt, matrix, range, written=True)
+    check(lib().hp_mapview_draw_yuv_host(C.byref(im), C.byref(d), pp, C.c_float(opacity)))

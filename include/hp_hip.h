@@ -439,6 +439,72 @@ int hp_redact_yuv(hp_redact* r, const hp_yuv_image* frame /* planes in DEVICE me
 int hp_redact_u8c3_host(uint8_t* bgr, int w, int h, int stride, const hp_redact_region* regions, int n, int effect, int cell);
 int hp_redact_yuv_host(const hp_yuv_image* frame, const hp_redact_region* regions, int n, int effect, int cell);
 
+/* ---- map view: what the network itself produced - confidence maps, part-affinity fields - colour-mapped, up-sampled and blended into a DEVICE-
+ * resident frame, 8-bit BGR or any hp_yuv_image layout in the frame's own matrix, range and bit depth (hyperpose_amd/csrc/mapview.hip): do the maps
+ * light up on the people?  The third annotator, and the dense one: it rewrites the whole region.  The picture is defined by exact rules, stated once
+ * in hyperpose_amd/csrc/mapview.hpp and DESIGN.md 1.1 "Map view":
+ *   index plane  the frame's maps [C][mh][mw] (fp32) -> uint8 [mh][mw], fp32 without fused operations, channels c_k = c0 + k * c_step, k < cn.
+ *                HP_MAPVIEW_MAX: m = 0; per channel: if (v > m) m = v (NaN and negatives leave m alone).  HP_MAPVIEW_FIELD: channel pairs (c_k,
+ *                c_k + 1) are (x, y) of a vector field; e = ax * ax + ay * ay; if (e > m2) m2 = e; m = sqrt(m2) correctly rounded.  Then
+ *                t = m * gain; t = t < 1.f ? t : 1.f; q = (int)rintf(t * 255.f).
+ *   taps         hp_mapview_taps, host doubles: the frame covers the fraction `cover` in (0, 1] of the m cells of an axis (hp_mapview_cover: iw /
+ *                (double)dw of hp_letterbox_inner for a letter-boxed slot, else 1).  For U upright pixels scale = (cover * m) / U, s = (u + 0.5) *
+ *                scale - 0.5; s < 0: {0, 0, 0}; else i = floor(s): { min(i, m - 1), min(i + 1, m - 1), (int)nearbyint((s - i) * 2048) } - the
+ *                half-pixel convention of the parser's up-sampling, so a blob lies under the key point drawn from it.
+ *   pixel index  int32: top = p[y0][x0] * (2048 - wx) + p[y0][x1] * wx, bot the same on row y1, idx = (top * (2048 - wy) + bot * wy + (1 << 21)) >> 22.
+ *   geometry     roi in stored pixels inside the frame (has_roi == 0: the whole frame); with the HP_ORIENT_* code's (swap, flip_x, flip_y) and a
+ *                stored pixel (lx, ly) local to the w x h roi: a = flip_x ? w - 1 - lx : lx, b = flip_y ? h - 1 - ly : ly, (ux, uy) = swap ? (b, a) :
+ *                (a, b); the x table has swap ? h : w entries over mw with cover_x, the y table the other count over mh with cover_y.
+ *   palette      256 entries (R, G, B, A) in [0, 255].  hp_mapview_palette: float64, t = i / 255, nearbyint(255 * clamp01(c)); JET r = 1.5 - |4t - 3|,
+ *                g = 1.5 - |4t - 2|, b = 1.5 - |4t - 1|; HEAT r = 3t, g = 3t - 1, b = 3t - 2; GREY r = g = b = t; A = 255 (ALPHA_CONSTANT) or i
+ *                (ALPHA_SCALED).  A YUV frame: each entry through hp_yuv_colours' formulas at the frame's matrix / range / depth
+ *                (hp_mapview_palette_yuv: out = (Y, U, V, A)).  SDR formulas only: a PQ / HLG frame gets them at depth 10, graphics white is out of scope.
+ *   samples      W = nearbyint(opacity * 256), opacity in (0, 1]; w = (W * A[idx] + 127) / 255; a B / G / R or luma sample with w > 0 becomes
+ *                (c * w + old * (256 - w) + 128) >> 8 on code values (P010: word >> 6, stored << 6; I010: & 1023); a chroma sample takes the largest
+ *                idx among its 1 x 1 / 2 x 1 / 2 x 2 pixels that lie in the roi and blends U and V with that idx's weight; weight 0 or no pixel in
+ *                the roi: the sample keeps its value.  No byte outside the roi's samples is read or written (row padding included).
+ * The bilinear rule above is the only up-sampling; there is no blur.  The handle owns pinned staging slots and device slots (palette, the two tap
+ * tables, the index plane) for maps of up to max_map_cells cells; a draw call only ENQUEUES on `stream` (NULL = the default stream): one copy, two
+ * launches, one event.  `maps` is a DEVICE pointer laid out as hp_engine_output's [frame][C][mh][mw] and must stay valid until the stream has run
+ * the call.  Frames follow hp_resize_yuv's rules, width and height at most 8192.  HP_ERR_INVALID, with a message that names the value, nothing
+ * launched and the frame untouched: opacity outside (0, 1]; gain not finite or <= 0; a cover outside (0, 1]; cn < 1 or c_step < 1; a channel (FIELD:
+ * a pair's second channel) >= C; mh * mw > max_map_cells; frame < 0; an unknown mode or orientation; a roi empty or not inside the frame; a
+ * palette value outside [0, 255]. */
+enum { HP_MAPVIEW_MAX = 0, HP_MAPVIEW_FIELD = 1 };
+enum { HP_MAPVIEW_JET = 0, HP_MAPVIEW_HEAT = 1, HP_MAPVIEW_GREY = 2 };
+enum { HP_MAPVIEW_ALPHA_CONSTANT = 0, HP_MAPVIEW_ALPHA_SCALED = 1 };
+typedef struct hp_mapview_desc {
+    const float* maps;              /* [frames][C][mh][mw], fp32 */
+    int32_t C, mh, mw;
+    int32_t frame;                  /* which frame of the batch */
+    int32_t c0, cn, c_step, mode;   /* the channel choice; HP_MAPVIEW_MAX or HP_MAPVIEW_FIELD */
+    float gain;
+    double cover_x, cover_y;        /* hp_mapview_cover */
+    int32_t orientation;            /* HP_ORIENT_*: how the frame is stored */
+    hp_roi roi;                     /* stored pixels; read when has_roi != 0 */
+    int32_t has_roi;
+} hp_mapview_desc;
+typedef struct hp_mapview hp_mapview;
+int hp_mapview_create(hp_mapview** out, int max_map_cells);
+void hp_mapview_destroy(hp_mapview* v);
+/* host only.  cover: the fractions of the network's input a frame_w x frame_h (upright) frame fills, and so of the maps' cells */
+int hp_mapview_cover(int frame_w, int frame_h, int in_w, int in_h, int keep_ratio, double cover[2]);
+int hp_mapview_taps(int U, int m, double cover, int32_t (*out)[3]); /* U entries (i0, i1, weight); U in 1 .. 8192, m in 1 .. 65535 */
+int hp_mapview_palette(int kind, int alpha_mode, int32_t out[256][4]);
+int hp_mapview_palette_yuv(const int32_t rgba[256][4], int matrix, int range, int depth, int32_t out[256][4]);
+/* device frames, written in place */
+int hp_mapview_draw_u8c3(hp_mapview* v, uint8_t* dev_bgr, int w, int h, int stride, const hp_mapview_desc* d, const int32_t palette[256][4],
+                         float opacity, void* stream);
+int hp_mapview_draw_yuv(hp_mapview* v, const hp_yuv_image* frame /* planes in DEVICE memory, WRITTEN */, const hp_mapview_desc* d,
+                        const int32_t palette[256][4], float opacity, void* stream);
+/* the same picture with maps and frame in HOST memory (plain C++, the rules above; no device needed); hp_mapview_index_host: the index plane
+ * alone, mh * mw bytes */
+int hp_mapview_draw_u8c3_host(uint8_t* bgr, int w, int h, int stride, const hp_mapview_desc* d, const int32_t palette[256][4], float opacity);
+int hp_mapview_draw_yuv_host(const hp_yuv_image* frame, const hp_mapview_desc* d, const int32_t palette[256][4], float opacity);
+int hp_mapview_index_host(const hp_mapview_desc* d, uint8_t* out);
+/* tests: synchronises the device, then copies the index plane of the handle's last draw call (at most cap bytes); returns its size in cells */
+int hp_mapview_debug_plane(hp_mapview* v, uint8_t* out, int cap);
+
 /* ---- hyperpose::parser::paf (include/hyperpose/operator/parser/paf.hpp:17-93, src/paf.cpp) -------- */
 typedef struct hp_paf hp_paf;
 

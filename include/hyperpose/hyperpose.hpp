@@ -7,5 +7,6 @@
 #include "stream/stream.hpp"
 #include "utility/data.hpp"
 #include "utility/human.hpp"
+#include "utility/map_view.hpp"
 #include "utility/overlay.hpp"
 #include "utility/redact.hpp"

@@ -15,6 +15,7 @@
 // std::vector<yuv_frame> (every layout, matrix and range of hp_yuv_image, host or device-resident; hp_resize_yuv) and std::vector<rgb_frame> (packed
 // RGB, BGRA-family and grey frames with a stride, host or device-resident; hp_resize_rgb).
 #pragma once
+#include <array>
 #include <atomic>
 #include <cstdint>
 #include <cstdlib>
@@ -408,6 +409,15 @@ namespace dnn {
         }
         hp_engine* handle() { return m_engine; }
         bool keep_ratio() const { return m_keep_ratio; }
+        /// Addition (utility/map_view.hpp): the fractions (x, y) of the network's input - and so of its output maps - that an UPRIGHT frame of
+        /// `frame` pixels fills: the letterbox's inner size over the input size under keep_ratio, (1, 1) otherwise (hp_mapview_cover)
+        std::array<double, 2> map_cover(cv::Size frame) const
+        {
+            std::array<double, 2> cover { 1., 1. };
+            if (hp_mapview_cover(frame.width, frame.height, m_inp_size.width, m_inp_size.height, m_keep_ratio ? 1 : 0, cover.data()) != HP_OK)
+                throw std::invalid_argument(hp_last_error());
+            return cover;
+        }
 
         /// frames or regions one inference() call takes: max_batch_size(), half of it while the flip ensemble is on, 1 / K of that under the scale ensemble
         size_t batch_room() const { return (size_t)m_max_batch_size / (flip_ensemble() ? 2 : 1) / scale_ensemble(); }
