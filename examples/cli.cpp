@@ -16,7 +16,8 @@
 //     hyperpose::rgb_frame of that layout (hp_rgb_image: read by the fused resize, nothing is repacked for the engine).  The frame is made on the host
 //     from the BGR picture: alpha 255, grey = (B + 2 G + R + 2) >> 2.  `--source=<file>.rgb` reads raw frames of `--yuv_w` x `--yuv_h` in that layout,
 //     back to back.  Operator runtime (as --yuv); refused from the flags alone: an unknown name, --rgb with --yuv or a .yuv source, --saving_yuv or
-//     --redact with --rgb (drawing and redaction have no RGB targets), a .rgb source without --rgb.
+//     --redact with --rgb (drawing and redaction have no RGB targets; --redact is allowed where --encode_yuv makes the target), a .rgb source
+//     without --rgb.
 //   * HDR video (addition): `--yuv_transfer=sdr|pq|hlg` (default sdr) `[--hdr_peak=<cd/m2> --hdr_white=<cd/m2> --hdr_keep_primaries]`, only with
 //     a .yuv source in a 10-bit layout (`--yuv_format=p010|i010`): the frames are HDR10 (pq) or HLG and are tone-mapped to SDR sRGB inside the
 //     fused resize (engine.set_tonemap; hp::hdr, defaults 1000 / 203, BT.2020 primaries converted to BT.709 unless --hdr_keep_primaries); the
@@ -47,6 +48,13 @@
 //   * redaction (addition): `--redact=head|body` pixelates (`--redact_effect=pixelate|black`) the heads or the whole persons on the --saving_yuv
 //     frames, on the device surface (hp::redact_humans: cells of `--redact_cell=16` pixels, regions grown by `--redact_margin=1.0`), BEFORE the
 //     skeletons are drawn on top; `--redact_only` leaves the skeletons out.  Refused from the flags alone without --saving_yuv or with a bad value.
+//   * encoder hand-off (addition): `--encode_yuv=<file> [--encode_format=nv12 --encode_matrix=bt709 --encode_range=limited --encode_align=2]`, for
+//     picture sources and `--rgb=<layout>` / .rgb sources: every frame is uploaded in its own layout (BGR24 pictures, or the --rgb layout),
+//     converted on the device to the frame an encoder takes (hp::to_yuv: any --yuv_format name, the stream's matrix and range, the size rounded up to
+//     --encode_align and to what the layout needs, by edge replication), `--redact` and the skeletons are applied on that surface as --saving_yuv
+//     applies them, and the frame is appended to <file>; <file>.humans is written as --saving_yuv writes it (the records are normalised to the
+//     source frame, without the padding).  Operator runtime.  Refused from the flags alone: with --yuv or a .yuv source (those have --saving_yuv),
+//     an unknown name, --encode_align outside 1 .. 256, the companions without --encode_yuv.
 //   * `--synthetic_humans=<n>` (addition, default 0): n seeded stand-in humans are added to every frame's parser output before anything is drawn -
 //     the built-in models carry synthetic weights and find nobody, so this is what makes a demonstration (or a test) of the drawing paths show
 //     something; operator runtime only.  A warning says that the pictures and the count are not the model's result.
@@ -118,6 +126,9 @@ static std::string FLAGS_show_maps, FLAGS_maps_palette = "jet", FLAGS_maps_alpha
 static double FLAGS_maps_opacity = 0.5, FLAGS_maps_gain = 1.0;
 static bool g_show_maps = false;
 static hp::map_view g_map_view;
+static std::string FLAGS_encode_yuv, FLAGS_encode_format = "nv12", FLAGS_encode_matrix = "bt709", FLAGS_encode_range = "limited"; // addition: --encode_yuv=<file> (hp::to_yuv)
+static int FLAGS_encode_align = 2;
+static int g_encode_format = HP_YUV_NV12, g_encode_matrix = HP_YUV_BT709, g_encode_range = HP_YUV_LIMITED; // ... parsed
 static int FLAGS_synthetic_humans = 0; // addition: stand-in humans added to every frame's poses (see the head of the file)
 static bool g_yuv_from_file = false; // the frames came from a .yuv source (else --yuv made NV12 ones)
 static int g_yuv_format = HP_YUV_I420, g_yuv_matrix = HP_YUV_BT601, g_yuv_range = HP_YUV_LIMITED;      // the same, parsed
@@ -131,12 +142,13 @@ static bool parse_flags(int argc, char** argv)
         { "runtime", &FLAGS_runtime }, { "saving_prefix", &FLAGS_saving_prefix }, { "saving_yuv", &FLAGS_saving_yuv }, { "tiles", &FLAGS_tiles }, { "yuv_format", &FLAGS_yuv_format },
         { "yuv_matrix", &FLAGS_yuv_matrix }, { "yuv_range", &FLAGS_yuv_range }, { "yuv_transfer", &FLAGS_yuv_transfer },
         { "scale_ensemble", &FLAGS_scale_ensemble }, { "redact", &FLAGS_redact }, { "redact_effect", &FLAGS_redact_effect }, { "rgb", &FLAGS_rgb },
-        { "show_maps", &FLAGS_show_maps }, { "maps_palette", &FLAGS_maps_palette }, { "maps_alpha", &FLAGS_maps_alpha } };
+        { "show_maps", &FLAGS_show_maps }, { "maps_palette", &FLAGS_maps_palette }, { "maps_alpha", &FLAGS_maps_alpha },
+        { "encode_yuv", &FLAGS_encode_yuv }, { "encode_format", &FLAGS_encode_format }, { "encode_matrix", &FLAGS_encode_matrix }, { "encode_range", &FLAGS_encode_range } };
     std::map<std::string, double*> dflags = { { "alpha", &FLAGS_alpha }, { "hdr_peak", &FLAGS_hdr_peak }, { "hdr_white", &FLAGS_hdr_white },
         { "redact_margin", &FLAGS_redact_margin }, { "maps_opacity", &FLAGS_maps_opacity }, { "maps_gain", &FLAGS_maps_gain } };
     std::map<std::string, int*> iflags = { { "w", &FLAGS_w }, { "h", &FLAGS_h }, { "max_batch_size", &FLAGS_max_batch_size }, { "tile_overlap", &FLAGS_tile_overlap },
         { "yuv_w", &FLAGS_yuv_w }, { "yuv_h", &FLAGS_yuv_h }, { "synthetic_humans", &FLAGS_synthetic_humans }, { "rotate", &FLAGS_rotate },
-        { "redact_cell", &FLAGS_redact_cell } };
+        { "redact_cell", &FLAGS_redact_cell }, { "encode_align", &FLAGS_encode_align } };
     std::map<std::string, bool*> bflags = { { "imshow", &FLAGS_imshow }, { "keep_ratio", &FLAGS_keep_ratio }, { "logging", &FLAGS_logging }, { "half", &FLAGS_half }, { "int8", &FLAGS_int8 }, { "yuv", &FLAGS_yuv }, { "tile_full", &FLAGS_tile_full },
         { "hdr_keep_primaries", &FLAGS_hdr_keep_primaries }, { "hflip", &FLAGS_hflip }, { "flip_ensemble", &FLAGS_flip_ensemble },
         { "redact_only", &FLAGS_redact_only } };
@@ -251,12 +263,32 @@ static bool parse_flags(int argc, char** argv)
             cli_log() << "ERROR: --rgb=" << FLAGS_rgb << " and --yuv (or a .yuv source) both say how the engine is fed: give one\n";
             return false;
         }
-        if (!FLAGS_saving_yuv.empty() || !FLAGS_redact.empty()) {
+        if (!FLAGS_saving_yuv.empty() || (!FLAGS_redact.empty() && FLAGS_encode_yuv.empty())) { // (--encode_yuv makes the frames --redact rewrites)
             cli_log() << "ERROR: --saving_yuv and --redact write video frames; with --rgb=" << FLAGS_rgb << " there is none (drawing and redaction have no RGB targets)\n";
             return false;
         }
     } else if (rgb_file) {
         cli_log() << "ERROR: a .rgb source holds raw frames: say their layout with --rgb=<rgb24|bgr24|bgra|rgba|argb|abgr|gray> (and --yuv_w, --yuv_h)\n";
+        return false;
+    }
+    // --encode_yuv and its companions: enumerated names, an alignment in [1, 256], a source that is not video already
+    if (!FLAGS_encode_yuv.empty()) {
+        const bool yuv_file = FLAGS_source.size() >= 4 && FLAGS_source.compare(FLAGS_source.size() - 4, 4, ".yuv") == 0;
+        if (FLAGS_yuv || yuv_file) {
+            cli_log() << "ERROR: --encode_yuv converts pictures and --rgb frames to video frames; --yuv and .yuv sources are video already: write them with --saving_yuv=<file>\n";
+            return false;
+        }
+        if (!pick("encode_format", FLAGS_encode_format, { { "i420", HP_YUV_I420 }, { "nv12", HP_YUV_NV12 }, { "p010", HP_YUV_P010 }, { "i010", HP_YUV_I010 },
+                                                            { "nv16", HP_YUV_NV16 }, { "i422", HP_YUV_I422 }, { "yuy2", HP_YUV_YUY2 }, { "uyvy", HP_YUV_UYVY }, { "i444", HP_YUV_I444 } }, g_encode_format)
+            || !pick("encode_matrix", FLAGS_encode_matrix, { { "bt601", HP_YUV_BT601 }, { "bt709", HP_YUV_BT709 }, { "bt2020", HP_YUV_BT2020 } }, g_encode_matrix)
+            || !pick("encode_range", FLAGS_encode_range, { { "limited", HP_YUV_LIMITED }, { "full", HP_YUV_FULL } }, g_encode_range))
+            return false;
+        if (FLAGS_encode_align < 1 || FLAGS_encode_align > 256) {
+            cli_log() << "ERROR: --encode_align=" << FLAGS_encode_align << " is outside [1, 256]\n";
+            return false;
+        }
+    } else if (FLAGS_encode_format != "nv12" || FLAGS_encode_matrix != "bt709" || FLAGS_encode_range != "limited" || FLAGS_encode_align != 2) {
+        cli_log() << "ERROR: --encode_format / --encode_matrix / --encode_range / --encode_align describe --encode_yuv=<file>\n";
         return false;
     }
     // --redact and its companions: enumerated names, an even cell in [2, 128], a margin in (0, 8]; the companions describe --redact
@@ -657,7 +689,7 @@ int main(int argc, char** argv)
         return 1;
     }
     // --redact rewrites the frames --saving_yuv writes: settled from the flags alone as well
-    if (g_redact && FLAGS_saving_yuv.empty()) {
+    if (g_redact && FLAGS_saving_yuv.empty() && FLAGS_encode_yuv.empty()) {
         cli_log() << "ERROR: --redact=" << FLAGS_redact << " redacts the frames of --saving_yuv=<file>; the PPM pictures are not redacted\n";
         return 1;
     }
@@ -753,7 +785,19 @@ int main(int argc, char** argv)
         cli_log() << "WARNING: the stream runtime carries cv::Mat frames (stream.hpp); YUV frames go through --runtime=" kOPERATOR "\n";
         FLAGS_runtime = kOPERATOR;
     }
-    std::ofstream yuv_out, humans_out;
+    if (!FLAGS_encode_yuv.empty() && FLAGS_runtime == kSTREAM) {
+        cli_log() << "WARNING: the stream runtime returns humans, not frames; --encode_yuv goes through --runtime=" kOPERATOR "\n";
+        FLAGS_runtime = kOPERATOR;
+    }
+    std::ofstream yuv_out, humans_out, encode_out, encode_humans_out;
+    if (!FLAGS_encode_yuv.empty()) {
+        encode_out.open(FLAGS_encode_yuv, std::ios::binary | std::ios::trunc);
+        encode_humans_out.open(FLAGS_encode_yuv + ".humans", std::ios::binary | std::ios::trunc);
+        if (!encode_out || !encode_humans_out) {
+            cli_log() << "ERROR: cannot write " << FLAGS_encode_yuv << "\n";
+            return 1;
+        }
+    }
     if (!FLAGS_saving_yuv.empty()) {
         yuv_out.open(FLAGS_saving_yuv, std::ios::binary | std::ios::trunc);
         humans_out.open(FLAGS_saving_yuv + ".humans", std::ios::binary | std::ios::trunc);
@@ -900,6 +944,43 @@ int main(int argc, char** argv)
                     humans_out.write((const char*)&count, sizeof(count));
                     humans_out.write((const char*)records.data(), records.size() * sizeof(hp_human));
                 }
+                if (encode_out.is_open()) { // the frame in its own layout -> device -> the encoder's frame, annotated where it lies, appended to the file
+                    const cv::Mat& m = batch[k];
+                    const hp::rgb_frame host = g_rgb_format >= 0 ? rgb_batch[k] : hp::rgb_frame(HP_RGB_BGR24, hp::detail::mat_data(m), m.cols, m.rows, m.cols * 3);
+                    const cv::Size size = hp::padded_size(g_encode_format, cv::Size(host.width, host.height), FLAGS_encode_align);
+                    std::vector<uint8_t> encoded(hp_yuv_packed_bytes(g_encode_format, size.width, size.height));
+                    hp::detail::dev_ptr src((size_t)host.stride * host.height), dst(encoded.size());
+                    if (!src.p || !dst.p || hp_memcpy_h2d(src.p, host.data, (size_t)host.stride * host.height) != HP_OK) {
+                        cli_log() << "ERROR: " << hp_last_error() << "\n";
+                        return 2;
+                    }
+                    hp::yuv_frame surface = hp::yuv_frame::packed(g_encode_format, dst.p, size.width, size.height, g_encode_matrix, g_encode_range, true);
+                    hp::to_yuv(hp::rgb_frame(host.format, src.p, host.width, host.height, host.stride, true), surface);
+                    std::vector<hp::human_t> drawn = poses; // upright, normalised to the source frame: what <file>.humans records
+                    if (FLAGS_keep_ratio && !g_tiled)
+                        for (auto& pose : drawn)
+                            hp::resume_ratio(pose, hp::oriented_size(m.size(), g_orient), engine.input_size());
+                    // the surface is the stored frame with padding on its right and below: stored coordinates, rescaled to the padded size
+                    std::vector<hp::human_t> on_surface = drawn;
+                    hp::to_stored(on_surface, g_orient);
+                    const float fx = (float)host.width / (float)size.width, fy = (float)host.height / (float)size.height;
+                    for (auto& pose : on_surface)
+                        for (auto& part : pose.parts)
+                            part.x *= fx, part.y *= fy;
+                    if (g_redact)
+                        hp::redact_humans(surface, on_surface, g_redaction);
+                    if (!FLAGS_redact_only)
+                        hp::draw_humans(surface, on_surface, FLAGS_alpha > 0 ? (float)FLAGS_alpha : 1.f);
+                    if (hp_device_synchronize() != HP_OK || hp_memcpy_d2h(encoded.data(), dst.p, encoded.size()) != HP_OK) {
+                        cli_log() << "ERROR: " << hp_last_error() << "\n";
+                        return 2;
+                    }
+                    encode_out.write((const char*)encoded.data(), encoded.size());
+                    const auto records = hp::detail::to_c_humans(drawn);
+                    const int32_t count = (int32_t)records.size();
+                    encode_humans_out.write((const char*)&count, sizeof(count));
+                    encode_humans_out.write((const char*)records.data(), records.size() * sizeof(hp_human));
+                }
                 render(batch[k], poses, FLAGS_keep_ratio && !g_tiled);
             }
         }
@@ -934,6 +1015,14 @@ int main(int argc, char** argv)
             return 3;
         }
         std::cout << images.size() << " annotated " << FLAGS_yuv_format_written() << " frames appended to " << FLAGS_saving_yuv << "\n";
+    }
+    if (encode_out.is_open()) {
+        encode_out.flush(), encode_humans_out.flush();
+        if (!encode_out || !encode_humans_out) {
+            cli_log() << "ERROR: writing " << FLAGS_encode_yuv << " failed\n";
+            return 3;
+        }
+        std::cout << images.size() << " " << FLAGS_encode_format << " frames (" << FLAGS_encode_matrix << ", " << FLAGS_encode_range << ") appended to " << FLAGS_encode_yuv << "\n";
     }
     return n_written == images.size() ? 0 : 3;
 }

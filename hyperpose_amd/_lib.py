@@ -168,6 +168,7 @@ SYMBOLS = [
     "hp_scale_stage_u8c3", "hp_scale_stage_u8c3_host", "hp_scale_tables", "hp_scale_merge", "hp_scale_merge_host", "hp_engine_set_scale_ensemble",
     "hp_engine_set_scale_ensemble_coco", "hp_engine_scale_ensemble", "hp_pipeline_set_scale_ensemble",
     "hp_resize_rgb", "hp_resize_rois_rgb", "hp_rgb_pixel_bytes", "hp_rgb_packed_bytes", "hp_rgb_to_bgr_host", "hp_pipeline_submit_rgb_images",
+    "hp_rgb_to_yuv", "hp_rgb_to_yuv_host", "hp_yuv_forward_coefficients", "hp_yuv_padded_size",
 ]
 
 

@@ -49,6 +49,8 @@ UNITS = [
     ("redact.hip", ["-ffp-contract=off"]),
     # the index plane is fp32 with no fused operations (csrc/mapview.hpp) and the reduce kernel runs in the engines' streams; the painter is integer
     ("mapview.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # the encoder hand-off is integer after its host-side coefficients (csrc/to_yuv.hpp); the flags of the other integer front-end units
+    ("to_yuv.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # the flip ensemble's merge is fp32 vector code in the engines' streams, beside fp16 MFMA kernels, and bit-equal to its host twin
     ("flip_ensemble.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # the scale ensemble's merge and its fp32 bicubic tables: the flip unit's reasons; its stage is resize_device.hpp's arithmetic once more

@@ -407,6 +407,52 @@ def resize_rgb_host(frame, dw: int, dh: int, fmt: str = "bgra", orientation: int
     return dst.to_numpy(np.uint8, (dh, dw, 3))
 
 
+# ---- encoder hand-off: RGB / grey frames to every YUV layout (hp_rgb_to_yuv; the rule: csrc/to_yuv.hpp, DESIGN.md 1.1 "Encoder hand-off") -----------
+
+def yuv_forward_coefficients(matrix: str = "bt601", range: str = "limited", depth: int = 8):
+    """``hp_yuv_forward_coefficients``: [y_off, c_off, YR, YG, YB, UR, UG, UB, VR, VG, VB], multiples of 2^-18."""
+    out = (C.c_int32 * 11)()
+    check(lib().hp_yuv_forward_coefficients(YUV_MATRICES[matrix], YUV_RANGES[range], int(depth), out))
+    return list(out)
+
+
+def yuv_padded_size(fmt: str, w: int, h: int, align: int = 1):
+    """``hp_yuv_padded_size``: the smallest (w, h) at least as large whose sides are multiples of ``align`` and of what the layout needs."""
+    pw, ph = C.c_int(), C.c_int()
+    check(lib().hp_yuv_padded_size(YUV_LAYOUTS[fmt][0], int(w), int(h), int(align), C.byref(pw), C.byref(ph)))
+    return pw.value, ph.value
+
+
+def rgb_to_yuv(im: RgbImage, dst: YuvImage, stream=None) -> None:
+    """``hp_rgb_to_yuv``: a device frame of any ``hp_rgb_image`` layout written into the device planes of ``dst`` in its layout, matrix, range and
+    bit depth; ``dst`` may be larger than ``im`` (edge replication).  Only enqueues; the annotators take ``dst`` as they take a decoder's surface."""
+    check(lib().hp_rgb_to_yuv(C.byref(im), C.byref(dst), C.c_void_p(stream) if stream else None))
+
+
+def rgb_to_yuv_host(frame, fmt_rgb: str = "bgra", yuv_fmt: str = "nv12", matrix: str = "bt709", range: str = "limited", pad_to=None, pitch=0,
+                    fill: int = 0xA5):
+    """``hp_rgb_to_yuv_host``: a host frame (array or ``RgbImage``) as the list of 2-D plane arrays of a ``yuv_fmt`` frame - the definition of what
+    ``rgb_to_yuv`` computes.  ``pad_to``: None (the smallest size the layout holds), an alignment (``yuv_padded_size``) or the output's (w, h).
+    With ``pitch`` (one number or one per plane) every plane is a view into rows that many bytes longer, pre-filled with ``fill`` (``.base`` shows
+    that the padding was not written)."""
+    im, keep = (frame, None) if isinstance(frame, RgbImage) else rgb_host_image(frame, fmt_rgb)  # (keep: the array the description points into)
+    w, h = pad_to if isinstance(pad_to, (tuple, list)) else yuv_padded_size(yuv_fmt, im.width, im.height, pad_to or 1)
+    shapes = yuv_plane_shapes(yuv_fmt, w, h)
+    if not shapes or shapes[0][0] == 0:
+        raise ValueError(f"rgb_to_yuv_host: a {yuv_fmt} frame cannot be {w} x {h}")
+    dt = np.dtype(np.uint16 if YUV_LAYOUTS[yuv_fmt][2] == 2 else np.uint8)
+    pitches = list(pitch) if isinstance(pitch, (list, tuple)) else [pitch] * len(shapes)
+    planes = []
+    for (rows, cols), extra in zip(shapes, pitches):
+        stride = cols * dt.itemsize + int(extra)
+        buf = np.full((rows, stride), fill, np.uint8)
+        planes.append(np.ndarray((rows, cols), dt, buffer=buf, strides=(stride, dt.itemsize)))
+    dst = _host_image(planes, yuv_fmt, matrix, range, written=True)
+    dst.width, dst.height = int(w), int(h)
+    check(lib().hp_rgb_to_yuv_host(C.byref(im), C.byref(dst)))
+    return planes
+
+
 # ---- flip ensemble: the frame flip, the map merge and the COCO tables (include/hp_hip.h; the definition: csrc/flip_ensemble.hpp) ---------------
 
 def flip_tables_coco(conf_channels: int = 19):

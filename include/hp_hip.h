@@ -349,6 +349,35 @@ size_t hp_rgb_packed_bytes(int format, int width, int height);
 /* the whole HOST frame as 8-bit BGR, rows bgr_stride bytes apart (>= width * 3; padding bytes are not written): the definition above */
 int hp_rgb_to_bgr_host(const hp_rgb_image* src, uint8_t* bgr, int bgr_stride);
 
+/* ---- encoder hand-off: a packed RGB or grey frame as the frame a video encoder takes - any hp_yuv_image layout, in the matrix, range and bit depth the
+ * stream is tagged with, padded to the size the encoder needs - converted on the device (hyperpose_amd/csrc/to_yuv.hip; the rule is stated once in
+ * to_yuv.hpp and DESIGN.md 1.1 "Encoder hand-off").  The forward counterpart of hp_resize_yuv; the annotators below (hp_overlay_*, hp_redact_*,
+ * hp_mapview_*) work on the result as on a decoder's surface: capture -> hp_rgb_to_yuv -> redact / maps / skeletons -> encoder, all on the device.
+ *   coefficients  hp_yuv_forward_coefficients: kr, kb of the matrix, kg = 1 - kr - kb, d = 8 or 10, S = 18, float64;
+ *                 LIMITED ys = 219 2^(d-8) / 255, cs = 224 2^(d-8) / 255, y_off = 16 2^(d-8), c_off = 128 2^(d-8); FULL ys = cs = (2^d - 1) / 255,
+ *                 y_off = 0, c_off = 2^(d-1);  YR = rint(kr ys 2^S), YB = rint(kb ys 2^S), YG = rint(ys 2^S) - YR - YB;
+ *                 UB = rint(0.5 cs 2^S), UR = -rint(kr / (2 (1 - kb)) cs 2^S), UG = -UB - UR;  VR = rint(0.5 cs 2^S),
+ *                 VB = -rint(kb / (2 (1 - kr)) cs 2^S), VG = -VR - VB;  out = { y_off, c_off, YR, YG, YB, UR, UG, UB, VR, VG, VB }
+ *   pixel         R, G, B as hp_rgb_to_bgr_host defines them;  Y = clip((YR R + YG G + YB B + (y_off << 18) + (1 << 17)) >> 18)
+ *   chroma        one sample covers n = 1 (4:4:4), 2 (4:2:2) or 4 (4:2:0) luma pixels, Rs, Gs, Bs their sums (the box mean; no co-sited filter):
+ *                 U = clip((UR Rs + UG Gs + UB Bs + n ((c_off << 18) + (1 << 17))) >> (18 + log2 n)), V likewise; clip to [0, 2^d - 1]; all int32.
+ *                 A grey pixel gives exactly c_off; against hp_yuv_colours' float rule a sample differs by at most 1 code value
+ *   padding       dst may be larger than src: output pixel (x, y) takes source pixel (min(x, sw - 1), min(y, sh - 1)) (edge replication), for odd
+ *                 captures going to 4:2:0 and for an encoder's alignment (1080 -> 1088); hp_yuv_padded_size gives such a size
+ *   samples       where hp_yuv_image's layouts put them; 16-bit layouts store value << shift (P010: 6, I010: 0), the other bits zero
+ * No byte of dst outside the samples of its width x height is written (row padding included), no byte of src outside width * pixel bytes of a row is
+ * read.  src and dst must not overlap: that is the caller's responsibility and is not checked.  HP_ERR_INVALID, with a message that names the layout
+ * and the quantity, nothing launched and dst untouched: whatever hp_resize_yuv rejects for an image (dst: format, matrix, range, a size the layout
+ * cannot hold, a null plane, a short stride, odd planes / strides of the 16-bit layouts on the device), whatever the hp_rgb_image rules reject (src),
+ * dst narrower or lower than src, dst wider or higher than 8192.  No resize, no orientation, no HDR transfer, no alpha. */
+int hp_rgb_to_yuv(const hp_rgb_image* src /* data in DEVICE memory */, const hp_yuv_image* dst /* planes in DEVICE memory, WRITTEN */, void* stream);
+/* the same bytes on frames in HOST memory (plain C++, written bytewise: the definition of the device call; no device needed) */
+int hp_rgb_to_yuv_host(const hp_rgb_image* src, const hp_yuv_image* dst);
+/* host only: the integer table above for a matrix / range / depth (8 or 10) */
+int hp_yuv_forward_coefficients(int matrix, int range, int depth, int32_t out[11]);
+/* host only: the smallest size >= width x height (both 1 .. 8192) whose sides are multiples of `align` (1 .. 256) and of what the layout needs */
+int hp_yuv_padded_size(int format, int width, int height, int align, int* padded_width, int* padded_height);
+
 /* ---- writing back: the skeletons of a frame's humans painted into a DEVICE-resident frame, 8-bit BGR or any hp_yuv_image layout in the frame's
  * own colour space and bit depth (hyperpose_amd/csrc/overlay.hip) - the last stage of the reference's stream, draw_human + writer
  * (src/stream.cpp:114-147), for frames that never leave the device.  The picture is defined by exact integer rules, stated once in

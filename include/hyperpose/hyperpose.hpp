@@ -6,6 +6,7 @@
 #include "operator/parser/proposal_network.hpp"
 #include "stream/stream.hpp"
 #include "utility/data.hpp"
+#include "utility/encode.hpp"
 #include "utility/human.hpp"
 #include "utility/map_view.hpp"
 #include "utility/overlay.hpp"
